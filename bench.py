@@ -6,19 +6,23 @@ Workload (BASELINE.json configs[1]): 65 536 vectorised MountainCar envs per GPU,
 episodes (all envs start at MountainCar::default(); diversity comes from the per-env Philox streams).
 A "step" = one pass of the hot path (transition -> handle -> sample) over the whole batch of envs.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 without a launcher (WORLD_SIZE unset): bench.py starts the N ranks itself (torch.distributed.run, one rank per
 GPU, rendezvous on 127.0.0.1).  Under a launcher it is one of the ranks.  Envs are sharded by global id with NO
 data-path collective (independent learners) => weak scaling.
 
-Timed regions (warm-up, >= 2 000 batch-steps, median of 5): a K-step call is short (K = 20 is ~15 us of
-arithmetic), so the call is repeated R times back to back between ONE pair of barrier + synchronize (R is chosen so that a
-region lasts >= ~1 s; config.repeats); the region is measured FIVE times and `value` / `ms_per_step` are the MEDIAN region
-(all ranks' env-steps / max-over-ranks region time); `regions_s` and `spread` carry all five.  rsrl_hip_train is asynchronous
-and, on its own stream, coalesces calls that arrive while the stream is busy (same results bit for bit, include/rsrl_hip.h):
-the R x K batch-steps run as launches of up to 4096 steps -- config.steps_per_launch and roofline.launches report what was
-actually launched, and `value_no_coalesce` is the same K-step driver call with one launch per call (RSRL_NO_COALESCE=1).
+Timed steps: after W warm-up batch-steps, exactly K batch-steps are timed.  They run as up to --regions (default 5)
+back-to-back regions of equal length (at least 4096 batch-steps each, so a short run is one region), each ONE train call
+between a barrier + synchronize pair; `ms_per_step` = the regions' total time (max over ranks) / K and `value` = all ranks'
+env-steps / that time; `regions_s` and `spread` carry the regions.  rsrl_hip_train runs a call as launches of up to 4096
+steps (include/rsrl_hip.h) -- config.steps_per_launch and roofline.launches report what was actually launched, and
+`value_no_coalesce` is a 20-step driver call with one launch per call (RSRL_NO_COALESCE=1).
+
+--dump-outputs DIR: after the timed steps, what they left for a caller of the hot path -- every learner's weights, env
+states, pending actions and episode step counts -- goes to DIR/<name>.npy (float32; learner_index.npy, float64, names the
+learners).  Above 64 MB in all a fixed, seeded sample of the learners is written.  The inputs depend only on the arguments
+(seed 0, W + K batch-steps from reset), so two builds can be compared array for array.
 
 roofline.frac is a fraction of a PUBLISHED peak (MI355X_MICROARCH.md): the fused kernel keeps W in the register file, so its
 bound is the fp32 vector unit -- frac = flop per env-step (profiles/isa_mix.json, from rocprofv3 instruction-class counters) x
@@ -45,8 +49,10 @@ N_SIMD, CLOCK_HZ = 1024, 2.4e9      # 256 CUs x 4 SIMDs, max clock
 # HBM bytes one launch of the fused kernel must move per learner, whatever its depth: W in + W out (2 x 432), state in/out
 # (2 x 8), action in/out (2 x 4), episode counter in/out (2 x 4), carried Q in/out (2 x 12)
 FUSED_BYTES_PER_LEARNER_LAUNCH = 2 * (432 + 8 + 4 + 4 + 12)
-TARGET_REGION_S = 1.0               # per timed region; the region is measured N_REGIONS times, `value` is the median
-N_REGIONS = 5
+N_REGIONS = 5                       # the timed steps are measured as up to this many regions (--regions)
+REGION_MIN_STEPS = 4096             # ... of at least one fuse depth each (the library's launch depth of the fused loop)
+DRIVER_CALL_STEPS = 20              # a driver loop's train() call (value_no_coalesce)
+DUMP_LIMIT_BYTES = 64 * 10 ** 6     # --dump-outputs: at most this much in all; above it a seeded sample of the learners
 SPEC_CYCLES = {"pk": 4.0, "other": 2.0}   # MI355X_MICROARCH.md: v_fma_f32 wave64 = 2 cycles on a SIMD-32; a packed fp32 op = two of them
 
 
@@ -216,6 +222,27 @@ def greedy_rollout_check(ctx, sample=256, limit=1000):
             "note": "CPU = f64 oracle (oracle/rsrl_oracle.c orc_run_rollout_greedy_margin) from the same weights; a learner can differ only "
                     "where an argmax margin is below fp32 resolution (max_min_margin_of_differing says how small the margin of the "
                     "differing learners was)"}
+
+
+def dump_outputs(ctx, out_dir, suffix="", limit_bytes=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what the timed steps left for a caller of the hot path -> out_dir/<name><suffix>.npy.  weights (M, F, A), states (D, M),
+    actions (M,), episode_steps (M,) in float32 (exact: small integers) and learner_index (M,) in float64; every learner while that fits
+    in limit_bytes, else a fixed sample (seed 0) of them in ascending order."""
+    import numpy as np
+    n = ctx.N
+    per_learner = 4 * (ctx.F * ctx.n_out + ctx.D + 2) + 8
+    m = min(n, limit_bytes // per_learner)
+    idx = np.arange(n) if m == n else np.sort(np.random.default_rng(0).choice(n, size=m, replace=False))
+    arrays = {"weights": np.stack([ctx.get_weights(int(i)) for i in idx]).astype(np.float32),
+              "states": ctx.states[:, idx].astype(np.float32),
+              "actions": ctx.actions[idx].astype(np.float32),
+              "episode_steps": ctx.episode_steps[idx].astype(np.float32),
+              "learner_index": idx.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+    return {"dir": out_dir, "learners": int(m), "of": int(n), "files": sorted(name + suffix + ".npy" for name in arrays),
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
 
 
 def parity_sample(m=2048):
@@ -622,7 +649,7 @@ def compact_line(full, detail_path="bench_detail.json"):
     for k in ("value", "ms_per_step"):
         line[k] = _num(line[k], 7)
     cfg = full.get("config") or {}
-    line["config"] = {k: (_num(v) if not isinstance(v, str) else v) for k, v in cfg.items() if k in ("workload", "envs_per_gpu", "steps_per_launch", "repeats", "ranks", "parallelism")}
+    line["config"] = {k: (_num(v) if not isinstance(v, str) else v) for k, v in cfg.items() if k in ("workload", "envs_per_gpu", "steps_per_launch", "regions", "ranks", "parallelism")}
     rl = full.get("roofline") or {}
     crl = {k: _num(rl.get(k)) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "useful_frac", "avg_launch_ms", "launches", "traffic", "profile_digest_matches")
            if k in rl}
@@ -714,11 +741,12 @@ def spawn_ranks(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2560)
-    ap.add_argument("--warmup", type=int, default=256)
-    ap.add_argument("--repeats", type=int, default=0, help="back-to-back repetitions of the K-step call inside one timed region (0 = auto: >= --region-seconds)")
-    ap.add_argument("--regions", type=int, default=N_REGIONS, help="how many times the timed region is measured (value = the median)")
-    ap.add_argument("--region-seconds", type=float, default=TARGET_REGION_S)
+    ap.add_argument("--steps", type=int, default=1 << 20, help="timed batch-steps in all (a batch-step = one pass of the hot path over every env)")
+    ap.add_argument("--warmup", type=int, default=256, help="untimed batch-steps before them")
+    ap.add_argument("--regions", type=int, default=N_REGIONS,
+                    help=f"the timed steps run as up to this many back-to-back regions of at least {REGION_MIN_STEPS} steps each (spread)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps left (weights, states, actions, episode step counts) to DIR/<name>.npy")
     ap.add_argument("--no-nocoalesce-leg", action="store_true", help="skip the one-launch-per-call measurement")
     ap.add_argument("--no-config-legs", action="store_true", help="skip the secondary C3 / C5 measurements")
     ap.add_argument("--steps-per-launch", type=int, default=0, help="fuse depth (0 = library default)")
@@ -730,6 +758,8 @@ def main():
     ap.add_argument("--detail", default=None, help="where the full result goes (default: bench_detail.json next to bench.py and under gpurun_out/)")
     ap.add_argument("--allow-oversubscribe", action="store_true", help="let several ranks share a device (test boxes only)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.regions < 1:
+        ap.error("--steps and --regions must be >= 1, --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -762,66 +792,62 @@ def main():
     if args.warmup > 0:
         ctx.train(args.warmup, want_stats=False)
     ctx.sync()
-    # R: how many K-step calls make a >= 1 s region (one untimed calibration burst; the same R on every rank)
-    repeats = args.repeats
-    if repeats <= 0:
-        burst = 64                                   # back-to-back, as in the timed region (the library coalesces short calls)
-        t0 = time.perf_counter()
-        for _ in range(burst):
-            ctx.train(args.steps, want_stats=False)
-        ctx.sync()
-        t_call = cp.max_over_ranks(time.perf_counter() - t0) / burst
-        repeats = int(min(4000000, max(3, -(-1.15 * args.region_seconds // max(t_call, 1e-7)))))    # (the burst is a little slower per call than the steady state)
 
-    def timed_region(n_calls):
-        """n_calls back-to-back K-step calls between one barrier + synchronize pair -> (max over ranks, this rank's own) seconds"""
+    def timed_region(n_calls, call_steps):
+        """n_calls back-to-back train(call_steps) calls between one barrier + synchronize pair -> (max over ranks, this rank's own) seconds"""
         cp.barrier()
         ctx.sync()
         t0 = time.perf_counter()
         for _ in range(n_calls):
-            ctx.train(args.steps, want_stats=False)
+            ctx.train(call_steps, want_stats=False)
         ctx.sync()
         own = time.perf_counter() - t0
         worst = cp.max_over_ranks(own)
         cp.barrier()
         return worst, own
 
+    # the K timed batch-steps: n_reg regions of (nearly) equal length, one train call each
+    n_reg = max(1, min(args.regions, args.steps // REGION_MIN_STEPS))
+    region_steps = [args.steps // n_reg + (1 if j < args.steps % n_reg else 0) for j in range(n_reg)]
     ctx.timing_enable(True)
-    regions = [timed_region(repeats) for _ in range(args.regions)]
+    regions = [timed_region(1, k) for k in region_steps]
     kernel_ms, launches, kname = ctx.timing_read()
     ctx.timing_enable(False)
-    order = sorted(range(len(regions)), key=lambda j: regions[j][0])
-    dt = regions[order[len(order) // 2]][0]                    # the MEDIAN region
-    own_rates = cp.all_gather_bytes(args.envs * args.steps * repeats / regions[order[len(order) // 2]][1])
-    # per rank, so that the first real multi-GPU run localises a slow rank: its own median region, its kernel time per batch-step by HIP events
+    dt = sum(r[0] for r in regions)                            # all K timed steps (max over ranks, region by region)
+    own_dt = sum(r[1] for r in regions)
+    own_rates = cp.all_gather_bytes(args.envs * args.steps / own_dt)
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(ctx, args.dump_outputs, "" if world == 1 else f"_rank{rank}", DUMP_LIMIT_BYTES // world)
+    # per rank, so that the first real multi-GPU run localises a slow rank: its own timed steps, its kernel time per batch-step by HIP events
     # on its own stream, its device and which physical device that is
     try:
         dev_id = "%x" % rsrl_amd.device_identity(device)
     except Exception:      # noqa: BLE001
         dev_id = None
     per_rank = cp.all_gather_bytes({"rank": rank, "local_rank": local_rank, "device": device, "device_identity": dev_id,
-                                    "kernel_us_per_batch_step": kernel_ms * 1e3 / max(1, args.steps * repeats * len(regions)),
+                                    "kernel_us_per_batch_step": kernel_ms * 1e3 / args.steps,
                                     "kernel_launches": launches, "regions_s": [r[1] for r in regions],
-                                    "env_steps_per_s": args.envs * args.steps * repeats / regions[order[len(order) // 2]][1]})
-    # the same K-step driver call WITHOUT launch coalescing (one launch per call): what a single train(K) costs
+                                    "env_steps_per_s": args.envs * args.steps / own_dt})
+    # a driver loop's short call WITHOUT launch coalescing (one launch per call): what a single train(20) costs
     no_coalesce = None
     if not args.no_nocoalesce_leg and args.steps_per_launch != 1:
         os.environ["RSRL_NO_COALESCE"] = "1"
         try:
             t0 = time.perf_counter()
             for _ in range(64):
-                ctx.train(args.steps, want_stats=False)
+                ctx.train(DRIVER_CALL_STEPS, want_stats=False)
             ctx.sync()
             t_call = cp.max_over_ranks(time.perf_counter() - t0) / 64
             n_nc = int(min(400000, max(3, -(-0.3 // max(t_call, 1e-7)))))
             ctx.timing_enable(True)
-            dt_nc = timed_region(n_nc)[0]
+            dt_nc = timed_region(n_nc, DRIVER_CALL_STEPS)[0]
             ms_nc, l_nc, _ = ctx.timing_read()
             ctx.timing_enable(False)
-            no_coalesce = {"value": args.envs * world * args.steps * n_nc / dt_nc, "unit": "env-steps/s", "calls": n_nc, "region_s": dt_nc,
+            no_coalesce = {"value": args.envs * world * DRIVER_CALL_STEPS * n_nc / dt_nc, "unit": "env-steps/s", "calls": n_nc, "region_s": dt_nc,
                            "launches": l_nc, "avg_launch_ms": ms_nc / max(1, l_nc),
-                           "what": f"the same {args.steps}-step driver call, one launch per call (RSRL_NO_COALESCE=1): every call loads and stores every "
-                                   "learner's weights around its steps; `value` is the coalesced figure"}
+                           "what": f"a {DRIVER_CALL_STEPS}-step driver call, one launch per call (RSRL_NO_COALESCE=1): every call loads and stores every "
+                                   "learner's weights around its steps; `value` is the timed steps' figure"}
         finally:
             os.environ.pop("RSRL_NO_COALESCE", None)
     rollout = guarded(lambda: greedy_rollout_check(ctx), 120) if rank == 0 else None
@@ -900,11 +926,12 @@ def main():
     if world > 1 and not hung:
         guarded(cp.barrier, 120)
     if rank == 0:
-        total_steps = args.steps * repeats
+        total_steps = args.steps
         total_env_steps = total_steps * args.envs * world
         value = total_env_steps / dt
         avg_launch_s = kernel_ms * 1e-3 / max(1, launches)
-        steps_per_launch = total_steps * len(regions) / max(1, launches)
+        steps_per_launch = total_steps / max(1, launches)
+        per_step_s = [r[0] / k for r, k in zip(regions, region_steps)]
         per_gpu_kernel_rate = args.envs * steps_per_launch / avg_launch_s if avg_launch_s > 0 else 0.0
         n_gpus = min(world, ndev)
         fused = kname == "k_train_reg"
@@ -920,15 +947,16 @@ def main():
             "value": value, "unit": "env-steps/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": dt * 1e3 / total_steps, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "timed_region_s": dt, "regions_s": [r[0] for r in regions],
-            "spread": (max(r[0] for r in regions) - min(r[0] for r in regions)) / dt,
-            "timing": f"median of {len(regions)} regions, each {repeats} back-to-back calls of {args.steps} batch-steps between one barrier + synchronize pair",
+            "timed_region_s": dt, "regions_s": [r[0] for r in regions], "region_steps": region_steps,
+            "spread": (max(per_step_s) - min(per_step_s)) / (dt / total_steps),
+            "timing": f"{total_steps} timed batch-steps as {len(regions)} region(s), each one train call between a barrier + synchronize pair; "
+                      "ms_per_step = their total time / the steps",
             "ranks_seen": world, "per_rank_env_steps_per_s": [float(x) for x in own_rates], "per_rank": per_rank,
             "config": {"workload": f"{args.envs} vectorised MountainCar envs per GPU, QLearning + Fourier(5), "
                                    "eps-greedy(0.1), gamma 0.9, SGD(0.001), per-env W, 1xMI355X per rank "
                                    "(BASELINE.json configs[1])",
-                       "envs_per_gpu": args.envs, "steps_per_launch": steps_per_launch, "repeats": repeats,
-                       "timed": f"{repeats} back-to-back calls of {args.steps} batch-steps per region, {len(regions)} regions",
+                       "envs_per_gpu": args.envs, "steps_per_launch": steps_per_launch, "regions": len(regions),
+                       "timed": f"{total_steps} batch-steps in {len(regions)} region(s) of {min(region_steps)}..{max(region_steps)} steps",
                        "ranks": world,
                        "parallelism": f"env-sharded x{world}, no data-path collective"},
         }
@@ -955,6 +983,8 @@ def main():
             ach = BYTES_PER_ENV_STEP * args.envs * steps_per_launch / avg_launch_s if avg_launch_s > 0 else 0.0
             out["roofline"] = dict({"bound": "hbm", "achieved": ach / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": ach / HBM_PEAK,
                                     "algorithmic_bytes_per_env_step": BYTES_PER_ENV_STEP}, **common)
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if rollout is not None:
             out["greedy_rollout"] = rollout
         if parity is not None:

@@ -19,7 +19,7 @@ if [ "${PROFILE_LEGS_ONLY:-0}" = "1" ]; then SKIP_BENCH=1; else SKIP_BENCH=0; fi
 python $R/bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_driver -o k -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-config-legs --no-shared-leg --no-streaming-leg > $O/bench_driver_profiled.json 2> $O/kt_driver.log
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_1024 -o k -- python $R/bench.py --gpus 1 --steps 1024 --warmup 5 --no-cpu-baseline --no-config-legs --no-shared-leg --no-streaming-leg --no-nocoalesce-leg > $O/bench_1024_profiled.json 2> $O/kt_1024.log
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_legs -o k -- python $R/bench.py --gpus 1 --steps 1024 --warmup 5 --no-cpu-baseline --regions 1 --region-seconds 0.2 --no-nocoalesce-leg > $O/bench_legs_profiled.json 2> $O/kt_legs.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_legs -o k -- python $R/bench.py --gpus 1 --steps 300000 --warmup 5 --no-cpu-baseline --regions 1 --no-nocoalesce-leg > $O/bench_legs_profiled.json 2> $O/kt_legs.log
 }
 G1="FETCH_SIZE"
 G2="WRITE_SIZE"

@@ -94,7 +94,7 @@ def _run(tmp_path, G, mode, kind, ragged=False):
     stub = _build.build_rccl_stub()
     script = tmp_path / "rccl_stub_run.py"
     script.write_text(SCRIPT)
-    env = dict(os.environ, RSRL_ROOT=ROOT, RCCL_STUB=stub, LD_PRELOAD=stub, G=str(G), MODE=mode, KIND=kind, RSRL_NO_GRAPH="1",
+    env = dict(os.environ, RSRL_ROOT=ROOT, RCCL_STUB=stub, LD_PRELOAD=":".join(filter(None, (stub, os.environ.get("LD_PRELOAD")))), G=str(G), MODE=mode, KIND=kind, RSRL_NO_GRAPH="1",
                GPU_MAX_HW_QUEUES=str(2 * G))
     if ragged:
         env["RAGGED"] = "1"

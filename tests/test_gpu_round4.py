@@ -367,7 +367,7 @@ def test_bench_two_ranks_on_one_gpu_has_no_error_leg(tmp_path, ranks):
     # ranks = 8: the world size of a node (the largest ever exercised was 4 in-process / 2 processes): eight processes share the one
     # device, the peer group of eight decides collectively which kernels fit it, hop 2 fans out to eight hipIpc-mapped receive buffers
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--allow-oversubscribe", "--envs", "4096", "--steps", "20", "--warmup", "5",
-                        "--region-seconds", "0.2", "--regions", "3", "--detail", str(tmp_path / "detail.json")], env=env, capture_output=True, text=True,
+                        "--regions", "3", "--detail", str(tmp_path / "detail.json")], env=env, capture_output=True, text=True,
                        timeout=900, cwd=str(tmp_path))
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert p.returncode == 0 and lines, (p.stdout[-1500:], p.stderr[-3000:])
