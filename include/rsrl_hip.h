@@ -263,7 +263,7 @@ int rsrl_hip_set_q_carry(rsrl_hip_ctx* ctx, const float* q /*[A][N]*/);
  *   calls above and launches them as one kernel when they arrive in this order on the same arrays; any other call launches the accepted ones
  *   first, one kernel each -- same results, same order; as with rsrl_hip_train's coalescing, acceptance is not completion: rsrl_hip_sync (or
  *   any call that returns data to the host) completes them.  On a caller-supplied stream every call enqueues its own kernel before it returns.
- *   RSRL_NO_TRAIT_DEFER=1 / RSRL_NO_TRAIT_FAST=1 in the environment switch the deferral / the fast kernels off (A/B runs).  (ABI 9)
+ *   RSRL_NO_TRAIT_DEFER=1 in the environment when the ctx is created switches the deferral off (A/B runs).  (ABI 9)
  *
  * Domain::transition                                rsrl_domains/src/lib.rs:436-446
  * Steps every env of the ctx with `actions` (NULL: the ctx's pending actions).  Outputs are

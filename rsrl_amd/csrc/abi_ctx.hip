@@ -15,6 +15,65 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
+// every environment switch the library reads: once, when the ctx is created -- except RSRL_NO_COALESCE, which rsrl_hip_train asks
+// at every call (bench.py turns it on and off around calls of a live ctx)
+static Switches read_switches() {
+    Switches sw;
+    sw.no_graph = getenv("RSRL_NO_GRAPH") != nullptr;
+    sw.no_persist = getenv("RSRL_NO_PERSIST") != nullptr;
+    sw.no_trait_defer = getenv("RSRL_NO_TRAIT_DEFER") != nullptr;
+    sw.k1_feature_major = getenv("RSRL_K1_FEATURE_MAJOR") != nullptr;
+    if (const char* e = getenv("RSRL_K1_QUAD")) sw.k1_quad = e[0] != '0' ? 1 : 0;
+    if (const char* e = getenv("RSRL_SPARSE_CHUNK")) { const int v = atoi(e); sw.sparse_chunk = v > 0 && v < 16 ? 16 : v; }
+    if (const char* e = getenv("RSRL_PEER_TIMEOUT_MS")) sw.peer_timeout_ms = atol(e);
+    if (const char* e = getenv("RSRL_WAVE_PK")) sw.no_wave_pk = e[0] == '0';
+    return sw;
+}
+bool no_coalesce_switch() { return getenv("RSRL_NO_COALESCE") != nullptr; }
+
+// the kernel family of a validated configuration (ctx.hpp AgentFamily), first match in the order of the enum.  w_elems: the ctx's weight count
+static AgentFamily classify(const rsrl_hip_config& cfg, size_t w_elems) {
+    using F = AgentFamily;
+    const bool fourier = cfg.basis == RSRL_FOURIER, tile = cfg.basis == RSRL_TILE_CODING;
+    const bool wave = is_wave(cfg), reg = fourier && !wave && !is_generic_fourier(cfg);      // (reg: a register-family Fourier order)
+    const int al = cfg.algo;
+    if (cfg.weight_mode == RSRL_W_SHARED) return fourier ? F::SharedDense : (is_sparse_lambda(cfg) ? F::SharedSparseLambda : F::SharedTile);
+    if (wave && is_wave_aux_algo(al)) return F::WaveAux;
+    if (is_pred(al)) return tile ? F::TdTile : (reg ? F::TdReg : F::TdGeneric);
+    if (al == RSRL_Q_SIGMA) return wave ? F::WaveQSigma : (reg ? F::QSigmaReg : F::QSigmaGeneric);
+    if (al == RSRL_GREEDY_GQ) return reg ? F::GqReg : F::GqGeneric;
+    if (is_lambda(al)) return tile ? F::LambdaTile : (wave ? F::WaveLambda : (reg ? F::LambdaReg : F::LambdaGeneric));
+    if (wave) return F::WaveControl;
+    // single-step streaming kernel: needs the whole W addressable through one 32-bit buffer descriptor
+    if (reg) return cfg.steps_per_launch == 1 && (uint64_t)w_elems * 4ull < (1ull << 32) ? F::RegStep : F::RegFused;
+    return F::Generic;
+}
+// what rsrl_hip_timing_read names after a driver-loop launch of the family (the persistent kernel and the trait-granular kernels name themselves)
+static const char* train_kernel_name(const rsrl_hip_ctx* c) {
+    switch (c->family) {
+    case AgentFamily::SharedDense: return "k_shared_step";
+    case AgentFamily::SharedTile: return "k_shared_ca";
+    case AgentFamily::SharedSparseLambda: return "k_sparse_trace_scatter";
+    case AgentFamily::WaveAux: return "k_wave_aux";
+    case AgentFamily::TdTile: return "k_td_tile";
+    case AgentFamily::TdGeneric: return "k_td_mem";
+    case AgentFamily::TdReg: return "k_train_td";
+    case AgentFamily::WaveQSigma: return "k_wave_qsigma";
+    case AgentFamily::QSigmaReg: case AgentFamily::QSigmaGeneric: return "k_train_qsigma";
+    case AgentFamily::GqReg: return "k_train_gq";
+    case AgentFamily::GqGeneric: return "k_train_gq_mem";
+    case AgentFamily::LambdaTile: return "k_lambda_tile";
+    case AgentFamily::WaveLambda: return "k_wave_lambda";
+    case AgentFamily::LambdaGeneric: return "k_train_lambda_mem";
+    case AgentFamily::LambdaReg: return "k_train_lambda";
+    case AgentFamily::WaveControl: return c->cfg.weight_dtype == RSRL_W_BF16 && !c->sw.no_wave_pk ? "k_train_wave_pk" : "k_train_wave";
+    case AgentFamily::RegStep: return c->w_ls != 1 ? (c->k1_quad ? "k_step_reg_q4" : "k_step_reg_lm") : "k_step_reg";
+    case AgentFamily::RegFused: return "k_train_reg";
+    case AgentFamily::Generic: return "k_train_mem";
+    }
+    return "";
+}
+
 RSRL_API_BEGIN
 
 int rsrl_hip_abi_version(void) { return RSRL_HIP_ABI_VERSION; }
@@ -191,8 +250,9 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
     HIP_TRY(hipSetDevice(cfg->device));
     { int cus = 0; HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device)); if (cus > 0) { c->n_simd = 4 * cus; c->n_cu = cus; } }
     if (cfg->peer_timeout_ms < 0) return fail(RSRL_HIP_EINVAL, "peer_timeout_ms must be >= 0");
+    c->sw = read_switches();
     if (cfg->peer_timeout_ms > 0) c->peer_timeout = (uint64_t)cfg->peer_timeout_ms * 100000ull;
-    else if (const char* e = getenv("RSRL_PEER_TIMEOUT_MS")) { const long ms = atol(e); if (ms > 0) c->peer_timeout = (uint64_t)ms * 100000ull; }
+    else if (c->sw.peer_timeout_ms > 0) c->peer_timeout = (uint64_t)c->sw.peer_timeout_ms * 100000ull;
     if (cfg->stream) { c->stream = (hipStream_t)cfg->stream; c->own_stream = false; }
     else { HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
     const int64_t N = cfg->n_envs;
@@ -200,23 +260,26 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
     c->w_stride = shared ? 1 : N;
     c->Aw = is_pred(cfg->algo) ? 1 : c->A;
     c->w_elems = (size_t)c->Aw * c->F * (size_t)(shared ? 1 : N);
+    c->family = classify(*cfg, c->w_elems);
     // a ctx that steps one batch-step per launch streams W every step: learner-major rows (W[N][A][F]) let k_step_reg_lm
     // write back only the touched column (RSRL_K1_FEATURE_MAJOR=1 keeps the feature-major layout, for A/B runs).  NOT the default layout: the fused loop runs on it
     // bit for bit, but its strided load / store of W costs 71 against 26 us per 20-step launch and 1.3 % of the coalesced rate (round 6, measured)
-    if (!shared && cfg->steps_per_launch == 1 && cfg->basis == RSRL_FOURIER && !is_wave(*cfg) && !is_generic_fourier(*cfg) &&
-        !has_aux(cfg->algo) && !is_pred(cfg->algo) && cfg->algo != RSRL_Q_SIGMA && (c->A * c->F) % 4 == 0 && c->F % 4 == 0 &&
-        (uint64_t)c->w_elems * 4ull < (1ull << 32) && !getenv("RSRL_K1_FEATURE_MAJOR")) {
+    if (c->family == AgentFamily::RegStep && (c->A * c->F) % 4 == 0 && c->F % 4 == 0 && !c->sw.k1_feature_major) {
         c->w_stride = 1;
         c->w_ls = (int64_t)c->A * c->F;
-        const char* kq = getenv("RSRL_K1_QUAD");
         // four lanes per learner (k_step_reg_q4) pays once there is more than one round of one-lane waves to overlap: measured
         // 19.8 vs 21.3 us per launch at 131 072 learners, 32.7 vs 38.0 at 262 144, but 9.8 vs 9.0 at 65 536 (RSRL_K1_QUAD=1 / 0 forces)
-        c->k1_quad = c->A <= 3 && (kq ? kq[0] != '0' : N >= 131072);
+        c->k1_quad = c->A <= 3 && (c->sw.k1_quad >= 0 ? c->sw.k1_quad == 1 : N >= 131072);
     }
+    c->train_kernel = train_kernel_name(c);
     c->dw_elems = (size_t)c->Aw * c->F;
-    c->n_stat_slots = is_wave(*cfg) ? wave_grid_for(N) : (c->k1_quad ? (size_t)((N + 63) / 64) : grid_for(N));     // one statistics slot per thread block
-    if ((is_lambda(cfg->algo) || is_pred(cfg->algo)) && cfg->basis == RSRL_TILE_CODING) c->n_stat_slots = (size_t)N;      // ... and there a block is a learner
-    if (is_lambda(cfg->algo) && is_generic_fourier(*cfg) && !is_wave(*cfg)) c->n_stat_slots = (size_t)((N + 63) / 64);     // k_train_lambda_mem4: 64 learners per block
+    // one statistics slot per thread block
+    switch (c->family) {
+    case AgentFamily::WaveAux: case AgentFamily::WaveQSigma: case AgentFamily::WaveLambda: case AgentFamily::WaveControl: c->n_stat_slots = wave_grid_for(N); break;
+    case AgentFamily::TdTile: case AgentFamily::LambdaTile: case AgentFamily::SharedSparseLambda: c->n_stat_slots = (size_t)N; break;      // (a block per learner)
+    case AgentFamily::LambdaGeneric: c->n_stat_slots = (size_t)((N + 63) / 64); break;                  // k_train_lambda_mem4: 64 learners per block
+    default: c->n_stat_slots = c->k1_quad ? (size_t)((N + 63) / 64) : grid_for(N); break;
+    }
     HIP_TRY(hipMalloc((void**)&c->state, sizeof(float) * c->D * (size_t)N));
     HIP_TRY(hipMalloc((void**)&c->action, sizeof(int32_t) * (size_t)N));
     HIP_TRY(hipMalloc((void**)&c->ep_step, sizeof(uint32_t) * (size_t)N));
@@ -225,8 +288,7 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
     HIP_TRY(hipMalloc((void**)&c->dW, sizeof(float) * c->dw_elems));
     HIP_TRY(hipMalloc((void**)&c->qcache, sizeof(float) * c->A * (size_t)N));
     // the trait-granular fast path: learner-major per-learner f32 weights on a basis / agent kernels_trait.hpp is instantiated for, one epsilon for the ctx
-    if (c->w_ls != 1 && cfg->weight_dtype == RSRL_W_F32 && cfg->epsilon_decay == 1.0 && trait_lm_available(cfg->domain, cfg->order, cfg->algo) &&
-        !getenv("RSRL_NO_TRAIT_FAST"))
+    if (c->w_ls != 1 && cfg->weight_dtype == RSRL_W_F32 && cfg->epsilon_decay == 1.0 && trait_lm_available(cfg->domain, cfg->order, cfg->algo))
         HIP_TRY(hipMalloc((void**)&c->tq_key, sizeof(float) * c->D * (size_t)N));
     if (cfg->algo == RSRL_Q_SIGMA) {
         const size_t nf = (size_t)(c->D + 5) * (size_t)cfg->n_steps * (size_t)N;
@@ -242,7 +304,7 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
         hipLaunchKernelGGL(k_fill_f32, dim3(grid_for(N)), dim3(kBlock), 0, c->stream, c->eps, N, (float)cfg->epsilon);
         KCHECK();
     }
-    if (is_sparse_lambda(*cfg)) {
+    if (c->family == AgentFamily::SharedSparseLambda) {
         const int64_t slice = (int64_t)(c->F / cfg->n_tilings) * c->A;
         if (slice > 65536) return fail(RSRL_HIP_EINVAL, "SARSALambda / QLambda over a shared tile table: one tiling's slice (cells * actions = %lld entries) must not "
                                                         "exceed 65 536 (16-bit slice-relative keys between the step and the trace kernel)", (long long)slice);
@@ -262,7 +324,7 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
     }
     if (shared) {
         HIP_TRY(hipMalloc((void**)&c->flags, (size_t)N));
-        if (cfg->basis == RSRL_FOURIER && !is_generic_fourier(*cfg)) {
+        if (c->family == AgentFamily::SharedDense) {
             c->sh_rows = (unsigned)((N + kSharedBlock - 1) / kSharedBlock);
             HIP_TRY(hipMalloc((void**)&c->sh_tab, sizeof(long long) * 3 * kTabRep * c->dw_elems));
             HIP_TRY(hipMemset(c->sh_tab, 0, sizeof(long long) * 3 * kTabRep * c->dw_elems));
@@ -280,12 +342,10 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
     // every learner adds its term to ONE copy with device atomics (same integers, same sum).
     if (shared && cfg->basis == RSRL_TILE_CODING) {
         c->tile_slice = (int64_t)(c->F / cfg->n_tilings) * c->A * 16 <= 128 * 1024;
-        // copies of the delta table the scatter blocks flush into (RSRL_TILE_REPLICAS tunes it; us per batch-step at 262 144 learners: 1: 25.7,
-        // 2: 24.7, 4: 24.1, 8: 24.8, 16: 26.4).  The scatter fused into the step kernel measured 28.7-35.0: scripts/ab/round6_pruned_knobs.patch
-        const char* e = getenv("RSRL_TILE_REPLICAS");
-        const int r = e ? atoi(e) : 4;
+        // four copies of the delta table the scatter blocks flush into (us per batch-step at 262 144 learners: 1: 25.7, 2: 24.7, 4: 24.1, 8: 24.8,
+        // 16: 26.4).  The scatter fused into the step kernel measured 28.7-35.0: scripts/ab/round6_pruned_knobs.patch
         const bool privatised = c->sp_keys ? c->sp_lds : c->tile_slice;
-        c->n_rep = !privatised ? 1 : (r < 1 ? 1 : (r > 16 ? 16 : r));                       // k_apply_rep sums up to 16 copies
+        c->n_rep = privatised ? 4 : 1;
         HIP_TRY(hipMalloc((void**)&c->dW_rep, sizeof(long long) * c->dw_elems * c->n_rep));
         HIP_TRY(hipMemsetAsync(c->dW_rep, 0, sizeof(long long) * c->dw_elems * c->n_rep, c->stream));
         if (c->tile_slice || c->sp_keys) {                               // the scatter is a kernel of its own (k_tile_scatter; k_sparse_trace_scatter)
@@ -400,7 +460,7 @@ int rsrl_hip_reset(rsrl_hip_ctx* c) {
     const BasisGeom g = make_geom(c);
     if (is_pred(c->cfg.algo)) {
         if (!launch_reset_td(c->cfg.domain, dim3(grid_for(k.n_envs)), dim3(kBlock), c->stream, k, c->t)) return NO_MODEL(c);
-    } else if (is_wave(c->cfg)) {
+    } else if (is_wave_family(c->family)) {
         for_wave(c, [&](auto tag) {
             using T = decltype(tag); using WT = typename T::wt;
             hipLaunchKernelGGL((k_wave_reset<T::domain, WT>), dim3(wave_grid_for(k.n_envs)), dim3(kBlock), 0, c->stream, k, (const WT*)c->W, c->t);
@@ -462,11 +522,6 @@ int rsrl_hip_set_actions(rsrl_hip_ctx* c, const int32_t* actions) {
 }
 
 // ---- ABI 8: the learners' state between two driver calls that is neither weights nor env state (include/rsrl_hip.h)
-bool carries_q(const rsrl_hip_ctx* c) {          // the kernels that read Common::qcache: the register family's one-step loops
-    const int al = c->cfg.algo;
-    return c->cfg.basis == RSRL_FOURIER && !is_wave(c->cfg) && !is_generic_fourier(c->cfg) && c->cfg.weight_mode == RSRL_W_PER_ENV &&
-           (al == RSRL_QLEARNING || al == RSRL_SARSA || al == RSRL_EXPECTED_SARSA || al == RSRL_PAL);
-}
 int rsrl_hip_get_episode_steps(rsrl_hip_ctx* c, uint32_t* steps) {
     CHECK_CTX(c); FLUSH(c); if (!steps) return fail(RSRL_HIP_EINVAL, "null argument");
     HIP_TRY(hipSetDevice(c->cfg.device));

@@ -80,10 +80,9 @@ int rsrl_hip_peer_export(rsrl_hip_ctx* c, int world_size, uint8_t* handle_out) {
     c->peer_old_bytes = sizeof(uint2) * 2 * (size_t)world_size * c->dw_elems;
     // second region: the hop-2 buffer of the persistent kernel, [2 (parity)][world][A*F rounded up to even] granules
     c->peer_recv_bytes = c->peer_old_bytes + sizeof(unsigned long long) * 2 * (size_t)world_size * (((size_t)c->dw_elems + 1) / 2 * 2);
-    // fine-grained (uncached across agents) memory, as RCCL uses for its own flag/buffer exchange; RSRL_PEER_COARSE=1 falls
-    // back to a plain allocation (same-device peers only need the system-scope accesses the kernels already use)
-    hipError_t e = getenv("RSRL_PEER_COARSE") ? hipErrorNotSupported
-                                             : hipExtMallocWithFlags((void**)&c->peer_recv, c->peer_recv_bytes, hipDeviceMallocFinegrained);
+    // fine-grained (uncached across agents) memory, as RCCL uses for its own flag/buffer exchange; where the runtime refuses it, a plain
+    // allocation (same-device peers only need the system-scope accesses the kernels already use)
+    hipError_t e = hipExtMallocWithFlags((void**)&c->peer_recv, c->peer_recv_bytes, hipDeviceMallocFinegrained);
     if (e != hipSuccess) { (void)hipGetLastError(); c->peer_recv = nullptr; e = hipMalloc((void**)&c->peer_recv, c->peer_recv_bytes); }
     PeerBlob b; memset(&b, 0, sizeof(b));
     if (e == hipSuccess) e = hipMemsetAsync(c->peer_recv, 0, c->peer_recv_bytes, c->stream);      // tag 0 never matches a batch-step (tags start at 1)
@@ -320,7 +319,7 @@ int rsrl_hip_group_train(rsrl_hip_ctx* const* ctxs, int n, int64_t n_steps) {
             HIP_TRY(hipSetDevice(c->cfg.device));
             TRY(enqueue_shared_step(c, ks[(size_t)i], make_geom(c), nullptr, j == 0 ? 0 : 1, c->t, nullptr, 2));
             c->t += 1;
-            c->kernel_name = shared_kernel_name(c);
+            c->kernel_name = c->train_kernel;
         }
     }
     for (int i = 0; i < n; ++i) {

@@ -69,8 +69,7 @@ static int enqueue_dense_step(rsrl_hip_ctx* c, const Common& k, const BasisGeom&
 // the all-reduces of all ranks of a single-thread group between the two parts, inside one ncclGroupStart / End.)
 int enqueue_shared_step(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, DevStats* d_stats, int do_c, uint64_t t, const uint64_t* t_dev, int xpart) {
     const dim3 grid(grid_for(k.n_envs)), block(kBlock);
-    const bool dense = c->cfg.basis == RSRL_FOURIER;
-    if (dense) {
+    if (c->family == AgentFamily::SharedDense) {
         if (xpart == 2) return RSRL_HIP_OK;                              // the next launch's prologue folds the all-reduced delta
         const int n = (int)c->dw_elems;
         const int fold = do_c ? fold_in_step(c) : 0;
@@ -89,7 +88,7 @@ int enqueue_shared_step(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, De
     }
     // SARSALambda / QLambda over the shared table (sparse per-learner traces, kernels_sparse_lambda.hpp) ride the same three launches: the step
     // kernel takes the TD target's residual (SARSA's / QLearning's formula, step size alpha), the scatter kernel is the one that also updates the traces
-    const bool sparse_lambda = c->sp_keys != nullptr;
+    const bool sparse_lambda = c->family == AgentFamily::SharedSparseLambda;
     const float step_size = (float)(sparse_lambda ? c->cfg.alpha : c->cfg.lr);
     if (xpart != 2 && !for_model(c, [&](auto tag) {
             using M = typename decltype(tag)::type;
@@ -101,8 +100,7 @@ int enqueue_shared_step(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, De
                     ks.alg.kind = c->cfg.algo == RSRL_SARSA_LAMBDA ? ALG_SARSA : ALG_QLEARNING; ks.alg.lr = step_size;
                     hipLaunchKernelGGL((k_shared_ca<M>), grid, block, 0, c->stream, ks, g, t, do_c | (c->cfg.algo == RSRL_Q_LAMBDA ? 2 : 0), dwp, c->flags, d_stats, nrep,
                                        (int64_t)c->dw_elems, t_dev, c->sc_keys, c->sc_terms);
-                    static const int per_env = getenv("RSRL_SPARSE_CHUNK") ? atoi(getenv("RSRL_SPARSE_CHUNK")) : 0;      // (A/B; 0: launch_shared.hip's rule)
-                    launch_sparse_trace_scatter(c, (int64_t)k.n_envs, per_env > 0 && per_env < 16 ? 16 : per_env);
+                    launch_sparse_trace_scatter(c, (int64_t)k.n_envs, c->sw.sparse_chunk);
                     return;
                 }
                 if (c->sc_keys) {
@@ -111,8 +109,7 @@ int enqueue_shared_step(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, De
                     const int slice = (int)((int64_t)(c->F / c->cfg.n_tilings) * c->A);
                     hipLaunchKernelGGL((k_shared_ca<M>), grid, block, 0, c->stream, k, g, t, do_c, dwp, c->flags, d_stats, nrep,
                                        (int64_t)c->dw_elems, t_dev, c->sc_keys, c->sc_terms);
-                    static const int chunks_env = getenv("RSRL_SCATTER_CHUNKS") ? atoi(getenv("RSRL_SCATTER_CHUNKS")) : 32;
-                    int64_t per = (k.n_envs + chunks_env - 1) / chunks_env;
+                    int64_t per = (k.n_envs + 31) / 32;                 // 32 chunks, whole 1 024-learner blocks
                     per = ((per + 1023) / 1024) * 1024;
                     const unsigned chunks = (unsigned)((k.n_envs + per - 1) / per);
                     // (the apply folded into the scatter kernel -- its blocks meeting at a per-tiling arrival counter -- measured SLOWER than the third
@@ -142,7 +139,7 @@ int enqueue_shared_step(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, De
     return RSRL_HIP_OK;
 }
 int enqueue_shared_c(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, uint64_t t_last) {
-    if (c->cfg.basis == RSRL_FOURIER) {
+    if (c->family == AgentFamily::SharedDense) {
         // closing launch: fold the last batch-step's delta, phase C; the result goes back to the canonical buffer
         const int fold = fold_in_step(c);
         TRY(enqueue_dense_step(c, k, g, nullptr, 1, fold, t_last + 1, nullptr));
@@ -210,20 +207,15 @@ static int ensure_step_graph(rsrl_hip_ctx* c, const Common& k, const BasisGeom& 
 // batch-step): 1 024 steps per launch instead of 256 is worth +7 % (8.3e10 -> 8.9e10 env-steps/s, 2 048: 9.0e10) and a
 // launch still lasts under a millisecond (2.4 ms for the trace agents).  The memory-resident and wave-family loops keep 256
 // (their steps are 15-150x longer).
-static bool register_family_fused(const rsrl_hip_ctx* c) {
-    const auto& g = c->cfg;
-    return g.weight_mode == RSRL_W_PER_ENV && g.basis == RSRL_FOURIER && !is_wave(g) && !is_generic_fourier(g) && !has_aux(g.algo) &&
-           !is_pred(g.algo) && g.algo != RSRL_Q_SIGMA;
-}
 static inline int64_t fuse_depth(const rsrl_hip_ctx* c) {
-    const auto& g = c->cfg;
-    if (g.steps_per_launch) return g.steps_per_launch;
-    // every register-resident loop (also the trace / GreedyGQ / TD ones, which load and store two matrices per launch)
-    const bool reg = g.weight_mode == RSRL_W_PER_ENV && g.basis == RSRL_FOURIER && !is_wave(g) && !is_generic_fourier(g) && g.algo != RSRL_Q_SIGMA;
-    // round 3, under the driver's invocation (20-step calls, coalesced; scripts/gpu_r3_v6.sh): 1 024 -> 8.96e10, 2 048 -> 9.06e10,
-    // 4 096 -> 9.12e10, 8 192 -> 9.17e10 env-steps/s; 4 096 (a 2.9 ms launch at 65 536 learners) is the default, RSRL_FUSE_DEPTH the A/B knob
-    static const int64_t reg_depth = getenv("RSRL_FUSE_DEPTH") ? atoll(getenv("RSRL_FUSE_DEPTH")) : 4096;
-    return reg ? (reg_depth > 0 ? reg_depth : 4096) : 256;
+    if (c->cfg.steps_per_launch) return c->cfg.steps_per_launch;
+    // every register-resident loop (also the trace / GreedyGQ / TD ones, which load and store two matrices per launch).  Round 3, under the driver's
+    // invocation (20-step calls, coalesced; scripts/gpu_r3_v6.sh): 1 024 -> 8.96e10, 2 048 -> 9.06e10, 4 096 -> 9.12e10, 8 192 -> 9.17e10 env-steps/s;
+    // 4 096 is a 2.9 ms launch at 65 536 learners
+    switch (c->family) {
+    case AgentFamily::TdReg: case AgentFamily::GqReg: case AgentFamily::LambdaReg: case AgentFamily::RegStep: case AgentFamily::RegFused: return 4096;
+    default: return 256;
+    }
 }
 
 // ---- co-residency of the persistent kernel ----------------------------------------------------------------------------------
@@ -270,7 +262,7 @@ unsigned persist_budget_shared(rsrl_hip_ctx* c) {
 // this rank alone: could it run the persistent kernel?  (multi-rank: what goes into the handle; the group decides)
 bool persist_capable(rsrl_hip_ctx* c) {
     if (c->cfg.weight_mode != RSRL_W_SHARED || !c->sh_tab) return false;
-    if (getenv("RSRL_NO_PERSIST")) return false;
+    if (c->sw.no_persist) return false;
     return c->sh_rows <= persist_budget_single(c);
 }
 bool persist_ok(rsrl_hip_ctx* c) {
@@ -346,8 +338,7 @@ static int persist_launch(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, 
     // (1) the runtime's own check of this grid, once per ctx: a cooperative launch (+15-19 us of host time, paid once).  Not when a
     // peer rank shares this process AND device: cooperative launches of one process go through one queue per device, and a rank
     // queued behind the peer it exchanges with would wait for itself.
-    static const bool no_coop = getenv("RSRL_PERSIST_NO_COOP") != nullptr;
-    const bool coop = !c->coop_validated && c->coop_allowed && !no_coop;
+    const bool coop = !c->coop_validated && c->coop_allowed;
     bool ok = false;
     hipError_t coop_err = hipSuccess;
     for_model(c, [&](auto tag) {
@@ -387,6 +378,63 @@ static int persist_launch(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, 
     return RSRL_HIP_OK;
 }
 
+// the per-learner families (ctx.hpp launch_agent): what one launch of the driver loop runs, or handle on io's transitions
+int launch_agent(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, uint64_t t, int chunk, DevStats* d_stats, const Transitions* io) {
+    const rsrl_hip_config& cf = c->cfg;
+    const dim3 grid(grid_for(io ? io->M : k.n_envs)), block(kBlock);
+    const bool td_lambda = cf.algo == RSRL_TD_LAMBDA;
+    bool ok = true;
+    switch (c->family) {
+    case AgentFamily::WaveAux: case AgentFamily::WaveQSigma: case AgentFamily::WaveLambda:
+        launch_wave_agent(c, k, t, chunk, d_stats, io); break;
+    case AgentFamily::TdTile: ok = launch_td_tile(cf.domain, cf.n_tilings, td_lambda, c->stream, k, g, make_td(c), t, chunk, d_stats, io); break;
+    case AgentFamily::TdGeneric: ok = launch_td_model(cf, grid, block, c->stream, k, make_td(c), g, td_lambda, t, chunk, d_stats, io); break;
+    case AgentFamily::TdReg: ok = launch_td(cf.domain, cf.order, td_lambda, grid, block, c->stream, k, make_td(c), t, chunk, d_stats, io); break;
+    case AgentFamily::QSigmaReg: ok = launch_qsigma(cf.domain, cf.order, grid, block, c->stream, k, make_qs(c), g, t, chunk, d_stats, io); break;
+    case AgentFamily::QSigmaGeneric: ok = launch_qsigma_model(cf, grid, block, c->stream, k, make_qs(c), g, t, chunk, d_stats, io); break;
+    case AgentFamily::GqReg: ok = launch_gq(cf.domain, cf.order, cf.policy, grid, block, c->stream, k, make_gq(c), t, chunk, d_stats, io); break;
+    case AgentFamily::GqGeneric: ok = launch_gq_model(cf, grid, block, c->stream, k, make_gq(c), g, t, chunk, d_stats, io); break;
+    case AgentFamily::LambdaTile: ok = launch_lambda_tile(cf.domain, cf.n_tilings, c->stream, k, g, make_lambda(c), t, chunk, d_stats, io); break;
+    case AgentFamily::LambdaGeneric: ok = launch_lambda_model(cf, grid, block, c->stream, k, make_lambda(c), g, t, chunk, d_stats, io); break;
+    case AgentFamily::LambdaReg: ok = launch_lambda(cf.domain, cf.order, cf.algo, cf.policy, grid, block, c->stream, k, make_lambda(c), t, chunk, d_stats, io); break;
+    // (below: driver loop only)
+    case AgentFamily::WaveControl:
+        for_wave(c, [&](auto tag) {
+            using T = decltype(tag); using WT = typename T::wt;
+            const dim3 wg(wave_grid_for(k.n_envs));
+            if constexpr (WaveIO<WT>::kBf16) {
+                // bf16 weights: the packed-register kernel, two waves per SIMD (kernels_wave.hpp; RSRL_WAVE_PK=0 keeps the fp32-register one: A/B, same bits)
+                if (!c->sw.no_wave_pk) {
+                    if (k.eps) hipLaunchKernelGGL((k_train_wave_pk<T::domain, true>), wg, block, 0, c->stream, k, (WT*)c->W, t, chunk, d_stats);      // the per-learner epsilon schedule
+                    else hipLaunchKernelGGL((k_train_wave_pk<T::domain>), wg, block, 0, c->stream, k, (WT*)c->W, t, chunk, d_stats);
+                    return;
+                }
+            }
+            if (k.eps) hipLaunchKernelGGL((k_train_wave<T::domain, WT, true>), wg, block, 0, c->stream, k, (WT*)c->W, t, chunk, d_stats);
+            else hipLaunchKernelGGL((k_train_wave<T::domain, WT>), wg, block, 0, c->stream, k, (WT*)c->W, t, chunk, d_stats);
+        });
+        break;
+    case AgentFamily::RegStep: return enqueue_k1_step(c, k, d_stats, t, nullptr);
+    case AgentFamily::RegFused:
+        switch (cf.domain) {
+        case 0: ok = launch_train_reg_d0(cf.order, cf.algo, cf.policy, grid, block, c->stream, k, t, chunk, d_stats); break;
+        case 1: ok = launch_train_reg_d1(cf.order, cf.algo, cf.policy, grid, block, c->stream, k, t, chunk, d_stats); break;
+        default: ok = launch_train_reg_d2(cf.order, cf.algo, cf.policy, grid, block, c->stream, k, t, chunk, d_stats); break;
+        }
+        break;
+    case AgentFamily::Generic:
+        ok = for_model(c, [&](auto tag) {
+            using M = typename decltype(tag)::type;
+            hipLaunchKernelGGL((k_train_mem<M>), grid, block, 0, c->stream, k, g, t, chunk, d_stats);
+        });
+        break;
+    default: ok = false; break;      // (the shared-W families: enqueue_shared_step)
+    }
+    if (!ok) return NO_MODEL(c);
+    KCHECK();
+    return RSRL_HIP_OK;
+}
+
 // SARSALambda / QLambda over one shared tile table (kernels_sparse_lambda.hpp): per batch-step phase A (one wave per learner: residual against W_t,
 // sparse trace update, the learner's terms into the fixed-point table), the table -> W (the same finalize -> [exchange] -> apply as rsrl_hip_handle),
 // phase C (sample from W_{t+1}, restarts).  Plain launches: correctness first.
@@ -402,14 +450,12 @@ int train_now(rsrl_hip_ctx* c, int64_t n_steps, rsrl_hip_stats* stats_out) {
     Common k = make_common(c);
     const BasisGeom g = make_geom(c);
     const bool shared = c->cfg.weight_mode == RSRL_W_SHARED;
-    const bool fourier = c->cfg.basis == RSRL_FOURIER;
+    const bool dense = c->family == AgentFamily::SharedDense;
     const int64_t spl = shared ? 1 : fuse_depth(c);
-    // single-step streaming kernel: needs the whole W addressable through one 32-bit buffer descriptor
-    const bool stream_k1 = !shared && fourier && !is_wave(c->cfg) && !is_generic_fourier(c->cfg) && !has_aux(c->cfg.algo) && !is_pred(c->cfg.algo) && c->cfg.algo != RSRL_Q_SIGMA &&
-                           spl == 1 && (uint64_t)c->w_elems * 4ull < (1ull << 32);
+    const bool stream_k1 = c->family == AgentFamily::RegStep;
     // launch-bound loops go through a captured graph (RSRL_NO_GRAPH=1 keeps the plain launches, for A/B runs)
     // (multi-rank included: the RCCL all-reduce and the peer-exchange kernels are captured with the step like any other node)
-    const bool graph_ok = (stream_k1 || shared) && c->own_stream && !stats_out && !getenv("RSRL_NO_GRAPH");
+    const bool graph_ok = (stream_k1 || shared) && c->own_stream && !stats_out && !c->sw.no_graph;
     bool t_dev_set = false;
     int64_t done = 0;
     // the delta tables rotate with the batch-step counter: a counter that did not simply continue (reset, restored checkpoint)
@@ -435,7 +481,7 @@ int train_now(rsrl_hip_ctx* c, int64_t n_steps, rsrl_hip_stats* stats_out) {
     while (done < n_steps) {
         // (dense shared W: the W / row buffers alternate every batch-step, the graph is captured at the parity of an odd step count)
         const int spg = steps_per_graph(c);
-        if (graph_ok && n_steps - done >= spg && (shared ? (done > 0 && (!fourier || (done & 1)) && (!rccl_dense(c) || c->t % 3u == 0)) : c->q_valid)) {
+        if (graph_ok && n_steps - done >= spg && (shared ? (done > 0 && (!dense || (done & 1)) && (!rccl_dense(c) || c->t % 3u == 0)) : c->q_valid)) {
             // the graph's nodes read the policy parameters from device memory: set_epsilon between calls (the reference's drivers
             // decay epsilon every episode, examples/sarsa_lambda.rs:68) refreshes 48 bytes instead of re-instantiating 32+ nodes
             Common kg = k; kg.q_valid = stream_k1 ? 1 : k.q_valid;
@@ -450,7 +496,7 @@ int train_now(rsrl_hip_ctx* c, int64_t n_steps, rsrl_hip_stats* stats_out) {
             TRY(timing_begin(c));
             HIP_TRY(hipGraphLaunch(c->step_graph_exec, c->stream));
             TRY(timing_end(c, (uint32_t)spg));
-            c->kernel_name = stream_k1 ? (c->w_ls != 1 ? (c->k1_quad ? "k_step_reg_q4" : "k_step_reg_lm") : "k_step_reg") : shared_kernel_name(c);
+            c->kernel_name = c->train_kernel;
             c->t += (uint64_t)spg;
             if (peer_steps) c->peer_seq += (uint64_t)spg;
             done += spg;
@@ -461,110 +507,12 @@ int train_now(rsrl_hip_ctx* c, int64_t n_steps, rsrl_hip_stats* stats_out) {
         TRY(timing_begin(c));
         if (shared) {
             TRY(enqueue_shared_step(c, k, g, d_stats, done == 0 ? 0 : 1, c->t, nullptr));
-            c->kernel_name = shared_kernel_name(c);
-        } else if (is_wave(c->cfg) && is_wave_aux_algo(c->cfg.algo)) {
-            launch_wave_agent(c, k, k.n_envs, c->t, chunk, d_stats, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
-            c->kernel_name = "k_wave_aux";
-            KCHECK();
-        } else if (is_pred(c->cfg.algo) && c->cfg.basis == RSRL_TILE_CODING) {
-            if (!launch_td_tile(c->cfg.domain, c->cfg.n_tilings, c->cfg.algo == RSRL_TD_LAMBDA, k.n_envs, c->stream, k, g, make_td(c), c->t, chunk, d_stats,
-                                nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr)) return NO_MODEL(c);
-            c->kernel_name = "k_td_tile";
-            KCHECK();
-        } else if (is_pred(c->cfg.algo) && is_generic_fourier(c->cfg)) {
-            if (!launch_td_model(c->cfg, dim3(grid_for(k.n_envs)), dim3(kBlock), c->stream, k, make_td(c), g, c->cfg.algo == RSRL_TD_LAMBDA, c->t, chunk, d_stats,
-                                 nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr)) return NO_MODEL(c);
-            c->kernel_name = "k_td_mem";
-            KCHECK();
-        } else if (is_pred(c->cfg.algo)) {
-            if (!launch_train_td(c->cfg.domain, c->cfg.order, c->cfg.algo == RSRL_TD_LAMBDA, dim3(grid_for(k.n_envs)), dim3(kBlock), c->stream, k,
-                                 make_td(c), c->t, chunk, d_stats)) return NO_MODEL(c);
-            c->kernel_name = "k_train_td";
-            KCHECK();
-        } else if (c->cfg.algo == RSRL_Q_SIGMA && is_wave(c->cfg)) {
-            launch_wave_agent(c, k, k.n_envs, c->t, chunk, d_stats, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
-            c->kernel_name = "k_wave_qsigma";
-            KCHECK();
-        } else if (c->cfg.algo == RSRL_Q_SIGMA) {
-            const bool reg = fourier && !is_generic_fourier(c->cfg);
-            if (!(reg ? launch_qsigma(c->cfg.domain, c->cfg.order, dim3(grid_for(k.n_envs)), dim3(kBlock), c->stream, k, make_qs(c), g, c->t, chunk, d_stats,
-                                      nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr)
-                      : launch_qsigma_model(c->cfg, dim3(grid_for(k.n_envs)), dim3(kBlock), c->stream, k, make_qs(c), g, c->t, chunk, d_stats,
-                                            nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr))) return NO_MODEL(c);
-            c->kernel_name = "k_train_qsigma";
-            KCHECK();
-        } else if (c->cfg.algo == RSRL_GREEDY_GQ) {
-            const bool reg = fourier && !is_generic_fourier(c->cfg);
-            if (!(reg ? launch_train_gq(c->cfg.domain, c->cfg.order, c->cfg.policy, dim3(grid_for(k.n_envs)), dim3(kBlock), c->stream, k,
-                                        make_gq(c), c->t, chunk, d_stats)
-                      : launch_gq_model(c->cfg, dim3(grid_for(k.n_envs)), dim3(kBlock), c->stream, k, make_gq(c), g, c->t, chunk, d_stats,
-                                        nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr))) return NO_MODEL(c);
-            c->kernel_name = reg ? "k_train_gq" : "k_train_gq_mem";
-            KCHECK();
-        } else if (is_lambda(c->cfg.algo) && c->cfg.basis == RSRL_TILE_CODING) {
-            if (!launch_lambda_tile(c->cfg.domain, c->cfg.n_tilings, k.n_envs, c->stream, k, g, make_lambda(c), c->t, chunk, d_stats, nullptr, nullptr,
-                                    nullptr, nullptr, nullptr, 0, nullptr)) return NO_MODEL(c);
-            c->kernel_name = "k_lambda_tile";
-            KCHECK();
-        } else if (is_lambda(c->cfg.algo) && is_wave(c->cfg)) {
-            launch_wave_agent(c, k, k.n_envs, c->t, chunk, d_stats, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
-            c->kernel_name = "k_wave_lambda";
-            KCHECK();
-        } else if (is_lambda(c->cfg.algo) && is_generic_fourier(c->cfg)) {
-            if (!launch_lambda_model(c->cfg, dim3(grid_for(k.n_envs)), dim3(kBlock), c->stream, k, make_lambda(c), g, c->t, chunk, d_stats, nullptr, nullptr,
-                                     nullptr, nullptr, nullptr, 0, nullptr)) return NO_MODEL(c);
-            c->kernel_name = "k_train_lambda_mem";
-            KCHECK();
-        } else if (is_lambda(c->cfg.algo)) {
-            if (!launch_train_lambda(c->cfg.domain, c->cfg.order, c->cfg.algo, c->cfg.policy, dim3(grid_for(k.n_envs)), dim3(kBlock),
-                                     c->stream, k, make_lambda(c), c->t, chunk, d_stats)) return NO_MODEL(c);
-            c->kernel_name = "k_train_lambda";
-            KCHECK();
-        } else if (is_wave(c->cfg)) {
-            // bf16 weights: the packed-register kernel, two waves per SIMD (kernels_wave.hpp; RSRL_WAVE_PK=0 keeps the fp32-register one: A/B, same bits)
-            static const bool wave_pk = !(getenv("RSRL_WAVE_PK") && getenv("RSRL_WAVE_PK")[0] == '0');
-            const bool pk = wave_pk && c->cfg.weight_dtype == RSRL_W_BF16;
-            for_wave(c, [&](auto tag) {
-                using T = decltype(tag); using WT = typename T::wt;
-                const dim3 wg(wave_grid_for(k.n_envs)), wb(kBlock);
-                if constexpr (WaveIO<WT>::kBf16) {
-                    if (pk) {
-                        if (k.eps) hipLaunchKernelGGL((k_train_wave_pk<T::domain, true>), wg, wb, 0, c->stream, k, (WT*)c->W, c->t, chunk, d_stats);      // the per-learner epsilon schedule
-                        else hipLaunchKernelGGL((k_train_wave_pk<T::domain>), wg, wb, 0, c->stream, k, (WT*)c->W, c->t, chunk, d_stats);
-                        return;
-                    }
-                }
-                if (k.eps) hipLaunchKernelGGL((k_train_wave<T::domain, WT, true>), wg, wb, 0, c->stream, k, (WT*)c->W, c->t, chunk, d_stats);
-                else hipLaunchKernelGGL((k_train_wave<T::domain, WT>), wg, wb, 0, c->stream, k, (WT*)c->W, c->t, chunk, d_stats);
-            });
-            c->kernel_name = pk ? "k_train_wave_pk" : "k_train_wave";
-            KCHECK();
-        } else if (stream_k1) {
-            TRY(enqueue_k1_step(c, k, d_stats, c->t, nullptr));
-            c->kernel_name = c->w_ls != 1 ? (c->k1_quad ? "k_step_reg_q4" : "k_step_reg_lm") : "k_step_reg";
-            c->q_valid = true; k.q_valid = 1;
-        } else if (fourier && !is_generic_fourier(c->cfg)) {
-            const dim3 gr(grid_for(k.n_envs)), b(kBlock);
-            const int kchunk = chunk;
-            bool ok;
-            switch (c->cfg.domain) {
-            case 0: ok = launch_train_reg_d0(c->cfg.order, c->cfg.algo, c->cfg.policy, gr, b, c->stream, k, c->t, kchunk, d_stats); break;
-            case 1: ok = launch_train_reg_d1(c->cfg.order, c->cfg.algo, c->cfg.policy, gr, b, c->stream, k, c->t, kchunk, d_stats); break;
-            default: ok = launch_train_reg_d2(c->cfg.order, c->cfg.algo, c->cfg.policy, gr, b, c->stream, k, c->t, kchunk, d_stats); break;
-            }
-            if (!ok) return NO_MODEL(c);
-            c->kernel_name = "k_train_reg";
-            KCHECK();
-            c->q_valid = true; k.q_valid = 1;       // the launch left Q(s,.) of its final state in qcache
         } else {
-            if (!for_model(c, [&](auto tag) {
-                    using M = typename decltype(tag)::type;
-                    hipLaunchKernelGGL((k_train_mem<M>), dim3(grid_for(k.n_envs)), dim3(kBlock), 0, c->stream, k, g, c->t, chunk, d_stats);
-                })) return NO_MODEL(c);
-            c->kernel_name = "k_train_mem";
-            KCHECK();
-            c->q_valid = false;
+            TRY(launch_agent(c, k, g, c->t, chunk, d_stats, nullptr));
+            if (carries_q(c)) { c->q_valid = true; k.q_valid = 1; }      // the launch left Q(s,.) of its final state in qcache
+            else if (c->family == AgentFamily::Generic) c->q_valid = false;
         }
+        c->kernel_name = c->train_kernel;
         TRY(timing_end(c));
         c->t += (uint64_t)chunk;
         if (peer_steps) c->peer_seq += (uint64_t)chunk;
@@ -591,7 +539,8 @@ int train_now(rsrl_hip_ctx* c, int64_t n_steps, rsrl_hip_stats* stats_out) {
 // Only on a ctx-OWNED stream: a caller who supplied config.stream orders its own work on it (hipStreamSynchronize, events, a
 // capture in progress -- which hipStreamQuery would invalidate); everything train() accepted must be on that stream when it returns.
 static bool coalescable(const rsrl_hip_ctx* c) {
-    return c->own_stream && register_family_fused(c) && c->cfg.steps_per_launch != 1 && !getenv("RSRL_NO_COALESCE");
+    // (steps_per_launch = 1 on a W too large for k_step_reg: k_train_reg one batch-step per launch, not coalesced)
+    return c->own_stream && c->family == AgentFamily::RegFused && c->cfg.steps_per_launch != 1 && !no_coalesce_switch();
 }
 // rsrl_hip_train is asynchronous when no statistics are requested: it returns once the work is accepted.  A short call (the
 // 20 batch-steps of a driver loop) costs a full load + store of every learner's weights around ~20 us of arithmetic, so calls
@@ -656,7 +605,7 @@ static int rollout_impl(rsrl_hip_ctx* c, int64_t step_limit, int64_t M, uint32_t
     const TrajOut tr{os.dev, oa.dev, orw.dev, otm.dev, M};
     const Common k = make_common(c);
     const BasisGeom g = make_geom(c);
-    if (is_wave(c->cfg)) {
+    if (is_wave_family(c->family)) {
         for_wave(c, [&](auto tag) {
             using T = decltype(tag); using WT = typename T::wt;
             hipLaunchKernelGGL((k_wave_rollout<T::domain, WT>), dim3(wave_grid_for(M)), dim3(kBlock), 0, c->stream, k, (const WT*)c->W, step_limit, on.dev, ot.dev, M, tr, rp);

@@ -79,7 +79,7 @@ int rsrl_hip_domain_step(rsrl_hip_ctx* c, const int32_t* actions, float* from_st
     // follow it (rsrl_hip_handle on exactly these arrays, rsrl_hip_domain_reset on the terminal flags, rsrl_hip_policy_sample of the ctx's envs) as
     // one kernel -- or, by whatever other call comes next, as the kernel it would have been now.  Same results, same order (kernels_trait.hpp).
     if (trait_fast(c) && c->own_stream && actions && from_states && next_states && rewards && terminal && is_device_ptr(actions) &&
-        is_device_ptr(from_states) && is_device_ptr(next_states) && is_device_ptr(rewards) && is_device_ptr(terminal) && !getenv("RSRL_NO_TRAIT_DEFER")) {
+        is_device_ptr(from_states) && is_device_ptr(next_states) && is_device_ptr(rewards) && is_device_ptr(terminal) && !c->sw.no_trait_defer) {
         c->tp = rsrl_hip_ctx::TraitPend{};
         c->tp.stage = 1; c->tp.act = actions; c->tp.from = from_states; c->tp.to = next_states; c->tp.rew = rewards; c->tp.term = terminal;
         return RSRL_HIP_OK;
@@ -135,20 +135,21 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
     const uint64_t call = (op == QOP_SAMPLE_STEP || op == QOP_SAMPLE_INIT) ? step_t : c->api_calls;      // (the driver loop's sample: addressed by the batch-step)
     if (op == QOP_SAMPLE) c->api_calls++;
     const BasisGeom g = make_geom(c);
-    if (is_pred(c->cfg.algo) && op == QOP_EVALUATE && is_wave(c->cfg)) {
-        for_wave(c, [&](auto tag) {
-            using T = decltype(tag); using WT = typename T::wt;
-            hipLaunchKernelGGL((k_wave_v_evaluate<T::domain, WT>), dim3(wave_grid_for(M_)), dim3(kBlock), 0, c->stream, (const WT*)c->W, d_states, M_, of.dev);
-        });
-    } else if (is_pred(c->cfg.algo) && op == QOP_EVALUATE && c->cfg.basis == RSRL_TILE_CODING) {
-        if (!launch_td_tile(c->cfg.domain, c->cfg.n_tilings, false, 0, c->stream, k, g, make_td(c), 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, M_,
-                            of.dev, d_states)) return NO_MODEL(c);
-    } else if (is_pred(c->cfg.algo) && op == QOP_EVALUATE && is_generic_fourier(c->cfg)) {
-        if (!launch_td_model(c->cfg, dim3(grid_for(M_)), dim3(kBlock), c->stream, k, make_td(c), g, false, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, M_,
-                             of.dev, d_states)) return NO_MODEL(c);
-    } else if (is_pred(c->cfg.algo) && op == QOP_EVALUATE) {
-        if (!launch_v_evaluate(c->cfg.domain, c->cfg.order, dim3(grid_for(M_)), dim3(kBlock), c->stream, k, d_states, M_, of.dev)) return NO_MODEL(c);
-    } else if (is_wave(c->cfg)) {
+    if (is_pred(c->cfg.algo) && op == QOP_EVALUATE) {          // V(s)
+        bool ok = true;
+        switch (c->family) {
+        case AgentFamily::WaveAux:
+            for_wave(c, [&](auto tag) {
+                using T = decltype(tag); using WT = typename T::wt;
+                hipLaunchKernelGGL((k_wave_v_evaluate<T::domain, WT>), dim3(wave_grid_for(M_)), dim3(kBlock), 0, c->stream, (const WT*)c->W, d_states, M_, of.dev);
+            });
+            break;
+        case AgentFamily::TdTile: ok = launch_v_tile(c->cfg.domain, c->cfg.n_tilings, c->stream, k, g, d_states, M_, of.dev); break;
+        case AgentFamily::TdGeneric: ok = launch_v_model(c->cfg, dim3(grid_for(M_)), dim3(kBlock), c->stream, k, g, d_states, M_, of.dev); break;
+        default: ok = launch_v_evaluate(c->cfg.domain, c->cfg.order, dim3(grid_for(M_)), dim3(kBlock), c->stream, k, d_states, M_, of.dev); break;
+        }
+        if (!ok) return NO_MODEL(c);
+    } else if (is_wave_family(c->family)) {
         for_wave(c, [&](auto tag) {
             using T = decltype(tag); using WT = typename T::wt;
             hipLaunchKernelGGL((k_wave_qop<T::domain, WT>), dim3(wave_grid_for(M_)), dim3(kBlock), 0, c->stream, k, (const WT*)c->W, op, d_states, M_, call, of.dev, oi.dev,
@@ -304,7 +305,7 @@ int rsrl_hip_handle(rsrl_hip_ctx* c, const float* from_states, const int32_t* ac
     TRY(stage_out(c, 5, td_error_out, (size_t)M, &otd));
     const Common k = make_common(c);
     const BasisGeom g = make_geom(c);
-    if (is_sparse_lambda(c->cfg)) {
+    if (c->family == AgentFamily::SharedSparseLambda) {
         // transition i is LEARNER i's (round 6): its residual against the shared table, its trace, the mini-batch's delta -- the driver loop's three launches on
         // the caller's transitions (kernels_sparse_lambda.hpp)
         const float step_size = (float)c->cfg.alpha;
@@ -338,51 +339,27 @@ int rsrl_hip_handle(rsrl_hip_ctx* c, const float* from_states, const int32_t* ac
     }
     if (trait_fast(c)) {
         TRY(launch_trait_handle(c, k, d_from, d_act, d_rew, d_to, d_term, M, c->t, otd.dev));
-    } else if (is_wave(c->cfg) && is_wave_aux_algo(c->cfg.algo)) {
-        launch_wave_agent(c, k, M, c->t, 1, nullptr, d_from, d_act, d_rew, d_to, d_term, M, otd.dev);
-    } else if (is_pred(c->cfg.algo) && c->cfg.basis == RSRL_TILE_CODING) {
-        if (!launch_td_tile(c->cfg.domain, c->cfg.n_tilings, c->cfg.algo == RSRL_TD_LAMBDA, M, c->stream, k, g, make_td(c), c->t, 1, nullptr, d_from, d_rew,
-                            d_to, d_term, M, otd.dev, nullptr)) return NO_MODEL(c);
-    } else if (is_pred(c->cfg.algo) && is_generic_fourier(c->cfg)) {
-        if (!launch_td_model(c->cfg, dim3(grid_for(M)), dim3(kBlock), c->stream, k, make_td(c), g, c->cfg.algo == RSRL_TD_LAMBDA, c->t, 1, nullptr, d_from, d_rew,
-                             d_to, d_term, M, otd.dev, nullptr)) return NO_MODEL(c);
-    } else if (is_pred(c->cfg.algo)) {
-        if (!launch_handle_td(c->cfg.domain, c->cfg.order, c->cfg.algo == RSRL_TD_LAMBDA, dim3(grid_for(M)), dim3(kBlock), c->stream, k, make_td(c),
-                              d_from, d_rew, d_to, d_term, M, otd.dev)) return NO_MODEL(c);
-    } else if (c->cfg.algo == RSRL_Q_SIGMA && is_wave(c->cfg)) {
-        launch_wave_agent(c, k, M, c->t, 1, nullptr, d_from, d_act, d_rew, d_to, d_term, M, otd.dev);
-    } else if (c->cfg.algo == RSRL_Q_SIGMA) {
-        const bool reg = c->cfg.basis == RSRL_FOURIER && !is_generic_fourier(c->cfg);
-        if (!(reg ? launch_qsigma(c->cfg.domain, c->cfg.order, dim3(grid_for(M)), dim3(kBlock), c->stream, k, make_qs(c), g, c->t, 0, nullptr,
-                                  d_from, d_act, d_rew, d_to, d_term, M, otd.dev)
-                  : launch_qsigma_model(c->cfg, dim3(grid_for(M)), dim3(kBlock), c->stream, k, make_qs(c), g, c->t, 0, nullptr,
-                                        d_from, d_act, d_rew, d_to, d_term, M, otd.dev))) return NO_MODEL(c);
-    } else if (c->cfg.algo == RSRL_GREEDY_GQ) {
-        const bool reg = c->cfg.basis == RSRL_FOURIER && !is_generic_fourier(c->cfg);
-        if (!(reg ? launch_handle_gq(c->cfg.domain, c->cfg.order, dim3(grid_for(M)), dim3(kBlock), c->stream, k, make_gq(c),
-                                     d_from, d_act, d_rew, d_to, d_term, M, otd.dev)
-                  : launch_gq_model(c->cfg, dim3(grid_for(M)), dim3(kBlock), c->stream, k, make_gq(c), g, c->t, 0, nullptr,
-                                    d_from, d_act, d_rew, d_to, d_term, M, otd.dev))) return NO_MODEL(c);
-    } else if (is_lambda(c->cfg.algo) && c->cfg.basis == RSRL_TILE_CODING) {
-        if (!launch_lambda_tile(c->cfg.domain, c->cfg.n_tilings, M, c->stream, k, g, make_lambda(c), c->t, 1, nullptr, d_from, d_act, d_rew, d_to, d_term,
-                                M, otd.dev)) return NO_MODEL(c);
-    } else if (is_lambda(c->cfg.algo) && is_wave(c->cfg)) {
-        launch_wave_agent(c, k, M, c->t, 1, nullptr, d_from, d_act, d_rew, d_to, d_term, M, otd.dev);
-    } else if (is_lambda(c->cfg.algo) && is_generic_fourier(c->cfg)) {
-        if (!launch_lambda_model(c->cfg, dim3(grid_for(M)), dim3(kBlock), c->stream, k, make_lambda(c), g, c->t, 1, nullptr, d_from, d_act, d_rew, d_to, d_term,
-                                 M, otd.dev)) return NO_MODEL(c);
-    } else if (is_lambda(c->cfg.algo)) {
-        if (!launch_handle_lambda(c->cfg.domain, c->cfg.order, dim3(grid_for(M)), dim3(kBlock), c->stream, k, make_lambda(c),
-                                  d_from, d_act, d_rew, d_to, d_term, M, c->t, otd.dev)) return NO_MODEL(c);
-    } else if (is_wave(c->cfg)) {
-        for_wave(c, [&](auto tag) {
-            using T = decltype(tag); using WT = typename T::wt;
-            hipLaunchKernelGGL((k_wave_handle<T::domain, WT>), dim3(wave_grid_for(M)), dim3(kBlock), 0, c->stream, k, (WT*)c->W, d_from, d_act, d_rew, d_to, d_term, M, c->t, otd.dev);
-        });
-    } else if (!for_model(c, [&](auto tag) {
-            using Mo = typename decltype(tag)::type;
-            hipLaunchKernelGGL((k_handle<Mo>), dim3(grid_for(M)), dim3(kBlock), 0, c->stream, k, g, d_from, d_act, d_rew, d_to, d_term, M, c->t, otd.dev, c->h_fx);
-        })) return NO_MODEL(c);
+    } else {
+        switch (c->family) {
+        case AgentFamily::WaveControl:
+            for_wave(c, [&](auto tag) {
+                using T = decltype(tag); using WT = typename T::wt;
+                hipLaunchKernelGGL((k_wave_handle<T::domain, WT>), dim3(wave_grid_for(M)), dim3(kBlock), 0, c->stream, k, (WT*)c->W, d_from, d_act, d_rew, d_to, d_term, M, c->t,
+                                   otd.dev);
+            });
+            break;
+        case AgentFamily::SharedDense: case AgentFamily::SharedTile: case AgentFamily::RegStep: case AgentFamily::RegFused: case AgentFamily::Generic:
+            if (!for_model(c, [&](auto tag) {
+                    using Mo = typename decltype(tag)::type;
+                    hipLaunchKernelGGL((k_handle<Mo>), dim3(grid_for(M)), dim3(kBlock), 0, c->stream, k, g, d_from, d_act, d_rew, d_to, d_term, M, c->t, otd.dev, c->h_fx);
+                })) return NO_MODEL(c);
+            break;
+        default: {
+            const Transitions io{d_from, d_act, d_rew, d_to, d_term, M, otd.dev};
+            TRY(launch_agent(c, k, g, c->t, 1, nullptr, &io));
+        }
+        }
+    }
     KCHECK();
     if (c->cfg.weight_mode == RSRL_W_SHARED) {
         // the mini-batch delta (accumulated in fixed point: exact, reproducible) of ALL ranks is applied by every rank (replicas

@@ -72,9 +72,8 @@ __global__ void k_checksum_lm(const uint32_t* __restrict__ p, int64_t N, int AF,
 __global__ void k_checksum(const uint32_t* __restrict__ p, size_t n, size_t index_offset, unsigned long long* __restrict__ out);
 struct rsrl_hip_ctx;
 // the order-7 wave family's memory-sweep agents (GreedyGQ / TD / TDLambda: k_wave_aux; QSigma: k_wave_qsigma; SARSALambda / QLambda: k_wave_lambda), driver loop
-// (from == nullptr: n_steps batch-steps of the ctx's learners) or Handler::handle on M caller-supplied transitions
-void launch_wave_agent(const rsrl_hip_ctx* c, const rsrl::Common& k, int64_t items, uint64_t t, int n_steps, rsrl::DevStats* d_stats, const float* from,
-                       const int32_t* act, const float* rew, const float* to, const uint8_t* term, int64_t M, float* td_out);
+// (io == nullptr: n_steps batch-steps of the ctx's learners) or Handler::handle on io's caller-supplied transitions
+void launch_wave_agent(const rsrl_hip_ctx* c, const rsrl::Common& k, uint64_t t, int n_steps, rsrl::DevStats* d_stats, const rsrl::Transitions* io);
 // the trace update + LDS scatter of the sparse-trace lambda agents for learners 0 .. n_learners-1 (kernels_sparse_lambda.hpp)
 void launch_sparse_trace_scatter(const rsrl_hip_ctx* c, int64_t n_learners, int per_block);
 // dynamic LDS beyond the default for that kernel (a tiling's slice of more than 64 KiB): false when the runtime refuses
@@ -96,8 +95,51 @@ int fail(int code, const char* fmt, ...);           // records the message for r
 // ------------------------------------------------------------------------------- ctx
 struct Scratch { void* p = nullptr; size_t cap = 0; };
 
+// The kernel family that serves a ctx: decided once, by classify() in rsrl_hip_create; the driver loop, handle, reset, the Q operations, rollouts and
+// the launch shapes switch on it.  Listed in the order classify() tests them (first match wins).
+enum class AgentFamily : uint8_t {
+    SharedDense,          // shared W, Fourier: k_shared_step / k_shared_persist
+    SharedTile,           // shared W, tile coding: k_shared_ca (+ k_tile_scatter)
+    SharedSparseLambda,   // SARSALambda / QLambda over one shared tile table, sparse per-learner traces: k_shared_ca + k_sparse_trace_scatter
+    WaveAux,              // order-7 wave family, GreedyGQ / TD / TDLambda: k_wave_aux
+    TdTile,               // TD / TDLambda, tile coding: k_td_tile
+    TdGeneric,            // ... generic Fourier orders: k_td_mem
+    TdReg,                // ... register-family Fourier: k_train_td
+    WaveQSigma,           // k_wave_qsigma
+    QSigmaReg,            // QSigma, register-family Fourier: k_train_qsigma<FourierModel>
+    QSigmaGeneric,        // ... tile coding, generic Fourier orders: k_train_qsigma<M>
+    GqReg,                // GreedyGQ, register-family Fourier: k_train_gq
+    GqGeneric,            // ... tile coding, generic Fourier orders: k_train_gq_mem
+    LambdaTile,           // SARSALambda / QLambda, per-learner tile tables: k_lambda_tile
+    WaveLambda,           // k_wave_lambda
+    LambdaGeneric,        // ... generic Fourier orders: k_train_lambda_mem4
+    LambdaReg,            // ... register-family Fourier: k_train_lambda
+    WaveControl,          // order-7 wave family, one-step agents: k_train_wave (f32) / k_train_wave_pk (bf16)
+    RegStep,              // register family, one batch-step per launch: k_step_reg / k_step_reg_lm / k_step_reg_q4
+    RegFused,             // register family, fused loop: k_train_reg
+    Generic,              // one-step agents on tile coding / generic Fourier orders, per-learner weights: k_train_mem
+};
+static inline bool is_wave_family(AgentFamily f) {
+    return f == AgentFamily::WaveAux || f == AgentFamily::WaveQSigma || f == AgentFamily::WaveLambda || f == AgentFamily::WaveControl;
+}
+
+// the environment switches, read once when the ctx is created (abi_ctx.hip read_switches)
+struct Switches {
+    bool no_graph = false;            // RSRL_NO_GRAPH: plain launches instead of captured step graphs
+    bool no_persist = false;          // RSRL_NO_PERSIST: shared dense W steps one launch per batch-step instead of the persistent kernel
+    bool no_trait_defer = false;      // RSRL_NO_TRAIT_DEFER: the trait-granular loop launches one kernel per call
+    bool k1_feature_major = false;    // RSRL_K1_FEATURE_MAJOR: the single-step kernel keeps the feature-major layout
+    int k1_quad = -1;                 // RSRL_K1_QUAD: 0 / 1 forces one / four lanes per learner, -1 = by size
+    int sparse_chunk = 0;             // RSRL_SPARSE_CHUNK: learners per block of the sparse-trace scatter (0 = one block per CU)
+    long peer_timeout_ms = 0;         // RSRL_PEER_TIMEOUT_MS (0 = unset)
+    bool no_wave_pk = false;          // RSRL_WAVE_PK=0: bf16 ctxs of the order-7 wave family on the fp32-register kernel k_train_wave
+};
+
 struct rsrl_hip_ctx {
     rsrl_hip_config cfg{};
+    AgentFamily family = AgentFamily::Generic;
+    const char* train_kernel = "";   // the family's driver-loop kernel, what rsrl_hip_timing_read names after a train launch
+    Switches sw;
     int D = 0, A = 0, F = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -266,10 +308,6 @@ static bool for_wave(const rsrl_hip_ctx* c, Fn&& fn) {
     return false;
 }
 
-// the step kernel of the shared-weight loops (what rsrl_hip_timing_read names): the dense bases', shared tile coding's, the sparse-trace lambda agents'
-static inline const char* shared_kernel_name(const rsrl_hip_ctx* c) {
-    return c->cfg.basis == RSRL_FOURIER ? "k_shared_step" : (c->sp_keys ? "k_sparse_trace_scatter" : "k_shared_ca");
-}
 static inline unsigned grid_for(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 // resolution of the fixed-point delta tables of shared tile coding: 2^(floor(log2 |lr|) - 28), the same bits the kernel derives
 static inline float tile_lsb(float lr) {
@@ -474,7 +512,12 @@ int exchange_table(rsrl_hip_ctx* c, uint64_t t);
 bool persist_capable(rsrl_hip_ctx* c);
 bool persist_ok(rsrl_hip_ctx* c);
 unsigned persist_budget_shared(rsrl_hip_ctx* c);
-extern "C" __attribute__((visibility("hidden"))) bool carries_q(const rsrl_hip_ctx* c);                                                                                                   // abi_ctx.hip
+// the kernels that read Common::qcache: the register family's one-step loops
+static inline bool carries_q(const rsrl_hip_ctx* c) { return c->family == AgentFamily::RegStep || c->family == AgentFamily::RegFused; }
+bool no_coalesce_switch();                                                                                                                  // abi_ctx.hip
+// the per-learner families' launch, driver loop (io == nullptr: chunk batch-steps from batch-step t) or Handler::handle on io's transitions (the families
+// with a handle kernel of their own; rsrl_hip_handle takes the rest to k_handle / k_wave_handle)                                            abi_train.hip
+int launch_agent(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, uint64_t t, int chunk, DevStats* d_stats, const Transitions* io);
 extern "C" __attribute__((visibility("hidden"))) int traces_rw(rsrl_hip_ctx* c, int64_t env_index, float* out, const float* in);                                                          // abi_weights.hip
 constexpr int kStepsPerGraph = 32;       // batch-steps per captured step graph (abi_train.hip)
 #define ST_RCCL_GUARD(c) do { if ((c)->st_rccl_group) return fail(RSRL_HIP_ESTATE, "this ctx is a rank of a single-thread RCCL group: its collectives must be " \

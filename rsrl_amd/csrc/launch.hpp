@@ -16,63 +16,58 @@ bool launch_train_reg_d2(int order, int algo, int policy, dim3 grid, dim3 block,
 
 // chunk == -1 selects the single-step streaming kernel (k_step_reg), -2 its learner-major form (k_step_reg_lm), -3 the learner-major
 // form with four lanes per learner (k_step_reg_q4: grid = learners / 64)
+
+// Handler::handle's M caller-supplied transitions (device arrays; td_out may be null).  The launchers below take a pointer to them: nullptr
+// runs the driver loop (chunk batch-steps of the ctx's learners) instead.  Host only: the kernels take the fields as arguments of their own.
+struct Transitions {
+    const float* from = nullptr; const int32_t* act = nullptr; const float* rew = nullptr; const float* to = nullptr; const uint8_t* term = nullptr;
+    int64_t M = 0; float* td_out = nullptr;
+};
+// what a launcher passes to a kernel that serves both: the transitions, or the driver loop's empty set
+static inline Transitions transitions_or_none(const Transitions* io) { return io ? *io : Transitions{}; }
+
 struct LambdaParams;
 struct BasisGeom;
-bool launch_train_lambda(int domain, int order, int algo, int policy, dim3 grid, dim3 block, hipStream_t st,
-                         const Common& k, const LambdaParams& lp, uint64_t t, int chunk, DevStats* stats);
-bool launch_handle_lambda(int domain, int order, dim3 grid, dim3 block, hipStream_t st, const Common& k, const LambdaParams& lp,
-                          const float* from, const int32_t* act, const float* rew, const float* to, const uint8_t* termf,
-                          int64_t Mn, uint64_t t, float* td_out);
-
-// lambda agents on tile coding, per-learner tables: n_blocks = learners (driver loop) or Mn (handle: from != nullptr)
-bool launch_lambda_tile(int domain, int n_tilings, int64_t n_blocks, hipStream_t st, const Common& k, const BasisGeom& g, const LambdaParams& lp,
-                        uint64_t t, int chunk, DevStats* stats, const float* from, const int32_t* act, const float* rew, const float* to,
-                        const uint8_t* termf, int64_t Mn, float* td_out);
+bool launch_lambda(int domain, int order, int algo, int policy, dim3 grid, dim3 block, hipStream_t st, const Common& k, const LambdaParams& lp,
+                   uint64_t t, int chunk, DevStats* stats, const Transitions* io);
+// lambda agents on tile coding, per-learner tables: one block per learner (driver loop) or per transition (handle)
+bool launch_lambda_tile(int domain, int n_tilings, hipStream_t st, const Common& k, const BasisGeom& g, const LambdaParams& lp, uint64_t t, int chunk,
+                        DevStats* stats, const Transitions* io);
 
 struct TdParams;
-bool launch_td_tile(int domain, int n_tilings, bool lambda, int64_t n_blocks, hipStream_t st, const Common& k, const BasisGeom& g, const TdParams& tp,
-                    uint64_t t, int chunk, DevStats* stats, const float* from, const float* rew, const float* to, const uint8_t* termf, int64_t Mn,
-                    float* td_out, const float* eval_states);
+// TD / TDLambda on tile coding: one block per learner (driver loop) or per transition (handle); V(s) of M states into out
+bool launch_td_tile(int domain, int n_tilings, bool lambda, hipStream_t st, const Common& k, const BasisGeom& g, const TdParams& tp, uint64_t t, int chunk,
+                    DevStats* stats, const Transitions* io);
+bool launch_v_tile(int domain, int n_tilings, hipStream_t st, const Common& k, const BasisGeom& g, const float* states, int64_t M, float* out);
 
 struct GqParams;
-bool launch_train_gq(int domain, int order, int policy, dim3 grid, dim3 block, hipStream_t st, const Common& k,
-                     const GqParams& gp, uint64_t t, int chunk, DevStats* stats);
-bool launch_handle_gq(int domain, int order, dim3 grid, dim3 block, hipStream_t st, const Common& k, const GqParams& gp,
-                      const float* from, const int32_t* act, const float* rew, const float* to, const uint8_t* termf,
-                      int64_t Mn, float* td_out);
+bool launch_gq(int domain, int order, int policy, dim3 grid, dim3 block, hipStream_t st, const Common& k, const GqParams& gp, uint64_t t, int chunk,
+               DevStats* stats, const Transitions* io);
 
-struct TdParams;
-bool launch_train_td(int domain, int order, bool lambda, dim3 grid, dim3 block, hipStream_t st, const Common& k, const TdParams& tp,
-                     uint64_t t, int chunk, DevStats* stats);
-bool launch_handle_td(int domain, int order, bool lambda, dim3 grid, dim3 block, hipStream_t st, const Common& k, const TdParams& tp,
-                      const float* from, const float* rew, const float* to, const uint8_t* termf, int64_t Mn, float* td_out);
+bool launch_td(int domain, int order, bool lambda, dim3 grid, dim3 block, hipStream_t st, const Common& k, const TdParams& tp, uint64_t t, int chunk,
+               DevStats* stats, const Transitions* io);
 bool launch_v_evaluate(int domain, int order, dim3 grid, dim3 block, hipStream_t st, const Common& k, const float* states, int64_t Mn, float* out);
 bool launch_reset_td(int domain, dim3 grid, dim3 block, hipStream_t st, const Common& k, uint64_t t);
 
 struct QsParams;
-struct BasisGeom;
-// from == nullptr: the QSigma driver loop (chunk batch-steps); otherwise Handler::handle on Mn caller-supplied transitions
 bool launch_qsigma(int domain, int order, dim3 grid, dim3 block, hipStream_t st, const Common& k, const QsParams& qp, const BasisGeom& g, uint64_t t,
-                   int chunk, DevStats* stats, const float* from, const int32_t* act, const float* rew, const float* to, const uint8_t* termf,
-                   int64_t Mn, float* td_out);
+                   int chunk, DevStats* stats, const Transitions* io);
 
-// the same two agents on the models without a register-family kernel (tile coding, generic Fourier orders); false if the configuration
+// the same agents on the models without a register-family kernel (tile coding, generic Fourier orders); false if the configuration
 // has a register-family kernel (use the launchers above) or none at all
 }  // namespace rsrl
 #include "../../include/rsrl_hip.h"
 namespace rsrl {
 bool launch_gq_model(const rsrl_hip_config& cfg, dim3 grid, dim3 block, hipStream_t st, const Common& k, const GqParams& gp, const BasisGeom& g, uint64_t t,
-                     int chunk, DevStats* stats, const float* from, const int32_t* act, const float* rew, const float* to, const uint8_t* termf,
-                     int64_t Mn, float* td_out);
+                     int chunk, DevStats* stats, const Transitions* io);
 bool launch_lambda_model(const rsrl_hip_config& cfg, dim3 grid, dim3 block, hipStream_t st, const Common& k, const LambdaParams& lp, const BasisGeom& g,
-                         uint64_t t, int chunk, DevStats* stats, const float* from, const int32_t* act, const float* rew, const float* to,
-                         const uint8_t* termf, int64_t Mn, float* td_out);
+                         uint64_t t, int chunk, DevStats* stats, const Transitions* io);
 bool launch_td_model(const rsrl_hip_config& cfg, dim3 grid, dim3 block, hipStream_t st, const Common& k, const TdParams& tp, const BasisGeom& g, bool lambda,
-                     uint64_t t, int chunk, DevStats* stats, const float* from, const float* rew, const float* to, const uint8_t* termf, int64_t Mn,
-                     float* out, const float* states);
+                     uint64_t t, int chunk, DevStats* stats, const Transitions* io);
+bool launch_v_model(const rsrl_hip_config& cfg, dim3 grid, dim3 block, hipStream_t st, const Common& k, const BasisGeom& g, const float* states, int64_t M,
+                    float* out);
 bool launch_qsigma_model(const rsrl_hip_config& cfg, dim3 grid, dim3 block, hipStream_t st, const Common& k, const QsParams& qp, const BasisGeom& g, uint64_t t,
-                         int chunk, DevStats* stats, const float* from, const int32_t* act, const float* rew, const float* to, const uint8_t* termf,
-                         int64_t Mn, float* td_out);
+                         int chunk, DevStats* stats, const Transitions* io);
 
 #define RSRL_TRAIN_CASE(DM, OR, AL, PO)                                                                     \
     if (order == OR && algo == AL && policy == PO) {                                                        \

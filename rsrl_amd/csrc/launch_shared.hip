@@ -5,17 +5,21 @@
 
 RSRL_DEFINE_FX_READER(fx_saturations_launch)
 
-void launch_wave_agent(const rsrl_hip_ctx* c, const Common& k, int64_t items, uint64_t t, int n_steps, DevStats* d_stats, const float* from, const int32_t* act,
-                       const float* rew, const float* to, const uint8_t* term, int64_t M, float* td_out) {
-    const dim3 grid(wave_grid_for(items)), block(kBlock);
+void launch_wave_agent(const rsrl_hip_ctx* c, const Common& k, uint64_t t, int n_steps, DevStats* d_stats, const Transitions* io) {
+    const Transitions x = transitions_or_none(io);
+    const dim3 grid(wave_grid_for(io ? io->M : k.n_envs)), block(kBlock);
     for_wave(c, [&](auto tag) {
         using T = decltype(tag); using WT = typename T::wt;
-        if (is_wave_aux_algo(c->cfg.algo)) {
-            hipLaunchKernelGGL((k_wave_aux<T::domain, WT>), grid, block, 0, c->stream, k, make_wave_aux(c), (WT*)c->W, t, n_steps, d_stats, from, act, rew, to, term, M, td_out);
-        } else if (c->cfg.algo == RSRL_Q_SIGMA) {
-            hipLaunchKernelGGL((k_wave_qsigma<T::domain, WT>), grid, block, 0, c->stream, k, make_qs(c), (WT*)c->W, t, n_steps, d_stats, from, act, rew, to, term, M, td_out);
-        } else {
-            hipLaunchKernelGGL((k_wave_lambda<T::domain, WT>), grid, block, 0, c->stream, k, make_lambda(c), (WT*)c->W, t, n_steps, d_stats, from, act, rew, to, term, M, td_out);
+        switch (c->family) {
+        case AgentFamily::WaveAux:
+            hipLaunchKernelGGL((k_wave_aux<T::domain, WT>), grid, block, 0, c->stream, k, make_wave_aux(c), (WT*)c->W, t, n_steps, d_stats, x.from, x.act, x.rew, x.to, x.term, x.M, x.td_out);
+            break;
+        case AgentFamily::WaveQSigma:
+            hipLaunchKernelGGL((k_wave_qsigma<T::domain, WT>), grid, block, 0, c->stream, k, make_qs(c), (WT*)c->W, t, n_steps, d_stats, x.from, x.act, x.rew, x.to, x.term, x.M, x.td_out);
+            break;
+        default:
+            hipLaunchKernelGGL((k_wave_lambda<T::domain, WT>), grid, block, 0, c->stream, k, make_lambda(c), (WT*)c->W, t, n_steps, d_stats, x.from, x.act, x.rew, x.to, x.term, x.M, x.td_out);
+            break;
         }
     });
 }
