@@ -54,9 +54,15 @@ typedef enum {
     RSRL_HIP_ESTATE  = -5    /* call not valid in the ctx's current state            */
 } rsrl_hip_status;
 
-/* rsrl_domains::{MountainCar, CartPole, Acrobot}
- *   mountain_car/discrete.rs:8-102, cart_pole.rs:7-121, acrobot.rs:8-152 */
-typedef enum { RSRL_MOUNTAIN_CAR = 0, RSRL_CART_POLE = 1, RSRL_ACROBOT = 2 } rsrl_domain;
+/* rsrl_domains::{MountainCar, CartPole, Acrobot, HIVTreatment}
+ *   mountain_car/discrete.rs:8-102, cart_pole.rs:7-121, acrobot.rs:8-152, hiv.rs:1-146 (exported at lib.rs:498-499)
+ * HIVTreatment: a hidden state [T1, T1*, T2, T2*, V, E] in f64 (hiv.rs:42-52) that every env-step integrates with 1 000 classical RK4
+ *   sub-steps (:54-71, ode.rs:1-43) in the reference's operation order -- the same bits as the reference; the env state the API carries
+ *   (D = 6) is its observation clip(-5, log10 y, 8) (:112-119) rounded to f32, the reward is taken from the observation in f64 (:121-135);
+ *   4 actions (:35), no terminal state (episodes end at max_episode_steps only).  Supported: QLearning, SARSA, ExpectedSARSA, PAL on the
+ *   Fourier basis of order 1-3, per-learner f32 weights, no epsilon schedule; every other combination is EINVAL at create.  The hidden
+ *   state: rsrl_hip_get_hidden_states / _set_hidden_states. */
+typedef enum { RSRL_MOUNTAIN_CAR = 0, RSRL_CART_POLE = 1, RSRL_ACROBOT = 2, RSRL_HIV_TREATMENT = 3 } rsrl_domain;
 /* lfa::basis::{Fourier (+with_bias), TileCoding}  (re-exported by rsrl/src/fa/linear.rs:11-14) */
 typedef enum { RSRL_FOURIER = 0, RSRL_TILE_CODING = 1 } rsrl_basis;
 /* rsrl::control::td::{QLearning, SARSA, ExpectedSARSA}
@@ -230,6 +236,12 @@ int rsrl_hip_set_states(rsrl_hip_ctx* ctx, const float* states /*[D][N]*/);
 /*   (set_states: the array must hold finite values within 1000 widths of each dimension's bounds, else EINVAL and the ctx is untouched -- the reference's
  *    wrap! macro, rsrl_domains/src/macros.rs:14-24, loops without end on an infinite angle; a HOST array is checked on the host, a DEVICE array on the
  *    device by the same rule (ABI 9: it used to be clamped silently, NaN passing)) */
+/*   (HIVTreatment: the states are the observations; set_states sets every hidden component to pow(10.0, (double)obs) -- inside (-5, 8) the exact
+ *    inverse of the observation, a clipped component (-5 or 8) cannot be inverted -- and requires every value within [-5, 8]) */
+/* HIVTreatment's hidden states, f64[6][N] (learner fastest), host or device memory.  set: the observations become emit() of the given states.
+ * EINVAL ("domain has no hidden state") on the other domains. */
+int rsrl_hip_get_hidden_states(rsrl_hip_ctx* ctx, double* y /*[6][N]*/);
+int rsrl_hip_set_hidden_states(rsrl_hip_ctx* ctx, const double* y /*[6][N]*/);
 int rsrl_hip_get_actions(rsrl_hip_ctx* ctx, int32_t* actions /*[N]*/);
 int rsrl_hip_set_actions(rsrl_hip_ctx* ctx, const int32_t* actions /*[N]*/);
 /* (ABI 8) The rest of a learner's state between two driver calls, so that a run can be carried into another ctx EXACTLY (with the checkpoint of
@@ -359,7 +371,8 @@ int rsrl_hip_set_td_weights(rsrl_hip_ctx* ctx, int64_t env_index, const float* v
  * load refuses a file whose header does not match the ctx's configuration or whose size is not exactly what the header
  * implies, and stages the data: a failing load leaves the ctx's weights untouched.  A loaded run's LEARNING resumes bit-identically (weights, traces,
  * backups, epsilons, step counter -- with the env states restored through rsrl_hip_set_states / _set_actions, the episodes' step counts through
- * rsrl_hip_set_episode_steps and, for the register-family loops, the carried Q(s,.) through rsrl_hip_set_q_carry: ABI 8); the evaluation-rollout draw
+ * rsrl_hip_set_episode_steps, for the register-family loops, the carried Q(s,.) through rsrl_hip_set_q_carry: ABI 8, and, for HIVTreatment,
+ * rsrl_hip_set_hidden_states); the evaluation-rollout draw
  * counter of rsrl_hip_rollout_policy is not part of the file (see there). */
 int rsrl_hip_save_weights(rsrl_hip_ctx* ctx, const char* path);
 int rsrl_hip_load_weights(rsrl_hip_ctx* ctx, const char* path);
@@ -423,7 +436,7 @@ int rsrl_hip_rollout_policy(rsrl_hip_ctx* ctx, int policy, double epsilon, doubl
                             float* rewards_out, uint8_t* terminal_out);
 
 /* Order-independent 64-bit checksums of the ctx's device state (sum of the 32-bit words, each multiplied by an odd
- * function of its index): out[0] weights (+traces), out[1] env states/actions/episode counters.  For determinism /
+ * function of its index): out[0] weights (+traces), out[1] env states/actions/episode counters (+ HIVTreatment's hidden states).  For determinism /
  * sharding / fusion-invariance checks at sizes where copying the weights out is not practical. */
 int rsrl_hip_checksum(rsrl_hip_ctx* ctx, uint64_t out[2]);
 

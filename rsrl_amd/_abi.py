@@ -50,6 +50,8 @@ SYMBOLS = {
     "rsrl_hip_reset": (C.c_int, [C.c_void_p]),
     "rsrl_hip_get_states": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rsrl_hip_set_states": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rsrl_hip_get_hidden_states": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rsrl_hip_set_hidden_states": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rsrl_hip_get_actions": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rsrl_hip_set_actions": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rsrl_hip_get_episode_steps": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _abi
 
-MOUNTAIN_CAR, CART_POLE, ACROBOT = 0, 1, 2
+MOUNTAIN_CAR, CART_POLE, ACROBOT, HIV_TREATMENT = 0, 1, 2, 3
 FOURIER, TILE_CODING = 0, 1
 QLEARNING, SARSA, EXPECTED_SARSA, SARSA_LAMBDA, Q_LAMBDA, PAL, GREEDY_GQ, TD, TD_LAMBDA, Q_SIGMA = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 TRACE_ACCUMULATE, TRACE_SATURATE, TRACE_DUTCH = 0, 1, 2
@@ -62,7 +62,7 @@ def device_count():
 class Context:
     """One object graph of the reference on one GPU, times `n_envs` independent environments in lock-step:
 
-        env    = MountainCar | CartPole | Acrobot ::default()                      (domain)
+        env    = MountainCar | CartPole | Acrobot | HIVTreatment ::default()                    (domain)
         basis  = Fourier::from_space(order, ..).with_bias() | TileCoding           (basis, order | n_tilings, tiles_per_dim)
         q_func = make_shared(LFA::vector(basis, SGD(lr), n_actions))               (lr; weight_mode: one per env or one shared)
         policy = Greedy | EpsilonGreedy(epsilon) | Softmax(tau) | Random           (policy, epsilon, tau)
@@ -153,6 +153,16 @@ class Context:
     @states.setter
     def states(self, v):
         _abi.check(self._L.rsrl_hip_set_states(self._h, _p(_in(v, np.float32, (self.D, self.N)))))
+
+    def get_hidden_states(self):
+        """HIVTreatment's hidden states [T1, T1*, T2, T2*, V, E], f64 (6, N); RsrlHipError on the other domains"""
+        out = np.empty((6, self.N), dtype=np.float64)
+        _abi.check(self._L.rsrl_hip_get_hidden_states(self._h, _p(out)))
+        return out
+
+    def set_hidden_states(self, y):
+        """set HIVTreatment's hidden states, f64 (6, N); the observations (`states`) follow"""
+        _abi.check(self._L.rsrl_hip_set_hidden_states(self._h, _p(_in(y, np.float64, (6, self.N)))))
 
     @property
     def actions(self):

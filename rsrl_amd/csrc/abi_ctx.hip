@@ -37,6 +37,7 @@ static AgentFamily classify(const rsrl_hip_config& cfg, size_t w_elems) {
     const bool fourier = cfg.basis == RSRL_FOURIER, tile = cfg.basis == RSRL_TILE_CODING;
     const bool wave = is_wave(cfg), reg = fourier && !wave && !is_generic_fourier(cfg);      // (reg: a register-family Fourier order)
     const int al = cfg.algo;
+    if (cfg.domain == RSRL_HIV_TREATMENT) return F::Hiv;
     if (cfg.weight_mode == RSRL_W_SHARED) return fourier ? F::SharedDense : (is_sparse_lambda(cfg) ? F::SharedSparseLambda : F::SharedTile);
     if (wave && is_wave_aux_algo(al)) return F::WaveAux;
     if (is_pred(al)) return tile ? F::TdTile : (reg ? F::TdReg : F::TdGeneric);
@@ -70,6 +71,7 @@ static const char* train_kernel_name(const rsrl_hip_ctx* c) {
     case AgentFamily::RegStep: return c->w_ls != 1 ? (c->k1_quad ? "k_step_reg_q4" : "k_step_reg_lm") : "k_step_reg";
     case AgentFamily::RegFused: return "k_train_reg";
     case AgentFamily::Generic: return "k_train_mem";
+    case AgentFamily::Hiv: return "k_hiv_train";
     }
     return "";
 }
@@ -132,6 +134,7 @@ int rsrl_hip_destroy(rsrl_hip_ctx* c) {
     if (c->qcache) (void)hipFree(c->qcache);
     if (c->tq_key) (void)hipFree(c->tq_key);
     if (c->Z) (void)hipFree(c->Z);
+    if (c->hiv_y) (void)hipFree(c->hiv_y);
     if (c->eps) (void)hipFree(c->eps);
     if (c->flags) (void)hipFree(c->flags);
     if (c->sp_keys) (void)hipFree(c->sp_keys);
@@ -159,7 +162,18 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
     case RSRL_MOUNTAIN_CAR: c->D = 2; c->A = 3; break;
     case RSRL_CART_POLE:    c->D = 4; c->A = 2; break;
     case RSRL_ACROBOT:      c->D = 4; c->A = 3; break;
+    case RSRL_HIV_TREATMENT: c->D = 6; c->A = 4; break;
     default: return fail(RSRL_HIP_EINVAL, "unknown domain %d", cfg->domain);
+    }
+    if (cfg->domain == RSRL_HIV_TREATMENT) {
+        // the kernels of train_hiv.hip: the one-step agents over the Fourier basis of order 1-3, per-learner f32 weights, one epsilon for the ctx
+        const int al = cfg->algo;
+        const bool one_step = al == RSRL_QLEARNING || al == RSRL_SARSA || al == RSRL_EXPECTED_SARSA || al == RSRL_PAL;
+        if (!one_step || cfg->basis != RSRL_FOURIER || cfg->order < 1 || cfg->order > 3 || cfg->weight_mode != RSRL_W_PER_ENV ||
+            cfg->weight_dtype != RSRL_W_F32 || cfg->epsilon_decay != 1.0)
+            return fail(RSRL_HIP_EINVAL, "HIVTreatment supports QLearning, SARSA, ExpectedSARSA and PAL on the Fourier basis of order 1-3 with per-learner "
+                                         "f32 weights and no epsilon schedule (got algo %d, basis %d, order %d, weight mode %d, dtype %d, epsilon_decay %g)",
+                        al, cfg->basis, cfg->order, cfg->weight_mode, cfg->weight_dtype, cfg->epsilon_decay);
     }
     if (cfg->n_envs < 1) return fail(RSRL_HIP_EINVAL, "n_envs must be >= 1");
     if (cfg->n_envs + cfg->env_offset > (int64_t)0xffffffffLL || cfg->env_offset < 0)
@@ -202,7 +216,7 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
     } else if (cfg->weight_dtype != RSRL_W_F32) {
         return fail(RSRL_HIP_EINVAL, "bf16 weights are available for Fourier order 7 on CartPole / Acrobot only");
     }
-    if (!is_wave(*cfg) && !model_supported(*cfg))
+    if (!is_wave(*cfg) && cfg->domain != RSRL_HIV_TREATMENT && !model_supported(*cfg))
         return fail(RSRL_HIP_EINVAL, "basis %d (order %d / %d tilings) on domain %d has no kernel yet", cfg->basis, cfg->order, cfg->n_tilings, cfg->domain);
     if (is_pred(cfg->algo)) {
         const bool tile_ok = cfg->basis == RSRL_TILE_CODING && cfg->weight_mode == RSRL_W_PER_ENV;
@@ -287,6 +301,7 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
     HIP_TRY(hipMalloc((void**)&c->W, c->w_bytes));
     HIP_TRY(hipMalloc((void**)&c->dW, sizeof(float) * c->dw_elems));
     HIP_TRY(hipMalloc((void**)&c->qcache, sizeof(float) * c->A * (size_t)N));
+    if (cfg->domain == RSRL_HIV_TREATMENT) HIP_TRY(hipMalloc((void**)&c->hiv_y, sizeof(double) * 6 * (size_t)N));      // (set by the domain reset of create)
     // the trait-granular fast path: learner-major per-learner f32 weights on a basis / agent kernels_trait.hpp is instantiated for, one epsilon for the ctx
     if (c->w_ls != 1 && cfg->weight_dtype == RSRL_W_F32 && cfg->epsilon_decay == 1.0 && trait_lm_available(cfg->domain, cfg->order, cfg->algo))
         HIP_TRY(hipMalloc((void**)&c->tq_key, sizeof(float) * c->D * (size_t)N));
@@ -409,7 +424,8 @@ int rsrl_hip_state_bounds(const rsrl_hip_ctx* c, double* lo, double* hi) {
         switch (c->cfg.domain) {
         case 0: lo[i] = Domain<0>::lo_d(i); hi[i] = Domain<0>::hi_d(i); break;
         case 1: lo[i] = Domain<1>::lo_d(i); hi[i] = Domain<1>::hi_d(i); break;
-        default: lo[i] = Domain<2>::lo_d(i); hi[i] = Domain<2>::hi_d(i); break;
+        case 2: lo[i] = Domain<2>::lo_d(i); hi[i] = Domain<2>::hi_d(i); break;
+        default: lo[i] = -5.0; hi[i] = 8.0; break;            // HIVTreatment: LIMITS of every observation component (hiv.rs:34, :137-145)
         }
     }
     return RSRL_HIP_OK;
@@ -418,6 +434,8 @@ int rsrl_hip_state_bounds(const rsrl_hip_ctx* c, double* lo, double* hi) {
 void state_limits(const rsrl_hip_ctx* c, float* lo, float* hi) {
     double l[8], h[8];
     (void)rsrl_hip_state_bounds(c, l, h);
+    // HIVTreatment: an observation outside its bounds is no observation (set_states inverts it through pow(10, obs))
+    if (c->hiv_y) { for (int d = 0; d < c->D; ++d) { lo[d] = (float)l[d]; hi[d] = (float)h[d]; } return; }
     for (int d = 0; d < c->D; ++d) { const double w = 1000.0 * (h[d] - l[d]); lo[d] = (float)(l[d] - w); hi[d] = (float)(h[d] + w); }
 }
 
@@ -458,7 +476,9 @@ int rsrl_hip_reset(rsrl_hip_ctx* c) {
     if (c->qs_len) HIP_TRY(hipMemsetAsync(c->qs_len, 0, sizeof(uint32_t) * (size_t)c->cfg.n_envs, c->stream));
     const Common k = make_common(c);
     const BasisGeom g = make_geom(c);
-    if (is_pred(c->cfg.algo)) {
+    if (c->family == AgentFamily::Hiv) {
+        launch_hiv_reset(c->stream, k, g, c->hiv_y, c->t);
+    } else if (is_pred(c->cfg.algo)) {
         if (!launch_reset_td(c->cfg.domain, dim3(grid_for(k.n_envs)), dim3(kBlock), c->stream, k, c->t)) return NO_MODEL(c);
     } else if (is_wave_family(c->family)) {
         for_wave(c, [&](auto tag) {
@@ -500,6 +520,26 @@ int rsrl_hip_set_states(rsrl_hip_ctx* c, const float* states) {
     }
     c->q_valid = false;
     HIP_TRY(hipMemcpyAsync(c->state, states, sizeof(float) * c->D * (size_t)c->cfg.n_envs, hipMemcpyDefault, c->stream));
+    if (c->hiv_y) { launch_hiv_emit(c->stream, c->hiv_y, c->state, c->cfg.n_envs, true); KCHECK(); }       // HIVTreatment: hidden state = 10^obs
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RSRL_HIP_OK;
+}
+int rsrl_hip_get_hidden_states(rsrl_hip_ctx* c, double* y) {
+    CHECK_CTX(c); FLUSH(c); if (!y) return fail(RSRL_HIP_EINVAL, "null argument");
+    if (!c->hiv_y) return fail(RSRL_HIP_EINVAL, "domain has no hidden state (domain %d): only HIVTreatment keeps one", c->cfg.domain);
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(hipMemcpyAsync(y, c->hiv_y, sizeof(double) * 6 * (size_t)c->cfg.n_envs, hipMemcpyDefault, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RSRL_HIP_OK;
+}
+int rsrl_hip_set_hidden_states(rsrl_hip_ctx* c, const double* y) {
+    CHECK_CTX(c); FLUSH(c); if (!y) return fail(RSRL_HIP_EINVAL, "null argument");
+    if (!c->hiv_y) return fail(RSRL_HIP_EINVAL, "domain has no hidden state (domain %d): only HIVTreatment keeps one", c->cfg.domain);
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    c->q_valid = false;
+    HIP_TRY(hipMemcpyAsync(c->hiv_y, y, sizeof(double) * 6 * (size_t)c->cfg.n_envs, hipMemcpyDefault, c->stream));
+    launch_hiv_emit(c->stream, c->hiv_y, c->state, c->cfg.n_envs, false);        // the observations follow
+    KCHECK();
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RSRL_HIP_OK;
 }

@@ -13,6 +13,7 @@ int rsrl_hip_comm_unique_id(uint8_t* id_bytes) {
 }
 int rsrl_hip_comm_init(rsrl_hip_ctx* c, const uint8_t* id_bytes, int world_size, int rank) {
     CHECK_CTX(c); FLUSH(c);
+    HIV_NO_EXCHANGE(c);
     if (!id_bytes || world_size < 1 || rank < 0 || rank >= world_size) return fail(RSRL_HIP_EINVAL, "bad communicator arguments");
     if (c->comm) return fail(RSRL_HIP_ESTATE, "communicator already initialised");
     if (c->cfg.weight_mode != RSRL_W_SHARED) return fail(RSRL_HIP_ESTATE, "per-env weights need no collective: shard by env_offset instead");
@@ -72,6 +73,7 @@ static uint64_t device_identity(int device) {
 static_assert(sizeof(PeerBlob) <= RSRL_HIP_PEER_HANDLE_BYTES, "peer handle blob must fit the ABI slot");
 int rsrl_hip_peer_export(rsrl_hip_ctx* c, int world_size, uint8_t* handle_out) {
     CHECK_CTX(c); FLUSH(c);
+    HIV_NO_EXCHANGE(c);
     if (!handle_out || world_size < 1 || world_size > 64) return fail(RSRL_HIP_EINVAL, "bad peer arguments");
     if (c->cfg.weight_mode != RSRL_W_SHARED) return fail(RSRL_HIP_ESTATE, "per-env weights need no exchange: shard by env_offset instead");
     if (c->cfg.exchange == RSRL_EXCHANGE_RCCL) return fail(RSRL_HIP_ESTATE, "this ctx was configured for the RCCL exchange: use rsrl_hip_comm_init");
@@ -127,6 +129,7 @@ int rsrl_hip_can_access_peer(int device, int peer_device) {
 }
 int rsrl_hip_peer_connect(rsrl_hip_ctx* c, const uint8_t* handles, int world_size, int rank) {
     CHECK_CTX(c); FLUSH(c);
+    HIV_NO_EXCHANGE(c);
     if (!handles || world_size < 1 || rank < 0 || rank >= world_size) return fail(RSRL_HIP_EINVAL, "bad peer arguments");
     if (!c->peer_recv || c->peer_world != world_size) return fail(RSRL_HIP_ESTATE, "call rsrl_hip_peer_export(world_size) first");
     if (c->multi) return fail(RSRL_HIP_ESTATE, "an exchange is already attached");
@@ -215,6 +218,7 @@ int rsrl_hip_group_create(rsrl_hip_ctx* const* ctxs, int n) {
         if (!c) return fail(RSRL_HIP_EINVAL, "null ctx in the group");
         for (int j = 0; j < i; ++j) if (ctxs[j] == c) return fail(RSRL_HIP_EINVAL, "ctx %d appears twice in the group", i);
         FLUSH(c);
+        HIV_NO_EXCHANGE(c);
         if (c->cfg.weight_mode != RSRL_W_SHARED) return fail(RSRL_HIP_ESTATE, "per-env weights need no exchange: shard by env_offset instead");
         if (c->multi || c->comm || c->peer_recv) return fail(RSRL_HIP_ESTATE, "ctx %d already has an exchange attached", i);
         if (c->cfg.exchange != ctxs[0]->cfg.exchange || c->dw_elems != ctxs[0]->dw_elems || c->cfg.basis != ctxs[0]->cfg.basis)

@@ -214,6 +214,8 @@ static inline int64_t fuse_depth(const rsrl_hip_ctx* c) {
     // 4 096 is a 2.9 ms launch at 65 536 learners
     switch (c->family) {
     case AgentFamily::TdReg: case AgentFamily::GqReg: case AgentFamily::LambdaReg: case AgentFamily::RegStep: case AgentFamily::RegFused: return 4096;
+    // HIVTreatment: one batch-step is 1 000 f64 RK4 sub-steps per learner, ~1 ms at 65 536 learners -- 16 keep a launch in the tens of milliseconds
+    case AgentFamily::Hiv: return 16;
     default: return 256;
     }
 }
@@ -428,6 +430,10 @@ int launch_agent(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, uint64_t 
             hipLaunchKernelGGL((k_train_mem<M>), grid, block, 0, c->stream, k, g, t, chunk, d_stats);
         });
         break;
+    case AgentFamily::Hiv:
+        if (io) launch_hiv_handle(c->stream, k, g, *io, t);
+        else launch_hiv_train(c->stream, k, g, c->hiv_y, t, chunk, d_stats);
+        break;
     default: ok = false; break;      // (the shared-W families: enqueue_shared_step)
     }
     if (!ok) return NO_MODEL(c);
@@ -605,7 +611,9 @@ static int rollout_impl(rsrl_hip_ctx* c, int64_t step_limit, int64_t M, uint32_t
     const TrajOut tr{os.dev, oa.dev, orw.dev, otm.dev, M};
     const Common k = make_common(c);
     const BasisGeom g = make_geom(c);
-    if (is_wave_family(c->family)) {
+    if (c->family == AgentFamily::Hiv) {
+        launch_hiv_rollout(c->stream, k, g, step_limit, on.dev, ot.dev, M, tr, rp);
+    } else if (is_wave_family(c->family)) {
         for_wave(c, [&](auto tag) {
             using T = decltype(tag); using WT = typename T::wt;
             hipLaunchKernelGGL((k_wave_rollout<T::domain, WT>), dim3(wave_grid_for(M)), dim3(kBlock), 0, c->stream, k, (const WT*)c->W, step_limit, on.dev, ot.dev, M, tr, rp);

@@ -15,6 +15,7 @@ int trait_cache_ready(rsrl_hip_ctx* c) {
 }
 int launch_domain_step(rsrl_hip_ctx* c, const Common& k, const int32_t* d_act, float* from, float* next, float* rew, uint8_t* term) {
     const dim3 g(grid_for(c->cfg.n_envs)), b(kBlock);
+    if (c->hiv_y) { launch_hiv_domain_step(c->stream, k, c->hiv_y, d_act, from, next, rew, term); KCHECK(); return RSRL_HIP_OK; }
     switch (c->cfg.domain) {
     case 0: hipLaunchKernelGGL(k_domain_step<0>, g, b, 0, c->stream, k, d_act, from, next, rew, term); break;
     case 1: hipLaunchKernelGGL(k_domain_step<1>, g, b, 0, c->stream, k, d_act, from, next, rew, term); break;
@@ -25,6 +26,7 @@ int launch_domain_step(rsrl_hip_ctx* c, const Common& k, const int32_t* d_act, f
 }
 int launch_domain_reset(rsrl_hip_ctx* c, const Common& k, const uint8_t* d_mask) {
     const dim3 g(grid_for(c->cfg.n_envs)), b(kBlock);
+    if (c->hiv_y) { launch_hiv_domain_reset(c->stream, k, c->hiv_y, d_mask); KCHECK(); return RSRL_HIP_OK; }
     switch (c->cfg.domain) {
     case 0: hipLaunchKernelGGL(k_domain_reset<0>, g, b, 0, c->stream, k, d_mask); break;
     case 1: hipLaunchKernelGGL(k_domain_reset<1>, g, b, 0, c->stream, k, d_mask); break;
@@ -149,6 +151,8 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
         default: ok = launch_v_evaluate(c->cfg.domain, c->cfg.order, dim3(grid_for(M_)), dim3(kBlock), c->stream, k, d_states, M_, of.dev); break;
         }
         if (!ok) return NO_MODEL(c);
+    } else if (c->family == AgentFamily::Hiv) {
+        launch_hiv_qop(c->stream, k, g, op, d_states, M_, call, of.dev, oi.dev, d_fin, d_iin);
     } else if (is_wave_family(c->family)) {
         for_wave(c, [&](auto tag) {
             using T = decltype(tag); using WT = typename T::wt;

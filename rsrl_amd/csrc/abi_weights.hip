@@ -441,6 +441,7 @@ int rsrl_hip_checksum(rsrl_hip_ctx* c, uint64_t out[2]) {
     run(c->state, sizeof(float) * c->D * N, 0, 1);
     run(c->action, sizeof(int32_t) * N, (size_t)1 << 36, 1);
     run(c->ep_step, sizeof(uint32_t) * N, (size_t)1 << 37, 1);
+    run(c->hiv_y, c->hiv_y ? sizeof(double) * 6 * N : 0, (size_t)1 << 38, 1);      // HIVTreatment's hidden states (f64: two words each)
     KCHECK();
     unsigned long long h[2];
     HIP_TRY(hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, c->stream));

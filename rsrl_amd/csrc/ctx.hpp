@@ -118,6 +118,7 @@ enum class AgentFamily : uint8_t {
     RegStep,              // register family, one batch-step per launch: k_step_reg / k_step_reg_lm / k_step_reg_q4
     RegFused,             // register family, fused loop: k_train_reg
     Generic,              // one-step agents on tile coding / generic Fourier orders, per-learner weights: k_train_mem
+    Hiv,                  // HIVTreatment (f64 hidden state): one-step agents, per-learner weights, Fourier orders 1-3: k_hiv_train (train_hiv.hip)
 };
 static inline bool is_wave_family(AgentFamily f) {
     return f == AgentFamily::WaveAux || f == AgentFamily::WaveQSigma || f == AgentFamily::WaveLambda || f == AgentFamily::WaveControl;
@@ -163,6 +164,7 @@ struct rsrl_hip_ctx {
     uint16_t* sp_keys = nullptr; float* sp_vals = nullptr; uint32_t* sp_len = nullptr;    // sparse traces: [N][kSparseCap] slice-relative keys (16 bit) and values, lengths [N][n_tilings]
     bool sp_lds = false;             //   one tiling's slice of the delta table fits LDS (k_sparse_trace_scatter)
     float* Z = nullptr;              // auxiliary matrix f32[A][F][N]: eligibility traces (lambda agents) / fa_td weights (GreedyGQ)
+    double* hiv_y = nullptr;         // HIVTreatment only: every learner's hidden state f64[6][N] (`state` holds its observation)
     bool q_valid = false;            // false whenever weights / states were changed from outside the driver loop
     // ---- the trait-granular fast path (kernels_trait.hpp): register-family Fourier basis, per-learner f32 weights, learner-major layout
     float* tq_key = nullptr;         // [D][N]: the state each learner's qcache entry belongs to (allocated iff the ctx takes the fast path)
@@ -349,6 +351,9 @@ static bool is_wave(const rsrl_hip_config& cfg) {
     return cfg.basis == RSRL_FOURIER && cfg.order == kWaveOrder && (cfg.domain == RSRL_CART_POLE || cfg.domain == RSRL_ACROBOT);
 }
 static inline unsigned wave_grid_for(int64_t items) { return (unsigned)((items + (kBlock / 64) - 1) / (kBlock / 64)); }
+// the HIVTreatment entry point of a multi-rank call: per-learner weights only, nothing to exchange
+#define HIV_NO_EXCHANGE(c) do { if ((c)->cfg.domain == RSRL_HIV_TREATMENT) return fail(RSRL_HIP_EINVAL, "HIVTreatment supports per-learner weights only: " \
+    "no communicator, peer exchange or group (shard by env_offset instead)"); } while (0)
 #define NO_MODEL(c) fail(RSRL_HIP_EINVAL, "no kernel for basis %d domain %d order %d tilings %d", (c)->cfg.basis, (c)->cfg.domain, (c)->cfg.order, (c)->cfg.n_tilings)
 
 // ---- host/device pointer staging ---------------------------------------------------------

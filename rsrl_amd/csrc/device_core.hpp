@@ -526,8 +526,7 @@ __device__ __forceinline__ void softmax_probs(const float (&q)[A], float tau, fl
     float m = q[0];
 #pragma unroll
     for (int i = 1; i < A; ++i) m = (q[i] > m) ? q[i] : m;
-    if (ulane >= 0) {
-        static_assert(A <= 3, "lane_pick3");
+    if constexpr (A <= 3) if (ulane >= 0) {                          // (lane_pick3: A <= 3; the wave-uniform callers all are)
         const float ql = lane_pick3(ulane, q[0], q[A > 1 ? 1 : 0], q[A > 2 ? 2 : 0]);
         const float el = exp_dev((ql - m) / tau);
         float z = 0.0f;

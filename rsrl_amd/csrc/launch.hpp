@@ -69,6 +69,21 @@ bool launch_v_model(const rsrl_hip_config& cfg, dim3 grid, dim3 block, hipStream
 bool launch_qsigma_model(const rsrl_hip_config& cfg, dim3 grid, dim3 block, hipStream_t st, const Common& k, const QsParams& qp, const BasisGeom& g, uint64_t t,
                          int chunk, DevStats* stats, const Transitions* io);
 
+// HIVTreatment (train_hiv.hip, kernels_hiv.hpp): one-step agents, per-learner f32 weights, Fourier orders 1-3.  Y = the hidden states f64[6][N]
+struct TrajOut;
+struct RolloutPolicy;
+void launch_hiv_reset(hipStream_t st, const Common& k, const BasisGeom& g, double* Y, uint64_t t);
+void launch_hiv_domain_step(hipStream_t st, const Common& k, double* Y, const int32_t* act, float* from, float* next, float* rew, uint8_t* term);
+void launch_hiv_domain_reset(hipStream_t st, const Common& k, double* Y, const uint8_t* mask);
+// state = emit(Y); from_obs: first Y = 10^state
+void launch_hiv_emit(hipStream_t st, double* Y, float* state, int64_t N, bool from_obs);
+void launch_hiv_qop(hipStream_t st, const Common& k, const BasisGeom& g, int op, const float* states, int64_t Mn, uint64_t call, float* fout, int32_t* iout,
+                    const float* fin, const int32_t* iin);
+void launch_hiv_handle(hipStream_t st, const Common& k, const BasisGeom& g, const Transitions& io, uint64_t t);
+void launch_hiv_train(hipStream_t st, const Common& k, const BasisGeom& g, double* Y, uint64_t t, int chunk, DevStats* stats);
+void launch_hiv_rollout(hipStream_t st, const Common& k, const BasisGeom& g, int64_t step_limit, uint32_t* n_states, float* total, int64_t Mn, const TrajOut& tr,
+                        const RolloutPolicy& rp);
+
 #define RSRL_TRAIN_CASE(DM, OR, AL, PO)                                                                     \
     if (order == OR && algo == AL && policy == PO) {                                                        \
         if (chunk == -3) {                                                                                  \

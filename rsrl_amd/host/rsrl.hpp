@@ -57,6 +57,7 @@ struct Domain { int kind; int64_t n_envs; };
 struct MountainCar : Domain { explicit MountainCar(int64_t n = 1) : Domain{RSRL_MOUNTAIN_CAR, n} {} };
 struct CartPole : Domain { explicit CartPole(int64_t n = 1) : Domain{RSRL_CART_POLE, n} {} };
 struct Acrobot : Domain { explicit Acrobot(int64_t n = 1) : Domain{RSRL_ACROBOT, n} {} };
+struct HIVTreatment : Domain { explicit HIVTreatment(int64_t n = 1) : Domain{RSRL_HIV_TREATMENT, n} {} };     // hiv.rs: f64 hidden state (rsrl_hip_get_hidden_states)
 }  // namespace domains
 
 // ---- rsrl::fa::linear ------------------------------------------------------------------------------
