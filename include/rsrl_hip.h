@@ -96,7 +96,21 @@ typedef enum { RSRL_QLEARNING = 0, RSRL_SARSA = 1, RSRL_EXPECTED_SARSA = 2, RSRL
                 * (q_sigma.rs:52-53 vs :113-114) -- so the library implements it with that one dead out-of-bounds read removed
                 * (rsrl_amd/csrc/kernels_qsigma.hpp).  Per-learner f32 weights on every basis: register-family and generic Fourier orders, tile
                 * coding, and (round 5) the order-7 wave family (one wavefront per learner, kernels_wave_aux.hpp k_wave_qsigma). */
-               RSRL_Q_SIGMA = 9 } rsrl_algo;
+               RSRL_Q_SIGMA = 9,
+               /* ActorCritic (control/ac.rs:49-115) with a Gibbs actor, policy = Gibbs::standard(LFA::vector(basis, SGD(1.0), A)) (softmax.rs:113-130,
+                * :154-163, :216-222), and the SARSA critic of examples/a2c.rs:22-67: SARSA{q_func = LFA::vector(basis, SGD(lr), A), policy, gamma}
+                * (sarsa.rs:43-73) handles each transition first -- its inner draw na ~ pi_theta(s') -- then the actor moves by
+                * theta[:,b] += alpha * c * (1[b==a] - p_b) * phi(s), p = softmax(theta^T phi(s) / tau) before the update (grad_log does not divide by tau,
+                * kept literally), c the critic's target with the UPDATED q_func:
+                *   RSRL_ACTOR_CRITIC     a2c.rs's closure (:38-49): c = Q(s,a) - sum_b Q(s,b) p_b
+                *   RSRL_Q_ACTOR_CRITIC   ActorCritic::qac, QCritic (ac.rs:23-31, :77-84): c = Q(s,a)
+                * config: lr = the critic's SGD rate, alpha = ActorCritic.alpha, gamma = SARSA.gamma, tau = Softmax.tau; policy must be RSRL_SOFTMAX and
+                * agent_policy -1 (the critic shares the actor).  Both matrices start at zero (LFA::vector).  The POLICY side of the ABI reads the actor's
+                * preferences theta^T phi(s) (policy_sample / _mode / _probs / _prob, reset's initial sample, the rollouts); the VALUE side reads the critic
+                * (q_evaluate, q_find_max / _min, q_expected_value, get / set_weights).  theta: rsrl_hip_get/set_policy_weights.  rsrl_hip_handle's
+                * td_error_out and the statistics' sum |delta| are the critic's.  Supported: per-learner f32 weights on the register-family Fourier orders
+                * (MountainCar 1-5, CartPole 1, Acrobot 1), no epsilon schedule; everything else is EINVAL at create (kernels_ac.hpp) */
+               RSRL_ACTOR_CRITIC = 10, RSRL_Q_ACTOR_CRITIC = 11 } rsrl_algo;
 /* rsrl::traces::{Accumulate, Saturate (Trace::replacing), Dutch}      traces.rs:188-240 */
 typedef enum { RSRL_TRACE_ACCUMULATE = 0, RSRL_TRACE_SATURATE = 1, RSRL_TRACE_DUTCH = 2 } rsrl_trace;
 /* rsrl::policies::{Greedy, EpsilonGreedy, Softmax, Random}
@@ -344,19 +358,24 @@ int rsrl_hip_set_traces(rsrl_hip_ctx* ctx, int64_t env_index, const float* z /*[
 /* the pub field `fa_td` of GreedyGQ (greedy_gq.rs:52): one learner's second approximator, row-major f32[F][A] */
 int rsrl_hip_get_td_weights(rsrl_hip_ctx* ctx, int64_t env_index, float* v /*[F][A]*/);
 int rsrl_hip_set_td_weights(rsrl_hip_ctx* ctx, int64_t env_index, const float* v /*[F][A]*/);
+/* the pub field `policy` of ActorCritic (ac.rs:61): the Gibbs actor's weights theta of one learner, row-major f32[F][A] like the weights.
+ * ESTATE on every ctx that is not an ActorCritic one (whose get/set_traces and get/set_td_weights are ESTATE in turn) */
+int rsrl_hip_get_policy_weights(rsrl_hip_ctx* ctx, int64_t env_index, float* theta /*[F][A]*/);
+int rsrl_hip_set_policy_weights(rsrl_hip_ctx* ctx, int64_t env_index, const float* theta /*[F][A]*/);
 /* Checkpoint of the approximator(s) (the reference's only persistence story is the optional serde
- * derive on the agents, rsrl/Cargo.toml:26).  File format version 2 (3 for files that carry QSigma's backups, 5 for sparse traces), little-endian,
+ * derive on the agents, rsrl/Cargo.toml:26).  File format version 2 (3 for files that carry QSigma's backups, 5 for sparse traces, 7 for ActorCritic), little-endian,
  * serialised field by field (no padding):
  *   offset  0  char magic[8] = "RSRLHIPW"
- *           8  u32  version = 2 (3 iff aux_kind = 3, 5 iff aux_kind = 4, 4 with the epsilon schedule)
+ *           8  u32  version = 2 (3 iff aux_kind = 3, 5 iff aux_kind = 4, 7 iff aux_kind = 5, 4 with the epsilon schedule)
  *          12  i32  domain, basis, order, n_tilings, tiles_per_dim, weight_mode, F, A (weight columns),
  *                   algo, weight_dtype, aux_kind (0 none, 1 eligibility traces, 2 GreedyGQ's fa_td weights,
- *                   3 QSigma's n-step backups, 4 sparse traces over a shared table)                             [11 x i32]
+ *                   3 QSigma's n-step backups, 4 sparse traces over a shared table, 5 ActorCritic's theta)      [11 x i32]
  *          56  i64  n_learners (1 in shared mode)
  *          64  u64  step_count
  *          72  n_learners x f32[F][A] weights in the reference's row-major (F, A) order (Parameterised::weights,
  *              params/mod.rs:118), independent of the device layout and storage dtype;
- *              then, if aux_kind is 1 or 2, n_learners x f32[F][A] of the auxiliary matrix (traces / fa_td);
+ *              then, if aux_kind is 1, 2 or 5, n_learners x f32[F][A] of the auxiliary matrix (traces / fa_td / the actor's theta; aux_kind 5 is
+ *              written as file version 7, which no other configuration reads);
  *              if aux_kind is 3 (file version 3): u32 head[N], u32 len[N], f32 entries[D + 5][n_steps][N] -- every learner's
  *              Backup ring {s, a, q, residual, pi, mu} (q_sigma.rs:30-63), so that a QSigma run with n_steps > 1 resumes
  *              bit-identically too.  Files of version 2 (no aux_kind 3) are still read.

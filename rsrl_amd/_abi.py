@@ -82,6 +82,8 @@ SYMBOLS = {
     "rsrl_hip_set_traces": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
     "rsrl_hip_get_td_weights": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
     "rsrl_hip_set_td_weights": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "rsrl_hip_get_policy_weights": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "rsrl_hip_set_policy_weights": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
     "rsrl_hip_train": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Stats)]),
     "rsrl_hip_step_count": (C.c_uint64, [C.c_void_p]),
     "rsrl_hip_pending_steps": (C.c_int64, [C.c_void_p]),

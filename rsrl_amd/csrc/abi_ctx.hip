@@ -38,6 +38,7 @@ static AgentFamily classify(const rsrl_hip_config& cfg, size_t w_elems) {
     const bool wave = is_wave(cfg), reg = fourier && !wave && !is_generic_fourier(cfg);      // (reg: a register-family Fourier order)
     const int al = cfg.algo;
     if (cfg.domain == RSRL_HIV_TREATMENT) return F::Hiv;
+    if (is_ac(al)) return F::AcReg;                         // (before the one-step agents: carries_q is false, no trait fast path)
     if (cfg.weight_mode == RSRL_W_SHARED) return fourier ? F::SharedDense : (is_sparse_lambda(cfg) ? F::SharedSparseLambda : F::SharedTile);
     if (wave && is_wave_aux_algo(al)) return F::WaveAux;
     if (is_pred(al)) return tile ? F::TdTile : (reg ? F::TdReg : F::TdGeneric);
@@ -72,6 +73,7 @@ static const char* train_kernel_name(const rsrl_hip_ctx* c) {
     case AgentFamily::RegFused: return "k_train_reg";
     case AgentFamily::Generic: return "k_train_mem";
     case AgentFamily::Hiv: return "k_hiv_train";
+    case AgentFamily::AcReg: return "k_train_ac";
     }
     return "";
 }
@@ -165,6 +167,17 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
     case RSRL_HIV_TREATMENT: c->D = 6; c->A = 4; break;
     default: return fail(RSRL_HIP_EINVAL, "unknown domain %d", cfg->domain);
     }
+    if (is_ac(cfg->algo)) {
+        // the kernels of train_ac.hip: per-learner f32 weights on the register-family Fourier orders; the Gibbs actor is the behaviour policy and the critic's
+        const bool reg = cfg->basis == RSRL_FOURIER && cfg->domain != RSRL_HIV_TREATMENT && cfg->order >= 1 && cfg->order <= 7 && !is_wave(*cfg) &&
+                         !is_generic_fourier(*cfg);
+        if (!reg || cfg->weight_mode != RSRL_W_PER_ENV || cfg->weight_dtype != RSRL_W_F32 || cfg->policy != RSRL_SOFTMAX || cfg->agent_policy != -1 ||
+            cfg->epsilon_decay != 1.0)
+            return fail(RSRL_HIP_EINVAL, "ActorCritic supports per-learner f32 weights on the register-family Fourier orders (MountainCar 1-5, CartPole 1, "
+                                         "Acrobot 1) with policy = Softmax (the Gibbs actor), agent_policy = -1 (the critic shares the actor) and no epsilon "
+                                         "schedule (got domain %d, basis %d, order %d, weight mode %d, dtype %d, policy %d, agent_policy %d, epsilon_decay %g)",
+                        cfg->domain, cfg->basis, cfg->order, cfg->weight_mode, cfg->weight_dtype, cfg->policy, cfg->agent_policy, cfg->epsilon_decay);
+    }
     if (cfg->domain == RSRL_HIV_TREATMENT) {
         // the kernels of train_hiv.hip: the one-step agents over the Fourier basis of order 1-3, per-learner f32 weights, one epsilon for the ctx
         const int al = cfg->algo;
@@ -178,7 +191,7 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
     if (cfg->n_envs < 1) return fail(RSRL_HIP_EINVAL, "n_envs must be >= 1");
     if (cfg->n_envs + cfg->env_offset > (int64_t)0xffffffffLL || cfg->env_offset < 0)
         return fail(RSRL_HIP_EINVAL, "global env ids must fit 32 bits");
-    if (cfg->algo < 0 || cfg->algo > RSRL_Q_SIGMA) return fail(RSRL_HIP_EINVAL, "unknown algo %d", cfg->algo);
+    if (cfg->algo < 0 || cfg->algo > RSRL_Q_ACTOR_CRITIC) return fail(RSRL_HIP_EINVAL, "unknown algo %d", cfg->algo);
     if (cfg->algo == RSRL_Q_SIGMA) {
         // any basis but the order-7 wave family: register-family Fourier, the generic Fourier orders, tile coding (per-learner tables)
         if (cfg->weight_mode != RSRL_W_PER_ENV) return fail(RSRL_HIP_EINVAL, "QSigma needs per-learner weights");
@@ -335,7 +348,7 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
     } else if (has_aux(cfg->algo)) {
         c->z_bytes = c->w_elems * 4;
         HIP_TRY(hipMalloc((void**)&c->Z, c->z_bytes));
-        HIP_TRY(hipMemsetAsync(c->Z, 0, c->z_bytes, c->stream));                  // Trace::zeros
+        HIP_TRY(hipMemsetAsync(c->Z, 0, c->z_bytes, c->stream));                  // Trace::zeros (ActorCritic's theta: LFA::vector zero-initialises)
     }
     if (shared) {
         HIP_TRY(hipMalloc((void**)&c->flags, (size_t)N));
@@ -474,7 +487,7 @@ int rsrl_hip_reset(rsrl_hip_ctx* c) {
     // QSigma: fresh episodes start from an empty n-step backup (as after a terminal transition, q_sigma.rs:154) -- entries of the
     // abandoned trajectories must not be mixed into the first anchor updates of the new ones
     if (c->qs_len) HIP_TRY(hipMemsetAsync(c->qs_len, 0, sizeof(uint32_t) * (size_t)c->cfg.n_envs, c->stream));
-    const Common k = make_common(c);
+    const Common k = make_policy_common(c);              // the initial policy.sample (ActorCritic: the actor's theta)
     const BasisGeom g = make_geom(c);
     if (c->family == AgentFamily::Hiv) {
         launch_hiv_reset(c->stream, k, g, c->hiv_y, c->t);

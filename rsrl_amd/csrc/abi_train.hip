@@ -213,7 +213,8 @@ static inline int64_t fuse_depth(const rsrl_hip_ctx* c) {
     // invocation (20-step calls, coalesced; scripts/gpu_r3_v6.sh): 1 024 -> 8.96e10, 2 048 -> 9.06e10, 4 096 -> 9.12e10, 8 192 -> 9.17e10 env-steps/s;
     // 4 096 is a 2.9 ms launch at 65 536 learners
     switch (c->family) {
-    case AgentFamily::TdReg: case AgentFamily::GqReg: case AgentFamily::LambdaReg: case AgentFamily::RegStep: case AgentFamily::RegFused: return 4096;
+    case AgentFamily::TdReg: case AgentFamily::GqReg: case AgentFamily::LambdaReg: case AgentFamily::RegStep: case AgentFamily::RegFused: case AgentFamily::AcReg:
+        return 4096;
     // HIVTreatment: one batch-step is 1 000 f64 RK4 sub-steps per learner, ~1 ms at 65 536 learners -- 16 keep a launch in the tens of milliseconds
     case AgentFamily::Hiv: return 16;
     default: return 256;
@@ -434,6 +435,9 @@ int launch_agent(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, uint64_t 
         if (io) launch_hiv_handle(c->stream, k, g, *io, t);
         else launch_hiv_train(c->stream, k, g, c->hiv_y, t, chunk, d_stats);
         break;
+    case AgentFamily::AcReg:
+        ok = launch_ac(cf.domain, cf.order, cf.algo == RSRL_Q_ACTOR_CRITIC ? AC_CRITIC_Q : AC_CRITIC_ADVANTAGE, grid, block, c->stream, k, c->Z, t, chunk, d_stats, io);
+        break;
     default: ok = false; break;      // (the shared-W families: enqueue_shared_step)
     }
     if (!ok) return NO_MODEL(c);
@@ -609,7 +613,7 @@ static int rollout_impl(rsrl_hip_ctx* c, int64_t step_limit, int64_t M, uint32_t
     if (oa.staged) HIP_TRY(hipMemsetAsync(oa.dev, 0, sizeof(int32_t) * oa.count, c->stream));
     if (orw.staged) HIP_TRY(hipMemsetAsync(orw.dev, 0, sizeof(float) * orw.count, c->stream));
     const TrajOut tr{os.dev, oa.dev, orw.dev, otm.dev, M};
-    const Common k = make_common(c);
+    const Common k = make_policy_common(c);             // Domain::rollout(|s| policy.mode(s) / .sample): ActorCritic's policy is the actor
     const BasisGeom g = make_geom(c);
     if (c->family == AgentFamily::Hiv) {
         launch_hiv_rollout(c->stream, k, g, step_limit, on.dev, ot.dev, M, tr, rp);

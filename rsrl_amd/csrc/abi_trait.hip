@@ -133,7 +133,9 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
     if (iin) TRY(check_host_actions(iin, (size_t)M_, c->A));
     TRY(stage_in(c, 3, fin, fin_count, &d_fin));
     TRY(stage_in(c, 4, iin, (size_t)M_, &d_iin));
-    const Common k = make_common(c);
+    // the policy's operations read the policy's weights (ActorCritic: the Gibbs actor's theta), the rest the action-value function
+    const bool policy_op = op == QOP_SAMPLE || op == QOP_SAMPLE_STEP || op == QOP_SAMPLE_INIT || op == QOP_MODE || op == QOP_PROBS || op == QOP_PROB_SA;
+    const Common k = policy_op ? make_policy_common(c) : make_common(c);
     const uint64_t call = (op == QOP_SAMPLE_STEP || op == QOP_SAMPLE_INIT) ? step_t : c->api_calls;      // (the driver loop's sample: addressed by the batch-step)
     if (op == QOP_SAMPLE) c->api_calls++;
     const BasisGeom g = make_geom(c);

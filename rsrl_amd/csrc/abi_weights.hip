@@ -106,6 +106,18 @@ int rsrl_hip_set_td_weights(rsrl_hip_ctx* c, int64_t env_index, const float* v) 
     if (c->cfg.algo != RSRL_GREEDY_GQ) return fail(RSRL_HIP_ESTATE, "only GreedyGQ has a second approximator (fa_td)");
     return traces_rw(c, env_index, nullptr, v);
 }
+int rsrl_hip_get_policy_weights(rsrl_hip_ctx* c, int64_t env_index, float* theta) {
+    if (!theta) return fail(RSRL_HIP_EINVAL, "null argument");
+    CHECK_CTX(c);
+    if (c->family != AgentFamily::AcReg) return fail(RSRL_HIP_ESTATE, "only ActorCritic has policy weights of its own (its policy reads Q otherwise)");
+    return traces_rw(c, env_index, theta, nullptr);
+}
+int rsrl_hip_set_policy_weights(rsrl_hip_ctx* c, int64_t env_index, const float* theta) {
+    if (!theta) return fail(RSRL_HIP_EINVAL, "null argument");
+    CHECK_CTX(c);
+    if (c->family != AgentFamily::AcReg) return fail(RSRL_HIP_ESTATE, "only ActorCritic has policy weights of its own (its policy reads Q otherwise)");
+    return traces_rw(c, env_index, nullptr, theta);
+}
 
 // ---- checkpoint: header + every learner's weights in the reference (F, A) order -----------------------------------
 // The header is serialised FIELD BY FIELD (little-endian, no implicit padding); layout in include/rsrl_hip.h.
@@ -114,6 +126,7 @@ constexpr uint32_t kCkptVersion = 3;          // files carrying aux_kind 3 (QSig
 constexpr uint32_t kCkptVersionEps = 4;       // ... or as version 4 when the ctx runs the per-learner epsilon schedule: f32 eps[N] follows the payload
 constexpr uint32_t kCkptVersionSparse = 6;    // files carrying aux_kind 4 (the sparse per-learner traces over a shared table): u64 n_envs, u64 env_offset, u32 len[N], lists
 constexpr uint32_t kCkptVersionSparse5 = 5;   // ... as round 5 wrote them (no n_envs / env_offset in front of the lengths): still read
+constexpr uint32_t kCkptVersionAc = 7;        // files carrying aux_kind 5 (ActorCritic's theta): laid out as aux_kind 1 / 2, a version of their own
 constexpr int64_t kSparseChunk = 4096;        // learners per staging chunk of the sparse lists
 constexpr size_t kCkptHeaderBytes = 72;
 struct Ckpt {
@@ -122,8 +135,13 @@ struct Ckpt {
     bool has_eps;                                 // (not a header field: the file version says it)
 };
 // 1 = eligibility traces, 2 = fa_td weights (both: a second matrix of W's shape), 3 = QSigma's per-learner n-step backups,
-// 4 = every learner's sparse trace over the shared table (the lists, compact)
-int aux_kind_of(const rsrl_hip_ctx* c) { return c->sp_keys ? 4 : (c->qs_buf ? 3 : (!c->Z ? 0 : (c->cfg.algo == RSRL_GREEDY_GQ ? 2 : 1))); }
+// 4 = every learner's sparse trace over the shared table (the lists, compact), 5 = ActorCritic's theta (a second matrix of W's shape)
+int aux_kind_of(const rsrl_hip_ctx* c) {
+    if (c->family == AgentFamily::AcReg) return 5;
+    return c->sp_keys ? 4 : (c->qs_buf ? 3 : (!c->Z ? 0 : (c->cfg.algo == RSRL_GREEDY_GQ ? 2 : 1)));
+}
+// aux_kinds whose payload is a second n_learners x f32[F][A] after the weights
+bool aux_is_matrix(int32_t kind) { return kind == 1 || kind == 2 || kind == 5; }
 size_t qs_floats(const rsrl_hip_ctx* c) { return (size_t)(c->D + 5) * (size_t)c->cfg.n_steps * (size_t)c->cfg.n_envs; }
 Ckpt ckpt_of(const rsrl_hip_ctx* c) {
     Ckpt h{};
@@ -141,7 +159,7 @@ uint64_t get64(const uint8_t*& p) { uint64_t v = 0; for (int i = 0; i < 8; ++i) 
 void ckpt_encode(const Ckpt& h, uint8_t (&buf)[kCkptHeaderBytes]) {
     uint8_t* p = buf;
     memcpy(p, "RSRLHIPW", 8); p += 8;
-    put32(p, h.has_eps ? kCkptVersionEps : (h.aux_kind == 4 ? kCkptVersionSparse : (h.aux_kind == 3 ? kCkptVersion : 2u)));
+    put32(p, h.has_eps ? kCkptVersionEps : (h.aux_kind == 5 ? kCkptVersionAc : (h.aux_kind == 4 ? kCkptVersionSparse : (h.aux_kind == 3 ? kCkptVersion : 2u))));
     const int32_t f[11] = {h.domain, h.basis, h.order, h.n_tilings, h.tiles_per_dim, h.weight_mode, h.F, h.A, h.algo, h.weight_dtype, h.aux_kind};
     for (int32_t v : f) put32(p, (uint32_t)v);
     put64(p, (uint64_t)h.n_learners); put64(p, h.step_count);
@@ -168,7 +186,7 @@ int rsrl_hip_save_weights(rsrl_hip_ctx* c, const char* path) {
     int rc = RSRL_HIP_OK;
     if (fwrite(hdr, 1, sizeof(hdr), f) != sizeof(hdr)) rc = fail(RSRL_HIP_EINVAL, "short write to %s", path);
     std::vector<float> w((size_t)c->F * c->Aw);
-    for (int pass = 0; pass < ((h.aux_kind == 1 || h.aux_kind == 2) ? 2 : 1); ++pass)            // every learner's weights, then every learner's auxiliary matrix
+    for (int pass = 0; pass < (aux_is_matrix(h.aux_kind) ? 2 : 1); ++pass)            // every learner's weights, then every learner's auxiliary matrix
         for (int64_t i = 0; rc == RSRL_HIP_OK && i < h.n_learners; ++i) {
             rc = pass == 0 ? rsrl_hip_get_weights(c, i, w.data()) : traces_rw(c, i, w.data(), nullptr);
             if (rc == RSRL_HIP_OK && fwrite(w.data(), sizeof(float), w.size(), f) != w.size()) rc = fail(RSRL_HIP_EINVAL, "short write to %s", path);
@@ -240,9 +258,13 @@ int rsrl_hip_load_weights(rsrl_hip_ctx* c, const char* path) {
     Ckpt h{}; uint32_t version = 0; uint8_t hdr[kCkptHeaderBytes];
     int rc = RSRL_HIP_OK;
     if (fread(hdr, 1, sizeof(hdr), f) != sizeof(hdr) || !ckpt_decode(hdr, &h, &version)) rc = fail(RSRL_HIP_EINVAL, "%s is not a rsrl_hip weight file", path);
-    else if (version != kCkptVersion && version != 2u && version != kCkptVersionEps && version != kCkptVersionSparse && version != kCkptVersionSparse5)
-        rc = fail(RSRL_HIP_EINVAL, "%s has checkpoint version %u, this library reads versions 2, %u, %u, %u and %u", path, version, kCkptVersion, kCkptVersionEps,
-                  kCkptVersionSparse5, kCkptVersionSparse);
+    else if (version != kCkptVersion && version != 2u && version != kCkptVersionEps && version != kCkptVersionSparse && version != kCkptVersionSparse5 &&
+             version != kCkptVersionAc)
+        rc = fail(RSRL_HIP_EINVAL, "%s has checkpoint version %u, this library reads versions 2, %u, %u, %u, %u and %u", path, version, kCkptVersion, kCkptVersionEps,
+                  kCkptVersionSparse5, kCkptVersionSparse, kCkptVersionAc);
+    // an ActorCritic file is version 7 with aux_kind 5 and nothing else is: any other pairing is not a file this library wrote
+    else if ((version == kCkptVersionAc) != (h.aux_kind == 5))
+        rc = fail(RSRL_HIP_EINVAL, "%s: checkpoint version %u with aux_kind %d is not a valid pairing", path, version, h.aux_kind);
     // a QSigma file written before the backups travelled (version 2, aux_kind 0) is still read: the weights are loaded and the run
     // resumes from EMPTY n-step backups, as after a terminal transition (q_sigma.rs:154)
     // (the same for a sparse-trace file of ABI 7's first build, version 2 / aux_kind 0: the run resumes from EMPTY lists, Trace::zeros)
@@ -258,7 +280,7 @@ int rsrl_hip_load_weights(rsrl_hip_ctx* c, const char* path) {
     std::vector<uint32_t> sp_len_in, sp_len_t;      // sparse traces: a learner's entries in the file; its sub-lists' lengths on the device
     long sp_prefix = 0;
     if (rc == RSRL_HIP_OK) {                                             // a truncated file is refused before anything is touched
-        long long expect = (long long)kCkptHeaderBytes + (long long)((h.aux_kind == 1 || h.aux_kind == 2) ? 2 : 1) * h.n_learners * (long long)per * 4 +
+        long long expect = (long long)kCkptHeaderBytes + (long long)(aux_is_matrix(h.aux_kind) ? 2 : 1) * h.n_learners * (long long)per * 4 +
                            (h.aux_kind == 3 ? (long long)c->cfg.n_envs * 8 + (long long)qs_floats(c) * 4 : 0) +
                            (h.has_eps ? (long long)c->cfg.n_envs * 4 : 0);
         if (h.aux_kind == 4) {                                           // the lists are compact: their lengths say how long the file is
@@ -300,7 +322,7 @@ int rsrl_hip_load_weights(rsrl_hip_ctx* c, const char* path) {
     }
     c->W = W_new; c->Z = Z_new;
     std::vector<float> w(per);
-    for (int pass = 0; pass < ((h.aux_kind == 1 || h.aux_kind == 2) ? 2 : 1); ++pass)
+    for (int pass = 0; pass < (aux_is_matrix(h.aux_kind) ? 2 : 1); ++pass)
         for (int64_t i = 0; rc == RSRL_HIP_OK && i < h.n_learners; ++i) {
             if (fread(w.data(), sizeof(float), per, f) != per) { rc = fail(RSRL_HIP_EINVAL, "%s: read error", path); break; }
             rc = pass == 0 ? rsrl_hip_set_weights(c, i, w.data()) : traces_rw(c, i, nullptr, w.data());

@@ -43,12 +43,14 @@
 #include "kernels_wave_aux.hpp"
 #include "kernels_sparse_lambda.hpp"
 #include "kernels_trait.hpp"
+#include "kernels_ac.hpp"
 
 using namespace rsrl;
 
 static inline bool is_lambda(int algo) { return algo == RSRL_SARSA_LAMBDA || algo == RSRL_Q_LAMBDA; }
 static inline bool is_pred(int algo) { return algo == RSRL_TD || algo == RSRL_TD_LAMBDA; }        // one weight column (V function)
-static inline bool has_aux(int algo) { return is_lambda(algo) || algo == RSRL_GREEDY_GQ || algo == RSRL_TD_LAMBDA; }   // second matrix of W's shape
+static inline bool is_ac(int algo) { return algo == RSRL_ACTOR_CRITIC || algo == RSRL_Q_ACTOR_CRITIC; }     // ActorCritic: theta is the second matrix
+static inline bool has_aux(int algo) { return is_lambda(algo) || algo == RSRL_GREEDY_GQ || algo == RSRL_TD_LAMBDA || is_ac(algo); }   // second matrix of W's shape
 
 // ---- the small kernels more than one unit launches, and the launches of kernel templates two units would otherwise both instantiate: defined ONCE, in
 // kernels_util.hip / launch_shared.hip (a kernel's host stub is an ordinary function: another unit launches it through this declaration)
@@ -119,6 +121,7 @@ enum class AgentFamily : uint8_t {
     RegFused,             // register family, fused loop: k_train_reg
     Generic,              // one-step agents on tile coding / generic Fourier orders, per-learner weights: k_train_mem
     Hiv,                  // HIVTreatment (f64 hidden state): one-step agents, per-learner weights, Fourier orders 1-3: k_hiv_train (train_hiv.hip)
+    AcReg,                // ActorCritic (both critics), register-family Fourier, per-learner f32 weights: k_train_ac (train_ac.hip); theta in Z
 };
 static inline bool is_wave_family(AgentFamily f) {
     return f == AgentFamily::WaveAux || f == AgentFamily::WaveQSigma || f == AgentFamily::WaveLambda || f == AgentFamily::WaveControl;
@@ -163,7 +166,7 @@ struct rsrl_hip_ctx {
     // lambda agents over ONE shared tile table: every learner's sparse trace + the step's mailbox (kernels_sparse_lambda.hpp)
     uint16_t* sp_keys = nullptr; float* sp_vals = nullptr; uint32_t* sp_len = nullptr;    // sparse traces: [N][kSparseCap] slice-relative keys (16 bit) and values, lengths [N][n_tilings]
     bool sp_lds = false;             //   one tiling's slice of the delta table fits LDS (k_sparse_trace_scatter)
-    float* Z = nullptr;              // auxiliary matrix f32[A][F][N]: eligibility traces (lambda agents) / fa_td weights (GreedyGQ)
+    float* Z = nullptr;              // auxiliary matrix f32[A][F][N]: eligibility traces (lambda agents) / fa_td weights (GreedyGQ) / the actor's theta (ActorCritic)
     double* hiv_y = nullptr;         // HIVTreatment only: every learner's hidden state f64[6][N] (`state` holds its observation)
     bool q_valid = false;            // false whenever weights / states were changed from outside the driver loop
     // ---- the trait-granular fast path (kernels_trait.hpp): register-family Fourier basis, per-learner f32 weights, learner-major layout
@@ -253,6 +256,14 @@ static Common make_common(const rsrl_hip_ctx* c) {
     k.qcache = c->qcache; k.q_valid = c->q_valid ? 1 : 0;
     k.eps = c->eps; k.eps_decay = (float)c->cfg.epsilon_decay; k.eps_min = (float)c->cfg.epsilon_min;
     k.xdelta = (int64_t)c->peer_seq - (int64_t)c->t;
+    return k;
+}
+
+// the weights the POLICY side reads: the actor's preferences theta for ActorCritic (the policy is Gibbs over theta, not over Q), W otherwise.
+// Policy::sample / mode / probabilities, reset's initial sample and the rollouts run the model kernels on it; the value side keeps make_common
+static Common make_policy_common(const rsrl_hip_ctx* c) {
+    Common k = make_common(c);
+    if (c->family == AgentFamily::AcReg) k.W = c->Z;
     return k;
 }
 

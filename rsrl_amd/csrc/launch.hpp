@@ -44,6 +44,11 @@ struct GqParams;
 bool launch_gq(int domain, int order, int policy, dim3 grid, dim3 block, hipStream_t st, const Common& k, const GqParams& gp, uint64_t t, int chunk,
                DevStats* stats, const Transitions* io);
 
+// ActorCritic (train_ac.hip, kernels_ac.hpp): theta = the actor's preferences f32[A][F][N]; critic = AC_CRITIC_ADVANTAGE / AC_CRITIC_Q.  io: handle at
+// batch-step t (the critic's inner draw), else chunk batch-steps of the driver loop from t
+bool launch_ac(int domain, int order, int critic, dim3 grid, dim3 block, hipStream_t st, const Common& k, float* theta, uint64_t t, int chunk,
+               DevStats* stats, const Transitions* io);
+
 bool launch_td(int domain, int order, bool lambda, dim3 grid, dim3 block, hipStream_t st, const Common& k, const TdParams& tp, uint64_t t, int chunk,
                DevStats* stats, const Transitions* io);
 bool launch_v_evaluate(int domain, int order, dim3 grid, dim3 block, hipStream_t st, const Common& k, const float* states, int64_t Mn, float* out);

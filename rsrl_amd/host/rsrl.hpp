@@ -111,6 +111,12 @@ struct Softmax : Policy {                 // Softmax::new(fa, tau) panics for |t
         if (tau_ < 1e-7 && tau_ > -1e-7) throw Error(RSRL_HIP_EINVAL, "Tau parameter in Softmax must be non-zero.");
     }
 };
+// Gibbs::standard(fa) = Softmax over the actor's OWN approximator with tau 1 (softmax.rs:46-61); the actor of ActorCritic, whose weights are
+// read through Session::policy_weights (its LFA's SGD rate never acts: ScaledGradientUpdate bypasses the optimiser, softmax.rs:216-222)
+struct Gibbs : Softmax {
+    explicit Gibbs(Shared<fa::linear::LFA> fa, double tau_ = 1.0) : Softmax(std::move(fa), tau_) {}
+    static Gibbs standard(Shared<fa::linear::LFA> fa) { return Gibbs(std::move(fa)); }
+};
 }  // namespace policies
 
 // ---- rsrl::control::td -----------------------------------------------------------------------------
@@ -174,6 +180,19 @@ struct GreedyGQ : Agent {
         : Agent{RSRL_GREEDY_GQ, std::move(fa_q), gamma, 1.0, RSRL_TRACE_ACCUMULATE, 0.0, fa_td.lr} {}
 };
 }}  // namespace control::td
+
+// ---- rsrl::control::ac: ActorCritic { critic, policy, alpha } with the Gibbs actor and a SARSA critic    (control/ac.rs:49-115, examples/a2c.rs)
+// critic: the SARSA evaluator (its q_func and gamma; it shares the actor as its policy, as the example does); the target is a2c.rs's closure
+// Q(s,a) - sum_b Q(s,b) pi(b|s), or Q(s,a) for ActorCritic::qac (QCritic).  The Session's policy must be the same Gibbs object.
+namespace control { namespace ac {
+struct ActorCritic : td::Agent {
+    ActorCritic(const td::SARSA& critic, const policies::Gibbs& /*policy*/, double alpha_)
+        : td::Agent{RSRL_ACTOR_CRITIC, critic.q_func, critic.gamma, alpha_} {}
+    static ActorCritic qac(const td::SARSA& critic, const policies::Gibbs& policy, double alpha_) {
+        ActorCritic a(critic, policy, alpha_); a.algo = RSRL_Q_ACTOR_CRITIC; return a;
+    }
+};
+}}  // namespace control::ac
 
 // ---- rsrl::prediction::td: TD { v_func, gamma } / TDLambda { fa_theta, trace, gamma }   (td.rs:25-30, td_lambda.rs:25-32)
 // The value function is a ScalarLFA (one weight column); drive these with policies::Random.
@@ -281,6 +300,10 @@ public:
     // the pub field `fa_td` of GreedyGQ                                             (greedy_gq.rs:52)
     std::vector<float> td_weights(int64_t env = 0) {
         std::vector<float> v((size_t)F_ * A_); check(rsrl_hip_get_td_weights(ctx_, env, v.data())); return v;
+    }
+    // the pub field `policy` of ActorCritic: the Gibbs actor's weights               (ac.rs:61)
+    std::vector<float> policy_weights(int64_t env = 0) {
+        std::vector<float> v((size_t)F_ * A_); check(rsrl_hip_get_policy_weights(ctx_, env, v.data())); return v;
     }
     // serde analogue: checkpoint of every learner's approximator(s)                  (rsrl/Cargo.toml:26)
     void save_weights(const std::string& path) { check(rsrl_hip_save_weights(ctx_, path.c_str())); }
