@@ -35,7 +35,7 @@ bool no_coalesce_switch() { return getenv("RSRL_NO_COALESCE") != nullptr; }
 static AgentFamily classify(const rsrl_hip_config& cfg, size_t w_elems) {
     using F = AgentFamily;
     const bool fourier = cfg.basis == RSRL_FOURIER, tile = cfg.basis == RSRL_TILE_CODING;
-    const bool wave = is_wave(cfg), reg = fourier && !wave && !is_generic_fourier(cfg);      // (reg: a register-family Fourier order)
+    const bool wave = is_wave(cfg), reg = is_reg_fourier(cfg);
     const int al = cfg.algo;
     if (cfg.domain == RSRL_HIV_TREATMENT) return F::Hiv;
     if (is_ac(al)) return F::AcReg;                         // (before the one-step agents: carries_q is false, no trait fast path)
@@ -158,118 +158,108 @@ int rsrl_hip_destroy(rsrl_hip_ctx* c) {
     return RSRL_HIP_OK;
 }
 
-static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
-    c->cfg = *cfg;
-    switch (cfg->domain) {
-    case RSRL_MOUNTAIN_CAR: c->D = 2; c->A = 3; break;
-    case RSRL_CART_POLE:    c->D = 4; c->A = 2; break;
-    case RSRL_ACROBOT:      c->D = 4; c->A = 3; break;
-    case RSRL_HIV_TREATMENT: c->D = 6; c->A = 4; break;
-    default: return fail(RSRL_HIP_EINVAL, "unknown domain %d", cfg->domain);
+// (state dimension, action count) of MountainCar, CartPole, Acrobot, HIVTreatment
+static const int kDomainShape[4][2] = {{2, 3}, {4, 2}, {4, 3}, {6, 4}};
+
+// admission: every rule that needs no device (a refused configuration is EINVAL on any machine, with or without a GPU).  create_impl checks
+// two more once the device is known: peer_timeout_ms, and the slice of a shared tile table with sparse traces.  The second section states
+// which kernels exist, one block per agent group; ActorCritic and HIVTreatment are whole rules of their own.
+static int check_config(const rsrl_hip_config& cfg) {
+    // ---- field ranges
+    if (cfg.domain < RSRL_MOUNTAIN_CAR || cfg.domain > RSRL_HIV_TREATMENT) return fail(RSRL_HIP_EINVAL, "unknown domain %d", cfg.domain);
+    const int D = kDomainShape[cfg.domain][0], A = kDomainShape[cfg.domain][1];
+    if (cfg.n_envs < 1) return fail(RSRL_HIP_EINVAL, "n_envs must be >= 1");
+    if (cfg.n_envs + cfg.env_offset > (int64_t)0xffffffffLL || cfg.env_offset < 0) return fail(RSRL_HIP_EINVAL, "global env ids must fit 32 bits");
+    if (cfg.algo < 0 || cfg.algo > RSRL_Q_ACTOR_CRITIC) return fail(RSRL_HIP_EINVAL, "unknown algo %d", cfg.algo);
+    if (cfg.policy < 0 || cfg.policy > RSRL_RANDOM) return fail(RSRL_HIP_EINVAL, "unknown policy %d", cfg.policy);
+    // Softmax::new panics for |tau| < 1e-7 (policies/softmax.rs:63-66)
+    if (cfg.policy == RSRL_SOFTMAX && std::fabs(cfg.tau) < 1e-7) return fail(RSRL_HIP_EINVAL, "Tau parameter in Softmax must be non-zero.");
+    if (cfg.weight_dtype != RSRL_W_F32 && cfg.weight_dtype != RSRL_W_BF16) return fail(RSRL_HIP_EINVAL, "unknown weight dtype %d", cfg.weight_dtype);
+    if (cfg.agent_policy < -1 || cfg.agent_policy > RSRL_RANDOM) return fail(RSRL_HIP_EINVAL, "unknown agent policy %d", cfg.agent_policy);
+    if (cfg.agent_policy == RSRL_SOFTMAX && std::fabs(cfg.agent_tau) < 1e-7) return fail(RSRL_HIP_EINVAL, "Tau parameter in Softmax must be non-zero.");
+    if (cfg.agent_policy == RSRL_EPSILON_GREEDY && !(cfg.agent_epsilon >= 0.0 && cfg.agent_epsilon <= 1.0))
+        return fail(RSRL_HIP_EINVAL, "agent_epsilon must be in [0,1]");
+    if (cfg.exchange != RSRL_EXCHANGE_RCCL && cfg.exchange != RSRL_EXCHANGE_PEER && cfg.exchange != RSRL_EXCHANGE_AUTO) return fail(RSRL_HIP_EINVAL, "unknown exchange %d", cfg.exchange);
+    const bool shared = cfg.weight_mode == RSRL_W_SHARED, per_env = cfg.weight_mode == RSRL_W_PER_ENV;
+    if (cfg.basis == RSRL_FOURIER) {
+        if (cfg.order < 1 || cfg.order > 7) return fail(RSRL_HIP_EINVAL, "Fourier order must be in [1, 7]");
+    } else if (cfg.basis == RSRL_TILE_CODING) {
+        if (cfg.tiles_per_dim < 1 || cfg.tiles_per_dim > 64) return fail(RSRL_HIP_EINVAL, "tiles_per_dim must be in [1, 64]");
+        int64_t cells = 1; for (int i = 0; i < D; ++i) cells *= cfg.tiles_per_dim;
+        if (cells > (int64_t)1 << 30 || cells * cfg.n_tilings > (int64_t)1 << 30) return fail(RSRL_HIP_EINVAL, "tile table too large");
+        // (a shared table is gathered through one 32-bit buffer descriptor)
+        if (shared && cells * cfg.n_tilings * A * 4 >= (int64_t)1 << 31) return fail(RSRL_HIP_EINVAL, "a shared tile table must be smaller than 2 GiB");
+    } else {
+        return fail(RSRL_HIP_EINVAL, "unknown basis %d", cfg.basis);
     }
-    if (is_ac(cfg->algo)) {
-        // the kernels of train_ac.hip: per-learner f32 weights on the register-family Fourier orders; the Gibbs actor is the behaviour policy and the critic's
-        const bool reg = cfg->basis == RSRL_FOURIER && cfg->domain != RSRL_HIV_TREATMENT && cfg->order >= 1 && cfg->order <= 7 && !is_wave(*cfg) &&
-                         !is_generic_fourier(*cfg);
-        if (!reg || cfg->weight_mode != RSRL_W_PER_ENV || cfg->weight_dtype != RSRL_W_F32 || cfg->policy != RSRL_SOFTMAX || cfg->agent_policy != -1 ||
-            cfg->epsilon_decay != 1.0)
+    if (cfg.algo == RSRL_TD_LAMBDA || is_lambda(cfg.algo)) {
+        if (cfg.trace < 0 || cfg.trace > RSRL_TRACE_DUTCH) return fail(RSRL_HIP_EINVAL, "unknown trace rule %d", cfg.trace);
+        if (!(cfg.lambda >= 0.0 && cfg.lambda <= 1.0)) return fail(RSRL_HIP_EINVAL, "lambda must be in [0, 1]");
+    }
+    if (cfg.algo == RSRL_Q_SIGMA) {
+        if (!(cfg.sigma >= 0.0 && cfg.sigma <= 1.0)) return fail(RSRL_HIP_EINVAL, "sigma must be in [0, 1]");
+        if (cfg.n_steps < 1 || cfg.n_steps > 32) return fail(RSRL_HIP_EINVAL, "n_steps must be in [1, 32]");
+    }
+    if (cfg.algo == RSRL_GREEDY_GQ && !(cfg.lr_td >= 0.0)) return fail(RSRL_HIP_EINVAL, "lr_td must be >= 0");
+    if (!(cfg.epsilon_decay > 0.0 && cfg.epsilon_decay <= 1.0)) return fail(RSRL_HIP_EINVAL, "epsilon_decay must be in (0, 1] (1 = no schedule)");
+    if (!(cfg.epsilon_min >= 0.0 && cfg.epsilon_min <= 1.0)) return fail(RSRL_HIP_EINVAL, "epsilon_min must be in [0, 1]");
+
+    // ---- which kernels exist
+    const int al = cfg.algo;
+    const bool tile = cfg.basis == RSRL_TILE_CODING, reg = is_reg_fourier(cfg), wave = is_wave(cfg);
+    const bool f32 = cfg.weight_dtype == RSRL_W_F32, esched = cfg.epsilon_decay != 1.0;
+    const bool one_step = al == RSRL_QLEARNING || al == RSRL_SARSA || al == RSRL_EXPECTED_SARSA || al == RSRL_PAL;
+    if (is_ac(al)) {
+        // train_ac.hip: per-learner f32 weights on the register-family Fourier orders; the Gibbs actor is the behaviour policy and the critic's
+        if (!reg || !per_env || !f32 || cfg.policy != RSRL_SOFTMAX || cfg.agent_policy != -1 || esched)
             return fail(RSRL_HIP_EINVAL, "ActorCritic supports per-learner f32 weights on the register-family Fourier orders (MountainCar 1-5, CartPole 1, "
                                          "Acrobot 1) with policy = Softmax (the Gibbs actor), agent_policy = -1 (the critic shares the actor) and no epsilon "
                                          "schedule (got domain %d, basis %d, order %d, weight mode %d, dtype %d, policy %d, agent_policy %d, epsilon_decay %g)",
-                        cfg->domain, cfg->basis, cfg->order, cfg->weight_mode, cfg->weight_dtype, cfg->policy, cfg->agent_policy, cfg->epsilon_decay);
+                        cfg.domain, cfg.basis, cfg.order, cfg.weight_mode, cfg.weight_dtype, cfg.policy, cfg.agent_policy, cfg.epsilon_decay);
+        return RSRL_HIP_OK;
     }
-    if (cfg->domain == RSRL_HIV_TREATMENT) {
-        // the kernels of train_hiv.hip: the one-step agents over the Fourier basis of order 1-3, per-learner f32 weights, one epsilon for the ctx
-        const int al = cfg->algo;
-        const bool one_step = al == RSRL_QLEARNING || al == RSRL_SARSA || al == RSRL_EXPECTED_SARSA || al == RSRL_PAL;
-        if (!one_step || cfg->basis != RSRL_FOURIER || cfg->order < 1 || cfg->order > 3 || cfg->weight_mode != RSRL_W_PER_ENV ||
-            cfg->weight_dtype != RSRL_W_F32 || cfg->epsilon_decay != 1.0)
+    if (cfg.domain == RSRL_HIV_TREATMENT) {
+        // train_hiv.hip: the one-step agents over the Fourier basis of order 1-3, per-learner f32 weights, one epsilon for the ctx
+        if (!one_step || tile || cfg.order > 3 || !per_env || !f32 || esched)
             return fail(RSRL_HIP_EINVAL, "HIVTreatment supports QLearning, SARSA, ExpectedSARSA and PAL on the Fourier basis of order 1-3 with per-learner "
                                          "f32 weights and no epsilon schedule (got algo %d, basis %d, order %d, weight mode %d, dtype %d, epsilon_decay %g)",
-                        al, cfg->basis, cfg->order, cfg->weight_mode, cfg->weight_dtype, cfg->epsilon_decay);
+                        al, cfg.basis, cfg.order, cfg.weight_mode, cfg.weight_dtype, cfg.epsilon_decay);
+        return RSRL_HIP_OK;
     }
-    if (cfg->n_envs < 1) return fail(RSRL_HIP_EINVAL, "n_envs must be >= 1");
-    if (cfg->n_envs + cfg->env_offset > (int64_t)0xffffffffLL || cfg->env_offset < 0)
-        return fail(RSRL_HIP_EINVAL, "global env ids must fit 32 bits");
-    if (cfg->algo < 0 || cfg->algo > RSRL_Q_ACTOR_CRITIC) return fail(RSRL_HIP_EINVAL, "unknown algo %d", cfg->algo);
-    if (cfg->algo == RSRL_Q_SIGMA) {
-        // any basis but the order-7 wave family: register-family Fourier, the generic Fourier orders, tile coding (per-learner tables)
-        if (cfg->weight_mode != RSRL_W_PER_ENV) return fail(RSRL_HIP_EINVAL, "QSigma needs per-learner weights");
-        if (!(cfg->sigma >= 0.0 && cfg->sigma <= 1.0)) return fail(RSRL_HIP_EINVAL, "sigma must be in [0, 1]");
-        if (cfg->n_steps < 1 || cfg->n_steps > 32) return fail(RSRL_HIP_EINVAL, "n_steps must be in [1, 32]");
-    }
-    if (cfg->policy < 0 || cfg->policy > RSRL_RANDOM) return fail(RSRL_HIP_EINVAL, "unknown policy %d", cfg->policy);
-    // Softmax::new panics for |tau| < 1e-7 (policies/softmax.rs:63-66)
-    if (cfg->policy == RSRL_SOFTMAX && std::fabs(cfg->tau) < 1e-7)
-        return fail(RSRL_HIP_EINVAL, "Tau parameter in Softmax must be non-zero.");
-    if (cfg->weight_dtype != RSRL_W_F32 && cfg->weight_dtype != RSRL_W_BF16) return fail(RSRL_HIP_EINVAL, "unknown weight dtype %d", cfg->weight_dtype);
-    if (cfg->agent_policy < -1 || cfg->agent_policy > RSRL_RANDOM) return fail(RSRL_HIP_EINVAL, "unknown agent policy %d", cfg->agent_policy);
-    if (cfg->agent_policy == RSRL_SOFTMAX && std::fabs(cfg->agent_tau) < 1e-7)
-        return fail(RSRL_HIP_EINVAL, "Tau parameter in Softmax must be non-zero.");
-    if (cfg->agent_policy == RSRL_EPSILON_GREEDY && !(cfg->agent_epsilon >= 0.0 && cfg->agent_epsilon <= 1.0))
-        return fail(RSRL_HIP_EINVAL, "agent_epsilon must be in [0,1]");
-    if (cfg->exchange != RSRL_EXCHANGE_RCCL && cfg->exchange != RSRL_EXCHANGE_PEER && cfg->exchange != RSRL_EXCHANGE_AUTO) return fail(RSRL_HIP_EINVAL, "unknown exchange %d", cfg->exchange);
-    if (cfg->basis == RSRL_FOURIER) {
-        if (cfg->order < 1 || cfg->order > 7) return fail(RSRL_HIP_EINVAL, "Fourier order must be in [1, 7]");
-        c->F = 1; for (int i = 0; i < c->D; ++i) c->F *= (cfg->order + 1);
-    } else if (cfg->basis == RSRL_TILE_CODING) {
-        if (cfg->tiles_per_dim < 1 || cfg->tiles_per_dim > 64) return fail(RSRL_HIP_EINVAL, "tiles_per_dim must be in [1, 64]");
-        int64_t cells = 1; for (int i = 0; i < c->D; ++i) cells *= cfg->tiles_per_dim;
-        if (cells * cfg->n_tilings > (int64_t)1 << 30) return fail(RSRL_HIP_EINVAL, "tile table too large");
-        // (a shared table is gathered through one 32-bit buffer descriptor)
-        if (cfg->weight_mode == RSRL_W_SHARED && cells * cfg->n_tilings * c->A * 4 >= (int64_t)1 << 31) return fail(RSRL_HIP_EINVAL, "a shared tile table must be smaller than 2 GiB");
-        c->F = (int)(cells * cfg->n_tilings);
-    } else {
-        return fail(RSRL_HIP_EINVAL, "unknown basis %d", cfg->basis);
-    }
-    if (cfg->weight_mode == RSRL_W_SHARED && !is_wave(*cfg) && is_generic_fourier(*cfg))
+    // the weight storage: one shared approximator on the register-family orders or tile coding; bf16 on the order-7 wave family
+    if (shared && wave) return fail(RSRL_HIP_EINVAL, "shared weights are not available for the order-7 wave family yet");
+    if (shared && !tile && !reg)
         return fail(RSRL_HIP_EINVAL, "shared weights need a register-family Fourier order (MountainCar 1-5, CartPole/Acrobot 1) or tile coding");
-    if (is_wave(*cfg)) {
-        if (cfg->weight_mode == RSRL_W_SHARED) return fail(RSRL_HIP_EINVAL, "shared weights are not available for the order-7 wave family yet");
-    } else if (cfg->weight_dtype != RSRL_W_F32) {
-        return fail(RSRL_HIP_EINVAL, "bf16 weights are available for Fourier order 7 on CartPole / Acrobot only");
+    if (!f32 && !wave) return fail(RSRL_HIP_EINVAL, "bf16 weights are available for Fourier order 7 on CartPole / Acrobot only");
+    if (!model_supported(cfg))
+        return fail(RSRL_HIP_EINVAL, "basis %d (order %d / %d tilings) on domain %d has no kernel yet", cfg.basis, cfg.order, cfg.n_tilings, cfg.domain);
+    // the agents
+    if (is_pred(al)) {
+        if (!per_env) return fail(RSRL_HIP_EINVAL, "the prediction agents (TD, TDLambda) need per-learner weights on a Fourier basis or on tile coding");
+        if (cfg.policy != RSRL_RANDOM) return fail(RSRL_HIP_EINVAL, "prediction agents have no Q function: the behaviour policy must be RSRL_RANDOM");
     }
-    if (!is_wave(*cfg) && cfg->domain != RSRL_HIV_TREATMENT && !model_supported(*cfg))
-        return fail(RSRL_HIP_EINVAL, "basis %d (order %d / %d tilings) on domain %d has no kernel yet", cfg->basis, cfg->order, cfg->n_tilings, cfg->domain);
-    if (is_pred(cfg->algo)) {
-        const bool tile_ok = cfg->basis == RSRL_TILE_CODING && cfg->weight_mode == RSRL_W_PER_ENV;
-        if (!tile_ok && (cfg->basis != RSRL_FOURIER || cfg->weight_mode != RSRL_W_PER_ENV))
-            return fail(RSRL_HIP_EINVAL, "the prediction agents (TD, TDLambda) need per-learner weights on a Fourier basis "
-                                         "or on tile coding");
-        if (cfg->policy != RSRL_RANDOM) return fail(RSRL_HIP_EINVAL, "prediction agents have no Q function: the behaviour policy must be RSRL_RANDOM");
-        if (cfg->algo == RSRL_TD_LAMBDA) {
-            if (cfg->trace < 0 || cfg->trace > RSRL_TRACE_DUTCH) return fail(RSRL_HIP_EINVAL, "unknown trace rule %d", cfg->trace);
-            if (!(cfg->lambda >= 0.0 && cfg->lambda <= 1.0)) return fail(RSRL_HIP_EINVAL, "lambda must be in [0, 1]");
-        }
-    }
-    if (cfg->algo == RSRL_GREEDY_GQ) {
-        if (cfg->weight_mode != RSRL_W_PER_ENV) return fail(RSRL_HIP_EINVAL, "GreedyGQ needs per-learner weights");
-        if (!(cfg->lr_td >= 0.0)) return fail(RSRL_HIP_EINVAL, "lr_td must be >= 0");
-    }
-    if (is_lambda(cfg->algo)) {
-        const bool tile_ok = cfg->basis == RSRL_TILE_CODING && cfg->weight_mode == RSRL_W_PER_ENV;     // dense per-learner trace tables
-        const bool wave_ok = cfg->basis == RSRL_FOURIER && is_wave(*cfg) && cfg->weight_mode == RSRL_W_PER_ENV;      // (f32, or bf16 + stochastic rounding: round 6)
-        // ... or sparse per-learner traces over ONE shared table (traces.rs:5-12 over params/sparse.rs; round 5)
-        const bool sparse_ok = is_sparse_lambda(*cfg) && (cfg->n_tilings == 4 || cfg->n_tilings == 8 || cfg->n_tilings == 16);
-        if (!tile_ok && !wave_ok && !sparse_ok && (cfg->basis != RSRL_FOURIER || is_wave(*cfg) || cfg->weight_mode != RSRL_W_PER_ENV))
-            return fail(RSRL_HIP_EINVAL, "the eligibility-trace agents need per-learner weights on a Fourier basis "
-                                         "or on tile coding (per-learner tables, or one shared table with sparse per-learner traces)");
-        if (cfg->trace < 0 || cfg->trace > RSRL_TRACE_DUTCH) return fail(RSRL_HIP_EINVAL, "unknown trace rule %d", cfg->trace);
-        if (!(cfg->lambda >= 0.0 && cfg->lambda <= 1.0)) return fail(RSRL_HIP_EINVAL, "lambda must be in [0, 1]");
-    }
-    if (!(cfg->epsilon_decay > 0.0 && cfg->epsilon_decay <= 1.0)) return fail(RSRL_HIP_EINVAL, "epsilon_decay must be in (0, 1] (1 = no schedule)");
-    if (!(cfg->epsilon_min >= 0.0 && cfg->epsilon_min <= 1.0)) return fail(RSRL_HIP_EINVAL, "epsilon_min must be in [0, 1]");
-    if (cfg->epsilon_decay != 1.0) {
-        // the kernels that run the schedule: k_train_reg<.., ESCHED>, k_train_lambda, k_train_mem
-        const bool reg = cfg->basis == RSRL_FOURIER && !is_wave(*cfg) && !is_generic_fourier(*cfg);
-        const bool one_step = cfg->algo == RSRL_QLEARNING || cfg->algo == RSRL_SARSA || cfg->algo == RSRL_EXPECTED_SARSA || cfg->algo == RSRL_PAL;
-        // (round 6: + the order-7 wave family -- k_train_wave / k_train_wave_pk <.., ESCHED>, k_wave_lambda -- f32 and bf16)
-        const bool ok = cfg->policy == RSRL_EPSILON_GREEDY && cfg->weight_mode == RSRL_W_PER_ENV && cfg->steps_per_launch != 1 &&
-                        (((reg || is_wave(*cfg)) && (one_step || is_lambda(cfg->algo))) || (!reg && !is_wave(*cfg) && one_step));
-        if (!ok) return fail(RSRL_HIP_EINVAL, "epsilon_decay (the per-learner epsilon schedule) needs policy = EpsilonGreedy, per-learner weights, steps_per_launch != 1 and "
-                                              "a one-step agent or SARSALambda / QLambda on a register-family or order-7 wave-family Fourier basis, or a one-step agent on "
-                                              "tile coding / a generic Fourier order");
-    }
+    if (al == RSRL_GREEDY_GQ && !per_env) return fail(RSRL_HIP_EINVAL, "GreedyGQ needs per-learner weights");
+    if (al == RSRL_Q_SIGMA && !per_env) return fail(RSRL_HIP_EINVAL, "QSigma needs per-learner weights");
+    // SARSALambda / QLambda: dense per-learner traces on any basis (the wave family: f32, or bf16 + stochastic rounding), or sparse per-learner
+    // traces over ONE shared tile table (traces.rs:5-12 over params/sparse.rs; its tilings 4, 8 or 16 as every tile model's)
+    if (is_lambda(al) && !per_env && !is_sparse_lambda(cfg))
+        return fail(RSRL_HIP_EINVAL, "the eligibility-trace agents need per-learner weights on a Fourier basis "
+                                     "or on tile coding (per-learner tables, or one shared table with sparse per-learner traces)");
+    // the per-learner epsilon schedule: k_train_reg<.., ESCHED>, k_train_lambda, k_train_mem, k_train_wave / k_train_wave_pk <.., ESCHED>, k_wave_lambda
+    if (esched && !(cfg.policy == RSRL_EPSILON_GREEDY && per_env && cfg.steps_per_launch != 1 && (one_step || (is_lambda(al) && (reg || wave)))))
+        return fail(RSRL_HIP_EINVAL, "epsilon_decay (the per-learner epsilon schedule) needs policy = EpsilonGreedy, per-learner weights, steps_per_launch != 1 and "
+                                     "a one-step agent or SARSALambda / QLambda on a register-family or order-7 wave-family Fourier basis, or a one-step agent on "
+                                     "tile coding / a generic Fourier order");
+    return RSRL_HIP_OK;
+}
+
+static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
+    TRY(check_config(*cfg));
+    c->cfg = *cfg;
+    c->D = kDomainShape[cfg->domain][0]; c->A = kDomainShape[cfg->domain][1];
+    c->F = 1;
+    for (int i = 0; i < c->D; ++i) c->F *= cfg->basis == RSRL_FOURIER ? cfg->order + 1 : cfg->tiles_per_dim;
+    if (cfg->basis == RSRL_TILE_CODING) c->F *= cfg->n_tilings;
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (ndev < 1) return fail(RSRL_HIP_EHIP, "no HIP device");

@@ -333,24 +333,21 @@ static inline float tile_lsb(float lr) {
 constexpr int kSharedBlock = 512;    // learners per block of k_shared_step: 256 blocks = one per CU for a 131 072-env shard
 
 // ---- (basis, domain, parameter) -> Model type: model_list.hpp
-static bool is_generic_fourier(const rsrl_hip_config& cfg) {
-    if (cfg.basis != RSRL_FOURIER) return false;
-#define X(TYPE, BS, DM, P) if (P != -1 && model_match(cfg, BS, DM, P)) return false;
-    RSRL_MODELS(X)
-#undef X
-    return true;
-}
 static bool model_supported(const rsrl_hip_config& cfg) {
+    if (is_reg_fourier(cfg)) return true;
 #define X(TYPE, BS, DM, P) if (model_match(cfg, BS, DM, P)) return true;
-    RSRL_MODELS(X)
+    RSRL_MEM_MODELS(X)
 #undef X
     return false;
 }
-// calls fn(Tag<Model>{}) for the ctx's model; false if none matches
+// calls fn(Tag<Model>{}) for the ctx's model, first match; false if none matches
 template <class Fn>
 static bool for_model(const rsrl_hip_ctx* c, Fn&& fn) {
+#define X(DM, OR) if (model_match(c->cfg, RSRL_FOURIER, DM, OR)) { fn(Tag<FourierModel<DM, OR>>{}); return true; }
+    RSRL_REG_FOURIER(X)
+#undef X
 #define X(TYPE, BS, DM, P) if (model_match(c->cfg, BS, DM, P)) { fn(Tag<RSRL_UNPAREN TYPE>{}); return true; }
-    RSRL_MODELS(X)
+    RSRL_MEM_MODELS(X)
 #undef X
     return false;
 }

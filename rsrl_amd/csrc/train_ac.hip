@@ -4,6 +4,7 @@
 // kernel's machine code moves.
 #include "launch.hpp"
 #include "kernels_ac.hpp"
+#include "model_list.hpp"
 
 namespace rsrl {
 
@@ -18,8 +19,7 @@ namespace rsrl {
 
 bool launch_ac(int domain, int order, int critic, dim3 grid, dim3 block, hipStream_t st, const Common& k, float* theta, uint64_t t, int chunk,
                DevStats* stats, const Transitions* io) {
-    RSRL_AC_CRITICS(0, 1) RSRL_AC_CRITICS(0, 2) RSRL_AC_CRITICS(0, 3) RSRL_AC_CRITICS(0, 4) RSRL_AC_CRITICS(0, 5)
-    RSRL_AC_CRITICS(1, 1) RSRL_AC_CRITICS(2, 1)
+    RSRL_REG_FOURIER(RSRL_AC_CRITICS)
     return false;
 }
 

@@ -19,11 +19,10 @@ namespace rsrl {
 bool launch_gq(int domain, int order, int policy, dim3 grid, dim3 block, hipStream_t st, const Common& k, const GqParams& gp, uint64_t t, int chunk,
                DevStats* stats, const Transitions* io) {
     if (io) {
-        RSRL_HGQ_CASE(0, 1) RSRL_HGQ_CASE(0, 2) RSRL_HGQ_CASE(0, 3) RSRL_HGQ_CASE(0, 4) RSRL_HGQ_CASE(0, 5) RSRL_HGQ_CASE(1, 1) RSRL_HGQ_CASE(2, 1)
+        RSRL_REG_FOURIER(RSRL_HGQ_CASE)
         return false;
     }
-    RSRL_GQ_POLICIES(0, 1) RSRL_GQ_POLICIES(0, 2) RSRL_GQ_POLICIES(0, 3) RSRL_GQ_POLICIES(0, 4) RSRL_GQ_POLICIES(0, 5)
-    RSRL_GQ_POLICIES(1, 1) RSRL_GQ_POLICIES(2, 1)
+    RSRL_REG_FOURIER(RSRL_GQ_POLICIES)
     return false;
 }
 // GreedyGQ on the models without a register-family kernel (tile coding, generic Fourier orders)

@@ -2,6 +2,7 @@
 #include "launch.hpp"
 #include "kernels_lambda.hpp"
 #include "kernels_lambda_mem.hpp"
+#include "model_list.hpp"
 namespace rsrl {
 
 #define RSRL_LAMBDA_CASE(DM, OR, AL, PO)                                                                      \
@@ -21,11 +22,10 @@ namespace rsrl {
 bool launch_lambda(int domain, int order, int algo, int policy, dim3 grid, dim3 block, hipStream_t st, const Common& k, const LambdaParams& lp,
                    uint64_t t, int chunk, DevStats* stats, const Transitions* io) {
     if (io) {
-        RSRL_HL_CASE(0, 1) RSRL_HL_CASE(0, 2) RSRL_HL_CASE(0, 3) RSRL_HL_CASE(0, 4) RSRL_HL_CASE(0, 5) RSRL_HL_CASE(1, 1) RSRL_HL_CASE(2, 1)
+        RSRL_REG_FOURIER(RSRL_HL_CASE)
         return false;
     }
-    RSRL_LAMBDA_ALGOS(0, 1) RSRL_LAMBDA_ALGOS(0, 2) RSRL_LAMBDA_ALGOS(0, 3) RSRL_LAMBDA_ALGOS(0, 4) RSRL_LAMBDA_ALGOS(0, 5)
-    RSRL_LAMBDA_ALGOS(1, 1) RSRL_LAMBDA_ALGOS(2, 1)
+    RSRL_REG_FOURIER(RSRL_LAMBDA_ALGOS)
     return false;
 }
 // SARSALambda / QLambda on the generic Fourier orders (kernels_lambda_mem.hpp); the driver loop runs four threads per learner, 64 learners per block

@@ -12,7 +12,7 @@ namespace rsrl {
     }
 bool launch_qsigma(int domain, int order, dim3 grid, dim3 block, hipStream_t st, const Common& k, const QsParams& qp, const BasisGeom& g, uint64_t t,
                    int chunk, DevStats* stats, const Transitions* io) {
-    RSRL_QS_CASE(0, 1) RSRL_QS_CASE(0, 2) RSRL_QS_CASE(0, 3) RSRL_QS_CASE(0, 4) RSRL_QS_CASE(0, 5) RSRL_QS_CASE(1, 1) RSRL_QS_CASE(2, 1)
+    RSRL_REG_FOURIER(RSRL_QS_CASE)
     return false;
 }
 // ... and on every other model (tile coding with per-learner tables, the generic Fourier orders): the agent is generic over the

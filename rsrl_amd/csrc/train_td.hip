@@ -1,6 +1,7 @@
 // prediction (TD / TDLambda) kernels of the register family
 #include "launch.hpp"
 #include "kernels_td.hpp"
+#include "model_list.hpp"
 namespace rsrl {
 
 #define RSRL_TD_CASE(DM, OR)                                                                                        \
@@ -17,10 +18,10 @@ namespace rsrl {
 bool launch_td(int domain, int order, bool lambda, dim3 grid, dim3 block, hipStream_t st, const Common& k, const TdParams& tp, uint64_t t, int chunk,
                DevStats* stats, const Transitions* io) {
     if (io) {
-        RSRL_HTD_CASE(0, 1) RSRL_HTD_CASE(0, 2) RSRL_HTD_CASE(0, 3) RSRL_HTD_CASE(0, 4) RSRL_HTD_CASE(0, 5) RSRL_HTD_CASE(1, 1) RSRL_HTD_CASE(2, 1)
+        RSRL_REG_FOURIER(RSRL_HTD_CASE)
         return false;
     }
-    RSRL_TD_CASE(0, 1) RSRL_TD_CASE(0, 2) RSRL_TD_CASE(0, 3) RSRL_TD_CASE(0, 4) RSRL_TD_CASE(0, 5) RSRL_TD_CASE(1, 1) RSRL_TD_CASE(2, 1)
+    RSRL_REG_FOURIER(RSRL_TD_CASE)
     return false;
 }
 #define RSRL_VEV_CASE(DM, OR)                                                                            \
@@ -29,7 +30,7 @@ bool launch_td(int domain, int order, bool lambda, dim3 grid, dim3 block, hipStr
         return true;                                                                                     \
     }
 bool launch_v_evaluate(int domain, int order, dim3 grid, dim3 block, hipStream_t st, const Common& k, const float* states, int64_t Mn, float* out) {
-    RSRL_VEV_CASE(0, 1) RSRL_VEV_CASE(0, 2) RSRL_VEV_CASE(0, 3) RSRL_VEV_CASE(0, 4) RSRL_VEV_CASE(0, 5) RSRL_VEV_CASE(1, 1) RSRL_VEV_CASE(2, 1)
+    RSRL_REG_FOURIER(RSRL_VEV_CASE)
     return false;
 }
 // TD / TDLambda on the generic Fourier orders: io != nullptr -> handle, else the driver loop
