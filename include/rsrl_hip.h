@@ -110,7 +110,20 @@ typedef enum { RSRL_QLEARNING = 0, RSRL_SARSA = 1, RSRL_EXPECTED_SARSA = 2, RSRL
                 * (q_evaluate, q_find_max / _min, q_expected_value, get / set_weights).  theta: rsrl_hip_get/set_policy_weights.  rsrl_hip_handle's
                 * td_error_out and the statistics' sum |delta| are the critic's.  Supported: per-learner f32 weights on the register-family Fourier orders
                 * (MountainCar 1-5, CartPole 1, Acrobot 1), no epsilon schedule; everything else is EINVAL at create (kernels_ac.hpp) */
-               RSRL_ACTOR_CRITIC = 10, RSRL_Q_ACTOR_CRITIC = 11 } rsrl_algo;
+               RSRL_ACTOR_CRITIC = 10, RSRL_Q_ACTOR_CRITIC = 11,
+               /* (12 is no algo.)  ActorCritic::tdac (ac.rs:32-52, :87-98): the same Gibbs actor with TDCritic over a state-value function V, the loop of
+                * examples/tdac.rs with the project's TD(0) prediction agent as its `eval` (TD{v_func = ScalarLFA(basis, SGD(lr)), gamma},
+                * prediction/td/td.rs:31-59; tdac.rs uses iLSTD).  Per transition (s, a, r, s', term), p = softmax(theta^T phi(s) / tau) before the update:
+                *   TD(0)   delta = r - V(s) (terminal) | r + gamma*V(s') - V(s);   w += lr*delta*phi(s)        (bit for bit a RSRL_TD ctx's w and delta)
+                *   critic  c = r - V'(s') (terminal: V of the terminal state s' itself) | r + gamma*V'(s') - V'(s), V' with the UPDATED w
+                *   actor   theta[:,b] += alpha * c * (1[b==a] - p_b) * phi(s)
+                * No inner draw.  config: lr = V's SGD rate, gamma = TD's and TDCritic's, alpha = ActorCritic.alpha, tau = Softmax.tau; policy must be
+                * RSRL_SOFTMAX and agent_policy -1.  Both start at zero.  The VALUE side is V, as for the prediction agents: q_evaluate writes f32[1][M],
+                * get / set_weights are [F][1], n_outputs is 1, q_find_max / _min / q_expected_value are ESTATE.  The POLICY side reads theta [F][A]
+                * (policy_sample / _mode / _probs / _prob, reset's initial sample, the rollouts; rsrl_hip_get/set_policy_weights).  rsrl_hip_handle's
+                * td_error_out and the statistics' sum |delta| are TD(0)'s delta.  Supported: as RSRL_ACTOR_CRITIC; everything else is EINVAL at create
+                * (kernels_tdac.hpp) */
+               RSRL_TD_ACTOR_CRITIC = 13 } rsrl_algo;
 /* rsrl::traces::{Accumulate, Saturate (Trace::replacing), Dutch}      traces.rs:188-240 */
 typedef enum { RSRL_TRACE_ACCUMULATE = 0, RSRL_TRACE_SATURATE = 1, RSRL_TRACE_DUTCH = 2 } rsrl_trace;
 /* rsrl::policies::{Greedy, EpsilonGreedy, Softmax, Random}
@@ -358,24 +371,29 @@ int rsrl_hip_set_traces(rsrl_hip_ctx* ctx, int64_t env_index, const float* z /*[
 /* the pub field `fa_td` of GreedyGQ (greedy_gq.rs:52): one learner's second approximator, row-major f32[F][A] */
 int rsrl_hip_get_td_weights(rsrl_hip_ctx* ctx, int64_t env_index, float* v /*[F][A]*/);
 int rsrl_hip_set_td_weights(rsrl_hip_ctx* ctx, int64_t env_index, const float* v /*[F][A]*/);
-/* the pub field `policy` of ActorCritic (ac.rs:61): the Gibbs actor's weights theta of one learner, row-major f32[F][A] like the weights.
+/* the pub field `policy` of ActorCritic (ac.rs:61): the Gibbs actor's weights theta of one learner, row-major f32[F][A] like the weights
+ * (RSRL_TD_ACTOR_CRITIC: f32[F][n_actions], while its weights are V's f32[F][1]).
  * ESTATE on every ctx that is not an ActorCritic one (whose get/set_traces and get/set_td_weights are ESTATE in turn) */
 int rsrl_hip_get_policy_weights(rsrl_hip_ctx* ctx, int64_t env_index, float* theta /*[F][A]*/);
 int rsrl_hip_set_policy_weights(rsrl_hip_ctx* ctx, int64_t env_index, const float* theta /*[F][A]*/);
 /* Checkpoint of the approximator(s) (the reference's only persistence story is the optional serde
- * derive on the agents, rsrl/Cargo.toml:26).  File format version 2 (3 for files that carry QSigma's backups, 5 for sparse traces, 7 for ActorCritic), little-endian,
+ * derive on the agents, rsrl/Cargo.toml:26).  File format version 2 (3 for files that carry QSigma's backups, 5 for sparse traces, 7 for ActorCritic, 8 for the TD ActorCritic),
+ * little-endian,
  * serialised field by field (no padding):
  *   offset  0  char magic[8] = "RSRLHIPW"
- *           8  u32  version = 2 (3 iff aux_kind = 3, 5 iff aux_kind = 4, 7 iff aux_kind = 5, 4 with the epsilon schedule)
+ *           8  u32  version = 2 (3 iff aux_kind = 3, 5 iff aux_kind = 4, 7 iff aux_kind = 5, 8 iff aux_kind = 6, 4 with the epsilon schedule)
  *          12  i32  domain, basis, order, n_tilings, tiles_per_dim, weight_mode, F, A (weight columns),
  *                   algo, weight_dtype, aux_kind (0 none, 1 eligibility traces, 2 GreedyGQ's fa_td weights,
- *                   3 QSigma's n-step backups, 4 sparse traces over a shared table, 5 ActorCritic's theta)      [11 x i32]
+ *                   3 QSigma's n-step backups, 4 sparse traces over a shared table, 5 ActorCritic's theta,
+ *                   6 the TD ActorCritic's theta)                                                                 [11 x i32]
  *          56  i64  n_learners (1 in shared mode)
  *          64  u64  step_count
  *          72  n_learners x f32[F][A] weights in the reference's row-major (F, A) order (Parameterised::weights,
  *              params/mod.rs:118), independent of the device layout and storage dtype;
  *              then, if aux_kind is 1, 2 or 5, n_learners x f32[F][A] of the auxiliary matrix (traces / fa_td / the actor's theta; aux_kind 5 is
  *              written as file version 7, which no other configuration reads);
+ *              if aux_kind is 6 (file version 8, which no other configuration reads; A = 1, the weights are V's w): n_learners x f32[F][n_actions]
+ *              of the actor's theta;
  *              if aux_kind is 3 (file version 3): u32 head[N], u32 len[N], f32 entries[D + 5][n_steps][N] -- every learner's
  *              Backup ring {s, a, q, residual, pi, mu} (q_sigma.rs:30-63), so that a QSigma run with n_steps > 1 resumes
  *              bit-identically too.  Files of version 2 (no aux_kind 3) are still read.

@@ -10,6 +10,7 @@ MOUNTAIN_CAR, CART_POLE, ACROBOT, HIV_TREATMENT = 0, 1, 2, 3
 FOURIER, TILE_CODING = 0, 1
 QLEARNING, SARSA, EXPECTED_SARSA, SARSA_LAMBDA, Q_LAMBDA, PAL, GREEDY_GQ, TD, TD_LAMBDA, Q_SIGMA = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 ACTOR_CRITIC, Q_ACTOR_CRITIC = 10, 11          # ActorCritic (control/ac.rs) with a Gibbs actor and a SARSA critic: a2c.rs's closure / QCritic
+TD_ACTOR_CRITIC = 13                           # ActorCritic::tdac: the Gibbs actor with TDCritic over a TD(0) V (12 is no algo)
 TRACE_ACCUMULATE, TRACE_SATURATE, TRACE_DUTCH = 0, 1, 2
 GREEDY, EPSILON_GREEDY, SOFTMAX, RANDOM = 0, 1, 2, 3
 W_PER_ENV, W_SHARED = 0, 1
@@ -334,7 +335,8 @@ class Context:
         _abi.check(self._L.rsrl_hip_set_td_weights(self._h, int(env_index), _p(_in(v, np.float32, (self.F, self.A)))))
 
     def get_policy_weights(self, env_index=0):
-        """ActorCritic.policy's weights theta of one learner (the Gibbs actor, ac.rs:61), f32 (F, A); RsrlHipError on the other agents"""
+        """ActorCritic.policy's weights theta of one learner (the Gibbs actor, ac.rs:61), f32 (F, A) -- also for TD_ACTOR_CRITIC, whose
+        get_weights is V's (F, 1); RsrlHipError on the other agents"""
         out = np.empty((self.F, self.A), dtype=np.float32)
         _abi.check(self._L.rsrl_hip_get_policy_weights(self._h, int(env_index), _p(out)))
         return out

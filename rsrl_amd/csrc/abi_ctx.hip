@@ -39,6 +39,7 @@ static AgentFamily classify(const rsrl_hip_config& cfg, size_t w_elems) {
     const int al = cfg.algo;
     if (cfg.domain == RSRL_HIV_TREATMENT) return F::Hiv;
     if (is_ac(al)) return F::AcReg;                         // (before the one-step agents: carries_q is false, no trait fast path)
+    if (is_tdac(al)) return F::TdAcReg;                     // (before the prediction agents: W is V's one column, but the policy is the actor's)
     if (cfg.weight_mode == RSRL_W_SHARED) return fourier ? F::SharedDense : (is_sparse_lambda(cfg) ? F::SharedSparseLambda : F::SharedTile);
     if (wave && is_wave_aux_algo(al)) return F::WaveAux;
     if (is_pred(al)) return tile ? F::TdTile : (reg ? F::TdReg : F::TdGeneric);
@@ -74,6 +75,7 @@ static const char* train_kernel_name(const rsrl_hip_ctx* c) {
     case AgentFamily::Generic: return "k_train_mem";
     case AgentFamily::Hiv: return "k_hiv_train";
     case AgentFamily::AcReg: return "k_train_ac";
+    case AgentFamily::TdAcReg: return "k_train_tdac";
     }
     return "";
 }
@@ -170,7 +172,7 @@ static int check_config(const rsrl_hip_config& cfg) {
     const int D = kDomainShape[cfg.domain][0], A = kDomainShape[cfg.domain][1];
     if (cfg.n_envs < 1) return fail(RSRL_HIP_EINVAL, "n_envs must be >= 1");
     if (cfg.n_envs + cfg.env_offset > (int64_t)0xffffffffLL || cfg.env_offset < 0) return fail(RSRL_HIP_EINVAL, "global env ids must fit 32 bits");
-    if (cfg.algo < 0 || cfg.algo > RSRL_Q_ACTOR_CRITIC) return fail(RSRL_HIP_EINVAL, "unknown algo %d", cfg.algo);
+    if (cfg.algo < 0 || cfg.algo > RSRL_TD_ACTOR_CRITIC || cfg.algo == 12) return fail(RSRL_HIP_EINVAL, "unknown algo %d", cfg.algo);
     if (cfg.policy < 0 || cfg.policy > RSRL_RANDOM) return fail(RSRL_HIP_EINVAL, "unknown policy %d", cfg.policy);
     // Softmax::new panics for |tau| < 1e-7 (policies/softmax.rs:63-66)
     if (cfg.policy == RSRL_SOFTMAX && std::fabs(cfg.tau) < 1e-7) return fail(RSRL_HIP_EINVAL, "Tau parameter in Softmax must be non-zero.");
@@ -214,6 +216,15 @@ static int check_config(const rsrl_hip_config& cfg) {
         if (!reg || !per_env || !f32 || cfg.policy != RSRL_SOFTMAX || cfg.agent_policy != -1 || esched)
             return fail(RSRL_HIP_EINVAL, "ActorCritic supports per-learner f32 weights on the register-family Fourier orders (MountainCar 1-5, CartPole 1, "
                                          "Acrobot 1) with policy = Softmax (the Gibbs actor), agent_policy = -1 (the critic shares the actor) and no epsilon "
+                                         "schedule (got domain %d, basis %d, order %d, weight mode %d, dtype %d, policy %d, agent_policy %d, epsilon_decay %g)",
+                        cfg.domain, cfg.basis, cfg.order, cfg.weight_mode, cfg.weight_dtype, cfg.policy, cfg.agent_policy, cfg.epsilon_decay);
+        return RSRL_HIP_OK;
+    }
+    if (is_tdac(al)) {
+        // train_tdac.hip: the same configurations as ActorCritic's
+        if (!reg || !per_env || !f32 || cfg.policy != RSRL_SOFTMAX || cfg.agent_policy != -1 || esched)
+            return fail(RSRL_HIP_EINVAL, "the TD ActorCritic (RSRL_TD_ACTOR_CRITIC) supports per-learner f32 weights on the register-family Fourier orders "
+                                         "(MountainCar 1-5, CartPole 1, Acrobot 1) with policy = Softmax (the Gibbs actor), agent_policy = -1 and no epsilon "
                                          "schedule (got domain %d, basis %d, order %d, weight mode %d, dtype %d, policy %d, agent_policy %d, epsilon_decay %g)",
                         cfg.domain, cfg.basis, cfg.order, cfg.weight_mode, cfg.weight_dtype, cfg.policy, cfg.agent_policy, cfg.epsilon_decay);
         return RSRL_HIP_OK;
@@ -275,7 +286,7 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
     const int64_t N = cfg->n_envs;
     const bool shared = cfg->weight_mode == RSRL_W_SHARED;
     c->w_stride = shared ? 1 : N;
-    c->Aw = is_pred(cfg->algo) ? 1 : c->A;
+    c->Aw = (is_pred(cfg->algo) || is_tdac(cfg->algo)) ? 1 : c->A;         // (the TD ActorCritic's weights are V's)
     c->w_elems = (size_t)c->Aw * c->F * (size_t)(shared ? 1 : N);
     c->family = classify(*cfg, c->w_elems);
     // a ctx that steps one batch-step per launch streams W every step: learner-major rows (W[N][A][F]) let k_step_reg_lm
@@ -335,8 +346,8 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
         HIP_TRY(hipMemsetAsync(c->sp_vals, 0, sizeof(float) * (size_t)kSparseCap * (size_t)N, c->stream));
         c->sp_lds = slice * 8 <= 128 * 1024;
         if (c->sp_lds && slice * 8 > 64 * 1024) c->sp_lds = sparse_trace_scatter_allow_lds(cfg->n_tilings, (int)(slice * 8));      // more dynamic LDS than a kernel gets by default
-    } else if (has_aux(cfg->algo)) {
-        c->z_bytes = c->w_elems * 4;
+    } else if (has_aux(cfg->algo) || c->family == AgentFamily::TdAcReg) {
+        c->z_bytes = (c->family == AgentFamily::TdAcReg ? (size_t)aux_cols(c) * c->F * (size_t)N : c->w_elems) * 4;      // (TdAcReg: theta, A columns)
         HIP_TRY(hipMalloc((void**)&c->Z, c->z_bytes));
         HIP_TRY(hipMemsetAsync(c->Z, 0, c->z_bytes, c->stream));                  // Trace::zeros (ActorCritic's theta: LFA::vector zero-initialises)
     }

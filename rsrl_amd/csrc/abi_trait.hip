@@ -124,6 +124,9 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
     if (!states || M_ < 1 || M_ > c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "bad batch (M=%lld, n_envs=%lld)", (long long)M_, (long long)c->cfg.n_envs);
     if (is_pred(c->cfg.algo) && op != QOP_EVALUATE && op != QOP_FEATURES)
         return fail(RSRL_HIP_ESTATE, "a prediction agent has a state-value function only (use rsrl_hip_q_evaluate for V(s))");
+    // the TD ActorCritic: its value side is V(s) (no action values to search or weigh), its policy side the actor's theta
+    if (is_tdac(c->cfg.algo) && (op == QOP_FIND_MAX || op == QOP_FIND_MIN || op == QOP_EXPECTED))
+        return fail(RSRL_HIP_ESTATE, "the TD ActorCritic's critic is a state-value function (use rsrl_hip_q_evaluate for V(s), the policy operations for the actor)");
     HIP_TRY(hipSetDevice(c->cfg.device));
     const float* d_states; OutBuf<float> of; OutBuf<int32_t> oi;
     TRY(stage_in(c, 0, states, (size_t)c->D * M_, &d_states));
@@ -139,7 +142,7 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
     const uint64_t call = (op == QOP_SAMPLE_STEP || op == QOP_SAMPLE_INIT) ? step_t : c->api_calls;      // (the driver loop's sample: addressed by the batch-step)
     if (op == QOP_SAMPLE) c->api_calls++;
     const BasisGeom g = make_geom(c);
-    if (is_pred(c->cfg.algo) && op == QOP_EVALUATE) {          // V(s)
+    if ((is_pred(c->cfg.algo) || is_tdac(c->cfg.algo)) && op == QOP_EVALUATE) {          // V(s) (the TD ActorCritic: its w, k_v_evaluate)
         bool ok = true;
         switch (c->family) {
         case AgentFamily::WaveAux:

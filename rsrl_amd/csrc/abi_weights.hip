@@ -63,12 +63,12 @@ int traces_rw(rsrl_hip_ctx* c, int64_t env_index, float* out, const float* in) {
     if (!c->Z) return fail(RSRL_HIP_ESTATE, "this agent has no auxiliary matrix (eligibility trace / fa_td weights)");
     if (env_index < 0 || env_index >= c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "env_index out of range");
     HIP_TRY(hipSetDevice(c->cfg.device));
-    const int n = c->F * c->Aw;
+    const int cols = aux_cols(c), n = c->F * cols;
     if (out) {
         OutBuf<float> oz;
         TRY(stage_out(c, 0, out, (size_t)n, &oz));
         if (is_wave(c->cfg)) hipLaunchKernelGGL((k_wave_weights_get<float>), dim3((n + 255) / 256), dim3(256), 0, c->stream, (const float*)c->Z + env_index * (int64_t)n, c->F, c->Aw, oz.dev);
-        else hipLaunchKernelGGL(k_weights_get, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->Z, c->cfg.basis == RSRL_TILE_CODING, c->w_stride, env_index, c->F, c->Aw, oz.dev);
+        else hipLaunchKernelGGL(k_weights_get, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->Z, c->cfg.basis == RSRL_TILE_CODING, c->w_stride, env_index, c->F, cols, oz.dev);
         KCHECK();
         bool sync = false; TRY(flush_out(c, &oz, &sync));
         if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
@@ -76,7 +76,7 @@ int traces_rw(rsrl_hip_ctx* c, int64_t env_index, float* out, const float* in) {
         const float* d_z;
         TRY(stage_in(c, 0, in, (size_t)n, &d_z));
         if (is_wave(c->cfg)) hipLaunchKernelGGL((k_wave_weights_set<float>), dim3((unsigned)(((int64_t)c->Aw * (c->F / 8) + 255) / 256)), dim3(256), 0, c->stream, c->Z, env_index, (int64_t)1, c->F, c->Aw, d_z);
-        else hipLaunchKernelGGL(k_weights_set, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->Z, c->cfg.basis == RSRL_TILE_CODING, c->w_stride, env_index, c->F, c->Aw, d_z);
+        else hipLaunchKernelGGL(k_weights_set, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->Z, c->cfg.basis == RSRL_TILE_CODING, c->w_stride, env_index, c->F, cols, d_z);
         KCHECK();
         if (!is_device_ptr(in)) HIP_TRY(hipStreamSynchronize(c->stream));
     }
@@ -109,13 +109,15 @@ int rsrl_hip_set_td_weights(rsrl_hip_ctx* c, int64_t env_index, const float* v) 
 int rsrl_hip_get_policy_weights(rsrl_hip_ctx* c, int64_t env_index, float* theta) {
     if (!theta) return fail(RSRL_HIP_EINVAL, "null argument");
     CHECK_CTX(c);
-    if (c->family != AgentFamily::AcReg) return fail(RSRL_HIP_ESTATE, "only ActorCritic has policy weights of its own (its policy reads Q otherwise)");
+    if (c->family != AgentFamily::AcReg && c->family != AgentFamily::TdAcReg)
+        return fail(RSRL_HIP_ESTATE, "only ActorCritic has policy weights of its own (its policy reads Q otherwise)");
     return traces_rw(c, env_index, theta, nullptr);
 }
 int rsrl_hip_set_policy_weights(rsrl_hip_ctx* c, int64_t env_index, const float* theta) {
     if (!theta) return fail(RSRL_HIP_EINVAL, "null argument");
     CHECK_CTX(c);
-    if (c->family != AgentFamily::AcReg) return fail(RSRL_HIP_ESTATE, "only ActorCritic has policy weights of its own (its policy reads Q otherwise)");
+    if (c->family != AgentFamily::AcReg && c->family != AgentFamily::TdAcReg)
+        return fail(RSRL_HIP_ESTATE, "only ActorCritic has policy weights of its own (its policy reads Q otherwise)");
     return traces_rw(c, env_index, nullptr, theta);
 }
 
@@ -127,6 +129,7 @@ constexpr uint32_t kCkptVersionEps = 4;       // ... or as version 4 when the ct
 constexpr uint32_t kCkptVersionSparse = 6;    // files carrying aux_kind 4 (the sparse per-learner traces over a shared table): u64 n_envs, u64 env_offset, u32 len[N], lists
 constexpr uint32_t kCkptVersionSparse5 = 5;   // ... as round 5 wrote them (no n_envs / env_offset in front of the lengths): still read
 constexpr uint32_t kCkptVersionAc = 7;        // files carrying aux_kind 5 (ActorCritic's theta): laid out as aux_kind 1 / 2, a version of their own
+constexpr uint32_t kCkptVersionTdac = 8;      // files carrying aux_kind 6 (the TD ActorCritic's theta, f32[F][n_actions] against V's f32[F][1]): ditto
 constexpr int64_t kSparseChunk = 4096;        // learners per staging chunk of the sparse lists
 constexpr size_t kCkptHeaderBytes = 72;
 struct Ckpt {
@@ -135,13 +138,15 @@ struct Ckpt {
     bool has_eps;                                 // (not a header field: the file version says it)
 };
 // 1 = eligibility traces, 2 = fa_td weights (both: a second matrix of W's shape), 3 = QSigma's per-learner n-step backups,
-// 4 = every learner's sparse trace over the shared table (the lists, compact), 5 = ActorCritic's theta (a second matrix of W's shape)
+// 4 = every learner's sparse trace over the shared table (the lists, compact), 5 = ActorCritic's theta (a second matrix of W's shape),
+// 6 = the TD ActorCritic's theta (a second matrix of A columns, W has one)
 int aux_kind_of(const rsrl_hip_ctx* c) {
     if (c->family == AgentFamily::AcReg) return 5;
+    if (c->family == AgentFamily::TdAcReg) return 6;
     return c->sp_keys ? 4 : (c->qs_buf ? 3 : (!c->Z ? 0 : (c->cfg.algo == RSRL_GREEDY_GQ ? 2 : 1)));
 }
-// aux_kinds whose payload is a second n_learners x f32[F][A] after the weights
-bool aux_is_matrix(int32_t kind) { return kind == 1 || kind == 2 || kind == 5; }
+// aux_kinds whose payload is a second n_learners x f32[F][aux_cols] after the weights
+bool aux_is_matrix(int32_t kind) { return kind == 1 || kind == 2 || kind == 5 || kind == 6; }
 size_t qs_floats(const rsrl_hip_ctx* c) { return (size_t)(c->D + 5) * (size_t)c->cfg.n_steps * (size_t)c->cfg.n_envs; }
 Ckpt ckpt_of(const rsrl_hip_ctx* c) {
     Ckpt h{};
@@ -159,7 +164,8 @@ uint64_t get64(const uint8_t*& p) { uint64_t v = 0; for (int i = 0; i < 8; ++i) 
 void ckpt_encode(const Ckpt& h, uint8_t (&buf)[kCkptHeaderBytes]) {
     uint8_t* p = buf;
     memcpy(p, "RSRLHIPW", 8); p += 8;
-    put32(p, h.has_eps ? kCkptVersionEps : (h.aux_kind == 5 ? kCkptVersionAc : (h.aux_kind == 4 ? kCkptVersionSparse : (h.aux_kind == 3 ? kCkptVersion : 2u))));
+    put32(p, h.has_eps ? kCkptVersionEps : (h.aux_kind == 6 ? kCkptVersionTdac : (h.aux_kind == 5 ? kCkptVersionAc : (h.aux_kind == 4 ? kCkptVersionSparse :
+                                                                                                                          (h.aux_kind == 3 ? kCkptVersion : 2u)))));
     const int32_t f[11] = {h.domain, h.basis, h.order, h.n_tilings, h.tiles_per_dim, h.weight_mode, h.F, h.A, h.algo, h.weight_dtype, h.aux_kind};
     for (int32_t v : f) put32(p, (uint32_t)v);
     put64(p, (uint64_t)h.n_learners); put64(p, h.step_count);
@@ -185,12 +191,14 @@ int rsrl_hip_save_weights(rsrl_hip_ctx* c, const char* path) {
     uint8_t hdr[kCkptHeaderBytes]; ckpt_encode(h, hdr);
     int rc = RSRL_HIP_OK;
     if (fwrite(hdr, 1, sizeof(hdr), f) != sizeof(hdr)) rc = fail(RSRL_HIP_EINVAL, "short write to %s", path);
-    std::vector<float> w((size_t)c->F * c->Aw);
-    for (int pass = 0; pass < (aux_is_matrix(h.aux_kind) ? 2 : 1); ++pass)            // every learner's weights, then every learner's auxiliary matrix
+    std::vector<float> w;
+    for (int pass = 0; pass < (aux_is_matrix(h.aux_kind) ? 2 : 1); ++pass) {          // every learner's weights, then every learner's auxiliary matrix
+        w.resize((size_t)c->F * (pass == 0 ? c->Aw : aux_cols(c)));
         for (int64_t i = 0; rc == RSRL_HIP_OK && i < h.n_learners; ++i) {
             rc = pass == 0 ? rsrl_hip_get_weights(c, i, w.data()) : traces_rw(c, i, w.data(), nullptr);
             if (rc == RSRL_HIP_OK && fwrite(w.data(), sizeof(float), w.size(), f) != w.size()) rc = fail(RSRL_HIP_EINVAL, "short write to %s", path);
         }
+    }
     if (rc == RSRL_HIP_OK && h.aux_kind == 3) {                        // QSigma: ring heads, lengths, entries (SoA [field][slot][learner])
         const size_t N = (size_t)c->cfg.n_envs, nf = qs_floats(c);
         std::vector<uint32_t> hl(2 * N); std::vector<float> buf(nf);
@@ -259,11 +267,12 @@ int rsrl_hip_load_weights(rsrl_hip_ctx* c, const char* path) {
     int rc = RSRL_HIP_OK;
     if (fread(hdr, 1, sizeof(hdr), f) != sizeof(hdr) || !ckpt_decode(hdr, &h, &version)) rc = fail(RSRL_HIP_EINVAL, "%s is not a rsrl_hip weight file", path);
     else if (version != kCkptVersion && version != 2u && version != kCkptVersionEps && version != kCkptVersionSparse && version != kCkptVersionSparse5 &&
-             version != kCkptVersionAc)
-        rc = fail(RSRL_HIP_EINVAL, "%s has checkpoint version %u, this library reads versions 2, %u, %u, %u, %u and %u", path, version, kCkptVersion, kCkptVersionEps,
-                  kCkptVersionSparse5, kCkptVersionSparse, kCkptVersionAc);
-    // an ActorCritic file is version 7 with aux_kind 5 and nothing else is: any other pairing is not a file this library wrote
-    else if ((version == kCkptVersionAc) != (h.aux_kind == 5))
+             version != kCkptVersionAc && version != kCkptVersionTdac)
+        rc = fail(RSRL_HIP_EINVAL, "%s has checkpoint version %u, this library reads versions 2, %u, %u, %u, %u, %u and %u", path, version, kCkptVersion, kCkptVersionEps,
+                  kCkptVersionSparse5, kCkptVersionSparse, kCkptVersionAc, kCkptVersionTdac);
+    // an ActorCritic file is version 7 with aux_kind 5, a TD ActorCritic file version 8 with aux_kind 6, and nothing else is either: any other pairing
+    // is not a file this library wrote
+    else if ((version == kCkptVersionAc) != (h.aux_kind == 5) || (version == kCkptVersionTdac) != (h.aux_kind == 6))
         rc = fail(RSRL_HIP_EINVAL, "%s: checkpoint version %u with aux_kind %d is not a valid pairing", path, version, h.aux_kind);
     // a QSigma file written before the backups travelled (version 2, aux_kind 0) is still read: the weights are loaded and the run
     // resumes from EMPTY n-step backups, as after a terminal transition (q_sigma.rs:154)
@@ -276,11 +285,11 @@ int rsrl_hip_load_weights(rsrl_hip_ctx* c, const char* path) {
          h.has_eps != want.has_eps))
         rc = fail(RSRL_HIP_EINVAL, "%s was written by a different configuration%s", path,
                   h.has_eps != want.has_eps ? " (the per-learner epsilon schedule, config.epsilon_decay, is part of it)" : "");
-    const size_t per = (size_t)c->F * c->Aw;
+    const size_t per = (size_t)c->F * c->Aw, per_aux = (size_t)c->F * aux_cols(c);      // a learner's weights; its auxiliary matrix (aux_kind 1, 2, 5, 6)
     std::vector<uint32_t> sp_len_in, sp_len_t;      // sparse traces: a learner's entries in the file; its sub-lists' lengths on the device
     long sp_prefix = 0;
     if (rc == RSRL_HIP_OK) {                                             // a truncated file is refused before anything is touched
-        long long expect = (long long)kCkptHeaderBytes + (long long)(aux_is_matrix(h.aux_kind) ? 2 : 1) * h.n_learners * (long long)per * 4 +
+        long long expect = (long long)kCkptHeaderBytes + h.n_learners * (long long)(per + (aux_is_matrix(h.aux_kind) ? per_aux : 0)) * 4 +
                            (h.aux_kind == 3 ? (long long)c->cfg.n_envs * 8 + (long long)qs_floats(c) * 4 : 0) +
                            (h.has_eps ? (long long)c->cfg.n_envs * 4 : 0);
         if (h.aux_kind == 4) {                                           // the lists are compact: their lengths say how long the file is
@@ -321,12 +330,14 @@ int rsrl_hip_load_weights(rsrl_hip_ctx* c, const char* path) {
         return fail(e == hipErrorOutOfMemory ? RSRL_HIP_ENOMEM : RSRL_HIP_EHIP, "staging buffers for %s: %s", path, hipGetErrorString(e));
     }
     c->W = W_new; c->Z = Z_new;
-    std::vector<float> w(per);
-    for (int pass = 0; pass < (aux_is_matrix(h.aux_kind) ? 2 : 1); ++pass)
+    std::vector<float> w;
+    for (int pass = 0; pass < (aux_is_matrix(h.aux_kind) ? 2 : 1); ++pass) {
+        w.resize(pass == 0 ? per : per_aux);
         for (int64_t i = 0; rc == RSRL_HIP_OK && i < h.n_learners; ++i) {
-            if (fread(w.data(), sizeof(float), per, f) != per) { rc = fail(RSRL_HIP_EINVAL, "%s: read error", path); break; }
+            if (fread(w.data(), sizeof(float), w.size(), f) != w.size()) { rc = fail(RSRL_HIP_EINVAL, "%s: read error", path); break; }
             rc = pass == 0 ? rsrl_hip_set_weights(c, i, w.data()) : traces_rw(c, i, nullptr, w.data());
         }
+    }
     uint16_t* spk_new = nullptr; float* spv_new = nullptr;              // sparse traces: shadow lists, switched in at the end like W
     if (rc == RSRL_HIP_OK && h.aux_kind == 4) {
         const int64_t N = c->cfg.n_envs;

@@ -51,6 +51,8 @@ static inline bool is_lambda(int algo) { return algo == RSRL_SARSA_LAMBDA || alg
 static inline bool is_pred(int algo) { return algo == RSRL_TD || algo == RSRL_TD_LAMBDA; }        // one weight column (V function)
 static inline bool is_ac(int algo) { return algo == RSRL_ACTOR_CRITIC || algo == RSRL_Q_ACTOR_CRITIC; }     // ActorCritic: theta is the second matrix
 static inline bool has_aux(int algo) { return is_lambda(algo) || algo == RSRL_GREEDY_GQ || algo == RSRL_TD_LAMBDA || is_ac(algo); }   // second matrix of W's shape
+// ActorCritic with the TD(0) V critic: W is V's single column, the second matrix (theta) has A columns
+static inline bool is_tdac(int algo) { return algo == RSRL_TD_ACTOR_CRITIC; }
 
 // ---- the small kernels more than one unit launches, and the launches of kernel templates two units would otherwise both instantiate: defined ONCE, in
 // kernels_util.hip / launch_shared.hip (a kernel's host stub is an ordinary function: another unit launches it through this declaration)
@@ -122,6 +124,7 @@ enum class AgentFamily : uint8_t {
     Generic,              // one-step agents on tile coding / generic Fourier orders, per-learner weights: k_train_mem
     Hiv,                  // HIVTreatment (f64 hidden state): one-step agents, per-learner weights, Fourier orders 1-3: k_hiv_train (train_hiv.hip)
     AcReg,                // ActorCritic (both critics), register-family Fourier, per-learner f32 weights: k_train_ac (train_ac.hip); theta in Z
+    TdAcReg,              // ActorCritic with the TD(0) V critic, same configurations: k_train_tdac (train_tdac.hip); w in W (one column), theta in Z (A columns)
 };
 static inline bool is_wave_family(AgentFamily f) {
     return f == AgentFamily::WaveAux || f == AgentFamily::WaveQSigma || f == AgentFamily::WaveLambda || f == AgentFamily::WaveControl;
@@ -167,6 +170,7 @@ struct rsrl_hip_ctx {
     uint16_t* sp_keys = nullptr; float* sp_vals = nullptr; uint32_t* sp_len = nullptr;    // sparse traces: [N][kSparseCap] slice-relative keys (16 bit) and values, lengths [N][n_tilings]
     bool sp_lds = false;             //   one tiling's slice of the delta table fits LDS (k_sparse_trace_scatter)
     float* Z = nullptr;              // auxiliary matrix f32[A][F][N]: eligibility traces (lambda agents) / fa_td weights (GreedyGQ) / the actor's theta (ActorCritic)
+                                     // -- of W's shape, except TdAcReg's theta: A columns against W's one (aux_cols)
     double* hiv_y = nullptr;         // HIVTreatment only: every learner's hidden state f64[6][N] (`state` holds its observation)
     bool q_valid = false;            // false whenever weights / states were changed from outside the driver loop
     // ---- the trait-granular fast path (kernels_trait.hpp): register-family Fourier basis, per-learner f32 weights, learner-major layout
@@ -263,9 +267,11 @@ static Common make_common(const rsrl_hip_ctx* c) {
 // Policy::sample / mode / probabilities, reset's initial sample and the rollouts run the model kernels on it; the value side keeps make_common
 static Common make_policy_common(const rsrl_hip_ctx* c) {
     Common k = make_common(c);
-    if (c->family == AgentFamily::AcReg) k.W = c->Z;
+    if (c->family == AgentFamily::AcReg || c->family == AgentFamily::TdAcReg) k.W = c->Z;      // (the model kernels take the column count from the model: A)
     return k;
 }
+// columns of the auxiliary matrix Z: W's (Aw), except the TD ActorCritic's theta (A)
+static inline int aux_cols(const rsrl_hip_ctx* c) { return c->family == AgentFamily::TdAcReg ? c->A : c->Aw; }
 
 static LambdaParams make_lambda(const rsrl_hip_ctx* c) {
     LambdaParams lp{};

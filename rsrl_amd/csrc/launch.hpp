@@ -48,6 +48,10 @@ bool launch_gq(int domain, int order, int policy, dim3 grid, dim3 block, hipStre
 // batch-step t (the critic's inner draw), else chunk batch-steps of the driver loop from t
 bool launch_ac(int domain, int order, int critic, dim3 grid, dim3 block, hipStream_t st, const Common& k, float* theta, uint64_t t, int chunk,
                DevStats* stats, const Transitions* io);
+// ActorCritic with the TD(0) V critic (train_tdac.hip, kernels_tdac.hpp): k.W = w f32[F][N], theta f32[A][F][N].  io: handle, else chunk
+// batch-steps of the driver loop from t
+bool launch_tdac(int domain, int order, dim3 grid, dim3 block, hipStream_t st, const Common& k, float* theta, uint64_t t, int chunk, DevStats* stats,
+                 const Transitions* io);
 
 bool launch_td(int domain, int order, bool lambda, dim3 grid, dim3 block, hipStream_t st, const Common& k, const TdParams& tp, uint64_t t, int chunk,
                DevStats* stats, const Transitions* io);

@@ -185,11 +185,22 @@ struct GreedyGQ : Agent {
 // critic: the SARSA evaluator (its q_func and gamma; it shares the actor as its policy, as the example does); the target is a2c.rs's closure
 // Q(s,a) - sum_b Q(s,b) pi(b|s), or Q(s,a) for ActorCritic::qac (QCritic).  The Session's policy must be the same Gibbs object.
 namespace control { namespace ac {
+// TDCritic { gamma, v_func } (ac.rs:32-52): the target r + gamma V(s') - V(s), or r - V(s') on a terminal transition
+struct TDCritic {
+    double gamma; Shared<fa::linear::LFA> v_func;
+};
 struct ActorCritic : td::Agent {
     ActorCritic(const td::SARSA& critic, const policies::Gibbs& /*policy*/, double alpha_)
         : td::Agent{RSRL_ACTOR_CRITIC, critic.q_func, critic.gamma, alpha_} {}
     static ActorCritic qac(const td::SARSA& critic, const policies::Gibbs& policy, double alpha_) {
         ActorCritic a(critic, policy, alpha_); a.algo = RSRL_Q_ACTOR_CRITIC; return a;
+    }
+    // ActorCritic::tdac (ac.rs:87-98): TDCritic over a state-value function v_func (a ScalarLFA, one weight column), which the library learns
+    // with TD(0) at v_func's SGD rate -- the `eval` of examples/tdac.rs.  The Session's weights are then V's [F][1]
+    ActorCritic(const TDCritic& critic, const policies::Gibbs& /*policy*/, double alpha_)
+        : td::Agent{RSRL_TD_ACTOR_CRITIC, critic.v_func, critic.gamma, alpha_} {}
+    static ActorCritic tdac(Shared<fa::linear::LFA> v_func, const policies::Gibbs& policy, double alpha_, double gamma) {
+        return ActorCritic(TDCritic{gamma, std::move(v_func)}, policy, alpha_);
     }
 };
 }}  // namespace control::ac

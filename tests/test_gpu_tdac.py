@@ -1,0 +1,326 @@
+"""ActorCritic with the TD(0) state-value critic (RSRL_TD_ACTOR_CRITIC, train_tdac.hip) on the device: handle against the f64 rule, the critic half
+bit for bit a TD ctx's, the policy side reading theta and the value side reading w, the driver loop against a restated loop, train against the
+trait-granular loop / launch depths / shards bit for bit, checkpoints, the checksum, the refusals and the C++ example."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import rsrl_amd
+from rsrl_amd import RsrlHipError
+from tests.tdac_numpy import tdac_rule
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TDAC = rsrl_amd.TD_ACTOR_CRITIC
+REG = [(rsrl_amd.MOUNTAIN_CAR, o) for o in (1, 2, 3, 4, 5)] + [(rsrl_amd.CART_POLE, 1), (rsrl_amd.ACROBOT, 1)]
+LOOP = [(rsrl_amd.MOUNTAIN_CAR, 3), (rsrl_amd.MOUNTAIN_CAR, 5), (rsrl_amd.CART_POLE, 1), (rsrl_amd.ACROBOT, 1)]
+
+
+def ctx(**kw):
+    base = dict(domain=rsrl_amd.MOUNTAIN_CAR, order=3, algo=TDAC, policy=rsrl_amd.SOFTMAX, n_envs=32, seed=5, gamma=0.95, lr=0.05, alpha=0.3, tau=1.0)
+    base.update(kw)
+    return rsrl_amd.Context(**base)
+
+
+def rand_states(orc, domain, n, rng):
+    lo, hi = orc.domain_bounds(domain)
+    return rng.uniform(lo, hi, size=(n, len(lo))).T.astype(np.float32)
+
+
+def near_boundary(p, x, margin=1e-5):
+    """the draw's uniform lies within margin of a cumulative-probability boundary: an fp32 rounding may pick the neighbour"""
+    u = (int(x[2]) >> 8) / 16777216.0
+    return bool(np.min(np.abs(np.cumsum(p)[:-1] - u), initial=1.0) < margin)
+
+
+def randomise(c, rng, scale=0.3):
+    Ws = [rng.normal(0.0, scale, size=(c.F, 1)).astype(np.float32) for _ in range(c.N)]
+    Ts = [rng.normal(0.0, scale, size=(c.F, c.A)).astype(np.float32) for _ in range(c.N)]
+    for i in range(c.N):
+        c.set_weights(Ws[i], i)
+        c.set_policy_weights(Ts[i], i)
+    return Ws, Ts
+
+
+def _transitions(c, orc, domain, rng):
+    N = c.N
+    c.states = rand_states(orc, domain, N, rng)
+    a = rng.integers(0, c.A, size=N).astype(np.int32)
+    frm, nxt, rew, term = c.domain_step(a)
+    term = (term | (rng.random(N) < 0.25)).astype(np.uint8)          # the critic reads V(s') of these: s' as domain_step reported it
+    return frm, a, rew, nxt, term
+
+
+@pytest.mark.parametrize("tau", [1.0, 0.5])
+@pytest.mark.parametrize("domain,order", REG)
+def test_handle_against_the_f64_rule(orc, domain, order, tau):
+    N, lr, gamma, alpha = 64, 0.05, 0.95, 0.3
+    rng = np.random.default_rng(domain * 100 + order * 10 + int(tau * 4))
+    with ctx(domain=domain, order=order, tau=tau, n_envs=N, seed=17, lr=lr, gamma=gamma, alpha=alpha) as c:
+        assert c.n_out == 1
+        Ws, Ts = randomise(c, rng)
+        frm, a, rew, nxt, term = _transitions(c, orc, domain, rng)
+        assert 0 < term.sum() < N
+        td = c.handle(frm, a, rew, nxt, term)
+        for i in range(N):
+            phi_s = orc.fourier_project(domain, order, frm[:, i])
+            phi_n = orc.fourier_project(domain, order, nxt[:, i])
+            w, Th = Ws[i].astype(np.float64), Ts[i].astype(np.float64)
+            d, w2, T2 = tdac_rule(w, Th, phi_s, phi_n, int(a[i]), float(rew[i]), bool(term[i]), gamma, lr, alpha, tau)
+            assert abs(td[i] - d) <= 2e-5 * (1 + abs(d)), (i, td[i], d)
+            sphi = np.abs(phi_s).sum()
+            for got, want, old in ((c.get_weights(i)[:, 0], w2, w[:, 0]), (c.get_policy_weights(i), T2, Th)):
+                x_scale = np.max(np.abs(want - old))
+                assert np.max(np.abs(got - want)) <= 3e-6 * (1 + x_scale) * sphi + 3e-6 * np.max(np.abs(old)), i
+
+
+@pytest.mark.parametrize("domain,order", LOOP)
+def test_the_critic_half_is_td0_bit_for_bit(orc, domain, order):
+    N = 64
+    kw = dict(domain=domain, order=order, n_envs=N, seed=3, lr=0.05, gamma=0.95)
+    rng = np.random.default_rng(order * 7 + domain)
+    with ctx(alpha=0.3, tau=0.7, **kw) as c, rsrl_amd.Context(algo=rsrl_amd.TD, policy=rsrl_amd.RANDOM, **kw) as v:
+        Ws, _ = randomise(c, rng, scale=1.0)
+        for i in range(N):
+            v.set_weights(Ws[i], i)
+        for _ in range(3):                                            # three rounds: theta moves, w must not notice
+            frm, a, rew, nxt, term = _transitions(c, orc, domain, rng)
+            td_ac = c.handle(frm, a, rew, nxt, term)
+            td_v = v.handle(frm, a, rew, nxt, term)
+            assert np.array_equal(td_ac.view(np.uint32), td_v.view(np.uint32))
+            for i in range(N):
+                assert np.array_equal(c.get_weights(i).view(np.uint32), v.get_weights(i).view(np.uint32)), i
+
+
+def test_policy_side_reads_theta_value_side_reads_w(orc):
+    N, seed, tau, domain, order = 64, 23, 0.5, rsrl_amd.MOUNTAIN_CAR, 3
+    rng = np.random.default_rng(4)
+    with ctx(n_envs=N, seed=seed, tau=tau, order=order, max_episode_steps=40) as c:
+        Ws, Ts = randomise(c, rng, scale=1.0)
+        S = rand_states(orc, domain, N, rng)
+        phis = [orc.fourier_project(domain, order, S[:, i]) for i in range(N)]
+        h = np.array([Ts[i].astype(np.float64).T @ phis[i] for i in range(N)]).T
+        v = np.array([Ws[i].astype(np.float64)[:, 0] @ phis[i] for i in range(N)])
+        probs = c.policy_probs(S)
+        want = np.array([orc.policy_probs(orc.SOFTMAX, h[:, i], tau=tau) for i in range(N)]).T
+        assert np.max(np.abs(probs - want)) <= 1e-6
+        assert np.array_equal(c.policy_mode(S), [orc.argmax_first(probs[:, i], prec="f32") for i in range(N)])
+        q = c.q_evaluate(S)
+        assert q.shape == (1, N) and np.allclose(q[0], v, atol=2e-5, rtol=1e-5)
+        for call in (lambda: c.q_find_max(S), lambda: c.q_find_min(S), lambda: c.q_expected_value(S, probs)):
+            with pytest.raises(RsrlHipError) as e:
+                call()
+            assert e.value.code == -5
+        sample = c.policy_sample(S)                                  # the first API call: BLK_API, call 0
+        for i in range(N):
+            x = orc.draw(seed, i, 0, orc.BLK_API)
+            if not near_boundary(want[:, i], x):
+                assert sample[i] == orc.policy_sample(orc.SOFTMAX, h[:, i], x, tau=tau), i
+        c.reset()
+        phi0 = orc.fourier_project(domain, order, orc.domain_reset(domain, prec="f32"))
+        acts = c.actions
+        for i in range(N):
+            h0 = Ts[i].astype(np.float64).T @ phi0
+            x = orc.draw(seed, i, 0, orc.BLK_INIT)
+            if not near_boundary(orc.policy_probs(orc.SOFTMAX, h0, tau=tau), x):
+                assert acts[i] == orc.policy_sample(orc.SOFTMAX, h0, x, tau=tau), i
+        # rollout_greedy = Domain::rollout(|s| policy.mode(s)): a host loop of domain_step + policy_mode through the same ctx
+        L = 30
+        n_states, total = c.rollout_greedy(L)
+        c.domain_reset()
+        tot = np.zeros(N, dtype=np.float32)
+        steps = np.zeros(N, dtype=np.int64)
+        done = np.zeros(N, dtype=bool)
+        for _ in range(L - 1):
+            frm, nxt, rew, term = c.domain_step(c.policy_mode(c.states))
+            live = ~done
+            tot[live] = (tot[live] + rew[live]).astype(np.float32)
+            steps[live] += 1
+            done |= term.astype(bool)
+        assert np.array_equal(n_states, steps + 1)
+        assert np.array_equal(total, tot)
+
+
+def _restated_loop(orc, domain, order, N, K, cap, seed, gamma, lr, alpha, tau, S0, A0):
+    """the driver loop per learner in f64 on the same draws -> (actions [K][N] after every batch-step, w, theta, learners with a draw within 1e-5
+    of a cumulative-probability boundary)"""
+    F, A = (order + 1) ** S0.shape[0], 2 if domain == rsrl_amd.CART_POLE else 3
+    acts, out_w, out_T, near = np.zeros((K, N), dtype=np.int64), [], [], np.zeros(N, dtype=bool)
+    for i in range(N):
+        w, Th = np.zeros(F), np.zeros((F, A))
+        s, a, ep = S0[:, i].copy(), int(A0[i]), 0
+        for t in range(K):
+            ns, r, term = orc.domain_step(domain, s, a, prec="f32d")
+            ns = np.asarray(ns, dtype=np.float32)                     # a terminal transition's s' is the terminal state: the critic reads it
+            ep += 1
+            trunc = (not term) and cap > 0 and ep >= cap
+            phi_s, phi_n = orc.fourier_project(domain, order, s), orc.fourier_project(domain, order, ns)
+            _, w, Th = tdac_rule(w, Th, phi_s, phi_n, a, float(np.float32(r)), term, gamma, lr, alpha, tau)
+            if term or trunc:
+                ep = 0
+                ns = orc.domain_reset(domain, prec="f32")
+            xs = orc.draw(seed, i, t, orc.BLK_RESET if trunc else orc.BLK_STEP)
+            hn = Th.T @ orc.fourier_project(domain, order, ns)
+            near[i] |= near_boundary(orc.policy_probs(orc.SOFTMAX, hn, tau=tau), xs)
+            a = orc.policy_sample(orc.SOFTMAX, hn, xs, tau=tau)
+            acts[t, i] = a
+            s = np.asarray(ns, dtype=np.float32)
+        out_w.append(w); out_T.append(Th)
+    return acts, out_w, out_T, near
+
+
+def test_driver_loop_against_a_restated_loop(orc):
+    N, K, cap, seed, gamma, lr, alpha, tau, domain, order = 32, 50, 20, 31, 0.95, 0.05, 0.002, 0.5, rsrl_amd.MOUNTAIN_CAR, 3
+    rng = np.random.default_rng(8)
+    with ctx(n_envs=N, seed=seed, gamma=gamma, lr=lr, alpha=alpha, tau=tau, max_episode_steps=cap) as c:
+        S0 = rand_states(orc, domain, N, rng)
+        S0[0, : N // 2] = rng.uniform(0.40, 0.49, size=N // 2).astype(np.float32)     # half of them start next to the goal: terminals on the way
+        S0[1, : N // 2] = rng.uniform(0.03, 0.07, size=N // 2).astype(np.float32)
+        A0 = rng.integers(0, 3, size=N).astype(np.int32)
+        c.states, c.actions = S0, A0
+        dev_acts, episodes, truncated = [], 0, 0
+        for _ in range(K):                                            # one batch-step per call: the same bits as train(K), every action seen
+            st = c.train(1)
+            episodes += st["episodes"]; truncated += st["episodes_truncated"]
+            dev_acts.append(c.actions)
+        acts, ws, Ts, near = _restated_loop(orc, domain, order, N, K, cap, seed, gamma, lr, alpha, tau, S0, A0)
+        same = (np.array(dev_acts) == acts).all(axis=0)               # an fp32 rounding may flip a softmax draw: that learner leaves the comparison
+        assert same.mean() >= 0.9, same
+        assert (same & ~near).mean() >= 0.5
+        for i in np.flatnonzero(same & ~near):
+            for got, want in ((c.get_weights(i)[:, 0], ws[i]), (c.get_policy_weights(i), Ts[i])):
+                assert np.max(np.abs(got - want)) <= 3e-6 * (1 + np.max(np.abs(want))) * K * 16, i
+        assert episodes > truncated > 0                               # terminals and caps both happened
+
+
+def _trait_loop(c, K, cap):
+    ep = c.episode_steps.astype(np.int64)
+    for _ in range(K):
+        frm, nxt, rew, term = c.domain_step(c.actions)
+        c.handle(frm, c.actions, rew, nxt, term)
+        ep += 1
+        mask = (term.astype(bool) | (ep >= cap)).astype(np.uint8)
+        c.domain_reset(mask)
+        ep[mask == 1] = 0
+        c.policy_sample()
+    c.episode_steps = ep.astype(np.uint32)
+
+
+def _snapshot(c):
+    return (np.stack([c.get_weights(i) for i in range(c.N)]), np.stack([c.get_policy_weights(i) for i in range(c.N)]), c.states, c.actions, c.episode_steps)
+
+
+def _diff(s1, s2):
+    names = ("weights", "theta", "states", "actions", "episode_steps")
+    return [n for n, x, y in zip(names, s1, s2) if not np.array_equal(x, y)]
+
+
+@pytest.mark.parametrize("domain,order", LOOP)
+def test_train_is_the_trait_loop_launch_depth_and_shard_invariant(domain, order):
+    N, K, cap = 64, 60, 23
+    kw = dict(domain=domain, order=order, n_envs=N, max_episode_steps=cap, tau=0.7, lr=0.02, alpha=0.2, gamma=0.97)
+    with ctx(**kw) as c:
+        c.reset()
+        c.timing_enable(True)
+        st = c.train(K)
+        assert c.timing_read()[2] == "k_train_tdac"
+        ref = _snapshot(c)
+        assert st["episodes"] > 0
+    with ctx(**kw) as c:
+        c.reset()
+        _trait_loop(c, K, cap)
+        assert _diff(_snapshot(c), ref) == []
+    for spl in (1, 7):
+        with ctx(steps_per_launch=spl, **kw) as c:
+            c.reset()
+            c.train(20)
+            c.train(1)
+            c.train(K - 21)
+            assert _diff(_snapshot(c), ref) == [], spl
+    shards = []
+    for off in (0, N // 2):
+        with ctx(env_offset=off, **dict(kw, n_envs=N // 2)) as c:
+            c.reset()
+            c.train(K)
+            shards.append(_snapshot(c))
+    joined = tuple(np.concatenate([shards[0][j], shards[1][j]], axis=0 if j < 2 else -1) for j in range(5))
+    assert _diff(joined, ref) == []
+
+
+def test_checkpoint_resumes_bitwise_and_refuses_other_agents(tmp_path):
+    kw = dict(n_envs=32, order=3, max_episode_steps=17, lr=0.02, alpha=0.2, tau=0.5)
+    path = os.path.join(str(tmp_path), "tdac.ckpt")
+    with ctx(**kw) as a:
+        a.reset()
+        a.train(25)
+        a.save_weights(path)
+        saved = (a.states, a.actions, a.episode_steps)
+        with ctx(**kw) as b:
+            b.load_weights(path)
+            b.states, b.actions, b.episode_steps = saved
+            assert _diff(_snapshot(a), _snapshot(b)) == []
+            a.train(20)
+            b.train(20)
+            assert _diff(_snapshot(a), _snapshot(b)) == []
+            assert a.checksum() == b.checksum()
+    with open(path, "rb") as f:
+        head = f.read(72)
+    assert int.from_bytes(head[8:12], "little") == 8 and int.from_bytes(head[40:44], "little") == 1 and int.from_bytes(head[52:56], "little") == 6
+    others = [dict(algo=rsrl_amd.ACTOR_CRITIC, policy=rsrl_amd.SOFTMAX), dict(algo=rsrl_amd.Q_ACTOR_CRITIC, policy=rsrl_amd.SOFTMAX),
+              dict(algo=rsrl_amd.TD, policy=rsrl_amd.RANDOM)]
+    for other in others:
+        with rsrl_amd.Context(domain=rsrl_amd.MOUNTAIN_CAR, **dict(kw, **other)) as o:
+            with pytest.raises(RsrlHipError) as e:
+                o.load_weights(path)
+            assert e.value.code == -1
+            opath = os.path.join(str(tmp_path), "other.ckpt")
+            o.save_weights(opath)
+            with ctx(**kw) as b:
+                with pytest.raises(RsrlHipError) as e:
+                    b.load_weights(opath)
+                assert e.value.code == -1
+
+
+def test_checksum_covers_theta():
+    with ctx(n_envs=8) as c:
+        c.reset()
+        c.train(5)
+        before = c.checksum()
+        th = c.get_policy_weights(3)
+        th[2, 1] += 0.25
+        c.set_policy_weights(th, 3)
+        assert c.checksum()[0] != before[0]
+        assert c.checksum()[1] == before[1]
+
+
+def test_refusals():
+    bad = [dict(basis=rsrl_amd.TILE_CODING), dict(order=6), dict(order=7), dict(domain=rsrl_amd.CART_POLE, order=7), dict(domain=rsrl_amd.CART_POLE, order=2),
+           dict(weight_mode=rsrl_amd.W_SHARED), dict(domain=rsrl_amd.CART_POLE, order=7, weight_dtype=rsrl_amd.W_BF16),
+           dict(domain=rsrl_amd.HIV_TREATMENT, order=1), dict(policy=rsrl_amd.EPSILON_GREEDY), dict(policy=rsrl_amd.GREEDY),
+           dict(agent_policy=rsrl_amd.SOFTMAX), dict(epsilon_decay=0.99)]
+    for b in bad:
+        with pytest.raises(RsrlHipError) as e:
+            ctx(**b)
+        assert e.value.code == -1 and "RSRL_TD_ACTOR_CRITIC" in str(e.value), b
+    with ctx(n_envs=4) as c:
+        for call in (lambda: c.get_traces(0), lambda: c.set_traces(np.zeros((c.F, 1)), 0), lambda: c.get_td_weights(0),
+                     lambda: c.set_td_weights(np.zeros((c.F, c.A)), 0)):
+            with pytest.raises(RsrlHipError) as e:
+                call()
+            assert e.value.code == -5
+
+
+def test_tdac_example_builds_and_runs(tmp_path):
+    exe = os.path.join(str(tmp_path), "tdac")
+    lib = os.path.join(ROOT, "rsrl_amd", "lib")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", os.path.join(ROOT, "examples", "tdac.cpp"), "-L" + lib, "-lrsrl_hip", "-Wl,-rpath," + lib, "-o", exe],
+                   check=True, timeout=300)
+    out = subprocess.run([exe, "64", "3", "200"], capture_output=True, text=True, timeout=300, check=True).stdout
+    assert "Batch 3:" in out and "OOS:" in out
+    tail = out.split("max |w| of learner 0:")[1]
+    wmax, tmax = float(tail.split()[0]), float(tail.split("max |theta| of learner 0:")[1].split()[0])
+    assert np.isfinite(wmax) and wmax > 0.0 and np.isfinite(tmax) and tmax > 0.0
+    assert "(16 weights)" in tail and "(48 weights)" in tail           # MountainCar, order 3: F = 16; V has one column, theta three
