@@ -123,7 +123,22 @@ typedef enum { RSRL_QLEARNING = 0, RSRL_SARSA = 1, RSRL_EXPECTED_SARSA = 2, RSRL
                 * (policy_sample / _mode / _probs / _prob, reset's initial sample, the rollouts; rsrl_hip_get/set_policy_weights).  rsrl_hip_handle's
                 * td_error_out and the statistics' sum |delta| are TD(0)'s delta.  Supported: as RSRL_ACTOR_CRITIC; everything else is EINVAL at create
                 * (kernels_tdac.hpp) */
-               RSRL_TD_ACTOR_CRITIC = 13 } rsrl_algo;
+               RSRL_TD_ACTOR_CRITIC = 13,
+               /* (14 is no algo.)  REINFORCE<Gibbs> (control/mc/reinforce.rs) and BaselineREINFORCE<B, Gibbs> (control/mc/baseline_reinforce.rs): Handler<&Batch>::handle
+                * walks the batch FORWARD and applies each transition's update in order, with theta as it stands after the previous one:
+                *   g = r + gamma * g  (0 before the first transition: the discounted sum of the rewards seen so far, NOT the return-to-go -- literal)
+                *   e = alpha * g  |  BaselineREINFORCE: alpha * (g - <B[:,a], phi(s)>)      p = softmax(theta^T phi(s) / tau)
+                *   theta[:,b] += e * (1[b==a] - p_b) * phi(s)                                (grad_log without 1/tau, as RSRL_ACTOR_CRITIC)
+                * The driver loop samples each episode from theta as it stood when the episode began (Trajectory::into_batch) and applies the updates
+                * online, which gives the bits of handling the episode's batch at its end: per learner it carries theta, the behaviour snapshot theta_b
+                * and the open episode's running return g; an episode's end (terminal or max_episode_steps) sets theta_b <- theta, g <- 0, as do
+                * rsrl_hip_reset and rsrl_hip_domain_reset for the learners they restart.  config: alpha, gamma, tau (lr is unused); policy must be
+                * RSRL_SOFTMAX and agent_policy -1.  theta starts at zero.  The POLICY side reads theta (policy_sample / _mode / _probs / _prob, reset's
+                * initial sample, the rollouts; rsrl_hip_get/set_policy_weights).  BaselineREINFORCE's baseline B (a VectorLFA, read-only) is the ctx's
+                * weights: get / set_weights and the Q operations read it.  REINFORCE has no value function: those are ESTATE.  rsrl_hip_handle is ESTATE
+                * (there is no Handler<&Transition>): rsrl_hip_handle_batch.  The statistics' sum |delta| is sum |g|.  Supported: as RSRL_ACTOR_CRITIC;
+                * everything else is EINVAL at create (kernels_reinforce.hpp) */
+               RSRL_REINFORCE = 15, RSRL_BASELINE_REINFORCE = 16 } rsrl_algo;
 /* rsrl::traces::{Accumulate, Saturate (Trace::replacing), Dutch}      traces.rs:188-240 */
 typedef enum { RSRL_TRACE_ACCUMULATE = 0, RSRL_TRACE_SATURATE = 1, RSRL_TRACE_DUTCH = 2 } rsrl_trace;
 /* rsrl::policies::{Greedy, EpsilonGreedy, Softmax, Random}
@@ -338,6 +353,16 @@ int rsrl_hip_tile_indices(rsrl_hip_ctx* ctx, const float* states, int64_t M, int
 int rsrl_hip_handle(rsrl_hip_ctx* ctx, const float* from_states, const int32_t* actions,
                     const float* rewards, const float* to_states, const uint8_t* terminal,
                     int64_t M, float* td_error_out);
+/* Handler<&Batch>::handle (rsrl_domains/src/lib.rs:210; reinforce.rs, baseline_reinforce.rs) for every learner of a REINFORCE ctx: learner i's batch
+ * is rows 0 .. lengths[i]-1 of its column (lengths[i] = 0: no batch, lengths[i] <= T), handled first to last with its own g from 0.  returns_out
+ * (optional) receives g at each handled transition and NaN in the rows past a learner's length.  theta_b and the carried g are not touched.  Like
+ * rsrl_hip_handle, one call is one batch-step (it advances rsrl_hip_step_count): the trait loop
+ *     domain_step -> (append the transition) -> handle_batch(lengths = episode length of the learners whose episode just ended, else 0)
+ *     -> domain_reset(ended) -> policy_sample(NULL)
+ * runs on the driver loop's draws.  Host or device arrays, as rsrl_hip_handle (host actions of the handled rows and host lengths are validated,
+ * device ones clamped).  ESTATE on every other agent. */
+int rsrl_hip_handle_batch(rsrl_hip_ctx* ctx, int64_t T, const float* states /*[T][D][N]*/, const int32_t* actions /*[T][N]*/,
+                          const float* rewards /*[T][N]*/, const uint32_t* lengths /*[N]*/, float* returns_out /*[T][N], optional*/);
 
 /* Policy::sample / Policy::mode / Function<(S,)> of the policy (action probabilities)
  *   policies/mod.rs:65-78; greedy.rs:30-44,77-83; epsilon_greedy.rs:38-45,74-82;
@@ -376,16 +401,24 @@ int rsrl_hip_set_td_weights(rsrl_hip_ctx* ctx, int64_t env_index, const float* v
  * ESTATE on every ctx that is not an ActorCritic one (whose get/set_traces and get/set_td_weights are ESTATE in turn) */
 int rsrl_hip_get_policy_weights(rsrl_hip_ctx* ctx, int64_t env_index, float* theta /*[F][A]*/);
 int rsrl_hip_set_policy_weights(rsrl_hip_ctx* ctx, int64_t env_index, const float* theta /*[F][A]*/);
+/* REINFORCE / BaselineREINFORCE: the open episode's state, so that a caller can save and restore it exactly (as get/set_q_carry): the behaviour
+ * snapshot theta_b of one learner (row-major f32[F][A], the policy theta when its episode began) and every learner's running return g.
+ * ESTATE on every other agent */
+int rsrl_hip_get_behaviour_weights(rsrl_hip_ctx* ctx, int64_t env_index, float* theta_b /*[F][A]*/);
+int rsrl_hip_set_behaviour_weights(rsrl_hip_ctx* ctx, int64_t env_index, const float* theta_b /*[F][A]*/);
+int rsrl_hip_get_return_carry(rsrl_hip_ctx* ctx, float* g /*[N]*/);
+int rsrl_hip_set_return_carry(rsrl_hip_ctx* ctx, const float* g /*[N]*/);
 /* Checkpoint of the approximator(s) (the reference's only persistence story is the optional serde
- * derive on the agents, rsrl/Cargo.toml:26).  File format version 2 (3 for files that carry QSigma's backups, 5 for sparse traces, 7 for ActorCritic, 8 for the TD ActorCritic),
+ * derive on the agents, rsrl/Cargo.toml:26).  File format version 2 (3 for files that carry QSigma's backups, 5 for sparse traces, 7 for ActorCritic, 8 for the TD ActorCritic,
+ * 9 for REINFORCE),
  * little-endian,
  * serialised field by field (no padding):
  *   offset  0  char magic[8] = "RSRLHIPW"
- *           8  u32  version = 2 (3 iff aux_kind = 3, 5 iff aux_kind = 4, 7 iff aux_kind = 5, 8 iff aux_kind = 6, 4 with the epsilon schedule)
+ *           8  u32  version = 2 (3 iff aux_kind = 3, 5 iff aux_kind = 4, 7 iff aux_kind = 5, 8 iff aux_kind = 6, 9 iff aux_kind = 7, 4 with the epsilon schedule)
  *          12  i32  domain, basis, order, n_tilings, tiles_per_dim, weight_mode, F, A (weight columns),
  *                   algo, weight_dtype, aux_kind (0 none, 1 eligibility traces, 2 GreedyGQ's fa_td weights,
  *                   3 QSigma's n-step backups, 4 sparse traces over a shared table, 5 ActorCritic's theta,
- *                   6 the TD ActorCritic's theta)                                                                 [11 x i32]
+ *                   6 the TD ActorCritic's theta, 7 REINFORCE's theta and open episode)                          [11 x i32]
  *          56  i64  n_learners (1 in shared mode)
  *          64  u64  step_count
  *          72  n_learners x f32[F][A] weights in the reference's row-major (F, A) order (Parameterised::weights,
@@ -394,6 +427,9 @@ int rsrl_hip_set_policy_weights(rsrl_hip_ctx* ctx, int64_t env_index, const floa
  *              written as file version 7, which no other configuration reads);
  *              if aux_kind is 6 (file version 8, which no other configuration reads; A = 1, the weights are V's w): n_learners x f32[F][n_actions]
  *              of the actor's theta;
+ *              if aux_kind is 7 (file version 9, which no other configuration reads; RSRL_REINFORCE / RSRL_BASELINE_REINFORCE): the weights section
+ *              is BaselineREINFORCE's baseline B, and is ABSENT for REINFORCE (no value function); then n_learners x f32[F][A] of theta,
+ *              n_learners x f32[F][A] of theta_b, f32 g[N];
  *              if aux_kind is 3 (file version 3): u32 head[N], u32 len[N], f32 entries[D + 5][n_steps][N] -- every learner's
  *              Backup ring {s, a, q, residual, pi, mu} (q_sigma.rs:30-63), so that a QSigma run with n_steps > 1 resumes
  *              bit-identically too.  Files of version 2 (no aux_kind 3) are still read.

@@ -11,6 +11,7 @@ FOURIER, TILE_CODING = 0, 1
 QLEARNING, SARSA, EXPECTED_SARSA, SARSA_LAMBDA, Q_LAMBDA, PAL, GREEDY_GQ, TD, TD_LAMBDA, Q_SIGMA = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 ACTOR_CRITIC, Q_ACTOR_CRITIC = 10, 11          # ActorCritic (control/ac.rs) with a Gibbs actor and a SARSA critic: a2c.rs's closure / QCritic
 TD_ACTOR_CRITIC = 13                           # ActorCritic::tdac: the Gibbs actor with TDCritic over a TD(0) V (12 is no algo)
+REINFORCE, BASELINE_REINFORCE = 15, 16         # (14 is no algo) control/mc: REINFORCE<Gibbs>, BaselineREINFORCE<B, Gibbs> (Handler<&Batch>: handle_batch)
 TRACE_ACCUMULATE, TRACE_SATURATE, TRACE_DUTCH = 0, 1, 2
 GREEDY, EPSILON_GREEDY, SOFTMAX, RANDOM = 0, 1, 2, 3
 W_PER_ENV, W_SHARED = 0, 1
@@ -267,6 +268,16 @@ class Context:
                                            _p(_in(terminal, np.uint8, (M,))), M, _p(td)))
         return td
 
+    def handle_batch(self, states, actions, rewards, lengths, returns=False):
+        """Handler<&Batch>::handle of REINFORCE / BASELINE_REINFORCE for every learner: states (T, D, N), actions / rewards (T, N), lengths (N,) --
+        learner i's batch is rows 0 .. lengths[i]-1 of its column.  returns=True: also the running return g at each handled transition, (T, N)
+        (NaN where nothing was handled).  One batch-step, as handle"""
+        T = int(np.shape(rewards)[0])
+        ret = np.full((T, self.N), np.nan, dtype=np.float32) if returns else None
+        _abi.check(self._L.rsrl_hip_handle_batch(self._h, T, _p(_in(states, np.float32, (T, self.D, self.N))), _p(_in(actions, np.int32, (T, self.N))),
+                                                 _p(_in(rewards, np.float32, (T, self.N))), _p(_in(lengths, np.uint32, (self.N,))), _p(ret)))
+        return ret
+
     def policy_sample(self, states=None):
         """Policy::sample.  states = None: the ctx's OWN envs (env.emit().state()) -- the driver loop's behaviour sample of the current batch-step
         (what rsrl_hip_train draws); the actions also become the ctx's pending ones"""
@@ -343,6 +354,26 @@ class Context:
 
     def set_policy_weights(self, theta, env_index=0):
         _abi.check(self._L.rsrl_hip_set_policy_weights(self._h, int(env_index), _p(_in(theta, np.float32, (self.F, self.A)))))
+
+    def get_behaviour_weights(self, env_index=0):
+        """REINFORCE's behaviour snapshot theta_b of one learner: its policy weights when the open episode began, f32 (F, A)"""
+        out = np.empty((self.F, self.A), dtype=np.float32)
+        _abi.check(self._L.rsrl_hip_get_behaviour_weights(self._h, int(env_index), _p(out)))
+        return out
+
+    def set_behaviour_weights(self, theta_b, env_index=0):
+        _abi.check(self._L.rsrl_hip_set_behaviour_weights(self._h, int(env_index), _p(_in(theta_b, np.float32, (self.F, self.A)))))
+
+    @property
+    def return_carry(self):
+        """REINFORCE's running return g of every learner's open episode, f32 (N,)"""
+        out = np.empty(self.N, dtype=np.float32)
+        _abi.check(self._L.rsrl_hip_get_return_carry(self._h, _p(out)))
+        return out
+
+    @return_carry.setter
+    def return_carry(self, g):
+        _abi.check(self._L.rsrl_hip_set_return_carry(self._h, _p(_in(g, np.float32, (self.N,)))))
 
     def save_weights(self, path):
         _abi.check(self._L.rsrl_hip_save_weights(self._h, str(path).encode()))

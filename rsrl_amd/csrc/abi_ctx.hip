@@ -40,6 +40,7 @@ static AgentFamily classify(const rsrl_hip_config& cfg, size_t w_elems) {
     if (cfg.domain == RSRL_HIV_TREATMENT) return F::Hiv;
     if (is_ac(al)) return F::AcReg;                         // (before the one-step agents: carries_q is false, no trait fast path)
     if (is_tdac(al)) return F::TdAcReg;                     // (before the prediction agents: W is V's one column, but the policy is the actor's)
+    if (is_reinforce(al)) return F::ReinforceReg;
     if (cfg.weight_mode == RSRL_W_SHARED) return fourier ? F::SharedDense : (is_sparse_lambda(cfg) ? F::SharedSparseLambda : F::SharedTile);
     if (wave && is_wave_aux_algo(al)) return F::WaveAux;
     if (is_pred(al)) return tile ? F::TdTile : (reg ? F::TdReg : F::TdGeneric);
@@ -76,6 +77,7 @@ static const char* train_kernel_name(const rsrl_hip_ctx* c) {
     case AgentFamily::Hiv: return "k_hiv_train";
     case AgentFamily::AcReg: return "k_train_ac";
     case AgentFamily::TdAcReg: return "k_train_tdac";
+    case AgentFamily::ReinforceReg: return "k_train_reinforce";
     }
     return "";
 }
@@ -138,6 +140,8 @@ int rsrl_hip_destroy(rsrl_hip_ctx* c) {
     if (c->qcache) (void)hipFree(c->qcache);
     if (c->tq_key) (void)hipFree(c->tq_key);
     if (c->Z) (void)hipFree(c->Z);
+    if (c->Zb) (void)hipFree(c->Zb);
+    if (c->ret_g) (void)hipFree(c->ret_g);
     if (c->hiv_y) (void)hipFree(c->hiv_y);
     if (c->eps) (void)hipFree(c->eps);
     if (c->flags) (void)hipFree(c->flags);
@@ -172,7 +176,7 @@ static int check_config(const rsrl_hip_config& cfg) {
     const int D = kDomainShape[cfg.domain][0], A = kDomainShape[cfg.domain][1];
     if (cfg.n_envs < 1) return fail(RSRL_HIP_EINVAL, "n_envs must be >= 1");
     if (cfg.n_envs + cfg.env_offset > (int64_t)0xffffffffLL || cfg.env_offset < 0) return fail(RSRL_HIP_EINVAL, "global env ids must fit 32 bits");
-    if (cfg.algo < 0 || cfg.algo > RSRL_TD_ACTOR_CRITIC || cfg.algo == 12) return fail(RSRL_HIP_EINVAL, "unknown algo %d", cfg.algo);
+    if (cfg.algo < 0 || cfg.algo > RSRL_BASELINE_REINFORCE || cfg.algo == 12 || cfg.algo == 14) return fail(RSRL_HIP_EINVAL, "unknown algo %d", cfg.algo);
     if (cfg.policy < 0 || cfg.policy > RSRL_RANDOM) return fail(RSRL_HIP_EINVAL, "unknown policy %d", cfg.policy);
     // Softmax::new panics for |tau| < 1e-7 (policies/softmax.rs:63-66)
     if (cfg.policy == RSRL_SOFTMAX && std::fabs(cfg.tau) < 1e-7) return fail(RSRL_HIP_EINVAL, "Tau parameter in Softmax must be non-zero.");
@@ -226,6 +230,16 @@ static int check_config(const rsrl_hip_config& cfg) {
             return fail(RSRL_HIP_EINVAL, "the TD ActorCritic (RSRL_TD_ACTOR_CRITIC) supports per-learner f32 weights on the register-family Fourier orders "
                                          "(MountainCar 1-5, CartPole 1, Acrobot 1) with policy = Softmax (the Gibbs actor), agent_policy = -1 and no epsilon "
                                          "schedule (got domain %d, basis %d, order %d, weight mode %d, dtype %d, policy %d, agent_policy %d, epsilon_decay %g)",
+                        cfg.domain, cfg.basis, cfg.order, cfg.weight_mode, cfg.weight_dtype, cfg.policy, cfg.agent_policy, cfg.epsilon_decay);
+        return RSRL_HIP_OK;
+    }
+    if (is_reinforce(al)) {
+        // train_reinforce.hip: the same configurations as ActorCritic's
+        if (!reg || !per_env || !f32 || cfg.policy != RSRL_SOFTMAX || cfg.agent_policy != -1 || esched)
+            return fail(RSRL_HIP_EINVAL, "%s supports per-learner f32 weights on the register-family Fourier orders (MountainCar 1-5, CartPole 1, Acrobot 1) "
+                                         "with policy = Softmax (the Gibbs policy), agent_policy = -1 and no epsilon schedule (got domain %d, basis %d, order %d, "
+                                         "weight mode %d, dtype %d, policy %d, agent_policy %d, epsilon_decay %g)",
+                        al == RSRL_REINFORCE ? "REINFORCE (RSRL_REINFORCE)" : "BaselineREINFORCE (RSRL_BASELINE_REINFORCE)",
                         cfg.domain, cfg.basis, cfg.order, cfg.weight_mode, cfg.weight_dtype, cfg.policy, cfg.agent_policy, cfg.epsilon_decay);
         return RSRL_HIP_OK;
     }
@@ -350,6 +364,15 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
         c->z_bytes = (c->family == AgentFamily::TdAcReg ? (size_t)aux_cols(c) * c->F * (size_t)N : c->w_elems) * 4;      // (TdAcReg: theta, A columns)
         HIP_TRY(hipMalloc((void**)&c->Z, c->z_bytes));
         HIP_TRY(hipMemsetAsync(c->Z, 0, c->z_bytes, c->stream));                  // Trace::zeros (ActorCritic's theta: LFA::vector zero-initialises)
+    } else if (c->family == AgentFamily::ReinforceReg) {
+        // theta (Z) and theta_b (Zb) of W's shape, both zero (LFA::vector); g = 0.  W is the baseline B (REINFORCE: allocated, never read)
+        c->z_bytes = c->w_elems * 4;
+        HIP_TRY(hipMalloc((void**)&c->Z, c->z_bytes));
+        HIP_TRY(hipMemsetAsync(c->Z, 0, c->z_bytes, c->stream));
+        HIP_TRY(hipMalloc((void**)&c->Zb, c->z_bytes));
+        HIP_TRY(hipMemsetAsync(c->Zb, 0, c->z_bytes, c->stream));
+        HIP_TRY(hipMalloc((void**)&c->ret_g, sizeof(float) * (size_t)N));
+        HIP_TRY(hipMemsetAsync(c->ret_g, 0, sizeof(float) * (size_t)N, c->stream));
     }
     if (shared) {
         HIP_TRY(hipMalloc((void**)&c->flags, (size_t)N));
@@ -488,6 +511,8 @@ int rsrl_hip_reset(rsrl_hip_ctx* c) {
     // QSigma: fresh episodes start from an empty n-step backup (as after a terminal transition, q_sigma.rs:154) -- entries of the
     // abandoned trajectories must not be mixed into the first anchor updates of the new ones
     if (c->qs_len) HIP_TRY(hipMemsetAsync(c->qs_len, 0, sizeof(uint32_t) * (size_t)c->cfg.n_envs, c->stream));
+    // REINFORCE: every episode starts anew, theta_b <- theta, g <- 0 (the initial sample below reads theta, which theta_b now is)
+    if (c->family == AgentFamily::ReinforceReg) { launch_reinforce_restart(c->stream, make_reinforce(c), c->cfg.n_envs, (int64_t)c->F * c->A, nullptr); KCHECK(); }
     const Common k = make_policy_common(c);              // the initial policy.sample (ActorCritic: the actor's theta)
     const BasisGeom g = make_geom(c);
     if (c->family == AgentFamily::Hiv) {

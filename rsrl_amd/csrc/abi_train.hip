@@ -214,7 +214,7 @@ static inline int64_t fuse_depth(const rsrl_hip_ctx* c) {
     // 4 096 is a 2.9 ms launch at 65 536 learners
     switch (c->family) {
     case AgentFamily::TdReg: case AgentFamily::GqReg: case AgentFamily::LambdaReg: case AgentFamily::RegStep: case AgentFamily::RegFused: case AgentFamily::AcReg:
-    case AgentFamily::TdAcReg:
+    case AgentFamily::TdAcReg: case AgentFamily::ReinforceReg:
         return 4096;
     // HIVTreatment: one batch-step is 1 000 f64 RK4 sub-steps per learner, ~1 ms at 65 536 learners -- 16 keep a launch in the tens of milliseconds
     case AgentFamily::Hiv: return 16;
@@ -440,6 +440,9 @@ int launch_agent(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, uint64_t 
         ok = launch_ac(cf.domain, cf.order, cf.algo == RSRL_Q_ACTOR_CRITIC ? AC_CRITIC_Q : AC_CRITIC_ADVANTAGE, grid, block, c->stream, k, c->Z, t, chunk, d_stats, io);
         break;
     case AgentFamily::TdAcReg: ok = launch_tdac(cf.domain, cf.order, grid, block, c->stream, k, c->Z, t, chunk, d_stats, io); break;
+    case AgentFamily::ReinforceReg:      // (io: rsrl_hip_handle refuses these agents before it gets here; rsrl_hip_handle_batch launches its own)
+        ok = !io && launch_reinforce(cf.domain, cf.order, cf.algo == RSRL_BASELINE_REINFORCE, grid, block, c->stream, k, make_reinforce(c), t, chunk, d_stats, nullptr);
+        break;
     default: ok = false; break;      // (the shared-W families: enqueue_shared_step)
     }
     if (!ok) return NO_MODEL(c);

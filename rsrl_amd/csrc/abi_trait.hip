@@ -114,6 +114,8 @@ int rsrl_hip_domain_reset(rsrl_hip_ctx* c, const uint8_t* mask) {
     TRY(stage_in(c, 0, mask, (size_t)N, &d_mask));
     const Common k = make_common(c);
     TRY(launch_domain_reset(c, k, d_mask));
+    // REINFORCE: the restarted learners begin new episodes, sampled from theta as it stands (theta_b <- theta, g <- 0)
+    if (c->family == AgentFamily::ReinforceReg) { launch_reinforce_restart(c->stream, make_reinforce(c), N, (int64_t)c->F * c->A, d_mask); KCHECK(); }
     if (mask && !is_device_ptr(mask)) HIP_TRY(hipStreamSynchronize(c->stream));
     return RSRL_HIP_OK;
 }
@@ -127,6 +129,9 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
     // the TD ActorCritic: its value side is V(s) (no action values to search or weigh), its policy side the actor's theta
     if (is_tdac(c->cfg.algo) && (op == QOP_FIND_MAX || op == QOP_FIND_MIN || op == QOP_EXPECTED))
         return fail(RSRL_HIP_ESTATE, "the TD ActorCritic's critic is a state-value function (use rsrl_hip_q_evaluate for V(s), the policy operations for the actor)");
+    // REINFORCE has no value function (BaselineREINFORCE's is the baseline B): only the policy's operations and the projection
+    if (c->cfg.algo == RSRL_REINFORCE && (op == QOP_EVALUATE || op == QOP_FIND_MAX || op == QOP_FIND_MIN || op == QOP_EXPECTED))
+        return fail(RSRL_HIP_ESTATE, "REINFORCE has no value function (use the policy operations; BaselineREINFORCE's value side is its baseline)");
     HIP_TRY(hipSetDevice(c->cfg.device));
     const float* d_states; OutBuf<float> of; OutBuf<int32_t> oi;
     TRY(stage_in(c, 0, states, (size_t)c->D * M_, &d_states));
@@ -291,6 +296,8 @@ int rsrl_hip_handle(rsrl_hip_ctx* c, const float* from_states, const int32_t* ac
     CHECK_CTX(c);
     if (!from_states || !actions || !rewards || !to_states || !terminal) return fail(RSRL_HIP_EINVAL, "null argument");
     if (M < 1 || M > c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "bad batch size");
+    if (c->family == AgentFamily::ReinforceReg)
+        return fail(RSRL_HIP_ESTATE, "REINFORCE and BaselineREINFORCE handle whole batches only (Handler<&Batch>): use rsrl_hip_handle_batch");
     // the transition rsrl_hip_domain_step has just been handed (same arrays, every learner): accepted, launched with it (rsrl_hip_domain_step)
     if (c->tp.stage == 1 && from_states == c->tp.from && actions == c->tp.act && rewards == c->tp.rew && to_states == c->tp.to && terminal == c->tp.term &&
         M == c->cfg.n_envs && (!td_error_out || is_device_ptr(td_error_out))) {
@@ -387,6 +394,51 @@ int rsrl_hip_handle(rsrl_hip_ctx* c, const float* from_states, const int32_t* ac
                         // bf16 stochastic rounding) advance exactly as they do inside rsrl_hip_train
     bool sync = !all_device;   // host inputs are staged asynchronously: they must have been read when the call returns; device arrays are asynchronous
     TRY(flush_out(c, &otd, &sync));
+    if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
+    return RSRL_HIP_OK;
+}
+
+int rsrl_hip_handle_batch(rsrl_hip_ctx* c, int64_t T, const float* states, const int32_t* actions, const float* rewards, const uint32_t* lengths,
+                          float* returns_out) {
+    CHECK_CTX(c);
+    if (c->family != AgentFamily::ReinforceReg)
+        return fail(RSRL_HIP_ESTATE, "only REINFORCE and BaselineREINFORCE handle whole batches (Handler<&Batch>); the other agents handle transitions (rsrl_hip_handle)");
+    if (T < 0) return fail(RSRL_HIP_EINVAL, "bad batch length T = %lld", (long long)T);
+    if (!lengths || (T > 0 && (!states || !actions || !rewards))) return fail(RSRL_HIP_EINVAL, "null argument");
+    FLUSH(c);
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    const int64_t N = c->cfg.n_envs;
+    // host arrays are validated where a learner's batch reads them (its rows 0 .. lengths[i]-1); device arrays are clamped by the kernel instead
+    const bool host_len = !is_device_ptr(lengths), host_act = actions && !is_device_ptr(actions);
+    if (host_len)
+        for (int64_t i = 0; i < N; ++i)
+            if ((int64_t)lengths[i] > T) return fail(RSRL_HIP_EINVAL, "lengths[%lld] = %u is more than the batch's %lld rows", (long long)i, lengths[i], (long long)T);
+    if (host_len && host_act)
+        for (int64_t i = 0; i < N; ++i)
+            for (int64_t t = 0; t < (int64_t)lengths[i]; ++t)
+                if (actions[t * N + i] < 0 || actions[t * N + i] >= c->A)
+                    return fail(RSRL_HIP_EINVAL, "actions[%lld][%lld] = %d is outside [0, %d)", (long long)t, (long long)i, actions[t * N + i], c->A);
+    const bool all_device = !host_len && (T == 0 || (is_device_ptr(states) && !host_act && is_device_ptr(rewards))) && (!returns_out || is_device_ptr(returns_out));
+    ReinforceBatch io;
+    const size_t TN = (size_t)T * (size_t)N;
+    TRY(stage_in(c, 0, T > 0 ? states : nullptr, TN * (size_t)c->D, &io.states));
+    TRY(stage_in(c, 1, T > 0 ? actions : nullptr, TN, &io.act));
+    TRY(stage_in(c, 2, T > 0 ? rewards : nullptr, TN, &io.rew));
+    TRY(stage_in(c, 3, lengths, (size_t)N, &io.len));
+    OutBuf<float> oret;
+    TRY(stage_out(c, 4, T > 0 ? returns_out : nullptr, TN, &oret));
+    io.T = T; io.ret_out = oret.dev;
+    if (T > 0) {
+        const Common k = make_common(c);
+        if (!launch_reinforce(c->cfg.domain, c->cfg.order, c->cfg.algo == RSRL_BASELINE_REINFORCE, dim3(grid_for(N)), dim3(kBlock), c->stream, k,
+                              make_reinforce(c), c->t, 1, nullptr, &io))
+            return NO_MODEL(c);
+        KCHECK();
+    }
+    c->q_valid = false;
+    c->t += 1;          // one handle_batch call = one batch-step, as rsrl_hip_handle: the trait loop stays on the driver loop's draw streams
+    bool sync = !all_device;
+    TRY(flush_out(c, &oret, &sync));
     if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
     return RSRL_HIP_OK;
 }

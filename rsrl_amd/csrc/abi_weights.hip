@@ -4,8 +4,12 @@
 
 RSRL_API_BEGIN
 
+static int no_value_function(rsrl_hip_ctx* c) {
+    return fail(RSRL_HIP_ESTATE, "REINFORCE has no value function (its policy's weights: rsrl_hip_get/set_policy_weights)");
+}
 int rsrl_hip_get_weights(rsrl_hip_ctx* c, int64_t env_index, float* w) {
     CHECK_CTX(c); FLUSH(c); if (!w) return fail(RSRL_HIP_EINVAL, "null argument");
+    if (c->cfg.algo == RSRL_REINFORCE) return no_value_function(c);
     const bool shared = c->cfg.weight_mode == RSRL_W_SHARED;
     if (!shared && (env_index < 0 || env_index >= c->cfg.n_envs)) return fail(RSRL_HIP_EINVAL, "env_index out of range");
     HIP_TRY(hipSetDevice(c->cfg.device));
@@ -26,6 +30,7 @@ int rsrl_hip_get_weights(rsrl_hip_ctx* c, int64_t env_index, float* w) {
 int rsrl_hip_set_weights(rsrl_hip_ctx* c, int64_t env_index, const float* w) {
     CHECK_CTX(c); FLUSH(c);
     c->q_valid = false; c->tq_valid = false; if (!w) return fail(RSRL_HIP_EINVAL, "null argument");
+    if (c->cfg.algo == RSRL_REINFORCE) return no_value_function(c);
     const bool shared = c->cfg.weight_mode == RSRL_W_SHARED;
     if (!shared && (env_index < 0 || env_index >= c->cfg.n_envs)) return fail(RSRL_HIP_EINVAL, "env_index out of range");
     HIP_TRY(hipSetDevice(c->cfg.device));
@@ -109,16 +114,61 @@ int rsrl_hip_set_td_weights(rsrl_hip_ctx* c, int64_t env_index, const float* v) 
 int rsrl_hip_get_policy_weights(rsrl_hip_ctx* c, int64_t env_index, float* theta) {
     if (!theta) return fail(RSRL_HIP_EINVAL, "null argument");
     CHECK_CTX(c);
-    if (c->family != AgentFamily::AcReg && c->family != AgentFamily::TdAcReg)
-        return fail(RSRL_HIP_ESTATE, "only ActorCritic has policy weights of its own (its policy reads Q otherwise)");
+    if (!has_policy_weights(c)) return fail(RSRL_HIP_ESTATE, "only ActorCritic and REINFORCE have policy weights of their own (the policy reads Q otherwise)");
     return traces_rw(c, env_index, theta, nullptr);
 }
 int rsrl_hip_set_policy_weights(rsrl_hip_ctx* c, int64_t env_index, const float* theta) {
     if (!theta) return fail(RSRL_HIP_EINVAL, "null argument");
     CHECK_CTX(c);
-    if (c->family != AgentFamily::AcReg && c->family != AgentFamily::TdAcReg)
-        return fail(RSRL_HIP_ESTATE, "only ActorCritic has policy weights of its own (its policy reads Q otherwise)");
+    if (!has_policy_weights(c)) return fail(RSRL_HIP_ESTATE, "only ActorCritic and REINFORCE have policy weights of their own (the policy reads Q otherwise)");
     return traces_rw(c, env_index, nullptr, theta);
+}
+// REINFORCE's open episode: the behaviour snapshot theta_b of one learner (f32[F][A], the weights' order) and every learner's running return g
+static int behaviour_rw(rsrl_hip_ctx* c, int64_t env_index, float* out, const float* in) {
+    CHECK_CTX(c); FLUSH(c);
+    if (c->family != AgentFamily::ReinforceReg) return fail(RSRL_HIP_ESTATE, "only REINFORCE and BaselineREINFORCE carry a behaviour snapshot of their policy");
+    if (env_index < 0 || env_index >= c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "env_index out of range");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    const int n = c->F * c->A;
+    if (out) {
+        OutBuf<float> oz;
+        TRY(stage_out(c, 0, out, (size_t)n, &oz));
+        hipLaunchKernelGGL(k_weights_get, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->Zb, false, c->w_stride, env_index, c->F, c->A, oz.dev);
+        KCHECK();
+        bool sync = false; TRY(flush_out(c, &oz, &sync));
+        if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
+    } else {
+        const float* d_z;
+        TRY(stage_in(c, 0, in, (size_t)n, &d_z));
+        hipLaunchKernelGGL(k_weights_set, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->Zb, false, c->w_stride, env_index, c->F, c->A, d_z);
+        KCHECK();
+        if (!is_device_ptr(in)) HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return RSRL_HIP_OK;
+}
+int rsrl_hip_get_behaviour_weights(rsrl_hip_ctx* c, int64_t env_index, float* theta_b) {
+    if (!theta_b) return fail(RSRL_HIP_EINVAL, "null argument");
+    return behaviour_rw(c, env_index, theta_b, nullptr);
+}
+int rsrl_hip_set_behaviour_weights(rsrl_hip_ctx* c, int64_t env_index, const float* theta_b) {
+    if (!theta_b) return fail(RSRL_HIP_EINVAL, "null argument");
+    return behaviour_rw(c, env_index, nullptr, theta_b);
+}
+int rsrl_hip_get_return_carry(rsrl_hip_ctx* c, float* g) {
+    CHECK_CTX(c); FLUSH(c); if (!g) return fail(RSRL_HIP_EINVAL, "null argument");
+    if (c->family != AgentFamily::ReinforceReg) return fail(RSRL_HIP_ESTATE, "only REINFORCE and BaselineREINFORCE carry an episode's running return");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(hipMemcpyAsync(g, c->ret_g, sizeof(float) * (size_t)c->cfg.n_envs, hipMemcpyDefault, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RSRL_HIP_OK;
+}
+int rsrl_hip_set_return_carry(rsrl_hip_ctx* c, const float* g) {
+    CHECK_CTX(c); FLUSH(c); if (!g) return fail(RSRL_HIP_EINVAL, "null argument");
+    if (c->family != AgentFamily::ReinforceReg) return fail(RSRL_HIP_ESTATE, "only REINFORCE and BaselineREINFORCE carry an episode's running return");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(hipMemcpyAsync(c->ret_g, g, sizeof(float) * (size_t)c->cfg.n_envs, hipMemcpyDefault, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RSRL_HIP_OK;
 }
 
 // ---- checkpoint: header + every learner's weights in the reference (F, A) order -----------------------------------
@@ -130,6 +180,7 @@ constexpr uint32_t kCkptVersionSparse = 6;    // files carrying aux_kind 4 (the 
 constexpr uint32_t kCkptVersionSparse5 = 5;   // ... as round 5 wrote them (no n_envs / env_offset in front of the lengths): still read
 constexpr uint32_t kCkptVersionAc = 7;        // files carrying aux_kind 5 (ActorCritic's theta): laid out as aux_kind 1 / 2, a version of their own
 constexpr uint32_t kCkptVersionTdac = 8;      // files carrying aux_kind 6 (the TD ActorCritic's theta, f32[F][n_actions] against V's f32[F][1]): ditto
+constexpr uint32_t kCkptVersionReinforce = 9; // files carrying aux_kind 7 (REINFORCE's theta, theta_b and g; no weights section for REINFORCE itself)
 constexpr int64_t kSparseChunk = 4096;        // learners per staging chunk of the sparse lists
 constexpr size_t kCkptHeaderBytes = 72;
 struct Ckpt {
@@ -139,14 +190,18 @@ struct Ckpt {
 };
 // 1 = eligibility traces, 2 = fa_td weights (both: a second matrix of W's shape), 3 = QSigma's per-learner n-step backups,
 // 4 = every learner's sparse trace over the shared table (the lists, compact), 5 = ActorCritic's theta (a second matrix of W's shape),
-// 6 = the TD ActorCritic's theta (a second matrix of A columns, W has one)
+// 6 = the TD ActorCritic's theta (a second matrix of A columns, W has one), 7 = REINFORCE's theta (a second matrix of W's shape), then its
+// open episode: theta_b (a third) and g[N]
 int aux_kind_of(const rsrl_hip_ctx* c) {
     if (c->family == AgentFamily::AcReg) return 5;
     if (c->family == AgentFamily::TdAcReg) return 6;
+    if (c->family == AgentFamily::ReinforceReg) return 7;
     return c->sp_keys ? 4 : (c->qs_buf ? 3 : (!c->Z ? 0 : (c->cfg.algo == RSRL_GREEDY_GQ ? 2 : 1)));
 }
 // aux_kinds whose payload is a second n_learners x f32[F][aux_cols] after the weights
-bool aux_is_matrix(int32_t kind) { return kind == 1 || kind == 2 || kind == 5 || kind == 6; }
+bool aux_is_matrix(int32_t kind) { return kind == 1 || kind == 2 || kind == 5 || kind == 6 || kind == 7; }
+// the weights section: every file has one except REINFORCE's (no value function; BaselineREINFORCE's is the baseline B)
+bool has_weights_section(const rsrl_hip_ctx* c) { return c->cfg.algo != RSRL_REINFORCE; }
 size_t qs_floats(const rsrl_hip_ctx* c) { return (size_t)(c->D + 5) * (size_t)c->cfg.n_steps * (size_t)c->cfg.n_envs; }
 Ckpt ckpt_of(const rsrl_hip_ctx* c) {
     Ckpt h{};
@@ -164,7 +219,7 @@ uint64_t get64(const uint8_t*& p) { uint64_t v = 0; for (int i = 0; i < 8; ++i) 
 void ckpt_encode(const Ckpt& h, uint8_t (&buf)[kCkptHeaderBytes]) {
     uint8_t* p = buf;
     memcpy(p, "RSRLHIPW", 8); p += 8;
-    put32(p, h.has_eps ? kCkptVersionEps : (h.aux_kind == 6 ? kCkptVersionTdac : (h.aux_kind == 5 ? kCkptVersionAc : (h.aux_kind == 4 ? kCkptVersionSparse :
+    put32(p, h.has_eps ? kCkptVersionEps : h.aux_kind == 7 ? kCkptVersionReinforce : (h.aux_kind == 6 ? kCkptVersionTdac : (h.aux_kind == 5 ? kCkptVersionAc : (h.aux_kind == 4 ? kCkptVersionSparse :
                                                                                                                           (h.aux_kind == 3 ? kCkptVersion : 2u)))));
     const int32_t f[11] = {h.domain, h.basis, h.order, h.n_tilings, h.tiles_per_dim, h.weight_mode, h.F, h.A, h.algo, h.weight_dtype, h.aux_kind};
     for (int32_t v : f) put32(p, (uint32_t)v);
@@ -192,12 +247,21 @@ int rsrl_hip_save_weights(rsrl_hip_ctx* c, const char* path) {
     int rc = RSRL_HIP_OK;
     if (fwrite(hdr, 1, sizeof(hdr), f) != sizeof(hdr)) rc = fail(RSRL_HIP_EINVAL, "short write to %s", path);
     std::vector<float> w;
-    for (int pass = 0; pass < (aux_is_matrix(h.aux_kind) ? 2 : 1); ++pass) {          // every learner's weights, then every learner's auxiliary matrix
+    for (int pass = has_weights_section(c) ? 0 : 1; pass < (aux_is_matrix(h.aux_kind) ? 2 : 1); ++pass) {     // every learner's weights, then every learner's auxiliary matrix
         w.resize((size_t)c->F * (pass == 0 ? c->Aw : aux_cols(c)));
         for (int64_t i = 0; rc == RSRL_HIP_OK && i < h.n_learners; ++i) {
             rc = pass == 0 ? rsrl_hip_get_weights(c, i, w.data()) : traces_rw(c, i, w.data(), nullptr);
             if (rc == RSRL_HIP_OK && fwrite(w.data(), sizeof(float), w.size(), f) != w.size()) rc = fail(RSRL_HIP_EINVAL, "short write to %s", path);
         }
+    }
+    if (h.aux_kind == 7) {                                              // REINFORCE's open episode: every learner's theta_b, then g[N]
+        for (int64_t i = 0; rc == RSRL_HIP_OK && i < h.n_learners; ++i) {
+            rc = behaviour_rw(c, i, w.data(), nullptr);
+            if (rc == RSRL_HIP_OK && fwrite(w.data(), sizeof(float), w.size(), f) != w.size()) rc = fail(RSRL_HIP_EINVAL, "short write to %s", path);
+        }
+        std::vector<float> g((size_t)c->cfg.n_envs);
+        if (rc == RSRL_HIP_OK) rc = rsrl_hip_get_return_carry(c, g.data());
+        if (rc == RSRL_HIP_OK && fwrite(g.data(), sizeof(float), g.size(), f) != g.size()) rc = fail(RSRL_HIP_EINVAL, "short write to %s", path);
     }
     if (rc == RSRL_HIP_OK && h.aux_kind == 3) {                        // QSigma: ring heads, lengths, entries (SoA [field][slot][learner])
         const size_t N = (size_t)c->cfg.n_envs, nf = qs_floats(c);
@@ -267,12 +331,13 @@ int rsrl_hip_load_weights(rsrl_hip_ctx* c, const char* path) {
     int rc = RSRL_HIP_OK;
     if (fread(hdr, 1, sizeof(hdr), f) != sizeof(hdr) || !ckpt_decode(hdr, &h, &version)) rc = fail(RSRL_HIP_EINVAL, "%s is not a rsrl_hip weight file", path);
     else if (version != kCkptVersion && version != 2u && version != kCkptVersionEps && version != kCkptVersionSparse && version != kCkptVersionSparse5 &&
-             version != kCkptVersionAc && version != kCkptVersionTdac)
-        rc = fail(RSRL_HIP_EINVAL, "%s has checkpoint version %u, this library reads versions 2, %u, %u, %u, %u, %u and %u", path, version, kCkptVersion, kCkptVersionEps,
-                  kCkptVersionSparse5, kCkptVersionSparse, kCkptVersionAc, kCkptVersionTdac);
+             version != kCkptVersionAc && version != kCkptVersionTdac && version != kCkptVersionReinforce)
+        rc = fail(RSRL_HIP_EINVAL, "%s has checkpoint version %u, this library reads versions 2, %u, %u, %u, %u, %u, %u and %u", path, version, kCkptVersion, kCkptVersionEps,
+                  kCkptVersionSparse5, kCkptVersionSparse, kCkptVersionAc, kCkptVersionTdac, kCkptVersionReinforce);
     // an ActorCritic file is version 7 with aux_kind 5, a TD ActorCritic file version 8 with aux_kind 6, and nothing else is either: any other pairing
     // is not a file this library wrote
-    else if ((version == kCkptVersionAc) != (h.aux_kind == 5) || (version == kCkptVersionTdac) != (h.aux_kind == 6))
+    else if ((version == kCkptVersionAc) != (h.aux_kind == 5) || (version == kCkptVersionTdac) != (h.aux_kind == 6) ||
+             (version == kCkptVersionReinforce) != (h.aux_kind == 7))
         rc = fail(RSRL_HIP_EINVAL, "%s: checkpoint version %u with aux_kind %d is not a valid pairing", path, version, h.aux_kind);
     // a QSigma file written before the backups travelled (version 2, aux_kind 0) is still read: the weights are loaded and the run
     // resumes from EMPTY n-step backups, as after a terminal transition (q_sigma.rs:154)
@@ -289,7 +354,8 @@ int rsrl_hip_load_weights(rsrl_hip_ctx* c, const char* path) {
     std::vector<uint32_t> sp_len_in, sp_len_t;      // sparse traces: a learner's entries in the file; its sub-lists' lengths on the device
     long sp_prefix = 0;
     if (rc == RSRL_HIP_OK) {                                             // a truncated file is refused before anything is touched
-        long long expect = (long long)kCkptHeaderBytes + h.n_learners * (long long)(per + (aux_is_matrix(h.aux_kind) ? per_aux : 0)) * 4 +
+        long long expect = (long long)kCkptHeaderBytes + h.n_learners * (long long)((has_weights_section(c) ? per : 0) + (aux_is_matrix(h.aux_kind) ? per_aux : 0)) * 4 +
+                           (h.aux_kind == 7 ? h.n_learners * (long long)per_aux * 4 + (long long)c->cfg.n_envs * 4 : 0) +
                            (h.aux_kind == 3 ? (long long)c->cfg.n_envs * 8 + (long long)qs_floats(c) * 4 : 0) +
                            (h.has_eps ? (long long)c->cfg.n_envs * 4 : 0);
         if (h.aux_kind == 4) {                                           // the lists are compact: their lengths say how long the file is
@@ -331,7 +397,7 @@ int rsrl_hip_load_weights(rsrl_hip_ctx* c, const char* path) {
     }
     c->W = W_new; c->Z = Z_new;
     std::vector<float> w;
-    for (int pass = 0; pass < (aux_is_matrix(h.aux_kind) ? 2 : 1); ++pass) {
+    for (int pass = has_weights_section(c) ? 0 : 1; pass < (aux_is_matrix(h.aux_kind) ? 2 : 1); ++pass) {
         w.resize(pass == 0 ? per : per_aux);
         for (int64_t i = 0; rc == RSRL_HIP_OK && i < h.n_learners; ++i) {
             if (fread(w.data(), sizeof(float), w.size(), f) != w.size()) { rc = fail(RSRL_HIP_EINVAL, "%s: read error", path); break; }
@@ -382,6 +448,11 @@ int rsrl_hip_load_weights(rsrl_hip_ctx* c, const char* path) {
         for (size_t i = 0; rc == RSRL_HIP_OK && i < N; ++i)
             if (hl[i] >= (uint32_t)c->cfg.n_steps || hl[N + i] > (uint32_t)c->cfg.n_steps) rc = fail(RSRL_HIP_EINVAL, "%s: corrupt QSigma backup of learner %zu", path, i);
     }
+    std::vector<float> rf_b, rf_g;                                      // REINFORCE: every learner's theta_b, g[N] -- installed at the end
+    if (rc == RSRL_HIP_OK && h.aux_kind == 7) {
+        rf_b.resize((size_t)h.n_learners * per_aux); rf_g.resize((size_t)c->cfg.n_envs);
+        if (fread(rf_b.data(), 4, rf_b.size(), f) != rf_b.size() || fread(rf_g.data(), 4, rf_g.size(), f) != rf_g.size()) rc = fail(RSRL_HIP_EINVAL, "%s: read error", path);
+    }
     std::vector<float> eps_in;
     if (rc == RSRL_HIP_OK && h.has_eps) {
         eps_in.resize((size_t)c->cfg.n_envs);
@@ -412,6 +483,8 @@ int rsrl_hip_load_weights(rsrl_hip_ctx* c, const char* path) {
         if (e2 == hipSuccess) e2 = hipStreamSynchronize(c->stream);
         if (e2 != hipSuccess) rc = fail(RSRL_HIP_EHIP, "installing the QSigma backups: %s", hipGetErrorString(e2));
     }
+    for (int64_t i = 0; rc == RSRL_HIP_OK && h.aux_kind == 7 && i < h.n_learners; ++i) rc = behaviour_rw(c, i, nullptr, rf_b.data() + (size_t)i * per_aux);
+    if (rc == RSRL_HIP_OK && h.aux_kind == 7) rc = rsrl_hip_set_return_carry(c, rf_g.data());
     if (rc == RSRL_HIP_OK && h.aux_kind == 4) {                        // the last step that can fail: the lengths
         hipError_t e2 = hipMemcpyAsync(c->sp_len, sp_len_t.data(), 4 * sp_len_t.size(), hipMemcpyHostToDevice, c->stream);
         if (e2 == hipSuccess) e2 = hipStreamSynchronize(c->stream);
@@ -435,6 +508,7 @@ int rsrl_hip_load_weights(rsrl_hip_ctx* c, const char* path) {
 int rsrl_hip_set_weights_all(rsrl_hip_ctx* c, const float* w) {
     CHECK_CTX(c); FLUSH(c);
     c->q_valid = false; c->tq_valid = false; if (!w) return fail(RSRL_HIP_EINVAL, "null argument");
+    if (c->cfg.algo == RSRL_REINFORCE) return no_value_function(c);
     if (c->cfg.weight_mode == RSRL_W_SHARED) return rsrl_hip_set_weights(c, 0, w);
     HIP_TRY(hipSetDevice(c->cfg.device));
     const int n = c->F * c->Aw; const float* d_w;

@@ -53,6 +53,8 @@ static inline bool is_ac(int algo) { return algo == RSRL_ACTOR_CRITIC || algo ==
 static inline bool has_aux(int algo) { return is_lambda(algo) || algo == RSRL_GREEDY_GQ || algo == RSRL_TD_LAMBDA || is_ac(algo); }   // second matrix of W's shape
 // ActorCritic with the TD(0) V critic: W is V's single column, the second matrix (theta) has A columns
 static inline bool is_tdac(int algo) { return algo == RSRL_TD_ACTOR_CRITIC; }
+// REINFORCE / BaselineREINFORCE: theta is the second matrix, theta_b (the behaviour snapshot) a third; W is the baseline B (unused by REINFORCE)
+static inline bool is_reinforce(int algo) { return algo == RSRL_REINFORCE || algo == RSRL_BASELINE_REINFORCE; }
 
 // ---- the small kernels more than one unit launches, and the launches of kernel templates two units would otherwise both instantiate: defined ONCE, in
 // kernels_util.hip / launch_shared.hip (a kernel's host stub is an ordinary function: another unit launches it through this declaration)
@@ -125,6 +127,7 @@ enum class AgentFamily : uint8_t {
     Hiv,                  // HIVTreatment (f64 hidden state): one-step agents, per-learner weights, Fourier orders 1-3: k_hiv_train (train_hiv.hip)
     AcReg,                // ActorCritic (both critics), register-family Fourier, per-learner f32 weights: k_train_ac (train_ac.hip); theta in Z
     TdAcReg,              // ActorCritic with the TD(0) V critic, same configurations: k_train_tdac (train_tdac.hip); w in W (one column), theta in Z (A columns)
+    ReinforceReg,         // REINFORCE / BaselineREINFORCE, same configurations: k_train_reinforce (train_reinforce.hip); B in W, theta in Z, theta_b in Zb, g in ret_g
 };
 static inline bool is_wave_family(AgentFamily f) {
     return f == AgentFamily::WaveAux || f == AgentFamily::WaveQSigma || f == AgentFamily::WaveLambda || f == AgentFamily::WaveControl;
@@ -171,6 +174,8 @@ struct rsrl_hip_ctx {
     bool sp_lds = false;             //   one tiling's slice of the delta table fits LDS (k_sparse_trace_scatter)
     float* Z = nullptr;              // auxiliary matrix f32[A][F][N]: eligibility traces (lambda agents) / fa_td weights (GreedyGQ) / the actor's theta (ActorCritic)
                                      // -- of W's shape, except TdAcReg's theta: A columns against W's one (aux_cols)
+    float* Zb = nullptr;             // REINFORCE only: the behaviour snapshot theta_b f32[A][F][N] (theta when the open episode began)
+    float* ret_g = nullptr;          //   and the open episode's running return g f32[N]
     double* hiv_y = nullptr;         // HIVTreatment only: every learner's hidden state f64[6][N] (`state` holds its observation)
     bool q_valid = false;            // false whenever weights / states were changed from outside the driver loop
     // ---- the trait-granular fast path (kernels_trait.hpp): register-family Fourier basis, per-learner f32 weights, learner-major layout
@@ -267,11 +272,20 @@ static Common make_common(const rsrl_hip_ctx* c) {
 // Policy::sample / mode / probabilities, reset's initial sample and the rollouts run the model kernels on it; the value side keeps make_common
 static Common make_policy_common(const rsrl_hip_ctx* c) {
     Common k = make_common(c);
-    if (c->family == AgentFamily::AcReg || c->family == AgentFamily::TdAcReg) k.W = c->Z;      // (the model kernels take the column count from the model: A)
+    if (c->family == AgentFamily::AcReg || c->family == AgentFamily::TdAcReg || c->family == AgentFamily::ReinforceReg) k.W = c->Z;      // (the model kernels take the column count from the model: A)
     return k;
 }
 // columns of the auxiliary matrix Z: W's (Aw), except the TD ActorCritic's theta (A)
 static inline int aux_cols(const rsrl_hip_ctx* c) { return c->family == AgentFamily::TdAcReg ? c->A : c->Aw; }
+// the agents with a Gibbs policy over weights of their own (theta in Z): ActorCritic (both critics, and TDCritic), REINFORCE (both)
+static inline bool has_policy_weights(const rsrl_hip_ctx* c) {
+    return c->family == AgentFamily::AcReg || c->family == AgentFamily::TdAcReg || c->family == AgentFamily::ReinforceReg;
+}
+static inline ReinforceState make_reinforce(const rsrl_hip_ctx* c) {
+    ReinforceState rs;
+    rs.theta = c->Z; rs.theta_b = c->Zb; rs.g = c->ret_g;
+    return rs;
+}
 
 static LambdaParams make_lambda(const rsrl_hip_ctx* c) {
     LambdaParams lp{};

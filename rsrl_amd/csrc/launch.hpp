@@ -52,6 +52,22 @@ bool launch_ac(int domain, int order, int critic, dim3 grid, dim3 block, hipStre
 // batch-steps of the driver loop from t
 bool launch_tdac(int domain, int order, dim3 grid, dim3 block, hipStream_t st, const Common& k, float* theta, uint64_t t, int chunk, DevStats* stats,
                  const Transitions* io);
+// REINFORCE / BaselineREINFORCE (train_reinforce.hip, kernels_reinforce.hpp): what the kernels carry besides Common (k.W = the baseline B f32[A][F][N])
+struct ReinforceState {
+    float* theta = nullptr;      // f32[A][F][N]: the agent's weights (the ctx's auxiliary matrix)
+    float* theta_b = nullptr;    // f32[A][F][N]: the behaviour snapshot, theta when the open episode began
+    float* g = nullptr;          // f32[N]: the open episode's running return
+};
+// Handler<&Batch>::handle's batches (device arrays): states [T][D][N], actions / rewards [T][N], lengths [N], ret_out [T][N] (may be null)
+struct ReinforceBatch {
+    const float* states = nullptr; const int32_t* act = nullptr; const float* rew = nullptr; const uint32_t* len = nullptr; int64_t T = 0;
+    float* ret_out = nullptr;
+};
+// io: handle_batch on io's batches, else chunk batch-steps of the driver loop from t
+bool launch_reinforce(int domain, int order, bool baseline, dim3 grid, dim3 block, hipStream_t st, const Common& k, const ReinforceState& rs, uint64_t t,
+                      int chunk, DevStats* stats, const ReinforceBatch* io);
+// new episodes for the learners in mask (every learner when mask is null): theta_b <- theta, g <- 0.  FA = F * A
+void launch_reinforce_restart(hipStream_t st, const ReinforceState& rs, int64_t N, int64_t FA, const uint8_t* mask);
 
 bool launch_td(int domain, int order, bool lambda, dim3 grid, dim3 block, hipStream_t st, const Common& k, const TdParams& tp, uint64_t t, int chunk,
                DevStats* stats, const Transitions* io);

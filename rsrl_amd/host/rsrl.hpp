@@ -45,6 +45,13 @@ struct Transition {                       // lib.rs:130-142, batched SoA
     std::vector<float> reward;            // [N]
     std::vector<uint8_t> terminal;        // [N]  (Observation::Terminal flag of `to`, lib.rs:170)
 };
+struct Batch {                            // Batch = Vec<Transition> (lib.rs:210), one per learner, batched SoA: learner i's is rows 0 .. lengths[i]-1
+    int64_t T = 0;                        // rows
+    std::vector<float> states;            // [T][D][N]  each transition's `from` state
+    std::vector<int32_t> actions;         // [T][N]
+    std::vector<float> rewards;           // [T][N]
+    std::vector<uint32_t> lengths;        // [N]  0 = no batch
+};
 struct Trajectory {                       // lib.rs:334-409, batched: `start` = states row 0, steps[k] = (states row k+1, actions[k], rewards[k])
     std::vector<uint32_t> n_states;       // [N]  Trajectory::n_states()  (:340); n_transitions = n_states - 1
     std::vector<float> total_reward;      // [N]  Trajectory::total_reward()  (:391)
@@ -205,6 +212,19 @@ struct ActorCritic : td::Agent {
 };
 }}  // namespace control::ac
 
+// ---- rsrl::control::mc: REINFORCE { policy, alpha, gamma } / BaselineREINFORCE { baseline, policy, alpha, gamma }
+// (control/mc/reinforce.rs, control/mc/baseline_reinforce.rs).  Handler<&Batch> only: Session::handle(const Batch&).  The policy is a Gibbs over its
+// own LFA (Session::policy_weights); the baseline is a read-only VectorLFA (Session::weights).  The Session's policy must be the same Gibbs object
+namespace control { namespace mc {
+struct REINFORCE : td::Agent {
+    REINFORCE(const policies::Gibbs& policy, double alpha_, double gamma_) : td::Agent{RSRL_REINFORCE, policy.q, gamma_, alpha_} {}
+};
+struct BaselineREINFORCE : td::Agent {
+    BaselineREINFORCE(Shared<fa::linear::LFA> baseline, const policies::Gibbs& /*policy*/, double alpha_, double gamma_)
+        : td::Agent{RSRL_BASELINE_REINFORCE, std::move(baseline), gamma_, alpha_} {}
+};
+}}  // namespace control::mc
+
 // ---- rsrl::prediction::td: TD { v_func, gamma } / TDLambda { fa_theta, trace, gamma }   (td.rs:25-30, td_lambda.rs:25-32)
 // The value function is a ScalarLFA (one weight column); drive these with policies::Random.
 namespace prediction { namespace td {
@@ -268,6 +288,12 @@ public:
         std::vector<float> td(N_);
         check(rsrl_hip_handle(ctx_, t.from.data(), t.action.data(), t.reward.data(), t.to.data(), t.terminal.data(), N_, td.data()));
         return td;
+    }
+    // Handler<&Batch>::handle of REINFORCE / BaselineREINFORCE -> the running return at each handled transition, [T][N] (reinforce.rs)
+    std::vector<float> handle(const domains::Batch& b) {
+        std::vector<float> g((size_t)b.T * N_);
+        check(rsrl_hip_handle_batch(ctx_, b.T, b.states.data(), b.actions.data(), b.rewards.data(), b.lengths.data(), g.data()));
+        return g;
     }
     // Policy::sample / Policy::mode                                               (policies/mod.rs:65-78)
     std::vector<int32_t> sample(const std::vector<float>& states) {
