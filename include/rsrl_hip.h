@@ -138,7 +138,30 @@ typedef enum { RSRL_QLEARNING = 0, RSRL_SARSA = 1, RSRL_EXPECTED_SARSA = 2, RSRL
                 * weights: get / set_weights and the Q operations read it.  REINFORCE has no value function: those are ESTATE.  rsrl_hip_handle is ESTATE
                 * (there is no Handler<&Transition>): rsrl_hip_handle_batch.  The statistics' sum |delta| is sum |g|.  Supported: as RSRL_ACTOR_CRITIC;
                 * everything else is EINVAL at create (kernels_reinforce.hpp) */
-               RSRL_REINFORCE = 15, RSRL_BASELINE_REINFORCE = 16 } rsrl_algo;
+               RSRL_REINFORCE = 15, RSRL_BASELINE_REINFORCE = 16,
+               /* (17 is no algo.)  Least-squares prediction, Handler<&Transition> (prediction/lstd/recursive_lstd.rs, prediction/lstd/ilstd.rs): a
+                * state-value function V(s) = phi(s) . theta with f64 theta and a f64 F x F matrix per learner; the Fourier features are evaluated in
+                * f64 on the device.  pd = phi(s) - gamma * phi(s'); every product is rounded, dot products are summed in index order.
+                *   RecursiveLSTD::new(basis, gamma): theta = 0, C = 1e-5 I.
+                *     non-terminal  g = C pd; a = 1 + g . phi(s); v = C phi(s); C += (-1/a) (v g^T), each v_r * g_j rounded before it is scaled;
+                *                   theta += (residual / a) v, residual = r + gamma theta.phi(s') - theta.phi(s)
+                *     terminal      v = C phi(s); a = 1 + v . phi(s); C.fill(0); theta += ((r - theta.phi(s)) / a) v.  As in the reference: after a
+                *                   learner's first terminal transition C is zero and theta never moves again.
+                *   iLSTD::new(basis, alpha, gamma, n_updates = config.n_steps): theta = 0, A = I, mu = 0.
+                *     mu += r phi(s); A += phi(s) pd^T (terminal: pd = phi(s)); mu -= (phi(s) pd^T) theta, computed as phi(s)_i * (pd . theta) (a
+                *     rounding difference); then n_updates rounds of solve(): idx = argmaxima(|mu|) (utils.rs: tolerance 1e-7 first, from f64::MIN;
+                *     a later larger value within 1e-7 is appended without raising the max), and for each j in idx IN ORDER u = alpha mu_j,
+                *     theta_j += u, mu -= u A[:,j] (a later j reads the mu an earlier one changed).
+                * config: gamma (both), alpha and n_steps 1..32 (iLSTD); lr is unused.  Supported: per-learner f32 weights (the f32 view of theta),
+                * policy RSRL_RANDOM, agent_policy -1, no epsilon schedule, the register-family Fourier orders (MountainCar 1-5, CartPole 1, Acrobot 1);
+                * everything else is EINVAL at create (kernels_lstd.hpp).  The driver loop is TD's: transition, handle, Random sample, auto-reset;
+                * truncation at max_episode_steps is not terminal.  rsrl_hip_reset does not touch the agents' state.  The value side is V
+                * (n_outputs 1): q_evaluate writes f32(phi(s) . theta) evaluated in f64; get/set_weights carry theta as f32[F][1] (rounded out,
+                * widened exactly in; C / A / mu untouched); rsrl_hip_get/set_lstd_state read and write the exact f64 state.  q_find_max / _min,
+                * q_expected_value, traces, td / policy weights and handle_batch are ESTATE.  rsrl_hip_handle's td_error_out and the statistics'
+                * sum |delta| are RecursiveLSTD's residual; iLSTD computes no TD error and reports, as a diagnostic, r + gamma V(s') - V(s) (terminal:
+                * r - V(s)) with theta from before the update */
+               RSRL_RECURSIVE_LSTD = 18, RSRL_ILSTD = 19 } rsrl_algo;
 /* rsrl::traces::{Accumulate, Saturate (Trace::replacing), Dutch}      traces.rs:188-240 */
 typedef enum { RSRL_TRACE_ACCUMULATE = 0, RSRL_TRACE_SATURATE = 1, RSRL_TRACE_DUTCH = 2 } rsrl_trace;
 /* rsrl::policies::{Greedy, EpsilonGreedy, Softmax, Random}
@@ -209,7 +232,8 @@ typedef struct {
     double   agent_epsilon;      /* EpsilonGreedy.epsilon of the agent's policy                                          */
     double   agent_tau;          /* Softmax.tau of the agent's policy                                                    */
     double   sigma;              /* QSigma.sigma in [0, 1]: 1 = SARSA-like sampling, 0 = tree backup (q_sigma.rs:66-72)          */
-    int32_t  n_steps;            /* QSigma: Backup::new(n_steps), 1..32 (q_sigma.rs:94-104)                                      */
+    int32_t  n_steps;            /* QSigma: Backup::new(n_steps), 1..32 (q_sigma.rs:94-104).  RSRL_ILSTD: iLSTD's n_updates, the
+                                    rounds of solve() per transition, 1..32                                                      */
     int32_t  peer_timeout_ms;    /* ABI 5 (was reserved0): bound of every in-kernel wait for a peer / block of the shared-W exchange, in
                                     milliseconds; 0 = RSRL_PEER_TIMEOUT_MS from the environment, else 4000.  Make it longer than the
                                     longest time one rank may spend away from the others (a rollout, a checkpoint) */
@@ -408,17 +432,24 @@ int rsrl_hip_get_behaviour_weights(rsrl_hip_ctx* ctx, int64_t env_index, float* 
 int rsrl_hip_set_behaviour_weights(rsrl_hip_ctx* ctx, int64_t env_index, const float* theta_b /*[F][A]*/);
 int rsrl_hip_get_return_carry(rsrl_hip_ctx* ctx, float* g /*[N]*/);
 int rsrl_hip_set_return_carry(rsrl_hip_ctx* ctx, const float* g /*[N]*/);
+/* RecursiveLSTD / iLSTD: the exact f64 state of one learner -- theta, the matrix (row-major: C for RecursiveLSTD, A for iLSTD) and iLSTD's mu
+ * (may be NULL: not read or written; ignored by RecursiveLSTD).  Host or device arrays.  ESTATE on every other agent */
+int rsrl_hip_get_lstd_state(rsrl_hip_ctx* ctx, int64_t env_index, double* theta /*[F]*/, double* mat /*[F][F]*/, double* mu /*[F], iLSTD only, may be NULL*/);
+int rsrl_hip_set_lstd_state(rsrl_hip_ctx* ctx, int64_t env_index, const double* theta /*[F]*/, const double* mat /*[F][F]*/,
+                            const double* mu /*[F], iLSTD only, may be NULL*/);
 /* Checkpoint of the approximator(s) (the reference's only persistence story is the optional serde
  * derive on the agents, rsrl/Cargo.toml:26).  File format version 2 (3 for files that carry QSigma's backups, 5 for sparse traces, 7 for ActorCritic, 8 for the TD ActorCritic,
- * 9 for REINFORCE),
+ * 9 for REINFORCE, 10 for RecursiveLSTD / iLSTD),
  * little-endian,
  * serialised field by field (no padding):
  *   offset  0  char magic[8] = "RSRLHIPW"
- *           8  u32  version = 2 (3 iff aux_kind = 3, 5 iff aux_kind = 4, 7 iff aux_kind = 5, 8 iff aux_kind = 6, 9 iff aux_kind = 7, 4 with the epsilon schedule)
+ *           8  u32  version = 2 (3 iff aux_kind = 3, 5 iff aux_kind = 4, 7 iff aux_kind = 5, 8 iff aux_kind = 6, 9 iff aux_kind = 7, 10 iff aux_kind = 8,
+ *                   4 with the epsilon schedule)
  *          12  i32  domain, basis, order, n_tilings, tiles_per_dim, weight_mode, F, A (weight columns),
  *                   algo, weight_dtype, aux_kind (0 none, 1 eligibility traces, 2 GreedyGQ's fa_td weights,
  *                   3 QSigma's n-step backups, 4 sparse traces over a shared table, 5 ActorCritic's theta,
- *                   6 the TD ActorCritic's theta, 7 REINFORCE's theta and open episode)                          [11 x i32]
+ *                   6 the TD ActorCritic's theta, 7 REINFORCE's theta and open episode, 8 the LSTD agents' f64 state)
+ *                                                                                                                 [11 x i32]
  *          56  i64  n_learners (1 in shared mode)
  *          64  u64  step_count
  *          72  n_learners x f32[F][A] weights in the reference's row-major (F, A) order (Parameterised::weights,
@@ -430,6 +461,9 @@ int rsrl_hip_set_return_carry(rsrl_hip_ctx* ctx, const float* g /*[N]*/);
  *              if aux_kind is 7 (file version 9, which no other configuration reads; RSRL_REINFORCE / RSRL_BASELINE_REINFORCE): the weights section
  *              is BaselineREINFORCE's baseline B, and is ABSENT for REINFORCE (no value function); then n_learners x f32[F][A] of theta,
  *              n_learners x f32[F][A] of theta_b, f32 g[N];
+ *              if aux_kind is 8 (file version 10, which no other configuration reads; RSRL_RECURSIVE_LSTD / RSRL_ILSTD): the weights section is
+ *              ABSENT (theta is f64); then n_learners x f64[F] of theta, n_learners x f64[F][F] of the matrix (C / A, row-major) and, for
+ *              iLSTD, n_learners x f64[F] of mu;
  *              if aux_kind is 3 (file version 3): u32 head[N], u32 len[N], f32 entries[D + 5][n_steps][N] -- every learner's
  *              Backup ring {s, a, q, residual, pi, mu} (q_sigma.rs:30-63), so that a QSigma run with n_steps > 1 resumes
  *              bit-identically too.  Files of version 2 (no aux_kind 3) are still read.

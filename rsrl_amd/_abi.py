@@ -88,6 +88,8 @@ SYMBOLS = {
     "rsrl_hip_set_behaviour_weights": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
     "rsrl_hip_get_return_carry": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rsrl_hip_set_return_carry": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rsrl_hip_get_lstd_state": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rsrl_hip_set_lstd_state": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rsrl_hip_handle_batch": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rsrl_hip_train": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Stats)]),
     "rsrl_hip_step_count": (C.c_uint64, [C.c_void_p]),

@@ -12,6 +12,7 @@ QLEARNING, SARSA, EXPECTED_SARSA, SARSA_LAMBDA, Q_LAMBDA, PAL, GREEDY_GQ, TD, TD
 ACTOR_CRITIC, Q_ACTOR_CRITIC = 10, 11          # ActorCritic (control/ac.rs) with a Gibbs actor and a SARSA critic: a2c.rs's closure / QCritic
 TD_ACTOR_CRITIC = 13                           # ActorCritic::tdac: the Gibbs actor with TDCritic over a TD(0) V (12 is no algo)
 REINFORCE, BASELINE_REINFORCE = 15, 16         # (14 is no algo) control/mc: REINFORCE<Gibbs>, BaselineREINFORCE<B, Gibbs> (Handler<&Batch>: handle_batch)
+RECURSIVE_LSTD, ILSTD = 18, 19                  # (17 is no algo) prediction/lstd: RecursiveLSTD, iLSTD (f64 theta and F x F matrix: get/set_lstd_state)
 TRACE_ACCUMULATE, TRACE_SATURATE, TRACE_DUTCH = 0, 1, 2
 GREEDY, EPSILON_GREEDY, SOFTMAX, RANDOM = 0, 1, 2, 3
 W_PER_ENV, W_SHARED = 0, 1
@@ -374,6 +375,18 @@ class Context:
     @return_carry.setter
     def return_carry(self, g):
         _abi.check(self._L.rsrl_hip_set_return_carry(self._h, _p(_in(g, np.float32, (self.N,)))))
+
+    def get_lstd_state(self, env_index=0):
+        """RecursiveLSTD / iLSTD: one learner's exact f64 state -> (theta (F,), the matrix (F, F): C / A, mu (F,) for iLSTD else None)"""
+        theta, mat = np.empty(self.F, dtype=np.float64), np.empty((self.F, self.F), dtype=np.float64)
+        mu = np.empty(self.F, dtype=np.float64) if self.cfg.algo == ILSTD else None
+        _abi.check(self._L.rsrl_hip_get_lstd_state(self._h, int(env_index), _p(theta), _p(mat), _p(mu)))
+        return theta, mat, mu
+
+    def set_lstd_state(self, theta, mat, mu=None, env_index=0):
+        """RecursiveLSTD / iLSTD: install one learner's f64 state exactly (mu: iLSTD only; None leaves it as it is)"""
+        _abi.check(self._L.rsrl_hip_set_lstd_state(self._h, int(env_index), _p(_in(theta, np.float64, (self.F,))), _p(_in(mat, np.float64, (self.F, self.F))),
+                                                   _p(None if mu is None else _in(mu, np.float64, (self.F,)))))
 
     def save_weights(self, path):
         _abi.check(self._L.rsrl_hip_save_weights(self._h, str(path).encode()))

@@ -216,6 +216,9 @@ static inline int64_t fuse_depth(const rsrl_hip_ctx* c) {
     case AgentFamily::TdReg: case AgentFamily::GqReg: case AgentFamily::LambdaReg: case AgentFamily::RegStep: case AgentFamily::RegFused: case AgentFamily::AcReg:
     case AgentFamily::TdAcReg: case AgentFamily::ReinforceReg:
         return 4096;
+    // RecursiveLSTD / iLSTD: O(F^2) f64 per learner-step, 0.76 / 1.03 ms per batch-step at 262 144 MountainCar order-5 learners:
+    // 32 keep a launch in the tens of milliseconds there; at 65 536 order-3 learners a 32-step launch lasts 0.6 ms
+    case AgentFamily::LstdReg: return 32;
     // HIVTreatment: one batch-step is 1 000 f64 RK4 sub-steps per learner, ~1 ms at 65 536 learners -- 16 keep a launch in the tens of milliseconds
     case AgentFamily::Hiv: return 16;
     default: return 256;
@@ -440,6 +443,7 @@ int launch_agent(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, uint64_t 
         ok = launch_ac(cf.domain, cf.order, cf.algo == RSRL_Q_ACTOR_CRITIC ? AC_CRITIC_Q : AC_CRITIC_ADVANTAGE, grid, block, c->stream, k, c->Z, t, chunk, d_stats, io);
         break;
     case AgentFamily::TdAcReg: ok = launch_tdac(cf.domain, cf.order, grid, block, c->stream, k, c->Z, t, chunk, d_stats, io); break;
+    case AgentFamily::LstdReg: ok = launch_lstd(cf.domain, cf.order, cf.algo == RSRL_ILSTD, c->stream, k, make_lstd(c), t, chunk, d_stats, io); break;
     case AgentFamily::ReinforceReg:      // (io: rsrl_hip_handle refuses these agents before it gets here; rsrl_hip_handle_batch launches its own)
         ok = !io && launch_reinforce(cf.domain, cf.order, cf.algo == RSRL_BASELINE_REINFORCE, grid, block, c->stream, k, make_reinforce(c), t, chunk, d_stats, nullptr);
         break;
@@ -601,7 +605,8 @@ static int rollout_impl(rsrl_hip_ctx* c, int64_t step_limit, int64_t M, uint32_t
     }
     if (step_limit < 1) return fail(RSRL_HIP_EINVAL, "step_limit must be >= 1, or 0 for no limit (bounded by config.max_episode_steps)");
     if (M < 1 || M > c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "bad batch (M=%lld, n_envs=%lld)", (long long)M, (long long)c->cfg.n_envs);
-    if (is_pred(c->cfg.algo)) return fail(RSRL_HIP_ESTATE, "a prediction agent has a state-value function only: no action values to roll out with");
+    if (is_pred(c->cfg.algo) || is_lstd(c->cfg.algo))          // (W is one column: the model kernels below would read A of them)
+        return fail(RSRL_HIP_ESTATE, "a prediction agent has a state-value function only: no action values to roll out with");
     if (!rp.sample && c->cfg.policy == RSRL_RANDOM) return fail(RSRL_HIP_EINVAL, "Random policy has no mode.");
     HIP_TRY(hipSetDevice(c->cfg.device));
     if (step_limit == 1) { actions_out = nullptr; rewards_out = nullptr; }      // Trajectory.steps is empty

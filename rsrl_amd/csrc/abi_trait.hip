@@ -124,7 +124,7 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
                size_t icount = 0, const float* fin = nullptr, size_t fin_count = 0, const int32_t* iin = nullptr, uint64_t step_t = 0) {
     CHECK_CTX(c); FLUSH(c);
     if (!states || M_ < 1 || M_ > c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "bad batch (M=%lld, n_envs=%lld)", (long long)M_, (long long)c->cfg.n_envs);
-    if (is_pred(c->cfg.algo) && op != QOP_EVALUATE && op != QOP_FEATURES)
+    if ((is_pred(c->cfg.algo) || is_lstd(c->cfg.algo)) && op != QOP_EVALUATE && op != QOP_FEATURES)
         return fail(RSRL_HIP_ESTATE, "a prediction agent has a state-value function only (use rsrl_hip_q_evaluate for V(s))");
     // the TD ActorCritic: its value side is V(s) (no action values to search or weigh), its policy side the actor's theta
     if (is_tdac(c->cfg.algo) && (op == QOP_FIND_MAX || op == QOP_FIND_MIN || op == QOP_EXPECTED))
@@ -147,7 +147,9 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
     const uint64_t call = (op == QOP_SAMPLE_STEP || op == QOP_SAMPLE_INIT) ? step_t : c->api_calls;      // (the driver loop's sample: addressed by the batch-step)
     if (op == QOP_SAMPLE) c->api_calls++;
     const BasisGeom g = make_geom(c);
-    if ((is_pred(c->cfg.algo) || is_tdac(c->cfg.algo)) && op == QOP_EVALUATE) {          // V(s) (the TD ActorCritic: its w, k_v_evaluate)
+    if (c->family == AgentFamily::LstdReg && op == QOP_EVALUATE) {                        // V(s) = f32(phi(s) . theta), in f64 (k_lstd_v)
+        if (!launch_lstd_v(c->cfg.domain, c->cfg.order, c->stream, c->lstd_theta, d_states, M_, of.dev)) return NO_MODEL(c);
+    } else if ((is_pred(c->cfg.algo) || is_tdac(c->cfg.algo)) && op == QOP_EVALUATE) {          // V(s) (the TD ActorCritic: its w, k_v_evaluate)
         bool ok = true;
         switch (c->family) {
         case AgentFamily::WaveAux:
@@ -204,6 +206,21 @@ static int sample_emit(rsrl_hip_ctx* c, int64_t M, int32_t* actions_out) {
     if (M != c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "policy_sample(states = NULL) samples for the ctx's own envs: M must be n_envs (%lld), got %lld", (long long)c->cfg.n_envs, (long long)M);
     if (is_pred(c->cfg.algo)) return fail(RSRL_HIP_ESTATE, "a prediction agent has a state-value function only (use rsrl_hip_q_evaluate for V(s))");
     const bool dev_out = is_device_ptr(actions_out);
+    if (c->family == AgentFamily::LstdReg) {
+        // RecursiveLSTD / iLSTD: the driver loop's Random sample (what rsrl_hip_train draws at batch-step step_count - 1; the initial sample's stream
+        // before the first handle), so that the trait-granular loop runs on the driver loop's draws
+        FLUSH(c);
+        HIP_TRY(hipSetDevice(c->cfg.device));
+        OutBuf<int32_t> oa;
+        TRY(stage_out(c, 2, actions_out, (size_t)M, &oa));
+        const Common k = make_common(c);
+        launch_lstd_sample(c->cfg.domain, c->stream, k, c->t ? c->t - 1 : 0, c->t ? BLK_STEP : BLK_INIT, oa.dev);
+        KCHECK();
+        bool sync = false;
+        TRY(flush_out(c, &oa, &sync));
+        if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
+        return RSRL_HIP_OK;
+    }
     if (c->tp.stage == 3 && dev_out) {
         // the whole batch-step -- transition, handle, new episodes, sample -- as ONE kernel
         const rsrl_hip_ctx::TraitPend p = c->tp;

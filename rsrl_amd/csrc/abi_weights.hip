@@ -7,9 +7,31 @@ RSRL_API_BEGIN
 static int no_value_function(rsrl_hip_ctx* c) {
     return fail(RSRL_HIP_ESTATE, "REINFORCE has no value function (its policy's weights: rsrl_hip_get/set_policy_weights)");
 }
+// RecursiveLSTD / iLSTD: the weights are theta (the reference's #[weights]), f64 on the device -- rounded to f32 on the way out, widened exactly on the
+// way in; the matrix and mu are not touched
+static int lstd_weights_rw(rsrl_hip_ctx* c, int64_t first, int64_t count, float* out, const float* in) {
+    if (first < 0 || first + count > c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "env_index out of range");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (out) {
+        OutBuf<float> ow;
+        TRY(stage_out(c, 0, out, (size_t)c->F, &ow));
+        launch_lstd_theta_get(c->stream, c->lstd_theta, c->F, first, ow.dev);
+        KCHECK();
+        bool sync = false; TRY(flush_out(c, &ow, &sync));
+        if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
+    } else {
+        const float* d_w;
+        TRY(stage_in(c, 0, in, (size_t)c->F, &d_w));
+        launch_lstd_theta_set(c->stream, c->lstd_theta, c->F, first, count, d_w);
+        KCHECK();
+        if (!is_device_ptr(in)) HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return RSRL_HIP_OK;
+}
 int rsrl_hip_get_weights(rsrl_hip_ctx* c, int64_t env_index, float* w) {
     CHECK_CTX(c); FLUSH(c); if (!w) return fail(RSRL_HIP_EINVAL, "null argument");
     if (c->cfg.algo == RSRL_REINFORCE) return no_value_function(c);
+    if (c->family == AgentFamily::LstdReg) return lstd_weights_rw(c, env_index, 1, w, nullptr);
     const bool shared = c->cfg.weight_mode == RSRL_W_SHARED;
     if (!shared && (env_index < 0 || env_index >= c->cfg.n_envs)) return fail(RSRL_HIP_EINVAL, "env_index out of range");
     HIP_TRY(hipSetDevice(c->cfg.device));
@@ -31,6 +53,7 @@ int rsrl_hip_set_weights(rsrl_hip_ctx* c, int64_t env_index, const float* w) {
     CHECK_CTX(c); FLUSH(c);
     c->q_valid = false; c->tq_valid = false; if (!w) return fail(RSRL_HIP_EINVAL, "null argument");
     if (c->cfg.algo == RSRL_REINFORCE) return no_value_function(c);
+    if (c->family == AgentFamily::LstdReg) return lstd_weights_rw(c, env_index, 1, nullptr, w);
     const bool shared = c->cfg.weight_mode == RSRL_W_SHARED;
     if (!shared && (env_index < 0 || env_index >= c->cfg.n_envs)) return fail(RSRL_HIP_EINVAL, "env_index out of range");
     HIP_TRY(hipSetDevice(c->cfg.device));
@@ -154,6 +177,36 @@ int rsrl_hip_set_behaviour_weights(rsrl_hip_ctx* c, int64_t env_index, const flo
     if (!theta_b) return fail(RSRL_HIP_EINVAL, "null argument");
     return behaviour_rw(c, env_index, nullptr, theta_b);
 }
+// RecursiveLSTD / iLSTD: one learner's exact f64 state (theta [F], the matrix [F][F], iLSTD's mu [F]; mu may be null).  Host or device arrays
+static int lstd_state_rw(rsrl_hip_ctx* c, int64_t env_index, double* theta, double* mat, double* mu, const double* theta_in, const double* mat_in,
+                         const double* mu_in) {
+    CHECK_CTX(c); FLUSH(c);
+    if (c->family != AgentFamily::LstdReg) return fail(RSRL_HIP_ESTATE, "only RecursiveLSTD and iLSTD carry a least-squares state");
+    if (env_index < 0 || env_index >= c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "env_index out of range");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    c->q_valid = false;
+    const size_t F = (size_t)c->F, i = (size_t)env_index;
+    const bool ilstd = c->lstd_mu != nullptr;
+    if (theta) {
+        HIP_TRY(hipMemcpyAsync(theta, c->lstd_theta + i * F, 8 * F, hipMemcpyDefault, c->stream));
+        HIP_TRY(hipMemcpyAsync(mat, c->lstd_mat + i * F * F, 8 * F * F, hipMemcpyDefault, c->stream));
+        if (ilstd && mu) HIP_TRY(hipMemcpyAsync(mu, c->lstd_mu + i * F, 8 * F, hipMemcpyDefault, c->stream));
+    } else {
+        HIP_TRY(hipMemcpyAsync(c->lstd_theta + i * F, theta_in, 8 * F, hipMemcpyDefault, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->lstd_mat + i * F * F, mat_in, 8 * F * F, hipMemcpyDefault, c->stream));
+        if (ilstd && mu_in) HIP_TRY(hipMemcpyAsync(c->lstd_mu + i * F, mu_in, 8 * F, hipMemcpyDefault, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RSRL_HIP_OK;
+}
+int rsrl_hip_get_lstd_state(rsrl_hip_ctx* c, int64_t env_index, double* theta, double* mat, double* mu) {
+    if (!theta || !mat) return fail(RSRL_HIP_EINVAL, "null argument");
+    return lstd_state_rw(c, env_index, theta, mat, mu, nullptr, nullptr, nullptr);
+}
+int rsrl_hip_set_lstd_state(rsrl_hip_ctx* c, int64_t env_index, const double* theta, const double* mat, const double* mu) {
+    if (!theta || !mat) return fail(RSRL_HIP_EINVAL, "null argument");
+    return lstd_state_rw(c, env_index, nullptr, nullptr, nullptr, theta, mat, mu);
+}
 int rsrl_hip_get_return_carry(rsrl_hip_ctx* c, float* g) {
     CHECK_CTX(c); FLUSH(c); if (!g) return fail(RSRL_HIP_EINVAL, "null argument");
     if (c->family != AgentFamily::ReinforceReg) return fail(RSRL_HIP_ESTATE, "only REINFORCE and BaselineREINFORCE carry an episode's running return");
@@ -181,6 +234,7 @@ constexpr uint32_t kCkptVersionSparse5 = 5;   // ... as round 5 wrote them (no n
 constexpr uint32_t kCkptVersionAc = 7;        // files carrying aux_kind 5 (ActorCritic's theta): laid out as aux_kind 1 / 2, a version of their own
 constexpr uint32_t kCkptVersionTdac = 8;      // files carrying aux_kind 6 (the TD ActorCritic's theta, f32[F][n_actions] against V's f32[F][1]): ditto
 constexpr uint32_t kCkptVersionReinforce = 9; // files carrying aux_kind 7 (REINFORCE's theta, theta_b and g; no weights section for REINFORCE itself)
+constexpr uint32_t kCkptVersionLstd = 10;     // files carrying aux_kind 8 (the LSTD agents' f64 theta, matrix and mu; no f32 weights section)
 constexpr int64_t kSparseChunk = 4096;        // learners per staging chunk of the sparse lists
 constexpr size_t kCkptHeaderBytes = 72;
 struct Ckpt {
@@ -191,8 +245,9 @@ struct Ckpt {
 // 1 = eligibility traces, 2 = fa_td weights (both: a second matrix of W's shape), 3 = QSigma's per-learner n-step backups,
 // 4 = every learner's sparse trace over the shared table (the lists, compact), 5 = ActorCritic's theta (a second matrix of W's shape),
 // 6 = the TD ActorCritic's theta (a second matrix of A columns, W has one), 7 = REINFORCE's theta (a second matrix of W's shape), then its
-// open episode: theta_b (a third) and g[N]
+// open episode: theta_b (a third) and g[N], 8 = the LSTD agents' f64 state (theta, the matrix, iLSTD's mu)
 int aux_kind_of(const rsrl_hip_ctx* c) {
+    if (c->family == AgentFamily::LstdReg) return 8;
     if (c->family == AgentFamily::AcReg) return 5;
     if (c->family == AgentFamily::TdAcReg) return 6;
     if (c->family == AgentFamily::ReinforceReg) return 7;
@@ -201,7 +256,9 @@ int aux_kind_of(const rsrl_hip_ctx* c) {
 // aux_kinds whose payload is a second n_learners x f32[F][aux_cols] after the weights
 bool aux_is_matrix(int32_t kind) { return kind == 1 || kind == 2 || kind == 5 || kind == 6 || kind == 7; }
 // the weights section: every file has one except REINFORCE's (no value function; BaselineREINFORCE's is the baseline B)
-bool has_weights_section(const rsrl_hip_ctx* c) { return c->cfg.algo != RSRL_REINFORCE; }
+bool has_weights_section(const rsrl_hip_ctx* c) { return c->cfg.algo != RSRL_REINFORCE && !is_lstd(c->cfg.algo); }
+// the LSTD agents' payload in doubles: every learner's theta, then every learner's matrix, then (iLSTD) every learner's mu -- the device arrays as they are
+size_t lstd_doubles(const rsrl_hip_ctx* c) { const size_t nv = (size_t)c->F * (size_t)c->cfg.n_envs; return nv + nv * (size_t)c->F + (c->lstd_mu ? nv : 0); }
 size_t qs_floats(const rsrl_hip_ctx* c) { return (size_t)(c->D + 5) * (size_t)c->cfg.n_steps * (size_t)c->cfg.n_envs; }
 Ckpt ckpt_of(const rsrl_hip_ctx* c) {
     Ckpt h{};
@@ -219,7 +276,7 @@ uint64_t get64(const uint8_t*& p) { uint64_t v = 0; for (int i = 0; i < 8; ++i) 
 void ckpt_encode(const Ckpt& h, uint8_t (&buf)[kCkptHeaderBytes]) {
     uint8_t* p = buf;
     memcpy(p, "RSRLHIPW", 8); p += 8;
-    put32(p, h.has_eps ? kCkptVersionEps : h.aux_kind == 7 ? kCkptVersionReinforce : (h.aux_kind == 6 ? kCkptVersionTdac : (h.aux_kind == 5 ? kCkptVersionAc : (h.aux_kind == 4 ? kCkptVersionSparse :
+    put32(p, h.has_eps ? kCkptVersionEps : h.aux_kind == 8 ? kCkptVersionLstd : h.aux_kind == 7 ? kCkptVersionReinforce : (h.aux_kind == 6 ? kCkptVersionTdac : (h.aux_kind == 5 ? kCkptVersionAc : (h.aux_kind == 4 ? kCkptVersionSparse :
                                                                                                                           (h.aux_kind == 3 ? kCkptVersion : 2u)))));
     const int32_t f[11] = {h.domain, h.basis, h.order, h.n_tilings, h.tiles_per_dim, h.weight_mode, h.F, h.A, h.algo, h.weight_dtype, h.aux_kind};
     for (int32_t v : f) put32(p, (uint32_t)v);
@@ -262,6 +319,16 @@ int rsrl_hip_save_weights(rsrl_hip_ctx* c, const char* path) {
         std::vector<float> g((size_t)c->cfg.n_envs);
         if (rc == RSRL_HIP_OK) rc = rsrl_hip_get_return_carry(c, g.data());
         if (rc == RSRL_HIP_OK && fwrite(g.data(), sizeof(float), g.size(), f) != g.size()) rc = fail(RSRL_HIP_EINVAL, "short write to %s", path);
+    }
+    if (rc == RSRL_HIP_OK && h.aux_kind == 8) {                        // the LSTD agents: theta, the matrices, mu -- f64, learner-major
+        const size_t nv = (size_t)c->F * (size_t)c->cfg.n_envs;
+        std::vector<double> buf(lstd_doubles(c));
+        hipError_t e = hipMemcpyAsync(buf.data(), c->lstd_theta, 8 * nv, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(buf.data() + nv, c->lstd_mat, 8 * nv * c->F, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && c->lstd_mu) e = hipMemcpyAsync(buf.data() + nv + nv * c->F, c->lstd_mu, 8 * nv, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(RSRL_HIP_EHIP, "reading the LSTD state: %s", hipGetErrorString(e));
+        if (rc == RSRL_HIP_OK && fwrite(buf.data(), 8, buf.size(), f) != buf.size()) rc = fail(RSRL_HIP_EINVAL, "short write to %s", path);
     }
     if (rc == RSRL_HIP_OK && h.aux_kind == 3) {                        // QSigma: ring heads, lengths, entries (SoA [field][slot][learner])
         const size_t N = (size_t)c->cfg.n_envs, nf = qs_floats(c);
@@ -331,13 +398,13 @@ int rsrl_hip_load_weights(rsrl_hip_ctx* c, const char* path) {
     int rc = RSRL_HIP_OK;
     if (fread(hdr, 1, sizeof(hdr), f) != sizeof(hdr) || !ckpt_decode(hdr, &h, &version)) rc = fail(RSRL_HIP_EINVAL, "%s is not a rsrl_hip weight file", path);
     else if (version != kCkptVersion && version != 2u && version != kCkptVersionEps && version != kCkptVersionSparse && version != kCkptVersionSparse5 &&
-             version != kCkptVersionAc && version != kCkptVersionTdac && version != kCkptVersionReinforce)
-        rc = fail(RSRL_HIP_EINVAL, "%s has checkpoint version %u, this library reads versions 2, %u, %u, %u, %u, %u, %u and %u", path, version, kCkptVersion, kCkptVersionEps,
-                  kCkptVersionSparse5, kCkptVersionSparse, kCkptVersionAc, kCkptVersionTdac, kCkptVersionReinforce);
+             version != kCkptVersionAc && version != kCkptVersionTdac && version != kCkptVersionReinforce && version != kCkptVersionLstd)
+        rc = fail(RSRL_HIP_EINVAL, "%s has checkpoint version %u, this library reads versions 2, %u, %u, %u, %u, %u, %u, %u and %u", path, version, kCkptVersion,
+                  kCkptVersionEps, kCkptVersionSparse5, kCkptVersionSparse, kCkptVersionAc, kCkptVersionTdac, kCkptVersionReinforce, kCkptVersionLstd);
     // an ActorCritic file is version 7 with aux_kind 5, a TD ActorCritic file version 8 with aux_kind 6, and nothing else is either: any other pairing
     // is not a file this library wrote
     else if ((version == kCkptVersionAc) != (h.aux_kind == 5) || (version == kCkptVersionTdac) != (h.aux_kind == 6) ||
-             (version == kCkptVersionReinforce) != (h.aux_kind == 7))
+             (version == kCkptVersionReinforce) != (h.aux_kind == 7) || (version == kCkptVersionLstd) != (h.aux_kind == 8))
         rc = fail(RSRL_HIP_EINVAL, "%s: checkpoint version %u with aux_kind %d is not a valid pairing", path, version, h.aux_kind);
     // a QSigma file written before the backups travelled (version 2, aux_kind 0) is still read: the weights are loaded and the run
     // resumes from EMPTY n-step backups, as after a terminal transition (q_sigma.rs:154)
@@ -356,6 +423,7 @@ int rsrl_hip_load_weights(rsrl_hip_ctx* c, const char* path) {
     if (rc == RSRL_HIP_OK) {                                             // a truncated file is refused before anything is touched
         long long expect = (long long)kCkptHeaderBytes + h.n_learners * (long long)((has_weights_section(c) ? per : 0) + (aux_is_matrix(h.aux_kind) ? per_aux : 0)) * 4 +
                            (h.aux_kind == 7 ? h.n_learners * (long long)per_aux * 4 + (long long)c->cfg.n_envs * 4 : 0) +
+                           (h.aux_kind == 8 && want.aux_kind == 8 ? (long long)lstd_doubles(c) * 8 : 0) +
                            (h.aux_kind == 3 ? (long long)c->cfg.n_envs * 8 + (long long)qs_floats(c) * 4 : 0) +
                            (h.has_eps ? (long long)c->cfg.n_envs * 4 : 0);
         if (h.aux_kind == 4) {                                           // the lists are compact: their lengths say how long the file is
@@ -453,6 +521,11 @@ int rsrl_hip_load_weights(rsrl_hip_ctx* c, const char* path) {
         rf_b.resize((size_t)h.n_learners * per_aux); rf_g.resize((size_t)c->cfg.n_envs);
         if (fread(rf_b.data(), 4, rf_b.size(), f) != rf_b.size() || fread(rf_g.data(), 4, rf_g.size(), f) != rf_g.size()) rc = fail(RSRL_HIP_EINVAL, "%s: read error", path);
     }
+    std::vector<double> lstd_in;                                        // the LSTD agents: their whole f64 state -- installed at the end
+    if (rc == RSRL_HIP_OK && h.aux_kind == 8) {
+        lstd_in.resize(lstd_doubles(c));
+        if (fread(lstd_in.data(), 8, lstd_in.size(), f) != lstd_in.size()) rc = fail(RSRL_HIP_EINVAL, "%s: read error", path);
+    }
     std::vector<float> eps_in;
     if (rc == RSRL_HIP_OK && h.has_eps) {
         eps_in.resize((size_t)c->cfg.n_envs);
@@ -485,6 +558,14 @@ int rsrl_hip_load_weights(rsrl_hip_ctx* c, const char* path) {
     }
     for (int64_t i = 0; rc == RSRL_HIP_OK && h.aux_kind == 7 && i < h.n_learners; ++i) rc = behaviour_rw(c, i, nullptr, rf_b.data() + (size_t)i * per_aux);
     if (rc == RSRL_HIP_OK && h.aux_kind == 7) rc = rsrl_hip_set_return_carry(c, rf_g.data());
+    if (rc == RSRL_HIP_OK && h.aux_kind == 8) {
+        const size_t nv = (size_t)c->F * (size_t)c->cfg.n_envs;
+        hipError_t e2 = hipMemcpyAsync(c->lstd_theta, lstd_in.data(), 8 * nv, hipMemcpyHostToDevice, c->stream);
+        if (e2 == hipSuccess) e2 = hipMemcpyAsync(c->lstd_mat, lstd_in.data() + nv, 8 * nv * c->F, hipMemcpyHostToDevice, c->stream);
+        if (e2 == hipSuccess && c->lstd_mu) e2 = hipMemcpyAsync(c->lstd_mu, lstd_in.data() + nv + nv * c->F, 8 * nv, hipMemcpyHostToDevice, c->stream);
+        if (e2 == hipSuccess) e2 = hipStreamSynchronize(c->stream);
+        if (e2 != hipSuccess) rc = fail(RSRL_HIP_EHIP, "installing the LSTD state: %s", hipGetErrorString(e2));
+    }
     if (rc == RSRL_HIP_OK && h.aux_kind == 4) {                        // the last step that can fail: the lengths
         hipError_t e2 = hipMemcpyAsync(c->sp_len, sp_len_t.data(), 4 * sp_len_t.size(), hipMemcpyHostToDevice, c->stream);
         if (e2 == hipSuccess) e2 = hipStreamSynchronize(c->stream);
@@ -509,6 +590,7 @@ int rsrl_hip_set_weights_all(rsrl_hip_ctx* c, const float* w) {
     CHECK_CTX(c); FLUSH(c);
     c->q_valid = false; c->tq_valid = false; if (!w) return fail(RSRL_HIP_EINVAL, "null argument");
     if (c->cfg.algo == RSRL_REINFORCE) return no_value_function(c);
+    if (c->family == AgentFamily::LstdReg) return lstd_weights_rw(c, 0, c->cfg.n_envs, nullptr, w);
     if (c->cfg.weight_mode == RSRL_W_SHARED) return rsrl_hip_set_weights(c, 0, w);
     HIP_TRY(hipSetDevice(c->cfg.device));
     const int n = c->F * c->Aw; const float* d_w;
@@ -549,6 +631,10 @@ int rsrl_hip_checksum(rsrl_hip_ctx* c, uint64_t out[2]) {
     run(c->action, sizeof(int32_t) * N, (size_t)1 << 36, 1);
     run(c->ep_step, sizeof(uint32_t) * N, (size_t)1 << 37, 1);
     run(c->hiv_y, c->hiv_y ? sizeof(double) * 6 * N : 0, (size_t)1 << 38, 1);      // HIVTreatment's hidden states (f64: two words each)
+    // the LSTD agents' f64 state (two words per double) with the weights: theta, the matrices, iLSTD's mu
+    run(c->lstd_theta, c->lstd_theta ? sizeof(double) * c->F * N : 0, (size_t)1 << 41, 0);
+    run(c->lstd_mat, c->lstd_mat ? sizeof(double) * c->F * c->F * N : 0, (size_t)1 << 42, 0);
+    run(c->lstd_mu, c->lstd_mu ? sizeof(double) * c->F * N : 0, (size_t)1 << 43, 0);
     KCHECK();
     unsigned long long h[2];
     HIP_TRY(hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, c->stream));

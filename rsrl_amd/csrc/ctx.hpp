@@ -55,6 +55,8 @@ static inline bool has_aux(int algo) { return is_lambda(algo) || algo == RSRL_GR
 static inline bool is_tdac(int algo) { return algo == RSRL_TD_ACTOR_CRITIC; }
 // REINFORCE / BaselineREINFORCE: theta is the second matrix, theta_b (the behaviour snapshot) a third; W is the baseline B (unused by REINFORCE)
 static inline bool is_reinforce(int algo) { return algo == RSRL_REINFORCE || algo == RSRL_BASELINE_REINFORCE; }
+// RecursiveLSTD / iLSTD: f64 theta, a f64 F x F matrix (and iLSTD's mu) per learner, outside W (which is allocated, one zero column, never read)
+static inline bool is_lstd(int algo) { return algo == RSRL_RECURSIVE_LSTD || algo == RSRL_ILSTD; }
 
 // ---- the small kernels more than one unit launches, and the launches of kernel templates two units would otherwise both instantiate: defined ONCE, in
 // kernels_util.hip / launch_shared.hip (a kernel's host stub is an ordinary function: another unit launches it through this declaration)
@@ -128,6 +130,7 @@ enum class AgentFamily : uint8_t {
     AcReg,                // ActorCritic (both critics), register-family Fourier, per-learner f32 weights: k_train_ac (train_ac.hip); theta in Z
     TdAcReg,              // ActorCritic with the TD(0) V critic, same configurations: k_train_tdac (train_tdac.hip); w in W (one column), theta in Z (A columns)
     ReinforceReg,         // REINFORCE / BaselineREINFORCE, same configurations: k_train_reinforce (train_reinforce.hip); B in W, theta in Z, theta_b in Zb, g in ret_g
+    LstdReg,              // RecursiveLSTD / iLSTD, register-family Fourier, per-learner state: k_train_lstd (train_lstd.hip); f64 state in lstd_theta / lstd_mat / lstd_mu
 };
 static inline bool is_wave_family(AgentFamily f) {
     return f == AgentFamily::WaveAux || f == AgentFamily::WaveQSigma || f == AgentFamily::WaveLambda || f == AgentFamily::WaveControl;
@@ -177,6 +180,9 @@ struct rsrl_hip_ctx {
     float* Zb = nullptr;             // REINFORCE only: the behaviour snapshot theta_b f32[A][F][N] (theta when the open episode began)
     float* ret_g = nullptr;          //   and the open episode's running return g f32[N]
     double* hiv_y = nullptr;         // HIVTreatment only: every learner's hidden state f64[6][N] (`state` holds its observation)
+    double* lstd_theta = nullptr;    // RecursiveLSTD / iLSTD only: theta f64[N][F], the matrix (C / A) f64[N][F][F], iLSTD's mu f64[N][F] (learner-major)
+    double* lstd_mat = nullptr;
+    double* lstd_mu = nullptr;
     bool q_valid = false;            // false whenever weights / states were changed from outside the driver loop
     // ---- the trait-granular fast path (kernels_trait.hpp): register-family Fourier basis, per-learner f32 weights, learner-major layout
     float* tq_key = nullptr;         // [D][N]: the state each learner's qcache entry belongs to (allocated iff the ctx takes the fast path)
@@ -285,6 +291,13 @@ static inline ReinforceState make_reinforce(const rsrl_hip_ctx* c) {
     ReinforceState rs;
     rs.theta = c->Z; rs.theta_b = c->Zb; rs.g = c->ret_g;
     return rs;
+}
+
+static inline LstdState make_lstd(const rsrl_hip_ctx* c) {
+    LstdState ls;
+    ls.theta = c->lstd_theta; ls.mat = c->lstd_mat; ls.mu = c->lstd_mu;
+    ls.gamma = c->cfg.gamma; ls.alpha = c->cfg.alpha; ls.n_updates = c->cfg.algo == RSRL_ILSTD ? c->cfg.n_steps : 0;
+    return ls;
 }
 
 static LambdaParams make_lambda(const rsrl_hip_ctx* c) {

@@ -69,6 +69,28 @@ bool launch_reinforce(int domain, int order, bool baseline, dim3 grid, dim3 bloc
 // new episodes for the learners in mask (every learner when mask is null): theta_b <- theta, g <- 0.  FA = F * A
 void launch_reinforce_restart(hipStream_t st, const ReinforceState& rs, int64_t N, int64_t FA, const uint8_t* mask);
 
+// RecursiveLSTD / iLSTD (train_lstd.hip, kernels_lstd.hpp): every learner's exact f64 state, learner-major, and the config's f64 parameters
+struct LstdState {
+    double* theta = nullptr;     // f64[N][F]
+    double* mat = nullptr;       // f64[N][F][F], row-major per learner: C (RecursiveLSTD) or A (iLSTD)
+    double* mu = nullptr;        // f64[N][F]: iLSTD only
+    double gamma = 0.0, alpha = 0.0;
+    int n_updates = 0;           // iLSTD's solve rounds (config.n_steps)
+};
+// lanes per learner of the LSTD kernels: the power of two >= F
+static inline int lstd_group_lanes(int F) { return F <= 4 ? 4 : (F <= 16 ? 16 : (F <= 32 ? 32 : 64)); }
+// incremental = iLSTD.  io: handle on io's transitions (transition i is learner i's), else chunk batch-steps of the driver loop from t.  The grid is
+// the launcher's own (G lanes per learner)
+bool launch_lstd(int domain, int order, bool incremental, hipStream_t st, const Common& k, const LstdState& ls, uint64_t t, int chunk, DevStats* stats,
+                 const Transitions* io);
+// V(s_i) of learner i for M states; Random.sample of the ctx's learners at (t, blk) into out and k.action; theta <-> f32
+bool launch_lstd_v(int domain, int order, hipStream_t st, const double* theta, const float* states, int64_t M, float* out);
+void launch_lstd_sample(int domain, hipStream_t st, const Common& k, uint64_t t, uint32_t blk, int32_t* out);
+void launch_lstd_theta_get(hipStream_t st, const double* theta, int F, int64_t i, float* w);
+void launch_lstd_theta_set(hipStream_t st, double* theta, int F, int64_t first, int64_t count, const float* w);
+// every learner's F x F block of mat (n = N * F * F doubles) := diag * I
+void launch_lstd_fill_eye(hipStream_t st, double* mat, int64_t n, int F, double diag);
+
 bool launch_td(int domain, int order, bool lambda, dim3 grid, dim3 block, hipStream_t st, const Common& k, const TdParams& tp, uint64_t t, int chunk,
                DevStats* stats, const Transitions* io);
 bool launch_v_evaluate(int domain, int order, dim3 grid, dim3 block, hipStream_t st, const Common& k, const float* states, int64_t Mn, float* out);

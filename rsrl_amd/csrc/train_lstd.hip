@@ -1,0 +1,58 @@
+// train_lstd.hip -- RecursiveLSTD and iLSTD (kernels_lstd.hpp) on the register-family Fourier orders: the fused driver loop, Handler::handle, V(s),
+// the driver loop's Random sample and the theta <-> f32 weights.  Kept in a translation unit of its own so that no other kernel's machine code moves.
+#include "launch.hpp"
+#include "kernels_lstd.hpp"
+#include "model_list.hpp"
+
+namespace rsrl {
+
+#define RSRL_LSTD_CASE(DM, OR)                                                                                                                  \
+    if (domain == DM && order == OR) {                                                                                                          \
+        constexpr int G = LstdGroup<FourierReg<DM, OR>::F>::G;                                                                                  \
+        const int64_t n = io ? io->M : k.n_envs;                                                                                                \
+        const dim3 grid((unsigned)((n * G + kBlock - 1) / kBlock)), block(kBlock);                                                              \
+        if (io) {                                                                                                                               \
+            if (incremental) hipLaunchKernelGGL((k_handle_lstd<DM, OR, LSTD_INCREMENTAL>), grid, block, 0, st, ls, io->from, io->rew, io->to, io->term, io->M, io->td_out); \
+            else hipLaunchKernelGGL((k_handle_lstd<DM, OR, LSTD_RECURSIVE>), grid, block, 0, st, ls, io->from, io->rew, io->to, io->term, io->M, io->td_out); \
+        } else if (incremental) hipLaunchKernelGGL((k_train_lstd<DM, OR, LSTD_INCREMENTAL>), grid, block, 0, st, k, ls, t, chunk, stats);       \
+        else hipLaunchKernelGGL((k_train_lstd<DM, OR, LSTD_RECURSIVE>), grid, block, 0, st, k, ls, t, chunk, stats);                            \
+        return true;                                                                                                                            \
+    }
+
+bool launch_lstd(int domain, int order, bool incremental, hipStream_t st, const Common& k, const LstdState& ls, uint64_t t, int chunk, DevStats* stats,
+                 const Transitions* io) {
+    RSRL_REG_FOURIER(RSRL_LSTD_CASE)
+    return false;
+}
+
+#define RSRL_LSTD_V_CASE(DM, OR)                                                                                                                \
+    if (domain == DM && order == OR) {                                                                                                          \
+        hipLaunchKernelGGL((k_lstd_v<DM, OR>), dim3((unsigned)((M + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, theta, states, M, out);        \
+        return true;                                                                                                                            \
+    }
+
+bool launch_lstd_v(int domain, int order, hipStream_t st, const double* theta, const float* states, int64_t M, float* out) {
+    RSRL_REG_FOURIER(RSRL_LSTD_V_CASE)
+    return false;
+}
+
+void launch_lstd_sample(int domain, hipStream_t st, const Common& k, uint64_t t, uint32_t blk, int32_t* out) {
+    const dim3 grid((unsigned)((k.n_envs + kBlock - 1) / kBlock)), block(kBlock);
+    if (domain == 0) hipLaunchKernelGGL(k_lstd_sample<0>, grid, block, 0, st, k, t, blk, out);
+    else if (domain == 1) hipLaunchKernelGGL(k_lstd_sample<1>, grid, block, 0, st, k, t, blk, out);
+    else hipLaunchKernelGGL(k_lstd_sample<2>, grid, block, 0, st, k, t, blk, out);
+}
+
+void launch_lstd_theta_get(hipStream_t st, const double* theta, int F, int64_t i, float* w) {
+    hipLaunchKernelGGL(k_lstd_theta_get, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, st, theta, F, i, w);
+}
+void launch_lstd_theta_set(hipStream_t st, double* theta, int F, int64_t first, int64_t count, const float* w) {
+    const int64_t n = count * F;
+    hipLaunchKernelGGL(k_lstd_theta_set, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, theta, F, first, count, w);
+}
+
+void launch_lstd_fill_eye(hipStream_t st, double* mat, int64_t n, int F, double diag) {
+    hipLaunchKernelGGL(k_lstd_fill_eye, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, mat, n, F, diag);
+}
+
+}  // namespace rsrl

@@ -237,6 +237,19 @@ struct TDLambda : control::td::Agent {
 };
 }}  // namespace prediction::td
 
+// ---- rsrl::prediction::lstd: RecursiveLSTD::new(basis, gamma) / iLSTD::new(basis, alpha, gamma, n_updates)   (recursive_lstd.rs, ilstd.rs)
+// theta and the F x F matrix are f64 on the device (Session::lstd_state); weights() is theta rounded to f32.  Drive these with policies::Random.
+namespace prediction { namespace lstd {
+struct RecursiveLSTD : control::td::Agent {
+    RecursiveLSTD(const fa::linear::basis::Fourier& basis, double gamma)
+        : control::td::Agent{RSRL_RECURSIVE_LSTD, make_shared(fa::linear::LFA::vector(basis, fa::linear::optim::SGD(0.0), 1)), gamma} {}
+};
+struct iLSTD : control::td::Agent {
+    iLSTD(const fa::linear::basis::Fourier& basis, double alpha_, double gamma, int n_updates)
+        : control::td::Agent{RSRL_ILSTD, make_shared(fa::linear::LFA::vector(basis, fa::linear::optim::SGD(0.0), 1)), gamma, alpha_} { n_steps = n_updates; }
+};
+}}  // namespace prediction::lstd
+
 // ---- the bound object graph: env + agent + policy sharing one q_func on one MI355X -------------------
 class Session {
 public:
@@ -337,6 +350,13 @@ public:
     // the pub field `fa_td` of GreedyGQ                                             (greedy_gq.rs:52)
     std::vector<float> td_weights(int64_t env = 0) {
         std::vector<float> v((size_t)F_ * A_); check(rsrl_hip_get_td_weights(ctx_, env, v.data())); return v;
+    }
+    // RecursiveLSTD / iLSTD: one learner's exact f64 state -- theta [F], the matrix [F][F] (C / A, row-major), iLSTD's mu [F] (empty otherwise)
+    struct LstdState { std::vector<double> theta, mat, mu; };
+    LstdState lstd_state(int64_t env = 0, bool with_mu = false) {
+        LstdState st{std::vector<double>((size_t)F_), std::vector<double>((size_t)F_ * F_), std::vector<double>(with_mu ? (size_t)F_ : 0)};
+        check(rsrl_hip_get_lstd_state(ctx_, env, st.theta.data(), st.mat.data(), with_mu ? st.mu.data() : nullptr));
+        return st;
     }
     // the pub field `policy` of ActorCritic: the Gibbs actor's weights               (ac.rs:61)
     std::vector<float> policy_weights(int64_t env = 0) {
