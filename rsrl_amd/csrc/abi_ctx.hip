@@ -141,6 +141,7 @@ int rsrl_hip_destroy(rsrl_hip_ctx* c) {
     if (c->d_dyn) (void)hipFree(c->d_dyn);
     if (c->qcache) (void)hipFree(c->qcache);
     if (c->tq_key) (void)hipFree(c->tq_key);
+    if (c->tq_q) (void)hipFree(c->tq_q);
     if (c->Z) (void)hipFree(c->Z);
     if (c->Zb) (void)hipFree(c->Zb);
     if (c->ret_g) (void)hipFree(c->ret_g);
@@ -349,8 +350,10 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
     HIP_TRY(hipMalloc((void**)&c->qcache, sizeof(float) * c->A * (size_t)N));
     if (cfg->domain == RSRL_HIV_TREATMENT) HIP_TRY(hipMalloc((void**)&c->hiv_y, sizeof(double) * 6 * (size_t)N));      // (set by the domain reset of create)
     // the trait-granular fast path: learner-major per-learner f32 weights on a basis / agent kernels_trait.hpp is instantiated for, one epsilon for the ctx
-    if (c->w_ls != 1 && cfg->weight_dtype == RSRL_W_F32 && cfg->epsilon_decay == 1.0 && trait_lm_available(cfg->domain, cfg->order, cfg->algo))
+    if (c->w_ls != 1 && cfg->weight_dtype == RSRL_W_F32 && cfg->epsilon_decay == 1.0 && trait_lm_available(cfg->domain, cfg->order, cfg->algo)) {
         HIP_TRY(hipMalloc((void**)&c->tq_key, sizeof(float) * c->D * (size_t)N));
+        HIP_TRY(hipMalloc((void**)&c->tq_q, sizeof(float) * c->A * (size_t)N));
+    }
     if (cfg->algo == RSRL_Q_SIGMA) {
         const size_t nf = (size_t)(c->D + 5) * (size_t)cfg->n_steps * (size_t)N;
         HIP_TRY(hipMalloc((void**)&c->qs_buf, sizeof(float) * nf));

@@ -40,7 +40,7 @@ int launch_trait_handle(rsrl_hip_ctx* c, const Common& k, const float* from, con
                                const uint8_t* term, int64_t M, uint64_t t, float* td) {
     TRY(trait_cache_ready(c));
     TraitIo io{};
-    io.from = from; io.act = act; io.rew = rew; io.to = to; io.termf = term; io.td_out = td; io.qkey = c->tq_key; io.Mn = M;
+    io.from = from; io.act = act; io.rew = rew; io.to = to; io.termf = term; io.td_out = td; io.qkey = c->tq_key; io.qval = c->tq_q; io.Mn = M;
     TRY(timing_begin(c));
     if (!launch_trait_lm(c->cfg.domain, c->cfg.order, c->cfg.algo, -1, c->stream, k, io, t)) return NO_MODEL(c);
     KCHECK();
@@ -143,7 +143,9 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
     TRY(stage_in(c, 4, iin, (size_t)M_, &d_iin));
     // the policy's operations read the policy's weights (ActorCritic: the Gibbs actor's theta), the rest the action-value function
     const bool policy_op = op == QOP_SAMPLE || op == QOP_SAMPLE_STEP || op == QOP_SAMPLE_INIT || op == QOP_MODE || op == QOP_PROBS || op == QOP_PROB_SA;
-    const Common k = policy_op ? make_policy_common(c) : make_common(c);
+    Common k = policy_op ? make_policy_common(c) : make_common(c);
+    // REINFORCE's driver-loop sample of an open episode is the behaviour policy's, pi_theta_b (kernels_reinforce.hpp): what train drew for batch-step t
+    if (c->family == AgentFamily::ReinforceReg && op == QOP_SAMPLE_STEP) k.W = c->Zb;
     const uint64_t call = (op == QOP_SAMPLE_STEP || op == QOP_SAMPLE_INIT) ? step_t : c->api_calls;      // (the driver loop's sample: addressed by the batch-step)
     if (op == QOP_SAMPLE) c->api_calls++;
     const BasisGeom g = make_geom(c);
@@ -230,7 +232,7 @@ static int sample_emit(rsrl_hip_ctx* c, int64_t M, int32_t* actions_out) {
         const Common k = make_common(c);
         TraitIo io{};
         io.act = p.act; io.td_out = p.td; io.o_from = p.from; io.o_to = p.to; io.o_rew = p.rew; io.o_term = p.term; io.o_act = actions_out;
-        io.qkey = c->tq_key; io.Mn = M;
+        io.qkey = c->tq_key; io.qval = c->tq_q; io.Mn = M;
         TRY(timing_begin(c));
         if (!launch_trait_lm(c->cfg.domain, c->cfg.order, c->cfg.algo, c->cfg.policy, c->stream, k, io, p.t_handle)) return NO_MODEL(c);
         KCHECK();
@@ -247,7 +249,7 @@ static int sample_emit(rsrl_hip_ctx* c, int64_t M, int32_t* actions_out) {
         TRY(trait_cache_ready(c));
         const Common k = make_common(c);
         TRY(timing_begin(c));
-        if (!launch_trait_sample(c->cfg.domain, c->cfg.order, c->stream, k, nullptr, M, t, blk, c->tq_key, oa.dev)) return NO_MODEL(c);
+        if (!launch_trait_sample(c->cfg.domain, c->cfg.order, c->stream, k, nullptr, M, t, blk, c->tq_key, c->tq_q, oa.dev)) return NO_MODEL(c);
         KCHECK();
         TRY(timing_end(c));
         bool sync = false;
@@ -274,7 +276,7 @@ int rsrl_hip_policy_sample(rsrl_hip_ctx* c, const float* states, int64_t M, int3
         TRY(trait_cache_ready(c));
         const Common k = make_common(c);
         const uint64_t call = c->api_calls++;
-        if (!launch_trait_sample(c->cfg.domain, c->cfg.order, c->stream, k, d_states, M, call, BLK_API, c->tq_key, oa.dev)) return NO_MODEL(c);
+        if (!launch_trait_sample(c->cfg.domain, c->cfg.order, c->stream, k, d_states, M, call, BLK_API, c->tq_key, c->tq_q, oa.dev)) return NO_MODEL(c);
         KCHECK();
         bool sync = !is_device_ptr(states);
         TRY(flush_out(c, &oa, &sync));

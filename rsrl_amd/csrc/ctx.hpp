@@ -185,8 +185,9 @@ struct rsrl_hip_ctx {
     double* lstd_mu = nullptr;
     bool q_valid = false;            // false whenever weights / states were changed from outside the driver loop
     // ---- the trait-granular fast path (kernels_trait.hpp): register-family Fourier basis, per-learner f32 weights, learner-major layout
-    float* tq_key = nullptr;         // [D][N]: the state each learner's qcache entry belongs to (allocated iff the ctx takes the fast path)
-    bool tq_valid = false;           // qcache / tq_key hold the hand-over of rsrl_hip_handle (false: the keys are emptied before the next trait kernel)
+    float* tq_key = nullptr;         // [D][N]: the state each learner's tq_q entry belongs to (allocated iff the ctx takes the fast path)
+    float* tq_q = nullptr;           // [A][N]: the hand-over's Q(key,.) -- its own buffer: qcache is the train loops' carry, which a query must not touch
+    bool tq_valid = false;           // tq_q / tq_key hold the hand-over of rsrl_hip_handle (false: the keys are emptied before the next trait kernel)
     // calls of the trait-granular loop accepted but not launched yet (ctx-owned stream, device pointers, the loop's own order):
     //   stage 1 = domain_step, 2 = + handle on exactly that transition, 3 = + domain_reset with the terminal flags as its mask;
     //   policy_sample(NULL) then launches the whole batch-step as ONE kernel; anything else launches the accepted calls one by one first

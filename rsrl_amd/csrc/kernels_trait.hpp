@@ -36,7 +36,8 @@ struct TraitIo {
     float* td_out;
     // TRAIT_STEP: `act` = rsrl_hip_domain_step's actions argument (null: the ctx's pending actions); its outputs and policy_sample's (stride n_envs; each optional)
     float* o_from; float* o_to; float* o_rew; uint8_t* o_term; int32_t* o_act;
-    float* qkey;          // [D][N]: the state qcache's entry of a learner belongs to
+    float* qkey;          // [D][N]: the state a learner's qval entry belongs to
+    float* qval;          // [A][N]: the hand-over, Q(qkey,.) (not Common::qcache: that is rsrl_hip_train's carry, which these calls leave alone)
     int64_t Mn;
 };
 
@@ -196,7 +197,7 @@ __global__ __launch_bounds__(kBlock) void k_trait_lm(Common c, TraitIo io, uint6
             if (io.td_out) io.td_out[i] = delta;
         }
 #pragma unroll
-        for (int b = 0; b < A; ++b) c.qcache[(int64_t)b * N + i] = q_n[b];
+        for (int b = 0; b < A; ++b) io.qval[(int64_t)b * N + i] = q_n[b];
 #pragma unroll
         for (int d = 0; d < D; ++d) io.qkey[(int64_t)d * N + i] = ns[d];
     }
@@ -206,7 +207,7 @@ __global__ __launch_bounds__(kBlock) void k_trait_lm(Common c, TraitIo io, uint6
 // also becomes the ctx's pending one; blk = BLK_STEP (the driver loop's behaviour draw of batch-step t) or BLK_API (the API stream, t = call counter).
 template <int DOMAIN, int ORDER>
 __global__ __launch_bounds__(kBlock) void k_trait_sample(Common c, const float* __restrict__ states, int64_t Mn, uint64_t t, uint32_t blk,
-                                                          float* __restrict__ qkey, int32_t* __restrict__ actions_out) {
+                                                          float* __restrict__ qkey, float* __restrict__ qval, int32_t* __restrict__ actions_out) {
     using Dom = Domain<DOMAIN>;
     using Bas = FourierReg<DOMAIN, ORDER>;
     constexpr int D = Dom::D, A = Dom::A, F = Bas::F, AF = A * F;
@@ -221,7 +222,7 @@ __global__ __launch_bounds__(kBlock) void k_trait_sample(Common c, const float* 
         key[d] = qkey[(int64_t)d * N + i];
     }
 #pragma unroll
-    for (int b = 0; b < A; ++b) q[b] = c.qcache[(int64_t)b * N + i];
+    for (int b = 0; b < A; ++b) q[b] = qval[(int64_t)b * N + i];
     if (!same_bits<D>(s, key)) {
         // no hand-over for this state (a restart the caller made by other means, a state of the caller's own): evaluate from the learner's weights
         typedef float f4 __attribute__((ext_vector_type(4)));
@@ -237,7 +238,7 @@ __global__ __launch_bounds__(kBlock) void k_trait_sample(Common c, const float* 
         q_from_reg<A, F>(wv, phi, q);
         // the entry now belongs to this state
 #pragma unroll
-        for (int b = 0; b < A; ++b) c.qcache[(int64_t)b * N + i] = q[b];
+        for (int b = 0; b < A; ++b) qval[(int64_t)b * N + i] = q[b];
 #pragma unroll
         for (int d = 0; d < D; ++d) qkey[(int64_t)d * N + i] = s[d];
     }
@@ -254,7 +255,7 @@ namespace rsrl {
 // policy < 0: Handler::handle on the caller's transitions (TRAIT_HANDLE); otherwise the fused batch-step (TRAIT_STEP)
 bool launch_trait_lm(int domain, int order, int algo, int policy, hipStream_t st, const Common& k, const TraitIo& io, uint64_t t);
 bool launch_trait_sample(int domain, int order, hipStream_t st, const Common& k, const float* states, int64_t Mn, uint64_t t, uint32_t blk, float* qkey,
-                         int32_t* actions_out);
+                         float* qval, int32_t* actions_out);
 bool trait_lm_available(int domain, int order, int algo);
 }  // namespace rsrl
 
@@ -273,6 +274,6 @@ bool trait_lm_available(int domain, int order, int algo);
 #define RSRL_TRAIT_ALGOS(DM, OR) RSRL_TRAIT_CASE(DM, OR, 0) RSRL_TRAIT_CASE(DM, OR, 1) RSRL_TRAIT_CASE(DM, OR, 2) RSRL_TRAIT_CASE(DM, OR, 5)
 #define RSRL_TRAIT_SAMPLE_CASE(DM, OR)                                                                                                           \
     if (domain == DM && order == OR) {                                                                                                           \
-        hipLaunchKernelGGL((k_trait_sample<DM, OR>), dim3((unsigned)((Mn + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, k, states, Mn, t, blk, qkey, actions_out); \
+        hipLaunchKernelGGL((k_trait_sample<DM, OR>), dim3((unsigned)((Mn + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, k, states, Mn, t, blk, qkey, qval, actions_out); \
         return true;                                                                                                                             \
     }

@@ -17,7 +17,7 @@ bool launch_trait_lm(int domain, int order, int algo, int policy, hipStream_t st
     return launch_trait_lm_d12(domain, order, algo, policy, st, k, io, t);
 }
 bool launch_trait_sample(int domain, int order, hipStream_t st, const Common& k, const float* states, int64_t Mn, uint64_t t, uint32_t blk, float* qkey,
-                         int32_t* actions_out) {
+                         float* qval, int32_t* actions_out) {
     RSRL_TRAIT_SAMPLE_CASE(0, 1) RSRL_TRAIT_SAMPLE_CASE(0, 3) RSRL_TRAIT_SAMPLE_CASE(0, 5) RSRL_TRAIT_SAMPLE_CASE(1, 1) RSRL_TRAIT_SAMPLE_CASE(2, 1)
     return false;
 }

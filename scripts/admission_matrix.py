@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Which configurations rsrl_hip_create admits, asked of the library on a machine WITHOUT a GPU: every admission rule runs before the device
-query, so a refused configuration returns EINVAL and an admitted one EHIP ("no device").  Sweeps GRID (133 120 configurations, about 1 s).
-    python scripts/admission_matrix.py            writes tests/golden/create_admission.json (tests/test_create_admission_cpu.py holds the library to it)
-    python scripts/admission_matrix.py --check    exits 1 if the library and the stored fixture disagree
+query, so a refused configuration returns EINVAL and an admitted one EHIP ("no device").  Sweeps GRID (133 120 configurations, about 1 s) and
+GRID_AGENTS -- the algos numbered after GRID's (13-19) on the same other axes, 71 680 configurations -- each into a fixture of its own.
+    python scripts/admission_matrix.py            writes tests/golden/create_admission.json and create_admission_agents.json
+                                                  (tests/test_create_admission_cpu.py holds the library to them)
+    python scripts/admission_matrix.py --check    exits 1 if the library and a stored fixture disagree
 Each admitted configuration is stored as one character per axis: the index of its value in that axis, in hex."""
 import ctypes as C
 import itertools
@@ -13,6 +15,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission.json")
+AGENTS_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_agents.json")
 EINVAL, EHIP = -1, -2
 
 # (config field, values): the first axis varies slowest
@@ -29,19 +32,22 @@ GRID = [
     ("epsilon_decay", [1.0, 0.99]),
     ("steps_per_launch", [0, 1]),
 ]
+# the TD ActorCritic (13), REINFORCE / BaselineREINFORCE (15, 16), RecursiveLSTD / iLSTD (18, 19) and the unassigned 14 and 17, on GRID's other axes
+GRID_AGENTS = [(name, list(range(13, 20)) if name == "algo" else vals) for name, vals in GRID]
+GRIDS = ((GRID, FIXTURE), (GRID_AGENTS, AGENTS_FIXTURE))
 
 
-def sweep():
-    """{index string: (return code, last error)} for every configuration of GRID."""
+def sweep(grid=GRID):
+    """{index string: (return code, last error)} for every configuration of the grid."""
     from rsrl_amd import _abi
     L = _abi.lib()
     base = _abi.Config()
     assert L.rsrl_hip_config_init(C.byref(base)) == 0
     out = {}
     h = C.c_void_p()
-    for idx in itertools.product(*(range(len(v)) for _, v in GRID)):
+    for idx in itertools.product(*(range(len(v)) for _, v in grid)):
         cfg = _abi.Config.from_buffer_copy(base)
-        for (name, vals), i in zip(GRID, idx):
+        for (name, vals), i in zip(grid, idx):
             setattr(cfg, name, vals[i])
         rc = L.rsrl_hip_create(C.byref(cfg), C.byref(h))
         out["".join("%x" % i for i in idx)] = (rc, (L.rsrl_hip_last_error() or b"").decode())
@@ -53,22 +59,26 @@ def admitted(results):
 
 
 def main():
-    res = sweep()
-    if any(rc == 0 for rc, _ in res.values()):
-        sys.exit("a ctx was created: run this on a machine without a GPU")
-    bad = sorted({rc for rc, _ in res.values()} - {EINVAL, EHIP})
-    if bad:
-        sys.exit(f"unexpected return codes {bad}")
-    doc = {"grid": [[n, v] for n, v in GRID], "admitted": admitted(res)}
-    if "--check" in sys.argv:
-        ok = json.load(open(FIXTURE)) == doc
-        print("fixture matches" if ok else "fixture DIFFERS")
-        sys.exit(0 if ok else 1)
-    with open(FIXTURE, "w") as f:         # one admitted configuration per line, so that a diff reads
-        f.write('{"grid": %s,\n "admitted": [\n' % json.dumps(doc["grid"]))
-        f.write(",\n".join(json.dumps(k) for k in doc["admitted"]))
-        f.write("\n]}\n")
-    print(f"{len(doc['admitted'])} of {len(res)} configurations admitted -> {os.path.relpath(FIXTURE, ROOT)}")
+    ok = True
+    for grid, fixture in GRIDS:
+        res = sweep(grid)
+        if any(rc == 0 for rc, _ in res.values()):
+            sys.exit("a ctx was created: run this on a machine without a GPU")
+        bad = sorted({rc for rc, _ in res.values()} - {EINVAL, EHIP})
+        if bad:
+            sys.exit(f"unexpected return codes {bad}")
+        doc = {"grid": [[n, v] for n, v in grid], "admitted": admitted(res)}
+        if "--check" in sys.argv:
+            same = json.load(open(fixture)) == doc
+            print(f"{os.path.relpath(fixture, ROOT)}: " + ("fixture matches" if same else "fixture DIFFERS"))
+            ok = ok and same
+            continue
+        with open(fixture, "w") as f:         # one admitted configuration per line, so that a diff reads
+            f.write('{"grid": %s,\n "admitted": [\n' % json.dumps(doc["grid"]))
+            f.write(",\n".join(json.dumps(k) for k in doc["admitted"]))
+            f.write("\n]}\n")
+        print(f"{len(doc['admitted'])} of {len(res)} configurations admitted -> {os.path.relpath(fixture, ROOT)}")
+    sys.exit(0 if ok else 1)
 
 
 if __name__ == "__main__":

@@ -17,10 +17,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import rsrl_amd as ra  # noqa: E402
 from rsrl_amd import _abi  # noqa: E402
 
+VALID_ALGOS = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 16, 18, 19)       # 12, 14 and 17 are no algo
 BAD_F = [float("nan"), float("inf"), -float("inf"), -1.0, 0.0, 1e308, -1e-320, 2.0]
 INT_FIELDS = {
-    "domain": [-1, 3, 99, 0, 1, 2], "basis": [-1, 2, 0, 1], "order": [-3, 0, 8, 100, 1, 5, 7], "n_tilings": [-1, 0, 3, 5, 64, 4, 8, 16],
-    "tiles_per_dim": [-1, 0, 1, 2, 1000, 65536, 8], "algo": [-1, 10, 255, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9], "policy": [-1, 4, 7, 0, 1, 2, 3],
+    "domain": [-1, 4, 99, 0, 1, 2, 3], "basis": [-1, 2, 0, 1], "order": [-3, 0, 8, 100, 1, 5, 7], "n_tilings": [-1, 0, 3, 5, 64, 4, 8, 16],
+    "tiles_per_dim": [-1, 0, 1, 2, 1000, 65536, 8], "algo": [-1, 12, 14, 17, 20, 255] + list(VALID_ALGOS), "policy": [-1, 4, 7, 0, 1, 2, 3],
     "weight_mode": [-1, 2, 0, 1], "weight_dtype": [-1, 2, 5, 0, 1], "trace": [-1, 3, 0, 1, 2], "agent_policy": [-2, 4, -1, 0, 1, 2],
     "exchange": [-1, 3, 9, 0, 1, 2], "n_steps": [-1, 0, 33, 1000, 1, 4, 32], "peer_timeout_ms": [-5, 0, 1, 10 ** 9], "device": [-1, 1, 99, 0],
 }
@@ -111,11 +112,81 @@ def poke(L, h, rng, log):
         L.rsrl_hip_sync(h)
         return rcs
     calls.append(ranks_bad)
+    def newer_bad():                                   # the newer agents' entry points (REINFORCE's batches, LSTD's f64 state, the actor's theta, HIV's hidden state):
+        T = int(rng.choice([1, 3]))                    # null arrays, non-finite values, learner indices out of range, lengths[i] > T, T < 0 -- on every ctx
+        nonfin = float(rng.choice([np.nan, np.inf, -np.inf, 1e30]))
+        sb = np.zeros((T, D, N), dtype=np.float32); ab = np.zeros((T, N), dtype=np.int32); rb = np.full((T, N), nonfin, dtype=np.float32)
+        ln = rng.integers(0, T + 1, N).astype(np.uint32); ret = np.zeros((T, N), dtype=np.float32)
+        over = ln.copy(); over[int(rng.integers(0, N))] = T + 1
+        badact = ab.copy(); badact[0, int(rng.integers(0, N))] = int(rng.choice([-1, A, 2 ** 31 - 1]))
+        rcs = [L.rsrl_hip_handle_batch(h, -1, p(sb), p(ab), p(rb), p(ln), p(ret)), L.rsrl_hip_handle_batch(h, -2 ** 40, None, None, None, p(ln), None),
+               L.rsrl_hip_handle_batch(h, T, p(sb), p(ab), p(rb), p(over), p(ret)), L.rsrl_hip_handle_batch(h, T, p(sb), p(badact), p(rb), p(np.full(N, T, np.uint32)), None),
+               L.rsrl_hip_handle_batch(h, T, None, p(ab), p(rb), p(ln), None), L.rsrl_hip_handle_batch(h, T, p(sb), p(ab), p(rb), None, None),
+               L.rsrl_hip_handle_batch(h, 0, None, None, None, p(np.zeros(N, np.uint32)), None),
+               L.rsrl_hip_handle_batch(h, T, p(sb), p(ab), p(rb), p(ln), p(ret))]
+        th = np.full(F * A + 16, nonfin, dtype=np.float32)
+        for j in (-1, N, 2 ** 40, 0):
+            rcs += [L.rsrl_hip_get_policy_weights(h, j, p(big) if F * A <= big.size else None), L.rsrl_hip_get_behaviour_weights(h, j, p(big) if F * A <= big.size else None)]
+        rcs += [L.rsrl_hip_get_policy_weights(h, 0, None), L.rsrl_hip_set_policy_weights(h, 0, None), L.rsrl_hip_set_policy_weights(h, N, p(th)),
+                L.rsrl_hip_set_policy_weights(h, 0, p(th)), L.rsrl_hip_get_behaviour_weights(h, 0, None), L.rsrl_hip_set_behaviour_weights(h, -1, p(th)),
+                L.rsrl_hip_set_behaviour_weights(h, N - 1, p(th)), L.rsrl_hip_set_behaviour_weights(h, 0, None)]
+        g = np.full(N, nonfin, dtype=np.float32)
+        rcs += [L.rsrl_hip_get_return_carry(h, None), L.rsrl_hip_set_return_carry(h, None), L.rsrl_hip_get_return_carry(h, p(g)), L.rsrl_hip_set_return_carry(h, p(g))]
+        theta, mat, mu = np.full(F, nonfin), np.full((F, F), nonfin), np.full(F, nonfin)
+        for j in (-1, N, 2 ** 40):
+            rcs += [L.rsrl_hip_get_lstd_state(h, j, p(theta), p(mat), p(mu)), L.rsrl_hip_set_lstd_state(h, j, p(theta), p(mat), p(mu))]
+        rcs += [L.rsrl_hip_get_lstd_state(h, 0, None, p(mat), None), L.rsrl_hip_get_lstd_state(h, 0, p(theta), None, None),
+                L.rsrl_hip_set_lstd_state(h, 0, None, p(mat), None), L.rsrl_hip_set_lstd_state(h, 0, p(theta), None, p(mu)),
+                L.rsrl_hip_set_lstd_state(h, N - 1, p(theta), p(mat), None if rng.random() < 0.5 else p(mu))]
+        y = np.full((6, N), float(rng.choice([np.nan, np.inf, -1.0, 0.0, 1e300])), dtype=np.float64)
+        rcs += [L.rsrl_hip_get_hidden_states(h, None), L.rsrl_hip_set_hidden_states(h, None), L.rsrl_hip_set_hidden_states(h, p(y))]
+        rcs.append(L.rsrl_hip_train(h, 3, None))
+        L.rsrl_hip_sync(h)
+        return rcs
+    calls.append(newer_bad)
     order = rng.permutation(len(calls))[: int(rng.integers(3, 12))]
     for j in order:
         rc = calls[int(j)]()
         log.append((int(j), rc if not isinstance(rc, tuple) else list(rc)))
     L.rsrl_hip_sync(h)
+
+
+def draw_config(L, rng):
+    """a plausible base, then 0-4 fields pushed out of range"""
+    cfg = _abi.Config()
+    L.rsrl_hip_config_init(C.byref(cfg))
+    cfg.n_envs = int(rng.choice([1, 3, 64, 300, 2000]))
+    cfg.seed = int(rng.integers(0, 1 << 30))
+    cfg.domain = int(rng.integers(0, 4)); cfg.basis = int(rng.integers(0, 2)); cfg.algo = int(rng.integers(0, 20)); cfg.policy = int(rng.integers(0, 4))
+    cfg.order = int(rng.choice([1, 2, 3, 5, 7])); cfg.weight_mode = int(rng.random() < 0.25)
+    if cfg.algo in (10, 11, 13, 15, 16, 18, 19) and rng.random() < 0.75:     # the actor-critics / REINFORCE (Gibbs: Softmax) and LSTD (Random) on their own ground
+        cfg.policy, cfg.basis, cfg.weight_mode = (3 if cfg.algo >= 18 else 2), 0, 0
+        cfg.order = int(rng.integers(1, 6)) if cfg.domain == 0 else 1
+    if cfg.domain == 3 and cfg.algo not in (10, 11, 13, 15, 16, 18, 19) and rng.random() < 0.75:     # HIVTreatment: a one-step agent, Fourier order 1-3
+        cfg.algo, cfg.basis, cfg.weight_mode, cfg.order = int(rng.choice([0, 1, 2, 5])), 0, 0, int(rng.integers(1, 4))
+    for _ in range(int(rng.integers(0, 5))):
+        k = rng.integers(0, 4)
+        if k == 0:
+            name = str(rng.choice(list(INT_FIELDS)))
+            setattr(cfg, name, int(rng.choice(INT_FIELDS[name])))
+        elif k == 1:
+            setattr(cfg, str(rng.choice(F_FIELDS)), float(rng.choice(BAD_F)))
+        elif k == 2:
+            cfg.n_envs = int(rng.choice([0, -1, -2 ** 40, 2 ** 62, 1]))
+        else:
+            name = str(rng.choice(["env_offset", "max_episode_steps", "steps_per_launch", "struct_size"]))
+            val = {"env_offset": [-1, 2 ** 40, 2 ** 32 - 1], "max_episode_steps": [0, 1, 2 ** 32 - 1], "steps_per_launch": [0, 1, 2 ** 32 - 1, 3],
+                   "struct_size": [0, 4, 17, 10 ** 6, C.sizeof(_abi.Config) - 8]}[name]
+            setattr(cfg, name, int(rng.choice(val)))
+    # never ask for more than ~2 GB: a table of F*A floats (twice with an auxiliary matrix) per learner
+    dims = {0: 2, 3: 6}.get(cfg.domain, 4)
+    feats = (max(1, min(8, cfg.order)) + 1) ** dims if cfg.basis == 0 else max(1, min(16, cfg.n_tilings)) * max(1, min(64, cfg.tiles_per_dim)) ** dims
+    per_learner = feats * 4 * 4 * 2 + (feats * feats * 8 if cfg.algo in (18, 19) else 0)      # (RecursiveLSTD / iLSTD: an f64 F x F matrix each)
+    if 0 < cfg.n_envs <= 10 ** 7 and cfg.weight_mode == 0 and per_learner * cfg.n_envs > 2e9:
+        cfg.n_envs = max(1, int(2e9 / per_learner))
+    if cfg.peer_timeout_ms == 0 or cfg.peer_timeout_ms > 300:
+        cfg.peer_timeout_ms = 200                               # (a rank whose peers never show up gives up after 0.2 s instead of the default 4 s)
+    return cfg
 
 
 def main():
@@ -126,33 +197,7 @@ def main():
     ref = healthy_checksum()
     created = refused = 0
     for idx in range(n_cases):
-        cfg = _abi.Config()
-        L.rsrl_hip_config_init(C.byref(cfg))
-        cfg.n_envs = int(rng.choice([1, 3, 64, 300, 2000]))
-        cfg.seed = int(rng.integers(0, 1 << 30))
-        # a plausible base, then 1-4 fields pushed out of range
-        cfg.domain = int(rng.integers(0, 3)); cfg.basis = int(rng.integers(0, 2)); cfg.algo = int(rng.integers(0, 10)); cfg.policy = int(rng.integers(0, 4))
-        cfg.order = int(rng.choice([1, 2, 3, 5, 7])); cfg.weight_mode = int(rng.random() < 0.25)
-        for _ in range(int(rng.integers(0, 5))):
-            k = rng.integers(0, 4)
-            if k == 0:
-                name = str(rng.choice(list(INT_FIELDS)))
-                setattr(cfg, name, int(rng.choice(INT_FIELDS[name])))
-            elif k == 1:
-                setattr(cfg, str(rng.choice(F_FIELDS)), float(rng.choice(BAD_F)))
-            elif k == 2:
-                cfg.n_envs = int(rng.choice([0, -1, -2 ** 40, 2 ** 62, 1]))
-            else:
-                name = str(rng.choice(["env_offset", "max_episode_steps", "steps_per_launch", "struct_size"]))
-                val = {"env_offset": [-1, 2 ** 40, 2 ** 32 - 1], "max_episode_steps": [0, 1, 2 ** 32 - 1], "steps_per_launch": [0, 1, 2 ** 32 - 1, 3],
-                       "struct_size": [0, 4, 17, 10 ** 6, C.sizeof(_abi.Config) - 8]}[name]
-                setattr(cfg, name, int(rng.choice(val)))
-        # never ask for more than ~2 GB: a table of F*A floats (twice with an auxiliary matrix) per learner
-        feats = (max(1, min(8, cfg.order)) + 1) ** (2 if cfg.domain == 0 else 4) if cfg.basis == 0 else max(1, min(16, cfg.n_tilings)) * max(1, min(64, cfg.tiles_per_dim)) ** (2 if cfg.domain == 0 else 4)
-        if 0 < cfg.n_envs <= 10 ** 7 and cfg.weight_mode == 0 and feats * 3 * 4 * 2 * cfg.n_envs > 2e9:
-            cfg.n_envs = max(1, int(2e9 / (feats * 24)))
-        if cfg.peer_timeout_ms == 0 or cfg.peer_timeout_ms > 300:
-            cfg.peer_timeout_ms = 200                               # (a rank whose peers never show up gives up after 0.2 s instead of the default 4 s)
+        cfg = draw_config(L, rng)
         h = C.c_void_p()
         rc = L.rsrl_hip_create(C.byref(cfg), C.byref(h))
         log = []

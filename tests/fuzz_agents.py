@@ -1,0 +1,417 @@
+#!/usr/bin/env python3
+"""Random campaign over the newer agents -- ActorCritic / QActorCritic (10, 11), the TD ActorCritic (13), REINFORCE / BaselineREINFORCE (15, 16),
+RecursiveLSTD / iLSTD (18, 19) on every register-family Fourier order, and the one-step agents on HIVTreatment (orders 1-3) -- at random learner
+counts (ragged waves and LSTD lane groups), env offsets, discounts, step sizes, temperatures, episode caps and launch depths.  Legs:
+
+    f64      Handler::handle on random in-bounds transitions (some terminal) for learners 0..M-1, M in {1, a random M < N, N}: learners M..N-1
+             bitwise untouched, up to 8 of the handled learners replayed in f64 (tests/{ac,tdac,lstd,hiv}_numpy.py) at the per-agent tests' bounds
+    batch    REINFORCE's handle_batch with a random T and ragged lengths (0 and T among them): returns bit for bit, theta against reinforce_batch
+    self     one uninterrupted train() against random splits with queries between them (which must change nothing), the host trait loop,
+             two env_offset shards, and a checkpoint saved and resumed -- bit for bit
+
+    python tests/fuzz_agents.py [n_cases=200] [seed=0]          (GPU box; test infrastructure: imports oracle/)
+
+One line per case and a SUMMARY {json} line; exit code 1 on any mismatch."""
+import json
+import os
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import rsrl_amd as ra  # noqa: E402
+from oracle import oracle as orc  # noqa: E402
+import fuzz_parity as fp  # noqa: E402
+from tests import hiv_numpy as hv  # noqa: E402
+from tests.ac_numpy import ac_rule  # noqa: E402
+from tests.lstd_numpy import ilstd, near_tie_band, recursive_lstd  # noqa: E402
+from tests.reinforce_numpy import reinforce_batch  # noqa: E402
+from tests.tdac_numpy import tdac_rule  # noqa: E402
+
+NAMES = {0: "HIV/QLearning", 1: "HIV/SARSA", 2: "HIV/ExpectedSARSA", 5: "HIV/PAL", 10: "ActorCritic", 11: "QActorCritic", 13: "TDActorCritic",
+         15: "REINFORCE", 16: "BaselineREINFORCE", 18: "RecursiveLSTD", 19: "iLSTD"}
+REG = [(0, o) for o in (1, 2, 3, 4, 5)] + [(1, 1), (2, 1)]          # the register-family Fourier orders check_config admits for them
+N_DIM = {0: 2, 1: 4, 2: 4, 3: 6}
+HIV_LO, HIV_HI = [-5.0] * 6, [8.0] * 6
+EPS64 = np.finfo(np.float64).eps
+TRAIT_LOOP = (10, 11, 13, 18, 19, 0, 1, 2, 5)                        # whose test file asserts train == the host trait loop
+
+
+AGENTS = (10, 11, 13, 15, 16, 18, 19, -1)                           # -1: HIVTreatment with a one-step agent
+
+
+def sample(rng, idx=None):
+    """-> device kwargs of one configuration (case idx: the agents in turn)"""
+    algo = AGENTS[idx % len(AGENTS)] if idx is not None else int(rng.choice(AGENTS))
+    if algo < 0:
+        algo = int(rng.choice([0, 1, 2, 5]))
+    if algo in (0, 1, 2, 5):
+        domain, order = 3, int(rng.integers(1, 4))
+    else:
+        domain, order = REG[int(rng.integers(0, len(REG)))]
+    F = (order + 1) ** N_DIM[domain]
+    kw = dict(domain=domain, order=order, algo=algo, seed=int(rng.integers(0, 1 << 20)), gamma=float(rng.choice([0.0, 0.9, 0.99, 1.0])),
+              lr=float(rng.choice([0.02, 0.2])) / F, alpha=float(rng.choice([0.02, 0.2])) / F, tau=float(rng.choice([0.05, 0.5, 1.0, 5.0])),
+              n_envs=int(rng.choice([1, 3, 5, 63, 64, 65, 130, 257, 1000])), env_offset=int(rng.choice([0, 64, 1000003])),
+              max_episode_steps=int(rng.choice([0, 1, 25, 200])), steps_per_launch=int(rng.choice([0, 1, 5])))
+    if algo in (10, 11, 13, 15, 16):
+        kw["policy"] = ra.SOFTMAX
+    elif algo in (18, 19):
+        kw["policy"] = ra.RANDOM
+        kw["n_steps"] = int(rng.choice([1, 2, 7, 32]))
+    else:
+        kw.update(policy=ra.EPSILON_GREEDY, epsilon=float(rng.choice([0.0, 0.1, 0.5])))
+        if algo in (2, 5):
+            kw["alpha"] = float(rng.choice([0.5, 1.0]))
+    return kw
+
+
+def rand_states(domain, n, rng):
+    lo, hi = (HIV_LO, HIV_HI) if domain == 3 else orc.domain_bounds(domain)
+    return rng.uniform(lo, hi, size=(n, len(lo))).T.astype(np.float32)
+
+
+def near_boundary(p, x, margin=1e-5):
+    """the draw's uniform lies within margin of a cumulative-probability boundary: an fp32 rounding may pick the neighbour"""
+    u = (int(x[2]) >> 8) / 16777216.0
+    return bool(np.min(np.abs(np.cumsum(p)[:-1] - u), initial=1.0) < margin)
+
+
+def hiv_rule(algo, W, phi_s, phi_n, a, r, gamma, alpha, eps, x_inner):
+    """the one-step agents' TD error and the error sent on, f64 (tests/test_gpu_hiv.py; HIVTreatment never terminates)"""
+    qs, qn = W.T @ phi_s, W.T @ phi_n
+    if algo == ra.QLEARNING:
+        d = r + gamma * qn.max() - qs[a]
+        return d, d
+    if algo == ra.SARSA:
+        na = orc.policy_sample(orc.EGREEDY, qn, x_inner, eps=eps)
+        d = r + gamma * qn[na] - qs[a]
+        return d, d
+    if algo == ra.EXPECTED_SARSA:
+        p = orc.policy_probs(orc.EGREEDY, qn, eps=eps)
+        d = r + gamma * float(np.dot(qn, p)) - qs[a]
+        return d, alpha * d
+    ast, nast = orc.argmax_first(qs), orc.argmax_first(qn)
+    td = r + gamma * qn[ast] - qs[a]
+    d = max(td - alpha * (qs[ast] - qs[a]), td - alpha * (qn[nast] - qn[a]))
+    return d, alpha * d
+
+
+def learner_state(c, i):
+    """everything one learner learns, as arrays (bitwise comparisons)"""
+    al = c.cfg.algo
+    if al in (18, 19):
+        th, mat, mu = c.get_lstd_state(i)
+        return [th, mat] + ([] if mu is None else [mu])
+    out = [] if al == ra.REINFORCE else [c.get_weights(i)]          # (REINFORCE has no value function; BaselineREINFORCE's is its baseline)
+    if al in (10, 11, 13, 15, 16):
+        out.append(c.get_policy_weights(i))
+    if al in (15, 16):
+        out.append(c.get_behaviour_weights(i))
+    return out
+
+
+def same_arrays(xs, ys):
+    return len(xs) == len(ys) and all(np.array_equal(np.asarray(x).view(np.uint8), np.asarray(y).view(np.uint8)) for x, y in zip(xs, ys))
+
+
+def randomise(c, rng, i):
+    al, F, A = c.cfg.algo, c.F, c.A
+    if al in (18, 19):
+        M = rng.normal(0.0, 1.0, size=(F, F))
+        if al == 18:
+            c.set_lstd_state(rng.normal(0.0, 0.5, size=F), 1e-3 * (np.eye(F) + (M + M.T) / (4.0 * F)), None, i)
+        else:
+            c.set_lstd_state(rng.normal(0.0, 0.5, size=F), np.eye(F) + 0.1 * M / np.sqrt(F), rng.normal(0.0, 1.0, size=F), i)
+        return
+    if al != ra.REINFORCE:
+        c.set_weights(rng.normal(0.0, 0.1 if c.cfg.domain == 3 else 0.3, size=(F, c.n_out)).astype(np.float32), i)
+    if al in (10, 11, 13, 15, 16):
+        c.set_policy_weights(rng.normal(0.0, 0.3, size=(F, A)).astype(np.float32), i)
+
+
+def f64_leg(c, kw, rng, worst):
+    """handle rounds on learners 0..M-1 against the f64 rules; -> findings"""
+    bad = []
+    N, al, dom, order = c.N, kw["algo"], kw["domain"], kw["order"]
+    gamma, lr, alpha, tau = kw["gamma"], kw["lr"], kw["alpha"], kw["tau"]
+    for i in sorted(set([0, N - 1] + list(rng.integers(0, N, size=min(N, 24))))):
+        randomise(c, rng, i)
+    for rnd in range(int(rng.integers(2, 4))):
+        M = int(rng.choice([1, int(rng.integers(1, N)) if N > 1 else 1, N]))
+        if dom != 3:
+            c.states = rand_states(dom, N, rng)
+        a = rng.integers(0, c.A, size=N).astype(np.int32)
+        frm, nxt, rew, term = c.domain_step(a)
+        if dom != 3:
+            term = (term | (rng.random(N) < 0.25)).astype(np.uint8)
+        watch = sorted(set(list(range(M, min(N, M + 70))) + [N - 1] + list(rng.integers(M, N, size=8) if M < N else [])) - set(range(M)))
+        before = {j: learner_state(c, j) for j in watch}
+        rep = sorted(set([0, M - 1] + list(rng.integers(0, M, size=6))))
+        start = {i: learner_state(c, i) for i in rep}
+        t = c.step_count
+        td = c.handle(frm[:, :M], a[:M], rew[:M], nxt[:, :M], term[:M])
+        for j in watch:
+            if not same_arrays(learner_state(c, j), before[j]):
+                bad.append(f"round {rnd}: learner {j} >= M = {M} changed")
+                break
+        for i in rep:
+            r, tm, ai = float(rew[i]), bool(term[i]), int(a[i])
+            got = learner_state(c, i)
+            if dom == 3:
+                phi_s, phi_n = hv.fourier(frm[:, i:i + 1], order, HIV_LO, HIV_HI)[:, 0], hv.fourier(nxt[:, i:i + 1], order, HIV_LO, HIV_HI)[:, 0]
+            else:
+                phi_s, phi_n = orc.fourier_project(dom, order, frm[:, i]), orc.fourier_project(dom, order, nxt[:, i])
+            x = orc.draw(kw["seed"], kw["env_offset"] + i, t, orc.BLK_INNER)
+            sphi = float(np.abs(phi_s).sum())
+            if al in (18, 19):
+                theta, mat = start[i][0], start[i][1]
+                if al == 18:
+                    d, theta, mat = recursive_lstd(theta, mat, phi_s, phi_n, r, tm, gamma)
+                    want = [theta, mat]
+                else:
+                    rounds = []
+                    d, theta, mat, mu = ilstd(theta, mat, start[i][2], phi_s, phi_n, r, tm, gamma, alpha, kw["n_steps"], rounds=rounds)
+                    if any(near_tie_band(m) for m in rounds):
+                        continue                                   # (an |mu_j| within 1e-9 of the 1e-7 tie band: which j is chosen is a rounding)
+                    want = [theta, mat, mu]
+                tol = 16.0 * c.F * (1 + (kw["n_steps"] if al == 19 else 0)) * EPS64
+                ok_td = abs(float(td[i]) - d) <= 2.0 ** -22 * (1.0 + abs(d))
+                errs = [float(np.max(np.abs(g - w))) / (1.0 + float(np.max(np.abs(w)))) for g, w in zip(got, want)]
+                fracs = [e / tol for e in errs]
+            elif dom == 3:
+                W = start[i][0].astype(np.float64)
+                d, e = hiv_rule(al, W, phi_s, phi_n, ai, r, gamma, alpha, kw["epsilon"], x)
+                ok_td = abs(float(td[i]) - d) <= 2e-5 * (1 + abs(d))
+                want_col = W[:, ai] + lr * e * phi_s
+                err = float(np.max(np.abs(got[0][:, ai] - want_col)))
+                errs = [err / (1.0 + float(np.max(np.abs(want_col))))]
+                fracs = [err / (3e-6 * (1 + abs(d)) * max(1.0, sphi))]
+            else:
+                W, Th = start[i][0].astype(np.float64), start[i][1].astype(np.float64)
+                if al in (10, 11):
+                    if not tm and near_boundary(orc.policy_probs(orc.SOFTMAX, Th.T @ phi_n, tau=tau), x):
+                        continue
+                    d, W2, T2 = ac_rule(orc, al == 11, W, Th, phi_s, phi_n, ai, r, tm, gamma, lr, alpha, tau, x)
+                    pairs = ((got[0], W2, W), (got[1], T2, Th))
+                else:
+                    d, w2, T2 = tdac_rule(W, Th, phi_s, phi_n, ai, r, tm, gamma, lr, alpha, tau)
+                    pairs = ((got[0][:, 0], w2, W[:, 0]), (got[1], T2, Th))
+                ok_td = abs(float(td[i]) - d) <= 2e-5 * (1 + abs(d))
+                errs, fracs = [], []
+                for g, w, old in pairs:
+                    bound = 3e-6 * (1 + float(np.max(np.abs(w - old)))) * sphi + 3e-6 * float(np.max(np.abs(old)))
+                    err = float(np.max(np.abs(g - w)))
+                    errs.append(err / (1.0 + float(np.max(np.abs(w)))))
+                    fracs.append(err / max(bound, 1e-300))
+            ok_w = all(f <= 1.0 for f in fracs)
+            wr = worst.setdefault(NAMES[al], {"td": 0.0, "w": 0.0, "bound_used": 0.0, "replayed": 0})
+            wr["td"] = max(wr["td"], abs(float(td[i]) - d) / (1 + abs(d)))
+            wr["w"] = max([wr["w"]] + errs)
+            wr["bound_used"] = max([wr["bound_used"]] + fracs)
+            wr["replayed"] += 1
+            if not (ok_td and ok_w):
+                bad.append(f"round {rnd} M {M}: learner {i} td {float(td[i]):.6g} vs f64 {d:.6g}, state errors {['%.1e' % e for e in errs]}")
+    return bad
+
+
+def f32_returns(rewards, gamma):
+    g, gm, out = np.float32(0.0), np.float32(gamma), []
+    for r in rewards:
+        g = np.float32(np.float32(r) + np.float32(gm * g))
+        out.append(g)
+    return out
+
+
+def batch_leg(c, kw, rng, worst):
+    """REINFORCE's Handler<&Batch> with ragged lengths; -> findings"""
+    bad = []
+    N, T, dom, order = c.N, int(rng.integers(1, 13)), kw["domain"], kw["order"]
+    rep = sorted(set([0, N - 1] + list(rng.integers(0, N, size=6))))
+    base = kw["algo"] == ra.BASELINE_REINFORCE
+    for i in rep:
+        randomise(c, rng, i)
+    Ts = {i: c.get_policy_weights(i) for i in rep}
+    Bs = {i: c.get_weights(i) for i in rep} if base else None
+    thb0, g0 = {i: c.get_behaviour_weights(i) for i in rep}, c.return_carry
+    S = np.stack([rand_states(dom, N, rng) for _ in range(T)])
+    A = rng.integers(0, c.A, size=(T, N)).astype(np.int32)
+    R = rng.normal(0.0, 1.0, size=(T, N)).astype(np.float32)
+    L = rng.integers(0, T + 1, size=N).astype(np.uint32)
+    L[rep[0]], L[rep[-1]] = 0, T                                    # (an empty batch and a full one among the replayed learners)
+    ret = c.handle_batch(S, A, R, L, returns=True)
+    for i in rep:
+        n = int(L[i])
+        if not np.array_equal(ret[:n, i].view(np.uint32), np.array(f32_returns(R[:n, i], kw["gamma"]), dtype=np.float32).view(np.uint32)) or \
+                not np.isnan(ret[n:, i]).all():
+            bad.append(f"returns of learner {i}")
+        got = c.get_policy_weights(i)
+        if n == 0:
+            if not np.array_equal(got, Ts[i]):
+                bad.append(f"learner {i} with an empty batch moved")
+            continue
+        phis = [orc.fourier_project(dom, order, S[t, :, i]) for t in range(n)]
+        want, _ = reinforce_batch(Ts[i], phis, A[:n, i], R[:n, i].astype(np.float64), kw["gamma"], kw["alpha"], kw["tau"], None if Bs is None else Bs[i])
+        sphi = sum(np.abs(p).sum() for p in phis)
+        bound = 3e-6 * (1 + float(np.max(np.abs(want - Ts[i])))) * sphi + 3e-6 * float(np.max(np.abs(Ts[i])))
+        err = float(np.max(np.abs(got - want)))
+        wr = worst.setdefault(NAMES[kw["algo"]], {"td": 0.0, "w": 0.0, "bound_used": 0.0, "replayed": 0})
+        wr["w"] = max(wr["w"], err / (1.0 + float(np.max(np.abs(want)))))
+        wr["bound_used"] = max(wr["bound_used"], err / max(bound, 1e-300))
+        wr["replayed"] += 1
+        if err > bound:
+            bad.append(f"theta of learner {i}: {err:.2e} > {bound:.2e}")
+        if not np.array_equal(c.get_behaviour_weights(i), thb0[i]):
+            bad.append(f"theta_b of learner {i} moved")
+    if not np.array_equal(c.return_carry, g0):
+        bad.append("the running returns moved")
+    return bad
+
+
+def snapshot(c, learners):
+    out = [c.states, c.actions, c.episode_steps]
+    for i in learners:
+        out += learner_state(c, i)
+    if c.cfg.algo in (15, 16):
+        out.append(c.return_carry)
+    if c.cfg.domain == 3:
+        out.append(c.get_hidden_states())
+    return out
+
+
+def trait_loop(c, K, cap):
+    ep = c.episode_steps.astype(np.int64)
+    for _ in range(K):
+        frm, nxt, rew, term = c.domain_step(c.actions)
+        c.handle(frm, c.actions, rew, nxt, term)
+        ep += 1
+        mask = (term.astype(bool) | (ep >= cap)).astype(np.uint8)
+        c.domain_reset(mask)
+        ep[mask == 1] = 0
+        c.policy_sample()
+    c.episode_steps = ep.astype(np.uint32)
+
+
+def self_leg(kw, rng, legs):
+    """-> findings: random splits with queries between, the trait loop, shards, a checkpoint -- each against one uninterrupted run"""
+    bad = []
+    N, K = kw["n_envs"], int(rng.choice([10, 25, 40]))
+    look = sorted(set([0, N // 2, N - 1]))
+    with ra.Context(**kw) as c:
+        c.reset()
+        c.train(K, want_stats=False)
+        ref = snapshot(c, look)
+        ck = c.checksum()
+    cuts = sorted(set(int(x) for x in rng.integers(1, K, size=int(rng.integers(1, 4)))))
+    calls = [b - a for a, b in zip([0] + cuts, cuts + [K])]
+    with ra.Context(**kw) as c, tempfile.TemporaryDirectory() as td:
+        c.reset()
+        made, counter = [], {}
+        for j, k in enumerate(calls):
+            c.train(k, want_stats=bool(rng.integers(0, 2)))
+            if j + 1 < len(calls):
+                b_, m_ = fp.query_leg(c, rng, td, counter)
+                bad += b_; made += m_
+        if not same_arrays(snapshot(c, look), ref) or c.checksum() != ck:
+            bad.append(f"train {calls} with queries {made} != train({K})")
+        legs["split+query"] = legs.get("split+query", 0) + 1
+    if kw["algo"] in TRAIT_LOOP and rng.random() < 0.5:
+        with ra.Context(**kw) as c:
+            c.reset()
+            trait_loop(c, K, kw["max_episode_steps"] or (1 << 62))
+            if not same_arrays(snapshot(c, look), ref):
+                bad.append("the host trait loop != train")
+        legs["trait"] = legs.get("trait", 0) + 1
+    if N >= 3 and rng.random() < 0.5:
+        n1 = int(rng.integers(1, N))
+        parts = []
+        for off, cnt in ((0, n1), (n1, N - n1)):
+            with ra.Context(**dict(kw, n_envs=cnt, env_offset=kw["env_offset"] + off)) as cs:
+                cs.reset()
+                cs.train(K, want_stats=False)
+                parts.append((cs.states, cs.actions, learner_state(cs, 0), learner_state(cs, cnt - 1)))
+        with ra.Context(**kw) as cf:
+            cf.reset()
+            cf.train(K, want_stats=False)
+            okp = np.array_equal(np.concatenate([parts[0][0], parts[1][0]], axis=1), cf.states) and \
+                np.array_equal(np.concatenate([parts[0][1], parts[1][1]]), cf.actions) and \
+                same_arrays(parts[0][2], learner_state(cf, 0)) and same_arrays(parts[0][3], learner_state(cf, n1 - 1)) and \
+                same_arrays(parts[1][2], learner_state(cf, n1)) and same_arrays(parts[1][3], learner_state(cf, N - 1))
+        if not okp:
+            bad.append(f"shards {n1} + {N - n1} != the unsharded run")
+        legs["shard"] = legs.get("shard", 0) + 1
+    if rng.random() < 0.5:
+        k1 = int(rng.integers(1, K))
+        with ra.Context(**kw) as c, ra.Context(**kw) as c2, tempfile.TemporaryDirectory() as td:
+            c.reset()
+            c.train(k1, want_stats=False)
+            path = os.path.join(td, "w.rsrlw")
+            c.save_weights(path)
+            c2.reset()
+            c2.train(2, want_stats=False)                           # (something to overwrite)
+            c2.load_weights(path)
+            c2.states, c2.actions, c2.episode_steps = c.states, c.actions, c.episode_steps
+            if kw["domain"] == 3:
+                c2.set_hidden_states(c.get_hidden_states())            # (after the observations: set_states re-derives the hidden state from them)
+            if kw["algo"] in (15, 16):
+                c2.return_carry = c.return_carry
+                for i in range(N):
+                    c2.set_behaviour_weights(c.get_behaviour_weights(i), i)
+            c2.train(K - k1, want_stats=False)
+            if not same_arrays(snapshot(c2, look), ref):
+                bad.append(f"checkpoint at {k1} resumed != train({K})")
+        legs["ckpt"] = legs.get("ckpt", 0) + 1
+    return bad
+
+
+def run_case(rng, idx, worst, legs):
+    kw = sample(rng, idx)
+    al = kw["algo"]
+    tag = f"{idx:4d} {NAMES[al]:18s} dom {kw['domain']} ord {kw['order']} N {kw['n_envs']:4d} off {kw['env_offset']:7d} cap {kw['max_episode_steps']:3d} " \
+          f"spl {kw['steps_per_launch']}"
+    try:
+        c = ra.Context(**kw)
+    except ra.RsrlHipError as e:
+        return "refused", tag + f"  REFUSED: {str(e)[:90]}", kw
+    bad = []
+    with c:
+        c.reset()
+        if al in (15, 16):
+            bad += [f"batch: {b}" for b in batch_leg(c, kw, rng, worst)]
+            legs["batch"] = legs.get("batch", 0) + 1
+        else:
+            bad += [f"f64: {b}" for b in f64_leg(c, kw, rng, worst)]
+            legs["f64"] = legs.get("f64", 0) + 1
+    bad += [f"self: {b}" for b in self_leg(kw, rng, legs)]
+    if bad:
+        return "MISMATCH", tag + f"  MISMATCH {bad[:4]}", kw
+    return "ok", tag + "  ok", kw
+
+
+def main():
+    n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
+    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+    rng = np.random.default_rng(seed)
+    counts, per_agent, failures, worst, legs = {}, {}, [], {}, {}
+    for idx in range(n_cases):
+        try:
+            status, line, kw = run_case(rng, idx, worst, legs)
+        except Exception as e:      # noqa: BLE001
+            status, line, kw = "ERROR", f"{idx:4d} ERROR {type(e).__name__}: {str(e)[:200]}", None
+        counts[status] = counts.get(status, 0) + 1
+        if kw is not None:
+            a = per_agent.setdefault(NAMES[kw["algo"]], {})
+            a[status] = a.get(status, 0) + 1
+        print(line, flush=True)
+        if status in ("MISMATCH", "ERROR"):
+            failures.append({"case": idx, "line": line, "config": kw})
+    print("SUMMARY " + json.dumps({"cases": n_cases, "seed": seed, "counts": counts, "per_agent": per_agent, "legs": legs,
+                                   "worst_vs_f64": worst, "failures": failures}, default=str), flush=True)
+    sys.exit(1 if failures else 0)
+
+
+if __name__ == "__main__":
+    main()

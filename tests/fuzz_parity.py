@@ -107,6 +107,105 @@ def sample(rng):
     return family, dev, okw, method, mkw
 
 
+REFUSALS = (-1, -5)          # EINVAL, ESTATE: a query the family does not have
+
+
+def query_states(c, rng, M):
+    """M states: a random mix of the ctx's own (what the trait path's hand-over cache holds) and random in-bounds ones"""
+    lo, hi = c.state_bounds()
+    lo, hi = np.clip(lo, -10, 10), np.clip(hi, -10, 10)
+    s = (lo[:, None] + rng.random((c.D, M)) * (hi - lo)[:, None]).astype(np.float32)
+    own = rng.random(M) < rng.choice([0.0, 0.5, 1.0])
+    s[:, own] = c.states[:, :M][:, own]
+    return np.ascontiguousarray(s)
+
+
+def query_leg(c, rng, tmpdir, counter):
+    """1-4 random calls that do not change learning state -- the value and policy sides, projections, every getter, the identity round trips
+    (save_weights, q_carry = q_carry) and the three evaluation rollouts -- on host and device arrays.  A call the ctx refuses must refuse with
+    EINVAL / ESTATE.  -> list of findings; counter['rollout_policy'] counts the rollout_policy calls (their draws are addressed by the call number)."""
+    import ctypes as C
+    bad = []
+    N, A = c.N, c.A
+    M = int(rng.integers(1, N + 1))
+    S = query_states(c, rng, M)
+    i = int(rng.integers(0, N))
+    lim = int(rng.choice([5, 30]))
+
+    def device_side():
+        from rsrl_amd._devmem import DeviceBuffer
+        L, h = c._L, c._h
+        dS, dA, dQ, dP = DeviceBuffer(c.D * M, "float32"), DeviceBuffer(M, "int32"), DeviceBuffer(c.n_out * M, "float32"), DeviceBuffer(A * M, "float32")
+        try:
+            dS.from_host(S)
+            p = lambda b: C.c_void_p(b.ptr)      # noqa: E731
+            rcs = [L.rsrl_hip_policy_sample(h, p(dS), M, p(dA)), L.rsrl_hip_q_evaluate(h, p(dS), M, p(dQ)), L.rsrl_hip_policy_probs(h, p(dS), M, p(dP))]
+            c.sync()
+            for rc in rcs:
+                if rc not in (0,) + REFUSALS:
+                    bad.append(f"device-array query rc {rc}")
+            if rcs[1] == 0 and not np.array_equal(dQ.to_host((c.n_out, M)), c.q_evaluate(S), equal_nan=True):
+                bad.append("q_evaluate: device arrays != host arrays")
+        finally:
+            for b in (dS, dA, dQ, dP):
+                b.free()
+
+    def carry_round_trip():
+        q = c.q_carry
+        if q is not None:
+            c.q_carry = q
+
+    def sample_own():
+        pending = c.actions
+        if not np.array_equal(c.policy_sample(), pending):
+            bad.append("policy_sample() is not the pending action of the batch-step")
+
+    def rollout_policy():
+        c.rollout_policy(int(rng.integers(0, 4)), lim, M=M, epsilon=0.25, tau=0.7)
+        counter["rollout_policy"] = counter.get("rollout_policy", 0) + 1      # (a call that ran: the next one draws from the next stream)
+
+    calls = {
+        "q_evaluate": lambda: c.q_evaluate(S), "q_find_max": lambda: c.q_find_max(S), "q_find_min": lambda: c.q_find_min(S),
+        "q_expected_value": lambda: c.q_expected_value(S, np.full((A, M), 1.0 / A, dtype=np.float32)),
+        "policy_sample": lambda: c.policy_sample(S), "policy_sample()": sample_own, "policy_mode": lambda: c.policy_mode(S),
+        "policy_probs": lambda: c.policy_probs(S), "policy_prob": lambda: c.policy_prob(S, rng.integers(0, A, M).astype(np.int32)),
+        "project": lambda: c.project(S), "tile_indices": lambda: c.tile_indices(S),
+        "get_weights": lambda: c.get_weights(i), "get_traces": lambda: c.get_traces(i), "get_td_weights": lambda: c.get_td_weights(i),
+        "get_policy_weights": lambda: c.get_policy_weights(i), "get_behaviour_weights": lambda: c.get_behaviour_weights(i),
+        "return_carry": lambda: c.return_carry, "get_lstd_state": lambda: c.get_lstd_state(i), "get_hidden_states": lambda: c.get_hidden_states(),
+        "epsilons": lambda: c.epsilons, "q_carry": lambda: c.q_carry, "checksum": lambda: c.checksum(),
+        "states": lambda: c.states, "actions": lambda: c.actions, "episode_steps": lambda: c.episode_steps,
+        "save_weights": lambda: c.save_weights(os.path.join(tmpdir, "q.rsrlw")), "q_carry=q_carry": carry_round_trip,
+        "rollout_greedy": lambda: c.rollout_greedy(lim), "rollout_trajectory": lambda: c.rollout_trajectory(lim, M=M), "rollout_policy": rollout_policy,
+        "device arrays": device_side,
+    }
+    # the calls that reach the trait path's hand-over (policy_sample of caller states, of the ctx's own, on device arrays) and the carry drawn more often
+    names = list(calls) + ["policy_sample", "policy_sample()", "device arrays", "q_carry=q_carry"] * 2
+    made = []
+    for j in rng.permutation(len(names))[: int(rng.integers(1, 5))]:
+        name = names[int(j)]
+        made.append(name)
+        try:
+            calls[name]()
+        except ra.RsrlHipError as e:
+            if e.code not in REFUSALS:
+                bad.append(f"{name}: {str(e)[:80]}")
+    return bad, made
+
+
+def _stat_check(ost, dst, stat_bad):
+    """the call's statistics: counters exact, the f64 sums of fp32 terms to their summation order"""
+    if ost and dst and stat_bad is None:
+        for key in ("env_steps", "episodes", "episodes_truncated", "sum_episode_steps"):
+            if int(ost[key]) != int(dst[key]):
+                stat_bad = f"stats.{key}: device {dst[key]} oracle {ost[key]}"
+        for key in ("sum_abs_td_error", "sum_reward"):
+            a_, b_ = float(dst[key]), float(ost[key])
+            if np.isfinite(a_) and np.isfinite(b_) and abs(a_ - b_) > 2e-4 * (1 + abs(b_)):
+                stat_bad = stat_bad or f"stats.{key}: device {a_} oracle {b_}"
+    return stat_bad
+
+
 def run_case(rng, idx):
     family, dev, okw, method, mkw = sample(rng)
     while os.environ.get("FUZZ_FAMILY") and family != os.environ["FUZZ_FAMILY"]:      # one family only (e.g. after a change to its kernels)
@@ -135,21 +234,22 @@ def run_case(rng, idx):
             (run.reset_wave if method == "train_wave" else run.reset)()
             c.reset()
             stat_bad = None
-            for k in calls:
-                ost = getattr(run, method)(k, **mkw) if k else None
-                dst = c.train(k, want_stats=bool(rng.integers(0, 2)))
-                # the call's statistics: counters exact, the f64 sums of fp32 terms to their summation order
-                if ost and dst and stat_bad is None:
-                    for key in ("env_steps", "episodes", "episodes_truncated", "sum_episode_steps"):
-                        if int(ost[key]) != int(dst[key]):
-                            stat_bad = f"stats.{key}: device {dst[key]} oracle {ost[key]}"
-                    for key in ("sum_abs_td_error", "sum_reward"):
-                        a_, b_ = float(dst[key]), float(ost[key])
-                        if np.isfinite(a_) and np.isfinite(b_) and abs(a_ - b_) > 2e-4 * (1 + abs(b_)):
-                            stat_bad = stat_bad or f"stats.{key}: device {a_} oracle {b_}"
+            qbad, qmade, qcount = [], [], {}
+            qrng = np.random.default_rng(int(rng.integers(0, 1 << 62)))
+            import tempfile
+            with tempfile.TemporaryDirectory() as qdir:
+                for j, k in enumerate(calls):
+                    ost = getattr(run, method)(k, **mkw) if k else None
+                    dst = c.train(k, want_stats=bool(rng.integers(0, 2)))
+                    if j + 1 < len(calls) or qrng.random() < 0.5:          # ---- queries between the train() calls (and before the comparison): change nothing
+                        b_, m_ = query_leg(c, qrng, qdir, qcount)
+                        qbad += b_; qmade += m_
+                    stat_bad = _stat_check(ost, dst, stat_bad)
         except ValueError as e:                                   # the oracle has no loop for it
             return "no_oracle", tag + f"  NO ORACLE LOOP: {str(e)[:80]}", dev
-        bad = [stat_bad] if stat_bad else []
+        bad = ([stat_bad] if stat_bad else []) + qbad
+        if qbad or not (np.array_equal(c.states.T, run.state, equal_nan=True) and np.array_equal(c.actions, run.action)):
+            tag += f"  queries {qmade}"                             # (which queries a mismatching case made)
         if not np.array_equal(c.states.T, run.state, equal_nan=True):
             bad.append("states")
         if not np.array_equal(c.actions, run.action):
@@ -216,7 +316,7 @@ def run_case(rng, idx):
             pol = int(rng.integers(0, 4))
             for call in range(2):
                 rd = c.rollout_policy(pol, lim, epsilon=0.25, tau=0.7)
-                n_o, _, a_o = run.rollout_policy(pol, lim, epsilon=0.25, tau=0.7, call=call)
+                n_o, _, a_o = run.rollout_policy(pol, lim, epsilon=0.25, tau=0.7, call=qcount.get("rollout_policy", 0) + call)      # (after the query leg's)
                 if not (np.array_equal(rd["n_states"], n_o) and np.array_equal(rd["actions"], a_o)):
                     bad.append(f"rollout_policy {pol} call {call} ({int((rd['n_states'] != n_o).sum())} of {n} learners)")
                     break

@@ -1,6 +1,7 @@
 """Which configurations rsrl_hip_create admits, pinned without a GPU.  Every admission rule runs before the device query, so on a machine
 without a device an admitted configuration returns EHIP ("no device") and a refused one EINVAL.  The sweep (scripts/admission_matrix.py, 133 120
-configurations) must admit exactly the configurations of tests/golden/create_admission.json, which that script wrote from the library."""
+configurations) must admit exactly the configurations of tests/golden/create_admission.json, which that script wrote from the library; its second
+grid (the algos numbered 13-19 on the same other axes, 71 680 configurations) those of tests/golden/create_admission_agents.json."""
 import importlib.util
 import json
 import os
@@ -46,3 +47,53 @@ def test_create_admits_exactly_the_fixture(matrix):
     for key, (rc, msg) in res.items():
         if rc != matrix.EHIP:
             assert rc == matrix.EINVAL and msg, (key, rc, msg)
+
+
+def test_the_two_grids_cover_every_algo_on_the_same_axes(matrix):
+    algos = set(dict(matrix.GRID)["algo"]) | set(dict(matrix.GRID_AGENTS)["algo"])
+    assert algos >= set(range(20)), sorted(set(range(20)) - algos)
+    assert [n for n, _ in matrix.GRID] == [n for n, _ in matrix.GRID_AGENTS]
+    assert all(v == w for (n, v), (_, w) in zip(matrix.GRID, matrix.GRID_AGENTS) if n != "algo"), "the second grid's other axes are the first's"
+    assert json.load(open(matrix.AGENTS_FIXTURE))["grid"] == [[n, v] for n, v in matrix.GRID_AGENTS], "GRID_AGENTS and its fixture drifted apart"
+
+
+def test_create_admits_exactly_the_agents_fixture(matrix):
+    """the TD ActorCritic, REINFORCE / BaselineREINFORCE and RecursiveLSTD / iLSTD on the configurations their rules admit; 14 and 17 (no algo) nowhere"""
+    if _gfx950_visible():
+        pytest.skip("GPU present: an admitted configuration would create a real ctx")
+    from rsrl_amd import _build
+    _build.build()
+    res = matrix.sweep(matrix.GRID_AGENTS)
+    want = json.load(open(matrix.AGENTS_FIXTURE))["admitted"]
+    assert matrix.admitted(res) == want
+    algos = dict(matrix.GRID_AGENTS)["algo"]
+    ia = [n for n, _ in matrix.GRID_AGENTS].index("algo")
+    assert {algos[int(k[ia], 16)] for k in want} == {13, 15, 16, 18, 19}
+    for key, (rc, msg) in res.items():
+        if rc != matrix.EHIP:
+            assert rc == matrix.EINVAL and msg, (key, rc, msg)
+        if algos[int(key[ia], 16)] in (14, 17):
+            assert rc == matrix.EINVAL and "unknown algo" in msg, (key, rc, msg)
+
+
+def test_the_campaign_samplers_draw_only_admitted_configurations(matrix):
+    """2 000 draws of each random campaign's sampler (tests/fuzz_parity.py, tests/fuzz_agents.py): rsrl_hip_create admits every one (EHIP -- no device
+    -- and not EINVAL), so that a sampler that drifts from the admission rules shows up here and not as refused cases on the GPU"""
+    if _gfx950_visible():
+        pytest.skip("GPU present: an admitted configuration would create a real ctx")
+    import sys
+
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import fuzz_agents
+    import fuzz_parity
+    import rsrl_amd as ra
+    from rsrl_amd import _build
+    _build.build()
+    for name, draw in (("fuzz_parity", lambda rng: fuzz_parity.sample(rng)[1]), ("fuzz_agents", fuzz_agents.sample)):
+        rng = np.random.default_rng(20261016)
+        for k in range(2000):
+            kw = draw(rng)
+            with pytest.raises(ra.RsrlHipError) as e:
+                ra.Context(**kw).close()
+            assert e.value.code == matrix.EHIP, (name, k, kw, str(e.value))

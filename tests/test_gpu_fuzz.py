@@ -74,3 +74,20 @@ def test_random_rank_groups_on_one_device():
     assert p.returncode == 0 and line, (p.stdout[-3000:], p.stderr[-2000:])
     d = json.loads(line[0][8:])
     assert not d["failures"] and d["counts"].get("ok", 0) >= 36, d["counts"]
+
+
+def test_random_configurations_of_the_newer_agents():
+    # tests/fuzz_agents.py: ActorCritic / QActorCritic, the TD ActorCritic, REINFORCE / BaselineREINFORCE, RecursiveLSTD / iLSTD on every register-family
+    # order and the one-step agents on HIVTreatment, at random learner counts, offsets, caps and launch depths: handle on partial batches against the f64
+    # rules (learners M..N-1 untouched), REINFORCE's ragged batches, and train against its splits (with queries between them), the trait loop, shards
+    # and a checkpoint, bit for bit.
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "fuzz_agents.py"), "200", "20261016"], capture_output=True, text=True, timeout=600)
+    line = [l for l in p.stdout.splitlines() if l.startswith("SUMMARY ")]
+    assert line, (p.stdout[-2000:], p.stderr[-2000:])
+    d = json.loads(line[0][8:])
+    assert p.returncode == 0 and not d["failures"], d["failures"][:3]
+    assert d["counts"].get("refused", 0) == 0, d["counts"]
+    per = d["per_agent"]
+    for name in ("ActorCritic", "QActorCritic", "TDActorCritic", "REINFORCE", "BaselineREINFORCE", "RecursiveLSTD", "iLSTD"):
+        assert per.get(name, {}).get("ok", 0) >= 20, (name, per)
+    assert sum(v.get("ok", 0) for k, v in per.items() if k.startswith("HIV/")) >= 20, per

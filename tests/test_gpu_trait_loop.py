@@ -199,3 +199,38 @@ def test_deferred_calls_are_not_lost_and_errors_still_surface():
     assert np.array_equal(frm.to_host((D, n)), s1)
     for b in (frm, to, rew, act, term):
         b.free()
+
+
+@pytest.mark.parametrize("name", list(CASES))
+@pytest.mark.parametrize("query", ["sample_states", "sample_own", "q_carry"])
+def test_a_query_between_train_calls_changes_nothing(name, query):
+    """train(k); <query>; train(k) == train(2k) bit for bit on the trait-fast ctx (steps_per_launch = 1): the hand-over cache of policy_sample is not the
+    Q(s,.) rsrl_hip_train carries from launch to launch.  (The queries: policy_sample of random states for learners 0..M-1, M < N -- a key miss for
+    every one of them --, policy_sample() of the ctx's own envs, and q_carry written back as it was read.)"""
+    import rsrl_amd as ra
+    dkw, _ = CASES[name]
+    k = K // 2
+    kw = dict(n_envs=N, seed=SEED, max_episode_steps=0, steps_per_launch=1, **dkw)
+    with ra.Context(**kw) as a, ra.Context(**kw) as b:
+        a.reset(); b.reset()
+        a.train(2 * k, want_stats=False)
+        b.train(k, want_stats=False)
+        if query == "sample_states":
+            rng = np.random.default_rng(7)
+            M = 200
+            lo, hi = b.state_bounds()
+            s = (lo[:, None] + rng.random((b.D, M)) * (hi - lo)[:, None]).astype(np.float32)
+            b.policy_sample(s)
+        elif query == "sample_own":
+            assert np.array_equal(b.policy_sample(), b.actions)
+        else:
+            q = b.q_carry
+            assert q is not None, "a register-family ctx carries Q(s,.) after train"
+            b.q_carry = q
+        b.train(k, want_stats=False)
+        assert a.step_count == b.step_count
+        assert np.array_equal(a.states, b.states), f"{name}/{query}: states"
+        assert np.array_equal(a.actions, b.actions), f"{name}/{query}: actions"
+        for i in range(N):
+            assert np.array_equal(a.get_weights(i), b.get_weights(i)), f"{name}/{query}: weights of learner {i}"
+        assert np.array_equal(a.q_carry, b.q_carry), f"{name}/{query}: the carried Q(s,.)"
