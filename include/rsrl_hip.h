@@ -438,13 +438,21 @@ int rsrl_hip_get_lstd_state(rsrl_hip_ctx* ctx, int64_t env_index, double* theta 
 int rsrl_hip_set_lstd_state(rsrl_hip_ctx* ctx, int64_t env_index, const double* theta /*[F]*/, const double* mat /*[F][F]*/,
                             const double* mu /*[F], iLSTD only, may be NULL*/);
 /* Checkpoint of the approximator(s) (the reference's only persistence story is the optional serde
- * derive on the agents, rsrl/Cargo.toml:26).  File format version 2 (3 for files that carry QSigma's backups, 5 for sparse traces, 7 for ActorCritic, 8 for the TD ActorCritic,
- * 9 for REINFORCE, 10 for RecursiveLSTD / iLSTD),
- * little-endian,
- * serialised field by field (no padding):
+ * derive on the agents, rsrl/Cargo.toml:26).  The file version follows from the header's aux_kind:
+ *   aux_kind                                        written as   payload after the header
+ *   0 none                                           2           weights
+ *   1 eligibility traces                             2           weights, auxiliary matrix
+ *   2 GreedyGQ's fa_td weights                       2           weights, auxiliary matrix
+ *   3 QSigma's n-step backups                        3           weights, backups       (version 2 / aux_kind 0 of a QSigma ctx: still read)
+ *   4 sparse traces over a shared table              6           weights, sparse lists  (version 5, and version 2 / aux_kind 0: still read)
+ *   5 ActorCritic's theta                            7           weights, auxiliary matrix
+ *   6 the TD ActorCritic's theta                     8           weights, auxiliary matrix
+ *   7 REINFORCE's theta and open episode             9           weights (BaselineREINFORCE only), auxiliary matrix, theta_b, g
+ *   8 the LSTD agents' f64 state                     10          f64 theta, matrices, mu
+ * and a ctx with config.epsilon_decay (aux_kind 0 or 1) writes version 4 instead, with f32 eps[N] behind the payload.  No other pairing of
+ * version and aux_kind is a file of this library; load refuses it.  Little-endian, serialised field by field (no padding):
  *   offset  0  char magic[8] = "RSRLHIPW"
- *           8  u32  version = 2 (3 iff aux_kind = 3, 5 iff aux_kind = 4, 7 iff aux_kind = 5, 8 iff aux_kind = 6, 9 iff aux_kind = 7, 10 iff aux_kind = 8,
- *                   4 with the epsilon schedule)
+ *           8  u32  version (the table above)
  *          12  i32  domain, basis, order, n_tilings, tiles_per_dim, weight_mode, F, A (weight columns),
  *                   algo, weight_dtype, aux_kind (0 none, 1 eligibility traces, 2 GreedyGQ's fa_td weights,
  *                   3 QSigma's n-step backups, 4 sparse traces over a shared table, 5 ActorCritic's theta,
@@ -466,12 +474,12 @@ int rsrl_hip_set_lstd_state(rsrl_hip_ctx* ctx, int64_t env_index, const double* 
  *              iLSTD, n_learners x f64[F] of mu;
  *              if aux_kind is 3 (file version 3): u32 head[N], u32 len[N], f32 entries[D + 5][n_steps][N] -- every learner's
  *              Backup ring {s, a, q, residual, pi, mu} (q_sigma.rs:30-63), so that a QSigma run with n_steps > 1 resumes
- *              bit-identically too.  Files of version 2 (no aux_kind 3) are still read.
+ *              bit-identically too.  A QSigma ctx still reads its configuration's version-2 file without them (aux_kind 0): the backups start empty.
  *              if aux_kind is 4 (file version 6; SARSALambda / QLambda over ONE shared tile-coded table): u64 n_envs, u64 env_offset (whose
  *              learners the lists belong to: a file of another shard is refused as a different configuration), u32 len[N], then for every
  *              learner in turn u32 key[len] (= feature index * A + action) and f32 value[len] -- its sparse trace (params/sparse.rs:13-97),
  *              the tilings' sub-lists one after the other, each in slot order, so that the run resumes bit-identically (the slot order decides
- *              which entry a full sub-list overwrites).  Version 5 (round 5: no n_envs / env_offset, one list per learner) is still read; its
+ *              which entry a full sub-list overwrites).  Version 5 (never written any more: no n_envs / env_offset, one list per learner) is still read; its
  *              entries go to the sub-lists of their keys' tilings, and a file with more than 512 / n_tilings entries of one tiling is refused.
  *              A ctx with config.epsilon_decay writes file version 4: everything above, then f32 eps[N], every learner's current
  *              epsilon (the schedule's state), so that a resumed run continues the schedule.
