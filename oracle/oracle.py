@@ -131,6 +131,7 @@ def _declare(L):
         g("orc_run_weights").argtypes = [C.c_void_p]
         g("orc_run_t").restype = C.c_uint64
         g("orc_run_t").argtypes = [C.c_void_p]
+        g("orc_run_set_t").argtypes = [C.c_void_p, C.c_uint64]
         g("orc_run_set_epsilon").argtypes = [C.c_void_p, C.c_double]
         g("orc_run_reset").argtypes = [C.c_void_p]
         g("orc_run_train").argtypes = [C.c_void_p, C.c_int64, C.POINTER(Stats)]
@@ -458,6 +459,10 @@ class Run:
     @property
     def t(self):
         return int(self._f("orc_run_t")(self._h))
+
+    @t.setter
+    def t(self, v):       # the batch-step counter a loaded checkpoint installs: the draws of reset() and of every loop are addressed from it
+        self._f("orc_run_set_t")(self._h, int(v))
 
     def set_epsilon(self, eps):
         self._f("orc_run_set_epsilon")(self._h, float(eps))

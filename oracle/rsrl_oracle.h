@@ -114,6 +114,7 @@ void orc_agent_init(orc_agent* ag, int domain, int basis_kind, int order, int n_
     uint32_t* orc_run_ep_step_##S(void* h);                                                             \
     R*    orc_run_weights_##S(void* h);                                                                 \
     uint64_t  orc_run_t_##S(void* h);                                                                   \
+    void  orc_run_set_t_##S(void* h, uint64_t t);                                                       \
     void  orc_run_set_epsilon_##S(void* h, double eps);                                                 \
     void  orc_run_reset_##S(void* h);                                                                   \
     R     orc_handle_lambda_##S(const orc_agent* ag, R* W, R* Z, const R* s, int a, R r, const R* ns, int term,   \

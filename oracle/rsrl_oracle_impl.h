@@ -868,6 +868,9 @@ uint32_t* FN(orc_run_ep_step)(void* h) { return ((FN(orc_run)*)h)->ep_step; }
 R* FN(orc_run_weights)(void* h) { return ((FN(orc_run)*)h)->W; }
 R* FN(orc_run_traces)(void* h) { return ((FN(orc_run)*)h)->Z; }
 uint64_t FN(orc_run_t)(void* h) { return ((FN(orc_run)*)h)->t; }
+/* the batch-step counter a checkpoint installs (rsrl_hip_load_weights: c->t = step_count): every later draw is addressed from it.  Nothing else of the
+ * run moves; the carried Q(s,.) is dropped like after any write from outside */
+void FN(orc_run_set_t)(void* h, uint64_t t) { FN(orc_run)* run = (FN(orc_run)*)h; run->t = t; run->q_valid = 0; }
 void FN(orc_run_set_epsilon)(void* h, double eps) {
     FN(orc_run)* run = (FN(orc_run)*)h; int64_t i;
     run->ag.epsilon = eps; run->ag.eps_thr = orc_eps_threshold(eps);

@@ -43,6 +43,9 @@ TRAIT_LOOP = (10, 11, 13, 18, 19, 0, 1, 2, 5)                        # whose tes
 AGENTS = (10, 11, 13, 15, 16, 18, 19, -1)                           # -1: HIVTreatment with a one-step agent
 
 
+TOP_OF_IDS = -1      # env_offset choice resolved to 2^32 - 1 - n_envs once n_envs is known
+
+
 def sample(rng, idx=None):
     """-> device kwargs of one configuration (case idx: the agents in turn)"""
     algo = AGENTS[idx % len(AGENTS)] if idx is not None else int(rng.choice(AGENTS))
@@ -55,8 +58,10 @@ def sample(rng, idx=None):
     F = (order + 1) ** N_DIM[domain]
     kw = dict(domain=domain, order=order, algo=algo, seed=int(rng.integers(0, 1 << 20)), gamma=float(rng.choice([0.0, 0.9, 0.99, 1.0])),
               lr=float(rng.choice([0.02, 0.2])) / F, alpha=float(rng.choice([0.02, 0.2])) / F, tau=float(rng.choice([0.05, 0.5, 1.0, 5.0])),
-              n_envs=int(rng.choice([1, 3, 5, 63, 64, 65, 130, 257, 1000])), env_offset=int(rng.choice([0, 64, 1000003])),
+              n_envs=int(rng.choice([1, 3, 5, 63, 64, 65, 130, 257, 1000])), env_offset=int(rng.choice([0, 64, 1000003, (1 << 31) - 65, TOP_OF_IDS])),
               max_episode_steps=int(rng.choice([0, 1, 25, 200])), steps_per_launch=int(rng.choice([0, 1, 5])))
+    if kw["env_offset"] == TOP_OF_IDS:       # the shard that ends at the largest learner id a ctx admits ((1 << 31) - 65: ids that straddle the sign bit)
+        kw["env_offset"] = (1 << 32) - 1 - kw["n_envs"]
     if algo in (10, 11, 13, 15, 16):
         kw["policy"] = ra.SOFTMAX
     elif algo in (18, 19):

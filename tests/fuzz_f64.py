@@ -29,7 +29,8 @@ def run_case(rng, idx):
     family, dev, okw, method, mkw = fp.sample(rng)
     shared = dev.get("weight_mode", ra.W_PER_ENV) == ra.W_SHARED
     n = min(dev["n_envs"], 48) if not shared else min(dev["n_envs"], 512)
-    dev = dict(dev, n_envs=n)
+    dev = dict(dev)
+    fp.resized(dev, okw, n)
     for k in ("epsilon_decay", "epsilon_min"):                  # (orc_run_teacher has no per-learner schedule)
         dev.pop(k, None); okw.pop(k, None)
     K = int(rng.choice([30, 80])) if family != "wave" else int(rng.choice([10, 25]))

@@ -24,12 +24,15 @@ NAMES = {0: "QLearning", 1: "SARSA", 2: "ExpectedSARSA", 3: "SARSALambda", 4: "Q
 N_DIM = {0: 2, 1: 4, 2: 4}
 
 
+TOP_OF_IDS = -1      # env_offset choice resolved to 2^32 - 1 - n_envs once n_envs is known
+
+
 def sample(rng):
     """-> (family, device kwargs, oracle kwargs, oracle method name, method kwargs)"""
     domain = int(rng.integers(0, 3))
     family = rng.choice(["reg", "reg", "generic", "tile", "tile", "wave", "shared_dense", "shared_tile", "sparse_lambda"])
     kw = dict(domain=domain, seed=int(rng.integers(0, 1 << 20)), gamma=float(rng.choice([0.0, 0.9, 0.9, 0.99, 1.0])),
-              max_episode_steps=int(rng.choice([0, 1, 25, 25, 200])), env_offset=int(rng.choice([0, 0, 64, 1000003])))
+              max_episode_steps=int(rng.choice([0, 1, 25, 25, 200])), env_offset=int(rng.choice([0, 0, 64, 1000003, (1 << 31) - 65, TOP_OF_IDS])))
     n = int(rng.choice([1, 3, 63, 64, 65, 130, 257, 257, 1000, 2049]))
     method, mkw = "train", {}
     if family in ("reg", "shared_dense"):
@@ -99,12 +102,22 @@ def sample(rng):
         dev["weight_mode"] = ra.W_SHARED
         n = dev["n_envs"] = int(rng.choice([5, 64, 300]))
         dev["alpha"] = kw["alpha"] = step / n
+    if kw["env_offset"] == TOP_OF_IDS:       # the shard that ends at the largest learner id a ctx admits ((1 << 31) - 65: ids that straddle the sign bit)
+        kw["env_offset"] = dev["env_offset"] = (1 << 32) - 1 - dev["n_envs"]
     okw = {k: v for k, v in kw.items() if k not in ("basis",)}
     okw["basis"] = orc.TILE if kw["basis"] == ra.TILE_CODING else orc.FOURIER
     okw["shared_w"] = dev.get("weight_mode", ra.W_PER_ENV) == ra.W_SHARED
     if okw["max_episode_steps"] == 0:
         okw["max_episode_steps"] = 0
     return family, dev, okw, method, mkw
+
+
+def resized(dev, okw, n):
+    """a sampled configuration at another learner count: the shard that ended at the largest learner id still does"""
+    if dev["env_offset"] + dev["n_envs"] == (1 << 32) - 1:
+        dev["env_offset"] = okw["env_offset"] = (1 << 32) - 1 - n
+    dev["n_envs"] = n
+    return n
 
 
 REFUSALS = (-1, -5)          # EINVAL, ESTATE: a query the family does not have
@@ -215,9 +228,9 @@ def run_case(rng, idx):
     if os.environ.get("FUZZ_LONG"):      # long horizons: across the default fuse depth (4 096), many graph replays, thousands of episodes
         total *= 10 if family == "wave" else 60
         if n > 130 and family not in ("shared_dense", "shared_tile"):
-            n = dev["n_envs"] = 130
+            n = resized(dev, okw, 130)
         elif n > 600:
-            n = dev["n_envs"] = 600
+            n = resized(dev, okw, 600)
     cuts = sorted(set(int(x) for x in rng.integers(1, total, size=int(rng.integers(0, 3)))))
     calls = [b - a for a, b in zip([0] + cuts, cuts + [total])]
     if rng.random() < 0.1:
@@ -419,17 +432,18 @@ def run_big(rng, idx):
     feats = (kw["order"] + 1) ** N_DIM[domain]
     kw["lr"] = 0.1 / feats
     n = int(rng.choice([131072, 131072 + 77, 200003, 262144, 700003]))
+    base = int(rng.choice([0, 0, (1 << 31) - 65, (1 << 32) - 1 - n]))       # the batch's own env_offset: also a shard at the top of the id space
     spl = int(rng.choice([1, 1, 0, 5]))
     K = int(rng.choice([5, 12]))
-    tag = f"{idx:4d} big           {NAMES[kw['algo']]:13s} dom {domain} N {n:6d} K {K:3d} spl {spl}"
-    with ra.Context(n_envs=n, steps_per_launch=spl, **kw) as c:
+    tag = f"{idx:4d} big           {NAMES[kw['algo']]:13s} dom {domain} N {n:6d} off {base} K {K:3d} spl {spl}"
+    with ra.Context(n_envs=n, env_offset=base, steps_per_launch=spl, **kw) as c:
         c.reset()
         c.train(K // 2, want_stats=False)
         c.train(K - K // 2, want_stats=False)
         S, Aact = c.states, c.actions
         bad = []
         for off in sorted(set([0, int(rng.integers(0, n - 70)), n - 64])):
-            ag = orc.make_agent(env_offset=off, **kw)
+            ag = orc.make_agent(env_offset=base + off, **kw)
             run = orc.Run(ag, 64, "f32d")
             run.reset()
             run.train_dev(K // 2)
@@ -439,7 +453,7 @@ def run_big(rng, idx):
             for j in (0, 63):
                 if not np.array_equal(c.get_weights(off + j), run.weights[j]):
                     bad.append(f"weights[{off + j}]")
-    return ("MISMATCH" if bad else "ok"), tag + (f"  MISMATCH {bad}" if bad else "  ok"), dict(kw, n_envs=n, steps_per_launch=spl)
+    return ("MISMATCH" if bad else "ok"), tag + (f"  MISMATCH {bad}" if bad else "  ok"), dict(kw, n_envs=n, env_offset=base, steps_per_launch=spl)
 
 
 def main():

@@ -83,3 +83,34 @@ def bits_equal(a, b):
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     na, nb = np.isnan(a), np.isnan(b)
     return bool(np.array_equal(na, nb) and np.array_equal(a[~na].view(np.uint64), b[~nb].view(np.uint64)))
+
+
+def q_learning_random_loop(orc, lo, hi, order, F, N, K, cap, seed, lr, gamma, t0=0, env_offset=0, W0=None):
+    """the driver loop of QLearning under the Random policy from a fresh default env, f64, on the draws of batch-steps t0 .. t0 + K - 1 of the learners
+    env_offset .. env_offset + N - 1 -> (first actions, actions, hidden states y, fp32 observations, episode steps, W (N, F, 4), truncations)"""
+    first = a = np.array([orc.policy_sample(orc.RANDOM, np.zeros(4), orc.draw(seed, env_offset + i, t0, orc.BLK_INIT)) for i in range(N)])
+    y = np.tile(DEFAULT.reshape(6, 1), (1, N))
+    obs32 = observe(y).astype(np.float32)
+    W = np.zeros((N, F, 4)) if W0 is None else np.array(W0, dtype=np.float64)          # (W0: the learners' initial weights (N, F, 4))
+    ep = np.zeros(N, dtype=int)
+    n_trunc = 0
+    for k in range(K):
+        t = t0 + k
+        y, obs, r = step(y, a)
+        nobs32 = obs.astype(np.float32)
+        r32 = r.astype(np.float32).astype(np.float64)
+        phi_s, phi_n = fourier(obs32, order, lo, hi), fourier(nobs32, order, lo, hi)
+        ep += 1
+        for i in range(N):
+            qs, qn = W[i].T @ phi_s[:, i], W[i].T @ phi_n[:, i]
+            W[i][:, a[i]] += lr * (r32[i] + gamma * qn.max() - qs[a[i]]) * phi_s[:, i]
+        a = np.array([orc.policy_sample(orc.RANDOM, np.zeros(4), orc.draw(seed, env_offset + i, t, orc.BLK_STEP)) for i in range(N)])
+        done = ep >= cap
+        if done.any():
+            n_trunc += int(done.sum())
+            y[:, done] = DEFAULT.reshape(6, 1)
+            nobs32[:, done] = observe(DEFAULT.reshape(6, 1)).astype(np.float32)
+            ep[done] = 0
+            a = np.where(done, [orc.policy_sample(orc.RANDOM, np.zeros(4), orc.draw(seed, env_offset + i, t, orc.BLK_RESET)) for i in range(N)], a)
+        obs32 = nobs32
+    return first, a, y, obs32, ep, W, n_trunc

@@ -98,3 +98,26 @@ def near_tie_band(mu, margin=1e-9):
     x = np.abs(np.asarray(mu, dtype=np.float64))
     d = np.abs(x[:, None] - x[None, :])
     return bool(np.any(np.abs(d - 1e-7) < margin))
+
+
+def replay_trait_loop(orc, rlstd, domain, order, F, transitions, gamma, alpha, n_updates, init=None):
+    """one learner's recorded transitions [(s, s', r, terminal)] through the rule from the agents' initial state (or init = (theta, matrix, mu))
+    -> (theta, matrix, mu)"""
+    theta, mat = np.zeros(F), (1e-5 if rlstd else 1.0) * np.eye(F)
+    mu = np.zeros(F)
+    if init is not None:
+        theta, mat = np.array(init[0], dtype=np.float64), np.array(init[1], dtype=np.float64)
+        mu = mu if init[2] is None else np.array(init[2], dtype=np.float64)
+    for s, ns, r, term in transitions:
+        phi_s, phi_n = orc.fourier_project(domain, order, s), orc.fourier_project(domain, order, ns)
+        if rlstd:
+            _, theta, mat = recursive_lstd(theta, mat, phi_s, phi_n, float(r), bool(term), gamma)
+        else:
+            _, theta, mat, mu = ilstd(theta, mat, mu, phi_s, phi_n, float(r), bool(term), gamma, alpha, n_updates, literal=False)
+    return theta, mat, mu
+
+
+def random_policy_actions(orc, seed, n_actions, N, t, block, env_offset=0):
+    """what the Random policy samples for the learners env_offset .. env_offset + N - 1 from batch-step t's draw of `block`"""
+    q = np.zeros(n_actions)
+    return np.array([orc.policy_sample(orc.RANDOM, q, orc.draw(seed, env_offset + i, t, block)) for i in range(N)])

@@ -97,3 +97,18 @@ def test_the_campaign_samplers_draw_only_admitted_configurations(matrix):
             with pytest.raises(ra.RsrlHipError) as e:
                 ra.Context(**kw).close()
             assert e.value.code == matrix.EHIP, (name, k, kw, str(e.value))
+
+
+def test_learner_ids_must_fit_32_bits():
+    # n_envs + env_offset == 2^32 is one id too many (the device's gid is a uint32_t and 2^32 - 1 is kept free); one less is admitted -- without a
+    # device that shows as EHIP ("no device"), with one as a ctx
+    import rsrl_amd as ra
+    for n, off in ((130, (1 << 32) - 130), (1, (1 << 32) - 1), (64, 1 << 32), (1, -1)):
+        with pytest.raises(ra.RsrlHipError, match="global env ids must fit 32 bits") as e:
+            ra.Context(n_envs=n, env_offset=off)
+        assert e.value.code == -1, (n, off)
+    for n, off in ((130, (1 << 32) - 1 - 130), (130, (1 << 31) - 65)):
+        try:
+            ra.Context(n_envs=n, env_offset=off).close()
+        except ra.RsrlHipError as e:
+            assert e.code == -2 and "device" in str(e), (n, off, str(e))

@@ -9,7 +9,7 @@ import pytest
 
 import rsrl_amd
 from rsrl_amd import RsrlHipError
-from tests.ac_numpy import ac_rule
+from tests.ac_numpy import ac_restated_loop as _restated_loop, ac_rule, near_boundary
 
 pytestmark = pytest.mark.gpu
 
@@ -27,12 +27,6 @@ def ctx(**kw):
 def rand_states(orc, domain, n, rng):
     lo, hi = orc.domain_bounds(domain)
     return rng.uniform(lo, hi, size=(n, len(lo))).T.astype(np.float32)
-
-
-def near_boundary(p, x, margin=1e-5):
-    """the draw's uniform lies within margin of a cumulative-probability boundary: an fp32 rounding may pick the neighbour"""
-    u = (int(x[2]) >> 8) / 16777216.0
-    return bool(np.min(np.abs(np.cumsum(p)[:-1] - u), initial=1.0) < margin)
 
 
 def randomise(c, rng, scale=0.3):
@@ -121,38 +115,6 @@ def test_policy_side_reads_theta_value_side_reads_w(orc):
             done |= term.astype(bool)
         assert np.array_equal(n_states, steps + 1)
         assert np.array_equal(total, tot)
-
-
-def _restated_loop(orc, critic_q, domain, order, N, K, cap, seed, gamma, lr, alpha, tau, S0, A0):
-    """the driver loop per learner in f64 on the same draws -> (actions [K][N] after every batch-step, W, theta, learners with a draw within 1e-5
-    of a cumulative-probability boundary: the critic's inner draw moves W without changing any action the loop shows)"""
-    F, A = (order + 1) ** S0.shape[0], 2 if domain == rsrl_amd.CART_POLE else 3
-    acts, out_W, out_T, near = np.zeros((K, N), dtype=np.int64), [], [], np.zeros(N, dtype=bool)
-    for i in range(N):
-        W, Th = np.zeros((F, A)), np.zeros((F, A))
-        s, a, ep = S0[:, i].copy(), int(A0[i]), 0
-        for t in range(K):
-            ns, r, term = orc.domain_step(domain, s, a, prec="f32d")
-            ns = np.asarray(ns, dtype=np.float32)
-            ep += 1
-            trunc = (not term) and cap > 0 and ep >= cap
-            if term:
-                ns = orc.domain_reset(domain, prec="f32")
-            phi_s, phi_n = orc.fourier_project(domain, order, s), orc.fourier_project(domain, order, ns)
-            xin = orc.draw(seed, i, t, orc.BLK_INNER)
-            near[i] |= (not term) and near_boundary(orc.policy_probs(orc.SOFTMAX, Th.T @ phi_n, tau=tau), xin)
-            _, W, Th = ac_rule(orc, critic_q, W, Th, phi_s, phi_n, a, float(np.float32(r)), term, gamma, lr, alpha, tau, xin)
-            if term or trunc:
-                ep = 0
-                ns = orc.domain_reset(domain, prec="f32")
-            xs = orc.draw(seed, i, t, orc.BLK_RESET if trunc else orc.BLK_STEP)
-            hn = Th.T @ orc.fourier_project(domain, order, ns)
-            near[i] |= near_boundary(orc.policy_probs(orc.SOFTMAX, hn, tau=tau), xs)
-            a = orc.policy_sample(orc.SOFTMAX, hn, xs, tau=tau)
-            acts[t, i] = a
-            s = np.asarray(ns, dtype=np.float32)
-        out_W.append(W); out_T.append(Th)
-    return acts, out_W, out_T, near
 
 
 @pytest.mark.parametrize("algo", [AC, QAC])

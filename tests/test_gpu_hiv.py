@@ -106,32 +106,9 @@ def test_driver_loop_against_a_restated_loop(orc):
     N, K, cap, seed, lr, gamma = 32, 30, 12, 21, 0.01, 0.9
     with ctx(n_envs=N, policy=rsrl_amd.RANDOM, max_episode_steps=cap, seed=seed, lr=lr, gamma=gamma) as c:
         c.reset()
-        a = np.array([orc.policy_sample(orc.RANDOM, np.zeros(4), orc.draw(seed, i, 0, orc.BLK_INIT)) for i in range(N)])
-        assert np.array_equal(c.actions, a)
+        first, a, y, obs32, ep, W, n_trunc = hv.q_learning_random_loop(orc, LO, HI, 1, c.F, N, K, cap, seed, lr, gamma)
+        assert np.array_equal(c.actions, first)
         st = c.train(K)
-        y = np.tile(hv.DEFAULT.reshape(6, 1), (1, N))
-        obs32 = hv.observe(y).astype(np.float32)
-        W = np.zeros((N, c.F, 4))
-        ep = np.zeros(N, dtype=int)
-        n_trunc = 0
-        for t in range(K):
-            y, obs, r = hv.step(y, a)
-            nobs32 = obs.astype(np.float32)
-            r32 = r.astype(np.float32).astype(np.float64)
-            phi_s, phi_n = hv.fourier(obs32, 1, LO, HI), hv.fourier(nobs32, 1, LO, HI)
-            ep += 1
-            for i in range(N):
-                qs, qn = W[i].T @ phi_s[:, i], W[i].T @ phi_n[:, i]
-                W[i][:, a[i]] += lr * (r32[i] + gamma * qn.max() - qs[a[i]]) * phi_s[:, i]
-            a = np.array([orc.policy_sample(orc.RANDOM, np.zeros(4), orc.draw(seed, i, t, orc.BLK_STEP)) for i in range(N)])
-            done = ep >= cap
-            if done.any():
-                n_trunc += int(done.sum())
-                y[:, done] = hv.DEFAULT.reshape(6, 1)
-                nobs32[:, done] = hv.observe(hv.DEFAULT.reshape(6, 1)).astype(np.float32)
-                ep[done] = 0
-                a = np.where(done, [orc.policy_sample(orc.RANDOM, np.zeros(4), orc.draw(seed, i, t, orc.BLK_RESET)) for i in range(N)], a)
-            obs32 = nobs32
         assert np.array_equal(c.actions, a)
         assert hv.bits_equal(c.get_hidden_states(), y)
         assert np.all(ulps_f32(c.states, obs32) <= 1)

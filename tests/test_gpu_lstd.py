@@ -9,7 +9,7 @@ import pytest
 
 import rsrl_amd
 from rsrl_amd import RsrlHipError
-from tests.lstd_numpy import ilstd, near_tie_band, recursive_lstd
+from tests.lstd_numpy import ilstd, near_tie_band, recursive_lstd, replay_trait_loop
 
 pytestmark = pytest.mark.gpu
 
@@ -214,14 +214,7 @@ def test_long_horizon_replayed_in_numpy(orc, algo):
             c.policy_sample()
         tol = 1e4 * F * K * EPS
         for k, i in enumerate(pick):
-            theta, mat = np.zeros(F), (1e-5 if algo == RLSTD else 1.0) * np.eye(F)
-            mu = np.zeros(F)
-            for frm, nxt, r, t in rec:
-                phi_s, phi_n = orc.fourier_project(domain, order, frm[:, k]), orc.fourier_project(domain, order, nxt[:, k])
-                if algo == RLSTD:
-                    _, theta, mat = recursive_lstd(theta, mat, phi_s, phi_n, float(r[k]), bool(t[k]), gamma)
-                else:
-                    _, theta, mat, mu = ilstd(theta, mat, mu, phi_s, phi_n, float(r[k]), bool(t[k]), gamma, alpha, n_upd, literal=False)
+            theta, mat, mu = replay_trait_loop(orc, algo == RLSTD, domain, order, F, [(frm[:, k], nxt[:, k], r[k], t[k]) for frm, nxt, r, t in rec], gamma, alpha, n_upd)
             g_th, g_m, g_mu = c.get_lstd_state(int(i))
             for g, w in ((g_th, theta), (g_m, mat)) + (((g_mu, mu),) if algo == ILSTD else ()):
                 assert np.max(np.abs(g - w)) <= tol * (1.0 + np.max(np.abs(w))), (i, np.max(np.abs(g - w)), tol * (1.0 + np.max(np.abs(w))))

@@ -10,8 +10,8 @@ import pytest
 
 import rsrl_amd
 from rsrl_amd import RsrlHipError
-from tests.ac_numpy import actor_step
-from tests.reinforce_numpy import reinforce_batch
+from tests.ac_numpy import actor_step, near_boundary
+from tests.reinforce_numpy import reinforce_batch, reinforce_restated_loop as _restated_loop
 
 pytestmark = pytest.mark.gpu
 
@@ -31,12 +31,6 @@ def ctx(**kw):
 def rand_states(orc, domain, n, rng):
     lo, hi = orc.domain_bounds(domain)
     return rng.uniform(lo, hi, size=(n, len(lo))).T.astype(np.float32)
-
-
-def near_boundary(p, x, margin=1e-5):
-    """the draw's uniform lies within margin of a cumulative-probability boundary: an fp32 rounding may pick the neighbour"""
-    u = (int(x[2]) >> 8) / 16777216.0
-    return bool(np.min(np.abs(np.cumsum(p)[:-1] - u), initial=1.0) < margin)
 
 
 def f32_returns(rewards, gamma):
@@ -120,35 +114,6 @@ def test_zero_baseline_is_reinforce_and_the_baseline_never_moves(orc, domain, or
         bb.train(7)
         for i in range(N):
             assert np.array_equal(bb.get_weights(i).view(np.uint32), Bs[i].view(np.uint32)), i
-
-
-def _restated_loop(orc, domain, order, N, K, cap, seed, gamma, alpha, tau, S0, A0, B=None):
-    """the driver loop per learner in f64 on the same draws, each episode sampled from theta as it stood when the episode began -> (actions
-    [K][N], theta, theta_b, learners with a draw within 1e-5 of a cumulative-probability boundary)"""
-    F, A = (order + 1) ** S0.shape[0], 2 if domain == rsrl_amd.CART_POLE else 3
-    acts, out_T, out_b, near = np.zeros((K, N), dtype=np.int64), [], [], np.zeros(N, dtype=bool)
-    for i in range(N):
-        Th, Tb, g = np.zeros((F, A)), np.zeros((F, A)), 0.0
-        s, a, ep = S0[:, i].copy(), int(A0[i]), 0
-        for t in range(K):
-            ns, r, term = orc.domain_step(domain, s, a, prec="f32d")
-            ep += 1
-            trunc = (not term) and cap > 0 and ep >= cap
-            phi_s = orc.fourier_project(domain, order, s)
-            g = float(np.float32(r)) + gamma * g
-            e = alpha * g if B is None else alpha * (g - B[i][:, a] @ phi_s)
-            Th = actor_step(Th, phi_s, a, e, tau)
-            if term or trunc:
-                ep, g, Tb = 0, 0.0, Th.copy()
-                ns = orc.domain_reset(domain, prec="f32")
-            xs = orc.draw(seed, i, t, orc.BLK_RESET if trunc else orc.BLK_STEP)
-            hb = Tb.T @ orc.fourier_project(domain, order, np.asarray(ns, dtype=np.float32))
-            near[i] |= near_boundary(orc.policy_probs(orc.SOFTMAX, hb, tau=tau), xs)
-            a = orc.policy_sample(orc.SOFTMAX, hb, xs, tau=tau)
-            acts[t, i] = a
-            s = np.asarray(ns, dtype=np.float32)
-        out_T.append(Th); out_b.append(Tb)
-    return acts, out_T, out_b, near
 
 
 @pytest.mark.parametrize("algo", ALGOS)
