@@ -113,7 +113,7 @@ typedef enum { RSRL_QLEARNING = 0, RSRL_SARSA = 1, RSRL_EXPECTED_SARSA = 2, RSRL
                RSRL_ACTOR_CRITIC = 10, RSRL_Q_ACTOR_CRITIC = 11,
                /* (12 is no algo.)  ActorCritic::tdac (ac.rs:32-52, :87-98): the same Gibbs actor with TDCritic over a state-value function V, the loop of
                 * examples/tdac.rs with the project's TD(0) prediction agent as its `eval` (TD{v_func = ScalarLFA(basis, SGD(lr)), gamma},
-                * prediction/td/td.rs:31-59; tdac.rs uses iLSTD).  Per transition (s, a, r, s', term), p = softmax(theta^T phi(s) / tau) before the update:
+                * prediction/td/td.rs:31-59; tdac.rs's own evaluator is iLSTD: RSRL_ILSTD_ACTOR_CRITIC).  Per transition (s, a, r, s', term), p = softmax(theta^T phi(s) / tau) before the update:
                 *   TD(0)   delta = r - V(s) (terminal) | r + gamma*V(s') - V(s);   w += lr*delta*phi(s)        (bit for bit a RSRL_TD ctx's w and delta)
                 *   critic  c = r - V'(s') (terminal: V of the terminal state s' itself) | r + gamma*V'(s') - V'(s), V' with the UPDATED w
                 *   actor   theta[:,b] += alpha * c * (1[b==a] - p_b) * phi(s)
@@ -161,7 +161,24 @@ typedef enum { RSRL_QLEARNING = 0, RSRL_SARSA = 1, RSRL_EXPECTED_SARSA = 2, RSRL
                 * q_expected_value, traces, td / policy weights and handle_batch are ESTATE.  rsrl_hip_handle's td_error_out and the statistics'
                 * sum |delta| are RecursiveLSTD's residual; iLSTD computes no TD error and reports, as a diagnostic, r + gamma V(s') - V(s) (terminal:
                 * r - V(s)) with theta from before the update */
-               RSRL_RECURSIVE_LSTD = 18, RSRL_ILSTD = 19 } rsrl_algo;
+               RSRL_RECURSIVE_LSTD = 18, RSRL_ILSTD = 19,
+               /* (20 is no algo.)  ActorCritic::tdac (control/ac.rs:87-98) with the Gibbs actor and TDCritic over the V that iLSTD learns: the agent
+                * and the loop of examples/tdac.rs (eval.handle, agent.handle, sample).  RSRL_ILSTD's f64 state (theta = 0, A = I, mu = 0) beside the
+                * actor's f32 theta (zero), per learner.  Per transition:
+                *   p       = softmax(theta_a^T phi(s) / tau), theta_a before its update                 (f32, RSRL_TD_ACTOR_CRITIC's arithmetic)
+                *   iLSTD   RSRL_ILSTD's handle, bit for bit (f64 features; terminal: pd = phi(s))
+                *   critic  c = r - V'(s') (terminal: V of the terminal state s' itself) | r + gamma*V'(s') - V'(s), V' = phi . theta with the UPDATED
+                *           f64 theta, summed in index order
+                *   actor   e = (float)(alpha * c), the one rounding out of f64; theta_a[:,b] += e * (1[b==a] - p_b) * phi(s)         (f32)
+                * No inner draw.  config: lr = iLSTD's alpha (the critic's rate, as for the other actor-critics), gamma = iLSTD's and TDCritic's,
+                * n_steps = iLSTD's n_updates in 1..32, alpha = ActorCritic.alpha, tau = Softmax.tau; policy must be RSRL_SOFTMAX and agent_policy -1.
+                * The VALUE side is RSRL_ILSTD's: q_evaluate writes f32(phi(s) . theta) as f32[1][M], get / set_weights carry theta as f32[F][1],
+                * rsrl_hip_get/set_lstd_state are exact, n_outputs is 1, q_find_max / _min / q_expected_value are ESTATE.  The POLICY side is
+                * RSRL_TD_ACTOR_CRITIC's: it reads theta_a [F][A] (policy_sample / _mode / _probs / _prob, reset's initial sample, the rollouts;
+                * rsrl_hip_get/set_policy_weights).  handle_batch, traces and td weights are ESTATE.  rsrl_hip_handle's td_error_out and the
+                * statistics' sum |delta| are iLSTD's diagnostic.  rsrl_hip_reset leaves both agents' state alone.  Supported: as
+                * RSRL_TD_ACTOR_CRITIC; everything else is EINVAL at create (kernels_tdac_lstd.hpp) */
+               RSRL_ILSTD_ACTOR_CRITIC = 21 } rsrl_algo;
 /* rsrl::traces::{Accumulate, Saturate (Trace::replacing), Dutch}      traces.rs:188-240 */
 typedef enum { RSRL_TRACE_ACCUMULATE = 0, RSRL_TRACE_SATURATE = 1, RSRL_TRACE_DUTCH = 2 } rsrl_trace;
 /* rsrl::policies::{Greedy, EpsilonGreedy, Softmax, Random}
@@ -232,7 +249,7 @@ typedef struct {
     double   agent_epsilon;      /* EpsilonGreedy.epsilon of the agent's policy                                          */
     double   agent_tau;          /* Softmax.tau of the agent's policy                                                    */
     double   sigma;              /* QSigma.sigma in [0, 1]: 1 = SARSA-like sampling, 0 = tree backup (q_sigma.rs:66-72)          */
-    int32_t  n_steps;            /* QSigma: Backup::new(n_steps), 1..32 (q_sigma.rs:94-104).  RSRL_ILSTD: iLSTD's n_updates, the
+    int32_t  n_steps;            /* QSigma: Backup::new(n_steps), 1..32 (q_sigma.rs:94-104).  RSRL_ILSTD / RSRL_ILSTD_ACTOR_CRITIC: iLSTD's n_updates, the
                                     rounds of solve() per transition, 1..32                                                      */
     int32_t  peer_timeout_ms;    /* ABI 5 (was reserved0): bound of every in-kernel wait for a peer / block of the shared-W exchange, in
                                     milliseconds; 0 = RSRL_PEER_TIMEOUT_MS from the environment, else 4000.  Make it longer than the
@@ -432,7 +449,7 @@ int rsrl_hip_get_behaviour_weights(rsrl_hip_ctx* ctx, int64_t env_index, float* 
 int rsrl_hip_set_behaviour_weights(rsrl_hip_ctx* ctx, int64_t env_index, const float* theta_b /*[F][A]*/);
 int rsrl_hip_get_return_carry(rsrl_hip_ctx* ctx, float* g /*[N]*/);
 int rsrl_hip_set_return_carry(rsrl_hip_ctx* ctx, const float* g /*[N]*/);
-/* RecursiveLSTD / iLSTD: the exact f64 state of one learner -- theta, the matrix (row-major: C for RecursiveLSTD, A for iLSTD) and iLSTD's mu
+/* RecursiveLSTD / iLSTD (and the iLSTD ActorCritic's critic): the exact f64 state of one learner -- theta, the matrix (row-major: C for RecursiveLSTD, A for iLSTD) and iLSTD's mu
  * (may be NULL: not read or written; ignored by RecursiveLSTD).  Host or device arrays.  ESTATE on every other agent */
 int rsrl_hip_get_lstd_state(rsrl_hip_ctx* ctx, int64_t env_index, double* theta /*[F]*/, double* mat /*[F][F]*/, double* mu /*[F], iLSTD only, may be NULL*/);
 int rsrl_hip_set_lstd_state(rsrl_hip_ctx* ctx, int64_t env_index, const double* theta /*[F]*/, const double* mat /*[F][F]*/,
@@ -449,6 +466,7 @@ int rsrl_hip_set_lstd_state(rsrl_hip_ctx* ctx, int64_t env_index, const double* 
  *   6 the TD ActorCritic's theta                     8           weights, auxiliary matrix
  *   7 REINFORCE's theta and open episode             9           weights (BaselineREINFORCE only), auxiliary matrix, theta_b, g
  *   8 the LSTD agents' f64 state                     10          f64 theta, matrices, mu
+ *   9 the iLSTD ActorCritic's f64 state and theta    10          f64 theta, matrices, mu, auxiliary matrix
  * and a ctx with config.epsilon_decay (aux_kind 0 or 1) writes version 4 instead, with f32 eps[N] behind the payload.  No other pairing of
  * version and aux_kind is a file of this library; load refuses it.  Little-endian, serialised field by field (no padding):
  *   offset  0  char magic[8] = "RSRLHIPW"
@@ -456,7 +474,8 @@ int rsrl_hip_set_lstd_state(rsrl_hip_ctx* ctx, int64_t env_index, const double* 
  *          12  i32  domain, basis, order, n_tilings, tiles_per_dim, weight_mode, F, A (weight columns),
  *                   algo, weight_dtype, aux_kind (0 none, 1 eligibility traces, 2 GreedyGQ's fa_td weights,
  *                   3 QSigma's n-step backups, 4 sparse traces over a shared table, 5 ActorCritic's theta,
- *                   6 the TD ActorCritic's theta, 7 REINFORCE's theta and open episode, 8 the LSTD agents' f64 state)
+ *                   6 the TD ActorCritic's theta, 7 REINFORCE's theta and open episode, 8 the LSTD agents' f64 state,
+ *                   9 the iLSTD ActorCritic's f64 state and theta)
  *                                                                                                                 [11 x i32]
  *          56  i64  n_learners (1 in shared mode)
  *          64  u64  step_count
@@ -472,6 +491,8 @@ int rsrl_hip_set_lstd_state(rsrl_hip_ctx* ctx, int64_t env_index, const double* 
  *              if aux_kind is 8 (file version 10, which no other configuration reads; RSRL_RECURSIVE_LSTD / RSRL_ILSTD): the weights section is
  *              ABSENT (theta is f64); then n_learners x f64[F] of theta, n_learners x f64[F][F] of the matrix (C / A, row-major) and, for
  *              iLSTD, n_learners x f64[F] of mu;
+ *              if aux_kind is 9 (file version 10 too; RSRL_ILSTD_ACTOR_CRITIC): aux_kind 8's sections of its iLSTD critic (mu included), then
+ *              n_learners x f32[F][n_actions] of the actor's theta;
  *              if aux_kind is 3 (file version 3): u32 head[N], u32 len[N], f32 entries[D + 5][n_steps][N] -- every learner's
  *              Backup ring {s, a, q, residual, pi, mu} (q_sigma.rs:30-63), so that a QSigma run with n_steps > 1 resumes
  *              bit-identically too.  A QSigma ctx still reads its configuration's version-2 file without them (aux_kind 0): the backups start empty.

@@ -13,6 +13,7 @@ ACTOR_CRITIC, Q_ACTOR_CRITIC = 10, 11          # ActorCritic (control/ac.rs) wit
 TD_ACTOR_CRITIC = 13                           # ActorCritic::tdac: the Gibbs actor with TDCritic over a TD(0) V (12 is no algo)
 REINFORCE, BASELINE_REINFORCE = 15, 16         # (14 is no algo) control/mc: REINFORCE<Gibbs>, BaselineREINFORCE<B, Gibbs> (Handler<&Batch>: handle_batch)
 RECURSIVE_LSTD, ILSTD = 18, 19                  # (17 is no algo) prediction/lstd: RecursiveLSTD, iLSTD (f64 theta and F x F matrix: get/set_lstd_state)
+ILSTD_ACTOR_CRITIC = 21                        # (20 is no algo) ActorCritic::tdac over iLSTD, tdac.rs's agent: lr = iLSTD's alpha, n_steps = its n_updates, alpha = the actor's
 TRACE_ACCUMULATE, TRACE_SATURATE, TRACE_DUTCH = 0, 1, 2
 GREEDY, EPSILON_GREEDY, SOFTMAX, RANDOM = 0, 1, 2, 3
 W_PER_ENV, W_SHARED = 0, 1
@@ -377,9 +378,9 @@ class Context:
         _abi.check(self._L.rsrl_hip_set_return_carry(self._h, _p(_in(g, np.float32, (self.N,)))))
 
     def get_lstd_state(self, env_index=0):
-        """RecursiveLSTD / iLSTD: one learner's exact f64 state -> (theta (F,), the matrix (F, F): C / A, mu (F,) for iLSTD else None)"""
+        """RecursiveLSTD / iLSTD / the iLSTD ActorCritic: one learner's exact f64 state -> (theta (F,), the matrix (F, F): C / A, mu (F,) for iLSTD else None)"""
         theta, mat = np.empty(self.F, dtype=np.float64), np.empty((self.F, self.F), dtype=np.float64)
-        mu = np.empty(self.F, dtype=np.float64) if self.cfg.algo == ILSTD else None
+        mu = np.empty(self.F, dtype=np.float64) if self.cfg.algo in (ILSTD, ILSTD_ACTOR_CRITIC) else None
         _abi.check(self._L.rsrl_hip_get_lstd_state(self._h, int(env_index), _p(theta), _p(mat), _p(mu)))
         return theta, mat, mu
 

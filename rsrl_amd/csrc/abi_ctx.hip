@@ -42,6 +42,7 @@ static AgentFamily classify(const rsrl_hip_config& cfg, size_t w_elems) {
     if (is_tdac(al)) return F::TdAcReg;                     // (before the prediction agents: W is V's one column, but the policy is the actor's)
     if (is_reinforce(al)) return F::ReinforceReg;
     if (is_lstd(al)) return F::LstdReg;
+    if (is_tdac_lstd(al)) return F::TdAcLstdReg;
     if (cfg.weight_mode == RSRL_W_SHARED) return fourier ? F::SharedDense : (is_sparse_lambda(cfg) ? F::SharedSparseLambda : F::SharedTile);
     if (wave && is_wave_aux_algo(al)) return F::WaveAux;
     if (is_pred(al)) return tile ? F::TdTile : (reg ? F::TdReg : F::TdGeneric);
@@ -80,6 +81,7 @@ static const char* train_kernel_name(const rsrl_hip_ctx* c) {
     case AgentFamily::TdAcReg: return "k_train_tdac";
     case AgentFamily::ReinforceReg: return "k_train_reinforce";
     case AgentFamily::LstdReg: return "k_train_lstd";
+    case AgentFamily::TdAcLstdReg: return "k_train_tdac_lstd";
     }
     return "";
 }
@@ -182,7 +184,7 @@ static int check_config(const rsrl_hip_config& cfg) {
     const int D = kDomainShape[cfg.domain][0], A = kDomainShape[cfg.domain][1];
     if (cfg.n_envs < 1) return fail(RSRL_HIP_EINVAL, "n_envs must be >= 1");
     if (cfg.n_envs + cfg.env_offset > (int64_t)0xffffffffLL || cfg.env_offset < 0) return fail(RSRL_HIP_EINVAL, "global env ids must fit 32 bits");
-    if (cfg.algo < 0 || cfg.algo > RSRL_ILSTD || cfg.algo == 12 || cfg.algo == 14 || cfg.algo == 17) return fail(RSRL_HIP_EINVAL, "unknown algo %d", cfg.algo);
+    if (cfg.algo < 0 || cfg.algo > RSRL_ILSTD_ACTOR_CRITIC || cfg.algo == 12 || cfg.algo == 14 || cfg.algo == 17 || cfg.algo == 20) return fail(RSRL_HIP_EINVAL, "unknown algo %d", cfg.algo);
     if (cfg.policy < 0 || cfg.policy > RSRL_RANDOM) return fail(RSRL_HIP_EINVAL, "unknown policy %d", cfg.policy);
     // Softmax::new panics for |tau| < 1e-7 (policies/softmax.rs:63-66)
     if (cfg.policy == RSRL_SOFTMAX && std::fabs(cfg.tau) < 1e-7) return fail(RSRL_HIP_EINVAL, "Tau parameter in Softmax must be non-zero.");
@@ -261,6 +263,18 @@ static int check_config(const rsrl_hip_config& cfg) {
             return fail(RSRL_HIP_EINVAL, "%s: n_steps (n_updates, the rounds of solve() per transition) must be in [1, 32], got %d", name, cfg.n_steps);
         return RSRL_HIP_OK;
     }
+    if (is_tdac_lstd(al)) {
+        // train_tdac_lstd.hip: the TD ActorCritic's configurations; n_steps is the critic's n_updates
+        const char* name = "the iLSTD ActorCritic (RSRL_ILSTD_ACTOR_CRITIC)";
+        if (!reg || !per_env || !f32 || cfg.policy != RSRL_SOFTMAX || cfg.agent_policy != -1 || esched)
+            return fail(RSRL_HIP_EINVAL, "%s supports per-learner f32 weights on the register-family Fourier orders (MountainCar 1-5, CartPole 1, Acrobot 1) "
+                                         "with policy = Softmax (the Gibbs actor), agent_policy = -1 and no epsilon schedule (got domain %d, basis %d, order %d, "
+                                         "weight mode %d, dtype %d, policy %d, agent_policy %d, epsilon_decay %g)",
+                        name, cfg.domain, cfg.basis, cfg.order, cfg.weight_mode, cfg.weight_dtype, cfg.policy, cfg.agent_policy, cfg.epsilon_decay);
+        if (cfg.n_steps < 1 || cfg.n_steps > 32)
+            return fail(RSRL_HIP_EINVAL, "%s: n_steps (the critic's n_updates, the rounds of solve() per transition) must be in [1, 32], got %d", name, cfg.n_steps);
+        return RSRL_HIP_OK;
+    }
     if (cfg.domain == RSRL_HIV_TREATMENT) {
         // train_hiv.hip: the one-step agents over the Fourier basis of order 1-3, per-learner f32 weights, one epsilon for the ctx
         if (!one_step || tile || cfg.order > 3 || !per_env || !f32 || esched)
@@ -318,7 +332,7 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
     const int64_t N = cfg->n_envs;
     const bool shared = cfg->weight_mode == RSRL_W_SHARED;
     c->w_stride = shared ? 1 : N;
-    c->Aw = (is_pred(cfg->algo) || is_tdac(cfg->algo) || is_lstd(cfg->algo)) ? 1 : c->A;         // (the TD ActorCritic's weights are V's)
+    c->Aw = (is_pred(cfg->algo) || is_tdac(cfg->algo) || is_lstd(cfg->algo) || is_tdac_lstd(cfg->algo)) ? 1 : c->A;         // (the TD / iLSTD ActorCritic's weights are V's)
     c->w_elems = (size_t)c->Aw * c->F * (size_t)(shared ? 1 : N);
     c->family = classify(*cfg, c->w_elems);
     // a ctx that steps one batch-step per launch streams W every step: learner-major rows (W[N][A][F]) let k_step_reg_lm
@@ -338,7 +352,7 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
     case AgentFamily::WaveAux: case AgentFamily::WaveQSigma: case AgentFamily::WaveLambda: case AgentFamily::WaveControl: c->n_stat_slots = wave_grid_for(N); break;
     case AgentFamily::TdTile: case AgentFamily::LambdaTile: case AgentFamily::SharedSparseLambda: c->n_stat_slots = (size_t)N; break;      // (a block per learner)
     case AgentFamily::LambdaGeneric: c->n_stat_slots = (size_t)((N + 63) / 64); break;                  // k_train_lambda_mem4: 64 learners per block
-    case AgentFamily::LstdReg: c->n_stat_slots = (size_t)((N * lstd_group_lanes(c->F) + kBlock - 1) / kBlock); break;      // k_train_lstd: G lanes per learner
+    case AgentFamily::LstdReg: case AgentFamily::TdAcLstdReg: c->n_stat_slots = (size_t)((N * lstd_group_lanes(c->F) + kBlock - 1) / kBlock); break;      // k_train_lstd: G lanes per learner
     default: c->n_stat_slots = c->k1_quad ? (size_t)((N + 63) / 64) : grid_for(N); break;
     }
     HIP_TRY(hipMalloc((void**)&c->state, sizeof(float) * c->D * (size_t)N));
@@ -381,8 +395,8 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
         HIP_TRY(hipMemsetAsync(c->sp_vals, 0, sizeof(float) * (size_t)kSparseCap * (size_t)N, c->stream));
         c->sp_lds = slice * 8 <= 128 * 1024;
         if (c->sp_lds && slice * 8 > 64 * 1024) c->sp_lds = sparse_trace_scatter_allow_lds(cfg->n_tilings, (int)(slice * 8));      // more dynamic LDS than a kernel gets by default
-    } else if (has_aux(cfg->algo) || c->family == AgentFamily::TdAcReg) {
-        c->z_bytes = (c->family == AgentFamily::TdAcReg ? (size_t)aux_cols(c) * c->F * (size_t)N : c->w_elems) * 4;      // (TdAcReg: theta, A columns)
+    } else if (has_aux(cfg->algo) || is_v_actor_critic(c)) {
+        c->z_bytes = (is_v_actor_critic(c) ? (size_t)aux_cols(c) * c->F * (size_t)N : c->w_elems) * 4;      // (TdAcReg / TdAcLstdReg: theta, A columns)
         HIP_TRY(hipMalloc((void**)&c->Z, c->z_bytes));
         HIP_TRY(hipMemsetAsync(c->Z, 0, c->z_bytes, c->stream));                  // Trace::zeros (ActorCritic's theta: LFA::vector zero-initialises)
     } else if (c->family == AgentFamily::ReinforceReg) {
@@ -394,15 +408,16 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
         HIP_TRY(hipMemsetAsync(c->Zb, 0, c->z_bytes, c->stream));
         HIP_TRY(hipMalloc((void**)&c->ret_g, sizeof(float) * (size_t)N));
         HIP_TRY(hipMemsetAsync(c->ret_g, 0, sizeof(float) * (size_t)N, c->stream));
-    } else if (c->family == AgentFamily::LstdReg) {
-        // theta = 0; RecursiveLSTD: C = 1e-5 I; iLSTD: A = I, mu = 0 (recursive_lstd.rs:24-33, ilstd.rs:27-40)
+    }
+    if (has_lstd_state(c)) {
+        // theta = 0; RecursiveLSTD: C = 1e-5 I; iLSTD (the iLSTD ActorCritic's critic too): A = I, mu = 0 (recursive_lstd.rs:24-33, ilstd.rs:27-40)
         const size_t nv = (size_t)c->F * (size_t)N, nm = nv * (size_t)c->F;
         HIP_TRY(hipMalloc((void**)&c->lstd_theta, sizeof(double) * nv));
         HIP_TRY(hipMemsetAsync(c->lstd_theta, 0, sizeof(double) * nv, c->stream));
         HIP_TRY(hipMalloc((void**)&c->lstd_mat, sizeof(double) * nm));
         launch_lstd_fill_eye(c->stream, c->lstd_mat, (int64_t)nm, c->F, cfg->algo == RSRL_RECURSIVE_LSTD ? 1e-5 : 1.0);
         KCHECK();
-        if (cfg->algo == RSRL_ILSTD) {
+        if (cfg->algo != RSRL_RECURSIVE_LSTD) {
             HIP_TRY(hipMalloc((void**)&c->lstd_mu, sizeof(double) * nv));
             HIP_TRY(hipMemsetAsync(c->lstd_mu, 0, sizeof(double) * nv, c->stream));
         }

@@ -218,7 +218,8 @@ static inline int64_t fuse_depth(const rsrl_hip_ctx* c) {
         return 4096;
     // RecursiveLSTD / iLSTD: O(F^2) f64 per learner-step, 0.76 / 1.03 ms per batch-step at 262 144 MountainCar order-5 learners:
     // 32 keep a launch in the tens of milliseconds there; at 65 536 order-3 learners a 32-step launch lasts 0.6 ms
-    case AgentFamily::LstdReg: return 32;
+    // (the iLSTD ActorCritic: the same f64 step with the actor's f32 work beside it)
+    case AgentFamily::LstdReg: case AgentFamily::TdAcLstdReg: return 32;
     // HIVTreatment: one batch-step is 1 000 f64 RK4 sub-steps per learner, ~1 ms at 65 536 learners -- 16 keep a launch in the tens of milliseconds
     case AgentFamily::Hiv: return 16;
     default: return 256;
@@ -444,6 +445,7 @@ int launch_agent(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, uint64_t 
         break;
     case AgentFamily::TdAcReg: ok = launch_tdac(cf.domain, cf.order, grid, block, c->stream, k, c->Z, t, chunk, d_stats, io); break;
     case AgentFamily::LstdReg: ok = launch_lstd(cf.domain, cf.order, cf.algo == RSRL_ILSTD, c->stream, k, make_lstd(c), t, chunk, d_stats, io); break;
+    case AgentFamily::TdAcLstdReg: ok = launch_tdac_lstd(cf.domain, cf.order, c->stream, k, make_tdac_lstd(c), t, chunk, d_stats, io); break;
     case AgentFamily::ReinforceReg:      // (io: rsrl_hip_handle refuses these agents before it gets here; rsrl_hip_handle_batch launches its own)
         ok = !io && launch_reinforce(cf.domain, cf.order, cf.algo == RSRL_BASELINE_REINFORCE, grid, block, c->stream, k, make_reinforce(c), t, chunk, d_stats, nullptr);
         break;

@@ -127,7 +127,7 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
     if ((is_pred(c->cfg.algo) || is_lstd(c->cfg.algo)) && op != QOP_EVALUATE && op != QOP_FEATURES)
         return fail(RSRL_HIP_ESTATE, "a prediction agent has a state-value function only (use rsrl_hip_q_evaluate for V(s))");
     // the TD ActorCritic: its value side is V(s) (no action values to search or weigh), its policy side the actor's theta
-    if (is_tdac(c->cfg.algo) && (op == QOP_FIND_MAX || op == QOP_FIND_MIN || op == QOP_EXPECTED))
+    if (is_v_actor_critic(c) && (op == QOP_FIND_MAX || op == QOP_FIND_MIN || op == QOP_EXPECTED))
         return fail(RSRL_HIP_ESTATE, "the TD ActorCritic's critic is a state-value function (use rsrl_hip_q_evaluate for V(s), the policy operations for the actor)");
     // REINFORCE has no value function (BaselineREINFORCE's is the baseline B): only the policy's operations and the projection
     if (c->cfg.algo == RSRL_REINFORCE && (op == QOP_EVALUATE || op == QOP_FIND_MAX || op == QOP_FIND_MIN || op == QOP_EXPECTED))
@@ -149,7 +149,7 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
     const uint64_t call = (op == QOP_SAMPLE_STEP || op == QOP_SAMPLE_INIT) ? step_t : c->api_calls;      // (the driver loop's sample: addressed by the batch-step)
     if (op == QOP_SAMPLE) c->api_calls++;
     const BasisGeom g = make_geom(c);
-    if (c->family == AgentFamily::LstdReg && op == QOP_EVALUATE) {                        // V(s) = f32(phi(s) . theta), in f64 (k_lstd_v)
+    if (has_lstd_state(c) && op == QOP_EVALUATE) {                        // V(s) = f32(phi(s) . theta), in f64 (k_lstd_v)
         if (!launch_lstd_v(c->cfg.domain, c->cfg.order, c->stream, c->lstd_theta, d_states, M_, of.dev)) return NO_MODEL(c);
     } else if ((is_pred(c->cfg.algo) || is_tdac(c->cfg.algo)) && op == QOP_EVALUATE) {          // V(s) (the TD ActorCritic: its w, k_v_evaluate)
         bool ok = true;

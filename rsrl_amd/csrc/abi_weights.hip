@@ -59,7 +59,7 @@ static int lstd_weights_rw(rsrl_hip_ctx* c, int64_t first, int64_t count, float*
 // Parameterised::weights of one learner, read (out) or written (in)
 static int weights_rw(rsrl_hip_ctx* c, int64_t env_index, float* out, const float* in) {
     if (c->cfg.algo == RSRL_REINFORCE) return no_value_function(c);
-    if (c->family == AgentFamily::LstdReg) return lstd_weights_rw(c, env_index, 1, out, in);
+    if (has_lstd_state(c)) return lstd_weights_rw(c, env_index, 1, out, in);
     const bool shared = c->cfg.weight_mode == RSRL_W_SHARED;
     if (!shared && (env_index < 0 || env_index >= c->cfg.n_envs)) return fail(RSRL_HIP_EINVAL, "env_index out of range");
     HIP_TRY(hipSetDevice(c->cfg.device));
@@ -135,7 +135,7 @@ int rsrl_hip_set_behaviour_weights(rsrl_hip_ctx* c, int64_t env_index, const flo
 static int lstd_state_rw(rsrl_hip_ctx* c, int64_t env_index, double* theta, double* mat, double* mu, const double* theta_in, const double* mat_in,
                          const double* mu_in) {
     CHECK_CTX(c); FLUSH(c);
-    if (c->family != AgentFamily::LstdReg) return fail(RSRL_HIP_ESTATE, "only RecursiveLSTD and iLSTD carry a least-squares state");
+    if (!has_lstd_state(c)) return fail(RSRL_HIP_ESTATE, "only RecursiveLSTD and iLSTD (the iLSTD ActorCritic's critic included) carry a least-squares state");
     if (env_index < 0 || env_index >= c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "env_index out of range");
     HIP_TRY(hipSetDevice(c->cfg.device));
     c->q_valid = false;
@@ -187,7 +187,7 @@ struct CkptKind {
     bool reads_kind0;            // a ctx of this kind also reads its configuration's version-2 / aux_kind-0 file, written before the kind's own section
     SectionId sections[3];       // travelled: the weights load, that section's state starts empty
 };
-constexpr int kCkptKinds = 9;
+constexpr int kCkptKinds = 10;
 constexpr CkptKind kCkptKind[kCkptKinds] = {
     /* 0 weights only                           */ {2, 0, true, false, {S_WEIGHTS}},
     /* 1 eligibility traces                     */ {2, 0, true, false, {S_WEIGHTS, S_AUX}},
@@ -198,9 +198,11 @@ constexpr CkptKind kCkptKind[kCkptKinds] = {
     /* 6 the TD ActorCritic's theta (A columns) */ {8, 0, false, false, {S_WEIGHTS, S_AUX}},
     /* 7 REINFORCE's theta and open episode     */ {9, 0, false, false, {S_WEIGHTS, S_AUX, S_BEHAVIOUR}},
     /* 8 the LSTD agents' f64 state             */ {10, 0, false, false, {S_LSTD}},
+    /* 9 the iLSTD ActorCritic: f64 state, theta */ {10, 0, false, false, {S_LSTD, S_AUX}},      // (version 10 too: the aux_kind tells the two apart)
 };
 int aux_kind_of(const rsrl_hip_ctx* c) {
     if (c->family == AgentFamily::LstdReg) return 8;
+    if (c->family == AgentFamily::TdAcLstdReg) return 9;
     if (c->family == AgentFamily::AcReg) return 5;
     if (c->family == AgentFamily::TdAcReg) return 6;
     if (c->family == AgentFamily::ReinforceReg) return 7;
@@ -591,7 +593,7 @@ int rsrl_hip_set_weights_all(rsrl_hip_ctx* c, const float* w) {
     CHECK_CTX(c); FLUSH(c);
     c->q_valid = false; c->tq_valid = false; if (!w) return fail(RSRL_HIP_EINVAL, "null argument");
     if (c->cfg.algo == RSRL_REINFORCE) return no_value_function(c);
-    if (c->family == AgentFamily::LstdReg) return lstd_weights_rw(c, 0, c->cfg.n_envs, nullptr, w);
+    if (has_lstd_state(c)) return lstd_weights_rw(c, 0, c->cfg.n_envs, nullptr, w);
     if (c->cfg.weight_mode == RSRL_W_SHARED) return rsrl_hip_set_weights(c, 0, w);
     HIP_TRY(hipSetDevice(c->cfg.device));
     const int n = c->F * c->Aw, gy = n < 1024 ? n : 1024;

@@ -57,6 +57,8 @@ static inline bool is_tdac(int algo) { return algo == RSRL_TD_ACTOR_CRITIC; }
 static inline bool is_reinforce(int algo) { return algo == RSRL_REINFORCE || algo == RSRL_BASELINE_REINFORCE; }
 // RecursiveLSTD / iLSTD: f64 theta, a f64 F x F matrix (and iLSTD's mu) per learner, outside W (which is allocated, one zero column, never read)
 static inline bool is_lstd(int algo) { return algo == RSRL_RECURSIVE_LSTD || algo == RSRL_ILSTD; }
+// ActorCritic::tdac with the iLSTD critic: iLSTD's f64 state (as is_lstd's, W allocated and never read) and the actor's theta, A columns, in Z
+static inline bool is_tdac_lstd(int algo) { return algo == RSRL_ILSTD_ACTOR_CRITIC; }
 
 // ---- the small kernels more than one unit launches, and the launches of kernel templates two units would otherwise both instantiate: defined ONCE, in
 // kernels_util.hip / launch_shared.hip (a kernel's host stub is an ordinary function: another unit launches it through this declaration)
@@ -131,6 +133,8 @@ enum class AgentFamily : uint8_t {
     TdAcReg,              // ActorCritic with the TD(0) V critic, same configurations: k_train_tdac (train_tdac.hip); w in W (one column), theta in Z (A columns)
     ReinforceReg,         // REINFORCE / BaselineREINFORCE, same configurations: k_train_reinforce (train_reinforce.hip); B in W, theta in Z, theta_b in Zb, g in ret_g
     LstdReg,              // RecursiveLSTD / iLSTD, register-family Fourier, per-learner state: k_train_lstd (train_lstd.hip); f64 state in lstd_theta / lstd_mat / lstd_mu
+    TdAcLstdReg,          // ActorCritic with the iLSTD critic, same configurations as TdAcReg: k_train_tdac_lstd (train_tdac_lstd.hip); iLSTD's f64 state as
+                          // LstdReg's, theta in Z (A columns)
 };
 static inline bool is_wave_family(AgentFamily f) {
     return f == AgentFamily::WaveAux || f == AgentFamily::WaveQSigma || f == AgentFamily::WaveLambda || f == AgentFamily::WaveControl;
@@ -176,11 +180,11 @@ struct rsrl_hip_ctx {
     uint16_t* sp_keys = nullptr; float* sp_vals = nullptr; uint32_t* sp_len = nullptr;    // sparse traces: [N][kSparseCap] slice-relative keys (16 bit) and values, lengths [N][n_tilings]
     bool sp_lds = false;             //   one tiling's slice of the delta table fits LDS (k_sparse_trace_scatter)
     float* Z = nullptr;              // auxiliary matrix f32[A][F][N]: eligibility traces (lambda agents) / fa_td weights (GreedyGQ) / the actor's theta (ActorCritic)
-                                     // -- of W's shape, except TdAcReg's theta: A columns against W's one (aux_cols)
+                                     // -- of W's shape, except TdAcReg's / TdAcLstdReg's theta: A columns against W's one (aux_cols)
     float* Zb = nullptr;             // REINFORCE only: the behaviour snapshot theta_b f32[A][F][N] (theta when the open episode began)
     float* ret_g = nullptr;          //   and the open episode's running return g f32[N]
     double* hiv_y = nullptr;         // HIVTreatment only: every learner's hidden state f64[6][N] (`state` holds its observation)
-    double* lstd_theta = nullptr;    // RecursiveLSTD / iLSTD only: theta f64[N][F], the matrix (C / A) f64[N][F][F], iLSTD's mu f64[N][F] (learner-major)
+    double* lstd_theta = nullptr;    // RecursiveLSTD / iLSTD / the iLSTD ActorCritic only: theta f64[N][F], the matrix (C / A) f64[N][F][F], iLSTD's mu f64[N][F] (learner-major)
     double* lstd_mat = nullptr;
     double* lstd_mu = nullptr;
     bool q_valid = false;            // false whenever weights / states were changed from outside the driver loop
@@ -275,19 +279,23 @@ static Common make_common(const rsrl_hip_ctx* c) {
     return k;
 }
 
+// the agents with a Gibbs policy over weights of their own (theta in Z): ActorCritic (both critics, TDCritic over TD(0) or iLSTD), REINFORCE (both)
+static inline bool has_policy_weights(const rsrl_hip_ctx* c) {
+    return c->family == AgentFamily::AcReg || c->family == AgentFamily::TdAcReg || c->family == AgentFamily::ReinforceReg || c->family == AgentFamily::TdAcLstdReg;
+}
 // the weights the POLICY side reads: the actor's preferences theta for ActorCritic (the policy is Gibbs over theta, not over Q), W otherwise.
 // Policy::sample / mode / probabilities, reset's initial sample and the rollouts run the model kernels on it; the value side keeps make_common
 static Common make_policy_common(const rsrl_hip_ctx* c) {
     Common k = make_common(c);
-    if (c->family == AgentFamily::AcReg || c->family == AgentFamily::TdAcReg || c->family == AgentFamily::ReinforceReg) k.W = c->Z;      // (the model kernels take the column count from the model: A)
+    if (has_policy_weights(c)) k.W = c->Z;      // (the model kernels take the column count from the model: A)
     return k;
 }
-// columns of the auxiliary matrix Z: W's (Aw), except the TD ActorCritic's theta (A)
-static inline int aux_cols(const rsrl_hip_ctx* c) { return c->family == AgentFamily::TdAcReg ? c->A : c->Aw; }
-// the agents with a Gibbs policy over weights of their own (theta in Z): ActorCritic (both critics, and TDCritic), REINFORCE (both)
-static inline bool has_policy_weights(const rsrl_hip_ctx* c) {
-    return c->family == AgentFamily::AcReg || c->family == AgentFamily::TdAcReg || c->family == AgentFamily::ReinforceReg;
-}
+// a state-value critic next to the actor: the weights are V's one column, theta has A
+static inline bool is_v_actor_critic(const rsrl_hip_ctx* c) { return c->family == AgentFamily::TdAcReg || c->family == AgentFamily::TdAcLstdReg; }
+// columns of the auxiliary matrix Z: W's (Aw), except the TD / iLSTD ActorCritic's theta (A)
+static inline int aux_cols(const rsrl_hip_ctx* c) { return is_v_actor_critic(c) ? c->A : c->Aw; }
+// the agents whose value function is the f64 least-squares state (lstd_theta / lstd_mat / lstd_mu)
+static inline bool has_lstd_state(const rsrl_hip_ctx* c) { return c->family == AgentFamily::LstdReg || c->family == AgentFamily::TdAcLstdReg; }
 static inline ReinforceState make_reinforce(const rsrl_hip_ctx* c) {
     ReinforceState rs;
     rs.theta = c->Z; rs.theta_b = c->Zb; rs.g = c->ret_g;
@@ -297,8 +305,15 @@ static inline ReinforceState make_reinforce(const rsrl_hip_ctx* c) {
 static inline LstdState make_lstd(const rsrl_hip_ctx* c) {
     LstdState ls;
     ls.theta = c->lstd_theta; ls.mat = c->lstd_mat; ls.mu = c->lstd_mu;
-    ls.gamma = c->cfg.gamma; ls.alpha = c->cfg.alpha; ls.n_updates = c->cfg.algo == RSRL_ILSTD ? c->cfg.n_steps : 0;
+    // (the iLSTD ActorCritic: config.alpha is ActorCritic.alpha, iLSTD's alpha is the critic's rate, config.lr)
+    ls.gamma = c->cfg.gamma; ls.alpha = is_tdac_lstd(c->cfg.algo) ? c->cfg.lr : c->cfg.alpha;
+    ls.n_updates = (c->cfg.algo == RSRL_ILSTD || is_tdac_lstd(c->cfg.algo)) ? c->cfg.n_steps : 0;
     return ls;
+}
+static inline TdacLstdState make_tdac_lstd(const rsrl_hip_ctx* c) {
+    TdacLstdState ts;
+    ts.ls = make_lstd(c); ts.theta = c->Z; ts.alpha = c->cfg.alpha;
+    return ts;
 }
 
 static LambdaParams make_lambda(const rsrl_hip_ctx* c) {

@@ -302,22 +302,4 @@ __global__ __launch_bounds__(kBlock) void k_lstd_sample(Common c, uint64_t t, ui
     out[i] = a;
 }
 
-// theta <-> f32[F] (get_weights rounds, set_weights widens exactly); set: learners first .. first + count - 1 all receive w
-__global__ __launch_bounds__(256) void k_lstd_theta_get(const double* __restrict__ theta, int F, int64_t i, float* __restrict__ w) {
-    const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (f < F) w[f] = (float)theta[i * F + f];
-}
-__global__ __launch_bounds__(256) void k_lstd_theta_set(double* __restrict__ theta, int F, int64_t first, int64_t count, const float* __restrict__ w) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= count * F) return;
-    theta[first * F + idx] = (double)w[idx % F];
-}
-
-__global__ __launch_bounds__(256) void k_lstd_fill_eye(double* __restrict__ mat, int64_t n, int F, double diag) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n) return;
-    const int64_t e = idx % ((int64_t)F * F);
-    mat[idx] = (e / F == e % F) ? diag : 0.0;
-}
-
 }  // namespace rsrl

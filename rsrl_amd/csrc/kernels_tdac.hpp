@@ -1,6 +1,6 @@
 // kernels_tdac.hpp -- ActorCritic with a TD(0) state-value critic (TDCritic) on the register family:
 //   ActorCritic::tdac / TDCritic   rsrl/src/control/ac.rs:32-52, :87-98, :108-114     driver rsrl/examples/tdac.rs (eval.handle, agent.handle, sample)
-//   the V learner                  TD{v_func = ScalarLFA(basis, SGD(lr)), gamma} (prediction/td/td.rs:31-59), in place of tdac.rs's iLSTD
+//   the V learner                  TD{v_func = ScalarLFA(basis, SGD(lr)), gamma} (prediction/td/td.rs:31-59), in place of tdac.rs's iLSTD (with iLSTD: kernels_tdac_lstd.hpp)
 //   the actor                      Gibbs::standard(LFA::vector(basis, SGD(1.0), A)) = Softmax(tau), as in kernels_ac.hpp
 // Two approximators per learner: the V learner's weights w f32[F][N] (the ctx's weights, ONE column, TD's layout) and the actor's preferences
 // theta f32[A][F][N] (the ctx's auxiliary matrix).  Per transition (s, a, r, s', term), in tdac.rs's order:

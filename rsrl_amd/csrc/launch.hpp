@@ -90,6 +90,15 @@ void launch_lstd_theta_get(hipStream_t st, const double* theta, int F, int64_t i
 void launch_lstd_theta_set(hipStream_t st, double* theta, int F, int64_t first, int64_t count, const float* w);
 // every learner's F x F block of mat (n = N * F * F doubles) := diag * I
 void launch_lstd_fill_eye(hipStream_t st, double* mat, int64_t n, int F, double diag);
+// ActorCritic::tdac with the iLSTD critic (train_tdac_lstd.hip, kernels_tdac_lstd.hpp): iLSTD's f64 state (ls.alpha = iLSTD's alpha, config.lr), the
+// actor's theta f32[A][F][N] and ActorCritic.alpha in f64.  io: handle, else chunk batch-steps of the driver loop from t; the grid is the launcher's own
+struct TdacLstdState {
+    LstdState ls;
+    float* theta = nullptr;
+    double alpha = 0.0;
+};
+bool launch_tdac_lstd(int domain, int order, hipStream_t st, const Common& k, const TdacLstdState& ts, uint64_t t, int chunk, DevStats* stats,
+                      const Transitions* io);
 
 bool launch_td(int domain, int order, bool lambda, dim3 grid, dim3 block, hipStream_t st, const Common& k, const TdParams& tp, uint64_t t, int chunk,
                DevStats* stats, const Transitions* io);

@@ -1,0 +1,27 @@
+// train_tdac_lstd.hip -- ActorCritic::tdac with the iLSTD critic (kernels_tdac_lstd.hpp) on the register-family Fourier orders: the fused driver loop
+// and Handler::handle.  The actor's side of the other entry points (reset's initial sample, the policy operations, rollouts) runs the existing model
+// kernels on the actor's theta, the value side train_lstd.hip's V kernel on the f64 theta.  Kept in a translation unit of its own so that no other
+// kernel's machine code moves.
+#include "launch.hpp"
+#include "kernels_tdac_lstd.hpp"
+#include "model_list.hpp"
+
+namespace rsrl {
+
+#define RSRL_TDAC_LSTD_CASE(DM, OR)                                                                                                             \
+    if (domain == DM && order == OR) {                                                                                                          \
+        constexpr int G = LstdGroup<FourierReg<DM, OR>::F>::G;                                                                                  \
+        const int64_t n = io ? io->M : k.n_envs;                                                                                                \
+        const dim3 grid((unsigned)((n * G + kBlock - 1) / kBlock)), block(kBlock);                                                              \
+        if (io) hipLaunchKernelGGL((k_handle_tdac_lstd<DM, OR>), grid, block, 0, st, k, ts, io->from, io->act, io->rew, io->to, io->term, io->M, io->td_out); \
+        else hipLaunchKernelGGL((k_train_tdac_lstd<DM, OR>), grid, block, 0, st, k, ts, t, chunk, stats);                                      \
+        return true;                                                                                                                            \
+    }
+
+bool launch_tdac_lstd(int domain, int order, hipStream_t st, const Common& k, const TdacLstdState& ts, uint64_t t, int chunk, DevStats* stats,
+                      const Transitions* io) {
+    RSRL_REG_FOURIER(RSRL_TDAC_LSTD_CASE)
+    return false;
+}
+
+}  // namespace rsrl

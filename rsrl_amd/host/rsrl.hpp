@@ -191,6 +191,7 @@ struct GreedyGQ : Agent {
 // ---- rsrl::control::ac: ActorCritic { critic, policy, alpha } with the Gibbs actor and a SARSA critic    (control/ac.rs:49-115, examples/a2c.rs)
 // critic: the SARSA evaluator (its q_func and gamma; it shares the actor as its policy, as the example does); the target is a2c.rs's closure
 // Q(s,a) - sum_b Q(s,b) pi(b|s), or Q(s,a) for ActorCritic::qac (QCritic).  The Session's policy must be the same Gibbs object.
+namespace prediction { namespace lstd { struct iLSTD; } }
 namespace control { namespace ac {
 // TDCritic { gamma, v_func } (ac.rs:32-52): the target r + gamma V(s') - V(s), or r - V(s') on a terminal transition
 struct TDCritic {
@@ -209,6 +210,10 @@ struct ActorCritic : td::Agent {
     static ActorCritic tdac(Shared<fa::linear::LFA> v_func, const policies::Gibbs& policy, double alpha_, double gamma) {
         return ActorCritic(TDCritic{gamma, std::move(v_func)}, policy, alpha_);
     }
+    // ActorCritic::tdac with examples/tdac.rs's own evaluator: TDCritic reads phi(s) . eval.theta, and iLSTD::handle runs before the actor's on
+    // every transition (RSRL_ILSTD_ACTOR_CRITIC).  eval's alpha, gamma and n_updates are iLSTD's; gamma is TDCritic's and must be eval's.  The
+    // Session's weights are iLSTD's theta as f32 [F][1]; Session::lstd_state(env, true) is the exact f64 state  (defined below iLSTD)
+    static inline ActorCritic tdac(const prediction::lstd::iLSTD& eval, const policies::Gibbs& policy, double alpha_, double gamma);
 };
 }}  // namespace control::ac
 
@@ -249,6 +254,14 @@ struct iLSTD : control::td::Agent {
         : control::td::Agent{RSRL_ILSTD, make_shared(fa::linear::LFA::vector(basis, fa::linear::optim::SGD(0.0), 1)), gamma, alpha_} { n_steps = n_updates; }
 };
 }}  // namespace prediction::lstd
+inline control::ac::ActorCritic control::ac::ActorCritic::tdac(const prediction::lstd::iLSTD& eval, const policies::Gibbs& policy, double alpha_, double gamma) {
+    if (gamma != eval.gamma) throw Error(RSRL_HIP_EINVAL, "ActorCritic::tdac over iLSTD: the library runs TDCritic and iLSTD with one gamma");
+    fa::linear::LFA v = *eval.q_func;
+    v.lr = eval.alpha;                                            // the critic's rate travels as config.lr, ActorCritic.alpha as config.alpha
+    ActorCritic a(TDCritic{gamma, make_shared(v)}, policy, alpha_);
+    a.algo = RSRL_ILSTD_ACTOR_CRITIC; a.n_steps = eval.n_steps;
+    return a;
+}
 
 // ---- the bound object graph: env + agent + policy sharing one q_func on one MI355X -------------------
 class Session {
@@ -351,7 +364,7 @@ public:
     std::vector<float> td_weights(int64_t env = 0) {
         std::vector<float> v((size_t)F_ * A_); check(rsrl_hip_get_td_weights(ctx_, env, v.data())); return v;
     }
-    // RecursiveLSTD / iLSTD: one learner's exact f64 state -- theta [F], the matrix [F][F] (C / A, row-major), iLSTD's mu [F] (empty otherwise)
+    // RecursiveLSTD / iLSTD (and ActorCritic::tdac over iLSTD): one learner's exact f64 state -- theta [F], the matrix [F][F] (C / A, row-major), iLSTD's mu [F] (empty otherwise)
     struct LstdState { std::vector<double> theta, mat, mu; };
     LstdState lstd_state(int64_t env = 0, bool with_mu = false) {
         LstdState st{std::vector<double>((size_t)F_), std::vector<double>((size_t)F_ * F_), std::vector<double>(with_mu ? (size_t)F_ : 0)};

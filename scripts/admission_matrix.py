@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Which configurations rsrl_hip_create admits, asked of the library on a machine WITHOUT a GPU: every admission rule runs before the device
 query, so a refused configuration returns EINVAL and an admitted one EHIP ("no device").  Sweeps GRID (133 120 configurations, about 1 s) and
-GRID_AGENTS -- the algos numbered after GRID's (13-19) on the same other axes, 71 680 configurations -- each into a fixture of its own.
-    python scripts/admission_matrix.py            writes tests/golden/create_admission.json and create_admission_agents.json
-                                                  (tests/test_create_admission_cpu.py holds the library to them)
+GRID_AGENTS -- the algos numbered after GRID's (13-19) on the same other axes, 71 680 configurations -- and GRID_AGENTS2 (20 and 21, 20 480
+configurations), each into a fixture of its own.
+    python scripts/admission_matrix.py            writes tests/golden/create_admission.json, create_admission_agents.json and
+                                                  create_admission_agents2.json (tests/test_create_admission_cpu.py and
+                                                  tests/test_tdac_lstd_cpu.py hold the library to them)
     python scripts/admission_matrix.py --check    exits 1 if the library and a stored fixture disagree
 Each admitted configuration is stored as one character per axis: the index of its value in that axis, in hex."""
 import ctypes as C
@@ -16,6 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission.json")
 AGENTS_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_agents.json")
+AGENTS2_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_agents2.json")
 EINVAL, EHIP = -1, -2
 
 # (config field, values): the first axis varies slowest
@@ -34,7 +37,9 @@ GRID = [
 ]
 # the TD ActorCritic (13), REINFORCE / BaselineREINFORCE (15, 16), RecursiveLSTD / iLSTD (18, 19) and the unassigned 14 and 17, on GRID's other axes
 GRID_AGENTS = [(name, list(range(13, 20)) if name == "algo" else vals) for name, vals in GRID]
-GRIDS = ((GRID, FIXTURE), (GRID_AGENTS, AGENTS_FIXTURE))
+# the unassigned 20 and the iLSTD ActorCritic (21), on GRID's other axes
+GRID_AGENTS2 = [(name, [20, 21] if name == "algo" else vals) for name, vals in GRID]
+GRIDS = ((GRID, FIXTURE), (GRID_AGENTS, AGENTS_FIXTURE), (GRID_AGENTS2, AGENTS2_FIXTURE))
 
 
 def sweep(grid=GRID):

@@ -1,0 +1,189 @@
+#!/usr/bin/env python3
+"""Random campaign over the iLSTD ActorCritic (RSRL_ILSTD_ACTOR_CRITIC, 21), in the style of tests/fuzz_agents.py and kept apart from it: every
+register-family Fourier order at random learner counts (ragged waves and lane groups), env offsets, discounts, rates, temperatures, solve rounds,
+episode caps and launch depths.  Legs:
+
+    f64      Handler::handle on random in-bounds transitions (some terminal) for learners 0..M-1, M in {1, a random M < N, N}: learners M..N-1
+             bitwise untouched, up to 8 of the handled learners replayed with tests/tdac_lstd_numpy.py at tests/test_gpu_tdac_lstd.py's bounds
+    critic   the same transitions through an iLSTD ctx (19): theta / A / mu and td_error_out bit for bit
+    self     one uninterrupted train() against random splits with policy queries between them (which must change nothing), the host trait loop,
+             two env_offset shards, and a checkpoint saved and resumed -- bit for bit
+
+    python tests/fuzz_tdac_lstd.py [n_cases=100] [seed=0]          (GPU box; test infrastructure: imports oracle/)
+
+One line per case and a SUMMARY {json} line; exit code 1 on any mismatch."""
+import json
+import os
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import rsrl_amd as ra  # noqa: E402
+from oracle import oracle as orc  # noqa: E402
+from tests.lstd_numpy import near_tie_band  # noqa: E402
+from tests.tdac_lstd_numpy import tdac_lstd_rule  # noqa: E402
+
+REG = [(0, o) for o in (1, 2, 3, 4, 5)] + [(1, 1), (2, 1)]
+EPS64 = np.finfo(np.float64).eps
+
+
+def draw_config(rng):
+    domain, order = REG[int(rng.integers(len(REG)))]
+    N = int(rng.choice([1, 3, 16, 17, 63, 64, 65, int(rng.integers(2, 200))]))
+    return dict(domain=domain, order=order, algo=ra.ILSTD_ACTOR_CRITIC, policy=ra.SOFTMAX, n_envs=N, seed=int(rng.integers(1 << 30)),
+                env_offset=int(rng.choice([0, 0, int(rng.integers(1, 1 << 20))])), gamma=float(rng.uniform(0.8, 0.999)),
+                lr=float(10 ** rng.uniform(-4, -1.3)), alpha=float(10 ** rng.uniform(-3, -0.5)), tau=float(rng.uniform(0.3, 2.0)),
+                n_steps=int(rng.integers(1, 5)), max_episode_steps=int(rng.choice([0, 7, 23, 200])), steps_per_launch=int(rng.choice([0, 0, 1, 5, 64])))
+
+
+def state_of(c):
+    out = [[], [], [], []]
+    for i in range(c.N):
+        for k, x in enumerate(c.get_lstd_state(i) + (c.get_policy_weights(i),)):
+            out[k].append(x)
+    return tuple(np.stack(x) for x in out)
+
+
+def snapshot(c):
+    return state_of(c) + (c.states, c.actions, c.episode_steps)
+
+
+def same(s1, s2):
+    return all(np.shape(x) == np.shape(y) and np.asarray(x).tobytes() == np.asarray(y).tobytes() for x, y in zip(s1, s2))
+
+
+def randomise(c, rng, also=()):
+    F, init = c.F, []
+    for i in range(c.N):
+        theta, M, mu = rng.normal(0.0, 0.5, size=F), rng.normal(0.0, 1.0, size=(F, F)), rng.normal(0.0, 1.0, size=F)
+        A, Th = np.eye(F) + 0.1 * M / np.sqrt(F), rng.normal(0.0, 0.3, size=(F, c.A)).astype(np.float32)
+        for x in (c,) + tuple(also):
+            x.set_lstd_state(theta, A, mu, i)
+        c.set_policy_weights(Th, i)
+        init.append((theta, A, mu, Th))
+    return init
+
+
+def leg_f64(kw, rng):
+    """-> list of failures"""
+    bad = []
+    N = kw["n_envs"]
+    ikw = dict(kw, algo=ra.ILSTD, policy=ra.RANDOM, alpha=kw["lr"])
+    with ra.Context(**kw) as c, ra.Context(**ikw) as v:
+        init = randomise(c, rng, also=(v,))
+        lo, hi = orc.domain_bounds(kw["domain"])
+        c.states = rng.uniform(lo, hi, size=(N, len(lo))).T.astype(np.float32)
+        a = rng.integers(0, c.A, size=N).astype(np.int32)
+        frm, nxt, rew, term = c.domain_step(a)
+        term = (term | (rng.random(N) < 0.25)).astype(np.uint8)
+        M = int(rng.choice([1, N, int(rng.integers(1, N + 1))]))
+        before = state_of(c)
+        sl = (slice(None), slice(0, M))
+        td = c.handle(np.ascontiguousarray(frm[sl]), a[:M], rew[:M], np.ascontiguousarray(nxt[sl]), term[:M])
+        td_v = v.handle(np.ascontiguousarray(frm[sl]), a[:M], rew[:M], np.ascontiguousarray(nxt[sl]), term[:M])
+        after = state_of(c)
+        if not all(x[M:].tobytes() == y[M:].tobytes() for x, y in zip(before, after)):
+            bad.append("learners M..N-1 moved")
+        if td.tobytes() != td_v.tobytes() or any(x.tobytes() != y.tobytes() for i in range(M) for x, y in zip(c.get_lstd_state(i), v.get_lstd_state(i))):
+            bad.append("critic != iLSTD ctx")
+        F = c.F
+        tol = 16.0 * F * (1 + kw["n_steps"]) * EPS64
+        for i in rng.choice(M, size=min(M, 8), replace=False):
+            theta, A, mu, Th = init[i]
+            phi_s, phi_n = orc.fourier_project(kw["domain"], kw["order"], frm[:, i]), orc.fourier_project(kw["domain"], kw["order"], nxt[:, i])
+            mus = []
+            d, th2, A2, mu2, T2 = tdac_lstd_rule(theta, A, mu, Th.astype(np.float64), phi_s, phi_n, int(a[i]), float(rew[i]), bool(term[i]), kw["gamma"],
+                                                 kw["lr"], kw["n_steps"], kw["alpha"], kw["tau"], rounds=mus)
+            if abs(float(td[i]) - d) > 2.0 ** -22 * (1.0 + abs(d)):
+                bad.append(f"delta of learner {i}")
+            if not any(near_tie_band(m) for m in mus):
+                for g, w in zip((after[0][i], after[1][i], after[2][i]), (th2, A2, mu2)):
+                    if np.max(np.abs(g - w)) > tol * (1.0 + np.max(np.abs(w))):
+                        bad.append(f"f64 state of learner {i}")
+            old = Th.astype(np.float64)
+            bound = 3e-6 * (1 + np.max(np.abs(T2 - old))) * np.abs(phi_s).sum() + 3e-6 * np.max(np.abs(old))
+            if np.max(np.abs(after[3][i] - T2)) > bound:
+                bad.append(f"actor of learner {i}")
+    return bad
+
+
+def trait_loop(c, K, cap):
+    ep = c.episode_steps.astype(np.int64)
+    for _ in range(K):
+        frm, nxt, rew, term = c.domain_step(c.actions)
+        c.handle(frm, c.actions, rew, nxt, term)
+        ep += 1
+        mask = term.astype(bool) | ((ep >= cap) if cap > 0 else False)
+        mask = np.asarray(mask, dtype=np.uint8)
+        c.domain_reset(mask)
+        ep[mask == 1] = 0
+        c.policy_sample()
+    c.episode_steps = ep.astype(np.uint32)
+
+
+def leg_self(kw, rng):
+    bad = []
+    K, N, cap = int(rng.integers(5, 40)), kw["n_envs"], kw["max_episode_steps"]
+    with ra.Context(**kw) as c:
+        c.reset()
+        c.train(K)
+        ref = snapshot(c)
+    with ra.Context(**kw) as c:                                      # random splits, policy queries in between
+        c.reset()
+        done = 0
+        while done < K:
+            k = int(rng.integers(1, K - done + 1))
+            c.train(k, want_stats=bool(rng.integers(2)))
+            done += k
+            S = c.states
+            c.policy_probs(S); c.policy_sample(S); c.q_evaluate(S)
+        if not same(snapshot(c), ref):
+            bad.append("splits with queries")
+    with ra.Context(**kw) as c:
+        c.reset()
+        trait_loop(c, K, cap)
+        if not same(snapshot(c), ref):
+            bad.append("trait loop")
+    if N >= 2:
+        h, parts = N // 2, []
+        for off, n in ((0, h), (h, N - h)):
+            with ra.Context(**dict(kw, n_envs=n, env_offset=kw["env_offset"] + off)) as c:
+                c.reset()
+                c.train(K)
+                parts.append(snapshot(c))
+        joined = tuple(np.concatenate([parts[0][j], parts[1][j]], axis=0 if j < 4 else -1) for j in range(7))
+        if not same(joined, ref):
+            bad.append("shards")
+    with tempfile.TemporaryDirectory() as tmp, ra.Context(**kw) as a, ra.Context(**kw) as b:
+        k1 = int(rng.integers(1, K)) if K > 1 else 1
+        a.reset()
+        a.train(k1)
+        path = os.path.join(tmp, "f.ckpt")
+        a.save_weights(path)
+        b.load_weights(path)
+        b.states, b.actions, b.episode_steps = a.states, a.actions, a.episode_steps
+        b.train(K - k1)
+        if K - k1 >= 0 and not same(snapshot(b), ref):
+            bad.append("checkpoint resume")
+    return bad
+
+
+def main():
+    n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
+    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+    rng = np.random.default_rng(seed)
+    fails = 0
+    for case in range(n_cases):
+        kw = draw_config(rng)
+        bad = [("f64", x) for x in leg_f64(kw, rng)] + [("self", x) for x in leg_self(kw, rng)]
+        fails += bool(bad)
+        print(f"case {case}: {'FAIL ' + json.dumps(bad) if bad else 'ok'} {json.dumps(kw)}", flush=True)
+    print("SUMMARY " + json.dumps(dict(cases=n_cases, seed=seed, failed=fails)), flush=True)
+    sys.exit(1 if fails else 0)
+
+
+if __name__ == "__main__":
+    main()
