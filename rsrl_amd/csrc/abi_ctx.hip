@@ -27,6 +27,7 @@ static Switches read_switches() {
     if (const char* e = getenv("RSRL_SPARSE_CHUNK")) { const int v = atoi(e); sw.sparse_chunk = v > 0 && v < 16 ? 16 : v; }
     if (const char* e = getenv("RSRL_PEER_TIMEOUT_MS")) sw.peer_timeout_ms = atol(e);
     if (const char* e = getenv("RSRL_WAVE_PK")) sw.no_wave_pk = e[0] == '0';
+    if (const char* e = getenv("RSRL_REG_PRODUCER")) sw.no_reg_producer = e[0] == '0';
     return sw;
 }
 bool no_coalesce_switch() { return getenv("RSRL_NO_COALESCE") != nullptr; }
@@ -344,6 +345,14 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
         // four lanes per learner (k_step_reg_q4) pays once there is more than one round of one-lane waves to overlap: measured
         // 19.8 vs 21.3 us per launch at 131 072 learners, 32.7 vs 38.0 at 262 144, but 9.8 vs 9.0 at 65 536 (RSRL_K1_QUAD=1 / 0 forces)
         c->k1_quad = c->A <= 3 && (c->sw.k1_quad >= 0 ? c->sw.k1_quad == 1 : N >= 131072);
+    }
+    // the fused loop with a producer wave per SIMD (kernels_reg_pw.hpp): only while the grid is at most one block per CU -- there a SIMD would hold ONE
+    // learner wave, and the partner fills its idle issue slots.  Above it k_train_reg already runs two learner waves per SIMD.  The schedule-free loop
+    // only; RSRL_REG_PRODUCER=0 keeps k_train_reg (A/B, same bits)
+    if (c->family == AgentFamily::RegFused && !c->sw.no_reg_producer && cfg->epsilon_decay == 1.0 && N <= (int64_t)kBlock * c->n_cu) {
+        int lds = 0;
+        HIP_TRY(hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, cfg->device));
+        c->reg_producer = train_reg_pw_serves(cfg->domain, cfg->order, cfg->algo, lds);
     }
     c->train_kernel = train_kernel_name(c);
     c->dw_elems = (size_t)c->Aw * c->F;

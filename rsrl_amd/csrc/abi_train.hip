@@ -424,6 +424,7 @@ int launch_agent(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, uint64_t 
         break;
     case AgentFamily::RegStep: return enqueue_k1_step(c, k, d_stats, t, nullptr);
     case AgentFamily::RegFused:
+        if (c->reg_producer && !k.eps) { ok = launch_train_reg_pw(cf.algo, cf.policy, grid, c->stream, k, t, chunk, d_stats); break; }
         switch (cf.domain) {
         case 0: ok = launch_train_reg_d0(cf.order, cf.algo, cf.policy, grid, block, c->stream, k, t, chunk, d_stats); break;
         case 1: ok = launch_train_reg_d1(cf.order, cf.algo, cf.policy, grid, block, c->stream, k, t, chunk, d_stats); break;

@@ -150,6 +150,7 @@ struct Switches {
     int sparse_chunk = 0;             // RSRL_SPARSE_CHUNK: learners per block of the sparse-trace scatter (0 = one block per CU)
     long peer_timeout_ms = 0;         // RSRL_PEER_TIMEOUT_MS (0 = unset)
     bool no_wave_pk = false;          // RSRL_WAVE_PK=0: bf16 ctxs of the order-7 wave family on the fp32-register kernel k_train_wave
+    bool no_reg_producer = false;     // RSRL_REG_PRODUCER=0: the fused loop keeps generating its own draws (k_train_reg instead of pw::k_train_reg)
 };
 
 struct rsrl_hip_ctx {
@@ -204,6 +205,7 @@ struct rsrl_hip_ctx {
     DevStats* d_stats = nullptr; DevStats* h_stats = nullptr;   // one slot per thread block
     size_t n_stat_slots = 0;
     bool k1_quad = false;                      // single-step streaming kernel with four lanes per learner (k_step_reg_q4)
+    bool reg_producer = false;                 // RegFused: the loop whose draws come from a partner wave per SIMD (pw::k_train_reg), decided at create
     uint64_t t = 0;          // batch-steps executed (RNG counter)
     int64_t pending = 0;     // batch-steps accepted by rsrl_hip_train but not launched yet (launch coalescing, see rsrl_hip_train)
     uint64_t api_calls = 0;  // RNG counter of rsrl_hip_policy_sample
