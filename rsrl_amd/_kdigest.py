@@ -73,8 +73,18 @@ def kernel_digests(lib_path, kernels):
     return out
 
 
+def differing_functions(lib_a, lib_b):
+    """names of the GPU functions whose code bytes differ between two builds of the library, or that only one of them holds"""
+    a, b = ({name: code for elf in _code_objects(open(p, "rb").read()) for name, code in _functions(elf)} for p in (lib_a, lib_b))
+    return sorted(n for n in a.keys() | b.keys() if a.get(n) != b.get(n))
+
+
 if __name__ == "__main__":
     import json
     import sys
     from . import _build
+    if sys.argv[1:2] == ["--against"]:                  # a refactor's check: which kernels' machine code moved against another build
+        diff = differing_functions(sys.argv[2], _build.LIB_PATH)
+        print("\n".join(diff + [f"{len(diff)} GPU functions differ"]))
+        sys.exit(1 if diff else 0)
     print(json.dumps(kernel_digests(_build.LIB_PATH, sys.argv[1:] or ["k_train_reg"]), indent=1))

@@ -159,14 +159,8 @@ int enqueue_shared_c(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, uint6
 // the single-step streaming kernel (register family, steps_per_launch = 1)
 static int enqueue_k1_step(rsrl_hip_ctx* c, const Common& k, DevStats* d_stats, uint64_t t, const uint64_t* t_dev) {
     const dim3 gr(grid_for(k.n_envs)), b(kBlock);
-    bool ok;
     const int kind = c->w_ls != 1 ? (c->k1_quad ? -3 : -2) : -1;              // learner-major rows: k_step_reg_q4 / k_step_reg_lm
-    switch (c->cfg.domain) {
-    case 0: ok = launch_train_reg_d0(c->cfg.order, c->cfg.algo, c->cfg.policy, gr, b, c->stream, k, t, kind, d_stats, t_dev); break;
-    case 1: ok = launch_train_reg_d1(c->cfg.order, c->cfg.algo, c->cfg.policy, gr, b, c->stream, k, t, kind, d_stats, t_dev); break;
-    default: ok = launch_train_reg_d2(c->cfg.order, c->cfg.algo, c->cfg.policy, gr, b, c->stream, k, t, kind, d_stats, t_dev); break;
-    }
-    if (!ok) return NO_MODEL(c);
+    if (!launch_train_reg(c->cfg.domain, c->cfg.order, c->cfg.algo, c->cfg.policy, gr, b, c->stream, k, t, kind, d_stats, t_dev)) return NO_MODEL(c);
     KCHECK();
     return RSRL_HIP_OK;
 }
@@ -425,11 +419,7 @@ int launch_agent(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, uint64_t 
     case AgentFamily::RegStep: return enqueue_k1_step(c, k, d_stats, t, nullptr);
     case AgentFamily::RegFused:
         if (c->reg_producer && !k.eps) { ok = launch_train_reg_pw(cf.algo, cf.policy, grid, c->stream, k, t, chunk, d_stats); break; }
-        switch (cf.domain) {
-        case 0: ok = launch_train_reg_d0(cf.order, cf.algo, cf.policy, grid, block, c->stream, k, t, chunk, d_stats); break;
-        case 1: ok = launch_train_reg_d1(cf.order, cf.algo, cf.policy, grid, block, c->stream, k, t, chunk, d_stats); break;
-        default: ok = launch_train_reg_d2(cf.order, cf.algo, cf.policy, grid, block, c->stream, k, t, chunk, d_stats); break;
-        }
+        ok = launch_train_reg(cf.domain, cf.order, cf.algo, cf.policy, grid, block, c->stream, k, t, chunk, d_stats);
         break;
     case AgentFamily::Generic:
         ok = for_model(c, [&](auto tag) {

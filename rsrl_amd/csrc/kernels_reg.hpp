@@ -412,6 +412,91 @@ __device__ __forceinline__ float expected_value(const float (&q)[A], const float
 // All A columns are written once at the end of the launch (one batch-step per launch is k_step_reg / k_step_reg_lm).
 // ---------------------------------------------------------------------------------------
 
+// One batch-step of the fused loop, for k_train_reg below and pw::k_train_reg (kernels_reg_pw.hpp): the transition, the TD error, the
+// column update, the rank-1 correction of Q(s'), the behaviour sample and the step-cap slow path, on the kernel's own locals.
+// ESCHED: the per-learner epsilon schedule; STATS = false: without the per-step accumulators (|delta|, reward, episode counts).
+// A function that RETURNS the step as a [&] lambda, not a struct of references with a fixed member list: the closure then holds what
+// the instantiation uses and nothing else, in the order the body first uses it (PAL reads c only for the schedule, and then before pol;
+// no accumulators without STATS).  The order in which the kernel's locals become registers follows the closure, and the machine code
+// follows that: every struct tried moved 28 to 160 of the 172 instantiations, this form none (profiles/reg_step_shared.md) -- and the
+// wait-state counts of tests/test_abi_cpu.py pin them.  After an edit here, compare again: python -m rsrl_amd._kdigest --against OLD.so
+// c: the kernel's Common, or a pointer to it that is null where the step reads nothing of it (pw::k_train_reg, see there).
+__device__ __forceinline__ const Common& step_common(const Common& c) { return c; }
+__device__ __forceinline__ const Common& step_common(const Common* c) { return *c; }
+template <int DOMAIN, int ORDER, int ALGO, int POLICY, bool ESCHED, bool STATS, int D, class Pre, int A, int F, bool PK, class C>
+__device__ __forceinline__ auto reg_step(float (&s)[D], int& a, Pre& pre_s, uint32_t& ep, const uint32_t& cap, WBuf<A, F, PK>& w, QCarry& q_s, const AlgoParams& alg,
+                                         PolicyParams& pol, const C& c, float& facc_abs, float& facc_r, uint32_t& n_ep, uint32_t& n_trunc) {
+    using Dom = Domain<DOMAIN>;
+    using Bas = FourierReg<DOMAIN, ORDER>;
+    using Phi = PhiBuf<F, PK>;
+    // x = this batch-step's behaviour-policy draw, xin = the agent's own (SARSA): halves of Philox blocks shared by two steps
+    return [&](const Phi& phi_s, Phi& phi_n, const U4& x, const U4& xin) {
+        // ---- Domain::transition
+        float ns[D];
+#pragma unroll
+        for (int d = 0; d < D; ++d) ns[d] = s[d];
+        float r;
+        const bool term = Dom::step(ns, a, r, pre_s);
+        ep += 1;
+        const bool trunc = !term && cap > 0 && ep >= cap;
+        if (term) Dom::reset(ns);              // select, not a branch: phi/Q of s0 take the s' slot
+        pre_s = Dom::pre(ns);                  // action-independent part of the NEXT transition, off the critical path
+        float q_n[A];
+        { float ph[F]; Bas::project(ns, ph); phi_n.set(ph); }
+        w.q(phi_n, q_n);
+        // ---- handle: delta with the PRE-update weights
+        static_assert(A <= 3, "ActionMask covers three actions");
+        const ActionMask am(a);
+        const float qsa = A > 2 ? bitsel(am.m2, q_s.v2, bitsel(am.m1, q_s.v1, q_s.v0)) : bitsel(am.m1, q_s.v1, q_s.v0);
+        const float q_s_all[3] = {q_s.v0, q_s.v1, q_s.v2};
+        float e;
+        float delta;
+        if constexpr (ALGO == ALG_PAL) {
+            float qs_arr[A];
+#pragma unroll
+            for (int b = 0; b < A; ++b) qs_arr[b] = q_s_all[b];
+            delta = td_error_pal<A>(alg, qs_arr, q_n, a, r, term, e);
+        } else {
+            delta = td_error_ap<A, ALGO>(alg, pol, step_common(c), qsa, q_n, r, term, xin, e);
+        }
+        // ---- Handler<StateActionUpdate>: W[:,a] += lr * e * phi(s)     fa/linear.rs:379-391
+        const float scale = alg.lr * e;
+        {
+            float sb[A];
+#pragma unroll
+            for (int b = 0; b < A; ++b) sb[b] = and_mask(am.of(b), scale);
+            w.axpy(sb, phi_s);
+        }
+        // ---- policy.sample with the UPDATED weights (at s', or at s0 after a terminal transition)
+        {   // W changed by a rank-1 term in column a only: Q_post[a] = Q_pre[a] + scale * <phi(s), phi(s')>
+            const float dot = Phi::dot(phi_s, phi_n);
+#pragma unroll
+            for (int b = 0; b < A; ++b) q_n[b] = bitsel(am.of(b), fmaf(scale, dot, q_n[b]), q_n[b]);
+        }
+        if constexpr (ESCHED) learner_eps_step(step_common(c), term | trunc, pol);        // the episode's last handle is done: its end decays epsilon
+        int na = policy_sample<A, true>(pol, q_n, x);               // (x is a half block: y == z)
+        if constexpr (STATS) {
+            facc_abs += fabsf(delta);
+            facc_r += r;
+            n_ep += term ? 1u : 0u;
+        }
+        ep = term ? 0u : ep;
+        if (__builtin_expect(trunc, 0)) {      // step cap: Q(s') was needed above, now the new episode (no barrier in here: pw's sit between steps)
+            if constexpr (STATS) { n_ep += 1; n_trunc += 1; }
+            ep = 0;
+            Dom::reset(ns);
+            pre_s = Dom::pre(ns);
+            { float ph[F]; Bas::project(ns, ph); phi_n.set(ph); }
+            w.q(phi_n, q_n);
+            na = policy_sample<A, true>(pol, q_n, x);    // the step's one behaviour sample: the same draw (BLK_RESET == BLK_STEP)
+        }
+#pragma unroll
+        for (int d = 0; d < D; ++d) s[d] = ns[d];
+        q_s.set<A>(q_n);
+        a = na;
+    };
+}
+
 // Registers: __launch_bounds__(kBlock, 2) = at most 256 per lane, so a launch of more than 1024 waves (> 65 536 learners) runs
 // TWO waves per SIMD: a lone wave issues one VALU instruction per ~3.4 cycles (packed fma 5.2, v_mad_u64 8, v_cndmask 8.4), two
 // co-resident waves one per 2.7 / 4.8 / 5.9 / 4.3 (profiles/r01_ubench_valu_issue.txt).  The loop itself needs ~225 registers;
@@ -477,68 +562,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_train_reg(Common c, uint64_t t0, 
         // only, places their waits at the first uses INSIDE the loop -- ~19 s_waitcnt per pair of steps that wait for nothing
         __builtin_amdgcn_s_waitcnt(0x0070);          // vmcnt(0) lgkmcnt(0)
 
-        // x = this batch-step's behaviour-policy draw, xin = the agent's own (SARSA): halves of Philox blocks shared by two steps
-        auto one_step = [&](const Phi& phi_s, Phi& phi_n, const U4& x, const U4& xin) {
-            // ---- Domain::transition
-            float ns[D];
-#pragma unroll
-            for (int d = 0; d < D; ++d) ns[d] = s[d];
-            float r;
-            const bool term = Dom::step(ns, a, r, pre_s);
-            ep += 1;
-            const bool trunc = !term && cap > 0 && ep >= cap;
-            if (term) Dom::reset(ns);              // select, not a branch: phi/Q of s0 take the s' slot
-            pre_s = Dom::pre(ns);                  // action-independent part of the NEXT transition, off the critical path
-            float q_n[A];
-            { float ph[F]; Bas::project(ns, ph); phi_n.set(ph); }
-            w.q(phi_n, q_n);
-            // ---- handle: delta with the PRE-update weights
-            static_assert(A <= 3, "ActionMask covers three actions");
-            const ActionMask am(a);
-            const float qsa = A > 2 ? bitsel(am.m2, q_s.v2, bitsel(am.m1, q_s.v1, q_s.v0)) : bitsel(am.m1, q_s.v1, q_s.v0);
-            const float q_s_all[3] = {q_s.v0, q_s.v1, q_s.v2};
-            float e;
-            float delta;
-            if constexpr (ALGO == ALG_PAL) {
-                float qs_arr[A];
-#pragma unroll
-                for (int b = 0; b < A; ++b) qs_arr[b] = q_s_all[b];
-                delta = td_error_pal<A>(alg, qs_arr, q_n, a, r, term, e);
-            } else {
-                delta = td_error_ap<A, ALGO>(alg, pol, c, qsa, q_n, r, term, xin, e);
-            }
-            // ---- Handler<StateActionUpdate>: W[:,a] += lr * e * phi(s)     fa/linear.rs:379-391
-            const float scale = alg.lr * e;
-            {
-                float sb[A];
-#pragma unroll
-                for (int b = 0; b < A; ++b) sb[b] = and_mask(am.of(b), scale);
-                w.axpy(sb, phi_s);
-            }
-            // ---- policy.sample with the UPDATED weights (at s', or at s0 after a terminal transition)
-            {   // W changed by a rank-1 term in column a only: Q_post[a] = Q_pre[a] + scale * <phi(s), phi(s')>
-                const float dot = Phi::dot(phi_s, phi_n);
-#pragma unroll
-                for (int b = 0; b < A; ++b) q_n[b] = bitsel(am.of(b), fmaf(scale, dot, q_n[b]), q_n[b]);
-            }
-            if constexpr (ESCHED) learner_eps_step(c, term | trunc, pol);        // the episode's last handle is done: its end decays epsilon
-            int na = policy_sample<A, true>(pol, q_n, x);               // (x is a half block: y == z)
-            facc_abs += fabsf(delta);
-            facc_r += r;
-            n_ep += term ? 1u : 0u; ep = term ? 0u : ep;
-            if (__builtin_expect(trunc, 0)) {      // step cap: Q(s') was needed above, now the new episode
-                n_ep += 1; n_trunc += 1; ep = 0;
-                Dom::reset(ns);
-                pre_s = Dom::pre(ns);
-                { float ph[F]; Bas::project(ns, ph); phi_n.set(ph); }
-                w.q(phi_n, q_n);
-                na = policy_sample<A, true>(pol, q_n, x);    // the step's one behaviour sample: the same draw (BLK_RESET == BLK_STEP)
-            }
-#pragma unroll
-            for (int d = 0; d < D; ++d) s[d] = ns[d];
-            q_s.set<A>(q_n);
-            a = na;
-        };
+        const auto one_step = reg_step<DOMAIN, ORDER, ALGO, POLICY, ESCHED, true>(s, a, pre_s, ep, cap, w, q_s, alg, pol, c, facc_abs, facc_r, n_ep, n_trunc);
 
         constexpr bool INNER = ALGO == ALG_SARSA;                    // the only agent that draws for itself on this path
         auto single = [&](uint64_t t) {                               // a step outside a pair: its half of the block
