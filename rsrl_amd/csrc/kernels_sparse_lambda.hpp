@@ -13,8 +13,16 @@
 // The sum over learners runs in 64-bit fixed point (lsb = 2^(floor(log2 alpha) - 28), FxScale): exact, order-independent, reproducible.
 //
 // The list.  kSparseCap = 512 entries per learner (the reference's buffer grows without bound), held as T SUB-LISTS, one per tiling, of
-// kSparseCap / T entries each (64 entries per tiling at T = 8: 64 steps that never revisit a tile of that tiling -- by then an accumulating trace
-// has decayed to rate^64).  A key belongs to exactly one tiling (key / (cells * A)), a step brings at most one new key per tiling, and every
+// kSparseCap / T entries each (CAP = 64 per tiling at T = 8, 32 at T = 16).  What the cap costs against the reference's trace z_ref, per (learner, tiling):
+// all three rules are z <- clip?(rate * z + g), g >= 0 -- monotone, a contraction by `rate` -- so with evicted entries read as 0,
+//     0 <= z <= z_ref elementwise,    D = ||z_ref - z||_1:  D' <= rate * D + m,    m = the evicted value <= the CAP-th largest decayed z_ref value
+//                                                                                       of the tiling among the keys other than the step's new one,
+// hence D <= B with B' = rate * B + kth, B = 0 after a reset or a Watkins cut: B follows from z_ref alone (tests/sparse_lambda_numpy.py) and is attained
+// (the f64 oracle reaches D / B = 1.000).  Measured on the device, teacher-forced by the f64 loop with dense traces (tests/test_gpu_sparse_cap.py,
+// profiles/sparse_cap_cost.md), MountainCar SARSA(lambda), eps .3, no step cap -- worst D / ||z_ref||_1 (B / ||z_ref||_1) and max|dW| / max|W| after K steps:
+//     T 8 dutch lambda .97 (64 learners, K 900) 7.5e-4 (2.8e-3), 7.8e-6;   T 16 saturate .95 (77, 500) 2.4e-2 (6.2e-2), 5.1e-4;   T 16 accumulate .95 (32, 400)
+//     1.8e-2 (3.1e-2), 9.1e-5.  While no sub-list fills (CartPole, Acrobot, MountainCar at T = 4) B is 0 and the lists ARE the reference's trace to fp32 rounding:
+//     every entry within 0.41 of u(z) = 2 * 2^-23 / (1 - rate) * max(1, z_ref), max|dW| <= 1.6e-6 max|W|.  A key belongs to exactly one tiling (key / (cells * A)), a step brings at most one new key per tiling, and every
 // operation on the trace -- decay, hit, append, evict, the learner's terms, reset -- acts on the tilings independently.  So the unit of work is
 // (learner, tiling), and the trace update runs INSIDE the scatter kernel that already owns a tiling's slice of the delta table in LDS:
 //
