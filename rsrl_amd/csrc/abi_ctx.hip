@@ -32,7 +32,8 @@ static Switches read_switches() {
 }
 bool no_coalesce_switch() { return getenv("RSRL_NO_COALESCE") != nullptr; }
 
-// the kernel family of a validated configuration (ctx.hpp AgentFamily), first match in the order of the enum.  w_elems: the ctx's weight count
+// the kernel family of a validated configuration (ctx.hpp AgentFamily), first match in the order of the enum.  w_elems: the ctx's weight count.
+// A decision, so a function; what a family IS stands in ctx.hpp's kFamily, the other place (with launch_agent) a new family is entered
 static AgentFamily classify(const rsrl_hip_config& cfg, size_t w_elems) {
     using F = AgentFamily;
     const bool fourier = cfg.basis == RSRL_FOURIER, tile = cfg.basis == RSRL_TILE_CODING;
@@ -57,34 +58,30 @@ static AgentFamily classify(const rsrl_hip_config& cfg, size_t w_elems) {
 }
 // what rsrl_hip_timing_read names after a driver-loop launch of the family (the persistent kernel and the trait-granular kernels name themselves)
 static const char* train_kernel_name(const rsrl_hip_ctx* c) {
-    switch (c->family) {
-    case AgentFamily::SharedDense: return "k_shared_step";
-    case AgentFamily::SharedTile: return "k_shared_ca";
-    case AgentFamily::SharedSparseLambda: return "k_sparse_trace_scatter";
-    case AgentFamily::WaveAux: return "k_wave_aux";
-    case AgentFamily::TdTile: return "k_td_tile";
-    case AgentFamily::TdGeneric: return "k_td_mem";
-    case AgentFamily::TdReg: return "k_train_td";
-    case AgentFamily::WaveQSigma: return "k_wave_qsigma";
-    case AgentFamily::QSigmaReg: case AgentFamily::QSigmaGeneric: return "k_train_qsigma";
-    case AgentFamily::GqReg: return "k_train_gq";
-    case AgentFamily::GqGeneric: return "k_train_gq_mem";
-    case AgentFamily::LambdaTile: return "k_lambda_tile";
-    case AgentFamily::WaveLambda: return "k_wave_lambda";
-    case AgentFamily::LambdaGeneric: return "k_train_lambda_mem";
-    case AgentFamily::LambdaReg: return "k_train_lambda";
-    case AgentFamily::WaveControl: return c->cfg.weight_dtype == RSRL_W_BF16 && !c->sw.no_wave_pk ? "k_train_wave_pk" : "k_train_wave";
-    case AgentFamily::RegStep: return c->w_ls != 1 ? (c->k1_quad ? "k_step_reg_q4" : "k_step_reg_lm") : "k_step_reg";
-    case AgentFamily::RegFused: return "k_train_reg";
-    case AgentFamily::Generic: return "k_train_mem";
-    case AgentFamily::Hiv: return "k_hiv_train";
-    case AgentFamily::AcReg: return "k_train_ac";
-    case AgentFamily::TdAcReg: return "k_train_tdac";
-    case AgentFamily::ReinforceReg: return "k_train_reinforce";
-    case AgentFamily::LstdReg: return "k_train_lstd";
-    case AgentFamily::TdAcLstdReg: return "k_train_tdac_lstd";
+    // (the two families whose kernel the configuration refines; every other name is the family's row of kFamily)
+    if (c->family == AgentFamily::WaveControl && c->cfg.weight_dtype == RSRL_W_BF16 && !c->sw.no_wave_pk) return "k_train_wave_pk";
+    if (c->family == AgentFamily::RegStep && c->w_ls != 1) return c->k1_quad ? "k_step_reg_q4" : "k_step_reg_lm";
+    return family_row(c).kernel;
+}
+// one statistics slot per thread block of the family's driver-loop kernel
+static size_t stat_slots(Slots geometry, int64_t N, int F) {
+    switch (geometry) {
+    case Slots::Block: return grid_for(N);
+    case Slots::Block64: return (size_t)((N + 63) / 64);
+    case Slots::WaveBlock: return wave_grid_for(N);
+    case Slots::Learner: return (size_t)N;
+    case Slots::LstdGroup: return (size_t)((N * lstd_group_lanes(F) + kBlock - 1) / kBlock);      // k_train_lstd: G lanes per learner
     }
-    return "";
+    return 0;
+}
+// THE owner of the device buffers create_impl allocates: allocated, zero-filled on the ctx's stream if asked, and recorded for rsrl_hip_destroy -- the
+// MEMBER, not its value: rsrl_hip_load_weights switches W, Z, sp_keys and sp_vals to shadow copies and frees the old ones itself
+template <class T>
+static int ctx_alloc(rsrl_hip_ctx* c, T** member, size_t bytes, bool zero = false) {
+    HIP_TRY(hipMalloc((void**)member, bytes));
+    c->owned.push_back((void**)member);
+    if (zero) HIP_TRY(hipMemsetAsync(*member, 0, bytes, c->stream));
+    return RSRL_HIP_OK;
 }
 
 RSRL_API_BEGIN
@@ -123,47 +120,17 @@ int rsrl_hip_destroy(rsrl_hip_ctx* c) {
     if (c->tp.stage) (void)trait_flush(c);       // trait calls accepted but not launched: the caller's arrays are still written
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (auto& ev : c->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
-    for (auto& s : c->scratch) if (s.p) (void)hipFree(s.p);
-    if (c->state) (void)hipFree(c->state);
-    if (c->action) (void)hipFree(c->action);
-    if (c->ep_step) (void)hipFree(c->ep_step);
-    if (c->W) (void)hipFree(c->W);
-    if (c->dW) (void)hipFree(c->dW);
-    if (c->dW_rep) (void)hipFree(c->dW_rep);
-    if (c->sh_tab) (void)hipFree(c->sh_tab);
-    if (c->h_fx) (void)hipFree(c->h_fx);
-    if (c->sc_keys) (void)hipFree(c->sc_keys);
-    if (c->sc_terms) (void)hipFree(c->sc_terms);
-    if (c->W2) (void)hipFree(c->W2);
-    if (c->qs_buf) (void)hipFree(c->qs_buf);
-    if (c->qs_head) (void)hipFree(c->qs_head);
-    if (c->qs_len) (void)hipFree(c->qs_len);
     if (c->step_graph_exec) (void)hipGraphExecDestroy(c->step_graph_exec);
     if (c->step_graph) (void)hipGraphDestroy(c->step_graph);
-    if (c->d_t) (void)hipFree(c->d_t);
-    if (c->d_dyn) (void)hipFree(c->d_dyn);
-    if (c->qcache) (void)hipFree(c->qcache);
-    if (c->tq_key) (void)hipFree(c->tq_key);
-    if (c->tq_q) (void)hipFree(c->tq_q);
-    if (c->Z) (void)hipFree(c->Z);
-    if (c->Zb) (void)hipFree(c->Zb);
-    if (c->ret_g) (void)hipFree(c->ret_g);
-    if (c->lstd_theta) (void)hipFree(c->lstd_theta);
-    if (c->lstd_mat) (void)hipFree(c->lstd_mat);
-    if (c->lstd_mu) (void)hipFree(c->lstd_mu);
-    if (c->hiv_y) (void)hipFree(c->hiv_y);
-    if (c->eps) (void)hipFree(c->eps);
-    if (c->flags) (void)hipFree(c->flags);
-    if (c->sp_keys) (void)hipFree(c->sp_keys);
-    if (c->sp_vals) (void)hipFree(c->sp_vals);
-    if (c->sp_len) (void)hipFree(c->sp_len);
-    if (c->d_stats) (void)hipFree(c->d_stats);
+    for (void** member : c->owned) if (*member) (void)hipFree(*member);      // everything create_impl allocated (ctx_alloc)
+    // what has a lifetime of its own: the staging slots, the pinned statistics, the communicator, the peer exchange's and the persistent kernel's buffers
+    // (abi_group.hip, ensure_persist_buffers)
+    for (auto& s : c->scratch) if (s.p) (void)hipFree(s.p);
     if (c->h_stats) (void)hipHostFree(c->h_stats);
     if (c->comm) (void)ncclCommDestroy(c->comm);
     for (size_t r = 0; r < c->peer_ptrs.size(); ++r) if (c->peer_opened[r] && c->peer_ptrs[r]) (void)hipIpcCloseMemHandle(c->peer_ptrs[r]);
     if (c->peer_recv) (void)hipFree(c->peer_recv);
     if (c->d_peer_ptrs) (void)hipFree(c->d_peer_ptrs);
-    if (c->d_peer_err) (void)hipFree(c->d_peer_err);
     if (c->px_A) (void)hipFree(c->px_A);
     if (c->px_B && c->px_B_owned) (void)hipFree(c->px_B);
     if (c->d_px_Bptrs) (void)hipFree(c->d_px_Bptrs);
@@ -173,19 +140,34 @@ int rsrl_hip_destroy(rsrl_hip_ctx* c) {
     return RSRL_HIP_OK;
 }
 
+// The agents that exist only on the register-family Fourier orders with per-learner f32 weights (train_ac.hip, train_tdac.hip, train_reinforce.hip,
+// train_lstd.hip, train_tdac_lstd.hip): the policy is the agent's own -- the Gibbs actor / policy, or the prediction agents' Random behaviour -- and the
+// critic shares it; iLSTD's n_updates travel as config.n_steps.  `storage`: register-family order, per-learner f32 weights, no epsilon schedule
+static int check_reg_only(const rsrl_hip_config& cfg, const AlgoRow& a, bool storage) {
+    if (!storage || cfg.policy != a.reg_policy || cfg.agent_policy != -1)
+        return fail(RSRL_HIP_EINVAL, "%s supports per-learner f32 weights on the register-family Fourier orders (MountainCar 1-5, CartPole 1, Acrobot 1) "
+                                     "with policy = %s%s, agent_policy = -1%s and no epsilon schedule (got domain %d, basis %d, order %d, weight mode %d, "
+                                     "dtype %d, policy %d, agent_policy %d, epsilon_decay %g)",
+                    a.name, a.reg_policy == RSRL_SOFTMAX ? "Softmax" : "Random", a.policy_words, a.shares_words,
+                    cfg.domain, cfg.basis, cfg.order, cfg.weight_mode, cfg.weight_dtype, cfg.policy, cfg.agent_policy, cfg.epsilon_decay);
+    if (a.n_updates && (cfg.n_steps < 1 || cfg.n_steps > 32))
+        return fail(RSRL_HIP_EINVAL, "%s: n_steps (%sn_updates, the rounds of solve() per transition) must be in [1, 32], got %d", a.name, a.n_updates, cfg.n_steps);
+    return RSRL_HIP_OK;
+}
+
 // (state dimension, action count) of MountainCar, CartPole, Acrobot, HIVTreatment
 static const int kDomainShape[4][2] = {{2, 3}, {4, 2}, {4, 3}, {6, 4}};
 
 // admission: every rule that needs no device (a refused configuration is EINVAL on any machine, with or without a GPU).  create_impl checks
 // two more once the device is known: peer_timeout_ms, and the slice of a shared tile table with sparse traces.  The second section states
-// which kernels exist, one block per agent group; ActorCritic and HIVTreatment are whole rules of their own.
+// which kernels exist, one block per agent group; the register-family-only agents (check_reg_only) and HIVTreatment are whole rules of their own.
 static int check_config(const rsrl_hip_config& cfg) {
     // ---- field ranges
     if (cfg.domain < RSRL_MOUNTAIN_CAR || cfg.domain > RSRL_HIV_TREATMENT) return fail(RSRL_HIP_EINVAL, "unknown domain %d", cfg.domain);
     const int D = kDomainShape[cfg.domain][0], A = kDomainShape[cfg.domain][1];
     if (cfg.n_envs < 1) return fail(RSRL_HIP_EINVAL, "n_envs must be >= 1");
     if (cfg.n_envs + cfg.env_offset > (int64_t)0xffffffffLL || cfg.env_offset < 0) return fail(RSRL_HIP_EINVAL, "global env ids must fit 32 bits");
-    if (cfg.algo < 0 || cfg.algo > RSRL_ILSTD_ACTOR_CRITIC || cfg.algo == 12 || cfg.algo == 14 || cfg.algo == 17 || cfg.algo == 20) return fail(RSRL_HIP_EINVAL, "unknown algo %d", cfg.algo);
+    if (cfg.algo < 0 || cfg.algo > RSRL_ILSTD_ACTOR_CRITIC || !kAlgo[cfg.algo].name) return fail(RSRL_HIP_EINVAL, "unknown algo %d", cfg.algo);
     if (cfg.policy < 0 || cfg.policy > RSRL_RANDOM) return fail(RSRL_HIP_EINVAL, "unknown policy %d", cfg.policy);
     // Softmax::new panics for |tau| < 1e-7 (policies/softmax.rs:63-66)
     if (cfg.policy == RSRL_SOFTMAX && std::fabs(cfg.tau) < 1e-7) return fail(RSRL_HIP_EINVAL, "Tau parameter in Softmax must be non-zero.");
@@ -223,59 +205,8 @@ static int check_config(const rsrl_hip_config& cfg) {
     const int al = cfg.algo;
     const bool tile = cfg.basis == RSRL_TILE_CODING, reg = is_reg_fourier(cfg), wave = is_wave(cfg);
     const bool f32 = cfg.weight_dtype == RSRL_W_F32, esched = cfg.epsilon_decay != 1.0;
-    const bool one_step = al == RSRL_QLEARNING || al == RSRL_SARSA || al == RSRL_EXPECTED_SARSA || al == RSRL_PAL;
-    if (is_ac(al)) {
-        // train_ac.hip: per-learner f32 weights on the register-family Fourier orders; the Gibbs actor is the behaviour policy and the critic's
-        if (!reg || !per_env || !f32 || cfg.policy != RSRL_SOFTMAX || cfg.agent_policy != -1 || esched)
-            return fail(RSRL_HIP_EINVAL, "ActorCritic supports per-learner f32 weights on the register-family Fourier orders (MountainCar 1-5, CartPole 1, "
-                                         "Acrobot 1) with policy = Softmax (the Gibbs actor), agent_policy = -1 (the critic shares the actor) and no epsilon "
-                                         "schedule (got domain %d, basis %d, order %d, weight mode %d, dtype %d, policy %d, agent_policy %d, epsilon_decay %g)",
-                        cfg.domain, cfg.basis, cfg.order, cfg.weight_mode, cfg.weight_dtype, cfg.policy, cfg.agent_policy, cfg.epsilon_decay);
-        return RSRL_HIP_OK;
-    }
-    if (is_tdac(al)) {
-        // train_tdac.hip: the same configurations as ActorCritic's
-        if (!reg || !per_env || !f32 || cfg.policy != RSRL_SOFTMAX || cfg.agent_policy != -1 || esched)
-            return fail(RSRL_HIP_EINVAL, "the TD ActorCritic (RSRL_TD_ACTOR_CRITIC) supports per-learner f32 weights on the register-family Fourier orders "
-                                         "(MountainCar 1-5, CartPole 1, Acrobot 1) with policy = Softmax (the Gibbs actor), agent_policy = -1 and no epsilon "
-                                         "schedule (got domain %d, basis %d, order %d, weight mode %d, dtype %d, policy %d, agent_policy %d, epsilon_decay %g)",
-                        cfg.domain, cfg.basis, cfg.order, cfg.weight_mode, cfg.weight_dtype, cfg.policy, cfg.agent_policy, cfg.epsilon_decay);
-        return RSRL_HIP_OK;
-    }
-    if (is_reinforce(al)) {
-        // train_reinforce.hip: the same configurations as ActorCritic's
-        if (!reg || !per_env || !f32 || cfg.policy != RSRL_SOFTMAX || cfg.agent_policy != -1 || esched)
-            return fail(RSRL_HIP_EINVAL, "%s supports per-learner f32 weights on the register-family Fourier orders (MountainCar 1-5, CartPole 1, Acrobot 1) "
-                                         "with policy = Softmax (the Gibbs policy), agent_policy = -1 and no epsilon schedule (got domain %d, basis %d, order %d, "
-                                         "weight mode %d, dtype %d, policy %d, agent_policy %d, epsilon_decay %g)",
-                        al == RSRL_REINFORCE ? "REINFORCE (RSRL_REINFORCE)" : "BaselineREINFORCE (RSRL_BASELINE_REINFORCE)",
-                        cfg.domain, cfg.basis, cfg.order, cfg.weight_mode, cfg.weight_dtype, cfg.policy, cfg.agent_policy, cfg.epsilon_decay);
-        return RSRL_HIP_OK;
-    }
-    if (is_lstd(al)) {
-        // train_lstd.hip: the prediction agents' configurations (Random behaviour) on the register-family Fourier orders
-        const char* name = al == RSRL_RECURSIVE_LSTD ? "RecursiveLSTD (RSRL_RECURSIVE_LSTD)" : "iLSTD (RSRL_ILSTD)";
-        if (!reg || !per_env || !f32 || cfg.policy != RSRL_RANDOM || cfg.agent_policy != -1 || esched)
-            return fail(RSRL_HIP_EINVAL, "%s supports per-learner f32 weights on the register-family Fourier orders (MountainCar 1-5, CartPole 1, Acrobot 1) "
-                                         "with policy = Random, agent_policy = -1 and no epsilon schedule (got domain %d, basis %d, order %d, weight mode %d, "
-                                         "dtype %d, policy %d, agent_policy %d, epsilon_decay %g)",
-                        name, cfg.domain, cfg.basis, cfg.order, cfg.weight_mode, cfg.weight_dtype, cfg.policy, cfg.agent_policy, cfg.epsilon_decay);
-        if (al == RSRL_ILSTD && (cfg.n_steps < 1 || cfg.n_steps > 32))
-            return fail(RSRL_HIP_EINVAL, "%s: n_steps (n_updates, the rounds of solve() per transition) must be in [1, 32], got %d", name, cfg.n_steps);
-        return RSRL_HIP_OK;
-    }
-    if (is_tdac_lstd(al)) {
-        // train_tdac_lstd.hip: the TD ActorCritic's configurations; n_steps is the critic's n_updates
-        const char* name = "the iLSTD ActorCritic (RSRL_ILSTD_ACTOR_CRITIC)";
-        if (!reg || !per_env || !f32 || cfg.policy != RSRL_SOFTMAX || cfg.agent_policy != -1 || esched)
-            return fail(RSRL_HIP_EINVAL, "%s supports per-learner f32 weights on the register-family Fourier orders (MountainCar 1-5, CartPole 1, Acrobot 1) "
-                                         "with policy = Softmax (the Gibbs actor), agent_policy = -1 and no epsilon schedule (got domain %d, basis %d, order %d, "
-                                         "weight mode %d, dtype %d, policy %d, agent_policy %d, epsilon_decay %g)",
-                        name, cfg.domain, cfg.basis, cfg.order, cfg.weight_mode, cfg.weight_dtype, cfg.policy, cfg.agent_policy, cfg.epsilon_decay);
-        if (cfg.n_steps < 1 || cfg.n_steps > 32)
-            return fail(RSRL_HIP_EINVAL, "%s: n_steps (the critic's n_updates, the rounds of solve() per transition) must be in [1, 32], got %d", name, cfg.n_steps);
-        return RSRL_HIP_OK;
-    }
+    const bool one_step = kAlgo[al].agent == Agent::OneStep;
+    if (kAlgo[al].reg_policy >= 0) return check_reg_only(cfg, kAlgo[al], reg && per_env && f32 && !esched);
     if (cfg.domain == RSRL_HIV_TREATMENT) {
         // train_hiv.hip: the one-step agents over the Fourier basis of order 1-3, per-learner f32 weights, one epsilon for the ctx
         if (!one_step || tile || cfg.order > 3 || !per_env || !f32 || esched)
@@ -333,7 +264,8 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
     const int64_t N = cfg->n_envs;
     const bool shared = cfg->weight_mode == RSRL_W_SHARED;
     c->w_stride = shared ? 1 : N;
-    c->Aw = (is_pred(cfg->algo) || is_tdac(cfg->algo) || is_lstd(cfg->algo) || is_tdac_lstd(cfg->algo)) ? 1 : c->A;         // (the TD / iLSTD ActorCritic's weights are V's)
+    const AlgoRow& agent = kAlgo[cfg->algo];
+    c->Aw = agent.v ? 1 : c->A;
     c->w_elems = (size_t)c->Aw * c->F * (size_t)(shared ? 1 : N);
     c->family = classify(*cfg, c->w_elems);
     // a ctx that steps one batch-step per launch streams W every step: learner-major rows (W[N][A][F]) let k_step_reg_lm
@@ -356,38 +288,27 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
     }
     c->train_kernel = train_kernel_name(c);
     c->dw_elems = (size_t)c->Aw * c->F;
-    // one statistics slot per thread block
-    switch (c->family) {
-    case AgentFamily::WaveAux: case AgentFamily::WaveQSigma: case AgentFamily::WaveLambda: case AgentFamily::WaveControl: c->n_stat_slots = wave_grid_for(N); break;
-    case AgentFamily::TdTile: case AgentFamily::LambdaTile: case AgentFamily::SharedSparseLambda: c->n_stat_slots = (size_t)N; break;      // (a block per learner)
-    case AgentFamily::LambdaGeneric: c->n_stat_slots = (size_t)((N + 63) / 64); break;                  // k_train_lambda_mem4: 64 learners per block
-    case AgentFamily::LstdReg: case AgentFamily::TdAcLstdReg: c->n_stat_slots = (size_t)((N * lstd_group_lanes(c->F) + kBlock - 1) / kBlock); break;      // k_train_lstd: G lanes per learner
-    default: c->n_stat_slots = c->k1_quad ? (size_t)((N + 63) / 64) : grid_for(N); break;
-    }
-    HIP_TRY(hipMalloc((void**)&c->state, sizeof(float) * c->D * (size_t)N));
-    HIP_TRY(hipMalloc((void**)&c->action, sizeof(int32_t) * (size_t)N));
-    HIP_TRY(hipMalloc((void**)&c->ep_step, sizeof(uint32_t) * (size_t)N));
+    c->n_stat_slots = stat_slots(c->k1_quad ? Slots::Block64 : family_row(c).slots, N, c->F);
+    TRY(ctx_alloc(c, &c->state, sizeof(float) * c->D * (size_t)N));
+    TRY(ctx_alloc(c, &c->action, sizeof(int32_t) * (size_t)N));
+    TRY(ctx_alloc(c, &c->ep_step, sizeof(uint32_t) * (size_t)N));
     c->w_bytes = c->w_elems * (cfg->weight_dtype == RSRL_W_BF16 ? 2 : 4);
-    HIP_TRY(hipMalloc((void**)&c->W, c->w_bytes));
-    HIP_TRY(hipMalloc((void**)&c->dW, sizeof(float) * c->dw_elems));
-    HIP_TRY(hipMalloc((void**)&c->qcache, sizeof(float) * c->A * (size_t)N));
-    if (cfg->domain == RSRL_HIV_TREATMENT) HIP_TRY(hipMalloc((void**)&c->hiv_y, sizeof(double) * 6 * (size_t)N));      // (set by the domain reset of create)
+    TRY(ctx_alloc(c, &c->W, c->w_bytes));
+    TRY(ctx_alloc(c, &c->dW, sizeof(float) * c->dw_elems));
+    TRY(ctx_alloc(c, &c->qcache, sizeof(float) * c->A * (size_t)N));
+    if (cfg->domain == RSRL_HIV_TREATMENT) TRY(ctx_alloc(c, &c->hiv_y, sizeof(double) * 6 * (size_t)N));      // (set by the domain reset of create)
     // the trait-granular fast path: learner-major per-learner f32 weights on a basis / agent kernels_trait.hpp is instantiated for, one epsilon for the ctx
     if (c->w_ls != 1 && cfg->weight_dtype == RSRL_W_F32 && cfg->epsilon_decay == 1.0 && trait_lm_available(cfg->domain, cfg->order, cfg->algo)) {
-        HIP_TRY(hipMalloc((void**)&c->tq_key, sizeof(float) * c->D * (size_t)N));
-        HIP_TRY(hipMalloc((void**)&c->tq_q, sizeof(float) * c->A * (size_t)N));
+        TRY(ctx_alloc(c, &c->tq_key, sizeof(float) * c->D * (size_t)N));
+        TRY(ctx_alloc(c, &c->tq_q, sizeof(float) * c->A * (size_t)N));
     }
-    if (cfg->algo == RSRL_Q_SIGMA) {
-        const size_t nf = (size_t)(c->D + 5) * (size_t)cfg->n_steps * (size_t)N;
-        HIP_TRY(hipMalloc((void**)&c->qs_buf, sizeof(float) * nf));
-        HIP_TRY(hipMalloc((void**)&c->qs_head, sizeof(uint32_t) * (size_t)N));
-        HIP_TRY(hipMalloc((void**)&c->qs_len, sizeof(uint32_t) * (size_t)N));
-        HIP_TRY(hipMemsetAsync(c->qs_buf, 0, sizeof(float) * nf, c->stream));
-        HIP_TRY(hipMemsetAsync(c->qs_head, 0, sizeof(uint32_t) * (size_t)N, c->stream));
-        HIP_TRY(hipMemsetAsync(c->qs_len, 0, sizeof(uint32_t) * (size_t)N, c->stream));          // Backup::new: empty
+    if (cfg->algo == RSRL_Q_SIGMA) {                                                  // Backup::new: empty
+        TRY(ctx_alloc(c, &c->qs_buf, sizeof(float) * (size_t)(c->D + 5) * (size_t)cfg->n_steps * (size_t)N, true));
+        TRY(ctx_alloc(c, &c->qs_head, sizeof(uint32_t) * (size_t)N, true));
+        TRY(ctx_alloc(c, &c->qs_len, sizeof(uint32_t) * (size_t)N, true));
     }
     if (cfg->epsilon_decay != 1.0) {
-        HIP_TRY(hipMalloc((void**)&c->eps, sizeof(float) * (size_t)N));
+        TRY(ctx_alloc(c, &c->eps, sizeof(float) * (size_t)N));
         hipLaunchKernelGGL(k_fill_f32, dim3(grid_for(N)), dim3(kBlock), 0, c->stream, c->eps, N, (float)cfg->epsilon);
         KCHECK();
     }
@@ -395,54 +316,42 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
         const int64_t slice = (int64_t)(c->F / cfg->n_tilings) * c->A;
         if (slice > 65536) return fail(RSRL_HIP_EINVAL, "SARSALambda / QLambda over a shared tile table: one tiling's slice (cells * actions = %lld entries) must not "
                                                         "exceed 65 536 (16-bit slice-relative keys between the step and the trace kernel)", (long long)slice);
-        HIP_TRY(hipMalloc((void**)&c->sp_keys, sizeof(uint16_t) * (size_t)kSparseCap * (size_t)N));
-        HIP_TRY(hipMalloc((void**)&c->sp_vals, sizeof(float) * (size_t)kSparseCap * (size_t)N));
-        HIP_TRY(hipMalloc((void**)&c->sp_len, sizeof(uint32_t) * (size_t)cfg->n_tilings * (size_t)N));
-        HIP_TRY(hipMemsetAsync(c->sp_len, 0, sizeof(uint32_t) * (size_t)cfg->n_tilings * (size_t)N, c->stream));        // Trace::zeros: empty lists
+        TRY(ctx_alloc(c, &c->sp_len, sizeof(uint32_t) * (size_t)cfg->n_tilings * (size_t)N, true));        // Trace::zeros: empty lists
         // (the lists are written only below their lengths; what lies beyond is never read as an entry, but a checkpoint copies whole rows)
-        HIP_TRY(hipMemsetAsync(c->sp_keys, 0, sizeof(uint16_t) * (size_t)kSparseCap * (size_t)N, c->stream));
-        HIP_TRY(hipMemsetAsync(c->sp_vals, 0, sizeof(float) * (size_t)kSparseCap * (size_t)N, c->stream));
+        TRY(ctx_alloc(c, &c->sp_keys, sizeof(uint16_t) * (size_t)kSparseCap * (size_t)N, true));
+        TRY(ctx_alloc(c, &c->sp_vals, sizeof(float) * (size_t)kSparseCap * (size_t)N, true));
         c->sp_lds = slice * 8 <= 128 * 1024;
         if (c->sp_lds && slice * 8 > 64 * 1024) c->sp_lds = sparse_trace_scatter_allow_lds(cfg->n_tilings, (int)(slice * 8));      // more dynamic LDS than a kernel gets by default
-    } else if (has_aux(cfg->algo) || is_v_actor_critic(c)) {
-        c->z_bytes = (is_v_actor_critic(c) ? (size_t)aux_cols(c) * c->F * (size_t)N : c->w_elems) * 4;      // (TdAcReg / TdAcLstdReg: theta, A columns)
-        HIP_TRY(hipMalloc((void**)&c->Z, c->z_bytes));
-        HIP_TRY(hipMemsetAsync(c->Z, 0, c->z_bytes, c->stream));                  // Trace::zeros (ActorCritic's theta: LFA::vector zero-initialises)
-    } else if (c->family == AgentFamily::ReinforceReg) {
-        // theta (Z) and theta_b (Zb) of W's shape, both zero (LFA::vector); g = 0.  W is the baseline B (REINFORCE: allocated, never read)
-        c->z_bytes = c->w_elems * 4;
-        HIP_TRY(hipMalloc((void**)&c->Z, c->z_bytes));
-        HIP_TRY(hipMemsetAsync(c->Z, 0, c->z_bytes, c->stream));
-        HIP_TRY(hipMalloc((void**)&c->Zb, c->z_bytes));
-        HIP_TRY(hipMemsetAsync(c->Zb, 0, c->z_bytes, c->stream));
-        HIP_TRY(hipMalloc((void**)&c->ret_g, sizeof(float) * (size_t)N));
-        HIP_TRY(hipMemsetAsync(c->ret_g, 0, sizeof(float) * (size_t)N, c->stream));
+    } else if (agent.aux != Aux::None) {
+        // Trace::zeros; the policy's theta (LFA::vector zero-initialises): of W's shape, or A columns next to V's one
+        c->z_bytes = (agent.aux == Aux::Policy ? (size_t)c->A * c->F * (size_t)N : c->w_elems) * 4;
+        TRY(ctx_alloc(c, &c->Z, c->z_bytes, true));
     }
-    if (has_lstd_state(c)) {
+    if (agent.episode) {      // REINFORCE: theta_b of theta's shape, zero as it is; g = 0
+        TRY(ctx_alloc(c, &c->Zb, c->z_bytes, true));
+        TRY(ctx_alloc(c, &c->ret_g, sizeof(float) * (size_t)N, true));
+    }
+    if (agent.lstd) {
         // theta = 0; RecursiveLSTD: C = 1e-5 I; iLSTD (the iLSTD ActorCritic's critic too): A = I, mu = 0 (recursive_lstd.rs:24-33, ilstd.rs:27-40)
         const size_t nv = (size_t)c->F * (size_t)N, nm = nv * (size_t)c->F;
-        HIP_TRY(hipMalloc((void**)&c->lstd_theta, sizeof(double) * nv));
-        HIP_TRY(hipMemsetAsync(c->lstd_theta, 0, sizeof(double) * nv, c->stream));
-        HIP_TRY(hipMalloc((void**)&c->lstd_mat, sizeof(double) * nm));
+        TRY(ctx_alloc(c, &c->lstd_theta, sizeof(double) * nv, true));
+        TRY(ctx_alloc(c, &c->lstd_mat, sizeof(double) * nm));
         launch_lstd_fill_eye(c->stream, c->lstd_mat, (int64_t)nm, c->F, cfg->algo == RSRL_RECURSIVE_LSTD ? 1e-5 : 1.0);
         KCHECK();
-        if (cfg->algo != RSRL_RECURSIVE_LSTD) {
-            HIP_TRY(hipMalloc((void**)&c->lstd_mu, sizeof(double) * nv));
-            HIP_TRY(hipMemsetAsync(c->lstd_mu, 0, sizeof(double) * nv, c->stream));
-        }
+        if (cfg->algo != RSRL_RECURSIVE_LSTD) TRY(ctx_alloc(c, &c->lstd_mu, sizeof(double) * nv, true));
     }
     if (shared) {
-        HIP_TRY(hipMalloc((void**)&c->flags, (size_t)N));
+        TRY(ctx_alloc(c, &c->flags, (size_t)N));
         if (c->family == AgentFamily::SharedDense) {
             c->sh_rows = (unsigned)((N + kSharedBlock - 1) / kSharedBlock);
-            HIP_TRY(hipMalloc((void**)&c->sh_tab, sizeof(long long) * 3 * kTabRep * c->dw_elems));
+            TRY(ctx_alloc(c, &c->sh_tab, sizeof(long long) * 3 * kTabRep * c->dw_elems));
             HIP_TRY(hipMemset(c->sh_tab, 0, sizeof(long long) * 3 * kTabRep * c->dw_elems));
-            HIP_TRY(hipMalloc((void**)&c->W2, c->w_bytes));
+            TRY(ctx_alloc(c, &c->W2, c->w_bytes));
         }
     }
-    HIP_TRY(hipMalloc((void**)&c->d_stats, sizeof(DevStats) * c->n_stat_slots));
-    HIP_TRY(hipMalloc((void**)&c->d_t, sizeof(uint64_t)));
-    HIP_TRY(hipMalloc((void**)&c->d_dyn, sizeof(DynParams)));
+    TRY(ctx_alloc(c, &c->d_stats, sizeof(DevStats) * c->n_stat_slots));
+    TRY(ctx_alloc(c, &c->d_t, sizeof(uint64_t)));
+    TRY(ctx_alloc(c, &c->d_dyn, sizeof(DynParams)));
     HIP_TRY(hipHostMalloc((void**)&c->h_stats, sizeof(DevStats) * c->n_stat_slots, hipHostMallocDefault));
     HIP_TRY(hipMemsetAsync(c->W, 0, c->w_bytes, c->stream));                      // LFA::vector zero-initialises
     HIP_TRY(hipMemsetAsync(c->dW, 0, sizeof(float) * c->dw_elems, c->stream));
@@ -455,18 +364,15 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
         // 16: 26.4).  The scatter fused into the step kernel measured 28.7-35.0: scripts/ab/round6_pruned_knobs.patch
         const bool privatised = c->sp_keys ? c->sp_lds : c->tile_slice;
         c->n_rep = privatised ? 4 : 1;
-        HIP_TRY(hipMalloc((void**)&c->dW_rep, sizeof(long long) * c->dw_elems * c->n_rep));
-        HIP_TRY(hipMemsetAsync(c->dW_rep, 0, sizeof(long long) * c->dw_elems * c->n_rep, c->stream));
+        TRY(ctx_alloc(c, &c->dW_rep, sizeof(long long) * c->dw_elems * c->n_rep, true));
         if (c->tile_slice || c->sp_keys) {                               // the scatter is a kernel of its own (k_tile_scatter; k_sparse_trace_scatter)
-            HIP_TRY(hipMalloc((void**)&c->sc_keys, sizeof(uint16_t) * (size_t)cfg->n_tilings * (size_t)N));
-            HIP_TRY(hipMalloc((void**)&c->sc_terms, sizeof(float) * (size_t)N));
+            TRY(ctx_alloc(c, &c->sc_keys, sizeof(uint16_t) * (size_t)cfg->n_tilings * (size_t)N));
+            TRY(ctx_alloc(c, &c->sc_terms, sizeof(float) * (size_t)N));
         }
     }
     if (shared) {
-        HIP_TRY(hipMalloc((void**)&c->d_peer_err, sizeof(uint32_t)));
-        HIP_TRY(hipMemsetAsync(c->d_peer_err, 0, sizeof(uint32_t), c->stream));
-        HIP_TRY(hipMalloc((void**)&c->h_fx, sizeof(long long) * c->dw_elems));
-        HIP_TRY(hipMemsetAsync(c->h_fx, 0, sizeof(long long) * c->dw_elems, c->stream));
+        TRY(ctx_alloc(c, &c->d_peer_err, sizeof(uint32_t), true));
+        TRY(ctx_alloc(c, &c->h_fx, sizeof(long long) * c->dw_elems, true));
     }
     HIP_TRY(hipMemsetAsync(c->action, 0, sizeof(int32_t) * (size_t)N, c->stream));
     HIP_TRY(hipMemsetAsync(c->ep_step, 0, sizeof(uint32_t) * (size_t)N, c->stream));

@@ -196,29 +196,8 @@ static int ensure_step_graph(rsrl_hip_ctx* c, const Common& k, const BasisGeom& 
     return RSRL_HIP_OK;
 }
 
-// batch-steps per launch of the fused loops.  Every launch of the register-family loop loads and stores every learner's weights
-// (60.7 MB at 65 536 MountainCar learners: ~11 us) and pays a launch-to-launch gap around its arithmetic (0.77 us per
-// batch-step): 1 024 steps per launch instead of 256 is worth +7 % (8.3e10 -> 8.9e10 env-steps/s, 2 048: 9.0e10) and a
-// launch still lasts under a millisecond (2.4 ms for the trace agents).  The memory-resident and wave-family loops keep 256
-// (their steps are 15-150x longer).
-static inline int64_t fuse_depth(const rsrl_hip_ctx* c) {
-    if (c->cfg.steps_per_launch) return c->cfg.steps_per_launch;
-    // every register-resident loop (also the trace / GreedyGQ / TD ones, which load and store two matrices per launch).  Round 3, under the driver's
-    // invocation (20-step calls, coalesced; scripts/gpu_r3_v6.sh): 1 024 -> 8.96e10, 2 048 -> 9.06e10, 4 096 -> 9.12e10, 8 192 -> 9.17e10 env-steps/s;
-    // 4 096 is a 2.9 ms launch at 65 536 learners
-    switch (c->family) {
-    case AgentFamily::TdReg: case AgentFamily::GqReg: case AgentFamily::LambdaReg: case AgentFamily::RegStep: case AgentFamily::RegFused: case AgentFamily::AcReg:
-    case AgentFamily::TdAcReg: case AgentFamily::ReinforceReg:
-        return 4096;
-    // RecursiveLSTD / iLSTD: O(F^2) f64 per learner-step, 0.76 / 1.03 ms per batch-step at 262 144 MountainCar order-5 learners:
-    // 32 keep a launch in the tens of milliseconds there; at 65 536 order-3 learners a 32-step launch lasts 0.6 ms
-    // (the iLSTD ActorCritic: the same f64 step with the actor's f32 work beside it)
-    case AgentFamily::LstdReg: case AgentFamily::TdAcLstdReg: return 32;
-    // HIVTreatment: one batch-step is 1 000 f64 RK4 sub-steps per learner, ~1 ms at 65 536 learners -- 16 keep a launch in the tens of milliseconds
-    case AgentFamily::Hiv: return 16;
-    default: return 256;
-    }
-}
+// batch-steps per launch of the fused loops: the configuration's, or the family's (ctx.hpp kFamily, with the measurements behind the depths)
+static inline int64_t fuse_depth(const rsrl_hip_ctx* c) { return c->cfg.steps_per_launch ? c->cfg.steps_per_launch : family_row(c).depth; }
 
 // ---- co-residency of the persistent kernel ----------------------------------------------------------------------------------
 // Shared weights, dense basis: the whole train call as ONE persistent launch (kernels_persist.hpp).  k_shared_persist spins on
@@ -380,7 +359,8 @@ static int persist_launch(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, 
     return RSRL_HIP_OK;
 }
 
-// the per-learner families (ctx.hpp launch_agent): what one launch of the driver loop runs, or handle on io's transitions
+// the per-learner families (ctx.hpp launch_agent): what one launch of the driver loop runs, or handle on io's transitions.  A switch because it
+// instantiates the kernel templates; what else a family is stands in ctx.hpp's kFamily, the other place (with classify) a new family is entered
 int launch_agent(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, uint64_t t, int chunk, DevStats* d_stats, const Transitions* io) {
     const rsrl_hip_config& cf = c->cfg;
     const dim3 grid(grid_for(io ? io->M : k.n_envs)), block(kBlock);

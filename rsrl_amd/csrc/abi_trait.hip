@@ -375,21 +375,21 @@ int rsrl_hip_handle(rsrl_hip_ctx* c, const float* from_states, const int32_t* ac
     if (trait_fast(c)) {
         TRY(launch_trait_handle(c, k, d_from, d_act, d_rew, d_to, d_term, M, c->t, otd.dev));
     } else {
-        switch (c->family) {
-        case AgentFamily::WaveControl:
+        switch (family_row(c).handle) {
+        case Handle::Wave:
             for_wave(c, [&](auto tag) {
                 using T = decltype(tag); using WT = typename T::wt;
                 hipLaunchKernelGGL((k_wave_handle<T::domain, WT>), dim3(wave_grid_for(M)), dim3(kBlock), 0, c->stream, k, (WT*)c->W, d_from, d_act, d_rew, d_to, d_term, M, c->t,
                                    otd.dev);
             });
             break;
-        case AgentFamily::SharedDense: case AgentFamily::SharedTile: case AgentFamily::RegStep: case AgentFamily::RegFused: case AgentFamily::Generic:
+        case Handle::Model:
             if (!for_model(c, [&](auto tag) {
                     using Mo = typename decltype(tag)::type;
                     hipLaunchKernelGGL((k_handle<Mo>), dim3(grid_for(M)), dim3(kBlock), 0, c->stream, k, g, d_from, d_act, d_rew, d_to, d_term, M, c->t, otd.dev, c->h_fx);
                 })) return NO_MODEL(c);
             break;
-        default: {
+        case Handle::Agent: {
             const Transitions io{d_from, d_act, d_rew, d_to, d_term, M, otd.dev};
             TRY(launch_agent(c, k, g, c->t, 1, nullptr, &io));
         }

@@ -180,7 +180,7 @@ struct Ckpt {
 };
 // the payload sections (what each holds: kSection below); S_EPS is never a row's member -- it ends the file of any ctx that runs the schedule
 enum SectionId : uint8_t { S_NONE = 0, S_WEIGHTS, S_AUX, S_BEHAVIOUR, S_LSTD, S_RING, S_SPARSE, S_EPS, S_COUNT };
-// THE table: what a file of each aux_kind is.  An agent with state of its own adds a row here and, if no section fits, a section below.
+// THE table: what a file of each aux_kind is.  An agent with state of its own adds a row here (its number: the agent's aux_kind in ctx.hpp kAlgo) and, if no section fits, a section below.
 struct CkptKind {
     uint32_t version, older;     // written as `version` (the epsilon schedule's files: kCkptVersionEps); `older`, no longer written, is still read (0: none)
     bool eps;                    // configurations of this kind can run the epsilon schedule: version kCkptVersionEps is theirs too
@@ -200,14 +200,8 @@ constexpr CkptKind kCkptKind[kCkptKinds] = {
     /* 8 the LSTD agents' f64 state             */ {10, 0, false, false, {S_LSTD}},
     /* 9 the iLSTD ActorCritic: f64 state, theta */ {10, 0, false, false, {S_LSTD, S_AUX}},      // (version 10 too: the aux_kind tells the two apart)
 };
-int aux_kind_of(const rsrl_hip_ctx* c) {
-    if (c->family == AgentFamily::LstdReg) return 8;
-    if (c->family == AgentFamily::TdAcLstdReg) return 9;
-    if (c->family == AgentFamily::AcReg) return 5;
-    if (c->family == AgentFamily::TdAcReg) return 6;
-    if (c->family == AgentFamily::ReinforceReg) return 7;
-    return c->sp_keys ? 4 : (c->qs_buf ? 3 : (!c->Z ? 0 : (c->cfg.algo == RSRL_GREEDY_GQ ? 2 : 1)));
-}
+// (the one kind the configuration decides, not the algo: SARSALambda / QLambda over ONE shared tile table keep sparse traces instead of Z)
+int aux_kind_of(const rsrl_hip_ctx* c) { return c->sp_keys ? 4 : kAlgo[c->cfg.algo].aux_kind; }
 // is (version, aux_kind) a header this library writes, or ever wrote?
 bool ckpt_pairing(uint32_t version, int32_t kind) {
     if (kind < 0 || kind >= kCkptKinds) return false;

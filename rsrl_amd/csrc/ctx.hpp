@@ -47,18 +47,57 @@
 
 using namespace rsrl;
 
-static inline bool is_lambda(int algo) { return algo == RSRL_SARSA_LAMBDA || algo == RSRL_Q_LAMBDA; }
-static inline bool is_pred(int algo) { return algo == RSRL_TD || algo == RSRL_TD_LAMBDA; }        // one weight column (V function)
-static inline bool is_ac(int algo) { return algo == RSRL_ACTOR_CRITIC || algo == RSRL_Q_ACTOR_CRITIC; }     // ActorCritic: theta is the second matrix
-static inline bool has_aux(int algo) { return is_lambda(algo) || algo == RSRL_GREEDY_GQ || algo == RSRL_TD_LAMBDA || is_ac(algo); }   // second matrix of W's shape
-// ActorCritic with the TD(0) V critic: W is V's single column, the second matrix (theta) has A columns
-static inline bool is_tdac(int algo) { return algo == RSRL_TD_ACTOR_CRITIC; }
-// REINFORCE / BaselineREINFORCE: theta is the second matrix, theta_b (the behaviour snapshot) a third; W is the baseline B (unused by REINFORCE)
-static inline bool is_reinforce(int algo) { return algo == RSRL_REINFORCE || algo == RSRL_BASELINE_REINFORCE; }
-// RecursiveLSTD / iLSTD: f64 theta, a f64 F x F matrix (and iLSTD's mu) per learner, outside W (which is allocated, one zero column, never read)
-static inline bool is_lstd(int algo) { return algo == RSRL_RECURSIVE_LSTD || algo == RSRL_ILSTD; }
-// ActorCritic::tdac with the iLSTD critic: iLSTD's f64 state (as is_lstd's, W allocated and never read) and the actor's theta, A columns, in Z
-static inline bool is_tdac_lstd(int algo) { return algo == RSRL_ILSTD_ACTOR_CRITIC; }
+// ---- THE agent table: what the reference's agent of each rsrl_algo is, one row per number.  Admission (check_config), the ctx's buffers (create_impl),
+// the accessors and the checkpoint read it; a new agent adds its row here, a line of classify() and a case of launch_agent ("Adding an agent").
+enum class Agent : uint8_t { None, OneStep, Lambda, Gq, Pred, QSigma, Ac, TdAc, Reinforce, Lstd, TdAcLstd };      // the group classify() and the kernels' dispatch know it by
+enum class Aux : uint8_t { None, LikeW, Policy };      // the second per-learner matrix Z: none, of W's shape, or the actor's A columns next to a one-column W
+struct AlgoRow {
+    const char* name = nullptr;      // as the admission messages print it (nullptr: the number is unassigned)
+    Agent agent = Agent::None;
+    bool v = false;                  // the value function has ONE column (V: ScalarLFA, or the f64 theta) instead of A
+    Aux aux = Aux::None;             // Z: traces (Lambda, TDLambda), fa_td's weights (Gq), the policy's theta (the actor-critics, REINFORCE)
+    int aux_kind = 0;                // the checkpoint's (abi_weights.hip kCkptKind), unless the configuration decides it (aux_kind_of)
+    bool episode = false;            // REINFORCE's open episode: the behaviour snapshot Zb and the running return ret_g
+    bool lstd = false;               // the f64 least-squares state (lstd_theta / lstd_mat / lstd_mu) is the value function
+    // the agents that exist only on the register-family Fourier orders with per-learner f32 weights (check_reg_only): the policy they require (-1: not
+    // one of them), the message's words behind it and behind "agent_policy = -1", and what it calls config.n_steps in front of "n_updates" (nullptr: not read)
+    int reg_policy = -1; const char* policy_words = ""; const char* shares_words = ""; const char* n_updates = nullptr;
+};
+constexpr AlgoRow kAlgo[RSRL_ILSTD_ACTOR_CRITIC + 1] = {
+    /*  0 */ {"QLearning", Agent::OneStep},
+    /*  1 */ {"SARSA", Agent::OneStep},
+    /*  2 */ {"ExpectedSARSA", Agent::OneStep},
+    /*  3 */ {"SARSALambda", Agent::Lambda, false, Aux::LikeW, 1},
+    /*  4 */ {"QLambda", Agent::Lambda, false, Aux::LikeW, 1},
+    /*  5 */ {"PAL", Agent::OneStep},
+    /*  6 */ {"GreedyGQ", Agent::Gq, false, Aux::LikeW, 2},
+    /*  7 */ {"TD", Agent::Pred, true},
+    /*  8 */ {"TDLambda", Agent::Pred, true, Aux::LikeW, 1},
+    /*  9 */ {"QSigma", Agent::QSigma, false, Aux::None, 3},
+    /* 10 */ {"ActorCritic", Agent::Ac, false, Aux::LikeW, 5, false, false, RSRL_SOFTMAX, " (the Gibbs actor)", " (the critic shares the actor)"},
+    /* 11 */ {"ActorCritic", Agent::Ac, false, Aux::LikeW, 5, false, false, RSRL_SOFTMAX, " (the Gibbs actor)", " (the critic shares the actor)"},
+    /* 12 */ {},
+    // (the TD / iLSTD ActorCritic: W is V's one column, theta has A)
+    /* 13 */ {"the TD ActorCritic (RSRL_TD_ACTOR_CRITIC)", Agent::TdAc, true, Aux::Policy, 6, false, false, RSRL_SOFTMAX, " (the Gibbs actor)"},
+    /* 14 */ {},
+    // (theta in Z, theta_b in Zb; W is the baseline B -- REINFORCE: allocated, never read)
+    /* 15 */ {"REINFORCE (RSRL_REINFORCE)", Agent::Reinforce, false, Aux::LikeW, 7, true, false, RSRL_SOFTMAX, " (the Gibbs policy)"},
+    /* 16 */ {"BaselineREINFORCE (RSRL_BASELINE_REINFORCE)", Agent::Reinforce, false, Aux::LikeW, 7, true, false, RSRL_SOFTMAX, " (the Gibbs policy)"},
+    /* 17 */ {},
+    // (the least-squares agents: W is allocated, one zero column, never read)
+    /* 18 */ {"RecursiveLSTD (RSRL_RECURSIVE_LSTD)", Agent::Lstd, true, Aux::None, 8, false, true, RSRL_RANDOM},
+    /* 19 */ {"iLSTD (RSRL_ILSTD)", Agent::Lstd, true, Aux::None, 8, false, true, RSRL_RANDOM, "", "", ""},
+    /* 20 */ {},
+    /* 21 */ {"the iLSTD ActorCritic (RSRL_ILSTD_ACTOR_CRITIC)", Agent::TdAcLstd, true, Aux::Policy, 9, false, true, RSRL_SOFTMAX, " (the Gibbs actor)", "", "the critic's "},
+};
+// (readers of the table, for configurations check_config has admitted: the algo is a row with a name)
+static inline bool is_lambda(int algo) { return kAlgo[algo].agent == Agent::Lambda; }
+static inline bool is_pred(int algo) { return kAlgo[algo].agent == Agent::Pred; }
+static inline bool is_ac(int algo) { return kAlgo[algo].agent == Agent::Ac; }
+static inline bool is_tdac(int algo) { return kAlgo[algo].agent == Agent::TdAc; }
+static inline bool is_reinforce(int algo) { return kAlgo[algo].agent == Agent::Reinforce; }
+static inline bool is_lstd(int algo) { return kAlgo[algo].agent == Agent::Lstd; }
+static inline bool is_tdac_lstd(int algo) { return kAlgo[algo].agent == Agent::TdAcLstd; }
 
 // ---- the small kernels more than one unit launches, and the launches of kernel templates two units would otherwise both instantiate: defined ONCE, in
 // kernels_util.hip / launch_shared.hip (a kernel's host stub is an ordinary function: another unit launches it through this declaration)
@@ -136,9 +175,62 @@ enum class AgentFamily : uint8_t {
     TdAcLstdReg,          // ActorCritic with the iLSTD critic, same configurations as TdAcReg: k_train_tdac_lstd (train_tdac_lstd.hip); iLSTD's f64 state as
                           // LstdReg's, theta in Z (A columns)
 };
-static inline bool is_wave_family(AgentFamily f) {
-    return f == AgentFamily::WaveAux || f == AgentFamily::WaveQSigma || f == AgentFamily::WaveLambda || f == AgentFamily::WaveControl;
+constexpr size_t kAgentFamilies = (size_t)AgentFamily::TdAcLstdReg + 1;      // (the enum's last value)
+// ---- THE family table: which kernels serve a family and what they can do, one row per AgentFamily value in the enum's order.  classify() (abi_ctx.hip: a
+// decision) and launch_agent (abi_train.hip: it instantiates the templates) are the two other places a new family is entered.
+enum class Slots : uint8_t { Block, Block64, WaveBlock, Learner, LstdGroup };      // a statistics slot per: kBlock learners, 64 learners (k_train_lambda_mem4; the
+                                                                                   // ctx's k1_quad), wave-family block, learner (a block each), kBlock lanes of G per learner
+enum class Handle : uint8_t { Model, Wave, Agent };      // rsrl_hip_handle's kernel: k_handle<Model>, k_wave_handle, or the family's own through launch_agent
+enum : uint8_t { kWave = 1, kCarriesQ = 2, kPolicyW = 4, kVCritic = 8, kLstd = 16 };
+struct FamilyRow {
+    AgentFamily family;      // (its own index: checked below)
+    const char* kernel;      // the driver-loop kernel timing_read names (WaveControl, RegStep: refined by train_kernel_name)
+    int depth;               // batch-steps per launch while config.steps_per_launch == 0 (the shared families: not read, they step one per launch)
+    Slots slots;
+    Handle handle;
+    uint8_t can;             // kWave: one wavefront per learner (is_wave_family); kCarriesQ: reads Common::qcache; kPolicyW: a Gibbs policy over weights of its
+};                           // own, theta in Z; kVCritic: a state-value critic next to the actor; kLstd: the value function is the f64 least-squares state
+// The depths.  Every launch of a register-resident loop loads and stores every learner's weights (60.7 MB at 65 536 MountainCar learners: ~11 us; the
+// trace / GreedyGQ / TD ones two matrices) and pays a launch-to-launch gap around its arithmetic (0.77 us per batch-step): 1 024 steps per launch instead
+// of 256 is worth +7 % (8.3e10 -> 8.9e10 env-steps/s).  Round 3, under the driver's invocation (20-step calls, coalesced): 1 024 -> 8.96e10,
+// 2 048 -> 9.06e10, 4 096 -> 9.12e10, 8 192 -> 9.17e10 env-steps/s; 4 096 is a 2.9 ms launch at 65 536 learners.  The memory-resident and wave-family loops keep 256 (their steps are 15-150x longer).  RecursiveLSTD / iLSTD (and
+// the iLSTD ActorCritic, the same f64 step with the actor's f32 work beside it): O(F^2) f64 per learner-step, 0.76 / 1.03 ms per batch-step at 262 144
+// MountainCar order-5 learners -- 32 keep a launch in the tens of milliseconds there.  HIVTreatment: one batch-step is 1 000 f64 RK4
+// sub-steps per learner, ~1 ms at 65 536 learners -- 16 keep a launch in the tens of milliseconds.
+constexpr FamilyRow kFamily[] = {
+    {AgentFamily::SharedDense, "k_shared_step", 256, Slots::Block, Handle::Model, 0},
+    {AgentFamily::SharedTile, "k_shared_ca", 256, Slots::Block, Handle::Model, 0},
+    {AgentFamily::SharedSparseLambda, "k_sparse_trace_scatter", 256, Slots::Learner, Handle::Agent, 0},      // (handle: rsrl_hip_handle's own branch)
+    {AgentFamily::WaveAux, "k_wave_aux", 256, Slots::WaveBlock, Handle::Agent, kWave},
+    {AgentFamily::TdTile, "k_td_tile", 256, Slots::Learner, Handle::Agent, 0},
+    {AgentFamily::TdGeneric, "k_td_mem", 256, Slots::Block, Handle::Agent, 0},
+    {AgentFamily::TdReg, "k_train_td", 4096, Slots::Block, Handle::Agent, 0},
+    {AgentFamily::WaveQSigma, "k_wave_qsigma", 256, Slots::WaveBlock, Handle::Agent, kWave},
+    {AgentFamily::QSigmaReg, "k_train_qsigma", 256, Slots::Block, Handle::Agent, 0},
+    {AgentFamily::QSigmaGeneric, "k_train_qsigma", 256, Slots::Block, Handle::Agent, 0},
+    {AgentFamily::GqReg, "k_train_gq", 4096, Slots::Block, Handle::Agent, 0},
+    {AgentFamily::GqGeneric, "k_train_gq_mem", 256, Slots::Block, Handle::Agent, 0},
+    {AgentFamily::LambdaTile, "k_lambda_tile", 256, Slots::Learner, Handle::Agent, 0},
+    {AgentFamily::WaveLambda, "k_wave_lambda", 256, Slots::WaveBlock, Handle::Agent, kWave},
+    {AgentFamily::LambdaGeneric, "k_train_lambda_mem", 256, Slots::Block64, Handle::Agent, 0},
+    {AgentFamily::LambdaReg, "k_train_lambda", 4096, Slots::Block, Handle::Agent, 0},
+    {AgentFamily::WaveControl, "k_train_wave", 256, Slots::WaveBlock, Handle::Wave, kWave},
+    {AgentFamily::RegStep, "k_step_reg", 4096, Slots::Block, Handle::Model, kCarriesQ},
+    {AgentFamily::RegFused, "k_train_reg", 4096, Slots::Block, Handle::Model, kCarriesQ},
+    {AgentFamily::Generic, "k_train_mem", 256, Slots::Block, Handle::Model, 0},
+    {AgentFamily::Hiv, "k_hiv_train", 16, Slots::Block, Handle::Agent, 0},
+    {AgentFamily::AcReg, "k_train_ac", 4096, Slots::Block, Handle::Agent, kPolicyW},
+    {AgentFamily::TdAcReg, "k_train_tdac", 4096, Slots::Block, Handle::Agent, kPolicyW | kVCritic},
+    {AgentFamily::ReinforceReg, "k_train_reinforce", 4096, Slots::Block, Handle::Agent, kPolicyW},      // (handle: refused, whole batches only)
+    {AgentFamily::LstdReg, "k_train_lstd", 32, Slots::LstdGroup, Handle::Agent, kLstd},
+    {AgentFamily::TdAcLstdReg, "k_train_tdac_lstd", 32, Slots::LstdGroup, Handle::Agent, kPolicyW | kVCritic | kLstd},
+};
+constexpr bool family_rows_in_order() {
+    for (size_t i = 0; i < sizeof(kFamily) / sizeof(kFamily[0]); ++i) if ((size_t)kFamily[i].family != i) return false;
+    return true;
 }
+static_assert(sizeof(kFamily) / sizeof(kFamily[0]) == kAgentFamilies && family_rows_in_order(), "kFamily: one row per AgentFamily value, in the enum's order");
+static inline bool is_wave_family(AgentFamily f) { return kFamily[(size_t)f].can & kWave; }
 
 // the environment switches, read once when the ctx is created (abi_ctx.hip read_switches)
 struct Switches {
@@ -211,6 +303,7 @@ struct rsrl_hip_ctx {
     uint64_t api_calls = 0;  // RNG counter of rsrl_hip_policy_sample
     uint64_t rollout_calls = 0;   // ... and of rsrl_hip_rollout_policy (one stream of draws per call)
     Scratch scratch[8];
+    std::vector<void**> owned;       // the device buffers create_impl allocated (ctx_alloc, abi_ctx.hip), by MEMBER: rsrl_hip_destroy frees what each holds then
     // timing of train launches
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
@@ -281,10 +374,9 @@ static Common make_common(const rsrl_hip_ctx* c) {
     return k;
 }
 
+static inline const FamilyRow& family_row(const rsrl_hip_ctx* c) { return kFamily[(size_t)c->family]; }
 // the agents with a Gibbs policy over weights of their own (theta in Z): ActorCritic (both critics, TDCritic over TD(0) or iLSTD), REINFORCE (both)
-static inline bool has_policy_weights(const rsrl_hip_ctx* c) {
-    return c->family == AgentFamily::AcReg || c->family == AgentFamily::TdAcReg || c->family == AgentFamily::ReinforceReg || c->family == AgentFamily::TdAcLstdReg;
-}
+static inline bool has_policy_weights(const rsrl_hip_ctx* c) { return family_row(c).can & kPolicyW; }
 // the weights the POLICY side reads: the actor's preferences theta for ActorCritic (the policy is Gibbs over theta, not over Q), W otherwise.
 // Policy::sample / mode / probabilities, reset's initial sample and the rollouts run the model kernels on it; the value side keeps make_common
 static Common make_policy_common(const rsrl_hip_ctx* c) {
@@ -293,11 +385,11 @@ static Common make_policy_common(const rsrl_hip_ctx* c) {
     return k;
 }
 // a state-value critic next to the actor: the weights are V's one column, theta has A
-static inline bool is_v_actor_critic(const rsrl_hip_ctx* c) { return c->family == AgentFamily::TdAcReg || c->family == AgentFamily::TdAcLstdReg; }
+static inline bool is_v_actor_critic(const rsrl_hip_ctx* c) { return family_row(c).can & kVCritic; }
 // columns of the auxiliary matrix Z: W's (Aw), except the TD / iLSTD ActorCritic's theta (A)
-static inline int aux_cols(const rsrl_hip_ctx* c) { return is_v_actor_critic(c) ? c->A : c->Aw; }
+static inline int aux_cols(const rsrl_hip_ctx* c) { return kAlgo[c->cfg.algo].aux == Aux::Policy ? c->A : c->Aw; }
 // the agents whose value function is the f64 least-squares state (lstd_theta / lstd_mat / lstd_mu)
-static inline bool has_lstd_state(const rsrl_hip_ctx* c) { return c->family == AgentFamily::LstdReg || c->family == AgentFamily::TdAcLstdReg; }
+static inline bool has_lstd_state(const rsrl_hip_ctx* c) { return family_row(c).can & kLstd; }
 static inline ReinforceState make_reinforce(const rsrl_hip_ctx* c) {
     ReinforceState rs;
     rs.theta = c->Z; rs.theta_b = c->Zb; rs.g = c->ret_g;
@@ -309,7 +401,7 @@ static inline LstdState make_lstd(const rsrl_hip_ctx* c) {
     ls.theta = c->lstd_theta; ls.mat = c->lstd_mat; ls.mu = c->lstd_mu;
     // (the iLSTD ActorCritic: config.alpha is ActorCritic.alpha, iLSTD's alpha is the critic's rate, config.lr)
     ls.gamma = c->cfg.gamma; ls.alpha = is_tdac_lstd(c->cfg.algo) ? c->cfg.lr : c->cfg.alpha;
-    ls.n_updates = (c->cfg.algo == RSRL_ILSTD || is_tdac_lstd(c->cfg.algo)) ? c->cfg.n_steps : 0;
+    ls.n_updates = kAlgo[c->cfg.algo].n_updates ? c->cfg.n_steps : 0;
     return ls;
 }
 static inline TdacLstdState make_tdac_lstd(const rsrl_hip_ctx* c) {
@@ -577,7 +669,7 @@ bool persist_capable(rsrl_hip_ctx* c);
 bool persist_ok(rsrl_hip_ctx* c);
 unsigned persist_budget_shared(rsrl_hip_ctx* c);
 // the kernels that read Common::qcache: the register family's one-step loops
-static inline bool carries_q(const rsrl_hip_ctx* c) { return c->family == AgentFamily::RegStep || c->family == AgentFamily::RegFused; }
+static inline bool carries_q(const rsrl_hip_ctx* c) { return family_row(c).can & kCarriesQ; }
 bool no_coalesce_switch();                                                                                                                  // abi_ctx.hip
 // the per-learner families' launch, driver loop (io == nullptr: chunk batch-steps from batch-step t) or Handler::handle on io's transitions (the families
 // with a handle kernel of their own; rsrl_hip_handle takes the rest to k_handle / k_wave_handle)                                            abi_train.hip

@@ -7,8 +7,8 @@ The counter: a checkpoint header stores step_count as a little-endian u64 at byt
 carried by a fresh ctx, so the oracle needs only Run.t = T0 (pinned on the CPU by tests/test_oracle_counter_cpu.py).  Runs start 5 or 4 steps
 below 2^32 and 2^33 (odd and even: the fused loops peel an odd first step and share one Philox block per pair of steps) and cross the edge inside a
 fused launch, with one and five steps per launch, between launches (train(3); train(1); train(K - 4)) and -- the launch-bound families -- inside a
-replayed step graph (32 steps per graph: train(3); train(33) without statistics; train(2); train(33) for the shared families).  One row per kernel family of train_kernel_name()
-(abi_ctx.hip); the kernel that ran is read back through timing_read().
+replayed step graph (32 steps per graph: train(3); train(33) without statistics; train(2); train(33) for the shared families).  One row per kernel name of kFamily (ctx.hpp) and its
+refinements in train_kernel_name() (abi_ctx.hip); the kernel that ran is read back through timing_read().
 
 The learner id: 130 learners whose ids straddle the sign bit inside one wave (env_offset = 2^31 - 65) and end at the largest id check_config admits
 (2^32 - 1 - 130), against the oracle built with the same env_offset.
