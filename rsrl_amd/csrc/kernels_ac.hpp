@@ -16,6 +16,7 @@
 #pragma once
 
 #include "models.hpp"
+#include "driver_loop.hpp"
 
 namespace rsrl {
 
@@ -104,28 +105,6 @@ __device__ __forceinline__ float ac_step(const Common& c, WBuf<A, F, PK>& w, WBu
     return delta;
 }
 
-// a learner's matrix between memory and registers.  The learner's base address goes through an empty asm at every call: the 2 x A x F element
-// addresses are then formed next to their access from one VGPR pair and a uniform offset -- otherwise the load's addresses are kept for the
-// store and take two VGPRs per weight (the spills of a 2 x 108-weight learner)
-template <int A, int F, bool PK>
-__device__ __forceinline__ void ac_load(WBuf<A, F, PK>& w, const float* __restrict__ W, int64_t N, int64_t i) {
-    const float* p = W + i;
-    asm("" : "+v"(p));
-#pragma unroll
-    for (int b = 0; b < A; ++b)
-#pragma unroll
-        for (int f = 0; f < F; ++f) w.put(b, f, p[(int64_t)(b * F + f) * N]);
-}
-template <int A, int F, bool PK>
-__device__ __forceinline__ void ac_store(const WBuf<A, F, PK>& w, float* __restrict__ W, int64_t N, int64_t i) {
-    float* p = W + i;
-    asm("" : "+v"(p));
-#pragma unroll
-    for (int b = 0; b < A; ++b)
-#pragma unroll
-        for (int f = 0; f < F; ++f) p[(int64_t)(b * F + f) * N] = w.get(b, f);
-}
-
 // the driver loop (a2c.rs:55-67): transition, critic, actor, then the behaviour sample a' ~ pi_theta'(s') with the UPDATED theta (BLK_STEP; an
 // episode cut by max_episode_steps restarts and samples there on BLK_RESET, a terminal one restarts before the sample) -- the one-step agents'
 // convention.  W and theta stay in registers for the whole launch (k_train_gq's layout); the sample's probabilities are the next step's p
@@ -137,59 +116,32 @@ __global__ __launch_bounds__(kBlock) void k_train_ac(Common c, float* __restrict
     constexpr int D = Dom::D, A = Dom::A, F = Bas::F;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t N = c.n_envs;
-    unsigned long long n_ep = 0, n_trunc = 0, sum_len = 0;
-    double sum_abs = 0.0, sum_r = 0.0;
+    Tally tally;
     if (i < N) {
-        const uint32_t gid = (uint32_t)(c.env_offset + i);
-        const uint32_t cap = c.max_episode_steps;
-        float s[D];
-#pragma unroll
-        for (int d = 0; d < D; ++d) s[d] = c.state[(int64_t)d * N + i];
-        int a = c.action[i];
-        uint32_t ep = c.ep_step[i];
+        Learner<D> env;
+        env.load(c, i);
         constexpr bool PK = (RSRL_PK != 0) && (F % 4 == 0);
         WBuf<A, F, PK> w, th;
-        ac_load<A, F, PK>(w, c.W, N, i);
-        ac_load<A, F, PK>(th, theta, N, i);
+        mat_load<A, F, PK>(w, c.W, N, i);
+        mat_load<A, F, PK>(th, theta, N, i);
         float p_s[A];
-        { PhiBuf<F, PK> phi; ac_project<Bas>(s, phi); ac_probs<A, F, PK>(c, th, phi, p_s); }
-        float facc_abs = 0.0f, facc_r = 0.0f;
+        { PhiBuf<F, PK> phi; ac_project<Bas>(env.s, phi); ac_probs<A, F, PK>(c, th, phi, p_s); }
         for (int k = 0; k < n_steps; ++k) {
             const uint64_t t = t0 + (uint64_t)k;
-            float ns[D];
-#pragma unroll
-            for (int d = 0; d < D; ++d) ns[d] = s[d];
-            float r;
-            const bool term = Dom::step(ns, a, r);
-            ep += 1;
-            const bool trunc = !term && cap > 0 && ep >= cap;
-            if (term) Dom::reset(ns);                       // a terminal transition never reads s': go straight to the restart state
-            const U4 xin = draw(c.seed, gid, t, BLK_INNER);
-            const float delta = ac_step<Bas, A, F, PK, CRITIC>(c, w, th, s, p_s, a, r, term, ns, xin);
-            facc_abs += fabsf(delta); facc_r += r;
-            if (term) { n_ep += 1; sum_len += ep; ep = 0; }
-            uint32_t blk = BLK_STEP;
-            if (trunc) {                                    // the cut episode restarts first: its restart state is where the one sample is taken
-                n_ep += 1; n_trunc += 1; sum_len += ep; ep = 0;
-                Dom::reset(ns);
-                blk = BLK_RESET;
-            }
-            // ---- policy.sample(rng, s') with the UPDATED theta
-            { PhiBuf<F, PK> phi; ac_project<Bas>(ns, phi); ac_probs<A, F, PK>(c, th, phi, p_s); }
-            const U4 x = draw(c.seed, gid, t, blk);
-            a = sample_probs<A>(p_s, x.z);
-#pragma unroll
-            for (int d = 0; d < D; ++d) s[d] = ns[d];
+            Transition<D> tr = env.template step<Dom>();
+            terminal_to_restart<Dom>(tr);                   // a terminal transition never reads s': go straight to the restart state
+            const U4 xin = draw(c.seed, env.gid, t, BLK_INNER);
+            const float delta = ac_step<Bas, A, F, PK, CRITIC>(c, w, th, env.s, p_s, env.a, tr.r, tr.term, tr.ns, xin);
+            // ---- policy.sample(rng, s') with the UPDATED theta (a cut episode restarts first: its restart state is where the one sample is taken)
+            restart_then_sample<Dom>(c, env, tally, tr, delta, t,
+                [&](const float (&ns)[D], bool) { PhiBuf<F, PK> phi; ac_project<Bas>(ns, phi); ac_probs<A, F, PK>(c, th, phi, p_s); },
+                [&](const U4& x) { return sample_probs<A>(p_s, x.z); });
         }
-        sum_abs = (double)facc_abs; sum_r = (double)facc_r;
-#pragma unroll
-        for (int d = 0; d < D; ++d) c.state[(int64_t)d * N + i] = s[d];
-        c.action[i] = a;
-        c.ep_step[i] = ep;
-        ac_store<A, F, PK>(w, c.W, N, i);
-        ac_store<A, F, PK>(th, theta, N, i);
+        env.store(c, i);
+        mat_store<A, F, PK>(w, c.W, N, i);
+        mat_store<A, F, PK>(th, theta, N, i);
     }
-    if (stats) block_stats_accumulate(stats, n_ep, n_trunc, sum_len, sum_abs, sum_r);
+    tally.hand_over(stats);
 }
 
 // Handler<&Transition>::handle of ActorCritic (with the critic's SARSA::handle before it, as a2c.rs:62-63) on caller-supplied transitions:
@@ -205,21 +157,17 @@ __global__ __launch_bounds__(kBlock) void k_handle_ac(Common c, float* __restric
     if (i >= Mn) return;
     const int64_t N = c.n_envs;
     constexpr bool PK = (RSRL_PK != 0) && (F % 4 == 0);
-    float s[D], ns[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) { s[d] = from[(int64_t)d * Mn + i]; ns[d] = to[(int64_t)d * Mn + i]; }
-    const int a = clamp_action<A>(act[i]);
-    const float r = rew[i];
-    const bool term = termf[i] != 0;
+    Given<D> tr;
+    tr.template load<A>(from, act, rew, to, termf, Mn, i);
     WBuf<A, F, PK> w, th;
-    ac_load<A, F, PK>(w, c.W, N, i);
-    ac_load<A, F, PK>(th, theta, N, i);
+    mat_load<A, F, PK>(w, c.W, N, i);
+    mat_load<A, F, PK>(th, theta, N, i);
     float p_s[A];
-    { PhiBuf<F, PK> phi; ac_project<Bas>(s, phi); ac_probs<A, F, PK>(c, th, phi, p_s); }
+    { PhiBuf<F, PK> phi; ac_project<Bas>(tr.s, phi); ac_probs<A, F, PK>(c, th, phi, p_s); }
     const U4 xin = draw(c.seed, (uint32_t)(c.env_offset + i), t, BLK_INNER);
-    const float delta = ac_step<Bas, A, F, PK, CRITIC>(c, w, th, s, p_s, a, r, term, ns, xin);
-    ac_store<A, F, PK>(w, c.W, N, i);
-    ac_store<A, F, PK>(th, theta, N, i);
+    const float delta = ac_step<Bas, A, F, PK, CRITIC>(c, w, th, tr.s, p_s, tr.a, tr.r, tr.term, tr.ns, xin);
+    mat_store<A, F, PK>(w, c.W, N, i);
+    mat_store<A, F, PK>(th, theta, N, i);
     if (td_out) td_out[i] = delta;
 }
 

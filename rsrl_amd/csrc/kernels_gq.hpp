@@ -11,6 +11,7 @@
 #pragma once
 
 #include "models.hpp"
+#include "driver_loop.hpp"
 
 namespace rsrl {
 
@@ -21,6 +22,8 @@ struct GqParams {
     float lr_td;       // SGD rate of fa_td
 };
 
+// The episode's end is the VALUE agents' convention (driver_loop.hpp) and the loop its ping_pong, both written out: orders 4 and 5 hold two matrices in 512
+// registers plus scratch, and every piece of the frame tried (the Tally alone included) moved some instantiation's spills up (profiles/driver_frame.md)
 template <int DOMAIN, int ORDER, int POLICY>
 __global__ __launch_bounds__(kBlock) void k_train_gq(Common c, GqParams gp, uint64_t t0, int n_steps, DevStats* __restrict__ stats) {
     using Dom = Domain<DOMAIN>;
@@ -141,15 +144,14 @@ __global__ __launch_bounds__(kBlock) void k_handle_gq(Common c, GqParams gp, con
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= Mn) return;
     const int64_t N = c.n_envs;
-    float s[D], ns[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) { s[d] = from[(int64_t)d * Mn + i]; ns[d] = to[(int64_t)d * Mn + i]; }
-    const int a = clamp_action<Dom::A>(act[i]);
-    const float r = rew[i];
-    const bool term = termf[i] != 0;
+    Given<D> g;
+    g.template load<A>(from, act, rew, to, termf, Mn, i);
+    const int a = g.a;
+    const float r = g.r;
+    const bool term = g.term;
     float phi_s[F], phi_n[F], q_s[A], q_n[A], e_s[A];
-    Bas::project(s, phi_s);
-    Bas::project(ns, phi_n);
+    Bas::project(g.s, phi_s);
+    Bas::project(g.ns, phi_n);
     q_from_mem<A, F>(c.W, N, i, phi_s, q_s);
     q_from_mem<A, F>(c.W, N, i, phi_n, q_n);
     q_from_mem<A, F>(gp.V, N, i, phi_s, e_s);

@@ -12,6 +12,7 @@
 #pragma once
 
 #include "models.hpp"
+#include "driver_loop.hpp"
 
 namespace rsrl {
 
@@ -32,6 +33,8 @@ __device__ __forceinline__ float trace_merge(int rule, float rate_eff, float z, 
     return v;
 }
 
+// The episode's end is the VALUE agents' convention (driver_loop.hpp) written out: order 5 holds W and Z in 512 registers plus scratch, and the frame's pieces
+// (the Tally alone included) moved some instantiation's spills up (profiles/driver_frame.md)
 template <int DOMAIN, int ORDER, int ALGO, int POLICY>
 __global__ __launch_bounds__(kBlock) void k_train_lambda(Common c, LambdaParams lp, uint64_t t0, int n_steps,
                                                          DevStats* __restrict__ stats) {
@@ -165,15 +168,14 @@ __global__ __launch_bounds__(kBlock) void k_handle_lambda(Common c, LambdaParams
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= Mn) return;
     const int64_t N = c.n_envs;
-    float s[D], ns[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) { s[d] = from[(int64_t)d * Mn + i]; ns[d] = to[(int64_t)d * Mn + i]; }
-    const int a = clamp_action<Dom::A>(act[i]);
-    const float r = rew[i];
-    const bool term = termf[i] != 0;
+    Given<D> g;
+    g.template load<A>(from, act, rew, to, termf, Mn, i);
+    const int a = g.a;
+    const float r = g.r;
+    const bool term = g.term;
     float phi_s[F], phi_n[F], q_s[A], q_n[A];
-    Bas::project(s, phi_s);
-    Bas::project(ns, phi_n);
+    Bas::project(g.s, phi_s);
+    Bas::project(g.ns, phi_n);
     q_from_mem<A, F>(c.W, N, i, phi_s, q_s);
     q_from_mem<A, F>(c.W, N, i, phi_n, q_n);
     AlgoParams alg = c.alg;

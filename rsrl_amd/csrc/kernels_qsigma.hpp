@@ -21,6 +21,7 @@
 #pragma once
 
 #include "models.hpp"
+#include "driver_loop.hpp"
 
 namespace rsrl {
 
@@ -101,21 +102,21 @@ __device__ __forceinline__ float qsigma_handle(const Common& c, const QsParams& 
     return residual;
 }
 
-// the driver loop (examples/q_learning.rs:34-55 with a QSigma agent): weights in memory, n_steps batch-steps per launch
+// the driver loop (examples/q_learning.rs:34-55 with a QSigma agent): weights in memory, n_steps batch-steps per launch.  One sample per step,
+// after the restart: restart_then_sample's convention, written out -- on Learner the tile-coding and generic-order instantiations spill more
+// scalar registers or lose a wave per SIMD (profiles/driver_frame.md); only the tally is the frame's
 template <class M>
 __global__ __launch_bounds__(kBlock) void k_train_qsigma(Common c, QsParams qp, BasisGeom g, uint64_t t0, int n_steps, DevStats* __restrict__ stats) {
     constexpr int D = M::D, A = M::A;
     const int64_t N = c.n_envs;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned long long n_ep = 0, n_trunc = 0, sum_len = 0;
-    double sum_abs = 0.0, sum_r = 0.0;
+    Tally tally;
     if (i < N) {
         const uint32_t gid = (uint32_t)(c.env_offset + i);
         const uint32_t cap = c.max_episode_steps;
         float s[D]; load_state<M>(c.state, N, i, s);
         int a = c.action[i];
         uint32_t ep = c.ep_step[i];
-        float facc_abs = 0.0f, facc_r = 0.0f;
         for (int k = 0; k < n_steps; ++k) {
             const uint64_t t = t0 + (uint64_t)k;
             float ns[D];
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(kBlock) void k_train_qsigma(Common c, QsParams qp, 
             const U4 xin = draw(c.seed, gid, t, BLK_INNER);
             const float res = qsigma_handle<M>(c, qp, g, i, N, s, a, r, ns, term, xin);
             if (term || trunc) {
-                n_ep += 1; n_trunc += trunc ? 1 : 0; sum_len += ep; ep = 0;
+                tally.episode_end(ep, trunc);
                 M::Dom::reset(ns);
             }
             // policy.sample with the UPDATED weights at s' (or at s0 after the episode ended)
@@ -137,17 +138,16 @@ __global__ __launch_bounds__(kBlock) void k_train_qsigma(Common c, QsParams qp, 
             M::q_all(c, i, g, fn, q_n);
             const U4 x = draw(c.seed, gid, t, BLK_STEP);
             a = policy_sample<A>(c.pol, q_n, x);
-            facc_abs += fabsf(res); facc_r += r;
+            tally.step(res, r);
 #pragma unroll
             for (int d = 0; d < D; ++d) s[d] = ns[d];
         }
-        sum_abs = (double)facc_abs; sum_r = (double)facc_r;
 #pragma unroll
         for (int d = 0; d < D; ++d) c.state[(int64_t)d * N + i] = s[d];
         c.action[i] = a;
         c.ep_step[i] = ep;
     }
-    if (stats) block_stats_accumulate(stats, n_ep, n_trunc, sum_len, sum_abs, sum_r);
+    tally.hand_over(stats);
 }
 
 // Handler<&Transition>::handle on caller-supplied transitions (item m = learner m)
@@ -158,11 +158,10 @@ __global__ __launch_bounds__(kBlock) void k_handle_qsigma(Common c, QsParams qp,
     constexpr int D = M::D, A = M::A;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= Mn) return;
-    float s[D], ns[D];
-    load_state<M>(from, Mn, i, s);
-    load_state<M>(to, Mn, i, ns);
+    Given<D> tr;
+    tr.template load<A>(from, act, rew, to, termf, Mn, i);
     const U4 xin = draw(c.seed, (uint32_t)(c.env_offset + i), t, BLK_INNER);
-    const float res = qsigma_handle<M>(c, qp, g, i, c.n_envs, s, clamp_action<A>(act[i]), rew[i], ns, termf[i] != 0, xin);
+    const float res = qsigma_handle<M>(c, qp, g, i, c.n_envs, tr.s, tr.a, tr.r, tr.ns, tr.term, xin);
     if (td_out) td_out[i] = res;
 }
 

@@ -32,7 +32,7 @@ __device__ __forceinline__ float reinforce_step(const Common& c, WBuf<A, F, PK>&
     float e;
     if constexpr (BASELINE) {
         WBuf<1, F, PK> col;
-        ac_load<1, F, PK>(col, c.W + (int64_t)clamp_action<A>(a) * F * N, N, i);
+        mat_load<1, F, PK>(col, c.W + (int64_t)clamp_action<A>(a) * F * N, N, i);
         float v[1];
         col.q(phi, v);
         e = c.alg.alpha * (g - v[0]);
@@ -57,43 +57,25 @@ __global__ __launch_bounds__(kBlock) void k_train_reinforce(Common c, ReinforceS
     constexpr int D = Dom::D, A = Dom::A, F = Bas::F;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t N = c.n_envs;
-    unsigned long long n_ep = 0, n_trunc = 0, sum_len = 0;
-    double sum_abs = 0.0, sum_r = 0.0;
+    Tally tally;
     if (i < N) {
-        const uint32_t gid = (uint32_t)(c.env_offset + i);
-        const uint32_t cap = c.max_episode_steps;
-        float s[D];
-#pragma unroll
-        for (int d = 0; d < D; ++d) s[d] = c.state[(int64_t)d * N + i];
-        int a = c.action[i];
-        uint32_t ep = c.ep_step[i];
+        Learner<D> env;
+        env.load(c, i);
         float g = rs.g[i];
         constexpr bool PK = (RSRL_PK != 0) && (F % 4 == 0);
         WBuf<A, F, PK> th, thb;
-        ac_load<A, F, PK>(th, rs.theta, N, i);
-        ac_load<A, F, PK>(thb, rs.theta_b, N, i);
+        mat_load<A, F, PK>(th, rs.theta, N, i);
+        mat_load<A, F, PK>(thb, rs.theta_b, N, i);
         PhiBuf<F, PK> phi;
         float p[A];
-        ac_project<Bas>(s, phi);
+        ac_project<Bas>(env.s, phi);
         ac_probs<A, F, PK>(c, th, phi, p);
-        float facc_abs = 0.0f, facc_r = 0.0f;
         for (int k = 0; k < n_steps; ++k) {
             const uint64_t t = t0 + (uint64_t)k;
-            float ns[D];
-#pragma unroll
-            for (int d = 0; d < D; ++d) ns[d] = s[d];
-            float r;
-            const bool term = Dom::step(ns, a, r);
-            ep += 1;
-            const bool trunc = !term && cap > 0 && ep >= cap;
-            facc_abs += fabsf(reinforce_step<A, F, PK, BASELINE>(c, th, phi, p, a, r, g, N, i));
-            facc_r += r;
-            const bool ended = term || trunc;
-            uint32_t blk = BLK_STEP;
-            if (term) { n_ep += 1; sum_len += ep; ep = 0; }
-            if (trunc) { n_ep += 1; n_trunc += 1; sum_len += ep; ep = 0; blk = BLK_RESET; }
-            if (ended) Dom::reset(ns);
+            Transition<D> tr = env.template step<Dom>();
+            const float ret = reinforce_step<A, F, PK, BASELINE>(c, th, phi, p, env.a, tr.r, g, N, i);
             // a new episode samples from theta as it stands now: skipped by a wave none of whose learners ended, a select per register otherwise
+            const bool ended = tr.ended();
             if (__ballot(ended) != 0ull) {
 #pragma unroll
                 for (int b = 0; b < A; ++b)
@@ -102,27 +84,24 @@ __global__ __launch_bounds__(kBlock) void k_train_reinforce(Common c, ReinforceS
             }
             g = ended ? 0.0f : g;
             // ---- phi(s') once: the next step's p from theta, the behaviour sample from theta_b
-            ac_project<Bas>(ns, phi);
-            float h[A], hb[A], pb[A];
-            th.q(phi, h);
-            thb.q(phi, hb);
-            softmax_probs<A>(h, c.pol.tau, p);
-            softmax_probs<A>(hb, c.pol.tau, pb);
-            const U4 x = draw(c.seed, gid, t, blk);
-            a = sample_probs<A>(pb, x.z);
-#pragma unroll
-            for (int d = 0; d < D; ++d) s[d] = ns[d];
+            float pb[A];
+            restart_then_sample<Dom>(c, env, tally, tr, ret, t,
+                [&](const float (&ns)[D], bool) {
+                    ac_project<Bas>(ns, phi);
+                    float h[A], hb[A];
+                    th.q(phi, h);
+                    thb.q(phi, hb);
+                    softmax_probs<A>(h, c.pol.tau, p);
+                    softmax_probs<A>(hb, c.pol.tau, pb);
+                },
+                [&](const U4& x) { return sample_probs<A>(pb, x.z); });
         }
-        sum_abs = (double)facc_abs; sum_r = (double)facc_r;
-#pragma unroll
-        for (int d = 0; d < D; ++d) c.state[(int64_t)d * N + i] = s[d];
-        c.action[i] = a;
-        c.ep_step[i] = ep;
+        env.store(c, i);
         rs.g[i] = g;
-        ac_store<A, F, PK>(th, rs.theta, N, i);
-        ac_store<A, F, PK>(thb, rs.theta_b, N, i);
+        mat_store<A, F, PK>(th, rs.theta, N, i);
+        mat_store<A, F, PK>(thb, rs.theta_b, N, i);
     }
-    if (stats) block_stats_accumulate(stats, n_ep, n_trunc, sum_len, sum_abs, sum_r);
+    tally.hand_over(stats);
 }
 
 // Handler<&Batch>::handle for every learner: learner i walks rows 0 .. len[i]-1 of its column of the batch (states [T][D][N], actions and rewards
@@ -144,7 +123,7 @@ __global__ __launch_bounds__(kBlock) void k_handle_reinforce(Common c, float* __
     if (L == 0) return;
     constexpr bool PK = (RSRL_PK != 0) && (F % 4 == 0);
     WBuf<A, F, PK> th;
-    ac_load<A, F, PK>(th, theta, N, i);
+    mat_load<A, F, PK>(th, theta, N, i);
     float g = 0.0f;
     for (int64_t t = 0; t < L; ++t) {
         float s[D];
@@ -159,7 +138,7 @@ __global__ __launch_bounds__(kBlock) void k_handle_reinforce(Common c, float* __
         reinforce_step<A, F, PK, BASELINE>(c, th, phi, p, a, r, g, N, i);
         if (ret_out) ret_out[t * N + i] = g;
     }
-    ac_store<A, F, PK>(th, theta, N, i);
+    mat_store<A, F, PK>(th, theta, N, i);
 }
 
 // a new episode for the learners in mask (all when mask is null): theta_b <- theta, g <- 0.  One thread per (element, learner), learners fastest

@@ -11,6 +11,7 @@
 #pragma once
 
 #include "models.hpp"
+#include "driver_loop.hpp"
 #include "kernels_lambda.hpp"
 
 namespace rsrl {
@@ -23,6 +24,8 @@ struct TdParams {
     int trace;         // TRACE_*
 };
 
+// The episode's end is the VALUE agents' convention (driver_loop.hpp) written out: on the frame (Learner, Tally, restart by callback, ping_pong)
+// the order-3 kernels ran 2 % slower than the parent's in every alternated run (profiles/driver_frame.md)
 template <int DOMAIN, int ORDER, bool LAMBDA>
 __global__ __launch_bounds__(kBlock) void k_train_td(Common c, TdParams tp, uint64_t t0, int n_steps, DevStats* __restrict__ stats) {
     using Dom = Domain<DOMAIN>;
@@ -132,14 +135,13 @@ __global__ __launch_bounds__(kBlock) void k_handle_td(Common c, TdParams tp, int
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= Mn) return;
     const int64_t N = c.n_envs;
-    float s[D], ns[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) { s[d] = from[(int64_t)d * Mn + i]; ns[d] = to[(int64_t)d * Mn + i]; }
-    const float r = rew[i];
-    const bool term = termf[i] != 0;
+    Given<D> g;
+    g.load(from, rew, to, termf, Mn, i);
+    const float r = g.r;
+    const bool term = g.term;
     float phi_s[F], phi_n[F], v_s[1], v_n[1];
-    Bas::project(s, phi_s);
-    Bas::project(ns, phi_n);
+    Bas::project(g.s, phi_s);
+    Bas::project(g.ns, phi_n);
     q_from_mem<1, F>(c.W, N, i, phi_s, v_s);
     q_from_mem<1, F>(c.W, N, i, phi_n, v_n);
     const float td = term ? (r - v_s[0]) : (r + c.alg.gamma * v_n[0] - v_s[0]);

@@ -52,7 +52,7 @@ __device__ __forceinline__ void tdac_probs_mem(const Common& c, const float* __r
 #pragma unroll
     for (int b = 0; b < A; ++b) {
         WBuf<1, F, PK> col;
-        ac_load<1, F, PK>(col, theta + (int64_t)b * F * N, N, i);
+        mat_load<1, F, PK>(col, theta + (int64_t)b * F * N, N, i);
         float hb[1];
         col.q(phi, hb);
         h[b] = hb[0];
@@ -65,10 +65,10 @@ __device__ __forceinline__ void tdac_actor_mem(float* __restrict__ theta, int64_
     for (int b = 0; b < A; ++b) {
         __builtin_amdgcn_sched_barrier(0);                // (one column in flight: the scheduler would otherwise hoist every column's loads)
         WBuf<1, F, PK> col;
-        ac_load<1, F, PK>(col, theta + (int64_t)b * F * N, N, i);
+        mat_load<1, F, PK>(col, theta + (int64_t)b * F * N, N, i);
         const float sb[1] = {sa[b]};
         col.axpy(sb, phi);
-        ac_store<1, F, PK>(col, theta + (int64_t)b * F * N, N, i);
+        mat_store<1, F, PK>(col, theta + (int64_t)b * F * N, N, i);
     }
 }
 
@@ -83,68 +83,35 @@ __global__ __launch_bounds__(kBlock) void k_train_tdac(Common c, float* __restri
     constexpr int D = Dom::D, A = Dom::A, F = Bas::F;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t N = c.n_envs;
-    unsigned long long n_ep = 0, n_trunc = 0, sum_len = 0;
-    double sum_abs = 0.0, sum_r = 0.0;
+    Tally tally;
     if (i < N) {
-        const uint32_t gid = (uint32_t)(c.env_offset + i);
-        const uint32_t cap = c.max_episode_steps;
-        float s[D];
-#pragma unroll
-        for (int d = 0; d < D; ++d) s[d] = c.state[(int64_t)d * N + i];
-        int a = c.action[i];
-        uint32_t ep = c.ep_step[i];
+        Learner<D> env;
+        env.load(c, i);
         constexpr bool PK = (RSRL_PK != 0) && (F % 4 == 0);
         using Phi = PhiBuf<F, PK>;
         WBuf<1, F, PK> w;
         WBuf<A, F, PK> th;
-        ac_load<1, F, PK>(w, c.W, N, i);
-        ac_load<A, F, PK>(th, theta, N, i);
+        mat_load<1, F, PK>(w, c.W, N, i);
+        mat_load<A, F, PK>(th, theta, N, i);
         Phi phi_a, phi_b;
         float p_s[A];
-        ac_project<Bas>(s, phi_a);
+        ac_project<Bas>(env.s, phi_a);
         ac_probs<A, F, PK>(c, th, phi_a, p_s);
-        float facc_abs = 0.0f, facc_r = 0.0f;
 
-        auto one_step = [&](const Phi& phi_s, Phi& phi_n, uint64_t t) {
-            float ns[D];
-#pragma unroll
-            for (int d = 0; d < D; ++d) ns[d] = s[d];
-            float r;
-            const bool term = Dom::step(ns, a, r);
-            ep += 1;
-            const bool trunc = !term && cap > 0 && ep >= cap;
-            ac_project<Bas>(ns, phi_n);                     // s' itself, the terminal state included: TDCritic reads V(s')
-            const float delta = tdac_step<A, F, PK>(c, w, phi_s, phi_n, p_s, a, r, term, [&](const float (&sa)[A]) { th.axpy(sa, phi_s); });
-            facc_abs += fabsf(delta); facc_r += r;
-            uint32_t blk = BLK_STEP;
-            if (term) { n_ep += 1; sum_len += ep; ep = 0; }
-            if (trunc) { n_ep += 1; n_trunc += 1; sum_len += ep; ep = 0; blk = BLK_RESET; }
-            if (term || trunc) {                            // the restart state is where the sample is taken
-                Dom::reset(ns);
-                ac_project<Bas>(ns, phi_n);
-            }
-            // ---- policy.sample(rng, s') with the UPDATED theta
-            ac_probs<A, F, PK>(c, th, phi_n, p_s);
-            const U4 x = draw(c.seed, gid, t, blk);
-            a = sample_probs<A>(p_s, x.z);
-#pragma unroll
-            for (int d = 0; d < D; ++d) s[d] = ns[d];
-        };
-        int k = 0;
-        for (; k + 1 < n_steps; k += 2) {
-            one_step(phi_a, phi_b, t0 + (uint64_t)k);
-            one_step(phi_b, phi_a, t0 + (uint64_t)k + 1);
-        }
-        if (k < n_steps) one_step(phi_a, phi_b, t0 + (uint64_t)k);
-        sum_abs = (double)facc_abs; sum_r = (double)facc_r;
-#pragma unroll
-        for (int d = 0; d < D; ++d) c.state[(int64_t)d * N + i] = s[d];
-        c.action[i] = a;
-        c.ep_step[i] = ep;
-        ac_store<1, F, PK>(w, c.W, N, i);
-        ac_store<A, F, PK>(th, theta, N, i);
+        ping_pong(phi_a, phi_b, t0, n_steps, [&](const Phi& phi_s, Phi& phi_n, uint64_t t) {
+            Transition<D> tr = env.template step<Dom>();
+            ac_project<Bas>(tr.ns, phi_n);                  // s' itself, the terminal state included: TDCritic reads V(s')
+            const float delta = tdac_step<A, F, PK>(c, w, phi_s, phi_n, p_s, env.a, tr.r, tr.term, [&](const float (&sa)[A]) { th.axpy(sa, phi_s); });
+            // ---- policy.sample(rng, s') with the UPDATED theta; the restart state is projected on terminal and truncated steps only
+            restart_then_sample<Dom>(c, env, tally, tr, delta, t,
+                [&](const float (&ns)[D], bool ended) { if (ended) ac_project<Bas>(ns, phi_n); ac_probs<A, F, PK>(c, th, phi_n, p_s); },
+                [&](const U4& x) { return sample_probs<A>(p_s, x.z); });
+        });
+        env.store(c, i);
+        mat_store<1, F, PK>(w, c.W, N, i);
+        mat_store<A, F, PK>(th, theta, N, i);
     }
-    if (stats) block_stats_accumulate(stats, n_ep, n_trunc, sum_len, sum_abs, sum_r);
+    tally.hand_over(stats);
 }
 
 // TD::handle then ActorCritic::handle (tdac.rs's order) on caller-supplied transitions: transition i is learner i's
@@ -159,21 +126,17 @@ __global__ __launch_bounds__(kBlock) void k_handle_tdac(Common c, float* __restr
     if (i >= Mn) return;
     const int64_t N = c.n_envs;
     constexpr bool PK = (RSRL_PK != 0) && (F % 4 == 0);
-    float s[D], ns[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) { s[d] = from[(int64_t)d * Mn + i]; ns[d] = to[(int64_t)d * Mn + i]; }
-    const int a = clamp_action<A>(act[i]);
-    const float r = rew[i];
-    const bool term = termf[i] != 0;
+    Given<D> tr;
+    tr.template load<A>(from, act, rew, to, termf, Mn, i);
     PhiBuf<F, PK> phi_s, phi_n;
-    ac_project<Bas>(s, phi_s);
-    ac_project<Bas>(ns, phi_n);
+    ac_project<Bas>(tr.s, phi_s);
+    ac_project<Bas>(tr.ns, phi_n);
     float p_s[A];
     tdac_probs_mem<A, F, PK>(c, theta, N, i, phi_s, p_s);
     WBuf<1, F, PK> w;
-    ac_load<1, F, PK>(w, c.W, N, i);
-    const float delta = tdac_step<A, F, PK>(c, w, phi_s, phi_n, p_s, a, r, term, [&](const float (&sa)[A]) { tdac_actor_mem<A, F, PK>(theta, N, i, sa, phi_s); });
-    ac_store<1, F, PK>(w, c.W, N, i);
+    mat_load<1, F, PK>(w, c.W, N, i);
+    const float delta = tdac_step<A, F, PK>(c, w, phi_s, phi_n, p_s, tr.a, tr.r, tr.term, [&](const float (&sa)[A]) { tdac_actor_mem<A, F, PK>(theta, N, i, sa, phi_s); });
+    mat_store<1, F, PK>(w, c.W, N, i);
     if (td_out) td_out[i] = delta;
 }
 

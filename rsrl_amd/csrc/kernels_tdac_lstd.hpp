@@ -41,11 +41,11 @@ struct TdacLstdLane {
 
     __device__ __forceinline__ void load(const TdacLstdState& ts, int64_t N, int64_t i, int r) {
         L.load(ts.ls, i, r);
-        ac_load<1, F, PK>(col, ts.theta + (int64_t)column(r) * F * N, N, i);
+        mat_load<1, F, PK>(col, ts.theta + (int64_t)column(r) * F * N, N, i);
     }
     __device__ __forceinline__ void store(const TdacLstdState& ts, int64_t N, int64_t i, int r) const {
         L.store(ts.ls, i, r);
-        if (r < A) ac_store<1, F, PK>(col, ts.theta + (int64_t)r * F * N, N, i);
+        if (r < A) mat_store<1, F, PK>(col, ts.theta + (int64_t)r * F * N, N, i);
     }
 
     // pi_th(s) = softmax(th^T phi / tau): lane b's preference, handed round the group
