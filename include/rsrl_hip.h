@@ -228,7 +228,9 @@ typedef struct {
     double   lr;                 /* SGD(lr)                                                   */
     double   alpha;              /* ExpectedSARSA.alpha (expected_sarsa.rs:26,64)             */
     double   epsilon;            /* EpsilonGreedy.epsilon (pub field, epsilon_greedy.rs:19)  */
-    double   tau;                /* Softmax.tau (softmax.rs:52); |tau| < 1e-7 is rejected (:63-66) */
+    double   tau;                /* Softmax.tau (softmax.rs:52); |tau| < 1e-7 is rejected (:63-66).  POSITIVE only: the reference admits any
+                                    non-zero tau, this library refuses tau < 0 with RSRL_HIP_EINVAL -- the kernels evaluate
+                                    exp((q - max q) / tau), which overflows fp32 for tau < 0 once (max q - min q) / |tau| > 88.7 */
     uint32_t steps_per_launch;   /* fuse depth of rsrl_hip_train (0 = library default: 4096 for the register-resident loops,
                                     256 for the memory-resident and wave-family ones). 1 = one batch-step per launch:
                                     the ctx then keeps W learner-major and streams it once per step (the 608 B/env-step
@@ -247,7 +249,7 @@ typedef struct {
                                     target under an EpsilonGreedy behaviour = off-policy ExpectedSARSA                   */
     int32_t  exchange;           /* rsrl_exchange: how ranks exchange the shared-W delta (rsrl_hip_comm_init)            */
     double   agent_epsilon;      /* EpsilonGreedy.epsilon of the agent's policy                                          */
-    double   agent_tau;          /* Softmax.tau of the agent's policy                                                    */
+    double   agent_tau;          /* Softmax.tau of the agent's policy; positive only, as `tau`                           */
     double   sigma;              /* QSigma.sigma in [0, 1]: 1 = SARSA-like sampling, 0 = tree backup (q_sigma.rs:66-72)          */
     int32_t  n_steps;            /* QSigma: Backup::new(n_steps), 1..32 (q_sigma.rs:94-104).  RSRL_ILSTD / RSRL_ILSTD_ACTOR_CRITIC: iLSTD's n_updates, the
                                     rounds of solve() per transition, 1..32                                                      */
@@ -561,7 +563,7 @@ int rsrl_hip_rollout_trajectory(rsrl_hip_ctx* ctx, int64_t step_limit, int64_t M
 /* Domain::rollout with ANY of the four policies as the closure, s -> policy.sample(rng, s)  (lib.rs:448-479 takes any
  * FnMut(&S) -> A; policies/mod.rs:65-78): an epsilon-greedy or softmax evaluation run next to the greedy one.  `policy` is an
  * rsrl_policy over the ctx's Q function with its own parameters (epsilon for RSRL_EPSILON_GREEDY, tau for RSRL_SOFTMAX; the ctx's
- * behaviour policy is not touched).  Outputs as rsrl_hip_rollout_trajectory (every one but n_states_out optional).  The draws
+ * behaviour policy is not touched; tau > 0 as in the config: a negative Softmax temperature is RSRL_HIP_EINVAL).  Outputs as rsrl_hip_rollout_trajectory (every one but n_states_out optional).  The draws
  * are a stream of their own, addressed by (number of rollout_policy calls made on the ctx so far, action selection k, global
  * learner id): a call is reproducible, successive calls are independent samples.  The call counter belongs to the ctx OBJECT: it starts
  * at 0 when the ctx is created and is neither saved by rsrl_hip_save_weights nor changed by rsrl_hip_load_weights / rsrl_hip_reset -- the n-th

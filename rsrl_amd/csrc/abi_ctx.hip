@@ -171,9 +171,12 @@ static int check_config(const rsrl_hip_config& cfg) {
     if (cfg.policy < 0 || cfg.policy > RSRL_RANDOM) return fail(RSRL_HIP_EINVAL, "unknown policy %d", cfg.policy);
     // Softmax::new panics for |tau| < 1e-7 (policies/softmax.rs:63-66)
     if (cfg.policy == RSRL_SOFTMAX && std::fabs(cfg.tau) < 1e-7) return fail(RSRL_HIP_EINVAL, "Tau parameter in Softmax must be non-zero.");
+    // the reference admits any non-zero tau; the kernels evaluate the max-shifted form exp((q - max q) / tau), whose exponents are >= 0 for tau < 0
+    if (cfg.policy == RSRL_SOFTMAX && cfg.tau < 0.0) return fail(RSRL_HIP_EINVAL, NEGATIVE_TAU_MSG, "tau", cfg.tau);
     if (cfg.weight_dtype != RSRL_W_F32 && cfg.weight_dtype != RSRL_W_BF16) return fail(RSRL_HIP_EINVAL, "unknown weight dtype %d", cfg.weight_dtype);
     if (cfg.agent_policy < -1 || cfg.agent_policy > RSRL_RANDOM) return fail(RSRL_HIP_EINVAL, "unknown agent policy %d", cfg.agent_policy);
     if (cfg.agent_policy == RSRL_SOFTMAX && std::fabs(cfg.agent_tau) < 1e-7) return fail(RSRL_HIP_EINVAL, "Tau parameter in Softmax must be non-zero.");
+    if (cfg.agent_policy == RSRL_SOFTMAX && cfg.agent_tau < 0.0) return fail(RSRL_HIP_EINVAL, NEGATIVE_TAU_MSG, "agent_tau", cfg.agent_tau);
     if (cfg.agent_policy == RSRL_EPSILON_GREEDY && !(cfg.agent_epsilon >= 0.0 && cfg.agent_epsilon <= 1.0))
         return fail(RSRL_HIP_EINVAL, "agent_epsilon must be in [0,1]");
     if (cfg.exchange != RSRL_EXCHANGE_RCCL && cfg.exchange != RSRL_EXCHANGE_PEER && cfg.exchange != RSRL_EXCHANGE_AUTO) return fail(RSRL_HIP_EINVAL, "unknown exchange %d", cfg.exchange);

@@ -630,6 +630,7 @@ int rsrl_hip_rollout_policy(rsrl_hip_ctx* c, int policy, double epsilon, double 
     if (policy < 0 || policy > RSRL_RANDOM) return fail(RSRL_HIP_EINVAL, "unknown policy %d", policy);
     if (policy == RSRL_EPSILON_GREEDY && !(epsilon >= 0.0 && epsilon <= 1.0)) return fail(RSRL_HIP_EINVAL, "epsilon must be in [0,1]");      // gen_bool panics otherwise
     if (policy == RSRL_SOFTMAX && std::fabs(tau) < 1e-7) return fail(RSRL_HIP_EINVAL, "Tau parameter in Softmax must be non-zero.");     // softmax.rs:63-66
+    if (policy == RSRL_SOFTMAX && tau < 0.0) return fail(RSRL_HIP_EINVAL, NEGATIVE_TAU_MSG, "tau", tau);
     RolloutPolicy rp{};
     rp.sample = 1; rp.pp.kind = policy;
     const double v = epsilon * 16777216.0;

@@ -132,6 +132,10 @@ bool sparse_trace_scatter_allow_lds(int n_tilings, int bytes);
 extern thread_local std::string g_last_error;      // (abi_ctx.hip)
 
 int fail(int code, const char* fmt, ...);           // records the message for rsrl_hip_last_error() and returns `code` (abi_ctx.hip)
+// Softmax with tau < 0 (create's tau / agent_tau, the policy rollout's tau); arguments: the field's name, its value
+#define NEGATIVE_TAU_MSG "%s = %g: only positive Softmax temperatures are evaluated -- the kernels compute exp((q - max q) / tau), whose exponents are " \
+                         ">= 0 for tau < 0 and overflow fp32 once (max q - min q) / |tau| exceeds 88.7 (inf / inf), where the reference's f64 form " \
+                         "still returns ordinary probabilities"
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
         hipError_t _e = (expr);                                                                    \

@@ -112,3 +112,34 @@ def test_learner_ids_must_fit_32_bits():
             ra.Context(n_envs=n, env_offset=off).close()
         except ra.RsrlHipError as e:
             assert e.code == -2 and "device" in str(e), (n, off, str(e))
+
+
+def test_negative_softmax_temperatures_are_refused():
+    """tau < 0 is EINVAL wherever a Softmax reads it (the behaviour policy's tau, the agent's own agent_tau; the Gibbs-actor agents require Softmax), with
+    the reason; |tau| < 1e-7 keeps the reference's own message; a policy that does not read tau admits any value.  Admitted configurations answer EHIP
+    ("no device") without a GPU, or become a ctx with one"""
+    import rsrl_amd as ra
+
+    def create(**kw):
+        try:
+            ra.Context(n_envs=4, **kw).close()
+            return 0, ""
+        except ra.RsrlHipError as e:
+            return e.code, str(e)
+
+    why = "only positive Softmax temperatures are evaluated"
+    for kw in (dict(policy=ra.SOFTMAX, tau=-1.0), dict(policy=ra.SOFTMAX, tau=-0.05), dict(policy=ra.SOFTMAX, tau=-1e-7), dict(policy=ra.SOFTMAX, tau=float("-inf")),
+               dict(algo=ra.SARSA, policy=ra.EPSILON_GREEDY, agent_policy=ra.SOFTMAX, agent_tau=-0.5),
+               dict(algo=ra.EXPECTED_SARSA, policy=ra.SOFTMAX, tau=1.0, agent_policy=ra.SOFTMAX, agent_tau=-2.0),
+               dict(order=3, algo=ra.ACTOR_CRITIC, policy=ra.SOFTMAX, tau=-1.0), dict(order=3, algo=ra.TD_ACTOR_CRITIC, policy=ra.SOFTMAX, tau=-1.0),
+               dict(order=3, algo=ra.REINFORCE, policy=ra.SOFTMAX, tau=-0.7), dict(order=1, algo=ra.ILSTD_ACTOR_CRITIC, n_steps=2, policy=ra.SOFTMAX, tau=-1.0)):
+        rc, msg = create(**kw)
+        assert rc == -1 and why in msg and "overflow fp32" in msg, (kw, rc, msg)
+        assert ("agent_tau" in msg) == ("agent_tau" in kw), (kw, msg)
+    for kw in (dict(policy=ra.SOFTMAX, tau=-1e-8), dict(policy=ra.SOFTMAX, tau=0.0), dict(algo=ra.SARSA, agent_policy=ra.SOFTMAX, agent_tau=-1e-9)):
+        rc, msg = create(**kw)
+        assert rc == -1 and "Tau parameter in Softmax must be non-zero" in msg, (kw, rc, msg)
+    for kw in (dict(policy=ra.SOFTMAX, tau=1e-7), dict(policy=ra.SOFTMAX, tau=1e6), dict(policy=ra.GREEDY, tau=-1.0), dict(policy=ra.EPSILON_GREEDY, tau=-1.0, agent_tau=-1.0),
+               dict(algo=ra.SARSA, policy=ra.SOFTMAX, tau=0.5, agent_policy=ra.GREEDY, agent_tau=-3.0)):
+        rc, msg = create(**kw)
+        assert rc in (0, -2) and (rc == 0 or "device" in msg), (kw, rc, msg)
