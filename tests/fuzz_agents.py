@@ -26,7 +26,8 @@ import rsrl_amd as ra  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
 import fuzz_parity as fp  # noqa: E402
 from tests import hiv_numpy as hv  # noqa: E402
-from tests.ac_numpy import ac_rule  # noqa: E402
+from tests.ac_numpy import ac_rule, near_boundary  # noqa: E402
+from tests.agent_contract import diff, learner_state, rand_states, snapshot, trait_loop  # noqa: E402
 from tests.lstd_numpy import ilstd, near_tie_band, recursive_lstd  # noqa: E402
 from tests.reinforce_numpy import reinforce_batch  # noqa: E402
 from tests.tdac_numpy import tdac_rule  # noqa: E402
@@ -74,17 +75,6 @@ def sample(rng, idx=None):
     return kw
 
 
-def rand_states(domain, n, rng):
-    lo, hi = (HIV_LO, HIV_HI) if domain == 3 else orc.domain_bounds(domain)
-    return rng.uniform(lo, hi, size=(n, len(lo))).T.astype(np.float32)
-
-
-def near_boundary(p, x, margin=1e-5):
-    """the draw's uniform lies within margin of a cumulative-probability boundary: an fp32 rounding may pick the neighbour"""
-    u = (int(x[2]) >> 8) / 16777216.0
-    return bool(np.min(np.abs(np.cumsum(p)[:-1] - u), initial=1.0) < margin)
-
-
 def hiv_rule(algo, W, phi_s, phi_n, a, r, gamma, alpha, eps, x_inner):
     """the one-step agents' TD error and the error sent on, f64 (tests/test_gpu_hiv.py; HIVTreatment never terminates)"""
     qs, qn = W.T @ phi_s, W.T @ phi_n
@@ -103,24 +93,6 @@ def hiv_rule(algo, W, phi_s, phi_n, a, r, gamma, alpha, eps, x_inner):
     td = r + gamma * qn[ast] - qs[a]
     d = max(td - alpha * (qs[ast] - qs[a]), td - alpha * (qn[nast] - qn[a]))
     return d, alpha * d
-
-
-def learner_state(c, i):
-    """everything one learner learns, as arrays (bitwise comparisons)"""
-    al = c.cfg.algo
-    if al in (18, 19):
-        th, mat, mu = c.get_lstd_state(i)
-        return [th, mat] + ([] if mu is None else [mu])
-    out = [] if al == ra.REINFORCE else [c.get_weights(i)]          # (REINFORCE has no value function; BaselineREINFORCE's is its baseline)
-    if al in (10, 11, 13, 15, 16):
-        out.append(c.get_policy_weights(i))
-    if al in (15, 16):
-        out.append(c.get_behaviour_weights(i))
-    return out
-
-
-def same_arrays(xs, ys):
-    return len(xs) == len(ys) and all(np.array_equal(np.asarray(x).view(np.uint8), np.asarray(y).view(np.uint8)) for x, y in zip(xs, ys))
 
 
 def randomise(c, rng, i):
@@ -148,7 +120,7 @@ def f64_leg(c, kw, rng, worst):
     for rnd in range(int(rng.integers(2, 4))):
         M = int(rng.choice([1, int(rng.integers(1, N)) if N > 1 else 1, N]))
         if dom != 3:
-            c.states = rand_states(dom, N, rng)
+            c.states = rand_states(orc, dom, N, rng)
         a = rng.integers(0, c.A, size=N).astype(np.int32)
         frm, nxt, rew, term = c.domain_step(a)
         if dom != 3:
@@ -156,16 +128,16 @@ def f64_leg(c, kw, rng, worst):
         watch = sorted(set(list(range(M, min(N, M + 70))) + [N - 1] + list(rng.integers(M, N, size=8) if M < N else [])) - set(range(M)))
         before = {j: learner_state(c, j) for j in watch}
         rep = sorted(set([0, M - 1] + list(rng.integers(0, M, size=6))))
-        start = {i: learner_state(c, i) for i in rep}
+        start = {i: list(learner_state(c, i).values()) for i in rep}
         t = c.step_count
         td = c.handle(frm[:, :M], a[:M], rew[:M], nxt[:, :M], term[:M])
         for j in watch:
-            if not same_arrays(learner_state(c, j), before[j]):
+            if diff(learner_state(c, j), before[j]):
                 bad.append(f"round {rnd}: learner {j} >= M = {M} changed")
                 break
         for i in rep:
             r, tm, ai = float(rew[i]), bool(term[i]), int(a[i])
-            got = learner_state(c, i)
+            got = list(learner_state(c, i).values())
             if dom == 3:
                 phi_s, phi_n = hv.fourier(frm[:, i:i + 1], order, HIV_LO, HIV_HI)[:, 0], hv.fourier(nxt[:, i:i + 1], order, HIV_LO, HIV_HI)[:, 0]
             else:
@@ -242,7 +214,7 @@ def batch_leg(c, kw, rng, worst):
     Ts = {i: c.get_policy_weights(i) for i in rep}
     Bs = {i: c.get_weights(i) for i in rep} if base else None
     thb0, g0 = {i: c.get_behaviour_weights(i) for i in rep}, c.return_carry
-    S = np.stack([rand_states(dom, N, rng) for _ in range(T)])
+    S = np.stack([rand_states(orc, dom, N, rng) for _ in range(T)])
     A = rng.integers(0, c.A, size=(T, N)).astype(np.int32)
     R = rng.normal(0.0, 1.0, size=(T, N)).astype(np.float32)
     L = rng.integers(0, T + 1, size=N).astype(np.uint32)
@@ -276,30 +248,6 @@ def batch_leg(c, kw, rng, worst):
     return bad
 
 
-def snapshot(c, learners):
-    out = [c.states, c.actions, c.episode_steps]
-    for i in learners:
-        out += learner_state(c, i)
-    if c.cfg.algo in (15, 16):
-        out.append(c.return_carry)
-    if c.cfg.domain == 3:
-        out.append(c.get_hidden_states())
-    return out
-
-
-def trait_loop(c, K, cap):
-    ep = c.episode_steps.astype(np.int64)
-    for _ in range(K):
-        frm, nxt, rew, term = c.domain_step(c.actions)
-        c.handle(frm, c.actions, rew, nxt, term)
-        ep += 1
-        mask = (term.astype(bool) | (ep >= cap)).astype(np.uint8)
-        c.domain_reset(mask)
-        ep[mask == 1] = 0
-        c.policy_sample()
-    c.episode_steps = ep.astype(np.uint32)
-
-
 def self_leg(kw, rng, legs):
     """-> findings: random splits with queries between, the trait loop, shards, a checkpoint -- each against one uninterrupted run"""
     bad = []
@@ -320,14 +268,14 @@ def self_leg(kw, rng, legs):
             if j + 1 < len(calls):
                 b_, m_ = fp.query_leg(c, rng, td, counter)
                 bad += b_; made += m_
-        if not same_arrays(snapshot(c, look), ref) or c.checksum() != ck:
+        if diff(snapshot(c, look), ref) or c.checksum() != ck:
             bad.append(f"train {calls} with queries {made} != train({K})")
         legs["split+query"] = legs.get("split+query", 0) + 1
     if kw["algo"] in TRAIT_LOOP and rng.random() < 0.5:
         with ra.Context(**kw) as c:
             c.reset()
-            trait_loop(c, K, kw["max_episode_steps"] or (1 << 62))
-            if not same_arrays(snapshot(c, look), ref):
+            trait_loop(c, K, kw["max_episode_steps"])
+            if diff(snapshot(c, look), ref):
                 bad.append("the host trait loop != train")
         legs["trait"] = legs.get("trait", 0) + 1
     if N >= 3 and rng.random() < 0.5:
@@ -343,8 +291,8 @@ def self_leg(kw, rng, legs):
             cf.train(K, want_stats=False)
             okp = np.array_equal(np.concatenate([parts[0][0], parts[1][0]], axis=1), cf.states) and \
                 np.array_equal(np.concatenate([parts[0][1], parts[1][1]]), cf.actions) and \
-                same_arrays(parts[0][2], learner_state(cf, 0)) and same_arrays(parts[0][3], learner_state(cf, n1 - 1)) and \
-                same_arrays(parts[1][2], learner_state(cf, n1)) and same_arrays(parts[1][3], learner_state(cf, N - 1))
+                not diff(parts[0][2], learner_state(cf, 0)) and not diff(parts[0][3], learner_state(cf, n1 - 1)) and \
+                not diff(parts[1][2], learner_state(cf, n1)) and not diff(parts[1][3], learner_state(cf, N - 1))
         if not okp:
             bad.append(f"shards {n1} + {N - n1} != the unsharded run")
         legs["shard"] = legs.get("shard", 0) + 1
@@ -366,7 +314,7 @@ def self_leg(kw, rng, legs):
                 for i in range(N):
                     c2.set_behaviour_weights(c.get_behaviour_weights(i), i)
             c2.train(K - k1, want_stats=False)
-            if not same_arrays(snapshot(c2, look), ref):
+            if diff(snapshot(c2, look), ref):
                 bad.append(f"checkpoint at {k1} resumed != train({K})")
         legs["ckpt"] = legs.get("ckpt", 0) + 1
     return bad

@@ -23,6 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import rsrl_amd as ra  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
+from tests.agent_contract import diff, join_shards, learner_state, rand_states, snapshot, trait_loop  # noqa: E402
 from tests.lstd_numpy import near_tie_band  # noqa: E402
 from tests.tdac_lstd_numpy import tdac_lstd_rule  # noqa: E402
 
@@ -37,22 +38,6 @@ def draw_config(rng):
                 env_offset=int(rng.choice([0, 0, int(rng.integers(1, 1 << 20))])), gamma=float(rng.uniform(0.8, 0.999)),
                 lr=float(10 ** rng.uniform(-4, -1.3)), alpha=float(10 ** rng.uniform(-3, -0.5)), tau=float(rng.uniform(0.3, 2.0)),
                 n_steps=int(rng.integers(1, 5)), max_episode_steps=int(rng.choice([0, 7, 23, 200])), steps_per_launch=int(rng.choice([0, 0, 1, 5, 64])))
-
-
-def state_of(c):
-    out = [[], [], [], []]
-    for i in range(c.N):
-        for k, x in enumerate(c.get_lstd_state(i) + (c.get_policy_weights(i),)):
-            out[k].append(x)
-    return tuple(np.stack(x) for x in out)
-
-
-def snapshot(c):
-    return state_of(c) + (c.states, c.actions, c.episode_steps)
-
-
-def same(s1, s2):
-    return all(np.shape(x) == np.shape(y) and np.asarray(x).tobytes() == np.asarray(y).tobytes() for x, y in zip(s1, s2))
 
 
 def randomise(c, rng, also=()):
@@ -74,18 +59,16 @@ def leg_f64(kw, rng):
     ikw = dict(kw, algo=ra.ILSTD, policy=ra.RANDOM, alpha=kw["lr"])
     with ra.Context(**kw) as c, ra.Context(**ikw) as v:
         init = randomise(c, rng, also=(v,))
-        lo, hi = orc.domain_bounds(kw["domain"])
-        c.states = rng.uniform(lo, hi, size=(N, len(lo))).T.astype(np.float32)
+        c.states = rand_states(orc, kw["domain"], N, rng)
         a = rng.integers(0, c.A, size=N).astype(np.int32)
         frm, nxt, rew, term = c.domain_step(a)
         term = (term | (rng.random(N) < 0.25)).astype(np.uint8)
         M = int(rng.choice([1, N, int(rng.integers(1, N + 1))]))
-        before = state_of(c)
+        before = [learner_state(c, i) for i in range(M, N)]
         sl = (slice(None), slice(0, M))
         td = c.handle(np.ascontiguousarray(frm[sl]), a[:M], rew[:M], np.ascontiguousarray(nxt[sl]), term[:M])
         td_v = v.handle(np.ascontiguousarray(frm[sl]), a[:M], rew[:M], np.ascontiguousarray(nxt[sl]), term[:M])
-        after = state_of(c)
-        if not all(x[M:].tobytes() == y[M:].tobytes() for x, y in zip(before, after)):
+        if any(diff(before[i - M], learner_state(c, i)) for i in range(M, N)):
             bad.append("learners M..N-1 moved")
         if td.tobytes() != td_v.tobytes() or any(x.tobytes() != y.tobytes() for i in range(M) for x, y in zip(c.get_lstd_state(i), v.get_lstd_state(i))):
             bad.append("critic != iLSTD ctx")
@@ -100,28 +83,14 @@ def leg_f64(kw, rng):
             if abs(float(td[i]) - d) > 2.0 ** -22 * (1.0 + abs(d)):
                 bad.append(f"delta of learner {i}")
             if not any(near_tie_band(m) for m in mus):
-                for g, w in zip((after[0][i], after[1][i], after[2][i]), (th2, A2, mu2)):
+                for g, w in zip(c.get_lstd_state(i), (th2, A2, mu2)):
                     if np.max(np.abs(g - w)) > tol * (1.0 + np.max(np.abs(w))):
                         bad.append(f"f64 state of learner {i}")
             old = Th.astype(np.float64)
             bound = 3e-6 * (1 + np.max(np.abs(T2 - old))) * np.abs(phi_s).sum() + 3e-6 * np.max(np.abs(old))
-            if np.max(np.abs(after[3][i] - T2)) > bound:
+            if np.max(np.abs(c.get_policy_weights(i) - T2)) > bound:
                 bad.append(f"actor of learner {i}")
     return bad
-
-
-def trait_loop(c, K, cap):
-    ep = c.episode_steps.astype(np.int64)
-    for _ in range(K):
-        frm, nxt, rew, term = c.domain_step(c.actions)
-        c.handle(frm, c.actions, rew, nxt, term)
-        ep += 1
-        mask = term.astype(bool) | ((ep >= cap) if cap > 0 else False)
-        mask = np.asarray(mask, dtype=np.uint8)
-        c.domain_reset(mask)
-        ep[mask == 1] = 0
-        c.policy_sample()
-    c.episode_steps = ep.astype(np.uint32)
 
 
 def leg_self(kw, rng):
@@ -140,12 +109,12 @@ def leg_self(kw, rng):
             done += k
             S = c.states
             c.policy_probs(S); c.policy_sample(S); c.q_evaluate(S)
-        if not same(snapshot(c), ref):
+        if diff(snapshot(c), ref):
             bad.append("splits with queries")
     with ra.Context(**kw) as c:
         c.reset()
         trait_loop(c, K, cap)
-        if not same(snapshot(c), ref):
+        if diff(snapshot(c), ref):
             bad.append("trait loop")
     if N >= 2:
         h, parts = N // 2, []
@@ -154,8 +123,7 @@ def leg_self(kw, rng):
                 c.reset()
                 c.train(K)
                 parts.append(snapshot(c))
-        joined = tuple(np.concatenate([parts[0][j], parts[1][j]], axis=0 if j < 4 else -1) for j in range(7))
-        if not same(joined, ref):
+        if diff(join_shards(*parts), ref):
             bad.append("shards")
     with tempfile.TemporaryDirectory() as tmp, ra.Context(**kw) as a, ra.Context(**kw) as b:
         k1 = int(rng.integers(1, K)) if K > 1 else 1
@@ -166,7 +134,7 @@ def leg_self(kw, rng):
         b.load_weights(path)
         b.states, b.actions, b.episode_steps = a.states, a.actions, a.episode_steps
         b.train(K - k1)
-        if K - k1 >= 0 and not same(snapshot(b), ref):
+        if K - k1 >= 0 and diff(snapshot(b), ref):
             bad.append("checkpoint resume")
     return bad
 

@@ -2,13 +2,13 @@
 compare against is the gradient of log softmax(theta^T phi)[a] (a finite-difference check that pins the restatement independently of the device)."""
 import os
 import re
-import subprocess
 
 import numpy as np
 
 import rsrl_amd
 from rsrl_amd import _abi
 from tests.ac_numpy import actor_step, softmax
+from tests.agent_contract import compile_example
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -24,9 +24,7 @@ def test_header_declares_the_algos_and_the_policy_weight_exports():
 
 
 def test_a2c_example_compiles(tmp_path):
-    obj = os.path.join(str(tmp_path), "a2c.o")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-c", os.path.join(ROOT, "examples", "a2c.cpp"), "-o", obj], check=True, timeout=300)
-    assert os.path.getsize(obj) > 0
+    compile_example(tmp_path, "a2c")
 
 
 def test_actor_step_is_the_gradient_of_log_pi():

@@ -2,7 +2,6 @@
 restatement of the rule, the policy side reading theta and the value side reading W, the driver loop against a restated loop, train against the
 trait-granular loop / launch depths / shards bit for bit, checkpoints, the checksum, the refusals and the C++ example."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -10,10 +9,10 @@ import pytest
 import rsrl_amd
 from rsrl_amd import RsrlHipError
 from tests.ac_numpy import ac_restated_loop as _restated_loop, ac_rule, near_boundary
+from tests.agent_contract import check_checkpoint_resume, check_foreign_checkpoints_refused, check_train_invariance, rand_states, run_example
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 AC, QAC = rsrl_amd.ACTOR_CRITIC, rsrl_amd.Q_ACTOR_CRITIC
 REG = [(rsrl_amd.MOUNTAIN_CAR, o) for o in (1, 2, 3, 4, 5)] + [(rsrl_amd.CART_POLE, 1), (rsrl_amd.ACROBOT, 1)]
 
@@ -22,11 +21,6 @@ def ctx(**kw):
     base = dict(domain=rsrl_amd.MOUNTAIN_CAR, order=3, algo=AC, policy=rsrl_amd.SOFTMAX, n_envs=32, seed=5, gamma=0.95, lr=0.05, alpha=0.3, tau=1.0)
     base.update(kw)
     return rsrl_amd.Context(**base)
-
-
-def rand_states(orc, domain, n, rng):
-    lo, hi = orc.domain_bounds(domain)
-    return rng.uniform(lo, hi, size=(n, len(lo))).T.astype(np.float32)
 
 
 def randomise(c, rng, scale=0.3):
@@ -144,87 +138,22 @@ def test_driver_loop_against_a_restated_loop(orc, algo):
         assert episodes > truncated > 0                               # terminals and caps both happened
 
 
-def _trait_loop(c, K, cap):
-    ep = c.episode_steps.astype(np.int64)
-    for _ in range(K):
-        frm, nxt, rew, term = c.domain_step(c.actions)
-        c.handle(frm, c.actions, rew, nxt, term)
-        ep += 1
-        mask = (term.astype(bool) | (ep >= cap)).astype(np.uint8)
-        c.domain_reset(mask)
-        ep[mask == 1] = 0
-        c.policy_sample()
-    c.episode_steps = ep.astype(np.uint32)
-
-
-def _snapshot(c):
-    return (np.stack([c.get_weights(i) for i in range(c.N)]), np.stack([c.get_policy_weights(i) for i in range(c.N)]), c.states, c.actions, c.episode_steps)
-
-
-def _diff(s1, s2):
-    names = ("weights", "theta", "states", "actions", "episode_steps")
-    return [n for n, x, y in zip(names, s1, s2) if not np.array_equal(x, y)]
-
-
 @pytest.mark.parametrize("algo", [AC, QAC])
 @pytest.mark.parametrize("domain,order", [(rsrl_amd.MOUNTAIN_CAR, 3), (rsrl_amd.MOUNTAIN_CAR, 5), (rsrl_amd.CART_POLE, 1), (rsrl_amd.ACROBOT, 1)])
 def test_train_is_the_trait_loop_launch_depth_and_shard_invariant(domain, order, algo):
     N, K, cap = 64, 60, 23
     kw = dict(domain=domain, order=order, algo=algo, n_envs=N, max_episode_steps=cap, tau=0.7, lr=0.02, alpha=0.2, gamma=0.97)
-    with ctx(**kw) as c:
-        c.reset()
-        st = c.train(K)
-        ref = _snapshot(c)
-        assert st["episodes"] > 0
-    with ctx(**kw) as c:
-        c.reset()
-        _trait_loop(c, K, cap)
-        assert _diff(_snapshot(c), ref) == []
-    for spl in (1, 7):
-        with ctx(steps_per_launch=spl, **kw) as c:
-            c.reset()
-            c.train(20)
-            c.train(1)
-            c.train(K - 21)
-            assert _diff(_snapshot(c), ref) == [], spl
-    shards = []
-    for off in (0, N // 2):
-        with ctx(env_offset=off, **dict(kw, n_envs=N // 2)) as c:
-            c.reset()
-            c.train(K)
-            shards.append(_snapshot(c))
-    joined = tuple(np.concatenate([shards[0][j], shards[1][j]], axis=0 if j < 2 else -1) for j in range(5))
-    assert _diff(joined, ref) == []
+    st, _ = check_train_invariance(ctx, kw, K, cap, depths=(1, 7), first_split=20)
+    assert st["episodes"] > 0
 
 
 def test_checkpoint_resumes_bitwise_and_refuses_other_agents(tmp_path):
     kw = dict(n_envs=32, order=3, max_episode_steps=17, lr=0.02, alpha=0.2, tau=0.5)
     path = os.path.join(str(tmp_path), "ac.ckpt")
-    with ctx(**kw) as a:
-        a.reset()
-        a.train(25)
-        a.save_weights(path)
-        saved = (a.states, a.actions, a.episode_steps)
-        with ctx(**kw) as b:
-            b.load_weights(path)
-            b.states, b.actions, b.episode_steps = saved
-            a.train(20)
-            b.train(20)
-            assert _diff(_snapshot(a), _snapshot(b)) == []
-            assert a.checksum() == b.checksum()
+    check_checkpoint_resume(ctx, kw, path, 25, 20, carry=("states", "actions", "episode_steps"))
     others = [dict(algo=rsrl_amd.SARSA), dict(algo=rsrl_amd.GREEDY_GQ, lr_td=0.01), dict(algo=QAC)]
-    for other in others:
-        okw = dict(kw, **other)
-        with rsrl_amd.Context(domain=rsrl_amd.MOUNTAIN_CAR, policy=rsrl_amd.SOFTMAX, **okw) as o:
-            with pytest.raises(RsrlHipError) as e:
-                o.load_weights(path)
-            assert e.value.code == -1
-            opath = os.path.join(str(tmp_path), "other.ckpt")
-            o.save_weights(opath)
-            with ctx(**kw) as b:
-                with pytest.raises(RsrlHipError) as e:
-                    b.load_weights(opath)
-                assert e.value.code == -1
+    others = [dict(kw, domain=rsrl_amd.MOUNTAIN_CAR, policy=rsrl_amd.SOFTMAX, **other) for other in others]
+    check_foreign_checkpoints_refused(ctx, kw, path, others, tmp_path)
 
 
 def test_checksum_covers_theta():
@@ -264,11 +193,7 @@ def test_refusals():
 
 
 def test_a2c_example_builds_and_runs(tmp_path):
-    exe = os.path.join(str(tmp_path), "a2c")
-    lib = os.path.join(ROOT, "rsrl_amd", "lib")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", os.path.join(ROOT, "examples", "a2c.cpp"), "-L" + lib, "-lrsrl_hip", "-Wl,-rpath," + lib, "-o", exe],
-                   check=True, timeout=300)
-    out = subprocess.run([exe, "64", "3", "200"], capture_output=True, text=True, timeout=300, check=True).stdout
+    out = run_example(tmp_path, "a2c", [64, 3, 200])
     assert "Batch 3:" in out and "OOS:" in out
     tmax = float(out.split("max |theta| of learner 0:")[1].split()[0])
     assert np.isfinite(tmax) and tmax > 0.0

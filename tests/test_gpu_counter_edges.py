@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 import rsrl_amd as ra
+from tests.agent_contract import trait_loop
 from tests.edge_helpers import (AB, BF16, E32, E33, EG, LAM, MC, OFFSETS, SHARED, SM, T_ALL, T_TWO, TILE, feats as _feats, install_counter,
                                 oracle_kwargs)
 
@@ -270,20 +271,6 @@ def test_ids_past_32_bits_are_refused():
 
 
 # ---- the trait-granular loop: policy_sample() addresses batch-step step_count - 1, handle's inner draw step_count
-def _trait_loop(c, k, cap):
-    ep = c.episode_steps.astype(np.int64)
-    for _ in range(k):
-        a = c.actions
-        frm, nxt, rew, term = c.domain_step(a)
-        c.handle(frm, a, rew, nxt, term)
-        ep += 1
-        mask = (term.astype(bool) | (ep >= cap)).astype(np.uint8)
-        c.domain_reset(mask)
-        ep[mask == 1] = 0
-        c.policy_sample()
-    c.episode_steps = ep.astype(np.uint32)
-
-
 @pytest.mark.parametrize("t0", T_TWO, ids=_label)
 @pytest.mark.parametrize("name,spl", [("regstep-lm-sarsa-mc3", 1), ("tile-sarsa-ab", 0), ("generic-sarsa-ab2", 0)])
 def test_trait_loop_crosses_the_edge_bitwise_vs_reference_order_oracle(orc, tmp_path, name, spl, t0):
@@ -293,12 +280,12 @@ def test_trait_loop_crosses_the_edge_bitwise_vs_reference_order_oracle(orc, tmp_
     run, _ = oracle_run(orc, dict(cs, method="train"), kw, t0, [12])
     with ra.Context(**kw) as c:
         install_counter(c, t0, tmp_path)
-        _trait_loop(c, 12, CAP)
+        trait_loop(c, 12, CAP)
         assert differences(c, run, kw, "train") == [], f"{name} T0 = {t0}"
         mine = c.actions.copy()
     with ra.Context(**kw) as c:                      # reference-free: the same low counter words under another high word
         install_counter(c, t0 + (E32 if t0 < E33 - 8 else E33), tmp_path)
-        _trait_loop(c, 12, CAP)
+        trait_loop(c, 12, CAP)
         assert not np.array_equal(c.actions, mine), f"{name}: the trait loop's draws do not use the counter's high word"
 
 

@@ -9,6 +9,7 @@ import pytest
 import rsrl_amd
 from rsrl_amd import RsrlHipError
 from tests import hiv_numpy as hv
+from tests.agent_contract import check_checkpoint_resume, check_train_invariance
 
 pytestmark = pytest.mark.gpu
 
@@ -118,80 +119,18 @@ def test_driver_loop_against_a_restated_loop(orc):
         assert st["episodes"] == n_trunc == st["episodes_truncated"] and st["env_steps"] == N * K
 
 
-def _trait_loop(c, K, cap):
-    """K iterations of domain_step -> handle -> domain_reset(cap mask) -> policy_sample(NULL), the step counts kept here"""
-    ep = c.episode_steps.astype(np.int64)
-    for _ in range(K):
-        frm, nxt, rew, term = c.domain_step(c.actions)
-        c.handle(frm, c.actions, rew, nxt, term)
-        ep += 1
-        mask = (ep >= cap).astype(np.uint8)
-        c.domain_reset(mask)
-        ep[mask == 1] = 0
-        c.policy_sample()
-    c.episode_steps = ep.astype(np.uint32)          # (Domain::transition does not count steps: the loop's driver does)
-
-
-def _snapshot(c):
-    return (np.stack([c.get_weights(i) for i in range(c.N)]), c.states, c.get_hidden_states(), c.actions, c.episode_steps)
-
-
-def _diff(s1, s2):
-    """which of (weights, observations, hidden states, actions, episode steps) differ: [] when all are bitwise equal"""
-    same = [np.array_equal(s1[j], s2[j]) for j in (0, 1, 3, 4)]
-    same.insert(2, hv.bits_equal(s1[2], s2[2]))
-    return [name for name, ok in zip(("weights", "states", "hidden", "actions", "episode_steps"), same) if not ok]
-
-
 @pytest.mark.parametrize("policy", [rsrl_amd.EPSILON_GREEDY, rsrl_amd.SOFTMAX])
 @pytest.mark.parametrize("algo", [rsrl_amd.SARSA, rsrl_amd.EXPECTED_SARSA])
 def test_train_is_the_trait_loop_and_split_invariant(policy, algo):
     N, K, cap = 64, 200, 45
     kw = dict(n_envs=N, order=2, algo=algo, policy=policy, max_episode_steps=cap, epsilon=0.2, tau=0.5, lr=1e-3)
-    with ctx(**kw) as c:
-        c.reset()
-        c.train(K)
-        ref = _snapshot(c)
-    with ctx(**kw) as c:
-        c.reset()
-        _trait_loop(c, K, cap)
-        assert _diff(_snapshot(c), ref) == []
-    with ctx(steps_per_launch=7, **kw) as c:
-        c.reset()
-        c.train(50)
-        c.train(1)
-        c.train(K - 51)
-        assert _diff(_snapshot(c), ref) == []
-    shards = []
-    for off in (0, N // 2):
-        kw2 = dict(kw, n_envs=N // 2)
-        with ctx(env_offset=off, **kw2) as c:
-            c.reset()
-            c.train(K)
-            shards.append(_snapshot(c))
-    joined = tuple(np.concatenate([shards[0][j], shards[1][j]], axis=0 if j == 0 else -1) for j in range(5))
-    assert _diff(joined, ref) == []
+    check_train_invariance(ctx, kw, K, cap, depths=(7,), first_split=50)
 
 
 def test_checkpoint_resumes_bitwise(tmp_path):
     kw = dict(n_envs=32, order=3, algo=rsrl_amd.QLEARNING, policy=rsrl_amd.EPSILON_GREEDY, max_episode_steps=17, lr=1e-4)
     path = os.path.join(str(tmp_path), "hiv.ckpt")
-    with ctx(**kw) as a:
-        a.reset()
-        a.train(25)
-        a.save_weights(path)
-        saved = (a.states, a.get_hidden_states(), a.actions, a.episode_steps)
-        with ctx(**kw) as b:
-            b.load_weights(path)
-            b.states = saved[0]
-            b.set_hidden_states(saved[1])
-            b.actions = saved[2]
-            b.episode_steps = saved[3]
-            assert np.array_equal(b.states, saved[0])
-            a.train(20)
-            b.train(20)
-            assert _diff(_snapshot(a), _snapshot(b)) == []
-            assert a.checksum() == b.checksum()
+    check_checkpoint_resume(ctx, kw, path, 25, 20, carry=("states", "hidden", "actions", "episode_steps"))
 
 
 def test_rollouts_from_a_fresh_default_env():

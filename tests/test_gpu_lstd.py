@@ -2,18 +2,18 @@
 trait-granular loop / launch depths / shards bit for bit, checkpoints and the checksum over the f64 state, a long horizon replayed in numpy, the value
 side, the refusals and the C++ example."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import rsrl_amd
 from rsrl_amd import RsrlHipError
+from tests.agent_contract import (check_checkpoint_resume, check_foreign_checkpoints_refused, check_train_invariance, diff, learner_state, rand_states,
+                                  run_example)
 from tests.lstd_numpy import ilstd, near_tie_band, recursive_lstd, replay_trait_loop
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RLSTD, ILSTD = rsrl_amd.RECURSIVE_LSTD, rsrl_amd.ILSTD
 ALGOS = [RLSTD, ILSTD]
 REG = [(rsrl_amd.MOUNTAIN_CAR, o) for o in (1, 2, 3, 4, 5)] + [(rsrl_amd.CART_POLE, 1), (rsrl_amd.ACROBOT, 1)]
@@ -21,24 +21,11 @@ LOOP = [(rsrl_amd.MOUNTAIN_CAR, 1), (rsrl_amd.MOUNTAIN_CAR, 3), (rsrl_amd.MOUNTA
 EPS = np.finfo(np.float64).eps
 
 
+BASE = dict(domain=rsrl_amd.MOUNTAIN_CAR, order=3, algo=RLSTD, policy=rsrl_amd.RANDOM, n_envs=32, seed=5, gamma=0.95, alpha=0.05, n_steps=3)
+
+
 def ctx(**kw):
-    base = dict(domain=rsrl_amd.MOUNTAIN_CAR, order=3, algo=RLSTD, policy=rsrl_amd.RANDOM, n_envs=32, seed=5, gamma=0.95, alpha=0.05, n_steps=3)
-    base.update(kw)
-    return rsrl_amd.Context(**base)
-
-
-def rand_states(orc, domain, n, rng):
-    lo, hi = orc.domain_bounds(domain)
-    return rng.uniform(lo, hi, size=(n, len(lo))).T.astype(np.float32)
-
-
-def state_of(c):
-    """every learner's (theta, matrix, mu) stacked"""
-    ts, ms, us = [], [], []
-    for i in range(c.N):
-        t, m, u = c.get_lstd_state(i)
-        ts.append(t); ms.append(m); us.append(np.zeros(0) if u is None else u)
-    return np.stack(ts), np.stack(ms), np.stack(us)
+    return rsrl_amd.Context(**dict(BASE, **kw))
 
 
 def randomise(c, algo, rng):
@@ -87,9 +74,8 @@ def test_handle_against_the_f64_rule(orc, domain, order, algo):
         # iLSTD's mu update is phi_s * (pd . theta) against the literal (phi_s pd^T) theta: 16 F eps per step relative to the state's magnitude
         steps = rounds_of_handle * (1 + (n_upd if algo == ILSTD else 0))
         tol = 16.0 * F * steps * EPS
-        got = state_of(c)
         for i in np.flatnonzero(~skipped):
-            for j, (g, w) in enumerate(zip((got[0][i], got[1][i], got[2][i]), ref[i])):
+            for j, (g, w) in enumerate(zip(c.get_lstd_state(int(i)), ref[i])):
                 if w is None:
                     continue
                 scale = 1.0 + np.max(np.abs(w))
@@ -97,97 +83,37 @@ def test_handle_against_the_f64_rule(orc, domain, order, algo):
         assert skipped.sum() <= N // 4, skipped.sum()          # (counted: an |mu_j| within 1e-9 of the 1e-7 tie band)
 
 
-def _trait_loop(c, K, cap):
-    ep = c.episode_steps.astype(np.int64)
-    for _ in range(K):
-        frm, nxt, rew, term = c.domain_step(c.actions)
-        c.handle(frm, c.actions, rew, nxt, term)
-        ep += 1
-        mask = (term.astype(bool) | (ep >= cap)).astype(np.uint8)
-        c.domain_reset(mask)
-        ep[mask == 1] = 0
-        c.policy_sample()
-    c.episode_steps = ep.astype(np.uint32)
-
-
-def _snapshot(c):
-    th, m, u = state_of(c)
-    return (th, m, u, c.states, c.actions, c.episode_steps)
-
-
-def _diff(s1, s2):
-    names = ("theta", "matrix", "mu", "states", "actions", "episode_steps")
-    return [n for n, x, y in zip(names, s1, s2) if np.shape(x) != np.shape(y) or np.asarray(x).tobytes() != np.asarray(y).tobytes()]
-
-
 @pytest.mark.parametrize("algo", ALGOS)
 @pytest.mark.parametrize("domain,order", LOOP)
 def test_train_is_the_trait_loop_launch_depth_and_shard_invariant(domain, order, algo):
     N, K, cap = 64, 60, 23
     kw = dict(domain=domain, order=order, algo=algo, n_envs=N, max_episode_steps=cap, gamma=0.97, alpha=0.02, n_steps=2)
-    with ctx(**kw) as c:
-        c.reset()
-        c.timing_enable(True)
-        st = c.train(K)
-        assert c.timing_read()[2] == "k_train_lstd"
-        ref = _snapshot(c)
-        assert st["episodes"] > 0 and st["env_steps"] == N * K
-        assert np.isfinite(ref[0]).all() and np.abs(ref[0]).max() > 0
-    with ctx(**kw) as c:
-        c.reset()
-        _trait_loop(c, K, cap)
-        assert _diff(_snapshot(c), ref) == []
-    for spl in (1, 64):
-        with ctx(steps_per_launch=spl, **kw) as c:
-            c.reset()
-            c.train(20)
-            c.train(1)
-            c.train(K - 21)
-            assert _diff(_snapshot(c), ref) == [], spl
-    shards = []
-    for off in (0, N // 2):
-        with ctx(env_offset=off, **dict(kw, n_envs=N // 2)) as c:
-            c.reset()
-            c.train(K)
-            shards.append(_snapshot(c))
-    joined = tuple(np.concatenate([shards[0][j], shards[1][j]], axis=0 if j < 3 else -1) for j in range(6))
-    assert _diff(joined, ref) == []
+    st, ref = check_train_invariance(ctx, kw, K, cap, depths=(1, 64), first_split=20, kernel="k_train_lstd")
+    assert st["episodes"] > 0 and st["env_steps"] == N * K
+    assert np.isfinite(ref["lstd_theta"]).all() and np.abs(ref["lstd_theta"]).max() > 0
 
 
 @pytest.mark.parametrize("algo", ALGOS)
 def test_checkpoint_resumes_bitwise_and_the_checksum_covers_the_f64_state(tmp_path, algo):
     kw = dict(n_envs=32, order=3, algo=algo, max_episode_steps=17)
     path = os.path.join(str(tmp_path), "lstd.ckpt")
-    with ctx(**kw) as a:
-        a.reset()
-        a.train(25)
-        a.save_weights(path)
-        saved = (a.states, a.actions, a.episode_steps)
-        with ctx(**kw) as b:
-            b.load_weights(path)
-            b.states, b.actions, b.episode_steps = saved
-            assert _diff(_snapshot(a), _snapshot(b)) == []
-            assert a.checksum() == b.checksum()
-            a.train(20)
-            b.train(20)
-            assert _diff(_snapshot(a), _snapshot(b)) == []
-            assert a.checksum() == b.checksum()
-            before = b.checksum()
-            th, m, u = b.get_lstd_state(5)
-            m[3, 4] = np.nextafter(m[3, 4], np.inf)                # one ulp of one learner's matrix: the f64 state is in out[0]
-            b.set_lstd_state(th, m, u, 5)
-            assert b.checksum()[0] != before[0] and b.checksum()[1] == before[1]
+
+    def one_ulp_of_the_matrix_moves_the_checksum(a, b):
+        before = b.checksum()
+        th, m, u = b.get_lstd_state(5)
+        m[3, 4] = np.nextafter(m[3, 4], np.inf)                # one ulp of one learner's matrix: the f64 state is in out[0]
+        b.set_lstd_state(th, m, u, 5)
+        assert b.checksum()[0] != before[0] and b.checksum()[1] == before[1]
+
+    check_checkpoint_resume(ctx, kw, path, 25, 20, carry=("states", "actions", "episode_steps"), then=one_ulp_of_the_matrix_moves_the_checksum)
     with open(path, "rb") as f:
         head = f.read(72)
     F = 16
     assert int.from_bytes(head[8:12], "little") == 10 and int.from_bytes(head[52:56], "little") == 8
     assert os.path.getsize(path) == 72 + 32 * 8 * (F + F * F + (F if algo == ILSTD else 0))
     other = RLSTD if algo == ILSTD else ILSTD
-    for o_kw in (dict(algo=other, policy=rsrl_amd.RANDOM), dict(algo=rsrl_amd.TD, policy=rsrl_amd.RANDOM)):
-        with ctx(**dict(kw, **o_kw)) as o:
-            with pytest.raises(RsrlHipError) as e:
-                o.load_weights(path)
-            assert e.value.code == -1
+    others = (dict(algo=other, policy=rsrl_amd.RANDOM), dict(algo=rsrl_amd.TD, policy=rsrl_amd.RANDOM))
+    check_foreign_checkpoints_refused(ctx, kw, path, [dict(BASE, **dict(kw, **o_kw)) for o_kw in others], tmp_path)
 
 
 @pytest.mark.parametrize("algo", ALGOS)
@@ -234,9 +160,9 @@ def test_initial_state_value_side_and_refusals(orc, algo):
             assert (u is None) == (algo == RLSTD) and (u is None or not u.any())
         c.reset()
         c.train(40)
-        st = state_of(c)
+        st = [learner_state(c, i) for i in range(N)]
         c.reset()                                                 # reset restarts the episodes only
-        assert all(np.array_equal(x, y) for x, y in zip(st, state_of(c)))
+        assert all(diff(st[i], learner_state(c, i)) == [] for i in range(N))
         # get_weights = f32(theta); q_evaluate = f32(phi . theta) evaluated in f64
         S = rand_states(orc, domain, N, rng)
         for i in range(N):
@@ -272,12 +198,8 @@ def test_initial_state_value_side_and_refusals(orc, algo):
 
 
 def test_lstd_example_builds_and_runs(tmp_path):
-    exe = os.path.join(str(tmp_path), "lstd")
-    lib = os.path.join(ROOT, "rsrl_amd", "lib")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", os.path.join(ROOT, "examples", "lstd.cpp"), "-L" + lib, "-lrsrl_hip", "-Wl,-rpath," + lib, "-o", exe],
-                   check=True, timeout=300)
     for mode in ("recursive", "ilstd"):
-        out = subprocess.run([exe, "64", "2", "200", "3", mode], capture_output=True, text=True, timeout=300, check=True).stdout
+        out = run_example(tmp_path, "lstd", [64, 2, 200, 3, mode])
         assert "Batch 2:" in out and "(16 features)" in out
         tmax = float(out.split("max |theta| of learner 0:")[1].split()[0])
         assert np.isfinite(tmax) and tmax > 0.0

@@ -3,19 +3,18 @@
 train against the host trait loop / launch depths / shards bit for bit, checkpoints of an open episode, the policy side reading theta, the
 refusals and the C++ example."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import rsrl_amd
 from rsrl_amd import RsrlHipError
-from tests.ac_numpy import actor_step, near_boundary
+from tests.ac_numpy import near_boundary
+from tests.agent_contract import check_checkpoint_resume, check_foreign_checkpoints_refused, check_train_invariance, rand_states, run_example, snapshot
 from tests.reinforce_numpy import reinforce_batch, reinforce_restated_loop as _restated_loop
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ALGOS = [rsrl_amd.REINFORCE, rsrl_amd.BASELINE_REINFORCE]
 REG = [(rsrl_amd.MOUNTAIN_CAR, o) for o in (1, 2, 3, 4, 5)] + [(rsrl_amd.CART_POLE, 1), (rsrl_amd.ACROBOT, 1)]
 LOOP = [(rsrl_amd.MOUNTAIN_CAR, 3), (rsrl_amd.MOUNTAIN_CAR, 5), (rsrl_amd.CART_POLE, 1), (rsrl_amd.ACROBOT, 1)]
@@ -26,11 +25,6 @@ def ctx(**kw):
     base = dict(domain=rsrl_amd.MOUNTAIN_CAR, order=3, algo=rsrl_amd.REINFORCE, policy=rsrl_amd.SOFTMAX, n_envs=32, seed=5, gamma=0.95, alpha=0.05, tau=1.0)
     base.update(kw)
     return rsrl_amd.Context(**base)
-
-
-def rand_states(orc, domain, n, rng):
-    lo, hi = orc.domain_bounds(domain)
-    return rng.uniform(lo, hi, size=(n, len(lo))).T.astype(np.float32)
 
 
 def f32_returns(rewards, gamma):
@@ -147,21 +141,10 @@ def test_driver_loop_against_a_restated_loop(orc, algo):
         assert episodes > truncated > 0                               # terminals and caps both happened
 
 
-def _snapshot(c):
-    return (np.stack([c.get_policy_weights(i) for i in range(c.N)]), np.stack([c.get_behaviour_weights(i) for i in range(c.N)]), c.return_carry,
-            c.states, c.actions, c.episode_steps)
-
-
-NAMES = ("theta", "theta_b", "g", "states", "actions", "episode_steps")
-
-
-def _diff(s1, s2):
-    return [n for n, x, y in zip(NAMES, s1, s2) if not np.array_equal(np.asarray(x).view(np.uint8), np.asarray(y).view(np.uint8))]
-
-
 def _host_trait_loop(c, K, cap):
     """domain_step -> append to host buffers -> handle_batch(the episodes that just ended) -> domain_reset(ended) -> policy_sample().  Returns
-    (theta at the end = train's theta_b, theta after the still-open prefixes too = train's theta, g of the open prefixes)"""
+    the snapshot train is held to: theta at the loop's end is train's theta_b, theta after the still-open prefixes too is train's theta, and
+    their g is train's return_carry"""
     N, D = c.N, c.D
     S, A, R = np.zeros((cap, D, N), np.float32), np.zeros((cap, N), np.int32), np.zeros((cap, N), np.float32)
     ep = c.episode_steps.astype(np.int64)
@@ -182,8 +165,7 @@ def _host_trait_loop(c, K, cap):
     theta_end = np.stack([c.get_policy_weights(i) for i in range(N)])
     ret = c.handle_batch(S, A, R, ep.astype(np.uint32), returns=True)
     g = np.where(ep > 0, ret[np.maximum(ep - 1, 0), cols], np.float32(0.0)).astype(np.float32)
-    theta_open = np.stack([c.get_policy_weights(i) for i in range(N)])
-    return theta_end, theta_open, g
+    return dict(snapshot(c), theta_b=theta_end, return_carry=g)
 
 
 @pytest.mark.parametrize("algo", ALGOS)
@@ -201,71 +183,27 @@ def test_train_is_the_trait_loop_launch_depth_and_shard_invariant(domain, order,
                 c.set_weights(Bs[off + i], i)
         c.reset()
 
-    with ctx(**kw) as c:
-        setup(c)
-        c.timing_enable(True)
-        st = c.train(K)
-        assert c.timing_read()[2] == "k_train_reinforce"
-        ref = _snapshot(c)
-        assert st["episodes"] > 0
-    with ctx(**kw) as c:
-        setup(c)
-        theta_end, theta_open, g = _host_trait_loop(c, K, cap)
-        host = (theta_open, theta_end, g, c.states, c.actions, c.episode_steps)
-        assert _diff(host, ref) == []
-    for spl in (1, 7):
-        with ctx(steps_per_launch=spl, **kw) as c:
-            setup(c)
-            c.train(20)
-            c.train(1)
-            c.train(K - 21)
-            assert _diff(_snapshot(c), ref) == [], spl
-    shards = []
-    for off in (0, N // 2):
-        with ctx(env_offset=off, **dict(kw, n_envs=N // 2)) as c:
-            setup(c, off)
-            c.train(K)
-            shards.append(_snapshot(c))
-    joined = tuple(np.concatenate([shards[0][j], shards[1][j]], axis=0 if j < 2 else -1) for j in range(6))
-    assert _diff(joined, ref) == []
+    st, _ = check_train_invariance(ctx, kw, K, cap, depths=(1, 7), first_split=20, kernel="k_train_reinforce", setup=setup, trait=_host_trait_loop)
+    assert st["episodes"] > 0
 
 
 @pytest.mark.parametrize("algo", ALGOS)
 def test_checkpoint_resumes_an_open_episode_bitwise(tmp_path, algo):
     kw = dict(algo=algo, n_envs=32, order=3, max_episode_steps=17, alpha=0.2, tau=0.5)
     path = os.path.join(str(tmp_path), "reinforce.ckpt")
-    with ctx(**kw) as a:
-        a.reset()
-        a.train(25)
-        a.save_weights(path)
-        saved = (a.states, a.actions, a.episode_steps)
+
+    def an_episode_is_open(a):
         assert (a.return_carry != 0).any()
-        with ctx(**kw) as b:
-            b.load_weights(path)
-            b.states, b.actions, b.episode_steps = saved
-            assert _diff(_snapshot(a), _snapshot(b)) == []
-            assert a.checksum() == b.checksum()
-            a.train(20)
-            b.train(20)
-            assert _diff(_snapshot(a), _snapshot(b)) == []
-            assert a.checksum() == b.checksum()
+
+    check_checkpoint_resume(ctx, kw, path, 25, 20, carry=("states", "actions", "episode_steps"), at_save=an_episode_is_open)
     with open(path, "rb") as f:
         head = f.read(72)
     assert int.from_bytes(head[8:12], "little") == 9 and int.from_bytes(head[52:56], "little") == 7
     other_algo = rsrl_amd.BASELINE_REINFORCE if algo == rsrl_amd.REINFORCE else rsrl_amd.REINFORCE
     others = [dict(algo=other_algo, policy=rsrl_amd.SOFTMAX), dict(algo=rsrl_amd.ACTOR_CRITIC, policy=rsrl_amd.SOFTMAX),
               dict(algo=rsrl_amd.TD_ACTOR_CRITIC, policy=rsrl_amd.SOFTMAX)]
-    for other in others:
-        with rsrl_amd.Context(domain=rsrl_amd.MOUNTAIN_CAR, **dict(kw, **other)) as o:
-            with pytest.raises(RsrlHipError) as e:
-                o.load_weights(path)
-            assert e.value.code == EINVAL
-            opath = os.path.join(str(tmp_path), "other.ckpt")
-            o.save_weights(opath)
-            with ctx(**kw) as b:
-                with pytest.raises(RsrlHipError) as e:
-                    b.load_weights(opath)
-                assert e.value.code == EINVAL
+    others = [dict(kw, domain=rsrl_amd.MOUNTAIN_CAR, **other) for other in others]
+    check_foreign_checkpoints_refused(ctx, kw, path, others, tmp_path)
 
 
 def test_checksum_covers_theta():
@@ -358,12 +296,8 @@ def test_refusals():
 
 
 def test_reinforce_example_builds_and_runs(tmp_path):
-    exe = os.path.join(str(tmp_path), "reinforce")
-    lib = os.path.join(ROOT, "rsrl_amd", "lib")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", os.path.join(ROOT, "examples", "reinforce.cpp"), "-L" + lib, "-lrsrl_hip", "-Wl,-rpath," + lib, "-o", exe],
-                   check=True, timeout=300)
     for baseline in ("0", "1"):
-        out = subprocess.run([exe, "64", "3", "200", baseline], capture_output=True, text=True, timeout=300, check=True).stdout
+        out = run_example(tmp_path, "reinforce", [64, 3, 200, baseline])
         assert "Batch 3:" in out and "OOS:" in out
         tmax = float(out.split("max |theta| of learner 0:")[1].split()[0])
         assert np.isfinite(tmax) and tmax > 0.0

@@ -2,7 +2,6 @@
 bit for bit a TD ctx's, the policy side reading theta and the value side reading w, the driver loop against a restated loop, train against the
 trait-granular loop / launch depths / shards bit for bit, checkpoints, the checksum, the refusals and the C++ example."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -10,11 +9,11 @@ import pytest
 import rsrl_amd
 from rsrl_amd import RsrlHipError
 from tests.ac_numpy import near_boundary
+from tests.agent_contract import check_checkpoint_resume, check_foreign_checkpoints_refused, check_train_invariance, rand_states, run_example
 from tests.tdac_numpy import tdac_restated_loop as _restated_loop, tdac_rule
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TDAC = rsrl_amd.TD_ACTOR_CRITIC
 REG = [(rsrl_amd.MOUNTAIN_CAR, o) for o in (1, 2, 3, 4, 5)] + [(rsrl_amd.CART_POLE, 1), (rsrl_amd.ACROBOT, 1)]
 LOOP = [(rsrl_amd.MOUNTAIN_CAR, 3), (rsrl_amd.MOUNTAIN_CAR, 5), (rsrl_amd.CART_POLE, 1), (rsrl_amd.ACROBOT, 1)]
@@ -24,11 +23,6 @@ def ctx(**kw):
     base = dict(domain=rsrl_amd.MOUNTAIN_CAR, order=3, algo=TDAC, policy=rsrl_amd.SOFTMAX, n_envs=32, seed=5, gamma=0.95, lr=0.05, alpha=0.3, tau=1.0)
     base.update(kw)
     return rsrl_amd.Context(**base)
-
-
-def rand_states(orc, domain, n, rng):
-    lo, hi = orc.domain_bounds(domain)
-    return rng.uniform(lo, hi, size=(n, len(lo))).T.astype(np.float32)
 
 
 def randomise(c, rng, scale=0.3):
@@ -163,92 +157,25 @@ def test_driver_loop_against_a_restated_loop(orc):
         assert episodes > truncated > 0                               # terminals and caps both happened
 
 
-def _trait_loop(c, K, cap):
-    ep = c.episode_steps.astype(np.int64)
-    for _ in range(K):
-        frm, nxt, rew, term = c.domain_step(c.actions)
-        c.handle(frm, c.actions, rew, nxt, term)
-        ep += 1
-        mask = (term.astype(bool) | (ep >= cap)).astype(np.uint8)
-        c.domain_reset(mask)
-        ep[mask == 1] = 0
-        c.policy_sample()
-    c.episode_steps = ep.astype(np.uint32)
-
-
-def _snapshot(c):
-    return (np.stack([c.get_weights(i) for i in range(c.N)]), np.stack([c.get_policy_weights(i) for i in range(c.N)]), c.states, c.actions, c.episode_steps)
-
-
-def _diff(s1, s2):
-    names = ("weights", "theta", "states", "actions", "episode_steps")
-    return [n for n, x, y in zip(names, s1, s2) if not np.array_equal(x, y)]
-
-
 @pytest.mark.parametrize("domain,order", LOOP)
 def test_train_is_the_trait_loop_launch_depth_and_shard_invariant(domain, order):
     N, K, cap = 64, 60, 23
     kw = dict(domain=domain, order=order, n_envs=N, max_episode_steps=cap, tau=0.7, lr=0.02, alpha=0.2, gamma=0.97)
-    with ctx(**kw) as c:
-        c.reset()
-        c.timing_enable(True)
-        st = c.train(K)
-        assert c.timing_read()[2] == "k_train_tdac"
-        ref = _snapshot(c)
-        assert st["episodes"] > 0
-    with ctx(**kw) as c:
-        c.reset()
-        _trait_loop(c, K, cap)
-        assert _diff(_snapshot(c), ref) == []
-    for spl in (1, 7):
-        with ctx(steps_per_launch=spl, **kw) as c:
-            c.reset()
-            c.train(20)
-            c.train(1)
-            c.train(K - 21)
-            assert _diff(_snapshot(c), ref) == [], spl
-    shards = []
-    for off in (0, N // 2):
-        with ctx(env_offset=off, **dict(kw, n_envs=N // 2)) as c:
-            c.reset()
-            c.train(K)
-            shards.append(_snapshot(c))
-    joined = tuple(np.concatenate([shards[0][j], shards[1][j]], axis=0 if j < 2 else -1) for j in range(5))
-    assert _diff(joined, ref) == []
+    st, _ = check_train_invariance(ctx, kw, K, cap, depths=(1, 7), first_split=20, kernel="k_train_tdac")
+    assert st["episodes"] > 0
 
 
 def test_checkpoint_resumes_bitwise_and_refuses_other_agents(tmp_path):
     kw = dict(n_envs=32, order=3, max_episode_steps=17, lr=0.02, alpha=0.2, tau=0.5)
     path = os.path.join(str(tmp_path), "tdac.ckpt")
-    with ctx(**kw) as a:
-        a.reset()
-        a.train(25)
-        a.save_weights(path)
-        saved = (a.states, a.actions, a.episode_steps)
-        with ctx(**kw) as b:
-            b.load_weights(path)
-            b.states, b.actions, b.episode_steps = saved
-            assert _diff(_snapshot(a), _snapshot(b)) == []
-            a.train(20)
-            b.train(20)
-            assert _diff(_snapshot(a), _snapshot(b)) == []
-            assert a.checksum() == b.checksum()
+    check_checkpoint_resume(ctx, kw, path, 25, 20, carry=("states", "actions", "episode_steps"))
     with open(path, "rb") as f:
         head = f.read(72)
     assert int.from_bytes(head[8:12], "little") == 8 and int.from_bytes(head[40:44], "little") == 1 and int.from_bytes(head[52:56], "little") == 6
     others = [dict(algo=rsrl_amd.ACTOR_CRITIC, policy=rsrl_amd.SOFTMAX), dict(algo=rsrl_amd.Q_ACTOR_CRITIC, policy=rsrl_amd.SOFTMAX),
               dict(algo=rsrl_amd.TD, policy=rsrl_amd.RANDOM)]
-    for other in others:
-        with rsrl_amd.Context(domain=rsrl_amd.MOUNTAIN_CAR, **dict(kw, **other)) as o:
-            with pytest.raises(RsrlHipError) as e:
-                o.load_weights(path)
-            assert e.value.code == -1
-            opath = os.path.join(str(tmp_path), "other.ckpt")
-            o.save_weights(opath)
-            with ctx(**kw) as b:
-                with pytest.raises(RsrlHipError) as e:
-                    b.load_weights(opath)
-                assert e.value.code == -1
+    others = [dict(kw, domain=rsrl_amd.MOUNTAIN_CAR, **other) for other in others]
+    check_foreign_checkpoints_refused(ctx, kw, path, others, tmp_path)
 
 
 def test_checksum_covers_theta():
@@ -281,11 +208,7 @@ def test_refusals():
 
 
 def test_tdac_example_builds_and_runs(tmp_path):
-    exe = os.path.join(str(tmp_path), "tdac")
-    lib = os.path.join(ROOT, "rsrl_amd", "lib")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", os.path.join(ROOT, "examples", "tdac.cpp"), "-L" + lib, "-lrsrl_hip", "-Wl,-rpath," + lib, "-o", exe],
-                   check=True, timeout=300)
-    out = subprocess.run([exe, "64", "3", "200"], capture_output=True, text=True, timeout=300, check=True).stdout
+    out = run_example(tmp_path, "tdac", [64, 3, 200])
     assert "Batch 3:" in out and "OOS:" in out
     tail = out.split("max |w| of learner 0:")[1]
     wmax, tmax = float(tail.split()[0]), float(tail.split("max |theta| of learner 0:")[1].split()[0])

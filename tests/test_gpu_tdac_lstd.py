@@ -6,7 +6,6 @@ import functools
 import importlib.util
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +13,8 @@ import pytest
 import rsrl_amd
 from rsrl_amd import RsrlHipError
 from tests.ac_numpy import near_boundary
+from tests.agent_contract import (check_checkpoint_resume, check_foreign_checkpoints_refused, check_train_invariance, diff, learner_state, rand_states,
+                                  run_example)
 from tests.tdac_lstd_numpy import handle_case
 
 pytestmark = pytest.mark.gpu
@@ -25,24 +26,11 @@ LOOP = [(rsrl_amd.MOUNTAIN_CAR, 1), (rsrl_amd.MOUNTAIN_CAR, 3), (rsrl_amd.MOUNTA
 EPS = np.finfo(np.float64).eps
 
 
+BASE = dict(domain=rsrl_amd.MOUNTAIN_CAR, order=3, algo=AC, policy=rsrl_amd.SOFTMAX, n_envs=32, seed=5, gamma=0.95, lr=0.05, alpha=0.3, tau=1.0, n_steps=3)
+
+
 def ctx(**kw):
-    base = dict(domain=rsrl_amd.MOUNTAIN_CAR, order=3, algo=AC, policy=rsrl_amd.SOFTMAX, n_envs=32, seed=5, gamma=0.95, lr=0.05, alpha=0.3, tau=1.0, n_steps=3)
-    base.update(kw)
-    return rsrl_amd.Context(**base)
-
-
-def rand_states(orc, domain, n, rng):
-    lo, hi = orc.domain_bounds(domain)
-    return rng.uniform(lo, hi, size=(n, len(lo))).T.astype(np.float32)
-
-
-def state_of(c):
-    """every learner's (theta, A, mu, the actor's theta) stacked"""
-    ts, ms, us, ps = [], [], [], []
-    for i in range(c.N):
-        t, m, u = c.get_lstd_state(i)
-        ts.append(t); ms.append(m); us.append(u); ps.append(c.get_policy_weights(i))
-    return np.stack(ts), np.stack(ms), np.stack(us), np.stack(ps)
+    return rsrl_amd.Context(**dict(BASE, **kw))
 
 
 def randomise(c, rng, also=()):
@@ -124,59 +112,13 @@ def test_the_critic_half_is_ilstd_bit_for_bit(orc, domain, order):
         assert np.array_equal(c.get_weights(5), v.get_weights(5))
 
 
-def _trait_loop(c, K, cap):
-    ep = c.episode_steps.astype(np.int64)
-    for _ in range(K):
-        frm, nxt, rew, term = c.domain_step(c.actions)
-        c.handle(frm, c.actions, rew, nxt, term)
-        ep += 1
-        mask = (term.astype(bool) | (ep >= cap)).astype(np.uint8)
-        c.domain_reset(mask)
-        ep[mask == 1] = 0
-        c.policy_sample()
-    c.episode_steps = ep.astype(np.uint32)
-
-
-def _snapshot(c):
-    return state_of(c) + (c.states, c.actions, c.episode_steps)
-
-
-def _diff(s1, s2):
-    names = ("theta", "A", "mu", "actor", "states", "actions", "episode_steps")
-    return [n for n, x, y in zip(names, s1, s2) if np.shape(x) != np.shape(y) or np.asarray(x).tobytes() != np.asarray(y).tobytes()]
-
-
 @pytest.mark.parametrize("domain,order", LOOP)
 def test_train_is_the_trait_loop_launch_depth_and_shard_invariant(domain, order):
     N, K, cap = 64, 60, 23
     kw = dict(domain=domain, order=order, n_envs=N, max_episode_steps=cap, tau=0.7, lr=0.02, alpha=0.2, gamma=0.97, n_steps=2)
-    with ctx(**kw) as c:
-        c.reset()
-        c.timing_enable(True)
-        st = c.train(K)
-        assert c.timing_read()[2] == "k_train_tdac_lstd"
-        ref = _snapshot(c)
-        assert st["episodes"] > 0 and st["env_steps"] == N * K and st["sum_abs_td_error"] > 0
-        assert np.isfinite(ref[0]).all() and np.abs(ref[0]).max() > 0 and np.abs(ref[3]).max() > 0
-    with ctx(**kw) as c:
-        c.reset()
-        _trait_loop(c, K, cap)
-        assert _diff(_snapshot(c), ref) == []
-    for spl in (1, 64):
-        with ctx(steps_per_launch=spl, **kw) as c:
-            c.reset()
-            c.train(20)
-            c.train(1)
-            c.train(K - 21)
-            assert _diff(_snapshot(c), ref) == [], spl
-    shards = []
-    for off in (0, N // 2):
-        with ctx(env_offset=off, **dict(kw, n_envs=N // 2)) as c:
-            c.reset()
-            c.train(K)
-            shards.append(_snapshot(c))
-    joined = tuple(np.concatenate([shards[0][j], shards[1][j]], axis=0 if j < 4 else -1) for j in range(7))
-    assert _diff(joined, ref) == []
+    st, ref = check_train_invariance(ctx, kw, K, cap, depths=(1, 64), first_split=20, kernel="k_train_tdac_lstd")
+    assert st["episodes"] > 0 and st["env_steps"] == N * K and st["sum_abs_td_error"] > 0
+    assert np.isfinite(ref["lstd_theta"]).all() and np.abs(ref["lstd_theta"]).max() > 0 and np.abs(ref["theta"]).max() > 0
 
 
 def _digest_recipe():
@@ -189,49 +131,27 @@ def _digest_recipe():
 def test_checkpoint_resumes_bitwise_and_the_checksum_covers_both_agents(tmp_path):
     kw = dict(n_envs=32, order=3, max_episode_steps=17, lr=0.02, alpha=0.2, tau=0.5)
     path = os.path.join(str(tmp_path), "tdac_lstd.ckpt")
-    with ctx(**kw) as a:
-        a.reset()
-        a.train(25)
-        a.save_weights(path)
-        saved = (a.states, a.actions, a.episode_steps)
-        with ctx(**kw) as b:
-            b.load_weights(path)
-            assert b.step_count == a.step_count
-            b.states, b.actions, b.episode_steps = saved
-            assert _diff(_snapshot(a), _snapshot(b)) == []
-            assert a.checksum() == b.checksum()
-            a.train(20)
-            b.train(20)
-            assert _diff(_snapshot(a), _snapshot(b)) == []
-            assert a.checksum() == b.checksum()
-            before = b.checksum()
-            th, m, u = b.get_lstd_state(5)
-            m[3, 4] = np.nextafter(m[3, 4], np.inf)                # one bit of one learner's f64 matrix
-            b.set_lstd_state(th, m, u, 5)
-            flipped = b.checksum()
-            assert flipped[0] != before[0] and flipped[1] == before[1]
-            pw = b.get_policy_weights(7)
-            pw[2, 1] = np.nextafter(pw[2, 1], np.float32(np.inf))  # one bit of one learner's actor
-            b.set_policy_weights(pw, 7)
-            assert b.checksum()[0] != flipped[0] and b.checksum()[0] != before[0] and b.checksum()[1] == before[1]
+
+    def one_bit_of_either_agent_moves_the_checksum(a, b):
+        before = b.checksum()
+        th, m, u = b.get_lstd_state(5)
+        m[3, 4] = np.nextafter(m[3, 4], np.inf)                # one bit of one learner's f64 matrix
+        b.set_lstd_state(th, m, u, 5)
+        flipped = b.checksum()
+        assert flipped[0] != before[0] and flipped[1] == before[1]
+        pw = b.get_policy_weights(7)
+        pw[2, 1] = np.nextafter(pw[2, 1], np.float32(np.inf))  # one bit of one learner's actor
+        b.set_policy_weights(pw, 7)
+        assert b.checksum()[0] != flipped[0] and b.checksum()[0] != before[0] and b.checksum()[1] == before[1]
+
+    check_checkpoint_resume(ctx, kw, path, 25, 20, carry=("states", "actions", "episode_steps"), then=one_bit_of_either_agent_moves_the_checksum)
     with open(path, "rb") as f:
         head = f.read(72)
     F, A = 16, 3
     assert int.from_bytes(head[8:12], "little") == 10 and int.from_bytes(head[40:44], "little") == 1 and int.from_bytes(head[52:56], "little") == 9
     assert os.path.getsize(path) == 72 + 32 * 8 * (F + F * F + F) + 32 * 4 * F * A
     others = [dict(algo=ILSTD, policy=rsrl_amd.RANDOM, alpha=0.02), dict(algo=rsrl_amd.TD_ACTOR_CRITIC), dict(algo=rsrl_amd.TD, policy=rsrl_amd.RANDOM)]
-    for other in others:
-        with ctx(**dict(kw, **other)) as o:
-            with pytest.raises(RsrlHipError) as e:
-                o.load_weights(path)
-            assert e.value.code == -1
-            opath = os.path.join(str(tmp_path), "other.ckpt")
-            o.save_weights(opath)
-            with ctx(**kw) as b:
-                before = b.checksum()
-                with pytest.raises(RsrlHipError) as e:
-                    b.load_weights(opath)
-                assert e.value.code == -1 and b.checksum() == before
+    check_foreign_checkpoints_refused(ctx, kw, path, [dict(BASE, **dict(kw, **other)) for other in others], tmp_path)
     # a truncated file is refused before anything is touched
     raw = open(path, "rb").read()
     open(path, "wb").write(raw[:-4])
@@ -306,9 +226,9 @@ def test_value_side_policy_side_reset_and_refusals(orc):
                 call()
             assert e.value.code == -5, k
         # ---- reset: the initial sample reads the actor, and neither agent's state moves
-        before = state_of(c)
+        before = [learner_state(c, i) for i in range(N)]
         c.reset()
-        assert all(x.tobytes() == y.tobytes() for x, y in zip(before, state_of(c)))
+        assert all(diff(before[i], learner_state(c, i)) == [] for i in range(N))
         phi0 = orc.fourier_project(domain, order, orc.domain_reset(domain, prec="f32"))
         acts = c.actions
         for i in range(N):
@@ -341,11 +261,7 @@ def test_value_side_policy_side_reset_and_refusals(orc):
 
 
 def test_example_builds_and_runs(tmp_path):
-    exe = os.path.join(str(tmp_path), "tdac_ilstd")
-    lib = os.path.join(ROOT, "rsrl_amd", "lib")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", os.path.join(ROOT, "examples", "tdac_ilstd.cpp"), "-L" + lib, "-lrsrl_hip", "-Wl,-rpath," + lib, "-o", exe],
-                   check=True, timeout=300)
-    out = subprocess.run([exe, "64", "3", "200"], capture_output=True, text=True, timeout=300, check=True).stdout
+    out = run_example(tmp_path, "tdac_ilstd", [64, 3, 200])
     assert "Batch 3:" in out and "OOS:" in out
     tail = out.split("iLSTD: max |theta| of learner 0:")[1]
     vmax, tmax = float(tail.split()[0]), float(tail.split("actor: max |theta| of learner 0:")[1].split()[0])

@@ -1,15 +1,14 @@
 """RecursiveLSTD and iLSTD (RSRL_RECURSIVE_LSTD, RSRL_ILSTD) without a GPU: the header declares them, every supported configuration passes admission
 and reaches the device query while every other one is refused with a message naming the algo, examples/lstd.cpp compiles, and hand-worked cases pin
 the f64 restatement the GPU tests compare against (tests/lstd_numpy.py)."""
-import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 
 import rsrl_amd
 from rsrl_amd import _abi
+from tests.agent_contract import compile_example, create_rc
 from tests.lstd_numpy import argmaxima, ilstd, ilstd_init, ilstd_solve, near_tie_band, recursive_lstd, recursive_lstd_init
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,21 +17,7 @@ SUPPORTED = [(rsrl_amd.MOUNTAIN_CAR, o) for o in (1, 2, 3, 4, 5)] + [(rsrl_amd.C
 ALGOS = [(rsrl_amd.RECURSIVE_LSTD, "RSRL_RECURSIVE_LSTD"), (rsrl_amd.ILSTD, "RSRL_ILSTD")]
 
 
-def _create(**kw):
-    """rsrl_hip_create on an LSTD config with kw on top -> (return code, last error); a ctx that was created is destroyed"""
-    L = _abi.lib()
-    cfg = _abi.Config()
-    assert L.rsrl_hip_config_init(C.byref(cfg)) == 0
-    base = dict(domain=rsrl_amd.MOUNTAIN_CAR, order=3, algo=rsrl_amd.RECURSIVE_LSTD, policy=rsrl_amd.RANDOM, n_envs=4)
-    base.update(kw)
-    for k, v in base.items():
-        setattr(cfg, k, v)
-    h = C.c_void_p()
-    rc = L.rsrl_hip_create(C.byref(cfg), C.byref(h))
-    msg = (L.rsrl_hip_last_error() or b"").decode()
-    if rc == 0:
-        L.rsrl_hip_destroy(h)
-    return rc, msg
+BASE = dict(domain=rsrl_amd.MOUNTAIN_CAR, order=3, algo=rsrl_amd.RECURSIVE_LSTD, policy=rsrl_amd.RANDOM, n_envs=4)
 
 
 def test_header_declares_the_algos_and_exports():
@@ -50,7 +35,7 @@ def test_supported_configurations_reach_the_device_query():
     for algo, _ in ALGOS:
         for domain, order in SUPPORTED:
             for extra in (dict(), dict(steps_per_launch=1), dict(max_episode_steps=100, gamma=0.9, alpha=0.01), dict(n_steps=32), dict(n_steps=1)):
-                rc, msg = _create(algo=algo, domain=domain, order=order, **extra)
+                rc, msg = create_rc(BASE, algo=algo, domain=domain, order=order, **extra)
                 # no GPU: every admission rule has passed and the device query answers "no device"; with one, the ctx is created
                 assert rc == 0 or (rc == EHIP and "device" in msg), (algo, domain, order, extra, rc, msg)
 
@@ -63,22 +48,20 @@ def test_other_configurations_are_refused_with_a_message():
            dict(policy=rsrl_amd.SOFTMAX), dict(agent_policy=rsrl_amd.RANDOM), dict(epsilon_decay=0.99)]
     for algo, name in ALGOS:
         for b in bad:
-            rc, msg = _create(algo=algo, **b)
+            rc, msg = create_rc(BASE, algo=algo, **b)
             assert rc == EINVAL and name in msg and "register-family Fourier" in msg, (algo, b, rc, msg)
     for n in (0, -1, 33, 1000):
-        rc, msg = _create(algo=rsrl_amd.ILSTD, n_steps=n)
+        rc, msg = create_rc(BASE, algo=rsrl_amd.ILSTD, n_steps=n)
         assert rc == EINVAL and "RSRL_ILSTD" in msg and "n_steps" in msg, (n, rc, msg)
-    rc, msg = _create(algo=rsrl_amd.RECURSIVE_LSTD, n_steps=0)      # RecursiveLSTD has no n_updates: n_steps is not its field
+    rc, msg = create_rc(BASE, algo=rsrl_amd.RECURSIVE_LSTD, n_steps=0)      # RecursiveLSTD has no n_updates: n_steps is not its field
     assert rc == 0 or (rc == EHIP and "device" in msg), (rc, msg)
     for n in (12, 14, 17, 20):
-        rc, msg = _create(algo=n)
+        rc, msg = create_rc(BASE, algo=n)
         assert rc == EINVAL and "unknown algo %d" % n in msg, (n, msg)
 
 
 def test_lstd_example_compiles(tmp_path):
-    obj = os.path.join(str(tmp_path), "lstd.o")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-c", os.path.join(ROOT, "examples", "lstd.cpp"), "-o", obj], check=True, timeout=300)
-    assert os.path.getsize(obj) > 0
+    compile_example(tmp_path, "lstd")
 
 
 def test_argmaxima_ties_come_first():

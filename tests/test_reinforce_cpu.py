@@ -6,12 +6,12 @@ import itertools
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 
 import rsrl_amd
 from rsrl_amd import _abi
+from tests.agent_contract import compile_example, create_rc
 from tests.reinforce_numpy import reinforce_batch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,21 +19,7 @@ EINVAL, EHIP = -1, -2
 FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission.json")
 
 
-def _create(**kw):
-    """rsrl_hip_create on a REINFORCE config with kw on top -> (return code, last error); a ctx that was created is destroyed"""
-    L = _abi.lib()
-    cfg = _abi.Config()
-    assert L.rsrl_hip_config_init(C.byref(cfg)) == 0
-    base = dict(domain=rsrl_amd.MOUNTAIN_CAR, order=3, algo=rsrl_amd.REINFORCE, policy=rsrl_amd.SOFTMAX, n_envs=4)
-    base.update(kw)
-    for k, v in base.items():
-        setattr(cfg, k, v)
-    h = C.c_void_p()
-    rc = L.rsrl_hip_create(C.byref(cfg), C.byref(h))
-    msg = (L.rsrl_hip_last_error() or b"").decode()
-    if rc == 0:
-        L.rsrl_hip_destroy(h)
-    return rc, msg
+BASE = dict(domain=rsrl_amd.MOUNTAIN_CAR, order=3, algo=rsrl_amd.REINFORCE, policy=rsrl_amd.SOFTMAX, n_envs=4)
 
 
 def test_rule_on_a_hand_worked_batch():
@@ -118,14 +104,12 @@ def test_refusals_name_the_algo():
            dict(policy=rsrl_amd.EPSILON_GREEDY), dict(policy=rsrl_amd.RANDOM), dict(agent_policy=rsrl_amd.SOFTMAX), dict(epsilon_decay=0.99)]
     for algo, name in ((rsrl_amd.REINFORCE, "RSRL_REINFORCE"), (rsrl_amd.BASELINE_REINFORCE, "RSRL_BASELINE_REINFORCE")):
         for b in bad:
-            rc, msg = _create(algo=algo, **b)
+            rc, msg = create_rc(BASE, algo=algo, **b)
             assert rc == EINVAL and name in msg and "register-family Fourier" in msg, (algo, b, rc, msg)
     for algo in (12, 14, 17, -1):
-        rc, msg = _create(algo=algo)
+        rc, msg = create_rc(BASE, algo=algo)
         assert rc == EINVAL and "unknown algo %d" % algo in msg
 
 
 def test_reinforce_example_compiles(tmp_path):
-    obj = os.path.join(str(tmp_path), "reinforce.o")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-c", os.path.join(ROOT, "examples", "reinforce.cpp"), "-o", obj], check=True, timeout=300)
-    assert os.path.getsize(obj) > 0
+    compile_example(tmp_path, "reinforce")

@@ -1,15 +1,13 @@
 """ActorCritic with the TD(0) state-value critic (RSRL_TD_ACTOR_CRITIC) without a GPU: the header declares it, every supported configuration
 passes admission and reaches the device query while every other one is refused with a message, examples/tdac.cpp compiles, and the f64 rule the
 GPU tests compare against reproduces a hand-checked case -- a terminal transition included, whose critic reads V of the terminal state."""
-import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 
 import rsrl_amd
-from rsrl_amd import _abi
+from tests.agent_contract import compile_example, create_rc
 from tests.tdac_numpy import tdac_rule
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,21 +15,7 @@ EINVAL, EHIP = -1, -2
 SUPPORTED = [(rsrl_amd.MOUNTAIN_CAR, o) for o in (1, 2, 3, 4, 5)] + [(rsrl_amd.CART_POLE, 1), (rsrl_amd.ACROBOT, 1)]
 
 
-def _create(**kw):
-    """rsrl_hip_create on a TD ActorCritic config with kw on top -> (return code, last error); a ctx that was created is destroyed"""
-    L = _abi.lib()
-    cfg = _abi.Config()
-    assert L.rsrl_hip_config_init(C.byref(cfg)) == 0
-    base = dict(domain=rsrl_amd.MOUNTAIN_CAR, order=3, algo=rsrl_amd.TD_ACTOR_CRITIC, policy=rsrl_amd.SOFTMAX, n_envs=4)
-    base.update(kw)
-    for k, v in base.items():
-        setattr(cfg, k, v)
-    h = C.c_void_p()
-    rc = L.rsrl_hip_create(C.byref(cfg), C.byref(h))
-    msg = (L.rsrl_hip_last_error() or b"").decode()
-    if rc == 0:
-        L.rsrl_hip_destroy(h)
-    return rc, msg
+BASE = dict(domain=rsrl_amd.MOUNTAIN_CAR, order=3, algo=rsrl_amd.TD_ACTOR_CRITIC, policy=rsrl_amd.SOFTMAX, n_envs=4)
 
 
 def test_header_declares_the_algo():
@@ -44,7 +28,7 @@ def test_header_declares_the_algo():
 def test_supported_configurations_reach_the_device_query():
     for domain, order in SUPPORTED:
         for extra in (dict(), dict(steps_per_launch=1), dict(tau=0.5, max_episode_steps=100)):
-            rc, msg = _create(domain=domain, order=order, **extra)
+            rc, msg = create_rc(BASE, domain=domain, order=order, **extra)
             # no GPU: every admission rule has passed and the device query answers "no device"; with one, the ctx is created
             assert rc == 0 or (rc == EHIP and "device" in msg), (domain, order, extra, rc, msg)
 
@@ -56,18 +40,16 @@ def test_other_configurations_are_refused_with_a_message():
            dict(domain=rsrl_amd.HIV_TREATMENT, order=1), dict(policy=rsrl_amd.EPSILON_GREEDY), dict(policy=rsrl_amd.GREEDY),
            dict(policy=rsrl_amd.RANDOM), dict(agent_policy=rsrl_amd.SOFTMAX), dict(epsilon_decay=0.99)]
     for b in bad:
-        rc, msg = _create(**b)
+        rc, msg = create_rc(BASE, **b)
         assert rc == EINVAL and "RSRL_TD_ACTOR_CRITIC" in msg and "register-family Fourier" in msg, (b, rc, msg)
-    rc, msg = _create(algo=12)
+    rc, msg = create_rc(BASE, algo=12)
     assert rc == EINVAL and "unknown algo 12" in msg
-    rc, msg = _create(algo=14)
+    rc, msg = create_rc(BASE, algo=14)
     assert rc == EINVAL and "unknown algo 14" in msg
 
 
 def test_tdac_example_compiles(tmp_path):
-    obj = os.path.join(str(tmp_path), "tdac.o")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-c", os.path.join(ROOT, "examples", "tdac.cpp"), "-o", obj], check=True, timeout=300)
-    assert os.path.getsize(obj) > 0
+    compile_example(tmp_path, "tdac")
 
 
 def test_rule_on_a_hand_checked_case():

@@ -2,7 +2,6 @@
 every configuration the TD ActorCritic (13) runs on passes admission and reaches the device query while every other one is refused with a message,
 20 is no algo, the third admission grid equals its fixture, examples/tdac_ilstd.cpp compiles, and hand-worked cases pin the restatement the GPU
 tests compare against (tests/tdac_lstd_numpy.py)."""
-import ctypes as C
 import importlib.util
 import json
 import os
@@ -13,8 +12,8 @@ import numpy as np
 import pytest
 
 import rsrl_amd
-from rsrl_amd import _abi
 from tests.ac_numpy import softmax
+from tests.agent_contract import compile_example, create_rc
 from tests.lstd_numpy import ilstd, ilstd_init
 from tests.tdac_lstd_numpy import critic_target, handle_case, tdac_lstd_rule
 
@@ -24,21 +23,7 @@ SUPPORTED = [(rsrl_amd.MOUNTAIN_CAR, o) for o in (1, 2, 3, 4, 5)] + [(rsrl_amd.C
 NAME = "RSRL_ILSTD_ACTOR_CRITIC"
 
 
-def _create(**kw):
-    """rsrl_hip_create on an iLSTD ActorCritic config with kw on top -> (return code, last error); a ctx that was created is destroyed"""
-    L = _abi.lib()
-    cfg = _abi.Config()
-    assert L.rsrl_hip_config_init(C.byref(cfg)) == 0
-    base = dict(domain=rsrl_amd.MOUNTAIN_CAR, order=3, algo=rsrl_amd.ILSTD_ACTOR_CRITIC, policy=rsrl_amd.SOFTMAX, n_envs=4, n_steps=2)
-    base.update(kw)
-    for k, v in base.items():
-        setattr(cfg, k, v)
-    h = C.c_void_p()
-    rc = L.rsrl_hip_create(C.byref(cfg), C.byref(h))
-    msg = (L.rsrl_hip_last_error() or b"").decode()
-    if rc == 0:
-        L.rsrl_hip_destroy(h)
-    return rc, msg
+BASE = dict(domain=rsrl_amd.MOUNTAIN_CAR, order=3, algo=rsrl_amd.ILSTD_ACTOR_CRITIC, policy=rsrl_amd.SOFTMAX, n_envs=4, n_steps=2)
 
 
 def _gfx950_visible():
@@ -72,7 +57,7 @@ def test_header_rust_block_and_python_constant_agree():
 def test_supported_configurations_reach_the_device_query():
     for domain, order in SUPPORTED:
         for extra in (dict(), dict(steps_per_launch=1), dict(tau=0.5, max_episode_steps=100, lr=1e-4, alpha=0.002, gamma=0.99), dict(n_steps=1), dict(n_steps=32)):
-            rc, msg = _create(domain=domain, order=order, **extra)
+            rc, msg = create_rc(BASE, domain=domain, order=order, **extra)
             # no GPU: every admission rule has passed and the device query answers "no device"; with one, the ctx is created
             assert rc == 0 or (rc == EHIP and "device" in msg), (domain, order, extra, rc, msg)
 
@@ -84,20 +69,20 @@ def test_other_configurations_are_refused_with_a_message():
            dict(domain=rsrl_amd.HIV_TREATMENT, order=1), dict(policy=rsrl_amd.EPSILON_GREEDY), dict(policy=rsrl_amd.GREEDY),
            dict(policy=rsrl_amd.RANDOM), dict(agent_policy=rsrl_amd.SOFTMAX), dict(epsilon_decay=0.99)]
     for b in bad:
-        rc, msg = _create(**b)
+        rc, msg = create_rc(BASE, **b)
         assert rc == EINVAL and NAME in msg and "register-family Fourier" in msg, (b, rc, msg)
     for n in (0, -1, 33, 1000):
-        rc, msg = _create(n_steps=n)
+        rc, msg = create_rc(BASE, n_steps=n)
         assert rc == EINVAL and NAME in msg and "n_steps" in msg, (n, rc, msg)
-    rc, msg = _create(tau=0.0)
+    rc, msg = create_rc(BASE, tau=0.0)
     assert rc == EINVAL and "Tau" in msg
 
 
 def test_twenty_is_no_algo():
     for kw in (dict(), dict(policy=rsrl_amd.RANDOM), dict(policy=rsrl_amd.EPSILON_GREEDY, order=5)):
-        rc, msg = _create(algo=20, **kw)
+        rc, msg = create_rc(BASE, algo=20, **kw)
         assert rc == EINVAL and "unknown algo 20" in msg, (kw, rc, msg)
-    rc, msg = _create(algo=22)
+    rc, msg = create_rc(BASE, algo=22)
     assert rc == EINVAL and "unknown algo 22" in msg
 
 
@@ -132,9 +117,7 @@ def test_create_admits_exactly_the_third_fixture(matrix):
 
 
 def test_example_compiles(tmp_path):
-    obj = os.path.join(str(tmp_path), "tdac_ilstd.o")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-c", os.path.join(ROOT, "examples", "tdac_ilstd.cpp"), "-o", obj], check=True, timeout=300)
-    assert os.path.getsize(obj) > 0
+    compile_example(tmp_path, "tdac_ilstd")
 
 
 def test_rule_on_a_hand_worked_non_terminal_transition():
@@ -212,7 +195,7 @@ def test_the_campaign_sampler_draws_only_admitted_configurations():
     for _ in range(300):
         kw = fz.draw_config(rng)
         assert kw["algo"] == rsrl_amd.ILSTD_ACTOR_CRITIC
-        rc, msg = _create(**dict(kw, n_envs=min(kw["n_envs"], 4)))
+        rc, msg = create_rc(BASE, **dict(kw, n_envs=min(kw["n_envs"], 4)))
         assert rc == 0 or (rc == EHIP and "device" in msg), (kw, rc, msg)
         seen.add((kw["domain"], kw["order"]))
     assert seen == set(SUPPORTED)
