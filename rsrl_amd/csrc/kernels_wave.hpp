@@ -83,6 +83,20 @@ __device__ __forceinline__ float wave_sum_uniform(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wave_sum_dpp_to_lane63(v)), 63));
 }
 
+// <phi, column> with the column streamed from memory, dot()'s order (4 interleaved chains over (j, v), then the wave total)
+template <class WT>
+__device__ __forceinline__ float wave_col_dot(const WT* __restrict__ col, int lane, const float (&phi)[8][8]) {
+    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float w8[8];
+        WaveIO<WT>::load8(col, (int64_t)j * 512 + lane * 8, w8);
+#pragma unroll
+        for (int v = 0; v < 8; ++v) acc[v & 3] = fmaf(phi[j][v], w8[v], acc[v & 3]);
+    }
+    return wave_sum_uniform((acc[0] + acc[1]) + (acc[2] + acc[3]));
+}
+
 template <int DOMAIN>
 struct WaveFourier {
     using Dom = Domain<DOMAIN>;
@@ -283,17 +297,7 @@ struct WaveFourier {
     template <class WT>
     __device__ static __forceinline__ void q_from_mem(const WT* __restrict__ Wi, int lane, const float (&phi)[8][8], float (&q)[A]) {
 #pragma unroll
-        for (int b = 0; b < A; ++b) {
-            float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float w8[8];
-                WaveIO<WT>::load8(Wi, (int64_t)b * F + j * 512 + lane * 8, w8);
-#pragma unroll
-                for (int v = 0; v < 8; ++v) acc[v & 3] = fmaf(phi[j][v], w8[v], acc[v & 3]);
-            }
-            q[b] = wave_sum_uniform((acc[0] + acc[1]) + (acc[2] + acc[3]));
-        }
+        for (int b = 0; b < A; ++b) q[b] = wave_col_dot(Wi + (int64_t)b * F, lane, phi);
     }
     // W[:,a] += scale*phi (one column, a is wave-uniform); bf16: stochastic rounding of every updated weight
     template <class WT>

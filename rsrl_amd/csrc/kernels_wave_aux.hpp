@@ -20,7 +20,7 @@
 // and the dot products of the sweep run over the rounded values -- what a fresh evaluation would read.
 #pragma once
 
-#include "kernels_wave.hpp"
+#include "wave_loop.hpp"
 #include "kernels_gq.hpp"
 #include "kernels_td.hpp"
 #include "kernels_qsigma.hpp"
@@ -37,20 +37,6 @@ struct WaveAuxParams {
     int trace;         // TDLambda: TRACE_*
 };
 
-// <phi, column> with the column streamed from memory, dot()'s order (4 interleaved chains over (j, v), then the wave total)
-template <int DOMAIN, class WT = float>
-__device__ __forceinline__ float wave_col_dot(const WT* __restrict__ col, int lane, const float (&phi)[8][8]) {
-    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        float w8[8];
-        WaveIO<WT>::load8(col, (int64_t)j * 512 + lane * 8, w8);
-#pragma unroll
-        for (int v = 0; v < 8; ++v) acc[v & 3] = fmaf(phi[j][v], w8[v], acc[v & 3]);
-    }
-    return wave_sum_uniform((acc[0] + acc[1]) + (acc[2] + acc[3]));
-}
-
 // from == nullptr: the driver loop, n_steps batch-steps of the wave's learner.  Otherwise Handler::handle on ONE caller-supplied transition per
 // learner (Mn of them; the prediction agents ignore `act`).
 template <int DOMAIN, class WT = float>
@@ -63,67 +49,41 @@ __global__ __launch_bounds__(kBlock) void k_wave_aux(Common c, WaveAuxParams ap,
     using IO = WaveIO<WT>;
     using IOX = WaveIO<float>;
     constexpr int D = WF::D, A = WF::A, F = WF::F;
-    const int lane = threadIdx.x & 63;
-    const int64_t N = c.n_envs;
     const bool driver = from == nullptr;
     const bool gq = ap.mode == WAUX_GQ;
     const int Aw = gq ? A : 1;                                                         // columns of the weight matrix
-    const int64_t i = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);      // learner of this wave (uniform)
-    unsigned long long n_ep = 0, n_trunc = 0, sum_len = 0;
-    double sum_abs = 0.0, sum_r = 0.0;
-    if (i < (driver ? N : Mn)) {
+    WaveLearner<D> env;
+    Tally tally;
+    if (env.i < (driver ? c.n_envs : Mn)) {
+        const int lane = env.lane;
         PolicyParams pol = c.pol;
         if (!gq) pol.kind = POL_RANDOM;                                                // prediction: the only policy that needs no Q
         const float gamma = c.alg.gamma, lr = c.alg.lr;
-        const uint32_t gid = (uint32_t)(c.env_offset + i);
-        const uint32_t cap = c.max_episode_steps;
-        WT* __restrict__ Wi = Wbase + i * (int64_t)Aw * F;
-        float* __restrict__ Xi = ap.aux ? ap.aux + i * (int64_t)Aw * F : nullptr;
-        float s[D];
-        int a = 0; uint32_t ep = 0;
-        if (driver) {
+        WT* __restrict__ Wi = Wbase + env.i * (int64_t)Aw * F;
+        float* __restrict__ Xi = ap.aux ? ap.aux + env.i * (int64_t)Aw * F : nullptr;
+        if (driver) env.load(c); else env.template load<A>(c, from, gq ? act : nullptr, Mn);
+        // GQ: Q(.,.); prediction: q[0] = V(.), the other entries 0
+        auto eval = [&](const float (&st)[D], float (&phi)[8][8], float (&q)[A]) {
+            WF::project(st, lane, phi);
 #pragma unroll
-            for (int d = 0; d < D; ++d) s[d] = c.state[(int64_t)d * N + i];
-            a = __builtin_amdgcn_readfirstlane(c.action[i]); ep = c.ep_step[i];
-        } else {
-#pragma unroll
-            for (int d = 0; d < D; ++d) s[d] = from[(int64_t)d * Mn + i];
-            if (gq) a = clamp_action<A>(__builtin_amdgcn_readfirstlane(act[i]));
-        }
+            for (int b = 0; b < A; ++b) q[b] = b < Aw ? wave_col_dot(Wi + (int64_t)b * F, lane, phi) : 0.0f;
+        };
         float phi_s[8][8], q_s[A];
-#pragma unroll
-        for (int b = 0; b < A; ++b) q_s[b] = 0.0f;
-        WF::project(s, lane, phi_s);
-#pragma unroll
-        for (int b = 0; b < A; ++b) if (b < Aw) q_s[b] = wave_col_dot<DOMAIN, WT>(Wi + (int64_t)b * F, lane, phi_s);       // GQ: Q(s,.); prediction: q_s[0] = V(s)
-        float facc_abs = 0.0f, facc_r = 0.0f;
+        [[clang::always_inline]] eval(env.s, phi_s, q_s);
         bool cut = false;                                                              // TDLambda: the previous transition was terminal
         for (int k = 0; k < (driver ? n_steps : 1); ++k) {
             const uint64_t t = t0 + (uint64_t)k;
-            float ns[D], r;
-            bool term, trunc = false;
-            if (driver) {
-#pragma unroll
-                for (int d = 0; d < D; ++d) ns[d] = s[d];
-                term = Dom::step(ns, a, r);
-                ep += 1;
-                trunc = !term && cap > 0 && ep >= cap;
-                if (term) Dom::reset(ns);
-            } else {
-#pragma unroll
-                for (int d = 0; d < D; ++d) ns[d] = to[(int64_t)d * Mn + i];
-                r = rew[i]; term = termf[i] != 0;
-            }
+            Transition<D> tr = driver ? env.template step<Dom>() : env.given(rew, to, termf, Mn);
+            if (driver) terminal_to_restart<Dom>(tr);                          // (Handler::handle projects the caller's s' as it is)
+            const int a = env.a;
+            const bool term = tr.term;
+            const float r = tr.r;
             float phi_n[8][8], q_n[A];
-#pragma unroll
-            for (int b = 0; b < A; ++b) q_n[b] = 0.0f;
-            WF::project(ns, lane, phi_n);
-#pragma unroll
-            for (int b = 0; b < A; ++b) if (b < Aw) q_n[b] = wave_col_dot<DOMAIN, WT>(Wi + (int64_t)b * F, lane, phi_n);   // PRE-update weights
+            [[clang::always_inline]] eval(tr.ns, phi_n, q_n);                          // PRE-update weights
             float delta;
             if (gq) {
                 const float qsa = select_a<A>(q_s, a);
-                const float td_est = wave_col_dot<DOMAIN>(Xi + (int64_t)a * F, lane, phi_s);
+                const float td_est = wave_col_dot(Xi + (int64_t)a * F, lane, phi_s);
                 float qmax;
                 const int na_star = __builtin_amdgcn_readfirstlane(find_max<A>(q_n, qmax));
                 delta = term ? (r - qsa) : (r + gamma * qmax - qsa);
@@ -131,54 +91,36 @@ __global__ __launch_bounds__(kBlock) void k_wave_aux(Common c, WaveAuxParams ap,
 #pragma unroll
                 for (int b = 0; b < A; ++b) {
                     const bool hit1 = a == b, hit2 = !term && na_star == b;            // wave-uniform
-                    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
                     U4 rnd = U4{0, 0, 0, 0};
-                    if constexpr (IO::kBf16) { if (hit1 || hit2) rnd = draw(c.seed, gid, t, BLK_SR_BASE + 64u * (uint32_t)b + (uint32_t)lane); }
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int64_t off = (int64_t)b * F + j * 512 + lane * 8;
-                        float w8[8];
-                        IO::load8(Wi, off, w8);
+                    if constexpr (IO::kBf16) { if (hit1 || hit2) rnd = draw(c.seed, env.gid, t, BLK_SR_BASE + 64u * (uint32_t)b + (uint32_t)lane); }
+                    float* __restrict__ vcol = Xi + (int64_t)b * F;                    // V[:,a] moves with W[:,a], inside the callback: it moves on a condition
+                    q_n[b] = wave_sweep_column<WT, false>(Wi + (int64_t)b * F, nullptr, lane, phi_n, rnd, hit1 || hit2, [&](int j, float (&w8)[8], float (&)[8]) {
                         if (hit1) {
 #pragma unroll
                             for (int v = 0; v < 8; ++v) w8[v] = fmaf(sc1, phi_s[j][v], w8[v]);
                             float v8[8];
-                            IOX::load8(Xi, off, v8);
+                            IOX::load8(vcol, wave_off(lane, j), v8);
 #pragma unroll
                             for (int v = 0; v < 8; ++v) v8[v] = fmaf(sc3, phi_s[j][v], v8[v]);
-                            IOX::store8(Xi, off, v8);
+                            IOX::store8(vcol, wave_off(lane, j), v8);
                         }
                         if (hit2) {
 #pragma unroll
                             for (int v = 0; v < 8; ++v) w8[v] = fmaf(sc2, phi_n[j][v], w8[v]);
                         }
-                        if (hit1 || hit2) {
-                            if constexpr (IO::kBf16) {
-#pragma unroll
-                                for (int v = 0; v < 8; ++v) w8[v] = round_bf16_sr(w8[v], sr_bits(rnd, j * 8 + v));
-                            }
-                            IO::store8(Wi, off, w8);
-                        }
-#pragma unroll
-                        for (int v = 0; v < 8; ++v) acc[v & 3] = fmaf(phi_n[j][v], w8[v], acc[v & 3]);
-                    }
-                    q_n[b] = wave_sum_uniform((acc[0] + acc[1]) + (acc[2] + acc[3]));
+                    });
                 }
             } else {
                 delta = term ? (r - q_s[0]) : (r + gamma * q_n[0] - q_s[0]);
                 const bool lam = ap.mode == WAUX_TDL;
                 const float rate_eff = cut ? 0.0f : ap.rate;
                 const float sc = lr * delta;
-                float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
                 U4 rnd = U4{0, 0, 0, 0};
-                if constexpr (IO::kBf16) rnd = draw(c.seed, gid, t, BLK_SR_BASE + (uint32_t)lane);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int64_t off = (int64_t)j * 512 + lane * 8;
-                    float w8[8], z8[8];
-                    IO::load8(Wi, off, w8);
-                    if (lam) {
-                        IOX::load8(Xi, off, z8);
+                if constexpr (IO::kBf16) rnd = draw(c.seed, env.gid, t, BLK_SR_BASE + (uint32_t)lane);
+                q_n[0] = wave_sweep_column<WT, false>(Wi, nullptr, lane, phi_n, rnd, true, [&](int j, float (&w8)[8], float (&)[8]) {
+                    if (lam) {                                                         // the trace moves inside the callback: it moves on a condition
+                        float z8[8];
+                        IOX::load8(Xi, wave_off(lane, j), z8);
 #pragma unroll
                         for (int v = 0; v < 8; ++v) {
                             float zz = fmaf(rate_eff, z8[v], 1.0f * phi_s[j][v]);      // WBuf::decay_add with the indicator 1
@@ -186,57 +128,24 @@ __global__ __launch_bounds__(kBlock) void k_wave_aux(Common c, WaveAuxParams ap,
                             w8[v] = fmaf(delta, zz, w8[v]);                            // ScaledGradientUpdate{alpha: td_error}: no learning rate
                             z8[v] = term ? 0.0f : zz;                                  // trace.reset() after a terminal transition
                         }
-                        IOX::store8(Xi, off, z8);
+                        IOX::store8(Xi, wave_off(lane, j), z8);
                     } else {
 #pragma unroll
                         for (int v = 0; v < 8; ++v) w8[v] = fmaf(sc, phi_s[j][v], w8[v]);
                     }
-                    if constexpr (IO::kBf16) {
-#pragma unroll
-                        for (int v = 0; v < 8; ++v) w8[v] = round_bf16_sr(w8[v], sr_bits(rnd, j * 8 + v));
-                    }
-                    IO::store8(Wi, off, w8);
-#pragma unroll
-                    for (int v = 0; v < 8; ++v) acc[v & 3] = fmaf(phi_n[j][v], w8[v], acc[v & 3]);
-                }
-                q_n[0] = wave_sum_uniform((acc[0] + acc[1]) + (acc[2] + acc[3]));
+                });
                 cut = term;
             }
-            if (!driver) { if (lane == 0 && td_out) td_out[i] = delta; break; }
-            const U4 x = draw(c.seed, gid, t, BLK_STEP);
-            int na = policy_sample<A>(pol, q_n, x);
-            facc_abs += fabsf(delta); facc_r += r;
-            if (term) { n_ep += 1; sum_len += ep; ep = 0; }
-            if (trunc) {                                                               // step cap: new episode (a trace is NOT reset)
-                n_ep += 1; n_trunc += 1; sum_len += ep; ep = 0;
-                Dom::reset(ns);
-                WF::project(ns, lane, phi_n);
-#pragma unroll
-                for (int b = 0; b < A; ++b) if (b < Aw) q_n[b] = wave_col_dot<DOMAIN, WT>(Wi + (int64_t)b * F, lane, phi_n);
-                const U4 xr = draw(c.seed, gid, t, BLK_RESET);
-                na = policy_sample<A>(pol, q_n, xr);
-            }
-#pragma unroll
-            for (int d = 0; d < D; ++d) s[d] = ns[d];
-#pragma unroll
-            for (int b = 0; b < A; ++b) q_s[b] = q_n[b];
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-#pragma unroll
-                for (int v = 0; v < 8; ++v) phi_s[j][v] = phi_n[j][v];
-            a = __builtin_amdgcn_readfirstlane(na);
+            if (!driver) { env.report(td_out, delta); break; }
+            // the VALUE agents' episode end; a step cap does NOT reset a trace
+            sample_then_restart<Dom>(c, env, tally, tr, delta, t,
+                [&](const float (&ns)[D]) { [[clang::always_inline]] eval(ns, phi_n, q_n); },
+                [&](const U4& x) { return policy_sample<A>(pol, q_n, x); });
+            wave_carry<A>(q_s, q_n, phi_s, phi_n);
         }
-        if (driver && lane == 0) {
-#pragma unroll
-            for (int d = 0; d < D; ++d) c.state[(int64_t)d * N + i] = s[d];
-            c.action[i] = a;
-            c.ep_step[i] = ep;
-            sum_abs = (double)facc_abs; sum_r = (double)facc_r;
-        } else {
-            n_ep = 0; n_trunc = 0; sum_len = 0;
-        }
+        if (driver) env.store(c);
     }
-    if (stats) block_stats_accumulate(stats, n_ep, n_trunc, sum_len, sum_abs, sum_r);
+    wave_hand_over(tally, env.lane, driver, stats);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -263,8 +172,7 @@ __global__ __launch_bounds__(kBlock) void k_wave_qsigma(Common c, QsParams qp, W
     const int64_t N = c.n_envs;
     const bool driver = from == nullptr;
     const int64_t i = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);      // learner of this wave (uniform)
-    unsigned long long n_ep = 0, n_trunc = 0, sum_len = 0;
-    double sum_abs = 0.0, sum_r = 0.0;
+    Tally tally;
     if (i < (driver ? N : Mn)) {
         const uint32_t gid = (uint32_t)(c.env_offset + i);
         const uint32_t cap = c.max_episode_steps;
@@ -280,11 +188,9 @@ __global__ __launch_bounds__(kBlock) void k_wave_qsigma(Common c, QsParams qp, W
             for (int d = 0; d < D; ++d) s[d] = from[(int64_t)d * Mn + i];
             a = clamp_action<A>(__builtin_amdgcn_readfirstlane(act[i]));
         }
-        float facc_abs = 0.0f, facc_r = 0.0f;
         float phi_s[8][8], q_s[A];
         WF::project(s, lane, phi_s);
-#pragma unroll
-        for (int b = 0; b < A; ++b) q_s[b] = wave_col_dot<DOMAIN, WT>(Wi + (int64_t)b * F, lane, phi_s);
+        WF::template q_from_mem<WT>(Wi, lane, phi_s, q_s);
         const int n = qp.n_steps;
         uint32_t head = qp.head[i], len = qp.len[i];
         const int64_t fs_stride = (int64_t)n * N;
@@ -315,8 +221,7 @@ __global__ __launch_bounds__(kBlock) void k_wave_qsigma(Common c, QsParams qp, W
             if (term) {
                 residual = r - qa; pi = 0.0f; mu = 1.0f;                              // :142-153
             } else {
-#pragma unroll
-                for (int b = 0; b < A; ++b) q_n[b] = wave_col_dot<DOMAIN, WT>(Wi + (int64_t)b * F, lane, phi_n);
+                WF::template q_from_mem<WT>(Wi, lane, phi_n, q_n);
                 const int na = policy_sample<A>(c.apol, q_n, xin);                   // :157 the agent's own draw
                 const float nqsna = select_a<A>(q_n, na);
                 float exp_nqs;
@@ -361,55 +266,34 @@ __global__ __launch_bounds__(kBlock) void k_wave_qsigma(Common c, QsParams qp, W
                 WF::project(as_, lane, phi_a);
                 WT* __restrict__ col = Wi + (int64_t)aa * F;
                 float wc[8][8];
-                float qacc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    IO::load8(col, (int64_t)j * 512 + lane * 8, wc[j]);
-#pragma unroll
-                    for (int v = 0; v < 8; ++v) qacc[v & 3] = fmaf(phi_a[j][v], wc[j][v], qacc[v & 3]);
-                }
-                const float qsa = wave_sum_uniform((qacc[0] + qacc[1]) + (qacc[2] + qacc[3]));      // :117 with the CURRENT weights
+                const float qsa = wave_col_read<WT>(col, lane, phi_a, wc);                          // :117 with the CURRENT weights
                 const float scale = c.alg.lr * (qp.alpha * isr * (gret - qsa));                      // :122; Handler<StateActionUpdate>: W[:,a] += lr*error*phi
                 U4 rnd = U4{0, 0, 0, 0};
                 if constexpr (IO::kBf16) rnd = draw(c.seed, gid, t, BLK_SR_BASE + 64u * (uint32_t)aa + (uint32_t)lane);
-                float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-#pragma unroll
-                    for (int v = 0; v < 8; ++v) {
-                        float x = fmaf(scale, phi_a[j][v], wc[j][v]);
-                        if constexpr (IO::kBf16) x = round_bf16_sr(x, sr_bits(rnd, j * 8 + v));
-                        wc[j][v] = x;
-                        acc[v & 3] = fmaf(phi_n[j][v], x, acc[v & 3]);
-                    }
-                    IO::store8(col, (int64_t)j * 512 + lane * 8, wc[j]);
-                }
+                const float part = wave_col_write<WT>(col, lane, wc, scale, phi_a, phi_n, rnd);
                 if (!restart && !term) {
-                    const float qpost = wave_sum_uniform((acc[0] + acc[1]) + (acc[2] + acc[3]));
+                    const float qpost = wave_sum_uniform(part);
 #pragma unroll
                     for (int b = 0; b < A; ++b) q_n[b] = (b == aa) ? qpost : q_n[b];
                 }
             }
             if (term) len = 0;                                                        // backup.clear() (:154)
             if (!driver) { if (lane == 0 && td_out) td_out[i] = residual; break; }
+            // the episode's end is restart_then_sample's convention (driver_loop.hpp) written out, and the loop keeps its own locals: with the state in
+            // WaveLearner / Transition the 24 loads of Q(s',.) above are issued one at a time instead of together and the bf16 kernel is a third slower
+            // (profiles/wave_frame.md).  The Tally, the column passes, q_from_mem and wave_carry are the frame's.
             if (restart) {
-                n_ep += 1; n_trunc += trunc ? 1 : 0; sum_len += ep; ep = 0;
+                tally.episode_end(ep, trunc);
                 Dom::reset(ns);
                 WF::project(ns, lane, phi_n);
-#pragma unroll
-                for (int b = 0; b < A; ++b) q_n[b] = wave_col_dot<DOMAIN, WT>(Wi + (int64_t)b * F, lane, phi_n);      // the UPDATED weights at s0
+                WF::template q_from_mem<WT>(Wi, lane, phi_n, q_n);                  // the UPDATED weights at s0
             }
             const U4 x = draw(c.seed, gid, t, BLK_STEP);
             a = __builtin_amdgcn_readfirstlane(policy_sample<A>(c.pol, q_n, x));
-            facc_abs += fabsf(residual); facc_r += r;
+            tally.step(residual, r);
 #pragma unroll
             for (int d = 0; d < D; ++d) s[d] = ns[d];
-#pragma unroll
-            for (int b = 0; b < A; ++b) q_s[b] = q_n[b];
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-#pragma unroll
-                for (int v = 0; v < 8; ++v) phi_s[j][v] = phi_n[j][v];
+            wave_carry<A>(q_s, q_n, phi_s, phi_n);
         }
         if (lane == 0) {
             qp.head[i] = head; qp.len[i] = len;
@@ -418,12 +302,10 @@ __global__ __launch_bounds__(kBlock) void k_wave_qsigma(Common c, QsParams qp, W
                 for (int d = 0; d < D; ++d) c.state[(int64_t)d * N + i] = s[d];
                 c.action[i] = a;
                 c.ep_step[i] = ep;
-                sum_abs = (double)facc_abs; sum_r = (double)facc_r;
             }
         }
-        if (lane != 0 || !driver) { n_ep = 0; n_trunc = 0; sum_len = 0; }
     }
-    if (stats) block_stats_accumulate(stats, n_ep, n_trunc, sum_len, sum_abs, sum_r);
+    wave_hand_over(tally, lane, driver, stats);
 }
 
 // V(s) of a prediction agent for M caller-supplied states (Function<(S,)> of the ScalarLFA), one wave per state
@@ -439,7 +321,7 @@ __global__ __launch_bounds__(kBlock) void k_wave_v_evaluate(const WT* __restrict
     for (int d = 0; d < D; ++d) s[d] = states[(int64_t)d * Mn + i];
     float phi[8][8];
     WF::project(s, lane, phi);
-    const float v = wave_col_dot<DOMAIN, WT>(Wbase + i * (int64_t)F, lane, phi);
+    const float v = wave_col_dot(Wbase + i * (int64_t)F, lane, phi);
     if (lane == 0) out[i] = v;
 }
 

@@ -1,7 +1,9 @@
 """Driver-loop rate of the thread-per-learner agents of the register family: us per batch-step and env-steps/s of each named agent's kernel on
 MountainCar at 65 536 and 262 144 learners, Fourier orders 3 and 5.  One JSON line per configuration; every agent by default.  (Replaces
 ac_rate.py, tdac_rate.py and reinforce_rate.py, which differed by their agent tables: name the agents a table held to get its rows.)
-    python scripts/agent_rate.py [AGENT ...] [--steps 256] [--warmup 32] [--sizes 65536,262144] [--orders 3,5]"""
+    python scripts/agent_rate.py [AGENT ...] [--steps 256] [--warmup 32] [--sizes 65536,262144] [--orders 3,5]
+--domain / --weight-dtype reach the other kernel families: `TD TDLambda GreedyGQ SARSALambda QLambda QSigma --domain acrobot --orders 7
+--sizes 8192 [--weight-dtype bf16]` times the order-7 wave family's memory-sweep kernels (k_wave_aux, k_wave_lambda, k_wave_qsigma)."""
 import argparse
 import json
 import os
@@ -25,6 +27,8 @@ AGENTS = {
     "REINFORCE": dict(algo=rsrl_amd.REINFORCE, **PG),
     "BaselineREINFORCE": dict(algo=rsrl_amd.BASELINE_REINFORCE, **PG),
 }
+DOMAINS = {"mountain_car": rsrl_amd.MOUNTAIN_CAR, "cart_pole": rsrl_amd.CART_POLE, "acrobot": rsrl_amd.ACROBOT}
+DTYPES = {"f32": rsrl_amd.W_F32, "bf16": rsrl_amd.W_BF16}
 
 
 def main():
@@ -34,6 +38,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=32)
     ap.add_argument("--sizes", default="65536,262144")
     ap.add_argument("--orders", default="3,5")
+    ap.add_argument("--domain", choices=list(DOMAINS), default="mountain_car")
+    ap.add_argument("--weight-dtype", choices=list(DTYPES), default="f32")
     a = ap.parse_args()
     unknown = [x for x in a.agents if x not in AGENTS]
     if unknown:
@@ -41,8 +47,8 @@ def main():
     for order in [int(x) for x in a.orders.split(",")]:
         for n in [int(x) for x in a.sizes.split(",")]:
             for agent in a.agents or AGENTS:
-                with rsrl_amd.Context(domain=rsrl_amd.MOUNTAIN_CAR, order=order, n_envs=n, max_episode_steps=1000, steps_per_launch=a.steps,
-                                      **AGENTS[agent]) as c:
+                with rsrl_amd.Context(domain=DOMAINS[a.domain], order=order, n_envs=n, max_episode_steps=1000, steps_per_launch=a.steps,
+                                      weight_dtype=DTYPES[a.weight_dtype], **AGENTS[agent]) as c:
                     c.reset()
                     c.train(a.warmup, want_stats=False)
                     c.sync()
