@@ -178,7 +178,24 @@ typedef enum { RSRL_QLEARNING = 0, RSRL_SARSA = 1, RSRL_EXPECTED_SARSA = 2, RSRL
                 * rsrl_hip_get/set_policy_weights).  handle_batch, traces and td weights are ESTATE.  rsrl_hip_handle's td_error_out and the
                 * statistics' sum |delta| are iLSTD's diagnostic.  rsrl_hip_reset leaves both agents' state alone.  Supported: as
                 * RSRL_TD_ACTOR_CRITIC; everything else is EINVAL at create (kernels_tdac_lstd.hpp) */
-               RSRL_ILSTD_ACTOR_CRITIC = 21 } rsrl_algo;
+               RSRL_ILSTD_ACTOR_CRITIC = 21,
+               /* (22 is no algo.)  GradientMC (prediction/mc.rs:26-58): every-visit Monte-Carlo prediction, v_func = ScalarLFA(basis, SGD(lr)).
+                * Handler<&Trajectory>::handle visits the transitions LAST TO FIRST (TrajectoryIter::next_back, rsrl_domains/src/lib.rs:289-319):
+                *   sum = 0;  for k = n-1 .. 0:  sum = r_k + gamma * sum;  w += lr * (sum - <w, phi(s_k)>) * phi(s_k)       (w as the previous visit left it)
+                * Only a transition's `from` and its reward are read; a trajectory cut by a step limit gets no bootstrap.  One visit is RSRL_TD's
+                * terminal-transition update with r := sum (the return an f32 multiply followed by an add).  The return runs backwards, so the driver
+                * loop keeps every learner's OPEN EPISODE on the device -- transition k's (from, reward) in row k, episode_steps[i] rows, at most
+                * max_episode_steps -- and sweeps it when the episode ends (terminal or max_episode_steps), then restarts; the environment side is
+                * RSRL_TD's draw for draw.  config: lr, gamma; max_episode_steps >= 1 (EINVAL for 0: an unbounded episode has no record size).
+                * Supported: as RSRL_RECURSIVE_LSTD (per-learner f32 weights, the register-family Fourier orders, policy RSRL_RANDOM, agent_policy
+                * -1, no epsilon schedule); everything else is EINVAL at create (kernels_gmc.hpp).  The value side is V (n_outputs 1): q_evaluate
+                * writes f32[1][M], get / set_weights are f32[F][1]; q_find_max / _min, q_expected_value, traces, td / policy weights, the lstd state
+                * and return_carry are ESTATE.  rsrl_hip_handle is ESTATE (there is no Handler<&Transition>): rsrl_hip_handle_batch.  The record is
+                * read and written with rsrl_hip_get/set_episode_record; rsrl_hip_reset and rsrl_hip_domain_reset empty the restarted learners'
+                * (episode_steps = 0), and rsrl_hip_set_episode_steps refuses a value above max_episode_steps.  The statistics' sum |delta| is the
+                * sum of |sum - pred| over the sweeps, booked at the step that ended the episode.  The checkpoint holds the weights only (RSRL_TD's
+                * layout): the open record is the caller's to carry, like the states, actions and episode steps */
+               RSRL_GRADIENT_MC = 23 } rsrl_algo;
 /* rsrl::traces::{Accumulate, Saturate (Trace::replacing), Dutch}      traces.rs:188-240 */
 typedef enum { RSRL_TRACE_ACCUMULATE = 0, RSRL_TRACE_SATURATE = 1, RSRL_TRACE_DUTCH = 2 } rsrl_trace;
 /* rsrl::policies::{Greedy, EpsilonGreedy, Softmax, Random}
@@ -341,6 +358,12 @@ int rsrl_hip_set_actions(rsrl_hip_ctx* ctx, const int32_t* actions /*[N]*/);
  *     launch continues from it.  EINVAL for a ctx whose kernels carry nothing. */
 int rsrl_hip_get_episode_steps(rsrl_hip_ctx* ctx, uint32_t* steps /*[N]*/);
 int rsrl_hip_set_episode_steps(rsrl_hip_ctx* ctx, const uint32_t* steps /*[N]*/);
+/* (RSRL_GRADIENT_MC: set_episode_steps refuses a value above max_episode_steps with EINVAL and changes nothing -- the kernel indexes the record by it.)
+ * RSRL_GRADIENT_MC's open episodes, cap = max_episode_steps rows: learner i's record is rows 0 .. episode_steps[i]-1 of its column, row k holding
+ * transition k's `from` state and reward.  get writes NaN in the rows past that; set installs both arrays whole (what lies past a learner's
+ * episode_steps is never read).  Host or device arrays.  ESTATE on every other agent */
+int rsrl_hip_get_episode_record(rsrl_hip_ctx* ctx, float* states /*[cap][D][N]*/, float* rewards /*[cap][N]*/);
+int rsrl_hip_set_episode_record(rsrl_hip_ctx* ctx, const float* states /*[cap][D][N]*/, const float* rewards /*[cap][N]*/);
 int rsrl_hip_get_q_carry(rsrl_hip_ctx* ctx, float* q /*[A][N]*/, int32_t* valid);
 int rsrl_hip_set_q_carry(rsrl_hip_ctx* ctx, const float* q /*[A][N]*/);
 
@@ -403,7 +426,11 @@ int rsrl_hip_handle(rsrl_hip_ctx* ctx, const float* from_states, const int32_t* 
  *     domain_step -> (append the transition) -> handle_batch(lengths = episode length of the learners whose episode just ended, else 0)
  *     -> domain_reset(ended) -> policy_sample(NULL)
  * runs on the driver loop's draws.  Host or device arrays, as rsrl_hip_handle (host actions of the handled rows and host lengths are validated,
- * device ones clamped).  ESTATE on every other agent. */
+ * device ones clamped).
+ * RSRL_GRADIENT_MC: Handler<&Trajectory>::handle for every learner.  Row k of states is transition k's `from`, learner i's trajectory is rows
+ * 0 .. lengths[i]-1, visited LAST TO FIRST; actions may be NULL and are ignored when given.  returns_out receives `sum` at each handled row and NaN
+ * past a learner's length; a learner of length 0 keeps its bytes.  The ctx's own open record is not touched.  The trait loop is the one above.
+ * ESTATE on every other agent. */
 int rsrl_hip_handle_batch(rsrl_hip_ctx* ctx, int64_t T, const float* states /*[T][D][N]*/, const int32_t* actions /*[T][N]*/,
                           const float* rewards /*[T][N]*/, const uint32_t* lengths /*[N]*/, float* returns_out /*[T][N], optional*/);
 

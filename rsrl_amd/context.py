@@ -14,6 +14,7 @@ TD_ACTOR_CRITIC = 13                           # ActorCritic::tdac: the Gibbs ac
 REINFORCE, BASELINE_REINFORCE = 15, 16         # (14 is no algo) control/mc: REINFORCE<Gibbs>, BaselineREINFORCE<B, Gibbs> (Handler<&Batch>: handle_batch)
 RECURSIVE_LSTD, ILSTD = 18, 19                  # (17 is no algo) prediction/lstd: RecursiveLSTD, iLSTD (f64 theta and F x F matrix: get/set_lstd_state)
 ILSTD_ACTOR_CRITIC = 21                        # (20 is no algo) ActorCritic::tdac over iLSTD, tdac.rs's agent: lr = iLSTD's alpha, n_steps = its n_updates, alpha = the actor's
+GRADIENT_MC = 23                               # (22 is no algo) prediction/mc.rs: GradientMC (Handler<&Trajectory>: handle_batch; episode_record)
 TRACE_ACCUMULATE, TRACE_SATURATE, TRACE_DUTCH = 0, 1, 2
 GREEDY, EPSILON_GREEDY, SOFTMAX, RANDOM = 0, 1, 2, 3
 W_PER_ENV, W_SHARED = 0, 1
@@ -191,6 +192,21 @@ class Context:
         _abi.check(self._L.rsrl_hip_set_episode_steps(self._h, _p(_in(v, np.uint32, (self.N,)))))
 
     @property
+    def episode_record(self):
+        """GRADIENT_MC's open episodes -> (states (cap, D, N), rewards (cap, N)), cap = max_episode_steps: learner i's record is rows
+        0 .. episode_steps[i]-1 of its column (row k: transition k's `from` and reward), NaN past that; RsrlHipError on the other agents"""
+        cap = int(self.cfg.max_episode_steps)
+        s, r = np.empty((cap, self.D, self.N), dtype=np.float32), np.empty((cap, self.N), dtype=np.float32)
+        _abi.check(self._L.rsrl_hip_get_episode_record(self._h, _p(s), _p(r)))
+        return s, r
+
+    @episode_record.setter
+    def episode_record(self, v):
+        cap = int(self.cfg.max_episode_steps)
+        s, r = v
+        _abi.check(self._L.rsrl_hip_set_episode_record(self._h, _p(_in(s, np.float32, (cap, self.D, self.N))), _p(_in(r, np.float32, (cap, self.N)))))
+
+    @property
     def q_carry(self):
         """Q(s,.) as the register-family loops carry it from launch to launch, (A, N) -- None while nothing is carried (ABI 8)"""
         out = np.empty((self.A, self.N), dtype=np.float32)
@@ -270,12 +286,17 @@ class Context:
                                            _p(_in(terminal, np.uint8, (M,))), M, _p(td)))
         return td
 
-    def handle_batch(self, states, actions, rewards, lengths, returns=False):
+    def handle_batch(self, states, actions=None, rewards=None, lengths=None, returns=False, T=None):
         """Handler<&Batch>::handle of REINFORCE / BASELINE_REINFORCE for every learner: states (T, D, N), actions / rewards (T, N), lengths (N,) --
         learner i's batch is rows 0 .. lengths[i]-1 of its column.  returns=True: also the running return g at each handled transition, (T, N)
-        (NaN where nothing was handled).  One batch-step, as handle"""
-        T = int(np.shape(rewards)[0])
-        ret = np.full((T, self.N), np.nan, dtype=np.float32) if returns else None
+        (NaN where nothing was handled).  One batch-step, as handle.
+        GRADIENT_MC: Handler<&Trajectory>::handle -- row k is transition k's `from` and reward, visited last to first; actions may be None (they
+        are not read), and the returns are the backward sums.  Arrays may be raw device pointers (int): then T is given, and `returns` may be the
+        device pointer the returns are written to"""
+        if rewards is None or lengths is None:
+            raise ValueError("handle_batch needs rewards and lengths")
+        T = int(np.shape(rewards)[0]) if T is None else int(T)
+        ret = returns if isinstance(returns, int) and not isinstance(returns, bool) else (np.full((T, self.N), np.nan, dtype=np.float32) if returns else None)
         _abi.check(self._L.rsrl_hip_handle_batch(self._h, T, _p(_in(states, np.float32, (T, self.D, self.N))), _p(_in(actions, np.int32, (T, self.N))),
                                                  _p(_in(rewards, np.float32, (T, self.N))), _p(_in(lengths, np.uint32, (self.N,))), _p(ret)))
         return ret

@@ -45,6 +45,7 @@ static AgentFamily classify(const rsrl_hip_config& cfg, size_t w_elems) {
     if (is_reinforce(al)) return F::ReinforceReg;
     if (is_lstd(al)) return F::LstdReg;
     if (is_tdac_lstd(al)) return F::TdAcLstdReg;
+    if (is_gmc(al)) return F::GmcReg;
     if (cfg.weight_mode == RSRL_W_SHARED) return fourier ? F::SharedDense : (is_sparse_lambda(cfg) ? F::SharedSparseLambda : F::SharedTile);
     if (wave && is_wave_aux_algo(al)) return F::WaveAux;
     if (is_pred(al)) return tile ? F::TdTile : (reg ? F::TdReg : F::TdGeneric);
@@ -141,7 +142,7 @@ int rsrl_hip_destroy(rsrl_hip_ctx* c) {
 }
 
 // The agents that exist only on the register-family Fourier orders with per-learner f32 weights (train_ac.hip, train_tdac.hip, train_reinforce.hip,
-// train_lstd.hip, train_tdac_lstd.hip): the policy is the agent's own -- the Gibbs actor / policy, or the prediction agents' Random behaviour -- and the
+// train_lstd.hip, train_tdac_lstd.hip, train_gmc.hip): the policy is the agent's own -- the Gibbs actor / policy, or the prediction agents' Random behaviour -- and the
 // critic shares it; iLSTD's n_updates travel as config.n_steps.  `storage`: register-family order, per-learner f32 weights, no epsilon schedule
 static int check_reg_only(const rsrl_hip_config& cfg, const AlgoRow& a, bool storage) {
     if (!storage || cfg.policy != a.reg_policy || cfg.agent_policy != -1)
@@ -152,6 +153,10 @@ static int check_reg_only(const rsrl_hip_config& cfg, const AlgoRow& a, bool sto
                     cfg.domain, cfg.basis, cfg.order, cfg.weight_mode, cfg.weight_dtype, cfg.policy, cfg.agent_policy, cfg.epsilon_decay);
     if (a.n_updates && (cfg.n_steps < 1 || cfg.n_steps > 32))
         return fail(RSRL_HIP_EINVAL, "%s: n_steps (%sn_updates, the rounds of solve() per transition) must be in [1, 32], got %d", a.name, a.n_updates, cfg.n_steps);
+    // GradientMC keeps every learner's open episode on the device, max_episode_steps rows of it
+    if (a.agent == Agent::Gmc && cfg.max_episode_steps < 1)
+        return fail(RSRL_HIP_EINVAL, "%s: max_episode_steps must be >= 1 -- the device records every learner's open episode, and an unbounded episode "
+                                     "(max_episode_steps = 0) has no record size", a.name);
     return RSRL_HIP_OK;
 }
 
@@ -167,7 +172,7 @@ static int check_config(const rsrl_hip_config& cfg) {
     const int D = kDomainShape[cfg.domain][0], A = kDomainShape[cfg.domain][1];
     if (cfg.n_envs < 1) return fail(RSRL_HIP_EINVAL, "n_envs must be >= 1");
     if (cfg.n_envs + cfg.env_offset > (int64_t)0xffffffffLL || cfg.env_offset < 0) return fail(RSRL_HIP_EINVAL, "global env ids must fit 32 bits");
-    if (cfg.algo < 0 || cfg.algo > RSRL_ILSTD_ACTOR_CRITIC || !kAlgo[cfg.algo].name) return fail(RSRL_HIP_EINVAL, "unknown algo %d", cfg.algo);
+    if (cfg.algo < 0 || cfg.algo > RSRL_GRADIENT_MC || !kAlgo[cfg.algo].name) return fail(RSRL_HIP_EINVAL, "unknown algo %d", cfg.algo);
     if (cfg.policy < 0 || cfg.policy > RSRL_RANDOM) return fail(RSRL_HIP_EINVAL, "unknown policy %d", cfg.policy);
     // Softmax::new panics for |tau| < 1e-7 (policies/softmax.rs:63-66)
     if (cfg.policy == RSRL_SOFTMAX && std::fabs(cfg.tau) < 1e-7) return fail(RSRL_HIP_EINVAL, "Tau parameter in Softmax must be non-zero.");
@@ -343,6 +348,14 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
         KCHECK();
         if (cfg->algo != RSRL_RECURSIVE_LSTD) TRY(ctx_alloc(c, &c->lstd_mu, sizeof(double) * nv, true));
     }
+    if (is_gmc(cfg->algo)) {
+        // the open episodes (empty: ep_step = 0 below).  Not zero-filled: nothing at or past a learner's ep_step is ever read (get_episode_record shows NaN)
+        const uint64_t rows = (uint64_t)cfg->max_episode_steps * (uint64_t)N;      // (<= 2^64 - 2^33: both factors fit 32 bits)
+        if (rows > (uint64_t)1 << 40) return fail(RSRL_HIP_ENOMEM, "GradientMC's episode record: max_episode_steps * n_envs = %llu rows do not fit any device",
+                                                  (unsigned long long)rows);
+        TRY(ctx_alloc(c, &c->rec_s, (size_t)(rows * (uint64_t)c->D * sizeof(float))));
+        TRY(ctx_alloc(c, &c->rec_r, (size_t)(rows * sizeof(float))));
+    }
     if (shared) {
         TRY(ctx_alloc(c, &c->flags, (size_t)N));
         if (c->family == AgentFamily::SharedDense) {
@@ -483,7 +496,7 @@ int rsrl_hip_reset(rsrl_hip_ctx* c) {
     const BasisGeom g = make_geom(c);
     if (c->family == AgentFamily::Hiv) {
         launch_hiv_reset(c->stream, k, g, c->hiv_y, c->t);
-    } else if (is_pred(c->cfg.algo) || is_lstd(c->cfg.algo)) {       // (the LSTD agents' state is untouched: the weights are not reset either)
+    } else if (is_v_only(c->cfg.algo)) {       // (the LSTD agents' state is untouched: the weights are not reset either; GradientMC's records empty with ep_step = 0)
         if (!launch_reset_td(c->cfg.domain, dim3(grid_for(k.n_envs)), dim3(kBlock), c->stream, k, c->t)) return NO_MODEL(c);
     } else if (is_wave_family(c->family)) {
         for_wave(c, [&](auto tag) {
@@ -577,7 +590,45 @@ int rsrl_hip_get_episode_steps(rsrl_hip_ctx* c, uint32_t* steps) {
 int rsrl_hip_set_episode_steps(rsrl_hip_ctx* c, const uint32_t* steps) {
     CHECK_CTX(c); FLUSH(c); if (!steps) return fail(RSRL_HIP_EINVAL, "null argument");
     HIP_TRY(hipSetDevice(c->cfg.device));
+    if (c->family == AgentFamily::GmcReg) {
+        // k_train_gmc indexes the learner's record by it: checked before anything is installed (a device array through a host copy)
+        const size_t n = (size_t)c->cfg.n_envs;
+        std::vector<uint32_t> h(n);
+        HIP_TRY(hipMemcpyAsync(h.data(), steps, sizeof(uint32_t) * n, hipMemcpyDefault, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < n; ++i)
+            if (h[i] > c->cfg.max_episode_steps)
+                return fail(RSRL_HIP_EINVAL, "episode_steps[%zu] = %u is more than max_episode_steps = %u, the rows of GradientMC's episode record", i, h[i],
+                            c->cfg.max_episode_steps);
+    }
     HIP_TRY(hipMemcpyAsync(c->ep_step, steps, sizeof(uint32_t) * (size_t)c->cfg.n_envs, hipMemcpyDefault, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RSRL_HIP_OK;
+}
+// GradientMC's open episodes (rec_s / rec_r): read with NaN past each learner's episode_steps, installed whole
+static const char* const kNoEpisodeRecord = "only GradientMC (RSRL_GRADIENT_MC) keeps the learners' open episodes on the device";
+int rsrl_hip_get_episode_record(rsrl_hip_ctx* c, float* states, float* rewards) {
+    CHECK_CTX(c); FLUSH(c); if (!states || !rewards) return fail(RSRL_HIP_EINVAL, "null argument");
+    if (c->family != AgentFamily::GmcReg) return fail(RSRL_HIP_ESTATE, "%s", kNoEpisodeRecord);
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    const int64_t N = c->cfg.n_envs, cap = (int64_t)c->cfg.max_episode_steps;
+    OutBuf<float> os, orw;
+    TRY(stage_out(c, 0, states, (size_t)cap * (size_t)c->D * (size_t)N, &os));
+    TRY(stage_out(c, 1, rewards, (size_t)cap * (size_t)N, &orw));
+    launch_gmc_record_get(c->stream, make_gmc(c), c->ep_step, N, cap, c->D, os.dev, orw.dev);
+    KCHECK();
+    bool sync = false;
+    TRY(flush_out(c, &os, &sync)); TRY(flush_out(c, &orw, &sync));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RSRL_HIP_OK;
+}
+int rsrl_hip_set_episode_record(rsrl_hip_ctx* c, const float* states, const float* rewards) {
+    CHECK_CTX(c); FLUSH(c); if (!states || !rewards) return fail(RSRL_HIP_EINVAL, "null argument");
+    if (c->family != AgentFamily::GmcReg) return fail(RSRL_HIP_ESTATE, "%s", kNoEpisodeRecord);
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    const size_t rows = (size_t)c->cfg.max_episode_steps * (size_t)c->cfg.n_envs;
+    HIP_TRY(hipMemcpyAsync(c->rec_s, states, sizeof(float) * rows * (size_t)c->D, hipMemcpyDefault, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->rec_r, rewards, sizeof(float) * rows, hipMemcpyDefault, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RSRL_HIP_OK;
 }

@@ -420,6 +420,9 @@ int launch_agent(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, uint64_t 
     case AgentFamily::ReinforceReg:      // (io: rsrl_hip_handle refuses these agents before it gets here; rsrl_hip_handle_batch launches its own)
         ok = !io && launch_reinforce(cf.domain, cf.order, cf.algo == RSRL_BASELINE_REINFORCE, grid, block, c->stream, k, make_reinforce(c), t, chunk, d_stats, nullptr);
         break;
+    case AgentFamily::GmcReg:            // (io: rsrl_hip_handle refuses the agent before it gets here; rsrl_hip_handle_batch launches its own)
+        ok = !io && launch_gmc(cf.domain, cf.order, grid, block, c->stream, k, make_gmc(c), t, chunk, d_stats, nullptr);
+        break;
     default: ok = false; break;      // (the shared-W families: enqueue_shared_step)
     }
     if (!ok) return NO_MODEL(c);
@@ -578,7 +581,7 @@ static int rollout_impl(rsrl_hip_ctx* c, int64_t step_limit, int64_t M, uint32_t
     }
     if (step_limit < 1) return fail(RSRL_HIP_EINVAL, "step_limit must be >= 1, or 0 for no limit (bounded by config.max_episode_steps)");
     if (M < 1 || M > c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "bad batch (M=%lld, n_envs=%lld)", (long long)M, (long long)c->cfg.n_envs);
-    if (is_pred(c->cfg.algo) || is_lstd(c->cfg.algo))          // (W is one column: the model kernels below would read A of them)
+    if (is_v_only(c->cfg.algo))          // (W is one column: the model kernels below would read A of them)
         return fail(RSRL_HIP_ESTATE, "a prediction agent has a state-value function only: no action values to roll out with");
     if (!rp.sample && c->cfg.policy == RSRL_RANDOM) return fail(RSRL_HIP_EINVAL, "Random policy has no mode.");
     HIP_TRY(hipSetDevice(c->cfg.device));

@@ -124,7 +124,7 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
                size_t icount = 0, const float* fin = nullptr, size_t fin_count = 0, const int32_t* iin = nullptr, uint64_t step_t = 0) {
     CHECK_CTX(c); FLUSH(c);
     if (!states || M_ < 1 || M_ > c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "bad batch (M=%lld, n_envs=%lld)", (long long)M_, (long long)c->cfg.n_envs);
-    if ((is_pred(c->cfg.algo) || is_lstd(c->cfg.algo)) && op != QOP_EVALUATE && op != QOP_FEATURES)
+    if (is_v_only(c->cfg.algo) && op != QOP_EVALUATE && op != QOP_FEATURES)
         return fail(RSRL_HIP_ESTATE, "a prediction agent has a state-value function only (use rsrl_hip_q_evaluate for V(s))");
     // the TD ActorCritic: its value side is V(s) (no action values to search or weigh), its policy side the actor's theta
     if (is_v_actor_critic(c) && (op == QOP_FIND_MAX || op == QOP_FIND_MIN || op == QOP_EXPECTED))
@@ -151,7 +151,7 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
     const BasisGeom g = make_geom(c);
     if (has_lstd_state(c) && op == QOP_EVALUATE) {                        // V(s) = f32(phi(s) . theta), in f64 (k_lstd_v)
         if (!launch_lstd_v(c->cfg.domain, c->cfg.order, c->stream, c->lstd_theta, d_states, M_, of.dev)) return NO_MODEL(c);
-    } else if ((is_pred(c->cfg.algo) || is_tdac(c->cfg.algo)) && op == QOP_EVALUATE) {          // V(s) (the TD ActorCritic: its w, k_v_evaluate)
+    } else if ((is_pred(c->cfg.algo) || is_tdac(c->cfg.algo) || is_gmc(c->cfg.algo)) && op == QOP_EVALUATE) {      // V(s) (the TD ActorCritic, GradientMC: their w, k_v_evaluate)
         bool ok = true;
         switch (c->family) {
         case AgentFamily::WaveAux:
@@ -208,8 +208,8 @@ static int sample_emit(rsrl_hip_ctx* c, int64_t M, int32_t* actions_out) {
     if (M != c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "policy_sample(states = NULL) samples for the ctx's own envs: M must be n_envs (%lld), got %lld", (long long)c->cfg.n_envs, (long long)M);
     if (is_pred(c->cfg.algo)) return fail(RSRL_HIP_ESTATE, "a prediction agent has a state-value function only (use rsrl_hip_q_evaluate for V(s))");
     const bool dev_out = is_device_ptr(actions_out);
-    if (c->family == AgentFamily::LstdReg) {
-        // RecursiveLSTD / iLSTD: the driver loop's Random sample (what rsrl_hip_train draws at batch-step step_count - 1; the initial sample's stream
+    if (c->family == AgentFamily::LstdReg || c->family == AgentFamily::GmcReg) {
+        // RecursiveLSTD / iLSTD / GradientMC: the driver loop's Random sample (what rsrl_hip_train draws at batch-step step_count - 1; the initial sample's stream
         // before the first handle), so that the trait-granular loop runs on the driver loop's draws
         FLUSH(c);
         HIP_TRY(hipSetDevice(c->cfg.device));
@@ -317,6 +317,8 @@ int rsrl_hip_handle(rsrl_hip_ctx* c, const float* from_states, const int32_t* ac
     if (M < 1 || M > c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "bad batch size");
     if (c->family == AgentFamily::ReinforceReg)
         return fail(RSRL_HIP_ESTATE, "REINFORCE and BaselineREINFORCE handle whole batches only (Handler<&Batch>): use rsrl_hip_handle_batch");
+    if (c->family == AgentFamily::GmcReg)
+        return fail(RSRL_HIP_ESTATE, "GradientMC handles whole trajectories only (Handler<&Trajectory>, visited last to first): use rsrl_hip_handle_batch");
     // the transition rsrl_hip_domain_step has just been handed (same arrays, every learner): accepted, launched with it (rsrl_hip_domain_step)
     if (c->tp.stage == 1 && from_states == c->tp.from && actions == c->tp.act && rewards == c->tp.rew && to_states == c->tp.to && terminal == c->tp.term &&
         M == c->cfg.n_envs && (!td_error_out || is_device_ptr(td_error_out))) {
@@ -420,10 +422,13 @@ int rsrl_hip_handle(rsrl_hip_ctx* c, const float* from_states, const int32_t* ac
 int rsrl_hip_handle_batch(rsrl_hip_ctx* c, int64_t T, const float* states, const int32_t* actions, const float* rewards, const uint32_t* lengths,
                           float* returns_out) {
     CHECK_CTX(c);
-    if (c->family != AgentFamily::ReinforceReg)
-        return fail(RSRL_HIP_ESTATE, "only REINFORCE and BaselineREINFORCE handle whole batches (Handler<&Batch>); the other agents handle transitions (rsrl_hip_handle)");
+    const bool gmc = c->family == AgentFamily::GmcReg;      // Handler<&Trajectory>: reads no actions
+    if (c->family != AgentFamily::ReinforceReg && !gmc)
+        return fail(RSRL_HIP_ESTATE, "only REINFORCE, BaselineREINFORCE (Handler<&Batch>) and GradientMC (Handler<&Trajectory>) handle whole batches; the other "
+                                     "agents handle transitions (rsrl_hip_handle)");
     if (T < 0) return fail(RSRL_HIP_EINVAL, "bad batch length T = %lld", (long long)T);
-    if (!lengths || (T > 0 && (!states || !actions || !rewards))) return fail(RSRL_HIP_EINVAL, "null argument");
+    if (gmc) actions = nullptr;
+    if (!lengths || (T > 0 && (!states || (!actions && !gmc) || !rewards))) return fail(RSRL_HIP_EINVAL, "null argument");
     FLUSH(c);
     HIP_TRY(hipSetDevice(c->cfg.device));
     const int64_t N = c->cfg.n_envs;
@@ -449,8 +454,10 @@ int rsrl_hip_handle_batch(rsrl_hip_ctx* c, int64_t T, const float* states, const
     io.T = T; io.ret_out = oret.dev;
     if (T > 0) {
         const Common k = make_common(c);
-        if (!launch_reinforce(c->cfg.domain, c->cfg.order, c->cfg.algo == RSRL_BASELINE_REINFORCE, dim3(grid_for(N)), dim3(kBlock), c->stream, k,
-                              make_reinforce(c), c->t, 1, nullptr, &io))
+        const GmcBatch gio{io.states, io.rew, io.len, io.T, io.ret_out};
+        if (gmc ? !launch_gmc(c->cfg.domain, c->cfg.order, dim3(grid_for(N)), dim3(kBlock), c->stream, k, make_gmc(c), c->t, 1, nullptr, &gio)
+                : !launch_reinforce(c->cfg.domain, c->cfg.order, c->cfg.algo == RSRL_BASELINE_REINFORCE, dim3(grid_for(N)), dim3(kBlock), c->stream, k,
+                                    make_reinforce(c), c->t, 1, nullptr, &io))
             return NO_MODEL(c);
         KCHECK();
     }

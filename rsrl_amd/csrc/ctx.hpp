@@ -49,7 +49,7 @@ using namespace rsrl;
 
 // ---- THE agent table: what the reference's agent of each rsrl_algo is, one row per number.  Admission (check_config), the ctx's buffers (create_impl),
 // the accessors and the checkpoint read it; a new agent adds its row here, a line of classify() and a case of launch_agent ("Adding an agent").
-enum class Agent : uint8_t { None, OneStep, Lambda, Gq, Pred, QSigma, Ac, TdAc, Reinforce, Lstd, TdAcLstd };      // the group classify() and the kernels' dispatch know it by
+enum class Agent : uint8_t { None, OneStep, Lambda, Gq, Pred, QSigma, Ac, TdAc, Reinforce, Lstd, TdAcLstd, Gmc };      // the group classify() and the kernels' dispatch know it by
 enum class Aux : uint8_t { None, LikeW, Policy };      // the second per-learner matrix Z: none, of W's shape, or the actor's A columns next to a one-column W
 struct AlgoRow {
     const char* name = nullptr;      // as the admission messages print it (nullptr: the number is unassigned)
@@ -63,7 +63,7 @@ struct AlgoRow {
     // one of them), the message's words behind it and behind "agent_policy = -1", and what it calls config.n_steps in front of "n_updates" (nullptr: not read)
     int reg_policy = -1; const char* policy_words = ""; const char* shares_words = ""; const char* n_updates = nullptr;
 };
-constexpr AlgoRow kAlgo[RSRL_ILSTD_ACTOR_CRITIC + 1] = {
+constexpr AlgoRow kAlgo[RSRL_GRADIENT_MC + 1] = {
     /*  0 */ {"QLearning", Agent::OneStep},
     /*  1 */ {"SARSA", Agent::OneStep},
     /*  2 */ {"ExpectedSARSA", Agent::OneStep},
@@ -89,6 +89,9 @@ constexpr AlgoRow kAlgo[RSRL_ILSTD_ACTOR_CRITIC + 1] = {
     /* 19 */ {"iLSTD (RSRL_ILSTD)", Agent::Lstd, true, Aux::None, 8, false, true, RSRL_RANDOM, "", "", ""},
     /* 20 */ {},
     /* 21 */ {"the iLSTD ActorCritic (RSRL_ILSTD_ACTOR_CRITIC)", Agent::TdAcLstd, true, Aux::Policy, 9, false, true, RSRL_SOFTMAX, " (the Gibbs actor)", "", "the critic's "},
+    /* 22 */ {},
+    // (W is V's one column, TD's layout; the open episodes live in rec_s / rec_r)
+    /* 23 */ {"GradientMC (RSRL_GRADIENT_MC)", Agent::Gmc, true, Aux::None, 0, false, false, RSRL_RANDOM},
 };
 // (readers of the table, for configurations check_config has admitted: the algo is a row with a name)
 static inline bool is_lambda(int algo) { return kAlgo[algo].agent == Agent::Lambda; }
@@ -98,6 +101,9 @@ static inline bool is_tdac(int algo) { return kAlgo[algo].agent == Agent::TdAc; 
 static inline bool is_reinforce(int algo) { return kAlgo[algo].agent == Agent::Reinforce; }
 static inline bool is_lstd(int algo) { return kAlgo[algo].agent == Agent::Lstd; }
 static inline bool is_tdac_lstd(int algo) { return kAlgo[algo].agent == Agent::TdAcLstd; }
+static inline bool is_gmc(int algo) { return kAlgo[algo].agent == Agent::Gmc; }
+// the agents whose value function is V alone and whose behaviour is Random: no action values to search, weigh, sample from or roll out with
+static inline bool is_v_only(int algo) { return is_pred(algo) || is_lstd(algo) || is_gmc(algo); }
 
 // ---- the small kernels more than one unit launches, and the launches of kernel templates two units would otherwise both instantiate: defined ONCE, in
 // kernels_util.hip / launch_shared.hip (a kernel's host stub is an ordinary function: another unit launches it through this declaration)
@@ -178,8 +184,9 @@ enum class AgentFamily : uint8_t {
     LstdReg,              // RecursiveLSTD / iLSTD, register-family Fourier, per-learner state: k_train_lstd (train_lstd.hip); f64 state in lstd_theta / lstd_mat / lstd_mu
     TdAcLstdReg,          // ActorCritic with the iLSTD critic, same configurations as TdAcReg: k_train_tdac_lstd (train_tdac_lstd.hip); iLSTD's f64 state as
                           // LstdReg's, theta in Z (A columns)
+    GmcReg,               // GradientMC, same configurations as LstdReg: k_train_gmc (train_gmc.hip); w in W (one column), the open episodes in rec_s / rec_r
 };
-constexpr size_t kAgentFamilies = (size_t)AgentFamily::TdAcLstdReg + 1;      // (the enum's last value)
+constexpr size_t kAgentFamilies = (size_t)AgentFamily::GmcReg + 1;      // (the enum's last value)
 // ---- THE family table: which kernels serve a family and what they can do, one row per AgentFamily value in the enum's order.  classify() (abi_ctx.hip: a
 // decision) and launch_agent (abi_train.hip: it instantiates the templates) are the two other places a new family is entered.
 enum class Slots : uint8_t { Block, Block64, WaveBlock, Learner, LstdGroup };      // a statistics slot per: kBlock learners, 64 learners (k_train_lambda_mem4; the
@@ -200,7 +207,9 @@ struct FamilyRow {
 // 2 048 -> 9.06e10, 4 096 -> 9.12e10, 8 192 -> 9.17e10 env-steps/s; 4 096 is a 2.9 ms launch at 65 536 learners.  The memory-resident and wave-family loops keep 256 (their steps are 15-150x longer).  RecursiveLSTD / iLSTD (and
 // the iLSTD ActorCritic, the same f64 step with the actor's f32 work beside it): O(F^2) f64 per learner-step, 0.76 / 1.03 ms per batch-step at 262 144
 // MountainCar order-5 learners -- 32 keep a launch in the tens of milliseconds there.  HIVTreatment: one batch-step is 1 000 f64 RK4
-// sub-steps per learner, ~1 ms at 65 536 learners -- 16 keep a launch in the tens of milliseconds.
+// sub-steps per learner, ~1 ms at 65 536 learners -- 16 keep a launch in the tens of milliseconds.  GradientMC starts from TdReg's 4 096: at 65 536
+// MountainCar order-3 learners (cap 1 000) the median of seven 8 192-step regions is 1.887 / 1.890 / 1.800 us per batch-step at 1 024 / 4 096 /
+// 16 384 steps per launch, inside the regions' own drift (1.14 -> 2.13 us as the learners' episodes fall out of step; profiles/gmc_rate.md).
 constexpr FamilyRow kFamily[] = {
     {AgentFamily::SharedDense, "k_shared_step", 256, Slots::Block, Handle::Model, 0},
     {AgentFamily::SharedTile, "k_shared_ca", 256, Slots::Block, Handle::Model, 0},
@@ -228,6 +237,7 @@ constexpr FamilyRow kFamily[] = {
     {AgentFamily::ReinforceReg, "k_train_reinforce", 4096, Slots::Block, Handle::Agent, kPolicyW},      // (handle: refused, whole batches only)
     {AgentFamily::LstdReg, "k_train_lstd", 32, Slots::LstdGroup, Handle::Agent, kLstd},
     {AgentFamily::TdAcLstdReg, "k_train_tdac_lstd", 32, Slots::LstdGroup, Handle::Agent, kPolicyW | kVCritic | kLstd},
+    {AgentFamily::GmcReg, "k_train_gmc", 4096, Slots::Block, Handle::Agent, 0},      // (handle: refused, whole trajectories only)
 };
 constexpr bool family_rows_in_order() {
     for (size_t i = 0; i < sizeof(kFamily) / sizeof(kFamily[0]); ++i) if ((size_t)kFamily[i].family != i) return false;
@@ -284,6 +294,8 @@ struct rsrl_hip_ctx {
     double* lstd_theta = nullptr;    // RecursiveLSTD / iLSTD / the iLSTD ActorCritic only: theta f64[N][F], the matrix (C / A) f64[N][F][F], iLSTD's mu f64[N][F] (learner-major)
     double* lstd_mat = nullptr;
     double* lstd_mu = nullptr;
+    float* rec_s = nullptr;          // GradientMC only: every learner's open episode, rows 0 .. ep_step[i]-1 of f32[max_episode_steps][D][N] (`from`) and
+    float* rec_r = nullptr;          //   f32[max_episode_steps][N] (the reward)
     bool q_valid = false;            // false whenever weights / states were changed from outside the driver loop
     // ---- the trait-granular fast path (kernels_trait.hpp): register-family Fourier basis, per-learner f32 weights, learner-major layout
     float* tq_key = nullptr;         // [D][N]: the state each learner's tq_q entry belongs to (allocated iff the ctx takes the fast path)
@@ -400,6 +412,11 @@ static inline ReinforceState make_reinforce(const rsrl_hip_ctx* c) {
     return rs;
 }
 
+static inline GmcState make_gmc(const rsrl_hip_ctx* c) {
+    GmcState gs;
+    gs.rec_s = c->rec_s; gs.rec_r = c->rec_r;
+    return gs;
+}
 static inline LstdState make_lstd(const rsrl_hip_ctx* c) {
     LstdState ls;
     ls.theta = c->lstd_theta; ls.mat = c->lstd_mat; ls.mu = c->lstd_mu;

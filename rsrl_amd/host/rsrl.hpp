@@ -242,6 +242,15 @@ struct TDLambda : control::td::Agent {
 };
 }}  // namespace prediction::td
 
+// ---- rsrl::prediction::mc: GradientMC { v_func, gamma }   (prediction/mc.rs:26-58)
+// Every-visit Monte-Carlo prediction through v_func's SGD rate.  Handler<&Trajectory> only: Session::handle(const Trajectory&) walks each learner's
+// trajectory last transition to first.  Drive it with policies::Random and a max_episode_steps >= 1 (the device records the open episodes).
+namespace prediction { namespace mc {
+struct GradientMC : control::td::Agent {
+    GradientMC(Shared<fa::linear::LFA> v_func, double gamma) : control::td::Agent{RSRL_GRADIENT_MC, std::move(v_func), gamma} {}
+};
+}}  // namespace prediction::mc
+
 // ---- rsrl::prediction::lstd: RecursiveLSTD::new(basis, gamma) / iLSTD::new(basis, alpha, gamma, n_updates)   (recursive_lstd.rs, ilstd.rs)
 // theta and the F x F matrix are f64 on the device (Session::lstd_state); weights() is theta rounded to f32.  Drive these with policies::Random.
 namespace prediction { namespace lstd {
@@ -320,6 +329,20 @@ public:
         std::vector<float> g((size_t)b.T * N_);
         check(rsrl_hip_handle_batch(ctx_, b.T, b.states.data(), b.actions.data(), b.rewards.data(), b.lengths.data(), g.data()));
         return g;
+    }
+    // Handler<&Trajectory>::handle of GradientMC -> the backward sum at each handled transition, [T][N] with T = the trajectory's rows of rewards
+    // (mc.rs:40-57).  Transition k's `from` is states row k (`start`, then steps[k-1].0) and its reward rewards row k; learner i has n_states[i] - 1
+    std::vector<float> handle(const domains::Trajectory& tr) {
+        const int64_t T = (int64_t)(tr.rewards.size() / (size_t)N_);
+        std::vector<uint32_t> len((size_t)N_);
+        for (int64_t i = 0; i < N_; ++i) len[(size_t)i] = tr.n_states[(size_t)i] > 0 ? tr.n_states[(size_t)i] - 1 : 0;
+        std::vector<float> g((size_t)T * N_);
+        check(rsrl_hip_handle_batch(ctx_, T, tr.states.data(), nullptr, tr.rewards.data(), len.data(), T > 0 ? g.data() : nullptr));
+        return g;
+    }
+    // policy.sample(rng, env.emit().state()): the driver loop's behaviour sample for the session's own envs (the actions become the pending ones)
+    std::vector<int32_t> sample() {
+        std::vector<int32_t> a(N_); check(rsrl_hip_policy_sample(ctx_, nullptr, N_, a.data())); return a;
     }
     // Policy::sample / Policy::mode                                               (policies/mod.rs:65-78)
     std::vector<int32_t> sample(const std::vector<float>& states) {

@@ -2,10 +2,12 @@
 """Which configurations rsrl_hip_create admits, asked of the library on a machine WITHOUT a GPU: every admission rule runs before the device
 query, so a refused configuration returns EINVAL and an admitted one EHIP ("no device").  Sweeps GRID (133 120 configurations, about 1 s) and
 GRID_AGENTS -- the algos numbered after GRID's (13-19) on the same other axes, 71 680 configurations -- and GRID_AGENTS2 (20 and 21, 20 480
-configurations), each into a fixture of its own.
-    python scripts/admission_matrix.py            writes tests/golden/create_admission.json, create_admission_agents.json and
-                                                  create_admission_agents2.json (tests/test_create_admission_cpu.py and
-                                                  tests/test_tdac_lstd_cpu.py hold the library to them)
+configurations) and GRID_AGENTS3 (22 and 23, with max_episode_steps = 200 on every configuration: GradientMC refuses the default 0), each into a
+fixture of its own.
+    python scripts/admission_matrix.py            writes tests/golden/create_admission.json, create_admission_agents.json,
+                                                  create_admission_agents2.json and create_admission_agents3.json
+                                                  (tests/test_create_admission_cpu.py, tests/test_tdac_lstd_cpu.py and tests/test_gmc_cpu.py
+                                                  hold the library to them)
     python scripts/admission_matrix.py --check    exits 1 if the library and a stored fixture disagree
 Each admitted configuration is stored as one character per axis: the index of its value in that axis, in hex."""
 import ctypes as C
@@ -19,6 +21,7 @@ sys.path.insert(0, ROOT)
 FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission.json")
 AGENTS_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_agents.json")
 AGENTS2_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_agents2.json")
+AGENTS3_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_agents3.json")
 EINVAL, EHIP = -1, -2
 
 # (config field, values): the first axis varies slowest
@@ -39,15 +42,21 @@ GRID = [
 GRID_AGENTS = [(name, list(range(13, 20)) if name == "algo" else vals) for name, vals in GRID]
 # the unassigned 20 and the iLSTD ActorCritic (21), on GRID's other axes
 GRID_AGENTS2 = [(name, [20, 21] if name == "algo" else vals) for name, vals in GRID]
-GRIDS = ((GRID, FIXTURE), (GRID_AGENTS, AGENTS_FIXTURE), (GRID_AGENTS2, AGENTS2_FIXTURE))
+# the unassigned 22 and GradientMC (23), on GRID's other axes; FIXED_AGENTS3 is set on every configuration of the grid
+GRID_AGENTS3 = [(name, [22, 23] if name == "algo" else vals) for name, vals in GRID]
+FIXED_AGENTS3 = {"max_episode_steps": 200}
+# (grid, fixture, fields set on every configuration)
+GRIDS = ((GRID, FIXTURE, {}), (GRID_AGENTS, AGENTS_FIXTURE, {}), (GRID_AGENTS2, AGENTS2_FIXTURE, {}), (GRID_AGENTS3, AGENTS3_FIXTURE, FIXED_AGENTS3))
 
 
-def sweep(grid=GRID):
-    """{index string: (return code, last error)} for every configuration of the grid."""
+def sweep(grid=GRID, fixed=None):
+    """{index string: (return code, last error)} for every configuration of the grid, the fields of `fixed` set on each."""
     from rsrl_amd import _abi
     L = _abi.lib()
     base = _abi.Config()
     assert L.rsrl_hip_config_init(C.byref(base)) == 0
+    for name, val in (fixed or {}).items():
+        setattr(base, name, val)
     out = {}
     h = C.c_void_p()
     for idx in itertools.product(*(range(len(v)) for _, v in grid)):
@@ -65,21 +74,26 @@ def admitted(results):
 
 def main():
     ok = True
-    for grid, fixture in GRIDS:
-        res = sweep(grid)
+    for grid, fixture, fixed in GRIDS:
+        res = sweep(grid, fixed)
         if any(rc == 0 for rc, _ in res.values()):
             sys.exit("a ctx was created: run this on a machine without a GPU")
         bad = sorted({rc for rc, _ in res.values()} - {EINVAL, EHIP})
         if bad:
             sys.exit(f"unexpected return codes {bad}")
         doc = {"grid": [[n, v] for n, v in grid], "admitted": admitted(res)}
+        if fixed:
+            doc["fixed"] = fixed
         if "--check" in sys.argv:
             same = json.load(open(fixture)) == doc
             print(f"{os.path.relpath(fixture, ROOT)}: " + ("fixture matches" if same else "fixture DIFFERS"))
             ok = ok and same
             continue
         with open(fixture, "w") as f:         # one admitted configuration per line, so that a diff reads
-            f.write('{"grid": %s,\n "admitted": [\n' % json.dumps(doc["grid"]))
+            f.write('{"grid": %s,\n' % json.dumps(doc["grid"]))
+            if fixed:
+                f.write(' "fixed": %s,\n' % json.dumps(fixed))
+            f.write(' "admitted": [\n')
             f.write(",\n".join(json.dumps(k) for k in doc["admitted"]))
             f.write("\n]}\n")
         print(f"{len(doc['admitted'])} of {len(res)} configurations admitted -> {os.path.relpath(fixture, ROOT)}")
