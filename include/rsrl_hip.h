@@ -195,7 +195,34 @@ typedef enum { RSRL_QLEARNING = 0, RSRL_SARSA = 1, RSRL_EXPECTED_SARSA = 2, RSRL
                 * (episode_steps = 0), and rsrl_hip_set_episode_steps refuses a value above max_episode_steps.  The statistics' sum |delta| is the
                 * sum of |sum - pred| over the sweeps, booked at the step that ended the episode.  The checkpoint holds the weights only (RSRL_TD's
                 * layout): the open record is the caller's to carry, like the states, actions and episode steps */
-               RSRL_GRADIENT_MC = 23 } rsrl_algo;
+               RSRL_GRADIENT_MC = 23,
+               /* (24 is no algo.)  The batch least-squares prediction agents (prediction/lstd), Handler<&Batch>: every transition's from, to, reward and
+                * terminal flag are read.  All arithmetic is f64, the features included (as RSRL_RECURSIVE_LSTD); every product is rounded.
+                * LSTD::new(basis, gamma) (lstd.rs:23-37): theta = 0, A = 1e-6 I, b = 0.  handle (lstd.rs:59-81) walks the batch FIRST TO LAST:
+                *   b += r phi(s);   non-terminal: pd = gamma phi(s') - phi(s), A -= phi(s) (x) pd;   terminal: A += phi(s) (x) phi(s);   then solve().
+                * LSTDLambda::new(basis, gamma, lambda) (lstd_lambda.rs:25-41): the same start and z = 0.  handle (lstd_lambda.rs:66-103) walks the batch
+                * LAST TO FIRST (`batch.iter().rev()`: the trace runs backwards in time); z survives from batch to batch, only a terminal transition zeroes it:
+                *   c = lambda gamma;  z = c z + phi(s);  b += r z;   non-terminal: pd = phi(s) - gamma phi(s'), A += z (x) pd;
+                *   terminal: A += z (x) phi(s), z = 0;   then solve().
+                * solve() (lstd.rs:40-50, lstd_lambda.rs:44-54) is theta <- A.solve(b) by LAPACK, with an SVD pseudo-inverse when LAPACK reports an exactly
+                * zero pivot.  Here it is ONE fixed operation order (kernels_lstd_batch.hpp; tests/lstd_batch_numpy.py restates it, bit for bit): Gaussian
+                * elimination with partial pivoting on a copy of A and b -- the pivot of column k is the first row in index order, among the rows not yet
+                * used, with the largest |a[i][k]| -- and back substitution with ascending j.  DEPARTURE: there is NO SVD fallback.  A solve whose pivot
+                * candidates hold no value above 0 is abandoned: theta keeps its value (what the reference does when both attempts fail) and the learner's
+                * singular_solves counter (u32) goes up by one.
+                * The driver loop is RSRL_GRADIENT_MC's on the f64 state: the transition's (from, reward) is appended to the learner's open episode (row
+                * k's `to` is row k+1's `from`; the last row's `to` and terminal flag are the step's own), at the episode's end (terminal or
+                * max_episode_steps) the batch is handled and solved, then the restart and the Random sample; the environment side is RSRL_TD's draw for
+                * draw.  config: gamma, lambda (RSRL_LSTD_LAMBDA); max_episode_steps >= 1 (EINVAL for 0).  Supported: as RSRL_GRADIENT_MC; everything else
+                * is EINVAL at create.  The value side is V, as RSRL_RECURSIVE_LSTD (n_outputs 1; q_evaluate writes f32(phi . theta); get / set_weights carry
+                * theta as f32[F][1]).  rsrl_hip_handle and rsrl_hip_handle_batch are ESTATE: rsrl_hip_handle_transitions.  rsrl_hip_lstd_solve is the
+                * public solve(); rsrl_hip_get/set_lstd_batch_state carry the exact state (rsrl_hip_get/set_lstd_state is ESTATE);
+                * rsrl_hip_get/set_episode_record, set_episode_steps, reset and domain_reset behave as for RSRL_GRADIENT_MC (a reset leaves the agent's
+                * state alone).  td_out and the statistics' sum |delta| are the diagnostic r + gamma V(s') - V(s) (terminal: r - V(s)) with theta as it
+                * stood before the batch's solve, booked at the step that ended the episode: the agents compute no TD error.  The checkpoint is aux_kind 10;
+                * the open record is the caller's to carry.  Not built: LambdaLSPE (its solve() zeroes A and b, so every batch shorter than F is a
+                * rank-deficient system that only the SVD fallback answers) */
+               RSRL_LSTD = 25, RSRL_LSTD_LAMBDA = 26 } rsrl_algo;
 /* rsrl::traces::{Accumulate, Saturate (Trace::replacing), Dutch}      traces.rs:188-240 */
 typedef enum { RSRL_TRACE_ACCUMULATE = 0, RSRL_TRACE_SATURATE = 1, RSRL_TRACE_DUTCH = 2 } rsrl_trace;
 /* rsrl::policies::{Greedy, EpsilonGreedy, Softmax, Random}
@@ -358,8 +385,8 @@ int rsrl_hip_set_actions(rsrl_hip_ctx* ctx, const int32_t* actions /*[N]*/);
  *     launch continues from it.  EINVAL for a ctx whose kernels carry nothing. */
 int rsrl_hip_get_episode_steps(rsrl_hip_ctx* ctx, uint32_t* steps /*[N]*/);
 int rsrl_hip_set_episode_steps(rsrl_hip_ctx* ctx, const uint32_t* steps /*[N]*/);
-/* (RSRL_GRADIENT_MC: set_episode_steps refuses a value above max_episode_steps with EINVAL and changes nothing -- the kernel indexes the record by it.)
- * RSRL_GRADIENT_MC's open episodes, cap = max_episode_steps rows: learner i's record is rows 0 .. episode_steps[i]-1 of its column, row k holding
+/* (RSRL_GRADIENT_MC, RSRL_LSTD, RSRL_LSTD_LAMBDA: set_episode_steps refuses a value above max_episode_steps with EINVAL and changes nothing -- the kernel indexes the record by it.)
+ * RSRL_GRADIENT_MC's (and RSRL_LSTD's, RSRL_LSTD_LAMBDA's) open episodes, cap = max_episode_steps rows: learner i's record is rows 0 .. episode_steps[i]-1 of its column, row k holding
  * transition k's `from` state and reward.  get writes NaN in the rows past that; set installs both arrays whole (what lies past a learner's
  * episode_steps is never read).  Host or device arrays.  ESTATE on every other agent */
 int rsrl_hip_get_episode_record(rsrl_hip_ctx* ctx, float* states /*[cap][D][N]*/, float* rewards /*[cap][N]*/);
@@ -433,6 +460,17 @@ int rsrl_hip_handle(rsrl_hip_ctx* ctx, const float* from_states, const int32_t* 
  * ESTATE on every other agent. */
 int rsrl_hip_handle_batch(rsrl_hip_ctx* ctx, int64_t T, const float* states /*[T][D][N]*/, const int32_t* actions /*[T][N]*/,
                           const float* rewards /*[T][N]*/, const uint32_t* lengths /*[N]*/, float* returns_out /*[T][N], optional*/);
+/* RSRL_LSTD / RSRL_LSTD_LAMBDA: Handler<&Batch>::handle for every learner, on whole transitions.  Learner i's batch is rows 0 .. lengths[i]-1 of its
+ * column; any row may be terminal; LSTD walks the rows first to last, LSTDLambda last to first, and both end in solve().  lengths[i] = 0 means no
+ * call: the learner keeps its bytes and no solve runs.  actions are not read.  td_out receives the diagnostic r + gamma V(s') - V(s) (terminal:
+ * r - V(s)) with theta as it stood before the solve at each handled row, NaN past a learner's length.  The ctx's own open record is not touched.
+ * The conventions are rsrl_hip_handle_batch's: host or device arrays (host lengths validated, device ones clamped), one call is one batch-step, and
+ *     domain_step -> (append the transition) -> handle_transitions(lengths = episode length of the learners whose episode just ended, else 0)
+ *     -> domain_reset(ended) -> policy_sample(NULL)
+ * runs on the driver loop's draws and leaves its bits.  ESTATE on every other agent; rsrl_hip_handle and rsrl_hip_handle_batch are ESTATE on these */
+int rsrl_hip_handle_transitions(rsrl_hip_ctx* ctx, int64_t T, const float* from_states /*[T][D][N]*/, const int32_t* actions /*[T][N], may be NULL, ignored*/,
+                                const float* rewards /*[T][N]*/, const float* to_states /*[T][D][N]*/, const uint8_t* terminal /*[T][N]*/,
+                                const uint32_t* lengths /*[N]*/, float* td_out /*[T][N], optional*/);
 
 /* Policy::sample / Policy::mode / Function<(S,)> of the policy (action probabilities)
  *   policies/mod.rs:65-78; greedy.rs:30-44,77-83; epsilon_greedy.rs:38-45,74-82;
@@ -483,6 +521,15 @@ int rsrl_hip_set_return_carry(rsrl_hip_ctx* ctx, const float* g /*[N]*/);
 int rsrl_hip_get_lstd_state(rsrl_hip_ctx* ctx, int64_t env_index, double* theta /*[F]*/, double* mat /*[F][F]*/, double* mu /*[F], iLSTD only, may be NULL*/);
 int rsrl_hip_set_lstd_state(rsrl_hip_ctx* ctx, int64_t env_index, const double* theta /*[F]*/, const double* mat /*[F][F]*/,
                             const double* mu /*[F], iLSTD only, may be NULL*/);
+/* LSTD / LSTDLambda: the exact f64 state of one learner -- theta, A (row-major), b, LSTDLambda's z (may be NULL: not read or written; ignored by
+ * LSTD) -- and its count of abandoned solves.  Host or device arrays.  ESTATE on every other agent */
+int rsrl_hip_get_lstd_batch_state(rsrl_hip_ctx* ctx, int64_t env_index, double* theta /*[F]*/, double* A /*[F][F]*/, double* b /*[F]*/,
+                                  double* z /*[F], LSTDLambda only, may be NULL*/, uint32_t* singular_solves);
+int rsrl_hip_set_lstd_batch_state(rsrl_hip_ctx* ctx, int64_t env_index, const double* theta /*[F]*/, const double* A /*[F][F]*/, const double* b /*[F]*/,
+                                  const double* z /*[F], LSTDLambda only, may be NULL*/, const uint32_t* singular_solves);
+/* LSTD / LSTDLambda: the agents' public solve() (lstd.rs:40, lstd_lambda.rs:44) for every learner: theta <- A.solve(b) in the library's fixed
+ * operation order; A, b and z are not written.  An abandoned solve keeps theta and counts in singular_solves.  ESTATE on every other agent */
+int rsrl_hip_lstd_solve(rsrl_hip_ctx* ctx);
 /* Checkpoint of the approximator(s) (the reference's only persistence story is the optional serde
  * derive on the agents, rsrl/Cargo.toml:26).  The file version follows from the header's aux_kind:
  *   aux_kind                                        written as   payload after the header
@@ -496,6 +543,7 @@ int rsrl_hip_set_lstd_state(rsrl_hip_ctx* ctx, int64_t env_index, const double* 
  *   7 REINFORCE's theta and open episode             9           weights (BaselineREINFORCE only), auxiliary matrix, theta_b, g
  *   8 the LSTD agents' f64 state                     10          f64 theta, matrices, mu
  *   9 the iLSTD ActorCritic's f64 state and theta    10          f64 theta, matrices, mu, auxiliary matrix
+ *   10 LSTD / LSTDLambda's f64 state                 10          f64 theta, A, b, z (LSTDLambda), u32 singular_solves
  * and a ctx with config.epsilon_decay (aux_kind 0 or 1) writes version 4 instead, with f32 eps[N] behind the payload.  No other pairing of
  * version and aux_kind is a file of this library; load refuses it.  Little-endian, serialised field by field (no padding):
  *   offset  0  char magic[8] = "RSRLHIPW"
@@ -504,7 +552,7 @@ int rsrl_hip_set_lstd_state(rsrl_hip_ctx* ctx, int64_t env_index, const double* 
  *                   algo, weight_dtype, aux_kind (0 none, 1 eligibility traces, 2 GreedyGQ's fa_td weights,
  *                   3 QSigma's n-step backups, 4 sparse traces over a shared table, 5 ActorCritic's theta,
  *                   6 the TD ActorCritic's theta, 7 REINFORCE's theta and open episode, 8 the LSTD agents' f64 state,
- *                   9 the iLSTD ActorCritic's f64 state and theta)
+ *                   9 the iLSTD ActorCritic's f64 state and theta, 10 LSTD / LSTDLambda's f64 state)
  *                                                                                                                 [11 x i32]
  *          56  i64  n_learners (1 in shared mode)
  *          64  u64  step_count
@@ -522,6 +570,9 @@ int rsrl_hip_set_lstd_state(rsrl_hip_ctx* ctx, int64_t env_index, const double* 
  *              iLSTD, n_learners x f64[F] of mu;
  *              if aux_kind is 9 (file version 10 too; RSRL_ILSTD_ACTOR_CRITIC): aux_kind 8's sections of its iLSTD critic (mu included), then
  *              n_learners x f32[F][n_actions] of the actor's theta;
+ *              if aux_kind is 10 (file version 10 too; RSRL_LSTD / RSRL_LSTD_LAMBDA): the weights section is ABSENT;
+ *              then n_learners x f64[F] of theta, n_learners x f64[F][F] of A (row-major), n_learners x f64[F] of b, for LSTDLambda
+ *              n_learners x f64[F] of z, then u32 singular_solves[N].  The open episodes are not in the file (as RSRL_GRADIENT_MC's);
  *              if aux_kind is 3 (file version 3): u32 head[N], u32 len[N], f32 entries[D + 5][n_steps][N] -- every learner's
  *              Backup ring {s, a, q, residual, pi, mu} (q_sigma.rs:30-63), so that a QSigma run with n_steps > 1 resumes
  *              bit-identically too.  A QSigma ctx still reads its configuration's version-2 file without them (aux_kind 0): the backups start empty.

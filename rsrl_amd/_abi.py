@@ -93,6 +93,10 @@ SYMBOLS = {
     "rsrl_hip_get_lstd_state": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rsrl_hip_set_lstd_state": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rsrl_hip_handle_batch": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rsrl_hip_handle_transitions": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 7),
+    "rsrl_hip_lstd_solve": (C.c_int, [C.c_void_p]),
+    "rsrl_hip_get_lstd_batch_state": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 5),
+    "rsrl_hip_set_lstd_batch_state": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 5),
     "rsrl_hip_train": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Stats)]),
     "rsrl_hip_step_count": (C.c_uint64, [C.c_void_p]),
     "rsrl_hip_pending_steps": (C.c_int64, [C.c_void_p]),

@@ -15,6 +15,7 @@ REINFORCE, BASELINE_REINFORCE = 15, 16         # (14 is no algo) control/mc: REI
 RECURSIVE_LSTD, ILSTD = 18, 19                  # (17 is no algo) prediction/lstd: RecursiveLSTD, iLSTD (f64 theta and F x F matrix: get/set_lstd_state)
 ILSTD_ACTOR_CRITIC = 21                        # (20 is no algo) ActorCritic::tdac over iLSTD, tdac.rs's agent: lr = iLSTD's alpha, n_steps = its n_updates, alpha = the actor's
 GRADIENT_MC = 23                               # (22 is no algo) prediction/mc.rs: GradientMC (Handler<&Trajectory>: handle_batch; episode_record)
+LSTD, LSTD_LAMBDA = 25, 26                      # (24 is no algo) prediction/lstd: LSTD, LSTDLambda (Handler<&Batch> on whole transitions: handle_transitions; lstd_solve; get/set_lstd_batch_state)
 TRACE_ACCUMULATE, TRACE_SATURATE, TRACE_DUTCH = 0, 1, 2
 GREEDY, EPSILON_GREEDY, SOFTMAX, RANDOM = 0, 1, 2, 3
 W_PER_ENV, W_SHARED = 0, 1
@@ -193,7 +194,7 @@ class Context:
 
     @property
     def episode_record(self):
-        """GRADIENT_MC's open episodes -> (states (cap, D, N), rewards (cap, N)), cap = max_episode_steps: learner i's record is rows
+        """GRADIENT_MC's (LSTD's, LSTD_LAMBDA's) open episodes -> (states (cap, D, N), rewards (cap, N)), cap = max_episode_steps: learner i's record is rows
         0 .. episode_steps[i]-1 of its column (row k: transition k's `from` and reward), NaN past that; RsrlHipError on the other agents"""
         cap = int(self.cfg.max_episode_steps)
         s, r = np.empty((cap, self.D, self.N), dtype=np.float32), np.empty((cap, self.N), dtype=np.float32)
@@ -285,6 +286,18 @@ class Context:
                                            _p(_in(rewards, np.float32, (M,))), _p(to_states),
                                            _p(_in(terminal, np.uint8, (M,))), M, _p(td)))
         return td
+
+    def handle_transitions(self, from_states, rewards, to_states, terminal, lengths, td=False, actions=None, T=None):
+        """Handler<&Batch>::handle of LSTD / LSTD_LAMBDA for every learner: from_states / to_states (T, D, N), rewards (T, N), terminal (T, N) uint8,
+        lengths (N,) -- learner i's batch is rows 0 .. lengths[i]-1 of its column (0: no call, the learner keeps its bytes); actions are not read.
+        td=True: also the diagnostic r + gamma V(s') - V(s) at each handled row, (T, N) (NaN where nothing was handled).  One batch-step.  Arrays
+        may be raw device pointers (int): then T is given, and `td` may be the device pointer the diagnostic is written to"""
+        T = int(np.shape(rewards)[0]) if T is None else int(T)
+        out = td if isinstance(td, int) and not isinstance(td, bool) else (np.full((T, self.N), np.nan, dtype=np.float32) if td else None)
+        _abi.check(self._L.rsrl_hip_handle_transitions(self._h, T, _p(_in(from_states, np.float32, (T, self.D, self.N))), _p(_in(actions, np.int32, (T, self.N))),
+                                                       _p(_in(rewards, np.float32, (T, self.N))), _p(_in(to_states, np.float32, (T, self.D, self.N))),
+                                                       _p(_in(terminal, np.uint8, (T, self.N))), _p(_in(lengths, np.uint32, (self.N,))), _p(out)))
+        return out
 
     def handle_batch(self, states, actions=None, rewards=None, lengths=None, returns=False, T=None):
         """Handler<&Batch>::handle of REINFORCE / BASELINE_REINFORCE for every learner: states (T, D, N), actions / rewards (T, N), lengths (N,) --
@@ -404,6 +417,25 @@ class Context:
         mu = np.empty(self.F, dtype=np.float64) if self.cfg.algo in (ILSTD, ILSTD_ACTOR_CRITIC) else None
         _abi.check(self._L.rsrl_hip_get_lstd_state(self._h, int(env_index), _p(theta), _p(mat), _p(mu)))
         return theta, mat, mu
+
+    def get_lstd_batch_state(self, env_index=0):
+        """LSTD / LSTDLambda: one learner's exact f64 state -> (theta (F,), A (F, F), b (F,), z (F,) for LSTDLambda else None, singular_solves)"""
+        theta, A, b = np.empty(self.F, dtype=np.float64), np.empty((self.F, self.F), dtype=np.float64), np.empty(self.F, dtype=np.float64)
+        z = np.empty(self.F, dtype=np.float64) if self.cfg.algo == LSTD_LAMBDA else None
+        sing = np.zeros(1, dtype=np.uint32)
+        _abi.check(self._L.rsrl_hip_get_lstd_batch_state(self._h, int(env_index), _p(theta), _p(A), _p(b), _p(z), _p(sing)))
+        return theta, A, b, z, int(sing[0])
+
+    def set_lstd_batch_state(self, theta, A, b, z=None, singular_solves=0, env_index=0):
+        """LSTD / LSTDLambda: install one learner's f64 state exactly (z: LSTDLambda only; None leaves it as it is)"""
+        sing = np.array([singular_solves], dtype=np.uint32)
+        _abi.check(self._L.rsrl_hip_set_lstd_batch_state(self._h, int(env_index), _p(_in(theta, np.float64, (self.F,))), _p(_in(A, np.float64, (self.F, self.F))),
+                                                         _p(_in(b, np.float64, (self.F,))), _p(None if z is None else _in(z, np.float64, (self.F,))), _p(sing)))
+
+    def lstd_solve(self):
+        """LSTD / LSTDLambda: the agents' public solve() for every learner -- theta <- A.solve(b) in the library's fixed operation order; an abandoned
+        solve (no pivot above 0) keeps theta and counts in singular_solves"""
+        _abi.check(self._L.rsrl_hip_lstd_solve(self._h))
 
     def set_lstd_state(self, theta, mat, mu=None, env_index=0):
         """RecursiveLSTD / iLSTD: install one learner's f64 state exactly (mu: iLSTD only; None leaves it as it is)"""

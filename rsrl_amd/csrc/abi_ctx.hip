@@ -46,6 +46,7 @@ static AgentFamily classify(const rsrl_hip_config& cfg, size_t w_elems) {
     if (is_lstd(al)) return F::LstdReg;
     if (is_tdac_lstd(al)) return F::TdAcLstdReg;
     if (is_gmc(al)) return F::GmcReg;
+    if (is_lstd_batch(al)) return F::LstdBatchReg;
     if (cfg.weight_mode == RSRL_W_SHARED) return fourier ? F::SharedDense : (is_sparse_lambda(cfg) ? F::SharedSparseLambda : F::SharedTile);
     if (wave && is_wave_aux_algo(al)) return F::WaveAux;
     if (is_pred(al)) return tile ? F::TdTile : (reg ? F::TdReg : F::TdGeneric);
@@ -142,7 +143,7 @@ int rsrl_hip_destroy(rsrl_hip_ctx* c) {
 }
 
 // The agents that exist only on the register-family Fourier orders with per-learner f32 weights (train_ac.hip, train_tdac.hip, train_reinforce.hip,
-// train_lstd.hip, train_tdac_lstd.hip, train_gmc.hip): the policy is the agent's own -- the Gibbs actor / policy, or the prediction agents' Random behaviour -- and the
+// train_lstd.hip, train_tdac_lstd.hip, train_gmc.hip, train_lstd_batch.hip): the policy is the agent's own -- the Gibbs actor / policy, or the prediction agents' Random behaviour -- and the
 // critic shares it; iLSTD's n_updates travel as config.n_steps.  `storage`: register-family order, per-learner f32 weights, no epsilon schedule
 static int check_reg_only(const rsrl_hip_config& cfg, const AlgoRow& a, bool storage) {
     if (!storage || cfg.policy != a.reg_policy || cfg.agent_policy != -1)
@@ -153,8 +154,8 @@ static int check_reg_only(const rsrl_hip_config& cfg, const AlgoRow& a, bool sto
                     cfg.domain, cfg.basis, cfg.order, cfg.weight_mode, cfg.weight_dtype, cfg.policy, cfg.agent_policy, cfg.epsilon_decay);
     if (a.n_updates && (cfg.n_steps < 1 || cfg.n_steps > 32))
         return fail(RSRL_HIP_EINVAL, "%s: n_steps (%sn_updates, the rounds of solve() per transition) must be in [1, 32], got %d", a.name, a.n_updates, cfg.n_steps);
-    // GradientMC keeps every learner's open episode on the device, max_episode_steps rows of it
-    if (a.agent == Agent::Gmc && cfg.max_episode_steps < 1)
+    // GradientMC, LSTD and LSTDLambda keep every learner's open episode on the device, max_episode_steps rows of it
+    if ((a.agent == Agent::Gmc || a.agent == Agent::LstdBatch) && cfg.max_episode_steps < 1)
         return fail(RSRL_HIP_EINVAL, "%s: max_episode_steps must be >= 1 -- the device records every learner's open episode, and an unbounded episode "
                                      "(max_episode_steps = 0) has no record size", a.name);
     return RSRL_HIP_OK;
@@ -172,7 +173,7 @@ static int check_config(const rsrl_hip_config& cfg) {
     const int D = kDomainShape[cfg.domain][0], A = kDomainShape[cfg.domain][1];
     if (cfg.n_envs < 1) return fail(RSRL_HIP_EINVAL, "n_envs must be >= 1");
     if (cfg.n_envs + cfg.env_offset > (int64_t)0xffffffffLL || cfg.env_offset < 0) return fail(RSRL_HIP_EINVAL, "global env ids must fit 32 bits");
-    if (cfg.algo < 0 || cfg.algo > RSRL_GRADIENT_MC || !kAlgo[cfg.algo].name) return fail(RSRL_HIP_EINVAL, "unknown algo %d", cfg.algo);
+    if (cfg.algo < 0 || cfg.algo > RSRL_LSTD_LAMBDA || !kAlgo[cfg.algo].name) return fail(RSRL_HIP_EINVAL, "unknown algo %d", cfg.algo);
     if (cfg.policy < 0 || cfg.policy > RSRL_RANDOM) return fail(RSRL_HIP_EINVAL, "unknown policy %d", cfg.policy);
     // Softmax::new panics for |tau| < 1e-7 (policies/softmax.rs:63-66)
     if (cfg.policy == RSRL_SOFTMAX && std::fabs(cfg.tau) < 1e-7) return fail(RSRL_HIP_EINVAL, "Tau parameter in Softmax must be non-zero.");
@@ -344,14 +345,18 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
         const size_t nv = (size_t)c->F * (size_t)N, nm = nv * (size_t)c->F;
         TRY(ctx_alloc(c, &c->lstd_theta, sizeof(double) * nv, true));
         TRY(ctx_alloc(c, &c->lstd_mat, sizeof(double) * nm));
-        launch_lstd_fill_eye(c->stream, c->lstd_mat, (int64_t)nm, c->F, cfg->algo == RSRL_RECURSIVE_LSTD ? 1e-5 : 1.0);
+        // LSTD / LSTDLambda: A = 1e-6 I, b = 0 (in lstd_mu's place), z = 0, no abandoned solve (lstd.rs:23-37, lstd_lambda.rs:25-41)
+        const bool batch = is_lstd_batch(cfg->algo);
+        launch_lstd_fill_eye(c->stream, c->lstd_mat, (int64_t)nm, c->F, batch ? 1e-6 : (cfg->algo == RSRL_RECURSIVE_LSTD ? 1e-5 : 1.0));
         KCHECK();
         if (cfg->algo != RSRL_RECURSIVE_LSTD) TRY(ctx_alloc(c, &c->lstd_mu, sizeof(double) * nv, true));
+        if (cfg->algo == RSRL_LSTD_LAMBDA) TRY(ctx_alloc(c, &c->lstd_z, sizeof(double) * nv, true));
+        if (batch) TRY(ctx_alloc(c, &c->lstd_sing, sizeof(uint32_t) * (size_t)N, true));
     }
-    if (is_gmc(cfg->algo)) {
+    if (keeps_record(cfg->algo)) {
         // the open episodes (empty: ep_step = 0 below).  Not zero-filled: nothing at or past a learner's ep_step is ever read (get_episode_record shows NaN)
         const uint64_t rows = (uint64_t)cfg->max_episode_steps * (uint64_t)N;      // (<= 2^64 - 2^33: both factors fit 32 bits)
-        if (rows > (uint64_t)1 << 40) return fail(RSRL_HIP_ENOMEM, "GradientMC's episode record: max_episode_steps * n_envs = %llu rows do not fit any device",
+        if (rows > (uint64_t)1 << 40) return fail(RSRL_HIP_ENOMEM, "the episode record: max_episode_steps * n_envs = %llu rows do not fit any device",
                                                   (unsigned long long)rows);
         TRY(ctx_alloc(c, &c->rec_s, (size_t)(rows * (uint64_t)c->D * sizeof(float))));
         TRY(ctx_alloc(c, &c->rec_r, (size_t)(rows * sizeof(float))));
@@ -590,15 +595,15 @@ int rsrl_hip_get_episode_steps(rsrl_hip_ctx* c, uint32_t* steps) {
 int rsrl_hip_set_episode_steps(rsrl_hip_ctx* c, const uint32_t* steps) {
     CHECK_CTX(c); FLUSH(c); if (!steps) return fail(RSRL_HIP_EINVAL, "null argument");
     HIP_TRY(hipSetDevice(c->cfg.device));
-    if (c->family == AgentFamily::GmcReg) {
-        // k_train_gmc indexes the learner's record by it: checked before anything is installed (a device array through a host copy)
+    if (keeps_record(c->cfg.algo)) {
+        // k_train_gmc / k_train_lstd_batch index the learner's record by it: checked before anything is installed (a device array through a host copy)
         const size_t n = (size_t)c->cfg.n_envs;
         std::vector<uint32_t> h(n);
         HIP_TRY(hipMemcpyAsync(h.data(), steps, sizeof(uint32_t) * n, hipMemcpyDefault, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         for (size_t i = 0; i < n; ++i)
             if (h[i] > c->cfg.max_episode_steps)
-                return fail(RSRL_HIP_EINVAL, "episode_steps[%zu] = %u is more than max_episode_steps = %u, the rows of GradientMC's episode record", i, h[i],
+                return fail(RSRL_HIP_EINVAL, "episode_steps[%zu] = %u is more than max_episode_steps = %u, the rows of the episode record", i, h[i],
                             c->cfg.max_episode_steps);
     }
     HIP_TRY(hipMemcpyAsync(c->ep_step, steps, sizeof(uint32_t) * (size_t)c->cfg.n_envs, hipMemcpyDefault, c->stream));
@@ -606,10 +611,10 @@ int rsrl_hip_set_episode_steps(rsrl_hip_ctx* c, const uint32_t* steps) {
     return RSRL_HIP_OK;
 }
 // GradientMC's open episodes (rec_s / rec_r): read with NaN past each learner's episode_steps, installed whole
-static const char* const kNoEpisodeRecord = "only GradientMC (RSRL_GRADIENT_MC) keeps the learners' open episodes on the device";
+static const char* const kNoEpisodeRecord = "only GradientMC, LSTD and LSTDLambda (RSRL_GRADIENT_MC, RSRL_LSTD, RSRL_LSTD_LAMBDA) keep the learners' open episodes on the device";
 int rsrl_hip_get_episode_record(rsrl_hip_ctx* c, float* states, float* rewards) {
     CHECK_CTX(c); FLUSH(c); if (!states || !rewards) return fail(RSRL_HIP_EINVAL, "null argument");
-    if (c->family != AgentFamily::GmcReg) return fail(RSRL_HIP_ESTATE, "%s", kNoEpisodeRecord);
+    if (!keeps_record(c->cfg.algo)) return fail(RSRL_HIP_ESTATE, "%s", kNoEpisodeRecord);
     HIP_TRY(hipSetDevice(c->cfg.device));
     const int64_t N = c->cfg.n_envs, cap = (int64_t)c->cfg.max_episode_steps;
     OutBuf<float> os, orw;
@@ -624,7 +629,7 @@ int rsrl_hip_get_episode_record(rsrl_hip_ctx* c, float* states, float* rewards) 
 }
 int rsrl_hip_set_episode_record(rsrl_hip_ctx* c, const float* states, const float* rewards) {
     CHECK_CTX(c); FLUSH(c); if (!states || !rewards) return fail(RSRL_HIP_EINVAL, "null argument");
-    if (c->family != AgentFamily::GmcReg) return fail(RSRL_HIP_ESTATE, "%s", kNoEpisodeRecord);
+    if (!keeps_record(c->cfg.algo)) return fail(RSRL_HIP_ESTATE, "%s", kNoEpisodeRecord);
     HIP_TRY(hipSetDevice(c->cfg.device));
     const size_t rows = (size_t)c->cfg.max_episode_steps * (size_t)c->cfg.n_envs;
     HIP_TRY(hipMemcpyAsync(c->rec_s, states, sizeof(float) * rows * (size_t)c->D, hipMemcpyDefault, c->stream));

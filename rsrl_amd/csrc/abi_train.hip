@@ -423,6 +423,9 @@ int launch_agent(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, uint64_t 
     case AgentFamily::GmcReg:            // (io: rsrl_hip_handle refuses the agent before it gets here; rsrl_hip_handle_batch launches its own)
         ok = !io && launch_gmc(cf.domain, cf.order, grid, block, c->stream, k, make_gmc(c), t, chunk, d_stats, nullptr);
         break;
+    case AgentFamily::LstdBatchReg:      // (io: rsrl_hip_handle refuses the agents before it gets here; rsrl_hip_handle_transitions launches its own)
+        ok = !io && launch_lstd_batch(cf.domain, cf.order, cf.algo == RSRL_LSTD_LAMBDA, c->stream, k, make_lstd_batch(c), t, chunk, d_stats, nullptr);
+        break;
     default: ok = false; break;      // (the shared-W families: enqueue_shared_step)
     }
     if (!ok) return NO_MODEL(c);

@@ -208,8 +208,8 @@ static int sample_emit(rsrl_hip_ctx* c, int64_t M, int32_t* actions_out) {
     if (M != c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "policy_sample(states = NULL) samples for the ctx's own envs: M must be n_envs (%lld), got %lld", (long long)c->cfg.n_envs, (long long)M);
     if (is_pred(c->cfg.algo)) return fail(RSRL_HIP_ESTATE, "a prediction agent has a state-value function only (use rsrl_hip_q_evaluate for V(s))");
     const bool dev_out = is_device_ptr(actions_out);
-    if (c->family == AgentFamily::LstdReg || c->family == AgentFamily::GmcReg) {
-        // RecursiveLSTD / iLSTD / GradientMC: the driver loop's Random sample (what rsrl_hip_train draws at batch-step step_count - 1; the initial sample's stream
+    if (c->family == AgentFamily::LstdReg || c->family == AgentFamily::GmcReg || c->family == AgentFamily::LstdBatchReg) {
+        // RecursiveLSTD / iLSTD / GradientMC / LSTD / LSTDLambda: the driver loop's Random sample (what rsrl_hip_train draws at batch-step step_count - 1; the initial sample's stream
         // before the first handle), so that the trait-granular loop runs on the driver loop's draws
         FLUSH(c);
         HIP_TRY(hipSetDevice(c->cfg.device));
@@ -319,6 +319,8 @@ int rsrl_hip_handle(rsrl_hip_ctx* c, const float* from_states, const int32_t* ac
         return fail(RSRL_HIP_ESTATE, "REINFORCE and BaselineREINFORCE handle whole batches only (Handler<&Batch>): use rsrl_hip_handle_batch");
     if (c->family == AgentFamily::GmcReg)
         return fail(RSRL_HIP_ESTATE, "GradientMC handles whole trajectories only (Handler<&Trajectory>, visited last to first): use rsrl_hip_handle_batch");
+    if (c->family == AgentFamily::LstdBatchReg)
+        return fail(RSRL_HIP_ESTATE, "LSTD and LSTDLambda handle whole batches only (Handler<&Batch>, then solve()): use rsrl_hip_handle_transitions");
     // the transition rsrl_hip_domain_step has just been handed (same arrays, every learner): accepted, launched with it (rsrl_hip_domain_step)
     if (c->tp.stage == 1 && from_states == c->tp.from && actions == c->tp.act && rewards == c->tp.rew && to_states == c->tp.to && terminal == c->tp.term &&
         M == c->cfg.n_envs && (!td_error_out || is_device_ptr(td_error_out))) {
@@ -424,8 +426,9 @@ int rsrl_hip_handle_batch(rsrl_hip_ctx* c, int64_t T, const float* states, const
     CHECK_CTX(c);
     const bool gmc = c->family == AgentFamily::GmcReg;      // Handler<&Trajectory>: reads no actions
     if (c->family != AgentFamily::ReinforceReg && !gmc)
-        return fail(RSRL_HIP_ESTATE, "only REINFORCE, BaselineREINFORCE (Handler<&Batch>) and GradientMC (Handler<&Trajectory>) handle whole batches; the other "
-                                     "agents handle transitions (rsrl_hip_handle)");
+        return fail(RSRL_HIP_ESTATE, "only REINFORCE, BaselineREINFORCE (Handler<&Batch>) and GradientMC (Handler<&Trajectory>) handle batches of (state, action, "
+                                     "reward) rows; LSTD and LSTDLambda read whole transitions (rsrl_hip_handle_transitions), the other agents handle "
+                                     "transitions one at a time (rsrl_hip_handle)");
     if (T < 0) return fail(RSRL_HIP_EINVAL, "bad batch length T = %lld", (long long)T);
     if (gmc) actions = nullptr;
     if (!lengths || (T > 0 && (!states || (!actions && !gmc) || !rewards))) return fail(RSRL_HIP_EINVAL, "null argument");
@@ -466,6 +469,60 @@ int rsrl_hip_handle_batch(rsrl_hip_ctx* c, int64_t T, const float* states, const
     bool sync = !all_device;
     TRY(flush_out(c, &oret, &sync));
     if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
+    return RSRL_HIP_OK;
+}
+
+// Handler<&Batch>::handle of LSTD / LSTDLambda for every learner (kernels_lstd_batch.hpp): whole transitions, then solve()
+int rsrl_hip_handle_transitions(rsrl_hip_ctx* c, int64_t T, const float* from_states, const int32_t* actions, const float* rewards, const float* to_states,
+                                const uint8_t* terminal, const uint32_t* lengths, float* td_out) {
+    CHECK_CTX(c);
+    (void)actions;      // (neither agent reads them)
+    if (c->family != AgentFamily::LstdBatchReg)
+        return fail(RSRL_HIP_ESTATE, "only LSTD and LSTDLambda handle batches of whole transitions (Handler<&Batch> reading from, to, reward and the terminal "
+                                     "flag); see rsrl_hip_handle and rsrl_hip_handle_batch for the other agents");
+    if (T < 0) return fail(RSRL_HIP_EINVAL, "bad batch length T = %lld", (long long)T);
+    if (!lengths || (T > 0 && (!from_states || !rewards || !to_states || !terminal))) return fail(RSRL_HIP_EINVAL, "null argument");
+    FLUSH(c);
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    const int64_t N = c->cfg.n_envs;
+    const bool host_len = !is_device_ptr(lengths);      // host lengths are validated; device ones are clamped by the kernel
+    if (host_len)
+        for (int64_t i = 0; i < N; ++i)
+            if ((int64_t)lengths[i] > T) return fail(RSRL_HIP_EINVAL, "lengths[%lld] = %u is more than the batch's %lld rows", (long long)i, lengths[i], (long long)T);
+    const bool all_device = !host_len && (T == 0 || (is_device_ptr(from_states) && is_device_ptr(rewards) && is_device_ptr(to_states) && is_device_ptr(terminal))) &&
+                            (!td_out || is_device_ptr(td_out));
+    TransitionBatch io;
+    const size_t TN = (size_t)T * (size_t)N;
+    TRY(stage_in(c, 0, T > 0 ? from_states : nullptr, TN * (size_t)c->D, &io.from));
+    TRY(stage_in(c, 1, T > 0 ? rewards : nullptr, TN, &io.rew));
+    TRY(stage_in(c, 2, T > 0 ? to_states : nullptr, TN * (size_t)c->D, &io.to));
+    TRY(stage_in(c, 3, T > 0 ? terminal : nullptr, TN, &io.term));
+    TRY(stage_in(c, 4, lengths, (size_t)N, &io.len));
+    OutBuf<float> otd;
+    TRY(stage_out(c, 5, T > 0 ? td_out : nullptr, TN, &otd));
+    io.T = T; io.td_out = otd.dev;
+    if (T > 0) {
+        const Common k = make_common(c);
+        if (!launch_lstd_batch(c->cfg.domain, c->cfg.order, c->cfg.algo == RSRL_LSTD_LAMBDA, c->stream, k, make_lstd_batch(c), c->t, 1, nullptr, &io)) return NO_MODEL(c);
+        KCHECK();
+    }
+    c->q_valid = false;
+    c->t += 1;          // one call = one batch-step, as rsrl_hip_handle_batch: the trait loop stays on the driver loop's draw streams
+    bool sync = !all_device;
+    TRY(flush_out(c, &otd, &sync));
+    if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
+    return RSRL_HIP_OK;
+}
+
+// the agents' public solve() (lstd.rs:40, lstd_lambda.rs:44) for every learner
+int rsrl_hip_lstd_solve(rsrl_hip_ctx* c) {
+    CHECK_CTX(c); FLUSH(c);
+    if (c->family != AgentFamily::LstdBatchReg) return fail(RSRL_HIP_ESTATE, "only LSTD and LSTDLambda have a solve() of their own");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (!launch_lstd_batch_solve(c->cfg.domain, c->cfg.order, c->cfg.algo == RSRL_LSTD_LAMBDA, c->stream, make_lstd_batch(c), c->cfg.n_envs)) return NO_MODEL(c);
+    KCHECK();
+    c->q_valid = false;
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return RSRL_HIP_OK;
 }
 RSRL_API_END

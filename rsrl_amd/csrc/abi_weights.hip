@@ -136,6 +136,7 @@ static int lstd_state_rw(rsrl_hip_ctx* c, int64_t env_index, double* theta, doub
                          const double* mu_in) {
     CHECK_CTX(c); FLUSH(c);
     if (!has_lstd_state(c)) return fail(RSRL_HIP_ESTATE, "only RecursiveLSTD and iLSTD (the iLSTD ActorCritic's critic included) carry a least-squares state");
+    if (has_batch_lstd_state(c)) return fail(RSRL_HIP_ESTATE, "LSTD and LSTDLambda carry A, b, z and singular_solves: rsrl_hip_get/set_lstd_batch_state");
     if (env_index < 0 || env_index >= c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "env_index out of range");
     HIP_TRY(hipSetDevice(c->cfg.device));
     c->q_valid = false;
@@ -154,6 +155,38 @@ int rsrl_hip_get_lstd_state(rsrl_hip_ctx* c, int64_t env_index, double* theta, d
 int rsrl_hip_set_lstd_state(rsrl_hip_ctx* c, int64_t env_index, const double* theta, const double* mat, const double* mu) {
     if (!theta || !mat) return fail(RSRL_HIP_EINVAL, "null argument");
     return lstd_state_rw(c, env_index, nullptr, nullptr, nullptr, theta, mat, mu);
+}
+// LSTD / LSTDLambda: one learner's exact f64 state (theta [F], A [F][F], b [F], LSTDLambda's z [F] -- may be null) and its count of abandoned
+// solves.  Host or device arrays
+static int lstd_batch_state_rw(rsrl_hip_ctx* c, int64_t env_index, double* const out[4], const double* const in[4], uint32_t* sing, const uint32_t* sing_in) {
+    CHECK_CTX(c); FLUSH(c);
+    if (!has_batch_lstd_state(c)) return fail(RSRL_HIP_ESTATE, "only LSTD and LSTDLambda carry the batch least-squares state (theta, A, b, z)");
+    if (env_index < 0 || env_index >= c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "env_index out of range");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    c->q_valid = false;
+    const size_t F = (size_t)c->F, i = (size_t)env_index;
+    const struct { double* dev; size_t n; } parts[4] = {
+        {c->lstd_theta + i * F, F}, {c->lstd_mat + i * F * F, F * F}, {c->lstd_mu + i * F, F}, {c->lstd_z ? c->lstd_z + i * F : nullptr, F}};
+    for (int p = 0; p < 4; ++p) {      // (z: LSTDLambda's only, and the caller's is optional)
+        if (!parts[p].dev) continue;
+        if (out && out[p]) HIP_TRY(hipMemcpyAsync(out[p], parts[p].dev, 8 * parts[p].n, hipMemcpyDefault, c->stream));
+        if (in && in[p]) HIP_TRY(hipMemcpyAsync(parts[p].dev, in[p], 8 * parts[p].n, hipMemcpyDefault, c->stream));
+    }
+    if (sing) HIP_TRY(hipMemcpyAsync(sing, c->lstd_sing + i, sizeof(uint32_t), hipMemcpyDefault, c->stream));
+    if (sing_in) HIP_TRY(hipMemcpyAsync(c->lstd_sing + i, sing_in, sizeof(uint32_t), hipMemcpyDefault, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RSRL_HIP_OK;
+}
+int rsrl_hip_get_lstd_batch_state(rsrl_hip_ctx* c, int64_t env_index, double* theta, double* A, double* b, double* z, uint32_t* singular_solves) {
+    if (!theta || !A || !b || !singular_solves) return fail(RSRL_HIP_EINVAL, "null argument");
+    double* const out[4] = {theta, A, b, z};
+    return lstd_batch_state_rw(c, env_index, out, nullptr, singular_solves, nullptr);
+}
+int rsrl_hip_set_lstd_batch_state(rsrl_hip_ctx* c, int64_t env_index, const double* theta, const double* A, const double* b, const double* z,
+                                  const uint32_t* singular_solves) {
+    if (!theta || !A || !b || !singular_solves) return fail(RSRL_HIP_EINVAL, "null argument");
+    const double* const in[4] = {theta, A, b, z};
+    return lstd_batch_state_rw(c, env_index, nullptr, in, nullptr, singular_solves);
 }
 static int return_carry_rw(rsrl_hip_ctx* c, float* out, const float* in) {
     CHECK_CTX(c); FLUSH(c); if (!out && !in) return fail(RSRL_HIP_EINVAL, "null argument");
@@ -179,7 +212,7 @@ struct Ckpt {
     bool has_eps;                                 // (not a header field: the file version says it)
 };
 // the payload sections (what each holds: kSection below); S_EPS is never a row's member -- it ends the file of any ctx that runs the schedule
-enum SectionId : uint8_t { S_NONE = 0, S_WEIGHTS, S_AUX, S_BEHAVIOUR, S_LSTD, S_RING, S_SPARSE, S_EPS, S_COUNT };
+enum SectionId : uint8_t { S_NONE = 0, S_WEIGHTS, S_AUX, S_BEHAVIOUR, S_LSTD, S_LSTD_BATCH, S_RING, S_SPARSE, S_EPS, S_COUNT };
 // THE table: what a file of each aux_kind is.  An agent with state of its own adds a row here (its number: the agent's aux_kind in ctx.hpp kAlgo) and, if no section fits, a section below.
 struct CkptKind {
     uint32_t version, older;     // written as `version` (the epsilon schedule's files: kCkptVersionEps); `older`, no longer written, is still read (0: none)
@@ -187,7 +220,7 @@ struct CkptKind {
     bool reads_kind0;            // a ctx of this kind also reads its configuration's version-2 / aux_kind-0 file, written before the kind's own section
     SectionId sections[3];       // travelled: the weights load, that section's state starts empty
 };
-constexpr int kCkptKinds = 10;
+constexpr int kCkptKinds = 11;
 constexpr CkptKind kCkptKind[kCkptKinds] = {
     /* 0 weights only                           */ {2, 0, true, false, {S_WEIGHTS}},
     /* 1 eligibility traces                     */ {2, 0, true, false, {S_WEIGHTS, S_AUX}},
@@ -199,6 +232,7 @@ constexpr CkptKind kCkptKind[kCkptKinds] = {
     /* 7 REINFORCE's theta and open episode     */ {9, 0, false, false, {S_WEIGHTS, S_AUX, S_BEHAVIOUR}},
     /* 8 the LSTD agents' f64 state             */ {10, 0, false, false, {S_LSTD}},
     /* 9 the iLSTD ActorCritic: f64 state, theta */ {10, 0, false, false, {S_LSTD, S_AUX}},      // (version 10 too: the aux_kind tells the two apart)
+    /* 10 LSTD / LSTDLambda: f64 theta, A, b, z  */ {10, 0, false, false, {S_LSTD, S_LSTD_BATCH}},      // (version 10 as well; S_LSTD: theta, A, then b in mu's place)
 };
 // (the one kind the configuration decides, not the algo: SARSALambda / QLambda over ONE shared tile table keep sparse traces instead of Z)
 int aux_kind_of(const rsrl_hip_ctx* c) { return c->sp_keys ? 4 : kAlgo[c->cfg.algo].aux_kind; }
@@ -261,7 +295,7 @@ struct CkptIo {
     uint32_t version = 0;                         // load: the file's
     bool kind0 = false;                           // load: a version-2 / aux_kind-0 file into a ctx whose row says reads_kind0 -- the kind's own section is not in it
     long long expect = (long long)kCkptHeaderBytes;      // load: the file's length, summed section by section
-    std::vector<float> theta_b, g, ring, eps; std::vector<uint32_t> ring_hl; std::vector<double> lstd;
+    std::vector<float> theta_b, g, ring, eps; std::vector<uint32_t> ring_hl, lstd_sing; std::vector<double> lstd, lstd_z;
     std::vector<uint32_t> sp_len_in, sp_len_t;    // sparse traces: a learner's entries in the file; its sub-lists' lengths on the device
     long sp_prefix = 0;
     uint16_t* spk_new = nullptr; float* spv_new = nullptr;      // sparse traces: shadow lists, switched in at the end like W
@@ -331,6 +365,26 @@ int lstd_read(CkptIo& io) { io.lstd.resize(lstd_doubles(io.c)); return get(io, i
 int lstd_install(CkptIo& io) {
     rsrl_hip_ctx* c = io.c; const size_t nv = (size_t)c->F * (size_t)c->cfg.n_envs; const double* in = io.lstd.data();
     return copy_sync(c, hipMemcpyHostToDevice, {{c->lstd_theta, in, 8 * nv}, {c->lstd_mat, in + nv, 8 * nv * c->F}, {c->lstd_mu, in + nv + nv * c->F, 8 * nv}}, "installing the LSTD state");
+}
+// ---- LSTD / LSTDLambda, behind S_LSTD's theta, A and b: f64 z[N][F] (LSTDLambda only), then u32 singular_solves[N] ----
+size_t lstd_z_doubles(const rsrl_hip_ctx* c) { return c->lstd_z ? (size_t)c->F * (size_t)c->cfg.n_envs : 0; }
+int lstd_batch_size(CkptIo& io) { io.expect += (long long)lstd_z_doubles(io.c) * 8 + (long long)io.c->cfg.n_envs * 4; return RSRL_HIP_OK; }
+int lstd_batch_write(CkptIo& io) {
+    rsrl_hip_ctx* c = io.c;
+    std::vector<double> z(lstd_z_doubles(c)); std::vector<uint32_t> sing((size_t)c->cfg.n_envs);
+    int rc = copy_sync(c, hipMemcpyDeviceToHost, {{z.data(), c->lstd_z, 8 * z.size()}, {sing.data(), c->lstd_sing, 4 * sing.size()}}, "reading the LSTD batch state");
+    if (rc == RSRL_HIP_OK) rc = put(io, z.data(), z.size());
+    return rc == RSRL_HIP_OK ? put(io, sing.data(), sing.size()) : rc;
+}
+int lstd_batch_read(CkptIo& io) {
+    io.lstd_z.resize(lstd_z_doubles(io.c)); io.lstd_sing.resize((size_t)io.c->cfg.n_envs);
+    const int rc = get(io, io.lstd_z.data(), io.lstd_z.size());
+    return rc == RSRL_HIP_OK ? get(io, io.lstd_sing.data(), io.lstd_sing.size()) : rc;
+}
+int lstd_batch_install(CkptIo& io) {
+    rsrl_hip_ctx* c = io.c;
+    return copy_sync(c, hipMemcpyHostToDevice, {{c->lstd_z, io.lstd_z.data(), 8 * io.lstd_z.size()}, {c->lstd_sing, io.lstd_sing.data(), 4 * io.lstd_sing.size()}},
+                     "installing the LSTD batch state");
 }
 // ---- QSigma: every learner's Backup ring.  A kind-0 file has none: the run resumes from EMPTY backups, as after a terminal transition (q_sigma.rs:154) ----
 size_t qs_floats(const rsrl_hip_ctx* c) { return (size_t)(c->D + 5) * (size_t)c->cfg.n_steps * (size_t)c->cfg.n_envs; }
@@ -495,6 +549,7 @@ const Section kSection[S_COUNT] = {
     /* S_AUX       */ {aux_size, aux_write, aux_read, nothing},                                  // n_learners x f32[F][aux_cols]: traces / fa_td's weights / the actor's theta
     /* S_BEHAVIOUR */ {behaviour_size, behaviour_write, behaviour_read, behaviour_install},      // n_learners x f32[F][A] of theta_b, then g[N]
     /* S_LSTD      */ {lstd_size, lstd_write, lstd_read, lstd_install},                          // f64: every learner's theta, then matrix, then (iLSTD) mu
+    /* S_LSTD_BATCH */ {lstd_batch_size, lstd_batch_write, lstd_batch_read, lstd_batch_install},     // f64 z (LSTDLambda), then u32 singular_solves[N]
     /* S_RING      */ {ring_size, ring_write, ring_read, ring_install},                          // head[N], len[N], entries (SoA [field][slot][learner])
     /* S_SPARSE    */ {sparse_size, sparse_write, sparse_read, sparse_install},                  // owner prefix, len[N], every learner's keys and values
     /* S_EPS       */ {eps_size, eps_write, eps_read, eps_install},                              // eps[N]
@@ -629,6 +684,8 @@ int rsrl_hip_checksum(rsrl_hip_ctx* c, uint64_t out[2]) {
     run(c->lstd_theta, c->lstd_theta ? sizeof(double) * c->F * N : 0, (size_t)1 << 41, 0);
     run(c->lstd_mat, c->lstd_mat ? sizeof(double) * c->F * c->F * N : 0, (size_t)1 << 42, 0);
     run(c->lstd_mu, c->lstd_mu ? sizeof(double) * c->F * N : 0, (size_t)1 << 43, 0);
+    run(c->lstd_z, c->lstd_z ? sizeof(double) * c->F * N : 0, (size_t)1 << 44, 0);            // LSTDLambda's trace, LSTD / LSTDLambda's abandoned solves
+    run(c->lstd_sing, c->lstd_sing ? sizeof(uint32_t) * N : 0, (size_t)1 << 45, 0);
     KCHECK();
     unsigned long long h[2];
     HIP_TRY(hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, c->stream));

@@ -49,7 +49,7 @@ using namespace rsrl;
 
 // ---- THE agent table: what the reference's agent of each rsrl_algo is, one row per number.  Admission (check_config), the ctx's buffers (create_impl),
 // the accessors and the checkpoint read it; a new agent adds its row here, a line of classify() and a case of launch_agent ("Adding an agent").
-enum class Agent : uint8_t { None, OneStep, Lambda, Gq, Pred, QSigma, Ac, TdAc, Reinforce, Lstd, TdAcLstd, Gmc };      // the group classify() and the kernels' dispatch know it by
+enum class Agent : uint8_t { None, OneStep, Lambda, Gq, Pred, QSigma, Ac, TdAc, Reinforce, Lstd, TdAcLstd, Gmc, LstdBatch };      // the group classify() and the kernels' dispatch know it by
 enum class Aux : uint8_t { None, LikeW, Policy };      // the second per-learner matrix Z: none, of W's shape, or the actor's A columns next to a one-column W
 struct AlgoRow {
     const char* name = nullptr;      // as the admission messages print it (nullptr: the number is unassigned)
@@ -63,7 +63,7 @@ struct AlgoRow {
     // one of them), the message's words behind it and behind "agent_policy = -1", and what it calls config.n_steps in front of "n_updates" (nullptr: not read)
     int reg_policy = -1; const char* policy_words = ""; const char* shares_words = ""; const char* n_updates = nullptr;
 };
-constexpr AlgoRow kAlgo[RSRL_GRADIENT_MC + 1] = {
+constexpr AlgoRow kAlgo[RSRL_LSTD_LAMBDA + 1] = {
     /*  0 */ {"QLearning", Agent::OneStep},
     /*  1 */ {"SARSA", Agent::OneStep},
     /*  2 */ {"ExpectedSARSA", Agent::OneStep},
@@ -92,6 +92,10 @@ constexpr AlgoRow kAlgo[RSRL_GRADIENT_MC + 1] = {
     /* 22 */ {},
     // (W is V's one column, TD's layout; the open episodes live in rec_s / rec_r)
     /* 23 */ {"GradientMC (RSRL_GRADIENT_MC)", Agent::Gmc, true, Aux::None, 0, false, false, RSRL_RANDOM},
+    /* 24 */ {},
+    // (the batch least-squares agents: W as the LSTD agents'; A in lstd_mat, b in lstd_mu, z / singular_solves of their own, the open episodes in rec_s / rec_r)
+    /* 25 */ {"LSTD (RSRL_LSTD)", Agent::LstdBatch, true, Aux::None, 10, false, true, RSRL_RANDOM},
+    /* 26 */ {"LSTDLambda (RSRL_LSTD_LAMBDA)", Agent::LstdBatch, true, Aux::None, 10, false, true, RSRL_RANDOM},
 };
 // (readers of the table, for configurations check_config has admitted: the algo is a row with a name)
 static inline bool is_lambda(int algo) { return kAlgo[algo].agent == Agent::Lambda; }
@@ -102,8 +106,11 @@ static inline bool is_reinforce(int algo) { return kAlgo[algo].agent == Agent::R
 static inline bool is_lstd(int algo) { return kAlgo[algo].agent == Agent::Lstd; }
 static inline bool is_tdac_lstd(int algo) { return kAlgo[algo].agent == Agent::TdAcLstd; }
 static inline bool is_gmc(int algo) { return kAlgo[algo].agent == Agent::Gmc; }
+static inline bool is_lstd_batch(int algo) { return kAlgo[algo].agent == Agent::LstdBatch; }
+// the agents that keep every learner's open episode on the device (rec_s / rec_r, max_episode_steps rows) and sweep it when it ends
+static inline bool keeps_record(int algo) { return is_gmc(algo) || is_lstd_batch(algo); }
 // the agents whose value function is V alone and whose behaviour is Random: no action values to search, weigh, sample from or roll out with
-static inline bool is_v_only(int algo) { return is_pred(algo) || is_lstd(algo) || is_gmc(algo); }
+static inline bool is_v_only(int algo) { return is_pred(algo) || is_lstd(algo) || is_gmc(algo) || is_lstd_batch(algo); }
 
 // ---- the small kernels more than one unit launches, and the launches of kernel templates two units would otherwise both instantiate: defined ONCE, in
 // kernels_util.hip / launch_shared.hip (a kernel's host stub is an ordinary function: another unit launches it through this declaration)
@@ -185,14 +192,16 @@ enum class AgentFamily : uint8_t {
     TdAcLstdReg,          // ActorCritic with the iLSTD critic, same configurations as TdAcReg: k_train_tdac_lstd (train_tdac_lstd.hip); iLSTD's f64 state as
                           // LstdReg's, theta in Z (A columns)
     GmcReg,               // GradientMC, same configurations as LstdReg: k_train_gmc (train_gmc.hip); w in W (one column), the open episodes in rec_s / rec_r
+    LstdBatchReg,         // LSTD / LSTDLambda, same configurations as GmcReg: k_train_lstd_batch (train_lstd_batch.hip); f64 state in lstd_theta / lstd_mat (A) /
+                          // lstd_mu (b) / lstd_z / lstd_sing, the open episodes in rec_s / rec_r
 };
-constexpr size_t kAgentFamilies = (size_t)AgentFamily::GmcReg + 1;      // (the enum's last value)
+constexpr size_t kAgentFamilies = (size_t)AgentFamily::LstdBatchReg + 1;      // (the enum's last value)
 // ---- THE family table: which kernels serve a family and what they can do, one row per AgentFamily value in the enum's order.  classify() (abi_ctx.hip: a
 // decision) and launch_agent (abi_train.hip: it instantiates the templates) are the two other places a new family is entered.
 enum class Slots : uint8_t { Block, Block64, WaveBlock, Learner, LstdGroup };      // a statistics slot per: kBlock learners, 64 learners (k_train_lambda_mem4; the
                                                                                    // ctx's k1_quad), wave-family block, learner (a block each), kBlock lanes of G per learner
 enum class Handle : uint8_t { Model, Wave, Agent };      // rsrl_hip_handle's kernel: k_handle<Model>, k_wave_handle, or the family's own through launch_agent
-enum : uint8_t { kWave = 1, kCarriesQ = 2, kPolicyW = 4, kVCritic = 8, kLstd = 16 };
+enum : uint8_t { kWave = 1, kCarriesQ = 2, kPolicyW = 4, kVCritic = 8, kLstd = 16, kBatchLstd = 32 };
 struct FamilyRow {
     AgentFamily family;      // (its own index: checked below)
     const char* kernel;      // the driver-loop kernel timing_read names (WaveControl, RegStep: refined by train_kernel_name)
@@ -200,7 +209,8 @@ struct FamilyRow {
     Slots slots;
     Handle handle;
     uint8_t can;             // kWave: one wavefront per learner (is_wave_family); kCarriesQ: reads Common::qcache; kPolicyW: a Gibbs policy over weights of its
-};                           // own, theta in Z; kVCritic: a state-value critic next to the actor; kLstd: the value function is the f64 least-squares state
+};                           // own, theta in Z; kVCritic: a state-value critic next to the actor; kLstd: the value function is the f64 least-squares state;
+                             // kBatchLstd: ... of the batch agents (A, b, z, singular_solves: get/set_lstd_batch_state, not get/set_lstd_state)
 // The depths.  Every launch of a register-resident loop loads and stores every learner's weights (60.7 MB at 65 536 MountainCar learners: ~11 us; the
 // trace / GreedyGQ / TD ones two matrices) and pays a launch-to-launch gap around its arithmetic (0.77 us per batch-step): 1 024 steps per launch instead
 // of 256 is worth +7 % (8.3e10 -> 8.9e10 env-steps/s).  Round 3, under the driver's invocation (20-step calls, coalesced): 1 024 -> 8.96e10,
@@ -238,6 +248,7 @@ constexpr FamilyRow kFamily[] = {
     {AgentFamily::LstdReg, "k_train_lstd", 32, Slots::LstdGroup, Handle::Agent, kLstd},
     {AgentFamily::TdAcLstdReg, "k_train_tdac_lstd", 32, Slots::LstdGroup, Handle::Agent, kPolicyW | kVCritic | kLstd},
     {AgentFamily::GmcReg, "k_train_gmc", 4096, Slots::Block, Handle::Agent, 0},      // (handle: refused, whole trajectories only)
+    {AgentFamily::LstdBatchReg, "k_train_lstd_batch", 256, Slots::LstdGroup, Handle::Agent, kLstd | kBatchLstd},      // (handle: refused, whole batches only)
 };
 constexpr bool family_rows_in_order() {
     for (size_t i = 0; i < sizeof(kFamily) / sizeof(kFamily[0]); ++i) if ((size_t)kFamily[i].family != i) return false;
@@ -293,8 +304,10 @@ struct rsrl_hip_ctx {
     double* hiv_y = nullptr;         // HIVTreatment only: every learner's hidden state f64[6][N] (`state` holds its observation)
     double* lstd_theta = nullptr;    // RecursiveLSTD / iLSTD / the iLSTD ActorCritic only: theta f64[N][F], the matrix (C / A) f64[N][F][F], iLSTD's mu f64[N][F] (learner-major)
     double* lstd_mat = nullptr;
-    double* lstd_mu = nullptr;
-    float* rec_s = nullptr;          // GradientMC only: every learner's open episode, rows 0 .. ep_step[i]-1 of f32[max_episode_steps][D][N] (`from`) and
+    double* lstd_mu = nullptr;       //   (LSTD / LSTDLambda: A in lstd_mat, b in lstd_mu)
+    double* lstd_z = nullptr;        // LSTDLambda only: the trace z f64[N][F]
+    uint32_t* lstd_sing = nullptr;   // LSTD / LSTDLambda only: u32[N], the solves abandoned on a zero pivot
+    float* rec_s = nullptr;          // GradientMC, LSTD / LSTDLambda only: every learner's open episode, rows 0 .. ep_step[i]-1 of f32[max_episode_steps][D][N] (`from`) and
     float* rec_r = nullptr;          //   f32[max_episode_steps][N] (the reward)
     bool q_valid = false;            // false whenever weights / states were changed from outside the driver loop
     // ---- the trait-granular fast path (kernels_trait.hpp): register-family Fourier basis, per-learner f32 weights, learner-major layout
@@ -416,6 +429,14 @@ static inline GmcState make_gmc(const rsrl_hip_ctx* c) {
     GmcState gs;
     gs.rec_s = c->rec_s; gs.rec_r = c->rec_r;
     return gs;
+}
+static inline bool has_batch_lstd_state(const rsrl_hip_ctx* c) { return family_row(c).can & kBatchLstd; }
+static inline LstdBatchState make_lstd_batch(const rsrl_hip_ctx* c) {
+    LstdBatchState ls;
+    ls.theta = c->lstd_theta; ls.mat = c->lstd_mat; ls.b = c->lstd_mu; ls.z = c->lstd_z; ls.sing = c->lstd_sing;
+    ls.rec_s = c->rec_s; ls.rec_r = c->rec_r;
+    ls.gamma = c->cfg.gamma; ls.lambda = c->cfg.lambda;
+    return ls;
 }
 static inline LstdState make_lstd(const rsrl_hip_ctx* c) {
     LstdState ls;

@@ -51,6 +51,8 @@ struct Batch {                            // Batch = Vec<Transition> (lib.rs:210
     std::vector<int32_t> actions;         // [T][N]
     std::vector<float> rewards;           // [T][N]
     std::vector<uint32_t> lengths;        // [N]  0 = no batch
+    std::vector<float> to;                // [T][D][N]  each transition's `to` state      (read by LSTD / LSTDLambda only: whole transitions)
+    std::vector<uint8_t> terminal;        // [T][N]     ... and its Observation::Terminal flag
 };
 struct Trajectory {                       // lib.rs:334-409, batched: `start` = states row 0, steps[k] = (states row k+1, actions[k], rewards[k])
     std::vector<uint32_t> n_states;       // [N]  Trajectory::n_states()  (:340); n_transitions = n_states - 1
@@ -262,6 +264,18 @@ struct iLSTD : control::td::Agent {
     iLSTD(const fa::linear::basis::Fourier& basis, double alpha_, double gamma, int n_updates)
         : control::td::Agent{RSRL_ILSTD, make_shared(fa::linear::LFA::vector(basis, fa::linear::optim::SGD(0.0), 1)), gamma, alpha_} { n_steps = n_updates; }
 };
+// LSTD::new(basis, gamma) / LSTDLambda::new(basis, gamma, lambda)   (lstd.rs:23-37, lstd_lambda.rs:25-41).  Handler<&Batch> on whole transitions:
+// Session::handle(const Batch&) with the batch's `to` and `terminal` filled; Session::solve() is their public solve().  theta, A, b and z are f64
+// on the device (Session::lstd_batch_state).  The solve is the library's own elimination: no SVD fallback, a zero pivot keeps theta and counts in
+// singular_solves.  Drive these with policies::Random and a max_episode_steps >= 1 (the device records the open episodes)
+struct LSTD : control::td::Agent {
+    LSTD(const fa::linear::basis::Fourier& basis, double gamma)
+        : control::td::Agent{RSRL_LSTD, make_shared(fa::linear::LFA::vector(basis, fa::linear::optim::SGD(0.0), 1)), gamma} {}
+};
+struct LSTDLambda : control::td::Agent {
+    LSTDLambda(const fa::linear::basis::Fourier& basis, double gamma, double lambda_)
+        : control::td::Agent{RSRL_LSTD_LAMBDA, make_shared(fa::linear::LFA::vector(basis, fa::linear::optim::SGD(0.0), 1)), gamma, 1.0, RSRL_TRACE_ACCUMULATE, lambda_} {}
+};
 }}  // namespace prediction::lstd
 inline control::ac::ActorCritic control::ac::ActorCritic::tdac(const prediction::lstd::iLSTD& eval, const policies::Gibbs& policy, double alpha_, double gamma) {
     if (gamma != eval.gamma) throw Error(RSRL_HIP_EINVAL, "ActorCritic::tdac over iLSTD: the library runs TDCritic and iLSTD with one gamma");
@@ -325,8 +339,15 @@ public:
         return td;
     }
     // Handler<&Batch>::handle of REINFORCE / BaselineREINFORCE -> the running return at each handled transition, [T][N] (reinforce.rs)
+    // ... and of LSTD / LSTDLambda, which read whole transitions (b.to and b.terminal filled; lstd.rs:59-81, lstd_lambda.rs:66-103) -> the
+    // diagnostic r + gamma V(s') - V(s) at each handled transition, [T][N]
     std::vector<float> handle(const domains::Batch& b) {
         std::vector<float> g((size_t)b.T * N_);
+        if (!b.to.empty() || !b.terminal.empty()) {
+            check(rsrl_hip_handle_transitions(ctx_, b.T, b.states.data(), b.actions.empty() ? nullptr : b.actions.data(), b.rewards.data(), b.to.data(),
+                                              b.terminal.data(), b.lengths.data(), b.T > 0 ? g.data() : nullptr));
+            return g;
+        }
         check(rsrl_hip_handle_batch(ctx_, b.T, b.states.data(), b.actions.data(), b.rewards.data(), b.lengths.data(), g.data()));
         return g;
     }
@@ -392,6 +413,16 @@ public:
     LstdState lstd_state(int64_t env = 0, bool with_mu = false) {
         LstdState st{std::vector<double>((size_t)F_), std::vector<double>((size_t)F_ * F_), std::vector<double>(with_mu ? (size_t)F_ : 0)};
         check(rsrl_hip_get_lstd_state(ctx_, env, st.theta.data(), st.mat.data(), with_mu ? st.mu.data() : nullptr));
+        return st;
+    }
+    // LSTD / LSTDLambda: solve() (lstd.rs:40, lstd_lambda.rs:44) for every learner, and one learner's exact f64 state -- theta [F], A [F][F]
+    // (row-major), b [F], LSTDLambda's z [F] (empty otherwise) and its count of abandoned solves
+    void solve() { check(rsrl_hip_lstd_solve(ctx_)); }
+    struct LstdBatchState { std::vector<double> theta, A, b, z; uint32_t singular_solves = 0; };
+    LstdBatchState lstd_batch_state(int64_t env = 0, bool with_z = false) {
+        LstdBatchState st{std::vector<double>((size_t)F_), std::vector<double>((size_t)F_ * F_), std::vector<double>((size_t)F_),
+                          std::vector<double>(with_z ? (size_t)F_ : 0)};
+        check(rsrl_hip_get_lstd_batch_state(ctx_, env, st.theta.data(), st.A.data(), st.b.data(), with_z ? st.z.data() : nullptr, &st.singular_solves));
         return st;
     }
     // the pub field `policy` of ActorCritic: the Gibbs actor's weights               (ac.rs:61)
