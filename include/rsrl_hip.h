@@ -61,8 +61,15 @@ typedef enum {
  *   (D = 6) is its observation clip(-5, log10 y, 8) (:112-119) rounded to f32, the reward is taken from the observation in f64 (:121-135);
  *   4 actions (:35), no terminal state (episodes end at max_episode_steps only).  Supported: QLearning, SARSA, ExpectedSARSA, PAL on the
  *   Fourier basis of order 1-3, per-learner f32 weights, no epsilon schedule; every other combination is EINVAL at create.  The hidden
- *   state: rsrl_hip_get_hidden_states / _set_hidden_states. */
-typedef enum { RSRL_MOUNTAIN_CAR = 0, RSRL_CART_POLE = 1, RSRL_ACROBOT = 2, RSRL_HIV_TREATMENT = 3 } rsrl_domain;
+ *   state: rsrl_hip_get_hidden_states / _set_hidden_states.
+ * ContinuousMountainCar (mountain_car/continuous.rs): MountainCar's state bounds and start state (-0.5, 0) -- the Fourier features of a state are
+ *   MountainCar's at the same order -- with ONE f32 action in [-1, 1] instead of an index:  a' = clip(-1, a, 1) (the reference's
+ *   action_space.map_onto, from the `spaces` crate that is not in the reference tree: recalled as a clip);
+ *   v = clip(-0.07, v + 0.0015 a' - 0.0025 cos(3x), 0.07); x = clip(-1.2, x + v, 0.6); terminal iff x >= 0.6; reward 0 on a terminal step, -1
+ *   otherwise.  The action set is not enumerable: rsrl_hip_n_actions is 0, rsrl_hip_action_bounds gives (-1, 1), and every action of the ctx is
+ *   f32 (the *_f32 entry points below; their int32 twins are ESTATE, as the *_f32 calls are on the other domains).  Supported:
+ *   RSRL_ILSTD_ACTOR_CRITIC with policy RSRL_BETA on the Fourier orders 1-5; every other combination is EINVAL at create. */
+typedef enum { RSRL_MOUNTAIN_CAR = 0, RSRL_CART_POLE = 1, RSRL_ACROBOT = 2, RSRL_HIV_TREATMENT = 3, RSRL_CONTINUOUS_MOUNTAIN_CAR = 4 } rsrl_domain;
 /* lfa::basis::{Fourier (+with_bias), TileCoding}  (re-exported by rsrl/src/fa/linear.rs:11-14) */
 typedef enum { RSRL_FOURIER = 0, RSRL_TILE_CODING = 1 } rsrl_basis;
 /* rsrl::control::td::{QLearning, SARSA, ExpectedSARSA}
@@ -177,7 +184,14 @@ typedef enum { RSRL_QLEARNING = 0, RSRL_SARSA = 1, RSRL_EXPECTED_SARSA = 2, RSRL
                 * RSRL_TD_ACTOR_CRITIC's: it reads theta_a [F][A] (policy_sample / _mode / _probs / _prob, reset's initial sample, the rollouts;
                 * rsrl_hip_get/set_policy_weights).  handle_batch, traces and td weights are ESTATE.  rsrl_hip_handle's td_error_out and the
                 * statistics' sum |delta| are iLSTD's diagnostic.  rsrl_hip_reset leaves both agents' state alone.  Supported: as
-                * RSRL_TD_ACTOR_CRITIC; everything else is EINVAL at create (kernels_tdac_lstd.hpp) */
+                * RSRL_TD_ACTOR_CRITIC; everything else is EINVAL at create (kernels_tdac_lstd.hpp).
+                * On RSRL_CONTINUOUS_MOUNTAIN_CAR the same agent runs with policy RSRL_BETA (the agent and the loop of examples/tdac_beta.rs:
+                * ActorCritic::tdac is generic over the policy): Fourier orders 1-5, per-learner f32 weights, agent_policy -1, no epsilon schedule.
+                * The critic half is unchanged -- theta / A / mu and the diagnostic are the bits of an RSRL_ILSTD ctx's on the same transitions -- and
+                * the actor is RSRL_BETA's update below with e = (float)(alpha * c).  The policy side reads the policy's two columns [F][2]
+                * (rsrl_hip_policy_sample_f32 / _mode_f32 / _params / _pdf, reset's initial sample, rsrl_hip_rollout_greedy = Domain::rollout with
+                * policy.mode, tdac_beta.rs:66); rsrl_hip_rollout_trajectory / _policy (int32 actions), policy_probs / _prob, q_find_max / _min,
+                * q_expected_value, traces, td weights and handle_batch are ESTATE.  The checkpoint is aux_kind 11 (kernels_tdac_beta.hpp) */
                RSRL_ILSTD_ACTOR_CRITIC = 21,
                /* (22 is no algo.)  GradientMC (prediction/mc.rs:26-58): every-visit Monte-Carlo prediction, v_func = ScalarLFA(basis, SGD(lr)).
                 * Handler<&Trajectory>::handle visits the transitions LAST TO FIRST (TrajectoryIter::next_back, rsrl_domains/src/lib.rs:289-319):
@@ -226,8 +240,24 @@ typedef enum { RSRL_QLEARNING = 0, RSRL_SARSA = 1, RSRL_EXPECTED_SARSA = 2, RSRL
 /* rsrl::traces::{Accumulate, Saturate (Trace::replacing), Dutch}      traces.rs:188-240 */
 typedef enum { RSRL_TRACE_ACCUMULATE = 0, RSRL_TRACE_SATURATE = 1, RSRL_TRACE_DUTCH = 2 } rsrl_trace;
 /* rsrl::policies::{Greedy, EpsilonGreedy, Softmax, Random}
- *   greedy.rs:16-84, epsilon_greedy.rs:14-83, softmax.rs:55-143, random.rs:13-48 */
-typedef enum { RSRL_GREEDY = 0, RSRL_EPSILON_GREEDY = 1, RSRL_SOFTMAX = 2, RSRL_RANDOM = 3 } rsrl_policy;
+ *   greedy.rs:16-84, epsilon_greedy.rs:14-83, softmax.rs:55-143, random.rs:13-48
+ * Beta (policies/beta.rs) over two Composition<ScalarLFA, Softplus> (fa/composition.rs:98-115, fa/transforms.rs:196-218): a CONTINUOUS policy, for
+ *   RSRL_ILSTD_ACTOR_CRITIC on RSRL_CONTINUOUS_MOUNTAIN_CAR only (EINVAL elsewhere, and as agent_policy).  Per learner two weight columns w_a, w_b
+ *   f32[F] (zero at create; rsrl_hip_get/set_policy_weights carry them as f32[F][2], column 0 = alpha's; rsrl_hip_n_policy_outputs = 2).  With
+ *   x_a = <w_a, phi(s)>, x_b likewise (f32): alpha = softplus(x_a) + 1, beta = softplus(x_b) + 1, softplus(x) = x for x >= 10 else ln(1 + exp(x))
+ *   (MIN_TOL = 1.0, beta.rs:19, :58-67): both >= 1.
+ *   sample  X = Ga / (Ga + Gb), Ga ~ Gamma(alpha, 1), Gb ~ Gamma(beta, 1) by Marsaglia-Tsang with at most 8 rounds per gamma (then the value is
+ *           d = k - 1/3), clamped to [2^-24, 1 - 2^-24].  Round j of the sample for purpose P (the step's draw, the initial sample, an API call)
+ *           takes the whole Philox block at block word P + 256 (j + 1): a function of (seed, global learner id, t, purpose) only.  The reference
+ *           samples through rstat / rand_distr from thread_rng(): distribution parity is the contract, as for every other policy.
+ *   mode    (alpha - 1) / (alpha + beta - 2) if both exceed 1, else the mean alpha / (alpha + beta) (beta.rs:141-150; rstat's modes() is not in the
+ *           reference tree: this is the library's definition).
+ *   update  g_a = ln a - psi(alpha) + psi(alpha + beta), g_b = ln(1 - a) - psi(beta) + psi(alpha + beta) (psi = digamma; the score is recalled from
+ *           rstat::univariate::beta, not pinned by the reference tree);  w_a += e g_a sigma(x_a) phi(s),  w_b += e g_b sigma(x_b) phi(s), sigma =
+ *           Softplus's gradient (1 for x >= 10, else the logistic), SGD(1.0) (beta.rs:153-187); both parameters are read before either column
+ *           moves.  DEPARTURE: a caller-supplied action is clamped to the sample's interval before its logarithms (the reference would produce
+ *           infinities for 0 and 1), in the spirit of the index actions' clamp. */
+typedef enum { RSRL_GREEDY = 0, RSRL_EPSILON_GREEDY = 1, RSRL_SOFTMAX = 2, RSRL_RANDOM = 3, RSRL_BETA = 4 } rsrl_policy;
 /* one LFA per learner (independent replicas) or one LFA shared by all learners
  * (synchronous mini-batch rule; N=1 == the reference rule) */
 typedef enum { RSRL_W_PER_ENV = 0, RSRL_W_SHARED = 1 } rsrl_weight_mode;
@@ -350,10 +380,16 @@ int rsrl_hip_n_actions(const rsrl_hip_ctx* ctx);
 /* columns of the weight matrix: n_actions for the control agents (VectorLFA), 1 for TD / TDLambda (ScalarLFA,
  * Parameterised::weights_dim = (F, 1), fa/linear.rs:201-203) */
 int rsrl_hip_n_outputs(const rsrl_hip_ctx* ctx);
+/* columns of the policy's own weight matrix (rsrl_hip_get/set_policy_weights): n_actions for the Gibbs actors, 2 for RSRL_BETA (alpha's, beta's);
+ * 0 for the agents whose policy reads Q */
+int rsrl_hip_n_policy_outputs(const rsrl_hip_ctx* ctx);
 int rsrl_hip_n_features(const rsrl_hip_ctx* ctx);
 int64_t rsrl_hip_n_envs(const rsrl_hip_ctx* ctx);
 /* state_space() bounds: mountain_car/discrete.rs:97-99, cart_pole.rs:112-118, acrobot.rs:143-149 */
 int rsrl_hip_state_bounds(const rsrl_hip_ctx* ctx, double* lo /*[D]*/, double* hi /*[D]*/);
+/* action_space() bounds of a continuous domain: (-1, 1) on RSRL_CONTINUOUS_MOUNTAIN_CAR (mountain_car/continuous.rs); EINVAL on the domains whose
+ * actions are indices (rsrl_hip_n_actions) */
+int rsrl_hip_action_bounds(const rsrl_hip_ctx* ctx, double* lo, double* hi);
 
 /* per-episode `Domain::default()` + initial `policy.sample(rng, env.emit().state())`
  *   examples/q_learning.rs:37-38 -- for every learner of the ctx */
@@ -373,6 +409,23 @@ int rsrl_hip_get_hidden_states(rsrl_hip_ctx* ctx, double* y /*[6][N]*/);
 int rsrl_hip_set_hidden_states(rsrl_hip_ctx* ctx, const double* y /*[6][N]*/);
 int rsrl_hip_get_actions(rsrl_hip_ctx* ctx, int32_t* actions /*[N]*/);
 int rsrl_hip_set_actions(rsrl_hip_ctx* ctx, const int32_t* actions /*[N]*/);
+/* ---- f32 actions: the twins of the int32 calls for a ctx on a continuous domain (RSRL_CONTINUOUS_MOUNTAIN_CAR), with their conventions -- host or
+ * device pointers, the same asynchrony, the same meaning of the step counter.  A HOST array of actions is validated (EINVAL unless every value is
+ * finite; rsrl_hip_set_actions_f32: inside the action bounds too), a DEVICE array is clamped by the kernels.  On such a ctx the int32 calls --
+ * rsrl_hip_get/set_actions, _domain_step, _handle, _policy_sample, _policy_mode -- are ESTATE; on every other ctx the f32 calls are.
+ *   rsrl_hip_domain_step_f32      rsrl_hip_domain_step            rsrl_hip_policy_sample_f32   rsrl_hip_policy_sample (states == NULL as there)
+ *   rsrl_hip_handle_f32           rsrl_hip_handle                 rsrl_hip_policy_mode_f32     rsrl_hip_policy_mode
+ * rsrl_hip_policy_params is beta.rs's pub compute_alpha / compute_beta, rsrl_hip_policy_pdf its Function<(S, A)> (the density, of the action
+ * clamped to [2^-24, 1 - 2^-24]); both read-only, state i against learner i's columns */
+int rsrl_hip_get_actions_f32(rsrl_hip_ctx* ctx, float* actions /*[N]*/);
+int rsrl_hip_set_actions_f32(rsrl_hip_ctx* ctx, const float* actions /*[N]*/);
+int rsrl_hip_domain_step_f32(rsrl_hip_ctx* ctx, const float* actions, float* from_states, float* next_states, float* rewards, uint8_t* terminal);
+int rsrl_hip_handle_f32(rsrl_hip_ctx* ctx, const float* from_states, const float* actions, const float* rewards, const float* to_states,
+                        const uint8_t* terminal, int64_t M, float* td_error_out);
+int rsrl_hip_policy_sample_f32(rsrl_hip_ctx* ctx, const float* states, int64_t M, float* actions_out);
+int rsrl_hip_policy_mode_f32(rsrl_hip_ctx* ctx, const float* states, int64_t M, float* actions_out);
+int rsrl_hip_policy_params(rsrl_hip_ctx* ctx, const float* states, int64_t M, float* alpha_out, float* beta_out);
+int rsrl_hip_policy_pdf(rsrl_hip_ctx* ctx, const float* states, const float* actions, int64_t M, float* out);
 /* (ABI 8) The rest of a learner's state between two driver calls, so that a run can be carried into another ctx EXACTLY (with the checkpoint of
  * rsrl_hip_save_weights, the states and the actions above):
  *   - the steps every learner's current episode has taken (what the driver loop's `for j in 0..step_limit` counter would hold,
@@ -544,6 +597,7 @@ int rsrl_hip_lstd_solve(rsrl_hip_ctx* ctx);
  *   8 the LSTD agents' f64 state                     10          f64 theta, matrices, mu
  *   9 the iLSTD ActorCritic's f64 state and theta    10          f64 theta, matrices, mu, auxiliary matrix
  *   10 LSTD / LSTDLambda's f64 state                 10          f64 theta, A, b, z (LSTDLambda), u32 singular_solves
+ *   11 the Beta iLSTD ActorCritic's state            10          f64 theta, matrices, mu, the policy's columns
  * and a ctx with config.epsilon_decay (aux_kind 0 or 1) writes version 4 instead, with f32 eps[N] behind the payload.  No other pairing of
  * version and aux_kind is a file of this library; load refuses it.  Little-endian, serialised field by field (no padding):
  *   offset  0  char magic[8] = "RSRLHIPW"
@@ -552,7 +606,8 @@ int rsrl_hip_lstd_solve(rsrl_hip_ctx* ctx);
  *                   algo, weight_dtype, aux_kind (0 none, 1 eligibility traces, 2 GreedyGQ's fa_td weights,
  *                   3 QSigma's n-step backups, 4 sparse traces over a shared table, 5 ActorCritic's theta,
  *                   6 the TD ActorCritic's theta, 7 REINFORCE's theta and open episode, 8 the LSTD agents' f64 state,
- *                   9 the iLSTD ActorCritic's f64 state and theta, 10 LSTD / LSTDLambda's f64 state)
+ *                   9 the iLSTD ActorCritic's f64 state and theta, 10 LSTD / LSTDLambda's f64 state,
+ *                   11 the Beta iLSTD ActorCritic's f64 state and policy columns)
  *                                                                                                                 [11 x i32]
  *          56  i64  n_learners (1 in shared mode)
  *          64  u64  step_count
@@ -573,6 +628,8 @@ int rsrl_hip_lstd_solve(rsrl_hip_ctx* ctx);
  *              if aux_kind is 10 (file version 10 too; RSRL_LSTD / RSRL_LSTD_LAMBDA): the weights section is ABSENT;
  *              then n_learners x f64[F] of theta, n_learners x f64[F][F] of A (row-major), n_learners x f64[F] of b, for LSTDLambda
  *              n_learners x f64[F] of z, then u32 singular_solves[N].  The open episodes are not in the file (as RSRL_GRADIENT_MC's);
+ *              if aux_kind is 11 (file version 10 too; RSRL_ILSTD_ACTOR_CRITIC with RSRL_BETA on RSRL_CONTINUOUS_MOUNTAIN_CAR): aux_kind 8's
+ *              sections of its iLSTD critic (mu included), then n_learners x f32[F][2] of the policy's columns (alpha's, beta's);
  *              if aux_kind is 3 (file version 3): u32 head[N], u32 len[N], f32 entries[D + 5][n_steps][N] -- every learner's
  *              Backup ring {s, a, q, residual, pi, mu} (q_sigma.rs:30-63), so that a QSigma run with n_steps > 1 resumes
  *              bit-identically too.  A QSigma ctx still reads its configuration's version-2 file without them (aux_kind 0): the backups start empty.
@@ -652,7 +709,7 @@ int rsrl_hip_rollout_policy(rsrl_hip_ctx* ctx, int policy, double epsilon, doubl
                             float* rewards_out, uint8_t* terminal_out);
 
 /* Order-independent 64-bit checksums of the ctx's device state (sum of the 32-bit words, each multiplied by an odd
- * function of its index): out[0] weights (+traces), out[1] env states/actions/episode counters (+ HIVTreatment's hidden states).  For determinism /
+ * function of its index): out[0] weights (+traces), out[1] env states/actions/episode counters (+ HIVTreatment's hidden states, a continuous ctx's f32 actions).  For determinism /
  * sharding / fusion-invariance checks at sizes where copying the weights out is not practical. */
 int rsrl_hip_checksum(rsrl_hip_ctx* ctx, uint64_t out[2]);
 

@@ -44,9 +44,11 @@ SYMBOLS = {
     "rsrl_hip_state_dim": (C.c_int, [C.c_void_p]),
     "rsrl_hip_n_actions": (C.c_int, [C.c_void_p]),
     "rsrl_hip_n_outputs": (C.c_int, [C.c_void_p]),
+    "rsrl_hip_n_policy_outputs": (C.c_int, [C.c_void_p]),
     "rsrl_hip_n_features": (C.c_int, [C.c_void_p]),
     "rsrl_hip_n_envs": (C.c_int64, [C.c_void_p]),
     "rsrl_hip_state_bounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "rsrl_hip_action_bounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rsrl_hip_reset": (C.c_int, [C.c_void_p]),
     "rsrl_hip_get_states": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rsrl_hip_set_states": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -54,6 +56,14 @@ SYMBOLS = {
     "rsrl_hip_set_hidden_states": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rsrl_hip_get_actions": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rsrl_hip_set_actions": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rsrl_hip_get_actions_f32": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rsrl_hip_set_actions_f32": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rsrl_hip_domain_step_f32": (C.c_int, [C.c_void_p] + [C.c_void_p] * 5),
+    "rsrl_hip_handle_f32": (C.c_int, [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]),
+    "rsrl_hip_policy_sample_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rsrl_hip_policy_mode_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rsrl_hip_policy_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "rsrl_hip_policy_pdf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "rsrl_hip_get_episode_steps": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rsrl_hip_set_episode_steps": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rsrl_hip_get_episode_record": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

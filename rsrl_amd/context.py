@@ -7,6 +7,7 @@ import numpy as np
 from . import _abi
 
 MOUNTAIN_CAR, CART_POLE, ACROBOT, HIV_TREATMENT = 0, 1, 2, 3
+CONTINUOUS_MOUNTAIN_CAR = 4                     # mountain_car/continuous.rs: one f32 action in [-1, 1] (Context.continuous; ILSTD_ACTOR_CRITIC with BETA only)
 FOURIER, TILE_CODING = 0, 1
 QLEARNING, SARSA, EXPECTED_SARSA, SARSA_LAMBDA, Q_LAMBDA, PAL, GREEDY_GQ, TD, TD_LAMBDA, Q_SIGMA = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 ACTOR_CRITIC, Q_ACTOR_CRITIC = 10, 11          # ActorCritic (control/ac.rs) with a Gibbs actor and a SARSA critic: a2c.rs's closure / QCritic
@@ -18,6 +19,7 @@ GRADIENT_MC = 23                               # (22 is no algo) prediction/mc.r
 LSTD, LSTD_LAMBDA = 25, 26                      # (24 is no algo) prediction/lstd: LSTD, LSTDLambda (Handler<&Batch> on whole transitions: handle_transitions; lstd_solve; get/set_lstd_batch_state)
 TRACE_ACCUMULATE, TRACE_SATURATE, TRACE_DUTCH = 0, 1, 2
 GREEDY, EPSILON_GREEDY, SOFTMAX, RANDOM = 0, 1, 2, 3
+BETA = 4                                        # policies/beta.rs over two Softplus-composed scalar LFAs: ILSTD_ACTOR_CRITIC on CONTINUOUS_MOUNTAIN_CAR
 W_PER_ENV, W_SHARED = 0, 1
 W_F32, W_BF16 = 0, 1
 EXCHANGE_RCCL, EXCHANGE_PEER, EXCHANGE_AUTO = 0, 1, 2
@@ -118,6 +120,9 @@ class Context:
         self.A = self._L.rsrl_hip_n_actions(self._h)
         self.n_out = self._L.rsrl_hip_n_outputs(self._h)      # weight columns: A, or 1 for TD / TDLambda
         self.F = self._L.rsrl_hip_n_features(self._h)
+        self.n_policy_out = self._L.rsrl_hip_n_policy_outputs(self._h)      # columns of the policy's own weights: A (Gibbs), 2 (BETA), 0 (the policy reads Q)
+        self._policy_cols = self.n_policy_out or self.A                     # (the accessors' array shape; an agent without policy weights is refused by the library)
+        self.continuous = domain == CONTINUOUS_MOUNTAIN_CAR                 # actions are f32 values (the *_f32 entry points), not int32 indices
         self.shared = weight_mode == W_SHARED
 
     # ---- lifetime
@@ -147,6 +152,16 @@ class Context:
         _abi.check(self._L.rsrl_hip_state_bounds(self._h, lo, hi))
         return np.array(lo[:]), np.array(hi[:])
 
+    def action_bounds(self):
+        """action_space() bounds of a continuous domain -> (lo, hi); RsrlHipError on the domains whose actions are indices"""
+        lo, hi = C.c_double(), C.c_double()
+        _abi.check(self._L.rsrl_hip_action_bounds(self._h, C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
+
+    def _act(self):
+        """(dtype, entry-point suffix) of the ctx's actions"""
+        return (np.float32, "_f32") if self.continuous else (np.int32, "")
+
     # ---- env state
     def reset(self):
         _abi.check(self._L.rsrl_hip_reset(self._h))
@@ -173,13 +188,16 @@ class Context:
 
     @property
     def actions(self):
-        out = np.empty(self.N, dtype=np.int32)
-        _abi.check(self._L.rsrl_hip_get_actions(self._h, _p(out)))
+        """the learners' pending actions (N,): int32 indices, or f32 values on a continuous domain"""
+        dt, sfx = self._act()
+        out = np.empty(self.N, dtype=dt)
+        _abi.check(getattr(self._L, "rsrl_hip_get_actions" + sfx)(self._h, _p(out)))
         return out
 
     @actions.setter
     def actions(self, v):
-        _abi.check(self._L.rsrl_hip_set_actions(self._h, _p(_in(v, np.int32, (self.N,)))))
+        dt, sfx = self._act()
+        _abi.check(getattr(self._L, "rsrl_hip_set_actions" + sfx)(self._h, _p(_in(v, dt, (self.N,)))))
 
     @property
     def episode_steps(self):
@@ -225,8 +243,8 @@ class Context:
         nxt = np.empty((self.D, self.N), dtype=np.float32)
         rew = np.empty(self.N, dtype=np.float32)
         term = np.empty(self.N, dtype=np.uint8)
-        _abi.check(self._L.rsrl_hip_domain_step(self._h, _p(_in(actions, np.int32, (self.N,))), _p(frm), _p(nxt),
-                                                _p(rew), _p(term)))
+        dt, sfx = self._act()
+        _abi.check(getattr(self._L, "rsrl_hip_domain_step" + sfx)(self._h, _p(_in(actions, dt, (self.N,))), _p(frm), _p(nxt), _p(rew), _p(term)))
         return frm, nxt, rew, term
 
     def domain_reset(self, mask=None):
@@ -282,9 +300,10 @@ class Context:
         from_states, M = self._batch(from_states)
         to_states, _ = self._batch(to_states)
         td = np.empty(M, dtype=np.float32)
-        _abi.check(self._L.rsrl_hip_handle(self._h, _p(from_states), _p(_in(actions, np.int32, (M,))),
-                                           _p(_in(rewards, np.float32, (M,))), _p(to_states),
-                                           _p(_in(terminal, np.uint8, (M,))), M, _p(td)))
+        dt, sfx = self._act()
+        _abi.check(getattr(self._L, "rsrl_hip_handle" + sfx)(self._h, _p(from_states), _p(_in(actions, dt, (M,))),
+                                                             _p(_in(rewards, np.float32, (M,))), _p(to_states),
+                                                             _p(_in(terminal, np.uint8, (M,))), M, _p(td)))
         return td
 
     def handle_transitions(self, from_states, rewards, to_states, terminal, lengths, td=False, actions=None, T=None):
@@ -317,19 +336,36 @@ class Context:
     def policy_sample(self, states=None):
         """Policy::sample.  states = None: the ctx's OWN envs (env.emit().state()) -- the driver loop's behaviour sample of the current batch-step
         (what rsrl_hip_train draws); the actions also become the ctx's pending ones"""
+        dt, sfx = self._act()
+        sample = getattr(self._L, "rsrl_hip_policy_sample" + sfx)
         if states is None:
-            out = np.empty(self.N, dtype=np.int32)
-            _abi.check(self._L.rsrl_hip_policy_sample(self._h, None, self.N, _p(out)))
+            out = np.empty(self.N, dtype=dt)
+            _abi.check(sample(self._h, None, self.N, _p(out)))
             return out
         states, M = self._batch(states)
-        out = np.empty(M, dtype=np.int32)
-        _abi.check(self._L.rsrl_hip_policy_sample(self._h, _p(states), M, _p(out)))
+        out = np.empty(M, dtype=dt)
+        _abi.check(sample(self._h, _p(states), M, _p(out)))
         return out
 
     def policy_mode(self, states):
+        dt, sfx = self._act()
         states, M = self._batch(states)
-        out = np.empty(M, dtype=np.int32)
-        _abi.check(self._L.rsrl_hip_policy_mode(self._h, _p(states), M, _p(out)))
+        out = np.empty(M, dtype=dt)
+        _abi.check(getattr(self._L, "rsrl_hip_policy_mode" + sfx)(self._h, _p(states), M, _p(out)))
+        return out
+
+    def policy_params(self, states):
+        """BETA's pub compute_alpha / compute_beta -> (alpha (M,), beta (M,)): state i against learner i's columns"""
+        states, M = self._batch(states)
+        a, b = np.empty(M, dtype=np.float32), np.empty(M, dtype=np.float32)
+        _abi.check(self._L.rsrl_hip_policy_params(self._h, _p(states), M, _p(a), _p(b)))
+        return a, b
+
+    def policy_pdf(self, states, actions):
+        """BETA's Function<(S, A)>: the density of actions (M,) f32, each clamped to [2^-24, 1 - 2^-24]"""
+        states, M = self._batch(states)
+        out = np.empty(M, dtype=np.float32)
+        _abi.check(self._L.rsrl_hip_policy_pdf(self._h, _p(states), _p(_in(actions, np.float32, (M,))), M, _p(out)))
         return out
 
     def policy_probs(self, states):
@@ -383,13 +419,13 @@ class Context:
 
     def get_policy_weights(self, env_index=0):
         """ActorCritic.policy's weights theta of one learner (the Gibbs actor, ac.rs:61), f32 (F, A) -- also for TD_ACTOR_CRITIC, whose
-        get_weights is V's (F, 1); RsrlHipError on the other agents"""
-        out = np.empty((self.F, self.A), dtype=np.float32)
+        get_weights is V's (F, 1) -- and BETA's two columns (F, 2), alpha's then beta's; RsrlHipError on the other agents"""
+        out = np.empty((self.F, self._policy_cols), dtype=np.float32)
         _abi.check(self._L.rsrl_hip_get_policy_weights(self._h, int(env_index), _p(out)))
         return out
 
     def set_policy_weights(self, theta, env_index=0):
-        _abi.check(self._L.rsrl_hip_set_policy_weights(self._h, int(env_index), _p(_in(theta, np.float32, (self.F, self.A)))))
+        _abi.check(self._L.rsrl_hip_set_policy_weights(self._h, int(env_index), _p(_in(theta, np.float32, (self.F, self._policy_cols)))))
 
     def get_behaviour_weights(self, env_index=0):
         """REINFORCE's behaviour snapshot theta_b of one learner: its policy weights when the open episode began, f32 (F, A)"""

@@ -44,7 +44,7 @@ static AgentFamily classify(const rsrl_hip_config& cfg, size_t w_elems) {
     if (is_tdac(al)) return F::TdAcReg;                     // (before the prediction agents: W is V's one column, but the policy is the actor's)
     if (is_reinforce(al)) return F::ReinforceReg;
     if (is_lstd(al)) return F::LstdReg;
-    if (is_tdac_lstd(al)) return F::TdAcLstdReg;
+    if (is_tdac_lstd(al)) return cfg.domain == RSRL_CONTINUOUS_MOUNTAIN_CAR ? F::TdAcBetaReg : F::TdAcLstdReg;
     if (is_gmc(al)) return F::GmcReg;
     if (is_lstd_batch(al)) return F::LstdBatchReg;
     if (cfg.weight_mode == RSRL_W_SHARED) return fourier ? F::SharedDense : (is_sparse_lambda(cfg) ? F::SharedSparseLambda : F::SharedTile);
@@ -80,6 +80,7 @@ static size_t stat_slots(Slots geometry, int64_t N, int F) {
 // MEMBER, not its value: rsrl_hip_load_weights switches W, Z, sp_keys and sp_vals to shadow copies and frees the old ones itself
 template <class T>
 static int ctx_alloc(rsrl_hip_ctx* c, T** member, size_t bytes, bool zero = false) {
+    if (bytes == 0) { *member = nullptr; return RSRL_HIP_OK; }      // (a continuous ctx's [A][N] arrays: A = 0)
     HIP_TRY(hipMalloc((void**)member, bytes));
     c->owned.push_back((void**)member);
     if (zero) HIP_TRY(hipMemsetAsync(*member, 0, bytes, c->stream));
@@ -161,20 +162,33 @@ static int check_reg_only(const rsrl_hip_config& cfg, const AlgoRow& a, bool sto
     return RSRL_HIP_OK;
 }
 
-// (state dimension, action count) of MountainCar, CartPole, Acrobot, HIVTreatment
-static const int kDomainShape[4][2] = {{2, 3}, {4, 2}, {4, 3}, {6, 4}};
+// (state dimension, action count) of MountainCar, CartPole, Acrobot, HIVTreatment, ContinuousMountainCar (0: the action set is not enumerable)
+static const int kDomainShape[5][2] = {{2, 3}, {4, 2}, {4, 3}, {6, 4}, {2, 0}};
+
+// ContinuousMountainCar and the Beta policy (train_tdac_beta.hip): each exists for the other only, under the iLSTD ActorCritic
+static int check_continuous(const rsrl_hip_config& cfg, const AlgoRow& a, bool storage) {
+    if (cfg.domain != RSRL_CONTINUOUS_MOUNTAIN_CAR || cfg.policy != RSRL_BETA || cfg.algo != RSRL_ILSTD_ACTOR_CRITIC || !storage || cfg.agent_policy != -1)
+        return fail(RSRL_HIP_EINVAL, "ContinuousMountainCar (RSRL_CONTINUOUS_MOUNTAIN_CAR) and the Beta policy (RSRL_BETA) support the iLSTD ActorCritic "
+                                     "(RSRL_ILSTD_ACTOR_CRITIC) with policy = Beta on ContinuousMountainCar, Fourier orders 1-5, per-learner f32 weights, "
+                                     "agent_policy = -1 and no epsilon schedule -- and nothing else (got domain %d, basis %d, order %d, algo %d, weight mode %d, "
+                                     "dtype %d, policy %d, agent_policy %d, epsilon_decay %g)",
+                    cfg.domain, cfg.basis, cfg.order, cfg.algo, cfg.weight_mode, cfg.weight_dtype, cfg.policy, cfg.agent_policy, cfg.epsilon_decay);
+    if (cfg.n_steps < 1 || cfg.n_steps > 32)
+        return fail(RSRL_HIP_EINVAL, "%s: n_steps (%sn_updates, the rounds of solve() per transition) must be in [1, 32], got %d", a.name, a.n_updates, cfg.n_steps);
+    return RSRL_HIP_OK;
+}
 
 // admission: every rule that needs no device (a refused configuration is EINVAL on any machine, with or without a GPU).  create_impl checks
 // two more once the device is known: peer_timeout_ms, and the slice of a shared tile table with sparse traces.  The second section states
 // which kernels exist, one block per agent group; the register-family-only agents (check_reg_only) and HIVTreatment are whole rules of their own.
 static int check_config(const rsrl_hip_config& cfg) {
     // ---- field ranges
-    if (cfg.domain < RSRL_MOUNTAIN_CAR || cfg.domain > RSRL_HIV_TREATMENT) return fail(RSRL_HIP_EINVAL, "unknown domain %d", cfg.domain);
+    if (cfg.domain < RSRL_MOUNTAIN_CAR || cfg.domain > RSRL_CONTINUOUS_MOUNTAIN_CAR) return fail(RSRL_HIP_EINVAL, "unknown domain %d", cfg.domain);
     const int D = kDomainShape[cfg.domain][0], A = kDomainShape[cfg.domain][1];
     if (cfg.n_envs < 1) return fail(RSRL_HIP_EINVAL, "n_envs must be >= 1");
     if (cfg.n_envs + cfg.env_offset > (int64_t)0xffffffffLL || cfg.env_offset < 0) return fail(RSRL_HIP_EINVAL, "global env ids must fit 32 bits");
     if (cfg.algo < 0 || cfg.algo > RSRL_LSTD_LAMBDA || !kAlgo[cfg.algo].name) return fail(RSRL_HIP_EINVAL, "unknown algo %d", cfg.algo);
-    if (cfg.policy < 0 || cfg.policy > RSRL_RANDOM) return fail(RSRL_HIP_EINVAL, "unknown policy %d", cfg.policy);
+    if (cfg.policy < 0 || cfg.policy > RSRL_BETA) return fail(RSRL_HIP_EINVAL, "unknown policy %d", cfg.policy);
     // Softmax::new panics for |tau| < 1e-7 (policies/softmax.rs:63-66)
     if (cfg.policy == RSRL_SOFTMAX && std::fabs(cfg.tau) < 1e-7) return fail(RSRL_HIP_EINVAL, "Tau parameter in Softmax must be non-zero.");
     // the reference admits any non-zero tau; the kernels evaluate the max-shifted form exp((q - max q) / tau), whose exponents are >= 0 for tau < 0
@@ -215,6 +229,8 @@ static int check_config(const rsrl_hip_config& cfg) {
     const bool tile = cfg.basis == RSRL_TILE_CODING, reg = is_reg_fourier(cfg), wave = is_wave(cfg);
     const bool f32 = cfg.weight_dtype == RSRL_W_F32, esched = cfg.epsilon_decay != 1.0;
     const bool one_step = kAlgo[al].agent == Agent::OneStep;
+    if (cfg.domain == RSRL_CONTINUOUS_MOUNTAIN_CAR || cfg.policy == RSRL_BETA)
+        return check_continuous(cfg, kAlgo[al], is_cmc_fourier(cfg) && per_env && f32 && !esched);
     if (kAlgo[al].reg_policy >= 0) return check_reg_only(cfg, kAlgo[al], reg && per_env && f32 && !esched);
     if (cfg.domain == RSRL_HIV_TREATMENT) {
         // train_hiv.hip: the one-step agents over the Fourier basis of order 1-3, per-learner f32 weights, one epsilon for the ctx
@@ -275,6 +291,7 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
     c->w_stride = shared ? 1 : N;
     const AlgoRow& agent = kAlgo[cfg->algo];
     c->Aw = agent.v ? 1 : c->A;
+    c->Ap = cfg->policy == RSRL_BETA ? 2 : (agent.reg_policy == RSRL_SOFTMAX ? c->A : 0);
     c->w_elems = (size_t)c->Aw * c->F * (size_t)(shared ? 1 : N);
     c->family = classify(*cfg, c->w_elems);
     // a ctx that steps one batch-step per launch streams W every step: learner-major rows (W[N][A][F]) let k_step_reg_lm
@@ -300,6 +317,7 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
     c->n_stat_slots = stat_slots(c->k1_quad ? Slots::Block64 : family_row(c).slots, N, c->F);
     TRY(ctx_alloc(c, &c->state, sizeof(float) * c->D * (size_t)N));
     TRY(ctx_alloc(c, &c->action, sizeof(int32_t) * (size_t)N));
+    if (is_continuous(c)) TRY(ctx_alloc(c, &c->action_f, sizeof(float) * (size_t)N, true));
     TRY(ctx_alloc(c, &c->ep_step, sizeof(uint32_t) * (size_t)N));
     c->w_bytes = c->w_elems * (cfg->weight_dtype == RSRL_W_BF16 ? 2 : 4);
     TRY(ctx_alloc(c, &c->W, c->w_bytes));
@@ -333,7 +351,7 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
         if (c->sp_lds && slice * 8 > 64 * 1024) c->sp_lds = sparse_trace_scatter_allow_lds(cfg->n_tilings, (int)(slice * 8));      // more dynamic LDS than a kernel gets by default
     } else if (agent.aux != Aux::None) {
         // Trace::zeros; the policy's theta (LFA::vector zero-initialises): of W's shape, or A columns next to V's one
-        c->z_bytes = (agent.aux == Aux::Policy ? (size_t)c->A * c->F * (size_t)N : c->w_elems) * 4;
+        c->z_bytes = (agent.aux == Aux::Policy ? (size_t)c->Ap * c->F * (size_t)N : c->w_elems) * 4;
         TRY(ctx_alloc(c, &c->Z, c->z_bytes, true));
     }
     if (agent.episode) {      // REINFORCE: theta_b of theta's shape, zero as it is; g = 0
@@ -433,6 +451,7 @@ int rsrl_hip_sync(rsrl_hip_ctx* c) {
 int rsrl_hip_state_dim(const rsrl_hip_ctx* c) { return c ? c->D : RSRL_HIP_EINVAL; }
 int rsrl_hip_n_actions(const rsrl_hip_ctx* c) { return c ? c->A : RSRL_HIP_EINVAL; }
 int rsrl_hip_n_outputs(const rsrl_hip_ctx* c) { return c ? c->Aw : RSRL_HIP_EINVAL; }
+int rsrl_hip_n_policy_outputs(const rsrl_hip_ctx* c) { return c ? c->Ap : RSRL_HIP_EINVAL; }
 int rsrl_hip_n_features(const rsrl_hip_ctx* c) { return c ? c->F : RSRL_HIP_EINVAL; }
 int64_t rsrl_hip_n_envs(const rsrl_hip_ctx* c) { return c ? c->cfg.n_envs : RSRL_HIP_EINVAL; }
 uint64_t rsrl_hip_step_count(const rsrl_hip_ctx* c) { return c ? c->t + (uint64_t)c->pending : 0; }
@@ -446,9 +465,18 @@ int rsrl_hip_state_bounds(const rsrl_hip_ctx* c, double* lo, double* hi) {
         case 0: lo[i] = Domain<0>::lo_d(i); hi[i] = Domain<0>::hi_d(i); break;
         case 1: lo[i] = Domain<1>::lo_d(i); hi[i] = Domain<1>::hi_d(i); break;
         case 2: lo[i] = Domain<2>::lo_d(i); hi[i] = Domain<2>::hi_d(i); break;
+        case 4: lo[i] = Domain<4>::lo_d(i); hi[i] = Domain<4>::hi_d(i); break;
         default: lo[i] = -5.0; hi[i] = 8.0; break;            // HIVTreatment: LIMITS of every observation component (hiv.rs:34, :137-145)
         }
     }
+    return RSRL_HIP_OK;
+}
+
+int rsrl_hip_action_bounds(const rsrl_hip_ctx* c, double* lo, double* hi) {
+    CHECK_CTX(c);
+    if (!lo || !hi) return fail(RSRL_HIP_EINVAL, "null argument");
+    if (!is_continuous(c)) return fail(RSRL_HIP_EINVAL, "domain %d has a finite action set (rsrl_hip_n_actions = %d indices): only ContinuousMountainCar has action bounds", c->cfg.domain, c->A);
+    *lo = Domain<4>::action_lo(); *hi = Domain<4>::action_hi();
     return RSRL_HIP_OK;
 }
 
@@ -499,7 +527,9 @@ int rsrl_hip_reset(rsrl_hip_ctx* c) {
     if (c->family == AgentFamily::ReinforceReg) { launch_reinforce_restart(c->stream, make_reinforce(c), c->cfg.n_envs, (int64_t)c->F * c->A, nullptr); KCHECK(); }
     const Common k = make_policy_common(c);              // the initial policy.sample (ActorCritic: the actor's theta)
     const BasisGeom g = make_geom(c);
-    if (c->family == AgentFamily::Hiv) {
+    if (c->family == AgentFamily::TdAcBetaReg) {      // (both agents' state is untouched: the initial sample reads the policy's columns)
+        if (!launch_beta_reset(c->cfg.order, c->stream, k, c->Z, c->t, c->action_f)) return NO_MODEL(c);
+    } else if (c->family == AgentFamily::Hiv) {
         launch_hiv_reset(c->stream, k, g, c->hiv_y, c->t);
     } else if (is_v_only(c->cfg.algo)) {       // (the LSTD agents' state is untouched: the weights are not reset either; GradientMC's records empty with ep_step = 0)
         if (!launch_reset_td(c->cfg.domain, dim3(grid_for(k.n_envs)), dim3(kBlock), c->stream, k, c->t)) return NO_MODEL(c);
@@ -568,6 +598,7 @@ int rsrl_hip_set_hidden_states(rsrl_hip_ctx* c, const double* y) {
 }
 int rsrl_hip_get_actions(rsrl_hip_ctx* c, int32_t* actions) {
     CHECK_CTX(c); FLUSH(c); if (!actions) return fail(RSRL_HIP_EINVAL, "null argument");
+    NEEDS_INDEX_ACTIONS(c, "rsrl_hip_get_actions");
     HIP_TRY(hipSetDevice(c->cfg.device));
     HIP_TRY(hipMemcpyAsync(actions, c->action, sizeof(int32_t) * (size_t)c->cfg.n_envs, hipMemcpyDefault, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -575,10 +606,31 @@ int rsrl_hip_get_actions(rsrl_hip_ctx* c, int32_t* actions) {
 }
 int rsrl_hip_set_actions(rsrl_hip_ctx* c, const int32_t* actions) {
     CHECK_CTX(c); FLUSH(c); if (!actions) return fail(RSRL_HIP_EINVAL, "null argument");
+    NEEDS_INDEX_ACTIONS(c, "rsrl_hip_set_actions");
     HIP_TRY(hipSetDevice(c->cfg.device));
     TRY(check_host_actions(actions, (size_t)c->cfg.n_envs, c->A));
     HIP_TRY(hipMemcpyAsync(c->action, actions, sizeof(int32_t) * (size_t)c->cfg.n_envs, hipMemcpyDefault, c->stream));
     hipLaunchKernelGGL(k_clamp_actions, dim3(grid_for(c->cfg.n_envs)), dim3(kBlock), 0, c->stream, c->action, c->cfg.n_envs, c->A);
+    KCHECK();
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RSRL_HIP_OK;
+}
+// the f32 twins (a continuous ctx's pending actions)
+int rsrl_hip_get_actions_f32(rsrl_hip_ctx* c, float* actions) {
+    CHECK_CTX(c); FLUSH(c); if (!actions) return fail(RSRL_HIP_EINVAL, "null argument");
+    NEEDS_F32_ACTIONS(c, "rsrl_hip_get_actions");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(hipMemcpyAsync(actions, c->action_f, sizeof(float) * (size_t)c->cfg.n_envs, hipMemcpyDefault, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RSRL_HIP_OK;
+}
+int rsrl_hip_set_actions_f32(rsrl_hip_ctx* c, const float* actions) {
+    CHECK_CTX(c); FLUSH(c); if (!actions) return fail(RSRL_HIP_EINVAL, "null argument");
+    NEEDS_F32_ACTIONS(c, "rsrl_hip_set_actions");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    TRY(check_host_actions_f32(actions, (size_t)c->cfg.n_envs, true));
+    HIP_TRY(hipMemcpyAsync(c->action_f, actions, sizeof(float) * (size_t)c->cfg.n_envs, hipMemcpyDefault, c->stream));
+    launch_cmc_clamp_actions(c->stream, c->action_f, c->cfg.n_envs);
     KCHECK();
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RSRL_HIP_OK;

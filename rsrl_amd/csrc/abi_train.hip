@@ -426,6 +426,9 @@ int launch_agent(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, uint64_t 
     case AgentFamily::LstdBatchReg:      // (io: rsrl_hip_handle refuses the agents before it gets here; rsrl_hip_handle_transitions launches its own)
         ok = !io && launch_lstd_batch(cf.domain, cf.order, cf.algo == RSRL_LSTD_LAMBDA, c->stream, k, make_lstd_batch(c), t, chunk, d_stats, nullptr);
         break;
+    case AgentFamily::TdAcBetaReg:       // (io: the int32 rsrl_hip_handle refuses a continuous ctx before it gets here; rsrl_hip_handle_f32 launches its own)
+        ok = !io && launch_tdac_beta(cf.order, c->stream, k, make_tdac_beta(c), t, chunk, d_stats, nullptr);
+        break;
     default: ok = false; break;      // (the shared-W families: enqueue_shared_step)
     }
     if (!ok) return NO_MODEL(c);
@@ -584,6 +587,22 @@ static int rollout_impl(rsrl_hip_ctx* c, int64_t step_limit, int64_t M, uint32_t
     }
     if (step_limit < 1) return fail(RSRL_HIP_EINVAL, "step_limit must be >= 1, or 0 for no limit (bounded by config.max_episode_steps)");
     if (M < 1 || M > c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "bad batch (M=%lld, n_envs=%lld)", (long long)M, (long long)c->cfg.n_envs);
+    if (is_continuous(c)) {
+        // Domain::rollout(|s| policy.mode(s)) (tdac_beta.rs:66): rsrl_hip_rollout_greedy only -- a trajectory's actions are int32 indices
+        if (rp.sample || states_out || actions_out || rewards_out || terminal_out || M != c->cfg.n_envs)
+            return fail(RSRL_HIP_ESTATE, "rsrl_hip_rollout_trajectory and rsrl_hip_rollout_policy write int32 action indices: this ctx's domain (ContinuousMountainCar) "
+                                         "has one f32 action -- rsrl_hip_rollout_greedy runs policy.mode");
+        HIP_TRY(hipSetDevice(c->cfg.device));
+        OutBuf<uint32_t> on; OutBuf<float> ot;
+        TRY(stage_out(c, 0, n_states_out, (size_t)M, &on));
+        TRY(stage_out(c, 1, total_reward_out, (size_t)M, &ot));
+        if (!launch_beta_rollout_mode(c->cfg.order, c->stream, make_common(c), c->Z, step_limit, on.dev, ot.dev)) return NO_MODEL(c);
+        KCHECK();
+        bool sync = false;
+        TRY(flush_out(c, &on, &sync)); TRY(flush_out(c, &ot, &sync));
+        if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
+        return RSRL_HIP_OK;
+    }
     if (is_v_only(c->cfg.algo))          // (W is one column: the model kernels below would read A of them)
         return fail(RSRL_HIP_ESTATE, "a prediction agent has a state-value function only: no action values to roll out with");
     if (!rp.sample && c->cfg.policy == RSRL_RANDOM) return fail(RSRL_HIP_EINVAL, "Random policy has no mode.");

@@ -19,6 +19,7 @@ int launch_domain_step(rsrl_hip_ctx* c, const Common& k, const int32_t* d_act, f
     switch (c->cfg.domain) {
     case 0: hipLaunchKernelGGL(k_domain_step<0>, g, b, 0, c->stream, k, d_act, from, next, rew, term); break;
     case 1: hipLaunchKernelGGL(k_domain_step<1>, g, b, 0, c->stream, k, d_act, from, next, rew, term); break;
+    case RSRL_CONTINUOUS_MOUNTAIN_CAR: return fail(RSRL_HIP_ESTATE, "ContinuousMountainCar steps on f32 actions (rsrl_hip_domain_step_f32)");
     default: hipLaunchKernelGGL(k_domain_step<2>, g, b, 0, c->stream, k, d_act, from, next, rew, term); break;
     }
     KCHECK();
@@ -28,7 +29,8 @@ int launch_domain_reset(rsrl_hip_ctx* c, const Common& k, const uint8_t* d_mask)
     const dim3 g(grid_for(c->cfg.n_envs)), b(kBlock);
     if (c->hiv_y) { launch_hiv_domain_reset(c->stream, k, c->hiv_y, d_mask); KCHECK(); return RSRL_HIP_OK; }
     switch (c->cfg.domain) {
-    case 0: hipLaunchKernelGGL(k_domain_reset<0>, g, b, 0, c->stream, k, d_mask); break;
+    case 0: case RSRL_CONTINUOUS_MOUNTAIN_CAR:      // (ContinuousMountainCar: MountainCar's state space and start state)
+        hipLaunchKernelGGL(k_domain_reset<0>, g, b, 0, c->stream, k, d_mask); break;
     case 1: hipLaunchKernelGGL(k_domain_reset<1>, g, b, 0, c->stream, k, d_mask); break;
     default: hipLaunchKernelGGL(k_domain_reset<2>, g, b, 0, c->stream, k, d_mask); break;
     }
@@ -75,6 +77,7 @@ RSRL_API_BEGIN
 int rsrl_hip_domain_step(rsrl_hip_ctx* c, const int32_t* actions, float* from_states, float* next_states,
                          float* rewards, uint8_t* terminal) {
     CHECK_CTX(c); FLUSH(c);
+    NEEDS_INDEX_ACTIONS(c, "rsrl_hip_domain_step");
     c->q_valid = false;
     HIP_TRY(hipSetDevice(c->cfg.device));
     // the trait-granular loop on a ctx-owned stream: a transition handed over in device arrays is ACCEPTED here and launched with the calls that
@@ -124,6 +127,10 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
                size_t icount = 0, const float* fin = nullptr, size_t fin_count = 0, const int32_t* iin = nullptr, uint64_t step_t = 0) {
     CHECK_CTX(c); FLUSH(c);
     if (!states || M_ < 1 || M_ > c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "bad batch (M=%lld, n_envs=%lld)", (long long)M_, (long long)c->cfg.n_envs);
+    // a continuous ctx: the value side is V (iLSTD's theta), the projection is MountainCar's; its policy side has entry points of its own
+    if (is_continuous(c) && op != QOP_EVALUATE && op != QOP_FEATURES)
+        return fail(RSRL_HIP_ESTATE, "this ctx's domain (ContinuousMountainCar) has one f32 action, not an enumerable set: no action values to search, weigh or "
+                                     "index, no action probabilities (the policy side: rsrl_hip_policy_sample_f32 / _mode_f32 / _params / _pdf; V(s): rsrl_hip_q_evaluate)");
     if (is_v_only(c->cfg.algo) && op != QOP_EVALUATE && op != QOP_FEATURES)
         return fail(RSRL_HIP_ESTATE, "a prediction agent has a state-value function only (use rsrl_hip_q_evaluate for V(s))");
     // the TD ActorCritic: its value side is V(s) (no action values to search or weigh), its policy side the actor's theta
@@ -150,7 +157,14 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
     if (op == QOP_SAMPLE) c->api_calls++;
     const BasisGeom g = make_geom(c);
     if (has_lstd_state(c) && op == QOP_EVALUATE) {                        // V(s) = f32(phi(s) . theta), in f64 (k_lstd_v)
-        if (!launch_lstd_v(c->cfg.domain, c->cfg.order, c->stream, c->lstd_theta, d_states, M_, of.dev)) return NO_MODEL(c);
+        if (!launch_lstd_v(feature_domain(c), c->cfg.order, c->stream, c->lstd_theta, d_states, M_, of.dev)) return NO_MODEL(c);
+    } else if (is_continuous(c)) {                                        // QOP_FEATURES: MountainCar's projection at the same order
+        bool ok = false;
+#define X(DM, OR) if (DM == RSRL_MOUNTAIN_CAR && c->cfg.order == OR) { \
+            hipLaunchKernelGGL((k_qop<FourierModel<DM, OR>>), dim3(grid_for(M_)), dim3(kBlock), 0, c->stream, k, g, op, d_states, M_, call, of.dev, oi.dev, d_fin, d_iin); ok = true; }
+        RSRL_REG_FOURIER(X)
+#undef X
+        if (!ok) return NO_MODEL(c);
     } else if ((is_pred(c->cfg.algo) || is_tdac(c->cfg.algo) || is_gmc(c->cfg.algo)) && op == QOP_EVALUATE) {      // V(s) (the TD ActorCritic, GradientMC: their w, k_v_evaluate)
         bool ok = true;
         switch (c->family) {
@@ -205,6 +219,7 @@ int rsrl_hip_q_find_max(rsrl_hip_ctx* c, const float* states, int64_t M, int32_t
 // states == NULL: policy.sample(rng, env.emit().state()) for the ctx's OWN envs (M = n_envs) -- the driver loop's behaviour sample: it draws what
 // batch-step step_count - 1 of rsrl_hip_train draws (the initial sample's stream before the first handle), and the actions also become the ctx's pending ones
 static int sample_emit(rsrl_hip_ctx* c, int64_t M, int32_t* actions_out) {
+    NEEDS_INDEX_ACTIONS(c, "rsrl_hip_policy_sample");
     if (M != c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "policy_sample(states = NULL) samples for the ctx's own envs: M must be n_envs (%lld), got %lld", (long long)c->cfg.n_envs, (long long)M);
     if (is_pred(c->cfg.algo)) return fail(RSRL_HIP_ESTATE, "a prediction agent has a state-value function only (use rsrl_hip_q_evaluate for V(s))");
     const bool dev_out = is_device_ptr(actions_out);
@@ -266,6 +281,7 @@ int rsrl_hip_policy_sample(rsrl_hip_ctx* c, const float* states, int64_t M, int3
     CHECK_CTX(c);
     if (!actions_out) return fail(RSRL_HIP_EINVAL, "null argument");
     if (!states) return sample_emit(c, M, actions_out);
+    NEEDS_INDEX_ACTIONS(c, "rsrl_hip_policy_sample");
     if (trait_fast(c) && M >= 1 && M <= c->cfg.n_envs) {
         // the fast path's sample: a state the hand-over cache holds costs 20 B instead of the learner's 432 B of weights; same bits either way
         FLUSH(c);
@@ -288,6 +304,7 @@ int rsrl_hip_policy_sample(rsrl_hip_ctx* c, const float* states, int64_t M, int3
 int rsrl_hip_policy_mode(rsrl_hip_ctx* c, const float* states, int64_t M, int32_t* actions_out) {
     CHECK_CTX(c);
     if (!actions_out) return fail(RSRL_HIP_EINVAL, "null argument");
+    NEEDS_INDEX_ACTIONS(c, "rsrl_hip_policy_mode");
     if (c->cfg.policy == RSRL_RANDOM) return fail(RSRL_HIP_EINVAL, "Random policy has no mode.");   // random.rs:47
     return qop(c, QOP_MODE, states, M, nullptr, 0, actions_out);
 }
@@ -315,6 +332,7 @@ int rsrl_hip_handle(rsrl_hip_ctx* c, const float* from_states, const int32_t* ac
     CHECK_CTX(c);
     if (!from_states || !actions || !rewards || !to_states || !terminal) return fail(RSRL_HIP_EINVAL, "null argument");
     if (M < 1 || M > c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "bad batch size");
+    NEEDS_INDEX_ACTIONS(c, "rsrl_hip_handle");
     if (c->family == AgentFamily::ReinforceReg)
         return fail(RSRL_HIP_ESTATE, "REINFORCE and BaselineREINFORCE handle whole batches only (Handler<&Batch>): use rsrl_hip_handle_batch");
     if (c->family == AgentFamily::GmcReg)
@@ -419,6 +437,122 @@ int rsrl_hip_handle(rsrl_hip_ctx* c, const float* from_states, const int32_t* ac
     TRY(flush_out(c, &otd, &sync));
     if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
     return RSRL_HIP_OK;
+}
+
+// ---- f32 actions: the twins of the calls above for a continuous ctx (ContinuousMountainCar with the Beta policy; kernels_tdac_beta.hpp)
+int rsrl_hip_domain_step_f32(rsrl_hip_ctx* c, const float* actions, float* from_states, float* next_states, float* rewards, uint8_t* terminal) {
+    CHECK_CTX(c); FLUSH(c);
+    NEEDS_F32_ACTIONS(c, "rsrl_hip_domain_step");
+    c->q_valid = false;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    const int64_t N = c->cfg.n_envs; const size_t DN = (size_t)c->D * N;
+    const float* d_act; OutBuf<float> ofrom, onext, orew; OutBuf<uint8_t> oterm;
+    TRY(check_host_actions_f32(actions, (size_t)N, false));      // (Domain::transition maps the action onto its bounds itself)
+    TRY(stage_in(c, 0, actions, (size_t)N, &d_act));
+    TRY(stage_out(c, 1, from_states, DN, &ofrom));
+    TRY(stage_out(c, 2, next_states, DN, &onext));
+    TRY(stage_out(c, 3, rewards, (size_t)N, &orew));
+    TRY(stage_out(c, 4, terminal, (size_t)N, &oterm));
+    const Common k = make_common(c);
+    launch_cmc_domain_step(c->stream, k, d_act, c->action_f, ofrom.dev, onext.dev, orew.dev, oterm.dev);
+    KCHECK();
+    bool sync = false;
+    TRY(flush_out(c, &ofrom, &sync)); TRY(flush_out(c, &onext, &sync));
+    TRY(flush_out(c, &orew, &sync)); TRY(flush_out(c, &oterm, &sync));
+    if (sync || (actions && !is_device_ptr(actions))) HIP_TRY(hipStreamSynchronize(c->stream));
+    return RSRL_HIP_OK;
+}
+
+int rsrl_hip_handle_f32(rsrl_hip_ctx* c, const float* from_states, const float* actions, const float* rewards, const float* to_states,
+                        const uint8_t* terminal, int64_t M, float* td_error_out) {
+    CHECK_CTX(c);
+    if (!from_states || !actions || !rewards || !to_states || !terminal) return fail(RSRL_HIP_EINVAL, "null argument");
+    if (M < 1 || M > c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "bad batch size");
+    NEEDS_F32_ACTIONS(c, "rsrl_hip_handle");
+    FLUSH(c);
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    TRY(check_host_actions_f32(actions, (size_t)M, false));      // (the update clamps the action to the sample's interval)
+    TransitionsF32 io;
+    OutBuf<float> otd;
+    const bool all_device = is_device_ptr(from_states) && is_device_ptr(actions) && is_device_ptr(rewards) && is_device_ptr(to_states) && is_device_ptr(terminal) &&
+                            (!td_error_out || is_device_ptr(td_error_out));
+    TRY(stage_in(c, 0, from_states, (size_t)c->D * M, &io.from));
+    TRY(stage_in(c, 1, actions, (size_t)M, &io.act));
+    TRY(stage_in(c, 2, rewards, (size_t)M, &io.rew));
+    TRY(stage_in(c, 3, to_states, (size_t)c->D * M, &io.to));
+    TRY(stage_in(c, 4, terminal, (size_t)M, &io.term));
+    TRY(stage_out(c, 5, td_error_out, (size_t)M, &otd));
+    io.M = M; io.td_out = otd.dev;
+    const Common k = make_common(c);
+    if (!launch_tdac_beta(c->cfg.order, c->stream, k, make_tdac_beta(c), c->t, 1, nullptr, &io)) return NO_MODEL(c);
+    KCHECK();
+    c->q_valid = false;
+    c->t += 1;          // one handle call = one batch-step, as rsrl_hip_handle
+    bool sync = !all_device;
+    TRY(flush_out(c, &otd, &sync));
+    if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
+    return RSRL_HIP_OK;
+}
+
+// the policy side on explicit states (or, for the sample, the ctx's own envs): one launch of k_beta_policy
+static int beta_op(rsrl_hip_ctx* c, int op, const float* states, int64_t M, uint64_t t, uint32_t purpose, const float* act_in, float* out0, float* out1, float* keep) {
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    const float* d_states; const float* d_act; OutBuf<float> o0, o1;
+    TRY(stage_in(c, 0, states, (size_t)c->D * M, &d_states));
+    TRY(stage_in(c, 3, act_in, (size_t)M, &d_act));
+    TRY(stage_out(c, 1, out0, (size_t)M, &o0));
+    TRY(stage_out(c, 2, out1, (size_t)M, &o1));
+    const Common k = make_common(c);
+    if (!launch_beta_policy(c->cfg.order, c->stream, k, c->Z, op, d_states, M, t, purpose, d_act, o0.dev, o1.dev, keep)) return NO_MODEL(c);
+    KCHECK();
+    bool sync = (states && !is_device_ptr(states)) || (act_in && !is_device_ptr(act_in));
+    TRY(flush_out(c, &o0, &sync)); TRY(flush_out(c, &o1, &sync));
+    if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
+    return RSRL_HIP_OK;
+}
+static int beta_batch(rsrl_hip_ctx* c, const float* states, int64_t M) {
+    if (!states || M < 1 || M > c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "bad batch (M=%lld, n_envs=%lld)", (long long)M, (long long)c->cfg.n_envs);
+    return RSRL_HIP_OK;
+}
+int rsrl_hip_policy_sample_f32(rsrl_hip_ctx* c, const float* states, int64_t M, float* actions_out) {
+    CHECK_CTX(c);
+    if (!actions_out) return fail(RSRL_HIP_EINVAL, "null argument");
+    NEEDS_F32_ACTIONS(c, "rsrl_hip_policy_sample");
+    FLUSH(c);
+    if (!states) {
+        // the ctx's OWN envs: the driver loop's behaviour sample -- what batch-step step_count - 1 of rsrl_hip_train draws (the initial sample's
+        // stream before the first handle) --, and the actions become the ctx's pending ones
+        if (M != c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "policy_sample(states = NULL) samples for the ctx's own envs: M must be n_envs (%lld), got %lld", (long long)c->cfg.n_envs, (long long)M);
+        return beta_op(c, BETA_OP_SAMPLE, nullptr, M, c->t ? c->t - 1 : 0, c->t ? BLK_STEP : BLK_INIT, nullptr, actions_out, nullptr, c->action_f);
+    }
+    TRY(beta_batch(c, states, M));
+    return beta_op(c, BETA_OP_SAMPLE, states, M, c->api_calls++, BLK_API, nullptr, actions_out, nullptr, nullptr);
+}
+int rsrl_hip_policy_mode_f32(rsrl_hip_ctx* c, const float* states, int64_t M, float* actions_out) {
+    CHECK_CTX(c);
+    if (!actions_out) return fail(RSRL_HIP_EINVAL, "null argument");
+    NEEDS_F32_ACTIONS(c, "rsrl_hip_policy_mode");
+    FLUSH(c);
+    TRY(beta_batch(c, states, M));
+    return beta_op(c, BETA_OP_MODE, states, M, 0, 0, nullptr, actions_out, nullptr, nullptr);
+}
+static const char* const kNoBetaPolicy = "only the Beta policy (RSRL_BETA, on ContinuousMountainCar) has shape parameters and a density";
+int rsrl_hip_policy_params(rsrl_hip_ctx* c, const float* states, int64_t M, float* alpha_out, float* beta_out) {
+    CHECK_CTX(c);
+    if (!alpha_out || !beta_out) return fail(RSRL_HIP_EINVAL, "null argument");
+    if (!is_continuous(c)) return fail(RSRL_HIP_ESTATE, "%s", kNoBetaPolicy);
+    FLUSH(c);
+    TRY(beta_batch(c, states, M));
+    return beta_op(c, BETA_OP_PARAMS, states, M, 0, 0, nullptr, alpha_out, beta_out, nullptr);
+}
+int rsrl_hip_policy_pdf(rsrl_hip_ctx* c, const float* states, const float* actions, int64_t M, float* out) {
+    CHECK_CTX(c);
+    if (!actions || !out) return fail(RSRL_HIP_EINVAL, "null argument");
+    if (!is_continuous(c)) return fail(RSRL_HIP_ESTATE, "%s", kNoBetaPolicy);
+    FLUSH(c);
+    TRY(beta_batch(c, states, M));
+    TRY(check_host_actions_f32(actions, (size_t)M, false));
+    return beta_op(c, BETA_OP_PDF, states, M, 0, 0, actions, out, nullptr, nullptr);
 }
 
 int rsrl_hip_handle_batch(rsrl_hip_ctx* c, int64_t T, const float* states, const int32_t* actions, const float* rewards, const uint32_t* lengths,

@@ -220,7 +220,7 @@ struct CkptKind {
     bool reads_kind0;            // a ctx of this kind also reads its configuration's version-2 / aux_kind-0 file, written before the kind's own section
     SectionId sections[3];       // travelled: the weights load, that section's state starts empty
 };
-constexpr int kCkptKinds = 11;
+constexpr int kCkptKinds = 12;
 constexpr CkptKind kCkptKind[kCkptKinds] = {
     /* 0 weights only                           */ {2, 0, true, false, {S_WEIGHTS}},
     /* 1 eligibility traces                     */ {2, 0, true, false, {S_WEIGHTS, S_AUX}},
@@ -233,9 +233,11 @@ constexpr CkptKind kCkptKind[kCkptKinds] = {
     /* 8 the LSTD agents' f64 state             */ {10, 0, false, false, {S_LSTD}},
     /* 9 the iLSTD ActorCritic: f64 state, theta */ {10, 0, false, false, {S_LSTD, S_AUX}},      // (version 10 too: the aux_kind tells the two apart)
     /* 10 LSTD / LSTDLambda: f64 theta, A, b, z  */ {10, 0, false, false, {S_LSTD, S_LSTD_BATCH}},      // (version 10 as well; S_LSTD: theta, A, then b in mu's place)
+    /* 11 the Beta iLSTD ActorCritic: f64 state, the policy's two columns */ {10, 0, false, false, {S_LSTD, S_AUX}},      // (kind 9's sections with f32[F][2] behind them)
 };
-// (the one kind the configuration decides, not the algo: SARSALambda / QLambda over ONE shared tile table keep sparse traces instead of Z)
-int aux_kind_of(const rsrl_hip_ctx* c) { return c->sp_keys ? 4 : kAlgo[c->cfg.algo].aux_kind; }
+// (the kinds the configuration decides, not the algo: SARSALambda / QLambda over ONE shared tile table keep sparse traces instead of Z; the iLSTD
+// ActorCritic with the Beta policy keeps two policy columns instead of the Gibbs actor's A)
+int aux_kind_of(const rsrl_hip_ctx* c) { return c->sp_keys ? 4 : (c->family == AgentFamily::TdAcBetaReg ? 11 : kAlgo[c->cfg.algo].aux_kind); }
 // is (version, aux_kind) a header this library writes, or ever wrote?
 bool ckpt_pairing(uint32_t version, int32_t kind) {
     if (kind < 0 || kind >= kCkptKinds) return false;
@@ -679,6 +681,7 @@ int rsrl_hip_checksum(rsrl_hip_ctx* c, uint64_t out[2]) {
     run(c->state, sizeof(float) * c->D * N, 0, 1);
     run(c->action, sizeof(int32_t) * N, (size_t)1 << 36, 1);
     run(c->ep_step, sizeof(uint32_t) * N, (size_t)1 << 37, 1);
+    run(c->action_f, c->action_f ? sizeof(float) * N : 0, (size_t)1 << 39, 1);      // a continuous ctx's f32 actions
     run(c->hiv_y, c->hiv_y ? sizeof(double) * 6 * N : 0, (size_t)1 << 38, 1);      // HIVTreatment's hidden states (f64: two words each)
     // the LSTD agents' f64 state (two words per double) with the weights: theta, the matrices, iLSTD's mu
     run(c->lstd_theta, c->lstd_theta ? sizeof(double) * c->F * N : 0, (size_t)1 << 41, 0);

@@ -194,8 +194,10 @@ enum class AgentFamily : uint8_t {
     GmcReg,               // GradientMC, same configurations as LstdReg: k_train_gmc (train_gmc.hip); w in W (one column), the open episodes in rec_s / rec_r
     LstdBatchReg,         // LSTD / LSTDLambda, same configurations as GmcReg: k_train_lstd_batch (train_lstd_batch.hip); f64 state in lstd_theta / lstd_mat (A) /
                           // lstd_mu (b) / lstd_z / lstd_sing, the open episodes in rec_s / rec_r
+    TdAcBetaReg,          // ActorCritic with the iLSTD critic and the Beta policy on ContinuousMountainCar, Fourier orders 1-5: k_train_tdac_beta
+                          // (train_tdac_beta.hip); iLSTD's f64 state as LstdReg's, the policy's two columns in Z, f32 actions in action_f
 };
-constexpr size_t kAgentFamilies = (size_t)AgentFamily::LstdBatchReg + 1;      // (the enum's last value)
+constexpr size_t kAgentFamilies = (size_t)AgentFamily::TdAcBetaReg + 1;      // (the enum's last value)
 // ---- THE family table: which kernels serve a family and what they can do, one row per AgentFamily value in the enum's order.  classify() (abi_ctx.hip: a
 // decision) and launch_agent (abi_train.hip: it instantiates the templates) are the two other places a new family is entered.
 enum class Slots : uint8_t { Block, Block64, WaveBlock, Learner, LstdGroup };      // a statistics slot per: kBlock learners, 64 learners (k_train_lambda_mem4; the
@@ -249,6 +251,7 @@ constexpr FamilyRow kFamily[] = {
     {AgentFamily::TdAcLstdReg, "k_train_tdac_lstd", 32, Slots::LstdGroup, Handle::Agent, kPolicyW | kVCritic | kLstd},
     {AgentFamily::GmcReg, "k_train_gmc", 4096, Slots::Block, Handle::Agent, 0},      // (handle: refused, whole trajectories only)
     {AgentFamily::LstdBatchReg, "k_train_lstd_batch", 256, Slots::LstdGroup, Handle::Agent, kLstd | kBatchLstd},      // (handle: refused, whole batches only)
+    {AgentFamily::TdAcBetaReg, "k_train_tdac_beta", 32, Slots::LstdGroup, Handle::Agent, kPolicyW | kVCritic | kLstd},      // (handle: rsrl_hip_handle_f32)
 };
 constexpr bool family_rows_in_order() {
     for (size_t i = 0; i < sizeof(kFamily) / sizeof(kFamily[0]); ++i) if ((size_t)kFamily[i].family != i) return false;
@@ -279,6 +282,8 @@ struct rsrl_hip_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     float* state = nullptr; int32_t* action = nullptr; uint32_t* ep_step = nullptr;
+    float* action_f = nullptr;       // a continuous domain's pending actions f32[N] (ContinuousMountainCar; `action` is then allocated and never read)
+    int Ap = 0;                      // columns of the policy's own weights (rsrl_hip_n_policy_outputs): A for the Gibbs actors, 2 for Beta, 0 when the policy reads Q
     float* W = nullptr; float* dW = nullptr;
     int Aw = 0;                      // columns of the weight matrix: A (control) or 1 (prediction: ScalarLFA)
     long long* dW_rep = nullptr; int n_rep = 1;  // shared tile coding: n_rep copies of the fixed-point (64-bit) delta table
@@ -416,7 +421,15 @@ static Common make_policy_common(const rsrl_hip_ctx* c) {
 // a state-value critic next to the actor: the weights are V's one column, theta has A
 static inline bool is_v_actor_critic(const rsrl_hip_ctx* c) { return family_row(c).can & kVCritic; }
 // columns of the auxiliary matrix Z: W's (Aw), except the TD / iLSTD ActorCritic's theta (A)
-static inline int aux_cols(const rsrl_hip_ctx* c) { return kAlgo[c->cfg.algo].aux == Aux::Policy ? c->A : c->Aw; }
+static inline int aux_cols(const rsrl_hip_ctx* c) { return kAlgo[c->cfg.algo].aux == Aux::Policy ? c->Ap : c->Aw; }
+// a ctx whose actions are f32 values, not indices (ContinuousMountainCar): the *_f32 entry points are its own, their int32 twins ESTATE
+static inline bool is_continuous(const rsrl_hip_ctx* c) { return c->cfg.domain == RSRL_CONTINUOUS_MOUNTAIN_CAR; }
+#define NEEDS_INDEX_ACTIONS(c, call) do { if (is_continuous(c)) return fail(RSRL_HIP_ESTATE, "%s carries int32 action indices: this ctx's domain " \
+    "(ContinuousMountainCar) has one f32 action -- use %s_f32", call, call); } while (0)
+#define NEEDS_F32_ACTIONS(c, call) do { if (!is_continuous(c)) return fail(RSRL_HIP_ESTATE, "%s_f32 carries f32 actions: this ctx's domain has a finite " \
+    "action set (int32 indices) -- use %s", call, call); } while (0)
+// the domain whose Fourier features the ctx's are (ContinuousMountainCar: MountainCar's), for the kernels that read only features
+static inline int feature_domain(const rsrl_hip_ctx* c) { return is_continuous(c) ? RSRL_MOUNTAIN_CAR : c->cfg.domain; }
 // the agents whose value function is the f64 least-squares state (lstd_theta / lstd_mat / lstd_mu)
 static inline bool has_lstd_state(const rsrl_hip_ctx* c) { return family_row(c).can & kLstd; }
 static inline ReinforceState make_reinforce(const rsrl_hip_ctx* c) {
@@ -449,6 +462,12 @@ static inline LstdState make_lstd(const rsrl_hip_ctx* c) {
 static inline TdacLstdState make_tdac_lstd(const rsrl_hip_ctx* c) {
     TdacLstdState ts;
     ts.ls = make_lstd(c); ts.theta = c->Z; ts.alpha = c->cfg.alpha;
+    return ts;
+}
+
+static inline TdacBetaState make_tdac_beta(const rsrl_hip_ctx* c) {
+    TdacBetaState ts;
+    ts.ls = make_lstd(c); ts.w = c->Z; ts.alpha = c->cfg.alpha; ts.action = c->action_f;
     return ts;
 }
 
@@ -602,6 +621,16 @@ static int check_host_actions(const int32_t* a, size_t n, int A) {
     if (!a || is_device_ptr(a)) return RSRL_HIP_OK;
     for (size_t i = 0; i < n; ++i)
         if (a[i] < 0 || a[i] >= A) return fail(RSRL_HIP_EINVAL, "action[%zu] = %d is outside [0, %d)", i, a[i], A);
+    return RSRL_HIP_OK;
+}
+// caller-supplied f32 actions (a continuous ctx): a HOST array must hold finite values (bounded: inside ContinuousMountainCar's action bounds too); a
+// DEVICE array is clamped by the kernels instead
+static int check_host_actions_f32(const float* a, size_t n, bool bounded) {
+    if (!a || is_device_ptr(a)) return RSRL_HIP_OK;
+    for (size_t i = 0; i < n; ++i) {
+        if (!std::isfinite(a[i])) return fail(RSRL_HIP_EINVAL, "action[%zu] = %g is not finite", i, (double)a[i]);
+        if (bounded && !(a[i] >= -1.0f && a[i] <= 1.0f)) return fail(RSRL_HIP_EINVAL, "action[%zu] = %g is outside [-1, 1]", i, (double)a[i]);
+    }
     return RSRL_HIP_OK;
 }
 // caller-supplied STATES: the reference's wrap! (rsrl_domains/src/macros.rs:14-24) brings an angle home by repeated +-2 pi -- a loop that does not end

@@ -264,6 +264,30 @@ template <> struct Domain<0> {
     }
 };
 
+// ContinuousMountainCar    rsrl_domains/src/mountain_car/continuous.rs
+// MountainCar's bounds, start state and f32 operation order (so the Fourier features of a state are domain 0's at the same order); only the force
+// term differs, and the action is ONE f32 in [-1, 1] instead of an index (A = 0: the action set is not enumerable).  The reference brings the
+// action into its bounds with action_space.map_onto, from the `spaces` crate, which is not in the reference tree: RECALLED as a clip.
+template <> struct Domain<4> {
+    static constexpr int D = 2, A = 0;
+    __host__ __device__ static constexpr double lo_d(int i) { return Domain<0>::lo_d(i); }
+    __host__ __device__ static constexpr double hi_d(int i) { return Domain<0>::hi_d(i); }
+    __host__ __device__ static constexpr double action_lo() { return -1.0; }
+    __host__ __device__ static constexpr double action_hi() { return 1.0; }
+    __device__ static __forceinline__ void reset(float (&s)[D]) { s[0] = -0.5f; s[1] = 0.0f; }
+    __device__ static __forceinline__ bool is_terminal(const float (&s)[D]) { return s[0] >= 0.6f; }
+    __device__ static __forceinline__ bool step(float (&s)[D], float a, float& r) {
+        const float act = clipf(-1.0f, a, 1.0f);                       // map_onto (recalled)
+        const float dv = 0.0015f * act + -0.0025f * cos_cw(3.0f * s[0]);
+        const float v = clipf(-0.07f, s[1] + dv, 0.07f);
+        const float x = clipf(-1.2f, s[0] + v, 0.6f);
+        s[0] = x; s[1] = v;
+        const bool term = x >= 0.6f;
+        r = term ? 0.0f : -1.0f;
+        return term;
+    }
+};
+
 // x / d for a COMPILE-TIME constant d, bit for bit the correctly rounded fp32 quotient the reference's `/` is (ode.rs:36 `/ 6.0`,
 // cart_pole.rs:60 `/ TOTAL_MASS`, the tile coder's (s - lo) / (hi - lo)): through f64 -- convert, ONE multiplication by RN64(1 / d),
 // convert back: three instructions where the IEEE fp32 division expands to ~11 (v_div_scale x 2, v_rcp, four fmas, v_div_fmas,

@@ -11,6 +11,9 @@
 // the register-family Fourier (domain, order) pairs, in the order every launcher instantiates them (moving one moves the
 // PC-relative offsets of the others' machine code).  The models of the Fourier rows: FourierModel<domain, order>
 #define RSRL_REG_FOURIER(X) X(0, 1) X(0, 2) X(0, 3) X(0, 4) X(0, 5) X(1, 1) X(2, 1)
+// ContinuousMountainCar (domain 4, f32 actions): the Fourier orders its one agent runs on (train_tdac_beta.hip) -- MountainCar's register-family
+// orders, with MountainCar's features.  NOT rows of RSRL_REG_FOURIER: no model kernel (an index action per learner) is instantiated for it
+#define RSRL_CMC_ORDERS(X) X(1) X(2) X(3) X(4) X(5)
 // the models WITHOUT a register-family kernel of their own (what the *_mem agent kernels are instantiated for)
 #define RSRL_MEM_MODELS(X)                                                                   \
     X((TileModel<0, 4>), RSRL_TILE_CODING, 0, 4) X((TileModel<0, 8>), RSRL_TILE_CODING, 0, 8) X((TileModel<0, 16>), RSRL_TILE_CODING, 0, 16) \
@@ -30,6 +33,13 @@ static inline bool model_match(const rsrl_hip_config& cfg, int basis, int domain
 static inline bool is_reg_fourier(const rsrl_hip_config& cfg) {
 #define X(DM, OR) if (model_match(cfg, RSRL_FOURIER, DM, OR)) return true;
     RSRL_REG_FOURIER(X)
+#undef X
+    return false;
+}
+// a ContinuousMountainCar configuration on one of its Fourier orders
+static inline bool is_cmc_fourier(const rsrl_hip_config& cfg) {
+#define X(OR) if (model_match(cfg, RSRL_FOURIER, RSRL_CONTINUOUS_MOUNTAIN_CAR, OR)) return true;
+    RSRL_CMC_ORDERS(X)
 #undef X
     return false;
 }

@@ -3,6 +3,7 @@
 // side above the ABI is C++ with the reference's names, argument meaning and error behaviour:
 //
 //   rsrl::domains::{MountainCar, CartPole, Acrobot}      rsrl_domains/src/{mountain_car/discrete,cart_pole,acrobot}.rs
+//   rsrl::domains::ContinuousMountainCar, rsrl::policies::Beta      rsrl_domains/src/mountain_car/continuous.rs, rsrl/src/policies/beta.rs
 //   rsrl::fa::linear::{basis::Fourier, optim::SGD, LFA}  rsrl/src/fa/linear.rs (re-exports of crate lfa)
 //   rsrl::policies::{Greedy, EpsilonGreedy, Softmax, Random}   rsrl/src/policies/*.rs
 //   rsrl::control::td::{QLearning, SARSA, ExpectedSARSA, PAL, SARSALambda, QLambda, GreedyGQ, QSigma}   rsrl/src/control/td/*.rs
@@ -67,6 +68,8 @@ struct MountainCar : Domain { explicit MountainCar(int64_t n = 1) : Domain{RSRL_
 struct CartPole : Domain { explicit CartPole(int64_t n = 1) : Domain{RSRL_CART_POLE, n} {} };
 struct Acrobot : Domain { explicit Acrobot(int64_t n = 1) : Domain{RSRL_ACROBOT, n} {} };
 struct HIVTreatment : Domain { explicit HIVTreatment(int64_t n = 1) : Domain{RSRL_HIV_TREATMENT, n} {} };     // hiv.rs: f64 hidden state (rsrl_hip_get_hidden_states)
+// mountain_car/continuous.rs: MountainCar's state space with one f32 action in [-1, 1] (Session::transition_f32 / sample_f32; n_actions() is 0)
+struct ContinuousMountainCar : Domain { explicit ContinuousMountainCar(int64_t n = 1) : Domain{RSRL_CONTINUOUS_MOUNTAIN_CAR, n} {} };
 }  // namespace domains
 
 // ---- rsrl::fa::linear ------------------------------------------------------------------------------
@@ -125,6 +128,13 @@ struct Softmax : Policy {                 // Softmax::new(fa, tau) panics for |t
 struct Gibbs : Softmax {
     explicit Gibbs(Shared<fa::linear::LFA> fa, double tau_ = 1.0) : Softmax(std::move(fa), tau_) {}
     static Gibbs standard(Shared<fa::linear::LFA> fa) { return Gibbs(std::move(fa)); }
+};
+// Beta::new(alpha, beta) (policies/beta.rs) with alpha = beta = Composition<ScalarLFA, Softplus> over the basis, zero weights: the policy of
+// examples/tdac_beta.rs on ContinuousMountainCar.  Its two weight columns are read through Session::policy_weights ([F][2])
+struct Beta : Policy {
+    Shared<fa::linear::LFA> q;
+    explicit Beta(const fa::linear::basis::Fourier& basis)
+        : Policy{RSRL_BETA}, q(make_shared(fa::linear::LFA::vector(basis, fa::linear::optim::SGD(1.0), 1))) {}
 };
 }  // namespace policies
 
@@ -216,6 +226,8 @@ struct ActorCritic : td::Agent {
     // every transition (RSRL_ILSTD_ACTOR_CRITIC).  eval's alpha, gamma and n_updates are iLSTD's; gamma is TDCritic's and must be eval's.  The
     // Session's weights are iLSTD's theta as f32 [F][1]; Session::lstd_state(env, true) is the exact f64 state  (defined below iLSTD)
     static inline ActorCritic tdac(const prediction::lstd::iLSTD& eval, const policies::Gibbs& policy, double alpha_, double gamma);
+    // ... generic over the policy: with policies::Beta on domains::ContinuousMountainCar, the agent of examples/tdac_beta.rs (same algo)
+    static inline ActorCritic tdac(const prediction::lstd::iLSTD& eval, const policies::Beta& policy, double alpha_, double gamma);
 };
 }}  // namespace control::ac
 
@@ -286,6 +298,10 @@ inline control::ac::ActorCritic control::ac::ActorCritic::tdac(const prediction:
     return a;
 }
 
+inline control::ac::ActorCritic control::ac::ActorCritic::tdac(const prediction::lstd::iLSTD& eval, const policies::Beta&, double alpha_, double gamma) {
+    return tdac(eval, policies::Gibbs::standard(eval.q_func), alpha_, gamma);      // (the Session's policy decides the kind)
+}
+
 // ---- the bound object graph: env + agent + policy sharing one q_func on one MI355X -------------------
 class Session {
 public:
@@ -309,7 +325,7 @@ public:
         cfg.seed = seed; cfg.max_episode_steps = max_episode_steps;
         check(rsrl_hip_create(&cfg, &ctx_));
         D_ = rsrl_hip_state_dim(ctx_); A_ = rsrl_hip_n_actions(ctx_); F_ = rsrl_hip_n_features(ctx_); N_ = env.n_envs;
-        O_ = rsrl_hip_n_outputs(ctx_);
+        O_ = rsrl_hip_n_outputs(ctx_); P_ = rsrl_hip_n_policy_outputs(ctx_);
     }
     ~Session() { rsrl_hip_destroy(ctx_); }
     Session(const Session&) = delete;
@@ -337,6 +353,35 @@ public:
         std::vector<float> td(N_);
         check(rsrl_hip_handle(ctx_, t.from.data(), t.action.data(), t.reward.data(), t.to.data(), t.terminal.data(), N_, td.data()));
         return td;
+    }
+    // ... with f32 actions, a continuous domain's (ContinuousMountainCar): Domain::transition, Handler<&Transition>::handle, Policy::sample / mode,
+    // Beta's compute_alpha / compute_beta
+    struct TransitionF32 { std::vector<float> from, action, reward, to; std::vector<uint8_t> terminal; };
+    TransitionF32 transition_f32(const std::vector<float>& a) {
+        TransitionF32 t;
+        t.from.resize((size_t)D_ * N_); t.to.resize((size_t)D_ * N_); t.reward.resize(N_); t.terminal.resize(N_);
+        t.action = a;
+        check(rsrl_hip_domain_step_f32(ctx_, a.data(), t.from.data(), t.to.data(), t.reward.data(), t.terminal.data()));
+        return t;
+    }
+    std::vector<float> handle(const TransitionF32& t) {
+        std::vector<float> td(N_);
+        check(rsrl_hip_handle_f32(ctx_, t.from.data(), t.action.data(), t.reward.data(), t.to.data(), t.terminal.data(), N_, td.data()));
+        return td;
+    }
+    std::vector<float> sample_f32() { std::vector<float> a(N_); check(rsrl_hip_policy_sample_f32(ctx_, nullptr, N_, a.data())); return a; }
+    std::vector<float> sample_f32(const std::vector<float>& states) {
+        std::vector<float> a(N_); check(rsrl_hip_policy_sample_f32(ctx_, states.data(), N_, a.data())); return a;
+    }
+    std::vector<float> mode_f32(const std::vector<float>& states) {
+        std::vector<float> a(N_); check(rsrl_hip_policy_mode_f32(ctx_, states.data(), N_, a.data())); return a;
+    }
+    std::pair<std::vector<float>, std::vector<float>> policy_params(const std::vector<float>& states) {
+        std::vector<float> a(N_), b(N_); check(rsrl_hip_policy_params(ctx_, states.data(), N_, a.data(), b.data())); return {a, b};
+    }
+    // Domain::rollout(|s| policy.mode(s), Some(limit)).total_reward() for every learner
+    std::vector<float> rollout_total_reward(int64_t step_limit) {
+        std::vector<uint32_t> n(N_); std::vector<float> tot(N_); check(rsrl_hip_rollout_greedy(ctx_, step_limit, n.data(), tot.data())); return tot;
     }
     // Handler<&Batch>::handle of REINFORCE / BaselineREINFORCE -> the running return at each handled transition, [T][N] (reinforce.rs)
     // ... and of LSTD / LSTDLambda, which read whole transitions (b.to and b.terminal filled; lstd.rs:59-81, lstd_lambda.rs:66-103) -> the
@@ -427,7 +472,7 @@ public:
     }
     // the pub field `policy` of ActorCritic: the Gibbs actor's weights               (ac.rs:61)
     std::vector<float> policy_weights(int64_t env = 0) {
-        std::vector<float> v((size_t)F_ * A_); check(rsrl_hip_get_policy_weights(ctx_, env, v.data())); return v;
+        std::vector<float> v((size_t)F_ * (P_ ? P_ : A_)); check(rsrl_hip_get_policy_weights(ctx_, env, v.data())); return v;
     }
     // serde analogue: checkpoint of every learner's approximator(s)                  (rsrl/Cargo.toml:26)
     void save_weights(const std::string& path) { check(rsrl_hip_save_weights(ctx_, path.c_str())); }
@@ -462,7 +507,7 @@ public:
 
 private:
     rsrl_hip_ctx* ctx_ = nullptr;
-    int D_ = 0, A_ = 0, F_ = 0, O_ = 0;      // O_: weight columns (A_, or 1 for the prediction agents)
+    int D_ = 0, A_ = 0, F_ = 0, O_ = 0, P_ = 0;      // O_: weight columns (A_, or 1 for the prediction agents); P_: the policy's own (A_, or Beta's 2)
     int64_t N_ = 0;
 };
 

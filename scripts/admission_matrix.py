@@ -3,7 +3,9 @@
 query, so a refused configuration returns EINVAL and an admitted one EHIP ("no device").  Sweeps GRID (133 120 configurations, about 1 s) and
 GRID_AGENTS -- the algos numbered after GRID's (13-19) on the same other axes, 71 680 configurations -- and GRID_AGENTS2 (20 and 21, 20 480
 configurations) and GRID_AGENTS3 (22 and 23, with max_episode_steps = 200 on every configuration: GradientMC refuses the default 0), each into a
-fixture of its own.
+fixture of its own; and GRID_BETA, the continuous axis: MountainCar and ContinuousMountainCar x the policies Softmax, Random, Beta x the algos iLSTD
+(19), the iLSTD ActorCritic (21) and the unassigned 27, with agent_policy -1 / Softmax / Beta (15 360 configurations) -> create_admission_beta.json
+(tests/test_tdac_beta_cpu.py).
     python scripts/admission_matrix.py            writes tests/golden/create_admission.json, create_admission_agents.json,
                                                   create_admission_agents2.json and create_admission_agents3.json
                                                   (tests/test_create_admission_cpu.py, tests/test_tdac_lstd_cpu.py and tests/test_gmc_cpu.py
@@ -22,6 +24,7 @@ FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission.json")
 AGENTS_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_agents.json")
 AGENTS2_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_agents2.json")
 AGENTS3_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_agents3.json")
+BETA_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_beta.json")
 EINVAL, EHIP = -1, -2
 
 # (config field, values): the first axis varies slowest
@@ -45,8 +48,23 @@ GRID_AGENTS2 = [(name, [20, 21] if name == "algo" else vals) for name, vals in G
 # the unassigned 22 and GradientMC (23), on GRID's other axes; FIXED_AGENTS3 is set on every configuration of the grid
 GRID_AGENTS3 = [(name, [22, 23] if name == "algo" else vals) for name, vals in GRID]
 FIXED_AGENTS3 = {"max_episode_steps": 200}
+# the continuous axis: ContinuousMountainCar (4) beside MountainCar, the Beta policy (4) beside Softmax and Random, as behaviour and as agent policy
+GRID_BETA = [
+    ("domain", [0, 4]),
+    ("basis", [0, 1]),
+    ("order", [1, 2, 3, 4, 5, 6, 7]),
+    ("algo", [19, 21, 27]),                  # 27: no such algo
+    ("policy", [2, 3, 4]),
+    ("weight_mode", [0, 1]),
+    ("weight_dtype", [0, 1]),
+    ("agent_policy", [-1, 2, 4]),
+    ("epsilon_decay", [1.0, 0.99]),
+    ("steps_per_launch", [0, 1]),
+    ("n_steps", [2, 33]),
+]
 # (grid, fixture, fields set on every configuration)
-GRIDS = ((GRID, FIXTURE, {}), (GRID_AGENTS, AGENTS_FIXTURE, {}), (GRID_AGENTS2, AGENTS2_FIXTURE, {}), (GRID_AGENTS3, AGENTS3_FIXTURE, FIXED_AGENTS3))
+GRIDS = ((GRID, FIXTURE, {}), (GRID_AGENTS, AGENTS_FIXTURE, {}), (GRID_AGENTS2, AGENTS2_FIXTURE, {}), (GRID_AGENTS3, AGENTS3_FIXTURE, FIXED_AGENTS3),
+         (GRID_BETA, BETA_FIXTURE, {}))
 
 
 def sweep(grid=GRID, fixed=None):
