@@ -68,7 +68,7 @@ typedef enum {
  *   v = clip(-0.07, v + 0.0015 a' - 0.0025 cos(3x), 0.07); x = clip(-1.2, x + v, 0.6); terminal iff x >= 0.6; reward 0 on a terminal step, -1
  *   otherwise.  The action set is not enumerable: rsrl_hip_n_actions is 0, rsrl_hip_action_bounds gives (-1, 1), and every action of the ctx is
  *   f32 (the *_f32 entry points below; their int32 twins are ESTATE, as the *_f32 calls are on the other domains).  Supported:
- *   RSRL_ILSTD_ACTOR_CRITIC with policy RSRL_BETA on the Fourier orders 1-5; every other combination is EINVAL at create. */
+ *   RSRL_ILSTD_ACTOR_CRITIC and RSRL_NAC with policy RSRL_BETA on the Fourier orders 1-5; every other combination is EINVAL at create. */
 typedef enum { RSRL_MOUNTAIN_CAR = 0, RSRL_CART_POLE = 1, RSRL_ACROBOT = 2, RSRL_HIV_TREATMENT = 3, RSRL_CONTINUOUS_MOUNTAIN_CAR = 4 } rsrl_domain;
 /* lfa::basis::{Fourier (+with_bias), TileCoding}  (re-exported by rsrl/src/fa/linear.rs:11-14) */
 typedef enum { RSRL_FOURIER = 0, RSRL_TILE_CODING = 1 } rsrl_basis;
@@ -236,13 +236,44 @@ typedef enum { RSRL_QLEARNING = 0, RSRL_SARSA = 1, RSRL_EXPECTED_SARSA = 2, RSRL
                 * stood before the batch's solve, booked at the step that ended the episode: the agents compute no TD error.  The checkpoint is aux_kind 10;
                 * the open record is the caller's to carry.  Not built: LambdaLSPE (its solve() zeroes A and b, so every batch shorter than F is a
                 * rank-deficient system that only the SVD fallback answers) */
-               RSRL_LSTD = 25, RSRL_LSTD_LAMBDA = 26 } rsrl_algo;
+               RSRL_LSTD = 25, RSRL_LSTD_LAMBDA = 26,
+               /* (27 is no algo.)  NAC (control/nac.rs:47-59), natural actor-critic, with the Beta policy and a SARSA critic over the stable
+                * compatible basis: the agent and the loop of examples/nac_beta.rs.  critic = SARSA{q_func: LFA::scalar(SCB{policy, basis},
+                * SGD(lr)), policy, gamma} (control/td/sarsa.rs:53-75); SCB::project((s, a)) (fa/linear.rs:79-103) is grad_log pi(a|s)
+                * (policies/beta.rs:119-129) chained with basis.project(s): 3F features
+                *   psi(s, a) = [ g_a sigma(x_a) phi(s) ; g_b sigma(x_b) phi(s) ; phi(s) ]     (x, g, sigma: RSRL_BETA's, below)
+                * and Q(s, a) = <w, psi(s, a)>, w f32[3F] per learner, zero at create (linear.rs:253-261); evaluated as three length-F dots
+                * combined, fma(c_a, d_0, fma(c_b, d_1, d_2)).  Per transition (SARSA::handle): delta = r - Q(s, a) on a terminal transition, else
+                * r + gamma Q(s', na) - Q(s, a) with na = policy.sample(s') on the agent's own stream (the reference: thread_rng()); then
+                * w += lr delta psi(s, a) (linear.rs:277-288).  The policy's columns do not move.  NAC::handle(()): g = w[0 .. 2F-1],
+                * norm = max(sqrt(sum g_j^2), 1e-3), w_a += (alpha / norm) g[0 .. F-1], w_b += (alpha / norm) g[F .. 2F-1] (beta.rs:247-276,
+                * fa/composition.rs:55-66, linear.rs:184-196); the response is norm; the critic's weights are not reset.
+                * config: lr = the critic's SGD rate (0.01 in the example), gamma = SARSA.gamma (0.999), alpha = NAC.alpha (0.1, rounded to f32
+                * once), n_steps = the actor's period P in [1, 65 536] (the example hard-codes 100); max_episode_steps may be 0.
+                * rsrl_hip_train is nac_beta.rs:55-76 with i the 0-based index of the step in its episode: t = env.transition(2a - 1) with the
+                * agent's action a in t's place; critic.handle(t); a = policy.sample(s') (after the restart when the episode ended); then
+                * NAC::handle(()) if i % P == 0 -- i = 0 included: the sample is drawn from the columns BEFORE the actor's step, the next
+                * transition's psi(s, a) is evaluated with the columns AFTER it.  The statistics' sum |delta| is SARSA's.
+                * The value side is the critic: rsrl_hip_get/set_weights carry w as f32[3F][1], rsrl_hip_n_outputs is 1, rsrl_hip_n_weight_rows
+                * is 3F (SCB::n_features); Q needs an action: rsrl_hip_q_evaluate_f32; rsrl_hip_q_evaluate / q_find_max / _min / q_expected_value
+                * are ESTATE.  The policy side is RSRL_BETA's unchanged (policy_sample_f32 / _mode_f32 / _params / _pdf, get/set_policy_weights
+                * f32[F][2], n_policy_outputs 2, reset's initial sample).  rsrl_hip_handle_f32 is critic.handle alone (td_error_out = delta; it does
+                * NOT move the actor); rsrl_hip_nac_update is NAC::handle(()); rsrl_hip_domain_step_f32 with actions == NULL applies the loop's
+                * 2a - 1 to the pending actions; rsrl_hip_rollout_greedy is Domain::rollout(|s| 2 * policy.mode(s) - 1) (nac_beta.rs:81-82);
+                * rsrl_hip_rollout_trajectory / _policy, handle_batch, handle_transitions, traces, td weights and the lstd state are ESTATE.
+                * Supported: RSRL_CONTINUOUS_MOUNTAIN_CAR with policy RSRL_BETA, agent_policy -1 (the critic shares the policy), Fourier orders
+                * 1-5, per-learner f32 weights, no epsilon schedule; everything else is EINVAL at create.  The checkpoint is aux_kind 12.
+                * DEPARTURES: f32 for the reference's f64; the score, modes() and map_onto recalled (RSRL_BETA, RSRL_CONTINUOUS_MOUNTAIN_CAR); the
+                * action clamped to [2^-24, 1 - 2^-24] before its logarithms; SARSA's thread_rng() draw is a keyed stream (distribution parity is
+                * the contract); the period is a parameter.  Not built: nac.rs (the Gaussian policy's normal::Grad is not in the reference tree)
+                * and nac_softmax.rs (kernels_nac_beta.hpp) */
+               RSRL_NAC = 28 } rsrl_algo;
 /* rsrl::traces::{Accumulate, Saturate (Trace::replacing), Dutch}      traces.rs:188-240 */
 typedef enum { RSRL_TRACE_ACCUMULATE = 0, RSRL_TRACE_SATURATE = 1, RSRL_TRACE_DUTCH = 2 } rsrl_trace;
 /* rsrl::policies::{Greedy, EpsilonGreedy, Softmax, Random}
  *   greedy.rs:16-84, epsilon_greedy.rs:14-83, softmax.rs:55-143, random.rs:13-48
  * Beta (policies/beta.rs) over two Composition<ScalarLFA, Softplus> (fa/composition.rs:98-115, fa/transforms.rs:196-218): a CONTINUOUS policy, for
- *   RSRL_ILSTD_ACTOR_CRITIC on RSRL_CONTINUOUS_MOUNTAIN_CAR only (EINVAL elsewhere, and as agent_policy).  Per learner two weight columns w_a, w_b
+ *   RSRL_ILSTD_ACTOR_CRITIC and RSRL_NAC on RSRL_CONTINUOUS_MOUNTAIN_CAR only (EINVAL elsewhere, and as agent_policy).  Per learner two weight columns w_a, w_b
  *   f32[F] (zero at create; rsrl_hip_get/set_policy_weights carry them as f32[F][2], column 0 = alpha's; rsrl_hip_n_policy_outputs = 2).  With
  *   x_a = <w_a, phi(s)>, x_b likewise (f32): alpha = softplus(x_a) + 1, beta = softplus(x_b) + 1, softplus(x) = x for x >= 10 else ln(1 + exp(x))
  *   (MIN_TOL = 1.0, beta.rs:19, :58-67): both >= 1.
@@ -384,6 +415,9 @@ int rsrl_hip_n_outputs(const rsrl_hip_ctx* ctx);
  * 0 for the agents whose policy reads Q */
 int rsrl_hip_n_policy_outputs(const rsrl_hip_ctx* ctx);
 int rsrl_hip_n_features(const rsrl_hip_ctx* ctx);
+/* rows of the weight matrix (rsrl_hip_get/set_weights carry f32[n_weight_rows][n_outputs]): 3 n_features for RSRL_NAC, whose critic's basis is the
+ * stable compatible basis (SCB::n_features, fa/linear.rs:79-103); n_features on every other ctx */
+int rsrl_hip_n_weight_rows(const rsrl_hip_ctx* ctx);
 int64_t rsrl_hip_n_envs(const rsrl_hip_ctx* ctx);
 /* state_space() bounds: mountain_car/discrete.rs:97-99, cart_pole.rs:112-118, acrobot.rs:143-149 */
 int rsrl_hip_state_bounds(const rsrl_hip_ctx* ctx, double* lo /*[D]*/, double* hi /*[D]*/);
@@ -416,7 +450,13 @@ int rsrl_hip_set_actions(rsrl_hip_ctx* ctx, const int32_t* actions /*[N]*/);
  *   rsrl_hip_domain_step_f32      rsrl_hip_domain_step            rsrl_hip_policy_sample_f32   rsrl_hip_policy_sample (states == NULL as there)
  *   rsrl_hip_handle_f32           rsrl_hip_handle                 rsrl_hip_policy_mode_f32     rsrl_hip_policy_mode
  * rsrl_hip_policy_params is beta.rs's pub compute_alpha / compute_beta, rsrl_hip_policy_pdf its Function<(S, A)> (the density, of the action
- * clamped to [2^-24, 1 - 2^-24]); both read-only, state i against learner i's columns */
+ * clamped to [2^-24, 1 - 2^-24]); both read-only, state i against learner i's columns.
+ * On an RSRL_NAC ctx (the loop of nac_beta.rs: the domain sees 2a - 1, the agent a) rsrl_hip_domain_step_f32 takes explicit actions literally, as the
+ * DOMAIN's, and with actions == NULL applies the loop's 2a - 1 to the ctx's pending actions (the agent's); rsrl_hip_handle_f32 is critic.handle.
+ * rsrl_hip_q_evaluate_f32 is Function<(S, A)>::evaluate of RSRL_NAC's critic, Q(s_i, a_i) = <w_i, psi(s_i, a_i)> against learner i's w and columns
+ * (read-only; the action is clamped as above); rsrl_hip_nac_update is NAC::handle(()) (control/nac.rs:47-59) for the learners whose mask byte is
+ * non-zero (mask == NULL: every learner): norm_out, which may be NULL, receives Response.norm, 0 for a learner left out.  Both are ESTATE on
+ * every other algo */
 int rsrl_hip_get_actions_f32(rsrl_hip_ctx* ctx, float* actions /*[N]*/);
 int rsrl_hip_set_actions_f32(rsrl_hip_ctx* ctx, const float* actions /*[N]*/);
 int rsrl_hip_domain_step_f32(rsrl_hip_ctx* ctx, const float* actions, float* from_states, float* next_states, float* rewards, uint8_t* terminal);
@@ -426,6 +466,8 @@ int rsrl_hip_policy_sample_f32(rsrl_hip_ctx* ctx, const float* states, int64_t M
 int rsrl_hip_policy_mode_f32(rsrl_hip_ctx* ctx, const float* states, int64_t M, float* actions_out);
 int rsrl_hip_policy_params(rsrl_hip_ctx* ctx, const float* states, int64_t M, float* alpha_out, float* beta_out);
 int rsrl_hip_policy_pdf(rsrl_hip_ctx* ctx, const float* states, const float* actions, int64_t M, float* out);
+int rsrl_hip_q_evaluate_f32(rsrl_hip_ctx* ctx, const float* states /*[D][M]*/, const float* actions /*[M]*/, int64_t M, float* q_out /*[M]*/);
+int rsrl_hip_nac_update(rsrl_hip_ctx* ctx, const uint8_t* mask /*[N], NULL = every learner*/, float* norm_out /*[N], may be NULL*/);
 /* (ABI 8) The rest of a learner's state between two driver calls, so that a run can be carried into another ctx EXACTLY (with the checkpoint of
  * rsrl_hip_save_weights, the states and the actions above):
  *   - the steps every learner's current episode has taken (what the driver loop's `for j in 0..step_limit` counter would hold,
@@ -598,6 +640,7 @@ int rsrl_hip_lstd_solve(rsrl_hip_ctx* ctx);
  *   9 the iLSTD ActorCritic's f64 state and theta    10          f64 theta, matrices, mu, auxiliary matrix
  *   10 LSTD / LSTDLambda's f64 state                 10          f64 theta, A, b, z (LSTDLambda), u32 singular_solves
  *   11 the Beta iLSTD ActorCritic's state            10          f64 theta, matrices, mu, the policy's columns
+ *   12 NAC's critic and the policy's columns         10          weights (3F rows), the policy's columns
  * and a ctx with config.epsilon_decay (aux_kind 0 or 1) writes version 4 instead, with f32 eps[N] behind the payload.  No other pairing of
  * version and aux_kind is a file of this library; load refuses it.  Little-endian, serialised field by field (no padding):
  *   offset  0  char magic[8] = "RSRLHIPW"
@@ -607,7 +650,7 @@ int rsrl_hip_lstd_solve(rsrl_hip_ctx* ctx);
  *                   3 QSigma's n-step backups, 4 sparse traces over a shared table, 5 ActorCritic's theta,
  *                   6 the TD ActorCritic's theta, 7 REINFORCE's theta and open episode, 8 the LSTD agents' f64 state,
  *                   9 the iLSTD ActorCritic's f64 state and theta, 10 LSTD / LSTDLambda's f64 state,
- *                   11 the Beta iLSTD ActorCritic's f64 state and policy columns)
+ *                   11 the Beta iLSTD ActorCritic's f64 state and policy columns, 12 NAC's critic and policy columns)
  *                                                                                                                 [11 x i32]
  *          56  i64  n_learners (1 in shared mode)
  *          64  u64  step_count
@@ -630,6 +673,8 @@ int rsrl_hip_lstd_solve(rsrl_hip_ctx* ctx);
  *              n_learners x f64[F] of z, then u32 singular_solves[N].  The open episodes are not in the file (as RSRL_GRADIENT_MC's);
  *              if aux_kind is 11 (file version 10 too; RSRL_ILSTD_ACTOR_CRITIC with RSRL_BETA on RSRL_CONTINUOUS_MOUNTAIN_CAR): aux_kind 8's
  *              sections of its iLSTD critic (mu included), then n_learners x f32[F][2] of the policy's columns (alpha's, beta's);
+ *              if aux_kind is 12 (file version 10 too; RSRL_NAC; the header's F is n_features, A = 1): the weights
+ *              are the critic's w, n_learners x f32[3F][1], then n_learners x f32[F][2] of the policy's columns;
  *              if aux_kind is 3 (file version 3): u32 head[N], u32 len[N], f32 entries[D + 5][n_steps][N] -- every learner's
  *              Backup ring {s, a, q, residual, pi, mu} (q_sigma.rs:30-63), so that a QSigma run with n_steps > 1 resumes
  *              bit-identically too.  A QSigma ctx still reads its configuration's version-2 file without them (aux_kind 0): the backups start empty.

@@ -46,6 +46,7 @@ SYMBOLS = {
     "rsrl_hip_n_outputs": (C.c_int, [C.c_void_p]),
     "rsrl_hip_n_policy_outputs": (C.c_int, [C.c_void_p]),
     "rsrl_hip_n_features": (C.c_int, [C.c_void_p]),
+    "rsrl_hip_n_weight_rows": (C.c_int, [C.c_void_p]),
     "rsrl_hip_n_envs": (C.c_int64, [C.c_void_p]),
     "rsrl_hip_state_bounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rsrl_hip_action_bounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -64,6 +65,8 @@ SYMBOLS = {
     "rsrl_hip_policy_mode_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "rsrl_hip_policy_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "rsrl_hip_policy_pdf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rsrl_hip_q_evaluate_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rsrl_hip_nac_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rsrl_hip_get_episode_steps": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rsrl_hip_set_episode_steps": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rsrl_hip_get_episode_record": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -17,6 +17,7 @@ RECURSIVE_LSTD, ILSTD = 18, 19                  # (17 is no algo) prediction/lst
 ILSTD_ACTOR_CRITIC = 21                        # (20 is no algo) ActorCritic::tdac over iLSTD, tdac.rs's agent: lr = iLSTD's alpha, n_steps = its n_updates, alpha = the actor's
 GRADIENT_MC = 23                               # (22 is no algo) prediction/mc.rs: GradientMC (Handler<&Trajectory>: handle_batch; episode_record)
 LSTD, LSTD_LAMBDA = 25, 26                      # (24 is no algo) prediction/lstd: LSTD, LSTDLambda (Handler<&Batch> on whole transitions: handle_transitions; lstd_solve; get/set_lstd_batch_state)
+NAC = 28                                        # (27 is no algo) control/nac.rs with the BETA policy and a SARSA critic over the stable compatible basis on CONTINUOUS_MOUNTAIN_CAR (nac_beta.rs): n_weight_rows = 3 F; q_evaluate_f32; nac_update
 TRACE_ACCUMULATE, TRACE_SATURATE, TRACE_DUTCH = 0, 1, 2
 GREEDY, EPSILON_GREEDY, SOFTMAX, RANDOM = 0, 1, 2, 3
 BETA = 4                                        # policies/beta.rs over two Softplus-composed scalar LFAs: ILSTD_ACTOR_CRITIC on CONTINUOUS_MOUNTAIN_CAR
@@ -120,6 +121,7 @@ class Context:
         self.A = self._L.rsrl_hip_n_actions(self._h)
         self.n_out = self._L.rsrl_hip_n_outputs(self._h)      # weight columns: A, or 1 for TD / TDLambda
         self.F = self._L.rsrl_hip_n_features(self._h)
+        self.n_weight_rows = self._L.rsrl_hip_n_weight_rows(self._h)      # rows of the weight matrix: F, or NAC's 3 F (SCB::n_features)
         self.n_policy_out = self._L.rsrl_hip_n_policy_outputs(self._h)      # columns of the policy's own weights: A (Gibbs), 2 (BETA), 0 (the policy reads Q)
         self._policy_cols = self.n_policy_out or self.A                     # (the accessors' array shape; an agent without policy weights is refused by the library)
         self.continuous = domain == CONTINUOUS_MOUNTAIN_CAR                 # actions are f32 values (the *_f32 entry points), not int32 indices
@@ -263,6 +265,19 @@ class Context:
         _abi.check(self._L.rsrl_hip_q_evaluate(self._h, _p(states), M, _p(out)))
         return out
 
+    def q_evaluate_f32(self, states, actions):
+        """NAC's critic, Function<(S, A)>: Q(s_i, a_i) = <w_i, psi(s_i, a_i)> against learner i's w and columns -> (M,) f32"""
+        states, M = self._batch(states)
+        out = np.empty(M, dtype=np.float32)
+        _abi.check(self._L.rsrl_hip_q_evaluate_f32(self._h, _p(states), _p(_in(actions, np.float32, (M,))), M, _p(out)))
+        return out
+
+    def nac_update(self, mask=None):
+        """NAC::handle(()) for the learners of mask ((N,) uint8, None: every learner) -> Response.norm (N,) f32, 0 for a learner left out"""
+        out = np.empty(self.N, dtype=np.float32)
+        _abi.check(self._L.rsrl_hip_nac_update(self._h, None if mask is None else _p(_in(mask, np.uint8, (self.N,))), _p(out)))
+        return out
+
     def q_find_max(self, states):
         states, M = self._batch(states)
         idx, val = np.empty(M, dtype=np.int32), np.empty(M, dtype=np.float32)
@@ -393,12 +408,12 @@ class Context:
 
     # ---- Parameterised
     def get_weights(self, env_index=0):
-        out = np.empty((self.F, self.n_out), dtype=np.float32)
+        out = np.empty((self.n_weight_rows, self.n_out), dtype=np.float32)
         _abi.check(self._L.rsrl_hip_get_weights(self._h, int(env_index), _p(out)))
         return out
 
     def set_weights(self, w, env_index=0):
-        _abi.check(self._L.rsrl_hip_set_weights(self._h, int(env_index), _p(_in(w, np.float32, (self.F, self.n_out)))))
+        _abi.check(self._L.rsrl_hip_set_weights(self._h, int(env_index), _p(_in(w, np.float32, (self.n_weight_rows, self.n_out)))))
 
     def get_traces(self, env_index=0):
         out = np.empty((self.F, self.n_out), dtype=np.float32)
@@ -485,7 +500,7 @@ class Context:
         _abi.check(self._L.rsrl_hip_load_weights(self._h, str(path).encode()))
 
     def set_weights_all(self, w):
-        _abi.check(self._L.rsrl_hip_set_weights_all(self._h, _p(_in(w, np.float32, (self.F, self.n_out)))))
+        _abi.check(self._L.rsrl_hip_set_weights_all(self._h, _p(_in(w, np.float32, (self.n_weight_rows, self.n_out)))))
 
     # ---- driver loop
     def train(self, n_steps, want_stats=True):

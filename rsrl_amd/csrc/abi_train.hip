@@ -429,6 +429,9 @@ int launch_agent(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, uint64_t 
     case AgentFamily::TdAcBetaReg:       // (io: the int32 rsrl_hip_handle refuses a continuous ctx before it gets here; rsrl_hip_handle_f32 launches its own)
         ok = !io && launch_tdac_beta(cf.order, c->stream, k, make_tdac_beta(c), t, chunk, d_stats, nullptr);
         break;
+    case AgentFamily::NacBetaReg:        // (io: as above)
+        ok = !io && launch_nac_beta(cf.order, c->stream, k, make_nac_beta(c), t, chunk, d_stats, nullptr);
+        break;
     default: ok = false; break;      // (the shared-W families: enqueue_shared_step)
     }
     if (!ok) return NO_MODEL(c);
@@ -596,7 +599,9 @@ static int rollout_impl(rsrl_hip_ctx* c, int64_t step_limit, int64_t M, uint32_t
         OutBuf<uint32_t> on; OutBuf<float> ot;
         TRY(stage_out(c, 0, n_states_out, (size_t)M, &on));
         TRY(stage_out(c, 1, total_reward_out, (size_t)M, &ot));
-        if (!launch_beta_rollout_mode(c->cfg.order, c->stream, make_common(c), c->Z, step_limit, on.dev, ot.dev)) return NO_MODEL(c);
+        // (NAC: the loop's mapping, Domain::rollout(|s| 2 * policy.mode(s) - 1), nac_beta.rs:81-82)
+        if (!(is_nac(c->cfg.algo) ? launch_nac_rollout_mode(c->cfg.order, c->stream, make_common(c), c->Z, step_limit, on.dev, ot.dev)
+                                  : launch_beta_rollout_mode(c->cfg.order, c->stream, make_common(c), c->Z, step_limit, on.dev, ot.dev))) return NO_MODEL(c);
         KCHECK();
         bool sync = false;
         TRY(flush_out(c, &on, &sync)); TRY(flush_out(c, &ot, &sync));

@@ -131,6 +131,8 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
     if (is_continuous(c) && op != QOP_EVALUATE && op != QOP_FEATURES)
         return fail(RSRL_HIP_ESTATE, "this ctx's domain (ContinuousMountainCar) has one f32 action, not an enumerable set: no action values to search, weigh or "
                                      "index, no action probabilities (the policy side: rsrl_hip_policy_sample_f32 / _mode_f32 / _params / _pdf; V(s): rsrl_hip_q_evaluate)");
+    if (is_nac(c->cfg.algo) && op == QOP_EVALUATE)
+        return fail(RSRL_HIP_ESTATE, "NAC's critic is Q(s, a) over the stable compatible basis: it needs an action (rsrl_hip_q_evaluate_f32)");
     if (is_v_only(c->cfg.algo) && op != QOP_EVALUATE && op != QOP_FEATURES)
         return fail(RSRL_HIP_ESTATE, "a prediction agent has a state-value function only (use rsrl_hip_q_evaluate for V(s))");
     // the TD ActorCritic: its value side is V(s) (no action values to search or weigh), its policy side the actor's theta
@@ -454,7 +456,9 @@ int rsrl_hip_domain_step_f32(rsrl_hip_ctx* c, const float* actions, float* from_
     TRY(stage_out(c, 3, rewards, (size_t)N, &orew));
     TRY(stage_out(c, 4, terminal, (size_t)N, &oterm));
     const Common k = make_common(c);
-    launch_cmc_domain_step(c->stream, k, d_act, c->action_f, ofrom.dev, onext.dev, orew.dev, oterm.dev);
+    // (NAC: explicit actions are the domain's, the pending ones the agent's -- stepped on through the loop's 2a - 1)
+    if (is_nac(c->cfg.algo)) launch_nac_domain_step(c->stream, k, d_act, c->action_f, ofrom.dev, onext.dev, orew.dev, oterm.dev);
+    else launch_cmc_domain_step(c->stream, k, d_act, c->action_f, ofrom.dev, onext.dev, orew.dev, oterm.dev);
     KCHECK();
     bool sync = false;
     TRY(flush_out(c, &ofrom, &sync)); TRY(flush_out(c, &onext, &sync));
@@ -484,7 +488,8 @@ int rsrl_hip_handle_f32(rsrl_hip_ctx* c, const float* from_states, const float* 
     TRY(stage_out(c, 5, td_error_out, (size_t)M, &otd));
     io.M = M; io.td_out = otd.dev;
     const Common k = make_common(c);
-    if (!launch_tdac_beta(c->cfg.order, c->stream, k, make_tdac_beta(c), c->t, 1, nullptr, &io)) return NO_MODEL(c);
+    if (!(is_nac(c->cfg.algo) ? launch_nac_beta(c->cfg.order, c->stream, k, make_nac_beta(c), c->t, 1, nullptr, &io)      // critic.handle: SARSA over SCB
+                              : launch_tdac_beta(c->cfg.order, c->stream, k, make_tdac_beta(c), c->t, 1, nullptr, &io))) return NO_MODEL(c);
     KCHECK();
     c->q_valid = false;
     c->t += 1;          // one handle call = one batch-step, as rsrl_hip_handle
@@ -553,6 +558,45 @@ int rsrl_hip_policy_pdf(rsrl_hip_ctx* c, const float* states, const float* actio
     TRY(beta_batch(c, states, M));
     TRY(check_host_actions_f32(actions, (size_t)M, false));
     return beta_op(c, BETA_OP_PDF, states, M, 0, 0, actions, out, nullptr, nullptr);
+}
+
+// ---- NAC (kernels_nac_beta.hpp): the critic's Function<(S, A)> and the actor's update
+static const char* const kNoNac = "only NAC (RSRL_NAC) has a critic over the stable compatible basis and an actor update of its own";
+int rsrl_hip_q_evaluate_f32(rsrl_hip_ctx* c, const float* states, const float* actions, int64_t M, float* q_out) {
+    CHECK_CTX(c);
+    if (!actions || !q_out) return fail(RSRL_HIP_EINVAL, "null argument");
+    if (!is_nac(c->cfg.algo)) return fail(RSRL_HIP_ESTATE, "%s", kNoNac);
+    FLUSH(c);
+    TRY(beta_batch(c, states, M));
+    TRY(check_host_actions_f32(actions, (size_t)M, false));      // (the score clamps the action to the sample's interval)
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    const float* d_states; const float* d_act; OutBuf<float> oq;
+    TRY(stage_in(c, 0, states, (size_t)c->D * M, &d_states));
+    TRY(stage_in(c, 1, actions, (size_t)M, &d_act));
+    TRY(stage_out(c, 2, q_out, (size_t)M, &oq));
+    if (!launch_nac_q(c->cfg.order, c->stream, make_common(c), make_nac_beta(c), d_states, d_act, M, oq.dev)) return NO_MODEL(c);
+    KCHECK();
+    bool sync = !is_device_ptr(states) || !is_device_ptr(actions);
+    TRY(flush_out(c, &oq, &sync));
+    if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
+    return RSRL_HIP_OK;
+}
+int rsrl_hip_nac_update(rsrl_hip_ctx* c, const uint8_t* mask, float* norm_out) {
+    CHECK_CTX(c);
+    if (!is_nac(c->cfg.algo)) return fail(RSRL_HIP_ESTATE, "%s", kNoNac);
+    FLUSH(c);
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    const size_t N = (size_t)c->cfg.n_envs;
+    const uint8_t* d_mask; OutBuf<float> on;
+    TRY(stage_in(c, 0, mask, N, &d_mask));
+    TRY(stage_out(c, 1, norm_out, N, &on));
+    if (!launch_nac_update(c->cfg.order, c->stream, make_common(c), make_nac_beta(c), d_mask, on.dev)) return NO_MODEL(c);
+    KCHECK();
+    c->q_valid = false;
+    bool sync = mask && !is_device_ptr(mask);
+    TRY(flush_out(c, &on, &sync));
+    if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
+    return RSRL_HIP_OK;
 }
 
 int rsrl_hip_handle_batch(rsrl_hip_ctx* c, int64_t T, const float* states, const int32_t* actions, const float* rewards, const uint32_t* lengths,

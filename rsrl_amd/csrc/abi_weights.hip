@@ -25,11 +25,12 @@ static int staged_rw(rsrl_hip_ctx* c, size_t n, float* out, const float* in, Lau
     return RSRL_HIP_OK;
 }
 // one learner's dense f32[F][cols] matrix out of, or into, a device buffer of W's layout (tile: the tile-coded tables'); wi = the learner's offset in it
-static int matrix_rw(rsrl_hip_ctx* c, float* buf, bool tile, int cols, int64_t wi, float* out, const float* in, bool* synced = nullptr) {
-    const int n = c->F * cols;
+// (rows: F, or the weight matrix's own count -- NAC's 3F)
+static int matrix_rw(rsrl_hip_ctx* c, float* buf, bool tile, int cols, int64_t wi, float* out, const float* in, bool* synced = nullptr, int rows = 0) {
+    const int F = rows ? rows : c->F, n = F * cols;
     return staged_rw(c, (size_t)n, out, in, [&](float* d_out, const float* d_in) {
-        if (d_out) hipLaunchKernelGGL(k_weights_get, dim3((n + 255) / 256), dim3(256), 0, c->stream, buf, tile, c->w_stride, wi, c->F, cols, d_out);
-        else hipLaunchKernelGGL(k_weights_set, dim3((n + 255) / 256), dim3(256), 0, c->stream, buf, tile, c->w_stride, wi, c->F, cols, d_in);
+        if (d_out) hipLaunchKernelGGL(k_weights_get, dim3((n + 255) / 256), dim3(256), 0, c->stream, buf, tile, c->w_stride, wi, F, cols, d_out);
+        else hipLaunchKernelGGL(k_weights_set, dim3((n + 255) / 256), dim3(256), 0, c->stream, buf, tile, c->w_stride, wi, F, cols, d_in);
     }, synced);
 }
 // ... of the order-7 wave family's layout (kernels_wave.hpp): W in the ctx's storage type, the auxiliary matrix always f32
@@ -69,7 +70,7 @@ static int weights_rw(rsrl_hip_ctx* c, int64_t env_index, float* out, const floa
             using WT = typename decltype(tag)::wt;
             rc = wave_matrix_rw(c, (WT*)c->W, env_index, out, in, &synced);
         });
-    } else rc = matrix_rw(c, c->W, c->cfg.basis == RSRL_TILE_CODING, c->Aw, (shared ? 0 : env_index) * c->w_ls, out, in, &synced);
+    } else rc = matrix_rw(c, c->W, c->cfg.basis == RSRL_TILE_CODING, c->Aw, (shared ? 0 : env_index) * c->w_ls, out, in, &synced, c->Fw);
     return rc == RSRL_HIP_OK && synced ? peer_check(c) : rc;      // a failed exchange must not pass for weights
 }
 int rsrl_hip_get_weights(rsrl_hip_ctx* c, int64_t env_index, float* w) {
@@ -220,7 +221,7 @@ struct CkptKind {
     bool reads_kind0;            // a ctx of this kind also reads its configuration's version-2 / aux_kind-0 file, written before the kind's own section
     SectionId sections[3];       // travelled: the weights load, that section's state starts empty
 };
-constexpr int kCkptKinds = 12;
+constexpr int kCkptKinds = 13;
 constexpr CkptKind kCkptKind[kCkptKinds] = {
     /* 0 weights only                           */ {2, 0, true, false, {S_WEIGHTS}},
     /* 1 eligibility traces                     */ {2, 0, true, false, {S_WEIGHTS, S_AUX}},
@@ -234,6 +235,8 @@ constexpr CkptKind kCkptKind[kCkptKinds] = {
     /* 9 the iLSTD ActorCritic: f64 state, theta */ {10, 0, false, false, {S_LSTD, S_AUX}},      // (version 10 too: the aux_kind tells the two apart)
     /* 10 LSTD / LSTDLambda: f64 theta, A, b, z  */ {10, 0, false, false, {S_LSTD, S_LSTD_BATCH}},      // (version 10 as well; S_LSTD: theta, A, then b in mu's place)
     /* 11 the Beta iLSTD ActorCritic: f64 state, the policy's two columns */ {10, 0, false, false, {S_LSTD, S_AUX}},      // (kind 9's sections with f32[F][2] behind them)
+    /* 12 NAC: the critic's w (3F rows), the policy's two columns */ {10, 0, false, false, {S_WEIGHTS, S_AUX}},      // (version 10 as well: load's message names
+                                                                                                                      // the versions read, and tests hold its text)
 };
 // (the kinds the configuration decides, not the algo: SARSALambda / QLambda over ONE shared tile table keep sparse traces instead of Z; the iLSTD
 // ActorCritic with the Beta policy keeps two policy columns instead of the Gibbs actor's A)
@@ -326,7 +329,7 @@ int matrices_io(CkptIo& io, size_t per, LearnerRw rw, bool write) {
     return rc;
 }
 int matrices_size(CkptIo& io, size_t per) { io.expect += io.n_learners * (long long)per * 4; return RSRL_HIP_OK; }
-size_t weights_per(const rsrl_hip_ctx* c) { return c->cfg.algo == RSRL_REINFORCE ? 0 : (size_t)c->F * c->Aw; }
+size_t weights_per(const rsrl_hip_ctx* c) { return c->cfg.algo == RSRL_REINFORCE ? 0 : (size_t)c->Fw * c->Aw; }
 int weights_via_abi(rsrl_hip_ctx* c, int64_t i, float* out, const float* in) { return out ? rsrl_hip_get_weights(c, i, out) : rsrl_hip_set_weights(c, i, in); }
 int weights_size(CkptIo& io) { return matrices_size(io, weights_per(io.c)); }
 int weights_write(CkptIo& io) { return matrices_io(io, weights_per(io.c), weights_via_abi, true); }
@@ -647,7 +650,7 @@ int rsrl_hip_set_weights_all(rsrl_hip_ctx* c, const float* w) {
     if (has_lstd_state(c)) return lstd_weights_rw(c, 0, c->cfg.n_envs, nullptr, w);
     if (c->cfg.weight_mode == RSRL_W_SHARED) return rsrl_hip_set_weights(c, 0, w);
     HIP_TRY(hipSetDevice(c->cfg.device));
-    const int n = c->F * c->Aw, gy = n < 1024 ? n : 1024;
+    const int n = c->Fw * c->Aw, gy = n < 1024 ? n : 1024;
     return staged_rw(c, (size_t)n, nullptr, w, [&](float*, const float* d_w) {
         if (is_wave(c->cfg)) {
             for_wave(c, [&](auto tag) {
@@ -657,7 +660,7 @@ int rsrl_hip_set_weights_all(rsrl_hip_ctx* c, const float* w) {
             });
         } else
         hipLaunchKernelGGL(k_weights_set_all, dim3(grid_for(c->cfg.n_envs), gy), dim3(kBlock), 0, c->stream, c->W, c->cfg.basis == RSRL_TILE_CODING, c->cfg.n_envs, c->cfg.basis == RSRL_TILE_CODING ? c->cfg.n_envs : c->w_stride, c->w_ls,
-                           c->F, c->Aw, d_w);
+                           c->Fw, c->Aw, d_w);
     });
 }
 

@@ -49,7 +49,7 @@ using namespace rsrl;
 
 // ---- THE agent table: what the reference's agent of each rsrl_algo is, one row per number.  Admission (check_config), the ctx's buffers (create_impl),
 // the accessors and the checkpoint read it; a new agent adds its row here, a line of classify() and a case of launch_agent ("Adding an agent").
-enum class Agent : uint8_t { None, OneStep, Lambda, Gq, Pred, QSigma, Ac, TdAc, Reinforce, Lstd, TdAcLstd, Gmc, LstdBatch };      // the group classify() and the kernels' dispatch know it by
+enum class Agent : uint8_t { None, OneStep, Lambda, Gq, Pred, QSigma, Ac, TdAc, Reinforce, Lstd, TdAcLstd, Gmc, LstdBatch, Nac };      // the group classify() and the kernels' dispatch know it by
 enum class Aux : uint8_t { None, LikeW, Policy };      // the second per-learner matrix Z: none, of W's shape, or the actor's A columns next to a one-column W
 struct AlgoRow {
     const char* name = nullptr;      // as the admission messages print it (nullptr: the number is unassigned)
@@ -63,7 +63,7 @@ struct AlgoRow {
     // one of them), the message's words behind it and behind "agent_policy = -1", and what it calls config.n_steps in front of "n_updates" (nullptr: not read)
     int reg_policy = -1; const char* policy_words = ""; const char* shares_words = ""; const char* n_updates = nullptr;
 };
-constexpr AlgoRow kAlgo[RSRL_LSTD_LAMBDA + 1] = {
+constexpr AlgoRow kAlgo[RSRL_NAC + 1] = {
     /*  0 */ {"QLearning", Agent::OneStep},
     /*  1 */ {"SARSA", Agent::OneStep},
     /*  2 */ {"ExpectedSARSA", Agent::OneStep},
@@ -96,6 +96,9 @@ constexpr AlgoRow kAlgo[RSRL_LSTD_LAMBDA + 1] = {
     // (the batch least-squares agents: W as the LSTD agents'; A in lstd_mat, b in lstd_mu, z / singular_solves of their own, the open episodes in rec_s / rec_r)
     /* 25 */ {"LSTD (RSRL_LSTD)", Agent::LstdBatch, true, Aux::None, 10, false, true, RSRL_RANDOM},
     /* 26 */ {"LSTDLambda (RSRL_LSTD_LAMBDA)", Agent::LstdBatch, true, Aux::None, 10, false, true, RSRL_RANDOM},
+    /* 27 */ {},
+    // (W is the SCB critic's one column of 3F rows -- weight_rows() --, the Beta policy's two columns in Z; admitted by check_continuous, not check_reg_only)
+    /* 28 */ {"NAC (RSRL_NAC)", Agent::Nac, true, Aux::Policy, 12},
 };
 // (readers of the table, for configurations check_config has admitted: the algo is a row with a name)
 static inline bool is_lambda(int algo) { return kAlgo[algo].agent == Agent::Lambda; }
@@ -107,6 +110,7 @@ static inline bool is_lstd(int algo) { return kAlgo[algo].agent == Agent::Lstd; 
 static inline bool is_tdac_lstd(int algo) { return kAlgo[algo].agent == Agent::TdAcLstd; }
 static inline bool is_gmc(int algo) { return kAlgo[algo].agent == Agent::Gmc; }
 static inline bool is_lstd_batch(int algo) { return kAlgo[algo].agent == Agent::LstdBatch; }
+static inline bool is_nac(int algo) { return kAlgo[algo].agent == Agent::Nac; }
 // the agents that keep every learner's open episode on the device (rec_s / rec_r, max_episode_steps rows) and sweep it when it ends
 static inline bool keeps_record(int algo) { return is_gmc(algo) || is_lstd_batch(algo); }
 // the agents whose value function is V alone and whose behaviour is Random: no action values to search, weigh, sample from or roll out with
@@ -196,8 +200,10 @@ enum class AgentFamily : uint8_t {
                           // lstd_mu (b) / lstd_z / lstd_sing, the open episodes in rec_s / rec_r
     TdAcBetaReg,          // ActorCritic with the iLSTD critic and the Beta policy on ContinuousMountainCar, Fourier orders 1-5: k_train_tdac_beta
                           // (train_tdac_beta.hip); iLSTD's f64 state as LstdReg's, the policy's two columns in Z, f32 actions in action_f
+    NacBetaReg,           // NAC with the Beta policy and the SCB SARSA critic on ContinuousMountainCar, Fourier orders 1-5: k_train_nac_beta (train_nac_beta.hip),
+                          // one thread per learner; the critic's w in W (3F rows, one column), the policy's two columns in Z, f32 actions in action_f
 };
-constexpr size_t kAgentFamilies = (size_t)AgentFamily::TdAcBetaReg + 1;      // (the enum's last value)
+constexpr size_t kAgentFamilies = (size_t)AgentFamily::NacBetaReg + 1;      // (the enum's last value)
 // ---- THE family table: which kernels serve a family and what they can do, one row per AgentFamily value in the enum's order.  classify() (abi_ctx.hip: a
 // decision) and launch_agent (abi_train.hip: it instantiates the templates) are the two other places a new family is entered.
 enum class Slots : uint8_t { Block, Block64, WaveBlock, Learner, LstdGroup };      // a statistics slot per: kBlock learners, 64 learners (k_train_lambda_mem4; the
@@ -252,6 +258,7 @@ constexpr FamilyRow kFamily[] = {
     {AgentFamily::GmcReg, "k_train_gmc", 4096, Slots::Block, Handle::Agent, 0},      // (handle: refused, whole trajectories only)
     {AgentFamily::LstdBatchReg, "k_train_lstd_batch", 256, Slots::LstdGroup, Handle::Agent, kLstd | kBatchLstd},      // (handle: refused, whole batches only)
     {AgentFamily::TdAcBetaReg, "k_train_tdac_beta", 32, Slots::LstdGroup, Handle::Agent, kPolicyW | kVCritic | kLstd},      // (handle: rsrl_hip_handle_f32)
+    {AgentFamily::NacBetaReg, "k_train_nac_beta", 256, Slots::Block, Handle::Agent, kPolicyW},      // (handle: rsrl_hip_handle_f32; a step is a long scalar chain: 256 as the memory-resident loops)
 };
 constexpr bool family_rows_in_order() {
     for (size_t i = 0; i < sizeof(kFamily) / sizeof(kFamily[0]); ++i) if ((size_t)kFamily[i].family != i) return false;
@@ -286,6 +293,7 @@ struct rsrl_hip_ctx {
     int Ap = 0;                      // columns of the policy's own weights (rsrl_hip_n_policy_outputs): A for the Gibbs actors, 2 for Beta, 0 when the policy reads Q
     float* W = nullptr; float* dW = nullptr;
     int Aw = 0;                      // columns of the weight matrix: A (control) or 1 (prediction: ScalarLFA)
+    int Fw = 0;                      // rows of the weight matrix (rsrl_hip_n_weight_rows): F, or NAC's 3F (the critic's basis is SCB)
     long long* dW_rep = nullptr; int n_rep = 1;  // shared tile coding: n_rep copies of the fixed-point (64-bit) delta table
     long long* sh_tab = nullptr;     // shared-W dense basis: 3 sets x kTabRep copies of the fixed-point delta table (models.hpp DeltaTab)
     long long* h_fx = nullptr;       // shared W: fixed-point delta table of rsrl_hip_handle (one entry per weight)
@@ -463,6 +471,12 @@ static inline TdacLstdState make_tdac_lstd(const rsrl_hip_ctx* c) {
     TdacLstdState ts;
     ts.ls = make_lstd(c); ts.theta = c->Z; ts.alpha = c->cfg.alpha;
     return ts;
+}
+
+static inline NacBetaState make_nac_beta(const rsrl_hip_ctx* c) {
+    NacBetaState ns;
+    ns.pol = c->Z; ns.action = c->action_f; ns.period = (uint32_t)c->cfg.n_steps;
+    return ns;
 }
 
 static inline TdacBetaState make_tdac_beta(const rsrl_hip_ctx* c) {

@@ -387,6 +387,9 @@ __global__ __launch_bounds__(kBlock) void k_beta_rollout_mode(Common c, const fl
     if (total) total[i] = tot;
 }
 
+// (the two kernels below are no templates: a second unit that includes this file for its device functions -- train_nac_beta.hip -- defines
+// RSRL_BETA_DEVICE_FUNCTIONS_ONLY and leaves their one definition to train_tdac_beta.hip)
+#ifndef RSRL_BETA_DEVICE_FUNCTIONS_ONLY
 // Domain::transition on the ctx's envs with f32 actions (k_domain_step's contract); actions == nullptr: the ctx's pending ones
 __global__ __launch_bounds__(kBlock) void k_cmc_domain_step(Common c, const float* __restrict__ actions, const float* __restrict__ pending,
                                                             float* __restrict__ from_out, float* __restrict__ next_out, float* __restrict__ rew_out,
@@ -418,5 +421,6 @@ __global__ void k_cmc_clamp_actions(float* __restrict__ a, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) a[i] = fminf(fmaxf(a[i], -1.0f), 1.0f);
 }
+#endif
 
 }  // namespace rsrl

@@ -7,7 +7,8 @@
 //   rsrl::fa::linear::{basis::Fourier, optim::SGD, LFA}  rsrl/src/fa/linear.rs (re-exports of crate lfa)
 //   rsrl::policies::{Greedy, EpsilonGreedy, Softmax, Random}   rsrl/src/policies/*.rs
 //   rsrl::control::td::{QLearning, SARSA, ExpectedSARSA, PAL, SARSALambda, QLambda, GreedyGQ, QSigma}   rsrl/src/control/td/*.rs
-//   rsrl::make_shared / Shared<T>                              rsrl/src/core.rs:13-44
+//   rsrl::control::nac::NAC, rsrl::fa::linear::basis::SCB, LFA::scalar, control::td::SARSA over them      rsrl/src/control/nac.rs, fa/linear.rs:79-103
+//   rsrl::make_shared / Shared<T>                            rsrl/src/core.rs:13-44
 //
 // Everything is BATCHED: a Domain is N environments, a state is a column of a [D][N] array.  The objects
 // are light descriptors until `bind()` creates the device context (one per (domain, q_func, agent, policy)
@@ -82,6 +83,7 @@ struct Fourier {                          // Fourier::from_space(order, space).w
     Fourier with_bias() const { Fourier f = *this; f.bias = true; return f; }
 };
 struct TileCoding { int n_tilings, tiles_per_dim; };
+struct SCB;                               // (below policies::Beta, which it holds)
 }  // namespace basis
 namespace optim { struct SGD { double lr; explicit SGD(double l) : lr(l) {} }; }
 struct LFA {                              // LFA::vector(basis, SGD(lr), n_actions)  (q_learning.rs:25)
@@ -95,6 +97,7 @@ struct LFA {                              // LFA::vector(basis, SGD(lr), n_actio
     static LFA vector(const basis::TileCoding& b, optim::SGD o, int /*n_actions*/) {
         return LFA{RSRL_TILE_CODING, 0, b.n_tilings, b.tiles_per_dim, o.lr};
     }
+    static inline LFA scalar(const basis::SCB& b, optim::SGD o);      // LFA::scalar(SCB{policy, basis}, SGD(lr)) (nac_beta.rs:38-42; defined below SCB)
 };
 }}  // namespace fa::linear
 
@@ -137,6 +140,15 @@ struct Beta : Policy {
         : Policy{RSRL_BETA}, q(make_shared(fa::linear::LFA::vector(basis, fa::linear::optim::SGD(1.0), 1))) {}
 };
 }  // namespace policies
+
+// SCB { policy, basis } (fa/linear.rs:79-103), the stable compatible basis: project((s, a)) = grad_log pi(a|s) chained with basis.project(s), 3F
+// features over policies::Beta.  LFA::scalar(SCB, SGD(lr)) is the q_func of NAC's SARSA critic (examples/nac_beta.rs)
+namespace fa { namespace linear {
+namespace basis {
+struct SCB { policies::Beta policy; Fourier basis; };
+}  // namespace basis
+inline LFA LFA::scalar(const basis::SCB& b, optim::SGD o) { return LFA::vector(b.basis, o, 1); }
+}}  // namespace fa::linear
 
 // ---- rsrl::control::td -----------------------------------------------------------------------------
 namespace control { namespace td {
@@ -230,6 +242,17 @@ struct ActorCritic : td::Agent {
     static inline ActorCritic tdac(const prediction::lstd::iLSTD& eval, const policies::Beta& policy, double alpha_, double gamma);
 };
 }}  // namespace control::ac
+
+// ---- rsrl::control::nac: NAC::new(critic, policy, alpha) (control/nac.rs) with policies::Beta and a SARSA critic over fa::linear::basis::SCB on
+// domains::ContinuousMountainCar, the agent of examples/nac_beta.rs.  critic: its q_func (the SGD rate) and gamma; it shares the policy, as the
+// example does.  `period`: the loop runs agent.handle(()) at every period-th step of an episode (nac_beta.rs:69 hard-codes 100).  The Session's
+// weights are the critic's w [3F][1]; Session::handle(TransitionF32) is critic.handle, Session::nac_update() agent.handle(())
+namespace control { namespace nac {
+struct NAC : td::Agent {
+    NAC(const td::SARSA& critic, const policies::Beta& /*policy*/, double alpha_, int period = 100)
+        : td::Agent{RSRL_NAC, critic.q_func, critic.gamma, alpha_} { n_steps = period; }
+};
+}}  // namespace control::nac
 
 // ---- rsrl::control::mc: REINFORCE { policy, alpha, gamma } / BaselineREINFORCE { baseline, policy, alpha, gamma }
 // (control/mc/reinforce.rs, control/mc/baseline_reinforce.rs).  Handler<&Batch> only: Session::handle(const Batch&).  The policy is a Gibbs over its
@@ -325,7 +348,7 @@ public:
         cfg.seed = seed; cfg.max_episode_steps = max_episode_steps;
         check(rsrl_hip_create(&cfg, &ctx_));
         D_ = rsrl_hip_state_dim(ctx_); A_ = rsrl_hip_n_actions(ctx_); F_ = rsrl_hip_n_features(ctx_); N_ = env.n_envs;
-        O_ = rsrl_hip_n_outputs(ctx_); P_ = rsrl_hip_n_policy_outputs(ctx_);
+        O_ = rsrl_hip_n_outputs(ctx_); P_ = rsrl_hip_n_policy_outputs(ctx_); R_ = rsrl_hip_n_weight_rows(ctx_);
     }
     ~Session() { rsrl_hip_destroy(ctx_); }
     Session(const Session&) = delete;
@@ -379,7 +402,12 @@ public:
     std::pair<std::vector<float>, std::vector<float>> policy_params(const std::vector<float>& states) {
         std::vector<float> a(N_), b(N_); check(rsrl_hip_policy_params(ctx_, states.data(), N_, a.data(), b.data())); return {a, b};
     }
-    // Domain::rollout(|s| policy.mode(s), Some(limit)).total_reward() for every learner
+    // control::nac::NAC: agent.handle(()) for every learner -> Response.norm; the critic's Function<(S, A)>::evaluate, Q(s_i, a_i) of learner i
+    std::vector<float> nac_update() { std::vector<float> n(N_); check(rsrl_hip_nac_update(ctx_, nullptr, n.data())); return n; }
+    std::vector<float> q_evaluate(const std::vector<float>& states, const std::vector<float>& actions) {
+        std::vector<float> q(N_); check(rsrl_hip_q_evaluate_f32(ctx_, states.data(), actions.data(), N_, q.data())); return q;
+    }
+    // Domain::rollout(|s| policy.mode(s), Some(limit)).total_reward() for every learner (NAC: the loop's |s| 2 * policy.mode(s) - 1)
     std::vector<float> rollout_total_reward(int64_t step_limit) {
         std::vector<uint32_t> n(N_); std::vector<float> tot(N_); check(rsrl_hip_rollout_greedy(ctx_, step_limit, n.data(), tot.data())); return tot;
     }
@@ -443,7 +471,7 @@ public:
     std::vector<float> epsilons() { std::vector<float> e(N_); check(rsrl_hip_get_epsilons(ctx_, e.data())); return e; }   // ... of every learner
     // Parameterised::weights()                                                    (params/mod.rs:118)
     std::vector<float> weights(int64_t env = 0) {
-        std::vector<float> w((size_t)F_ * O_); check(rsrl_hip_get_weights(ctx_, env, w.data())); return w;
+        std::vector<float> w((size_t)R_ * O_); check(rsrl_hip_get_weights(ctx_, env, w.data())); return w;
     }
     // the pub field `trace` of SARSALambda / QLambda                                (sarsa_lambda.rs:41)
     std::vector<float> trace(int64_t env = 0) {
@@ -507,7 +535,7 @@ public:
 
 private:
     rsrl_hip_ctx* ctx_ = nullptr;
-    int D_ = 0, A_ = 0, F_ = 0, O_ = 0, P_ = 0;      // O_: weight columns (A_, or 1 for the prediction agents); P_: the policy's own (A_, or Beta's 2)
+    int D_ = 0, A_ = 0, F_ = 0, O_ = 0, P_ = 0, R_ = 0;      // O_: weight columns (A_, or 1 for the prediction agents); P_: the policy's own (A_, or Beta's 2); R_: weight rows (F_, or NAC's 3 F_)
     int64_t N_ = 0;
 };
 

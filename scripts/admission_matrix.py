@@ -5,7 +5,9 @@ GRID_AGENTS -- the algos numbered after GRID's (13-19) on the same other axes, 7
 configurations) and GRID_AGENTS3 (22 and 23, with max_episode_steps = 200 on every configuration: GradientMC refuses the default 0), each into a
 fixture of its own; and GRID_BETA, the continuous axis: MountainCar and ContinuousMountainCar x the policies Softmax, Random, Beta x the algos iLSTD
 (19), the iLSTD ActorCritic (21) and the unassigned 27, with agent_policy -1 / Softmax / Beta (15 360 configurations) -> create_admission_beta.json
-(tests/test_tdac_beta_cpu.py).
+(tests/test_tdac_beta_cpu.py); and GRID_NAC: ContinuousMountainCar / MountainCar x Softmax / Random / Beta x the algos 21, the unassigned 27 and NAC
+(28) x agent_policy -1 / Beta x the Fourier orders 0-6 x n_steps (NAC's period) 0, 1, 100, 65 536, 65 537 (1 260 configurations) ->
+create_admission_nac.json (tests/test_nac_beta_cpu.py).
     python scripts/admission_matrix.py            writes tests/golden/create_admission.json, create_admission_agents.json,
                                                   create_admission_agents2.json and create_admission_agents3.json
                                                   (tests/test_create_admission_cpu.py, tests/test_tdac_lstd_cpu.py and tests/test_gmc_cpu.py
@@ -25,6 +27,7 @@ AGENTS_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_agents.
 AGENTS2_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_agents2.json")
 AGENTS3_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_agents3.json")
 BETA_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_beta.json")
+NAC_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_nac.json")
 EINVAL, EHIP = -1, -2
 
 # (config field, values): the first axis varies slowest
@@ -62,9 +65,18 @@ GRID_BETA = [
     ("steps_per_launch", [0, 1]),
     ("n_steps", [2, 33]),
 ]
+# NAC (28) beside the iLSTD ActorCritic and the unassigned 27: its one domain and policy beside the others, its period's range and both ends' neighbours
+GRID_NAC = [
+    ("domain", [4, 0]),
+    ("policy", [2, 3, 4]),
+    ("algo", [21, 27, 28]),                  # 27: no such algo
+    ("agent_policy", [-1, 4]),
+    ("order", [0, 1, 2, 3, 4, 5, 6]),
+    ("n_steps", [0, 1, 100, 65536, 65537]),
+]
 # (grid, fixture, fields set on every configuration)
 GRIDS = ((GRID, FIXTURE, {}), (GRID_AGENTS, AGENTS_FIXTURE, {}), (GRID_AGENTS2, AGENTS2_FIXTURE, {}), (GRID_AGENTS3, AGENTS3_FIXTURE, FIXED_AGENTS3),
-         (GRID_BETA, BETA_FIXTURE, {}))
+         (GRID_BETA, BETA_FIXTURE, {}), (GRID_NAC, NAC_FIXTURE, {}))
 
 
 def sweep(grid=GRID, fixed=None):
