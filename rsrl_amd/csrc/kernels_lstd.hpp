@@ -172,6 +172,57 @@ struct LstdLane {
     }
 };
 
+// TDCritic::target (ac.rs:87-98) from an iLSTD lane's UPDATED theta, for the actor-critics that own one (kernels_tdac_lstd.hpp, kernels_tdac_beta.hpp):
+// c = r - V(s') (terminal: V of the terminal state itself) | r + gamma*V(s') - V(s), every product rounded, summed in index order.  Called after
+// LstdLane::step with its phs / phn.  Returns c in f64: the caller rounds e = (float)(alpha * c) itself (with alpha passed in and the product
+// here, k_train_tdac_beta<5> gains two scalar spills).  theta and gamma arrive by REFERENCE: by value they are read before the first wave sync,
+// and k_handle_tdac_lstd<0, 4> then takes 322 registers for 256 (one wave per SIMD for two; profiles/group_frame.md)
+template <int F>
+__device__ __forceinline__ double tdcritic_target(const double& theta, const double& gamma, double (*lv)[F], int r, double phs, double phn,
+                                                  double rew, bool term) {
+    lstd_wave_sync();                                     // (the solve's reads of the slice before it is written again)
+    if (r < F) {
+        lv[LV_X][r] = phs * theta;
+        lv[LV_Y][r] = phn * theta;
+    }
+    lstd_wave_sync();
+    const double v_s = lstd_sum<F>(lv[LV_X]);
+    const double v_n = lstd_sum<F>(lv[LV_Y]);
+    return term ? rew - v_n : rew + gamma * v_n - v_s;
+}
+
+// ---- Handler<&Transition>::handle's prologue in the lane-group layout, shared by k_handle_lstd, k_handle_tdac_lstd and k_handle_tdac_beta: which
+// transition and which row this lane is, the group's LDS slice (the __shared__ array stays declared in the kernel), the return value by lane 0.
+// An AGGREGATE made by here(): with a constructor k_handle_tdac_lstd<0, 5> and its unit's driver loop gain scalar spills (profiles/group_frame.md).
+// The layout's four DRIVER LOOPS (k_train_lstd, k_train_tdac_lstd, k_train_tdac_beta, k_train_lstd_batch) are on no frame: each keeps its own text,
+// with the convention it follows named above it -- on shared learner / tally / episode-end pieces 11 instantiations gained scalar spills
+template <int F, int NVEC>
+struct GroupId {
+    static constexpr int G = LstdGroup<F>::G;
+    int64_t i;             // transition (= learner) of this group; whole groups leave at `i >= Mn`: a group never straddles the bound
+    int r;                 // lane of the group: row r for r < F; lanes r >= F carry no state and write nothing
+
+    __device__ __forceinline__ static GroupId here() {
+        const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        return GroupId{tid / G, (int)(tid % G)};
+    }
+    __device__ __forceinline__ bool own() const { return r < F; }
+    using Slice = double (*)[F];
+    __device__ __forceinline__ Slice slice(double (&lds)[LstdGroup<F>::kPerBlock][NVEC][F]) const { return lds[threadIdx.x / G]; }
+    __device__ __forceinline__ void report(float* __restrict__ td_out, double delta) const { if (td_out && r == 0) td_out[i] = (float)delta; }
+};
+// ... and transition i of the caller's batch of Mn.  The kernel reads the reward where the step reads it, (double)rew[i], and an agent's action itself
+template <int D>
+struct GroupGiven {
+    float s[D], ns[D];
+    bool term;
+    __device__ __forceinline__ void load(const float* __restrict__ from, const float* __restrict__ to, const uint8_t* __restrict__ termf, int64_t Mn, int64_t i) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) { s[d] = from[(int64_t)d * Mn + i]; ns[d] = to[(int64_t)d * Mn + i]; }
+        term = termf[i] != 0;
+    }
+};
+
 // the driver loop (prediction with a Random behaviour policy, as k_train_td): transition, handle, a' ~ Random (BLK_STEP; BLK_RESET after a cap),
 // auto-reset; truncation at max_episode_steps is not terminal.  Every lane of a group steps the learner's environment (the same bits in each);
 // the rows stay in registers for the whole launch
@@ -251,27 +302,22 @@ template <int DOMAIN, int ORDER, int ALGO>
 __global__ __launch_bounds__(kBlock) void k_handle_lstd(LstdState ls, const float* __restrict__ from, const float* __restrict__ rew,
                                                         const float* __restrict__ to, const uint8_t* __restrict__ termf, int64_t Mn,
                                                         float* __restrict__ td_out) {
-    using Dom = Domain<DOMAIN>;
-    constexpr int D = Dom::D, F = FourierReg<DOMAIN, ORDER>::F;
-    constexpr int G = LstdGroup<F>::G;
+    constexpr int D = Domain<DOMAIN>::D, F = FourierReg<DOMAIN, ORDER>::F;
+    using Grp = GroupId<F, LV_N>;
     __shared__ double lds[LstdGroup<F>::kPerBlock][LV_N][F];
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t i = tid / G;
-    const int r = (int)(tid % G);
-    if (i >= Mn) return;                                  // (whole groups: a group never straddles the bound)
-    double (*lv)[F] = lds[threadIdx.x / G];
-    float s[D], ns[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) { s[d] = from[(int64_t)d * Mn + i]; ns[d] = to[(int64_t)d * Mn + i]; }
-    const bool term = termf[i] != 0;
+    const Grp g = Grp::here();
+    if (g.i >= Mn) return;
+    double (*lv)[F] = g.slice(lds);
+    GroupGiven<D> tr;
+    tr.load(from, to, termf, Mn, g.i);
     LstdLane<F, ALGO> L;
-    L.load(ls, i, r);
-    const double phs = lstd_feature<DOMAIN, ORDER>(s, r);
-    const double phn = lstd_feature<DOMAIN, ORDER>(ns, r);
-    if (r < F) lv[LV_PHS][r] = phs;
-    const double delta = L.template step<G>(ls, lv, r, phs, phn, (double)rew[i], term);
-    L.store(ls, i, r);
-    if (td_out && r == 0) td_out[i] = (float)delta;
+    L.load(ls, g.i, g.r);
+    const double phs = lstd_feature<DOMAIN, ORDER>(tr.s, g.r);
+    const double phn = lstd_feature<DOMAIN, ORDER>(tr.ns, g.r);
+    if (g.own()) lv[LV_PHS][g.r] = phs;
+    const double delta = L.template step<Grp::G>(ls, lv, g.r, phs, phn, (double)rew[g.i], tr.term);
+    L.store(ls, g.i, g.r);
+    g.report(td_out, delta);
 }
 
 // V(s) = phi(s) . theta in f64, rounded to f32: state i against learner i's theta, one thread per state

@@ -144,17 +144,8 @@ struct TdacBetaLane {
         // ---- iLSTD::handle
         const double delta = L.template step<G>(ts.ls, lv, r, phs, phn, rew, term);
         // ---- TDCritic::target with the updated theta
-        lstd_wave_sync();                                 // (the solve's reads of the slice before it is written again)
-        if (r < F) {
-            lv[LV_X][r] = phs * L.theta;
-            lv[LV_Y][r] = phn * L.theta;
-        }
-        lstd_wave_sync();
-        const double v_s = lstd_sum<F>(lv[LV_X]);
-        const double v_n = lstd_sum<F>(lv[LV_Y]);
-        const double target = term ? rew - v_n : rew + ts.ls.gamma * v_n - v_s;
+        const float e = (float)(ts.alpha * tdcritic_target<F>(L.theta, ts.ls.gamma, lv, r, phs, phn, rew, term));
         // ---- the actor: this lane's column
-        const float e = (float)(ts.alpha * target);
         float alpha, beta;
         beta_params(xa, xb, alpha, beta);
         const float ac = beta_clamp(a);
@@ -254,30 +245,27 @@ __global__ __launch_bounds__(kBlock) void k_handle_tdac_beta(Common c, TdacBetaS
     using Dom = Domain<kCmc>;
     using Lane = TdacBetaLane<ORDER>;
     using Bas = typename Lane::Bas;
-    constexpr int D = Dom::D, F = Lane::F, G = Lane::G;
+    constexpr int D = Dom::D, F = Lane::F;
     __shared__ double lds[LstdGroup<F>::kPerBlock][LV_N][F];
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t i = tid / G;
-    const int r = (int)(tid % G);
-    if (i >= Mn) return;                                  // (whole groups: a group never straddles the bound)
-    double (*lv)[F] = lds[threadIdx.x / G];
-    float s[D], ns[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) { s[d] = from[(int64_t)d * Mn + i]; ns[d] = to[(int64_t)d * Mn + i]; }
-    const float a = act[i];
-    const bool term = termf[i] != 0;
+    const auto g = GroupId<F, LV_N>::here();
+    const int r = g.r;
+    if (g.i >= Mn) return;
+    double (*lv)[F] = g.slice(lds);
+    GroupGiven<D> tr;
+    tr.load(from, to, termf, Mn, g.i);
+    const float a = act[g.i];
     Lane ln;
-    ln.load(ts, c.n_envs, i, r);
-    const double phs = lstd_feature<kCmc, ORDER>(s, r);
-    const double phn = lstd_feature<kCmc, ORDER>(ns, r);
+    ln.load(ts, c.n_envs, g.i, r);
+    const double phs = lstd_feature<kCmc, ORDER>(tr.s, r);
+    const double phn = lstd_feature<kCmc, ORDER>(tr.ns, r);
     typename Lane::Phi phi_s;
     float xa, xb;
-    ac_project<Bas>(s, phi_s);
+    ac_project<Bas>(tr.s, phi_s);
     ln.prefs(phi_s, xa, xb);
-    if (r < F) lv[LV_PHS][r] = phs;
-    const double delta = ln.step(ts, lv, r, phs, phn, phi_s, xa, xb, a, (double)rew[i], term);
-    ln.store(ts, c.n_envs, i, r);
-    if (td_out && r == 0) td_out[i] = (float)delta;
+    if (g.own()) lv[LV_PHS][r] = phs;
+    const double delta = ln.step(ts, lv, r, phs, phn, phi_s, xa, xb, a, (double)rew[g.i], tr.term);
+    ln.store(ts, c.n_envs, g.i, r);
+    g.report(td_out, delta);
 }
 
 // ---- the policy side on explicit states, one thread per state: state i against learner i's columns (the single-column forms: the bits of the lanes')

@@ -66,17 +66,8 @@ struct TdacLstdLane {
         // ---- iLSTD::handle
         const double delta = L.template step<G>(ts.ls, lv, r, phs, phn, rew, term);
         // ---- TDCritic::target with the updated theta
-        lstd_wave_sync();                                 // (the solve's reads of the slice before it is written again)
-        if (r < F) {
-            lv[LV_X][r] = phs * L.theta;
-            lv[LV_Y][r] = phn * L.theta;
-        }
-        lstd_wave_sync();
-        const double v_s = lstd_sum<F>(lv[LV_X]);
-        const double v_n = lstd_sum<F>(lv[LV_Y]);
-        const double target = term ? rew - v_n : rew + ts.ls.gamma * v_n - v_s;
+        const float e = (float)(ts.alpha * tdcritic_target<F>(L.theta, ts.ls.gamma, lv, r, phs, phn, rew, term));
         // ---- the actor: this lane's column
-        const float e = (float)(ts.alpha * target);
         const int bb = column(r);
         float pb = p_s[0];
 #pragma unroll
@@ -175,30 +166,27 @@ __global__ __launch_bounds__(kBlock) void k_handle_tdac_lstd(Common c, TdacLstdS
     using Dom = Domain<DOMAIN>;
     using Lane = TdacLstdLane<DOMAIN, ORDER>;
     using Bas = typename Lane::Bas;
-    constexpr int D = Dom::D, A = Lane::A, F = Lane::F, G = Lane::G;
+    constexpr int D = Dom::D, A = Lane::A, F = Lane::F;
     __shared__ double lds[LstdGroup<F>::kPerBlock][LV_N][F];
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t i = tid / G;
-    const int r = (int)(tid % G);
-    if (i >= Mn) return;                                  // (whole groups: a group never straddles the bound)
-    double (*lv)[F] = lds[threadIdx.x / G];
-    float s[D], ns[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) { s[d] = from[(int64_t)d * Mn + i]; ns[d] = to[(int64_t)d * Mn + i]; }
-    const int a = clamp_action<A>(act[i]);
-    const bool term = termf[i] != 0;
+    const auto g = GroupId<F, LV_N>::here();
+    const int r = g.r;
+    if (g.i >= Mn) return;
+    double (*lv)[F] = g.slice(lds);
+    GroupGiven<D> tr;
+    tr.load(from, to, termf, Mn, g.i);
+    const int a = clamp_action<A>(act[g.i]);
     Lane ln;
-    ln.load(ts, c.n_envs, i, r);
-    const double phs = lstd_feature<DOMAIN, ORDER>(s, r);
-    const double phn = lstd_feature<DOMAIN, ORDER>(ns, r);
+    ln.load(ts, c.n_envs, g.i, r);
+    const double phs = lstd_feature<DOMAIN, ORDER>(tr.s, r);
+    const double phn = lstd_feature<DOMAIN, ORDER>(tr.ns, r);
     typename Lane::Phi phi_s;
     float p_s[A];
-    ac_project<Bas>(s, phi_s);
+    ac_project<Bas>(tr.s, phi_s);
     ln.probs(c, phi_s, p_s);
-    if (r < F) lv[LV_PHS][r] = phs;
-    const double delta = ln.step(c, ts, lv, r, phs, phn, phi_s, p_s, a, (double)rew[i], term);
-    ln.store(ts, c.n_envs, i, r);
-    if (td_out && r == 0) td_out[i] = (float)delta;
+    if (g.own()) lv[LV_PHS][r] = phs;
+    const double delta = ln.step(c, ts, lv, r, phs, phn, phi_s, p_s, a, (double)rew[g.i], tr.term);
+    ln.store(ts, c.n_envs, g.i, r);
+    g.report(td_out, delta);
 }
 
 }  // namespace rsrl

@@ -27,9 +27,7 @@ __global__ __launch_bounds__(256) void k_lstd_fill_eye(double* __restrict__ mat,
 
 #define RSRL_LSTD_CASE(DM, OR)                                                                                                                  \
     if (domain == DM && order == OR) {                                                                                                          \
-        constexpr int G = LstdGroup<FourierReg<DM, OR>::F>::G;                                                                                  \
-        const int64_t n = io ? io->M : k.n_envs;                                                                                                \
-        const dim3 grid((unsigned)((n * G + kBlock - 1) / kBlock)), block(kBlock);                                                              \
+        const dim3 grid = lstd_grid(io ? io->M : k.n_envs, LstdGroup<FourierReg<DM, OR>::F>::G), block(kBlock);                                 \
         if (io) {                                                                                                                               \
             if (incremental) hipLaunchKernelGGL((k_handle_lstd<DM, OR, LSTD_INCREMENTAL>), grid, block, 0, st, ls, io->from, io->rew, io->to, io->term, io->M, io->td_out); \
             else hipLaunchKernelGGL((k_handle_lstd<DM, OR, LSTD_RECURSIVE>), grid, block, 0, st, ls, io->from, io->rew, io->to, io->term, io->M, io->td_out); \

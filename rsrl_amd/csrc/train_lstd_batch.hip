@@ -15,8 +15,7 @@ namespace rsrl {
 
 #define RSRL_LSTD_BATCH_CASE(DM, OR)                                                                                                            \
     if (domain == DM && order == OR) {                                                                                                          \
-        constexpr int G = LstdGroup<FourierReg<DM, OR>::F>::G;                                                                                  \
-        const dim3 grid((unsigned)((k.n_envs * G + kBlock - 1) / kBlock)), block(kBlock);                                                       \
+        const dim3 grid = lstd_grid(k.n_envs, LstdGroup<FourierReg<DM, OR>::F>::G), block(kBlock);                                              \
         if (lambda) { RSRL_LSTD_BATCH_KERNELS(DM, OR, true) } else { RSRL_LSTD_BATCH_KERNELS(DM, OR, false) }                                   \
         return true;                                                                                                                            \
     }
@@ -29,8 +28,7 @@ bool launch_lstd_batch(int domain, int order, bool lambda, hipStream_t st, const
 
 #define RSRL_LSTD_BATCH_SOLVE_CASE(DM, OR)                                                                                                      \
     if (domain == DM && order == OR) {                                                                                                          \
-        constexpr int G = LstdGroup<FourierReg<DM, OR>::F>::G;                                                                                  \
-        const dim3 grid((unsigned)((N * G + kBlock - 1) / kBlock)), block(kBlock);                                                              \
+        const dim3 grid = lstd_grid(N, LstdGroup<FourierReg<DM, OR>::F>::G), block(kBlock);                                                     \
         if (lambda) hipLaunchKernelGGL((k_lstd_batch_solve<DM, OR, true>), grid, block, 0, st, ls, N);                                          \
         else hipLaunchKernelGGL((k_lstd_batch_solve<DM, OR, false>), grid, block, 0, st, ls, N);                                                \
         return true;                                                                                                                            \

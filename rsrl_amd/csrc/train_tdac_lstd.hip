@@ -10,9 +10,7 @@ namespace rsrl {
 
 #define RSRL_TDAC_LSTD_CASE(DM, OR)                                                                                                             \
     if (domain == DM && order == OR) {                                                                                                          \
-        constexpr int G = LstdGroup<FourierReg<DM, OR>::F>::G;                                                                                  \
-        const int64_t n = io ? io->M : k.n_envs;                                                                                                \
-        const dim3 grid((unsigned)((n * G + kBlock - 1) / kBlock)), block(kBlock);                                                              \
+        const dim3 grid = lstd_grid(io ? io->M : k.n_envs, LstdGroup<FourierReg<DM, OR>::F>::G), block(kBlock);                                 \
         if (io) hipLaunchKernelGGL((k_handle_tdac_lstd<DM, OR>), grid, block, 0, st, k, ts, io->from, io->act, io->rew, io->to, io->term, io->M, io->td_out); \
         else hipLaunchKernelGGL((k_train_tdac_lstd<DM, OR>), grid, block, 0, st, k, ts, t, chunk, stats);                                      \
         return true;                                                                                                                            \
