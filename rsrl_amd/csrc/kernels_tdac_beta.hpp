@@ -65,8 +65,12 @@ __device__ __forceinline__ void beta_params(float xa, float xb, float& alpha, fl
     alpha = softplus_dev(xa) + 1.0f;
     beta = softplus_dev(xb) + 1.0f;
 }
+// (alpha - 1) / (alpha + beta - 2) with the denominator formed as (alpha - 1) + (beta - 1): both differences are exact, where alpha + beta rounds to
+// a multiple of 2^-22 first -- for parameters a few ulps above 1 (preferences in (-17, -10)) that rounding moved the mode by up to a third
+// (tests/fuzz_beta.py's finding)
 __device__ __forceinline__ float beta_mode(float alpha, float beta) {
-    return (alpha > 1.0f && beta > 1.0f) ? (alpha - 1.0f) / (alpha + beta - 2.0f) : alpha / (alpha + beta);
+    const float am = alpha - 1.0f, bm = beta - 1.0f;
+    return (alpha > 1.0f && beta > 1.0f) ? am / (am + bm) : alpha / (alpha + beta);
 }
 __device__ __forceinline__ float beta_clamp(float a) { return fminf(fmaxf(a, kBetaLo), kBetaHi); }      // (NaN -> kBetaLo)
 // the density, through ln Gamma: exp((alpha - 1) ln a + (beta - 1) ln(1 - a) - ln B(alpha, beta)) of the clamped action

@@ -27,7 +27,9 @@ def rand_states(orc, domain, n, rng):
 
 def learner_state(c, i):
     """everything learner i learns, name -> array: the f64 least-squares state, the value weights (REINFORCE has none; BaselineREINFORCE's are its
-    baseline; the iLSTD agents' are f32(lstd_theta) and left out), the actor's theta, REINFORCE's behaviour snapshot"""
+    baseline; the iLSTD agents' are f32(lstd_theta) and left out; LSTD's and LSTDLambda's f32(lstd_theta) stay next to theta / A / b / z and the
+    singular counter; NAC's are the critic's 3F rows), the actor's theta (the Gibbs actor's A columns, the Beta policy's two), REINFORCE's
+    behaviour snapshot"""
     al, out = c.cfg.algo, {}
     if al in (ra.RECURSIVE_LSTD, ra.ILSTD, ra.ILSTD_ACTOR_CRITIC):
         out["lstd_theta"], out["lstd_matrix"], mu = c.get_lstd_state(i)
@@ -35,7 +37,12 @@ def learner_state(c, i):
             out["lstd_mu"] = mu
     elif al != ra.REINFORCE:
         out["weights"] = c.get_weights(i)
-    if al in (ra.ACTOR_CRITIC, ra.Q_ACTOR_CRITIC, ra.TD_ACTOR_CRITIC, ra.REINFORCE, ra.BASELINE_REINFORCE, ra.ILSTD_ACTOR_CRITIC):
+    if al in (ra.LSTD, ra.LSTD_LAMBDA):
+        out["lstd_theta"], out["lstd_A"], out["lstd_b"], z, sing = c.get_lstd_batch_state(i)
+        if z is not None:
+            out["lstd_z"] = z
+        out["singular_solves"] = np.array(sing, dtype=np.uint32)
+    if al in (ra.ACTOR_CRITIC, ra.Q_ACTOR_CRITIC, ra.TD_ACTOR_CRITIC, ra.REINFORCE, ra.BASELINE_REINFORCE, ra.ILSTD_ACTOR_CRITIC, ra.NAC):
         out["theta"] = c.get_policy_weights(i)
     if al in (ra.REINFORCE, ra.BASELINE_REINFORCE):
         out["theta_b"] = c.get_behaviour_weights(i)
@@ -89,6 +96,58 @@ def trait_loop(c, K, cap):
         ep[mask == 1] = 0
         c.policy_sample()
     c.episode_steps = ep.astype(np.uint32)
+
+
+def record_bits(c):
+    """the episode record of GradientMC / LSTD / LSTDLambda as bit patterns with the learner on axis 0, where every per-learner entry joins:
+    name -> uint32 array (N, cap, D) / (N, cap).  The accessor shows NaN past each learner's rows, which `diff` refuses raw"""
+    s, r = c.episode_record
+    return dict(record_states=np.moveaxis(np.ascontiguousarray(s).view(np.uint32), -1, 0), record_rewards=np.moveaxis(np.ascontiguousarray(r).view(np.uint32), -1, 0))
+
+
+def gmc_trait_loop(c, K, cap):
+    """GradientMC: domain_step -> append (from, r) on the host -> handle_batch(the length of the episodes that just ended, else 0) ->
+    domain_reset(ended) -> policy_sample(); at the end the open rows become the ctx's record"""
+    D = c.D
+    S, R = np.zeros((cap, D, c.N), np.float32), np.zeros((cap, c.N), np.float32)
+    ep = c.episode_steps.astype(np.int64)
+    cols = np.arange(c.N)
+    for _ in range(K):
+        frm, _, rew, term = c.domain_step(c.actions)
+        S[ep, :, cols] = frm.T
+        R[ep, cols] = rew
+        ep += 1
+        ended = term.astype(bool) | (ep >= cap)
+        c.handle_batch(S, None, R, np.where(ended, ep, 0).astype(np.uint32))
+        c.domain_reset(ended.astype(np.uint8))
+        ep[ended] = 0
+        c.policy_sample()
+    c.episode_steps = ep.astype(np.uint32)
+    c.episode_record = (S, R)
+
+
+def lstd_batch_trait_loop(c, K, cap):
+    """LSTD / LSTDLambda: domain_step -> append the transition on the host -> handle_transitions(the length of the episodes that just ended,
+    else 0) -> domain_reset(ended) -> policy_sample(); at the end the open rows become the ctx's record"""
+    D = c.D
+    S, S2 = np.zeros((cap, D, c.N), np.float32), np.zeros((cap, D, c.N), np.float32)
+    R, Tm = np.zeros((cap, c.N), np.float32), np.zeros((cap, c.N), np.uint8)
+    ep = c.episode_steps.astype(np.int64)
+    cols = np.arange(c.N)
+    for _ in range(K):
+        frm, nxt, rew, term = c.domain_step(c.actions)
+        S[ep, :, cols] = frm.T
+        S2[ep, :, cols] = nxt.T
+        R[ep, cols] = rew
+        Tm[ep, cols] = term
+        ep += 1
+        ended = term.astype(bool) | (ep >= cap)
+        c.handle_transitions(S, R, S2, Tm, np.where(ended, ep, 0).astype(np.uint32))
+        c.domain_reset(ended.astype(np.uint8))
+        ep[ended] = 0
+        c.policy_sample()
+    c.episode_steps = ep.astype(np.uint32)
+    c.episode_record = (S, R)
 
 
 def check_train_invariance(make_ctx, kw, K, cap, depths, first_split, kernel=None, setup=None, trait=trait_loop):

@@ -2,7 +2,8 @@
 """Adversarial campaign against the C ABI: configurations with out-of-range, non-finite and contradictory fields, and calls with null pointers, learner
 indices and batch sizes out of range, non-finite states, actions outside the action set.  Whatever comes in, every entry point must RETURN (an error
 code with a message, or success) -- no crash, no hang, no NaN-poisoned neighbour: after every abuse a small healthy ctx on the same device must still
-train to the same checksum.
+train to the same checksum.  After the random cases, late_agents_leg aims a fixed list of such arguments at the entry points of GradientMC, LSTD,
+LSTDLambda, the Beta iLSTD ActorCritic and NAC.
 
     python tests/fuzz_abi.py [n_cases=300] [seed=0]        (GPU box; each case runs in this process: a crash ends the campaign with its number)"""
 import ctypes as C
@@ -151,6 +152,146 @@ def poke(L, h, rng, log):
     L.rsrl_hip_sync(h)
 
 
+LATE = {"GradientMC": dict(domain=0, order=3, algo=23, policy=3, max_episode_steps=7, lr=0.01),
+        "LSTD": dict(domain=0, order=2, algo=25, policy=3, max_episode_steps=7),
+        "LSTDLambda": dict(domain=1, order=1, algo=26, policy=3, max_episode_steps=5, lam=0.8),
+        "BetaActorCritic": dict(domain=4, order=3, algo=21, policy=4, n_steps=2, lr=0.02, alpha=0.2, max_episode_steps=9),
+        "NAC": dict(domain=4, order=2, algo=28, policy=4, n_steps=3, lr=0.01, alpha=0.1, max_episode_steps=9)}
+
+
+def late_agents_leg(L, rng):
+    """the entry points of the five newest agents -- the *_f32 twins, handle_transitions, handle_batch on GradientMC, lstd_solve, nac_update, the
+    episode-record accessors, policy_params, policy_pdf, set_lstd_batch_state, set_episode_steps -- with arguments the ABI's validation is documented
+    to reject (null pointers, T < 0, a huge T with no arrays, lengths above T, non-finite f32 actions, batch sizes outside [1, n_envs], episode_steps
+    above the cap, the int32 calls on the continuous domain and the f32 ones on a discrete one) or to accept (lengths of T rows above the cap, finite
+    actions outside [0, 1], non-finite A / b / z, an all-zero mask, T = 0).  Every call returns; a refusal (rc != 0) moves nothing (checksum).
+    -> (findings, {agent: [calls, refused]})"""
+    bad, tally = [], {}
+    p = lambda a: a.ctypes.data_as(C.c_void_p)       # noqa: E731
+    for name, kw in LATE.items():
+        N = int(rng.choice([5, 66]))
+        with ra.Context(n_envs=N, seed=int(rng.integers(1 << 20)), env_offset=int(rng.choice([0, (1 << 31) - 3])), **kw) as c:
+            h, D, F, cap, al = c._h, c.D, c.F, kw["max_episode_steps"], kw["algo"]
+            c.reset()
+            c.train(4, want_stats=False)
+            nonfin = float(rng.choice([np.nan, np.inf, -np.inf]))
+            T = 3
+            S, R = np.zeros((T, D, N), np.float32), np.zeros((T, N), np.float32)
+            S[:, 0, :] = -0.5
+            Tm, ln, over = np.zeros((T, N), np.uint8), np.full(N, T, np.uint32), np.full(N, T, np.uint32)
+            over[int(rng.integers(0, N))] = T + 1
+            td, ai, out_i = np.zeros((cap + 3, N), np.float32), np.zeros(N, np.int32), np.zeros(N, np.int32)
+            s1, af, r1, t1, o1, o2 = S[0].copy(), np.full(N, 0.5, np.float32), np.zeros(N, np.float32), np.zeros(N, np.uint8), np.zeros(N, np.float32), np.zeros(N, np.float32)
+            a_nonfin, a_out = af.copy(), af.copy()
+            a_nonfin[int(rng.integers(0, N))] = nonfin
+            a_out[int(rng.integers(0, N))] = float(rng.choice([-3.0, 1.5, 1e30]))
+            steps_over = np.zeros(N, np.uint32)
+            steps_over[int(rng.integers(0, N))] = cap + 1
+            Sl, Rl = np.zeros((cap + 3, D, N), np.float32), np.zeros((cap + 3, N), np.float32)
+            Sl[:, 0, :] = -0.5
+            theta, A, b, z, sing = np.zeros(F), np.full((F, F), nonfin), np.full(F, nonfin), np.full(F, nonfin), np.zeros(1, np.uint32)
+            rec_s, rec_r = np.zeros((cap, D, N), np.float32), np.zeros((cap, N), np.float32)
+            calls = [  # (what, the call, the codes it may return: None = any refusal, 0 = must succeed)
+                ("handle_transitions T < 0", lambda: L.rsrl_hip_handle_transitions(h, -1, p(S), None, p(R), p(S), p(Tm), p(ln), None), None),
+                ("handle_transitions huge T, no arrays", lambda: L.rsrl_hip_handle_transitions(h, 2 ** 40, None, None, None, None, None, p(ln), None), None),
+                ("handle_transitions null lengths", lambda: L.rsrl_hip_handle_transitions(h, T, p(S), None, p(R), p(S), p(Tm), None, None), None),
+                ("handle_transitions null rewards", lambda: L.rsrl_hip_handle_transitions(h, T, p(S), None, None, p(S), p(Tm), p(ln), None), None),
+                ("handle_transitions lengths above T", lambda: L.rsrl_hip_handle_transitions(h, T, p(S), None, p(R), p(S), p(Tm), p(over), None), None),
+                ("handle_batch T < 0", lambda: L.rsrl_hip_handle_batch(h, -7, p(S), None, p(R), p(ln), None), None),
+                ("handle_batch huge T, no arrays", lambda: L.rsrl_hip_handle_batch(h, 2 ** 40, None, None, None, p(ln), None), None),
+                ("handle_batch lengths above T", lambda: L.rsrl_hip_handle_batch(h, T, p(S), None, p(R), p(over), None), None),
+                ("handle_batch null lengths", lambda: L.rsrl_hip_handle_batch(h, T, p(S), None, p(R), None, None), None),
+                ("set_episode_steps above the cap", lambda: L.rsrl_hip_set_episode_steps(h, p(steps_over)), None if al in (23, 25, 26) else 0),
+                ("set_episode_steps null", lambda: L.rsrl_hip_set_episode_steps(h, None), None),
+                ("get_episode_record null", lambda: L.rsrl_hip_get_episode_record(h, None, p(rec_r)), None),
+                ("set_episode_record null", lambda: L.rsrl_hip_set_episode_record(h, p(rec_s), None), None),
+                ("get_lstd_batch_state out of range", lambda: L.rsrl_hip_get_lstd_batch_state(h, N, p(theta), p(A.copy()), p(b.copy()), None, p(sing)), None),
+                ("set_lstd_batch_state null A", lambda: L.rsrl_hip_set_lstd_batch_state(h, 0, p(theta), None, p(b), None, p(sing)), None),
+                ("set_lstd_batch_state index -1", lambda: L.rsrl_hip_set_lstd_batch_state(h, -1, p(theta), p(A), p(b), p(z), p(sing)), None),
+                ("handle_f32 null actions", lambda: L.rsrl_hip_handle_f32(h, p(s1), None, p(r1), p(s1), p(t1), N, p(o1)), None),
+                ("handle_f32 M = 0", lambda: L.rsrl_hip_handle_f32(h, p(s1), p(af), p(r1), p(s1), p(t1), 0, p(o1)), None),
+                ("handle_f32 M > N", lambda: L.rsrl_hip_handle_f32(h, p(s1), p(af), p(r1), p(s1), p(t1), N + 1, p(o1)), None),
+                ("handle_f32 non-finite action", lambda: L.rsrl_hip_handle_f32(h, p(s1), p(a_nonfin), p(r1), p(s1), p(t1), N, p(o1)), None),
+                ("set_actions_f32 non-finite", lambda: L.rsrl_hip_set_actions_f32(h, p(a_nonfin)), None),
+                ("set_actions_f32 out of bounds", lambda: L.rsrl_hip_set_actions_f32(h, p(a_out)), None),
+                ("set_actions_f32 null", lambda: L.rsrl_hip_set_actions_f32(h, None), None),
+                ("domain_step_f32 non-finite action", lambda: L.rsrl_hip_domain_step_f32(h, p(a_nonfin), p(s1.copy()), p(s1.copy()), p(r1), p(t1)), None),
+                ("policy_sample_f32 null out", lambda: L.rsrl_hip_policy_sample_f32(h, p(s1), N, None), None),
+                ("policy_sample_f32 own envs, M != N", lambda: L.rsrl_hip_policy_sample_f32(h, None, N - 1, p(o1)), None),
+                ("policy_mode_f32 M < 0", lambda: L.rsrl_hip_policy_mode_f32(h, p(s1), -4, p(o1)), None),
+                ("policy_params null states", lambda: L.rsrl_hip_policy_params(h, None, N, p(o1), p(o2)), None),
+                ("policy_params null out", lambda: L.rsrl_hip_policy_params(h, p(s1), N, p(o1), None), None),
+                ("policy_params M > N", lambda: L.rsrl_hip_policy_params(h, p(s1), N + 9, p(o1), p(o2)), None),
+                ("policy_pdf non-finite action", lambda: L.rsrl_hip_policy_pdf(h, p(s1), p(a_nonfin), N, p(o1)), None),
+                ("policy_pdf null actions", lambda: L.rsrl_hip_policy_pdf(h, p(s1), None, N, p(o1)), None),
+                ("q_evaluate_f32 non-finite action", lambda: L.rsrl_hip_q_evaluate_f32(h, p(s1), p(a_nonfin), N, p(o1)), None),
+                ("q_evaluate_f32 M = 0", lambda: L.rsrl_hip_q_evaluate_f32(h, p(s1), p(af), 0, p(o1)), None),
+            ]
+            if al in (21, 28):       # the int32 calls on the continuous domain
+                calls += [("handle (int32)", lambda: L.rsrl_hip_handle(h, p(s1), p(ai), p(r1), p(s1), p(t1), N, p(o1)), None),
+                          ("set_actions (int32)", lambda: L.rsrl_hip_set_actions(h, p(ai)), None), ("get_actions (int32)", lambda: L.rsrl_hip_get_actions(h, p(out_i)), None),
+                          ("policy_sample (int32)", lambda: L.rsrl_hip_policy_sample(h, p(s1), N, p(out_i)), None),
+                          ("domain_step (int32)", lambda: L.rsrl_hip_domain_step(h, p(ai), p(s1.copy()), p(s1.copy()), p(r1), p(t1)), None),
+                          ("handle_transitions", lambda: L.rsrl_hip_handle_transitions(h, T, p(S), None, p(R), p(S), p(Tm), p(ln), None), None),
+                          ("lstd_solve", lambda: L.rsrl_hip_lstd_solve(h), None), ("get_episode_record", lambda: L.rsrl_hip_get_episode_record(h, p(rec_s), p(rec_r)), None),
+                          # ... and what it accepts: finite actions outside [0, 1] are clamped by the update, the score and the density
+                          ("handle_f32 actions outside [0, 1]", lambda: L.rsrl_hip_handle_f32(h, p(s1), p(a_out), p(r1), p(s1), p(t1), N, p(o1)), 0),
+                          ("policy_pdf actions outside [0, 1]", lambda: L.rsrl_hip_policy_pdf(h, p(s1), p(a_out), N, p(o1)), 0),
+                          ("policy_params", lambda: L.rsrl_hip_policy_params(h, p(s1), N, p(o1), p(o2)), 0)]
+            else:                    # ... and the f32 ones on a discrete one
+                calls += [("handle_f32", lambda: L.rsrl_hip_handle_f32(h, p(s1), p(af), p(r1), p(s1), p(t1), N, p(o1)), None),
+                          ("get_actions_f32", lambda: L.rsrl_hip_get_actions_f32(h, p(o1)), None), ("set_actions_f32", lambda: L.rsrl_hip_set_actions_f32(h, p(af)), None),
+                          ("policy_sample_f32", lambda: L.rsrl_hip_policy_sample_f32(h, p(s1), N, p(o1)), None),
+                          ("policy_params", lambda: L.rsrl_hip_policy_params(h, p(s1), N, p(o1), p(o2)), None),
+                          ("policy_pdf", lambda: L.rsrl_hip_policy_pdf(h, p(s1), p(af), N, p(o1)), None),
+                          ("q_evaluate_f32", lambda: L.rsrl_hip_q_evaluate_f32(h, p(s1), p(af), N, p(o1)), None),
+                          ("nac_update", lambda: L.rsrl_hip_nac_update(h, None, p(o1)), None)]
+            if al == 28:
+                calls += [("nac_update, an all-zero mask", lambda: L.rsrl_hip_nac_update(h, p(np.zeros(N, np.uint8)), p(o1)), 0),
+                          ("q_evaluate_f32 actions outside [0, 1]", lambda: L.rsrl_hip_q_evaluate_f32(h, p(s1), p(a_out), N, p(o1)), 0)]
+            else:
+                calls += [("nac_update", lambda: L.rsrl_hip_nac_update(h, None, p(o1)), None), ("q_evaluate_f32", lambda: L.rsrl_hip_q_evaluate_f32(h, p(s1), p(af), N, p(o1)), None)]
+            if al == 23:
+                calls += [("handle_batch, T rows above the cap", lambda: L.rsrl_hip_handle_batch(h, cap + 3, p(Sl), None, p(Rl), p(np.full(N, cap + 3, np.uint32)), p(td)), 0),
+                          ("handle_batch T = 0", lambda: L.rsrl_hip_handle_batch(h, 0, None, None, None, p(np.zeros(N, np.uint32)), None), 0),
+                          ("handle_transitions", lambda: L.rsrl_hip_handle_transitions(h, T, p(S), None, p(R), p(S), p(Tm), p(ln), None), None),
+                          ("lstd_solve", lambda: L.rsrl_hip_lstd_solve(h), None)]
+            if al in (25, 26):
+                calls += [("handle_batch", lambda: L.rsrl_hip_handle_batch(h, T, p(S), None, p(R), p(ln), None), None),
+                          ("handle_transitions, T rows above the cap", lambda: L.rsrl_hip_handle_transitions(h, cap + 3, p(Sl), None, p(Rl), p(Sl), p(np.zeros((cap + 3, N), np.uint8)),
+                                                                                                       p(np.full(N, cap + 3, np.uint32)), p(td)), 0),
+                          ("set_lstd_batch_state non-finite A, b, z", lambda: L.rsrl_hip_set_lstd_batch_state(h, N - 1, p(theta), p(A), p(b), p(z) if al == 26 else None, p(sing)), 0),
+                          ("lstd_solve over a non-finite matrix", lambda: L.rsrl_hip_lstd_solve(h), 0),
+                          ("handle_transitions onto a non-finite matrix", lambda: L.rsrl_hip_handle_transitions(h, T, p(S), None, p(R), p(S), p(Tm), p(ln), None), 0)]
+            n_ref = 0
+            order = list(rng.permutation(len(calls)))
+            for j in order:
+                what, call, want = calls[int(j)]
+                before = c.checksum()
+                rc = call()
+                L.rsrl_hip_sync(h)
+                if not isinstance(rc, int):
+                    bad.append(f"{name}: {what} returned {rc!r}")
+                elif want == 0 and rc != 0:
+                    bad.append(f"{name}: {what} refused with {rc}: {(L.rsrl_hip_last_error() or b'').decode()[:80]}")
+                elif want is None and rc == 0:
+                    bad.append(f"{name}: {what} was accepted")
+                if rc != 0:
+                    n_ref += 1
+                    if c.checksum() != before:
+                        bad.append(f"{name}: {what} was refused ({rc}) and moved the ctx")
+            if al in (25, 26):                                    # (in this order, whatever the permutation above made of it)
+                rcs = [L.rsrl_hip_set_lstd_batch_state(h, N - 1, p(theta), p(A), p(b), p(z) if al == 26 else None, p(sing)), L.rsrl_hip_lstd_solve(h)]
+                if rcs != [0, 0] or c.get_lstd_batch_state(N - 1)[4] != 1:
+                    bad.append(f"{name}: the solve of a non-finite matrix was not counted as abandoned ({rcs})")
+            rc = L.rsrl_hip_train(h, 3, None)                     # the ctx still trains (whatever it learnt from the garbage it accepted)
+            L.rsrl_hip_sync(h)
+            if rc != 0:
+                bad.append(f"{name}: train after the leg: {rc}")
+            tally[name] = [len(calls), n_ref]
+    return bad, tally
+
+
 def draw_config(L, rng):
     """a plausible base, then 0-4 fields pushed out of range"""
     cfg = _abi.Config()
@@ -215,10 +356,17 @@ def main():
         if not ok:
             print("SUMMARY " + json.dumps({"cases": idx + 1, "failed_at": idx, "log": log}), flush=True)
             sys.exit(1)
+    # the five newest agents' entry points, then the healthy ctx once more
+    failures, late = late_agents_leg(L, rng)
+    if healthy_checksum() != ref:
+        failures.append("the healthy ctx changed after the late agents' leg")
+    for f in failures:
+        print("LATE " + f, flush=True)
     # null handles
     for fn in ("rsrl_hip_reset", "rsrl_hip_sync", "rsrl_hip_destroy"):
         getattr(L, fn)(None)
-    print("SUMMARY " + json.dumps({"cases": n_cases, "seed": seed, "created": created, "refused": refused, "failures": []}), flush=True)
+    print("SUMMARY " + json.dumps({"cases": n_cases, "seed": seed, "created": created, "refused": refused, "late": late, "failures": failures}), flush=True)
+    sys.exit(1 if failures else 0)
 
 
 if __name__ == "__main__":

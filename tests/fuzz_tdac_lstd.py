@@ -9,7 +9,7 @@ episode caps and launch depths.  Legs:
     self     one uninterrupted train() against random splits with policy queries between them (which must change nothing), the host trait loop,
              two env_offset shards, and a checkpoint saved and resumed -- bit for bit
 
-    python tests/fuzz_tdac_lstd.py [n_cases=100] [seed=0]          (GPU box; test infrastructure: imports oracle/)
+    python tests/fuzz_tdac_lstd.py [n_cases=100] [seed=0] [agents=21]          (GPU box; test infrastructure: imports oracle/)
 
 One line per case and a SUMMARY {json} line; exit code 1 on any mismatch."""
 import json
@@ -29,6 +29,7 @@ from tests.tdac_lstd_numpy import tdac_lstd_rule  # noqa: E402
 
 REG = [(0, o) for o in (1, 2, 3, 4, 5)] + [(1, 1), (2, 1)]
 EPS64 = np.finfo(np.float64).eps
+NAME = "iLSTDActorCritic"
 
 
 def draw_config(rng):
@@ -140,17 +141,34 @@ def leg_self(kw, rng):
 
 
 def main():
-    n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+    pos = [a for a in sys.argv[1:] if "=" not in a]
+    n_cases = int(pos[0]) if len(pos) > 0 else 100
+    seed = int(pos[1]) if len(pos) > 1 else 0
+    agents = [a[7:] for a in sys.argv[1:] if a.startswith("agents=")]
+    if agents and agents[0] not in ("21", NAME):                    # (the one agent of this campaign: the argument exists for the suite's uniform call)
+        sys.exit(f"agents= must be 21 or {NAME}")
     rng = np.random.default_rng(seed)
-    fails = 0
+    counts, failures = {}, []
     for case in range(n_cases):
         kw = draw_config(rng)
-        bad = [("f64", x) for x in leg_f64(kw, rng)] + [("self", x) for x in leg_self(kw, rng)]
-        fails += bool(bad)
+        try:
+            with ra.Context(**kw):
+                pass
+        except ra.RsrlHipError as e:
+            counts["refused"] = counts.get("refused", 0) + 1
+            print(f"case {case}: REFUSED {str(e)[:90]} {json.dumps(kw)}", flush=True)
+            continue
+        try:
+            bad = [("f64", x) for x in leg_f64(kw, rng)] + [("self", x) for x in leg_self(kw, rng)]
+        except Exception as e:      # noqa: BLE001
+            bad = [("error", f"{type(e).__name__}: {str(e)[:200]}")]
+        status = "MISMATCH" if bad else "ok"
+        counts[status] = counts.get(status, 0) + 1
+        if bad:
+            failures.append({"case": case, "legs": bad, "config": kw})
         print(f"case {case}: {'FAIL ' + json.dumps(bad) if bad else 'ok'} {json.dumps(kw)}", flush=True)
-    print("SUMMARY " + json.dumps(dict(cases=n_cases, seed=seed, failed=fails)), flush=True)
-    sys.exit(1 if fails else 0)
+    print("SUMMARY " + json.dumps(dict(cases=n_cases, seed=seed, counts=counts, per_agent={NAME: counts}, failures=failures, failed=len(failures))), flush=True)
+    sys.exit(1 if failures else 0)
 
 
 if __name__ == "__main__":

@@ -91,3 +91,51 @@ def test_random_configurations_of_the_newer_agents():
     for name in ("ActorCritic", "QActorCritic", "TDActorCritic", "REINFORCE", "BaselineREINFORCE", "RecursiveLSTD", "iLSTD"):
         assert per.get(name, {}).get("ok", 0) >= 20, (name, per)
     assert sum(v.get("ok", 0) for k, v in per.items() if k.startswith("HIV/")) >= 20, per
+
+
+def _campaign_slice(script, agent):
+    """one agent's slice of a campaign script as a subprocess -> its SUMMARY; asserts what every slice asserts: exit code 0, no failure, every
+    sampled configuration created, at least 20 of the 24 cases ok for the agent, and at most 5 % of the replayed learner-rounds left out"""
+    from tests.fuzz_episodic import SUITE_CASES, SUITE_SEED      # (24 cases on one seed: tests/test_fuzz_late_cpu.py checks the same slice's shares)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", script), str(SUITE_CASES), str(SUITE_SEED), "agents=" + agent], capture_output=True,
+                       text=True, timeout=600)
+    line = [l for l in p.stdout.splitlines() if l.startswith("SUMMARY ")]
+    assert line, (p.stdout[-2000:], p.stderr[-2000:])
+    d = json.loads(line[0][8:])
+    print(agent, d["counts"], d.get("legs"), d.get("worst"))
+    assert p.returncode == 0 and not d["failures"], d["failures"][:3]
+    assert d["counts"].get("refused", 0) == 0, d["counts"]
+    assert d["per_agent"].get(agent, {}).get("ok", 0) >= 20, d["per_agent"]
+    replayed = d.get("replayed", sum(w.get("replayed", 0) for w in d.get("worst", {}).values() if isinstance(w, dict)))
+    assert d.get("left_out", 0) <= 0.05 * max(replayed, 1), (d.get("left_out"), replayed)
+    return d
+
+
+@pytest.mark.parametrize("agent", ["GradientMC", "LSTD", "LSTDLambda"])
+def test_random_configurations_of_the_episode_record_agents(agent):
+    # tests/fuzz_episodic.py: GradientMC, LSTD and LSTDLambda on every register-family order at random learner counts (idle and ragged lane groups),
+    # env offsets up to the top of the id range, caps from 1 (every step ends an episode) to 200 (the record never closes) and launch depths:
+    # handle_batch / handle_transitions on ragged batches against td_chain (bit for bit) and the f64 rules, lstd_solve against lu_solve bit for bit
+    # with crafted matrices planted, train against its splits with read-only calls between them, the host trait loop, shards and a checkpoint with
+    # the record carried -- bit for bit, the f64 state and the record included -- and the environment side against RSRL_TD's.
+    d = _campaign_slice("fuzz_episodic.py", agent)
+    assert d["counts"].get("diverged", 0) == 0, d["counts"]          # (at most 2 % of the LSTD cases: none of 24)
+    assert d["legs"]["batch"] >= 20 and d["legs"]["trait"] >= 20 and d["legs"]["ckpt"] >= 20 and d["legs"]["env"] >= 20 and d["legs"].get("shard", 0) >= 3, d["legs"]
+
+
+def test_random_configurations_of_the_ilstd_actor_critic():
+    # tests/fuzz_tdac_lstd.py: the iLSTD ActorCritic (21) on the discrete domains -- handle against the f64 rule and an iLSTD ctx bit for bit,
+    # train against its splits, the trait loop, shards and a checkpoint.
+    _campaign_slice("fuzz_tdac_lstd.py", "iLSTDActorCritic")
+
+
+@pytest.mark.parametrize("agent", ["BetaActorCritic", "NAC"])
+def test_random_configurations_of_the_beta_policy_agents(agent):
+    # tests/fuzz_beta.py: the Beta iLSTD ActorCritic and NAC on ContinuousMountainCar, orders 1-5, with policy columns in every branch of the device's
+    # Softplus and actions on the clamp: handle on partial batches (the critic half bit for bit an iLSTD ctx's; the columns, w, delta and Q against the
+    # f64 rules), nac_update bit for bit under a random mask and next to the norm's floor, the policy side against the f64 restatement, and train against
+    # its splits with read-only calls between them, the host trait loop, shards and a checkpoint, bit for bit.  (Its finding: policy_mode of
+    # parameters a few ulps above 1 -- tests/test_gpu_tdac_beta.py test_policy_mode_of_parameters_a_few_ulps_above_one.)
+    d = _campaign_slice("fuzz_beta.py", agent)
+    assert d["counts"].get("diverged", 0) == 0, d["counts"]
+    assert d["legs"]["f64"] >= 20 and d["legs"]["trait"] >= 20 and d["legs"]["ckpt"] >= 20 and d["legs"].get("shard", 0) >= 2, d["legs"]

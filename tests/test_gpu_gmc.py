@@ -10,7 +10,8 @@ import pytest
 import rsrl_amd as ra
 from rsrl_amd import RsrlHipError
 from rsrl_amd._devmem import DeviceBuffer
-from tests.agent_contract import assert_same, check_foreign_checkpoints_refused, check_train_invariance, rand_states, run_example, snapshot
+from tests.agent_contract import (assert_same, check_foreign_checkpoints_refused, check_train_invariance, gmc_trait_loop, rand_states, run_example,
+                                  snapshot)
 from tests.gmc_numpy import f32_returns, td_chain
 
 pytestmark = pytest.mark.gpu
@@ -121,27 +122,6 @@ class Recording(ra.Context):
             s, r = self.episode_record
             Recording.log.append(dict(record_states=s, record_rewards=r))
         return super().__exit__(*exc)
-
-
-def gmc_trait_loop(c, K, cap):
-    """domain_step -> append (from, r) on the host -> handle_batch(the length of the episodes that just ended, else 0) -> domain_reset(ended) ->
-    policy_sample(); at the end the open rows become the ctx's record"""
-    D = c.D
-    S, R = np.zeros((cap, D, c.N), np.float32), np.zeros((cap, c.N), np.float32)
-    ep = c.episode_steps.astype(np.int64)
-    cols = np.arange(c.N)
-    for _ in range(K):
-        frm, _, rew, term = c.domain_step(c.actions)
-        S[ep, :, cols] = frm.T
-        R[ep, cols] = rew
-        ep += 1
-        ended = term.astype(bool) | (ep >= cap)
-        c.handle_batch(S, None, R, np.where(ended, ep, 0).astype(np.uint32))
-        c.domain_reset(ended.astype(np.uint8))
-        ep[ended] = 0
-        c.policy_sample()
-    c.episode_steps = ep.astype(np.uint32)
-    c.episode_record = (S, R)
 
 
 @pytest.mark.parametrize("case,K,first_split", [(CASE_A, 50, 10), (CASE_B, 120, 33)], ids=["mountain-car-truncations", "cart-pole-ragged"])

@@ -11,7 +11,7 @@ import rsrl_amd as ra
 from rsrl_amd import RsrlHipError
 from rsrl_amd._devmem import DeviceBuffer
 from tests.agent_contract import (assert_same, check_checkpoint_resume, check_foreign_checkpoints_refused, check_train_invariance, join_shards,
-                                  rand_states, run_example, snapshot)
+                                  lstd_batch_trait_loop, rand_states, record_bits, run_example, snapshot)
 from tests.lstd_batch_numpy import handle, initial_state, lu_solve, residual, state_of
 
 pytestmark = pytest.mark.gpu
@@ -51,8 +51,7 @@ def full_snapshot(c):
     each learner's rows, which the harness's comparison refuses) with the learner on axis 0, where every per-learner entry joins"""
     out = snapshot(c)
     out.update(f64_state(c))
-    s, r = c.episode_record
-    out["record_states"], out["record_rewards"] = np.moveaxis(bits(s), -1, 0), np.moveaxis(bits(r), -1, 0)
+    out.update(record_bits(c))
     return out
 
 
@@ -194,30 +193,6 @@ def test_handle_transitions_against_the_f64_rule(orc, domain, order, algo):
             buf.free()
 
 
-def batch_trait_loop(c, K, cap):
-    """domain_step -> append the transition on the host -> handle_transitions(the length of the episodes that just ended, else 0) ->
-    domain_reset(ended) -> policy_sample(); at the end the open rows become the ctx's record"""
-    D = c.D
-    S, S2 = np.zeros((cap, D, c.N), np.float32), np.zeros((cap, D, c.N), np.float32)
-    R, Tm = np.zeros((cap, c.N), np.float32), np.zeros((cap, c.N), np.uint8)
-    ep = c.episode_steps.astype(np.int64)
-    cols = np.arange(c.N)
-    for _ in range(K):
-        frm, nxt, rew, term = c.domain_step(c.actions)
-        S[ep, :, cols] = frm.T
-        S2[ep, :, cols] = nxt.T
-        R[ep, cols] = rew
-        Tm[ep, cols] = term
-        ep += 1
-        ended = term.astype(bool) | (ep >= cap)
-        c.handle_transitions(S, R, S2, Tm, np.where(ended, ep, 0).astype(np.uint32))
-        c.domain_reset(ended.astype(np.uint8))
-        ep[ended] = 0
-        c.policy_sample()
-    c.episode_steps = ep.astype(np.uint32)
-    c.episode_record = (S, R)
-
-
 # every end a truncation, in a partly filled last block (16 learners per block: 4.5 blocks); ragged terminal and truncated ends among the groups
 # of one wave; one learner per wave (F = 36), a partly filled block again
 CASES = {"mountain-car-truncations": (dict(domain=ra.MOUNTAIN_CAR, order=3, max_episode_steps=7, n_envs=72), 50, 10),
@@ -232,7 +207,7 @@ def test_train_is_the_trait_loop_launch_depth_and_shard_invariant(case, algo):
     cap = kw["max_episode_steps"]
     Recording.log = []
     st, ref = check_train_invariance(lambda **k: Recording(**dict(BASE, **k)), dict(kw, algo=algo), K, cap, depths=(1, 16), first_split=first_split,
-                                     kernel="k_train_lstd_batch", trait=batch_trait_loop)
+                                     kernel="k_train_lstd_batch", trait=lstd_batch_trait_loop)
     print("statistics", st)
     assert st["env_steps"] == kw["n_envs"] * K and st["episodes"] > 0 and st["sum_abs_td_error"] > 0
     if case == "cart-pole-ragged":

@@ -5,9 +5,10 @@ for bit against the float32 restatement, the critic's rule and Q(s, a) against t
 The f32 chain of psi, ln and exp has no derivable bound: the bounds of MEASURED below are four times the maxima profiles/nac_beta_rate.md records
 (the factor covers inputs the measurement did not see); every test prints its figure before it asserts.
 
-The contract's adapter: tests/agent_contract.learner_state does not know algo 28 and compares `weights` only, so the contract tests run on NacCtx, a
-thin subclass of Context whose get_weights(i) returns the (5F, 1) stack of the critic's w and the policy's two columns -- the snapshot then carries
-everything the learner learns.  Every other test uses the plain Context."""
+The contract's adapter: the contract tests run on NacCtx, a thin subclass of Context whose get_weights(i) returns the (5F, 1) stack of the critic's w
+and the policy's two columns, and assert on that stack.  (tests/agent_contract.learner_state has since learnt algo 28 -- `weights` and `theta` -- so
+the snapshot carries the columns a second time under `theta`; the adapter stays for what these tests assert on the stack.)  Every other test uses
+the plain Context."""
 import functools
 import os
 

@@ -179,6 +179,26 @@ def test_policy_side_against_the_restatement(orc):
         assert q.shape == (1, N) and abs(q[0, 9] - vv) <= abs(np.spacing(vv))
 
 
+def test_policy_mode_of_parameters_a_few_ulps_above_one():
+    """preferences in (-17, -10): alpha - 1 and beta - 1 are one to a few hundred f32 ulps of 1, both above 1, so the mode is their ratio.  Found by
+    tests/fuzz_beta.py: with the denominator formed as alpha + beta - 2 the sum rounded to a multiple of 2^-22 first and the mode of
+    (1 + 2^-23, 1 + 2^-22) came out as 1/4 or 1/2 for 1/3"""
+    prefs = [(-15.9, -15.2), (-15.2, -14.5), (-14.0, -15.5), (-12.0, -13.0), (-16.5, -10.5), (-10.5, -16.5), (-15.9, -15.9), (-15.2, -15.9)]
+    n = len(prefs)
+    with ctx(order=1, n_envs=n) as c:
+        for i, pr in enumerate(prefs):
+            W = np.zeros((c.F, 2), dtype=np.float32)
+            W[c.F - 1] = pr
+            c.set_policy_weights(W, i)
+        S = np.zeros((2, n), dtype=np.float32)
+        S[0] = -0.5
+        ga, gb = c.policy_params(S)
+        assert ga.min() > 1.0 and gb.min() > 1.0 and max(ga.max(), gb.max()) < 1.0 + 1e-4
+        assert ga[0] == np.float32(1.0 + 2.0 ** -23) and gb[0] == np.float32(1.0 + 2.0 ** -22)      # the pair of the docstring: the mode is 1/3
+        mode = c.policy_mode(S)
+        hold("mode", float(np.max(np.abs(mode - bn.beta_mode(ga.astype(np.float64), gb.astype(np.float64))))))
+
+
 @pytest.mark.parametrize("alpha,beta", SHAPES)
 def test_sampler_distribution_range_and_draws(alpha, beta):
     """4 096 learners with identical columns, 16 policy_sample calls on explicit states: 65 536 draws"""
