@@ -267,7 +267,33 @@ typedef enum { RSRL_QLEARNING = 0, RSRL_SARSA = 1, RSRL_EXPECTED_SARSA = 2, RSRL
                 * action clamped to [2^-24, 1 - 2^-24] before its logarithms; SARSA's thread_rng() draw is a keyed stream (distribution parity is
                 * the contract); the period is a parameter.  Not built: nac.rs (the Gaussian policy's normal::Grad is not in the reference tree)
                 * and nac_softmax.rs (kernels_nac_beta.hpp) */
-               RSRL_NAC = 28 } rsrl_algo;
+               RSRL_NAC = 28,
+               /* (29 is no algo.)  GTD2 (prediction/td/gtd2.rs:27-86) and TDC (prediction/td/tdc.rs:41-101): gradient-TD prediction over TWO
+                * ScalarLFAs on one basis, theta (fa_theta / q_func: the value function) and w (fa_w / td_est: the second weight column), per
+                * learner f32[F] each, zero at create.  With phi = phi(s), phi' = phi(s'), all three products read BEFORE anything moves:
+                *   w_s = <w, phi>, th_s = <theta, phi>, th_n = <theta, phi'>;   td = r - th_s (terminal) | r + gamma th_n - th_s
+                *   w     += lr_td (td - w_s) phi                                                         (both)
+                *   GTD2:  theta += lr w_s phi;   theta -= gamma (lr w_s) phi'      (ScaledGradientUpdate{w_s, phi - gamma phi'})
+                *   TDC :  theta += lr td phi;    theta -= (lr w_s) phi'            (GradientUpdate(td phi - w_s phi'): no gamma, tdc.rs:91)
+                * Neither rule has a terminal case for the gradient: phi' of a terminal transition is the terminal state's own features (what
+                * rsrl_hip_domain_step reports) and is subtracted as on any other step.  The f32 operation order is fixed (kernels_gtd.hpp;
+                * tests/gtd_numpy.py restates it bit for bit): RSRL_TD's dot products and TD error, then one fused multiply-add per element and
+                * column move, theta's two moves one after the other.  RSRL_TDC with w = 0 and lr_td = 0 is RSRL_TD's arithmetic.
+                * DEPARTURE: the reference applies these updates past the optimiser (fa/linear.rs:170-196: scaled_addto / addto), so every move
+                * has the literal step size 1 -- except TDC's td_est, which goes through its SGD (linear.rs:237-248).  On a Fourier basis, where
+                * ||phi||^2 reaches F, both rules then diverge (f64, MountainCar order 1, random transitions: |theta| and |w| pass 1e6 within 64
+                * transitions).  Here config.lr scales every move of theta and config.lr_td every move of w: lr = lr_td = 1 is the reference's
+                * GTD2, lr = 1 the reference's TDC with td_est = SGD(lr_td); a multiplication by 1.0f is exact, so those settings are the literal
+                * rules.  config: lr, lr_td (>= 0, else EINVAL), gamma.  The driver loop is RSRL_TD's: transition, handle, Random sample,
+                * auto-reset -- the environment side is RSRL_TD's draw for draw; truncation at max_episode_steps is not terminal; rsrl_hip_reset
+                * leaves both columns alone.  Supported: as RSRL_RECURSIVE_LSTD (per-learner f32 weights, the register-family Fourier orders,
+                * policy RSRL_RANDOM, agent_policy -1, no epsilon schedule); everything else is EINVAL at create (kernels_gtd.hpp).  The value
+                * side is V (n_outputs 1): q_evaluate writes f32[1][M] from theta, get / set_weights carry theta as f32[F][1],
+                * rsrl_hip_get/set_td_weights carry w as f32[F][1]; q_find_max / _min and q_expected_value are ESTATE.  rsrl_hip_handle takes
+                * transitions as RSRL_TD's does; td_error_out and the statistics' sum |delta| are td.  handle_batch, handle_transitions, traces,
+                * policy weights and the lstd state are ESTATE.  The checkpoint is aux_kind 13 (theta, then w); a file of one of the two agents
+                * does not load into a ctx of the other */
+               RSRL_GTD2 = 30, RSRL_TDC = 31 } rsrl_algo;
 /* rsrl::traces::{Accumulate, Saturate (Trace::replacing), Dutch}      traces.rs:188-240 */
 typedef enum { RSRL_TRACE_ACCUMULATE = 0, RSRL_TRACE_SATURATE = 1, RSRL_TRACE_DUTCH = 2 } rsrl_trace;
 /* rsrl::policies::{Greedy, EpsilonGreedy, Softmax, Random}
@@ -596,7 +622,8 @@ int rsrl_hip_set_weights(rsrl_hip_ctx* ctx, int64_t env_index, const float* w /*
  * row-major f32[F][A] like the weights */
 int rsrl_hip_get_traces(rsrl_hip_ctx* ctx, int64_t env_index, float* z /*[F][A]*/);
 int rsrl_hip_set_traces(rsrl_hip_ctx* ctx, int64_t env_index, const float* z /*[F][A]*/);
-/* the pub field `fa_td` of GreedyGQ (greedy_gq.rs:52): one learner's second approximator, row-major f32[F][A] */
+/* the pub field `fa_td` of GreedyGQ (greedy_gq.rs:52): one learner's second approximator, row-major f32[F][A]; RSRL_GTD2's fa_w and RSRL_TDC's
+ * td_est (gtd2.rs:29, tdc.rs:43): the second weight column w, f32[F][1].  ESTATE on every other agent */
 int rsrl_hip_get_td_weights(rsrl_hip_ctx* ctx, int64_t env_index, float* v /*[F][A]*/);
 int rsrl_hip_set_td_weights(rsrl_hip_ctx* ctx, int64_t env_index, const float* v /*[F][A]*/);
 /* the pub field `policy` of ActorCritic (ac.rs:61): the Gibbs actor's weights theta of one learner, row-major f32[F][A] like the weights
@@ -641,6 +668,7 @@ int rsrl_hip_lstd_solve(rsrl_hip_ctx* ctx);
  *   10 LSTD / LSTDLambda's f64 state                 10          f64 theta, A, b, z (LSTDLambda), u32 singular_solves
  *   11 the Beta iLSTD ActorCritic's state            10          f64 theta, matrices, mu, the policy's columns
  *   12 NAC's critic and the policy's columns         10          weights (3F rows), the policy's columns
+ *   13 GTD2 / TDC: theta and the second column w     10          weights, auxiliary matrix
  * and a ctx with config.epsilon_decay (aux_kind 0 or 1) writes version 4 instead, with f32 eps[N] behind the payload.  No other pairing of
  * version and aux_kind is a file of this library; load refuses it.  Little-endian, serialised field by field (no padding):
  *   offset  0  char magic[8] = "RSRLHIPW"
@@ -650,7 +678,8 @@ int rsrl_hip_lstd_solve(rsrl_hip_ctx* ctx);
  *                   3 QSigma's n-step backups, 4 sparse traces over a shared table, 5 ActorCritic's theta,
  *                   6 the TD ActorCritic's theta, 7 REINFORCE's theta and open episode, 8 the LSTD agents' f64 state,
  *                   9 the iLSTD ActorCritic's f64 state and theta, 10 LSTD / LSTDLambda's f64 state,
- *                   11 the Beta iLSTD ActorCritic's f64 state and policy columns, 12 NAC's critic and policy columns)
+ *                   11 the Beta iLSTD ActorCritic's f64 state and policy columns, 12 NAC's critic and policy columns,
+ *                   13 GTD2's / TDC's second weight column)
  *                                                                                                                 [11 x i32]
  *          56  i64  n_learners (1 in shared mode)
  *          64  u64  step_count
@@ -675,6 +704,8 @@ int rsrl_hip_lstd_solve(rsrl_hip_ctx* ctx);
  *              sections of its iLSTD critic (mu included), then n_learners x f32[F][2] of the policy's columns (alpha's, beta's);
  *              if aux_kind is 12 (file version 10 too; RSRL_NAC; the header's F is n_features, A = 1): the weights
  *              are the critic's w, n_learners x f32[3F][1], then n_learners x f32[F][2] of the policy's columns;
+ *              if aux_kind is 13 (file version 10 too; RSRL_GTD2 / RSRL_TDC; A = 1, the weights are theta): n_learners x f32[F][1] of the
+ *              second weight column w (fa_w / td_est);
  *              if aux_kind is 3 (file version 3): u32 head[N], u32 len[N], f32 entries[D + 5][n_steps][N] -- every learner's
  *              Backup ring {s, a, q, residual, pi, mu} (q_sigma.rs:30-63), so that a QSigma run with n_steps > 1 resumes
  *              bit-identically too.  A QSigma ctx still reads its configuration's version-2 file without them (aux_kind 0): the backups start empty.

@@ -18,6 +18,7 @@ ILSTD_ACTOR_CRITIC = 21                        # (20 is no algo) ActorCritic::td
 GRADIENT_MC = 23                               # (22 is no algo) prediction/mc.rs: GradientMC (Handler<&Trajectory>: handle_batch; episode_record)
 LSTD, LSTD_LAMBDA = 25, 26                      # (24 is no algo) prediction/lstd: LSTD, LSTDLambda (Handler<&Batch> on whole transitions: handle_transitions; lstd_solve; get/set_lstd_batch_state)
 NAC = 28                                        # (27 is no algo) control/nac.rs with the BETA policy and a SARSA critic over the stable compatible basis on CONTINUOUS_MOUNTAIN_CAR (nac_beta.rs): n_weight_rows = 3 F; q_evaluate_f32; nac_update
+GTD2, TDC = 30, 31                              # (29 is no algo) prediction/td: GTD2, TDC -- gradient TD with a second weight column (get/set_td_weights, (F, 1)); lr scales theta's moves, lr_td w's
 TRACE_ACCUMULATE, TRACE_SATURATE, TRACE_DUTCH = 0, 1, 2
 GREEDY, EPSILON_GREEDY, SOFTMAX, RANDOM = 0, 1, 2, 3
 BETA = 4                                        # policies/beta.rs over two Softplus-composed scalar LFAs: ILSTD_ACTOR_CRITIC on CONTINUOUS_MOUNTAIN_CAR
@@ -79,6 +80,7 @@ class Context:
         agent  = QLearning{gamma} | SARSA | ExpectedSARSA{alpha} | PAL{alpha}      (algo, gamma, alpha)
                  | SARSALambda / QLambda {trace(gamma, lam), alpha}                (lam, trace)
                  | GreedyGQ {fa_td = LFA(SGD(lr_td))} | TD | TDLambda              (lr_td; TD/TDLambda need policy=RANDOM)
+                 | GTD2 {fa_theta, fa_w} | TDC {q_func, td_est}                     (lr: theta's moves, lr_td: w's; policy=RANDOM)
                  | QSigma {alpha, gamma, sigma, n_steps}                            (sigma, n_steps)
                  SARSA / ExpectedSARSA / SARSALambda own a policy of their own       (agent_policy, agent_epsilon, agent_tau;
                                                                                      None = the behaviour policy object)
@@ -124,6 +126,7 @@ class Context:
         self.n_weight_rows = self._L.rsrl_hip_n_weight_rows(self._h)      # rows of the weight matrix: F, or NAC's 3 F (SCB::n_features)
         self.n_policy_out = self._L.rsrl_hip_n_policy_outputs(self._h)      # columns of the policy's own weights: A (Gibbs), 2 (BETA), 0 (the policy reads Q)
         self._policy_cols = self.n_policy_out or self.A                     # (the accessors' array shape; an agent without policy weights is refused by the library)
+        self._td_cols = 1 if algo in (GTD2, TDC) else self.A                # (get/set_td_weights' array shape: GreedyGQ's fa_td has A columns)
         self.continuous = domain == CONTINUOUS_MOUNTAIN_CAR                 # actions are f32 values (the *_f32 entry points), not int32 indices
         self.shared = weight_mode == W_SHARED
 
@@ -424,13 +427,13 @@ class Context:
         _abi.check(self._L.rsrl_hip_set_traces(self._h, int(env_index), _p(_in(z, np.float32, (self.F, self.n_out)))))
 
     def get_td_weights(self, env_index=0):
-        """GreedyGQ.fa_td's weights of one learner (greedy_gq.rs:52)"""
-        out = np.empty((self.F, self.A), dtype=np.float32)
+        """GreedyGQ.fa_td's weights of one learner (greedy_gq.rs:52), (F, A); GTD2.fa_w's / TDC.td_est's second weight column, (F, 1)"""
+        out = np.empty((self.F, self._td_cols), dtype=np.float32)
         _abi.check(self._L.rsrl_hip_get_td_weights(self._h, int(env_index), _p(out)))
         return out
 
     def set_td_weights(self, v, env_index=0):
-        _abi.check(self._L.rsrl_hip_set_td_weights(self._h, int(env_index), _p(_in(v, np.float32, (self.F, self.A)))))
+        _abi.check(self._L.rsrl_hip_set_td_weights(self._h, int(env_index), _p(_in(v, np.float32, (self.F, self._td_cols)))))
 
     def get_policy_weights(self, env_index=0):
         """ActorCritic.policy's weights theta of one learner (the Gibbs actor, ac.rs:61), f32 (F, A) -- also for TD_ACTOR_CRITIC, whose

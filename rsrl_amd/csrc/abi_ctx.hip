@@ -48,6 +48,7 @@ static AgentFamily classify(const rsrl_hip_config& cfg, size_t w_elems) {
     if (is_gmc(al)) return F::GmcReg;
     if (is_lstd_batch(al)) return F::LstdBatchReg;
     if (is_nac(al)) return F::NacBetaReg;
+    if (is_gtd(al)) return F::GtdReg;
     if (cfg.weight_mode == RSRL_W_SHARED) return fourier ? F::SharedDense : (is_sparse_lambda(cfg) ? F::SharedSparseLambda : F::SharedTile);
     if (wave && is_wave_aux_algo(al)) return F::WaveAux;
     if (is_pred(al)) return tile ? F::TdTile : (reg ? F::TdReg : F::TdGeneric);
@@ -145,7 +146,7 @@ int rsrl_hip_destroy(rsrl_hip_ctx* c) {
 }
 
 // The agents that exist only on the register-family Fourier orders with per-learner f32 weights (train_ac.hip, train_tdac.hip, train_reinforce.hip,
-// train_lstd.hip, train_tdac_lstd.hip, train_gmc.hip, train_lstd_batch.hip): the policy is the agent's own -- the Gibbs actor / policy, or the prediction agents' Random behaviour -- and the
+// train_lstd.hip, train_tdac_lstd.hip, train_gmc.hip, train_lstd_batch.hip, train_gtd.hip): the policy is the agent's own -- the Gibbs actor / policy, or the prediction agents' Random behaviour -- and the
 // critic shares it; iLSTD's n_updates travel as config.n_steps.  `storage`: register-family order, per-learner f32 weights, no epsilon schedule
 static int check_reg_only(const rsrl_hip_config& cfg, const AlgoRow& a, bool storage) {
     if (!storage || cfg.policy != a.reg_policy || cfg.agent_policy != -1)
@@ -196,7 +197,7 @@ static int check_config(const rsrl_hip_config& cfg) {
     const int D = kDomainShape[cfg.domain][0], A = kDomainShape[cfg.domain][1];
     if (cfg.n_envs < 1) return fail(RSRL_HIP_EINVAL, "n_envs must be >= 1");
     if (cfg.n_envs + cfg.env_offset > (int64_t)0xffffffffLL || cfg.env_offset < 0) return fail(RSRL_HIP_EINVAL, "global env ids must fit 32 bits");
-    if (cfg.algo < 0 || cfg.algo > RSRL_NAC || !kAlgo[cfg.algo].name) return fail(RSRL_HIP_EINVAL, "unknown algo %d", cfg.algo);
+    if (cfg.algo < 0 || cfg.algo > RSRL_TDC || !kAlgo[cfg.algo].name) return fail(RSRL_HIP_EINVAL, "unknown algo %d", cfg.algo);
     if (cfg.policy < 0 || cfg.policy > RSRL_BETA) return fail(RSRL_HIP_EINVAL, "unknown policy %d", cfg.policy);
     // Softmax::new panics for |tau| < 1e-7 (policies/softmax.rs:63-66)
     if (cfg.policy == RSRL_SOFTMAX && std::fabs(cfg.tau) < 1e-7) return fail(RSRL_HIP_EINVAL, "Tau parameter in Softmax must be non-zero.");
@@ -229,7 +230,7 @@ static int check_config(const rsrl_hip_config& cfg) {
         if (!(cfg.sigma >= 0.0 && cfg.sigma <= 1.0)) return fail(RSRL_HIP_EINVAL, "sigma must be in [0, 1]");
         if (cfg.n_steps < 1 || cfg.n_steps > 32) return fail(RSRL_HIP_EINVAL, "n_steps must be in [1, 32]");
     }
-    if (cfg.algo == RSRL_GREEDY_GQ && !(cfg.lr_td >= 0.0)) return fail(RSRL_HIP_EINVAL, "lr_td must be >= 0");
+    if ((cfg.algo == RSRL_GREEDY_GQ || is_gtd(cfg.algo)) && !(cfg.lr_td >= 0.0)) return fail(RSRL_HIP_EINVAL, "lr_td must be >= 0");
     if (!(cfg.epsilon_decay > 0.0 && cfg.epsilon_decay <= 1.0)) return fail(RSRL_HIP_EINVAL, "epsilon_decay must be in (0, 1] (1 = no schedule)");
     if (!(cfg.epsilon_min >= 0.0 && cfg.epsilon_min <= 1.0)) return fail(RSRL_HIP_EINVAL, "epsilon_min must be in [0, 1]");
 

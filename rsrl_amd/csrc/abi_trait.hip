@@ -167,7 +167,7 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
         RSRL_REG_FOURIER(X)
 #undef X
         if (!ok) return NO_MODEL(c);
-    } else if ((is_pred(c->cfg.algo) || is_tdac(c->cfg.algo) || is_gmc(c->cfg.algo)) && op == QOP_EVALUATE) {      // V(s) (the TD ActorCritic, GradientMC: their w, k_v_evaluate)
+    } else if ((is_pred(c->cfg.algo) || is_tdac(c->cfg.algo) || is_gmc(c->cfg.algo) || is_gtd(c->cfg.algo)) && op == QOP_EVALUATE) {      // V(s) (the TD ActorCritic, GradientMC: their w; GTD2 / TDC: theta; k_v_evaluate)
         bool ok = true;
         switch (c->family) {
         case AgentFamily::WaveAux:
@@ -225,8 +225,8 @@ static int sample_emit(rsrl_hip_ctx* c, int64_t M, int32_t* actions_out) {
     if (M != c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "policy_sample(states = NULL) samples for the ctx's own envs: M must be n_envs (%lld), got %lld", (long long)c->cfg.n_envs, (long long)M);
     if (is_pred(c->cfg.algo)) return fail(RSRL_HIP_ESTATE, "a prediction agent has a state-value function only (use rsrl_hip_q_evaluate for V(s))");
     const bool dev_out = is_device_ptr(actions_out);
-    if (c->family == AgentFamily::LstdReg || c->family == AgentFamily::GmcReg || c->family == AgentFamily::LstdBatchReg) {
-        // RecursiveLSTD / iLSTD / GradientMC / LSTD / LSTDLambda: the driver loop's Random sample (what rsrl_hip_train draws at batch-step step_count - 1; the initial sample's stream
+    if (c->family == AgentFamily::LstdReg || c->family == AgentFamily::GmcReg || c->family == AgentFamily::LstdBatchReg || c->family == AgentFamily::GtdReg) {
+        // RecursiveLSTD / iLSTD / GradientMC / LSTD / LSTDLambda / GTD2 / TDC: the driver loop's Random sample (what rsrl_hip_train draws at batch-step step_count - 1; the initial sample's stream
         // before the first handle), so that the trait-granular loop runs on the driver loop's draws
         FLUSH(c);
         HIP_TRY(hipSetDevice(c->cfg.device));

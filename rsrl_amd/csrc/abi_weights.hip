@@ -113,7 +113,7 @@ static int aux_entry(rsrl_hip_ctx* c, int64_t env_index, float* out, const float
     return traces_rw(c, env_index, out, in);
 }
 static bool has_traces(const rsrl_hip_ctx* c) { return is_lambda(c->cfg.algo) || c->cfg.algo == RSRL_TD_LAMBDA; }
-static bool has_td_weights(const rsrl_hip_ctx* c) { return c->cfg.algo == RSRL_GREEDY_GQ; }
+static bool has_td_weights(const rsrl_hip_ctx* c) { return c->cfg.algo == RSRL_GREEDY_GQ || is_gtd(c->cfg.algo); }      // (fa_td; GTD2's fa_w, TDC's td_est)
 static const char* const kNoPolicyWeights = "only ActorCritic and REINFORCE have policy weights of their own (the policy reads Q otherwise)";
 int rsrl_hip_get_traces(rsrl_hip_ctx* c, int64_t env_index, float* z) { return aux_entry(c, env_index, z, nullptr, has_traces, "this agent has no eligibility trace"); }
 int rsrl_hip_set_traces(rsrl_hip_ctx* c, int64_t env_index, const float* z) { return aux_entry(c, env_index, nullptr, z, has_traces, "this agent has no eligibility trace"); }
@@ -221,7 +221,7 @@ struct CkptKind {
     bool reads_kind0;            // a ctx of this kind also reads its configuration's version-2 / aux_kind-0 file, written before the kind's own section
     SectionId sections[3];       // travelled: the weights load, that section's state starts empty
 };
-constexpr int kCkptKinds = 13;
+constexpr int kCkptKinds = 14;
 constexpr CkptKind kCkptKind[kCkptKinds] = {
     /* 0 weights only                           */ {2, 0, true, false, {S_WEIGHTS}},
     /* 1 eligibility traces                     */ {2, 0, true, false, {S_WEIGHTS, S_AUX}},
@@ -237,6 +237,7 @@ constexpr CkptKind kCkptKind[kCkptKinds] = {
     /* 11 the Beta iLSTD ActorCritic: f64 state, the policy's two columns */ {10, 0, false, false, {S_LSTD, S_AUX}},      // (kind 9's sections with f32[F][2] behind them)
     /* 12 NAC: the critic's w (3F rows), the policy's two columns */ {10, 0, false, false, {S_WEIGHTS, S_AUX}},      // (version 10 as well: load's message names
                                                                                                                       // the versions read, and tests hold its text)
+    /* 13 GTD2 / TDC: theta, the second column w */ {10, 0, false, false, {S_WEIGHTS, S_AUX}},      // (version 10 as well; the header's algo tells the two agents apart)
 };
 // (the kinds the configuration decides, not the algo: SARSALambda / QLambda over ONE shared tile table keep sparse traces instead of Z; the iLSTD
 // ActorCritic with the Beta policy keeps two policy columns instead of the Gibbs actor's A)

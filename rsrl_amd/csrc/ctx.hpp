@@ -49,7 +49,7 @@ using namespace rsrl;
 
 // ---- THE agent table: what the reference's agent of each rsrl_algo is, one row per number.  Admission (check_config), the ctx's buffers (create_impl),
 // the accessors and the checkpoint read it; a new agent adds its row here, a line of classify() and a case of launch_agent ("Adding an agent").
-enum class Agent : uint8_t { None, OneStep, Lambda, Gq, Pred, QSigma, Ac, TdAc, Reinforce, Lstd, TdAcLstd, Gmc, LstdBatch, Nac };      // the group classify() and the kernels' dispatch know it by
+enum class Agent : uint8_t { None, OneStep, Lambda, Gq, Pred, QSigma, Ac, TdAc, Reinforce, Lstd, TdAcLstd, Gmc, LstdBatch, Nac, Gtd };      // the group classify() and the kernels' dispatch know it by
 enum class Aux : uint8_t { None, LikeW, Policy };      // the second per-learner matrix Z: none, of W's shape, or the actor's A columns next to a one-column W
 struct AlgoRow {
     const char* name = nullptr;      // as the admission messages print it (nullptr: the number is unassigned)
@@ -63,7 +63,7 @@ struct AlgoRow {
     // one of them), the message's words behind it and behind "agent_policy = -1", and what it calls config.n_steps in front of "n_updates" (nullptr: not read)
     int reg_policy = -1; const char* policy_words = ""; const char* shares_words = ""; const char* n_updates = nullptr;
 };
-constexpr AlgoRow kAlgo[RSRL_NAC + 1] = {
+constexpr AlgoRow kAlgo[RSRL_TDC + 1] = {
     /*  0 */ {"QLearning", Agent::OneStep},
     /*  1 */ {"SARSA", Agent::OneStep},
     /*  2 */ {"ExpectedSARSA", Agent::OneStep},
@@ -99,6 +99,10 @@ constexpr AlgoRow kAlgo[RSRL_NAC + 1] = {
     /* 27 */ {},
     // (W is the SCB critic's one column of 3F rows -- weight_rows() --, the Beta policy's two columns in Z; admitted by check_continuous, not check_reg_only)
     /* 28 */ {"NAC (RSRL_NAC)", Agent::Nac, true, Aux::Policy, 12},
+    /* 29 */ {},
+    // (the gradient-TD agents: W is theta's one column, TD's layout; Z is the second column w -- fa_w / td_est --, [F][1])
+    /* 30 */ {"GTD2 (RSRL_GTD2)", Agent::Gtd, true, Aux::LikeW, 13, false, false, RSRL_RANDOM},
+    /* 31 */ {"TDC (RSRL_TDC)", Agent::Gtd, true, Aux::LikeW, 13, false, false, RSRL_RANDOM},
 };
 // (readers of the table, for configurations check_config has admitted: the algo is a row with a name)
 static inline bool is_lambda(int algo) { return kAlgo[algo].agent == Agent::Lambda; }
@@ -111,10 +115,11 @@ static inline bool is_tdac_lstd(int algo) { return kAlgo[algo].agent == Agent::T
 static inline bool is_gmc(int algo) { return kAlgo[algo].agent == Agent::Gmc; }
 static inline bool is_lstd_batch(int algo) { return kAlgo[algo].agent == Agent::LstdBatch; }
 static inline bool is_nac(int algo) { return kAlgo[algo].agent == Agent::Nac; }
+static inline bool is_gtd(int algo) { return kAlgo[algo].agent == Agent::Gtd; }
 // the agents that keep every learner's open episode on the device (rec_s / rec_r, max_episode_steps rows) and sweep it when it ends
 static inline bool keeps_record(int algo) { return is_gmc(algo) || is_lstd_batch(algo); }
 // the agents whose value function is V alone and whose behaviour is Random: no action values to search, weigh, sample from or roll out with
-static inline bool is_v_only(int algo) { return is_pred(algo) || is_lstd(algo) || is_gmc(algo) || is_lstd_batch(algo); }
+static inline bool is_v_only(int algo) { return is_pred(algo) || is_lstd(algo) || is_gmc(algo) || is_lstd_batch(algo) || is_gtd(algo); }
 
 // ---- the small kernels more than one unit launches, and the launches of kernel templates two units would otherwise both instantiate: defined ONCE, in
 // kernels_util.hip / launch_shared.hip (a kernel's host stub is an ordinary function: another unit launches it through this declaration)
@@ -202,8 +207,9 @@ enum class AgentFamily : uint8_t {
                           // (train_tdac_beta.hip); iLSTD's f64 state as LstdReg's, the policy's two columns in Z, f32 actions in action_f
     NacBetaReg,           // NAC with the Beta policy and the SCB SARSA critic on ContinuousMountainCar, Fourier orders 1-5: k_train_nac_beta (train_nac_beta.hip),
                           // one thread per learner; the critic's w in W (3F rows, one column), the policy's two columns in Z, f32 actions in action_f
+    GtdReg,               // GTD2 / TDC, same configurations as LstdReg: k_train_gtd (train_gtd.hip); theta in W (one column), the second column w in Z
 };
-constexpr size_t kAgentFamilies = (size_t)AgentFamily::NacBetaReg + 1;      // (the enum's last value)
+constexpr size_t kAgentFamilies = (size_t)AgentFamily::GtdReg + 1;      // (the enum's last value)
 // ---- THE family table: which kernels serve a family and what they can do, one row per AgentFamily value in the enum's order.  classify() (abi_ctx.hip: a
 // decision) and launch_agent (abi_train.hip: it instantiates the templates) are the two other places a new family is entered.
 enum class Slots : uint8_t { Block, Block64, WaveBlock, Learner, LstdGroup };      // a statistics slot per: kBlock learners, 64 learners (k_train_lambda_mem4; the
@@ -259,6 +265,7 @@ constexpr FamilyRow kFamily[] = {
     {AgentFamily::LstdBatchReg, "k_train_lstd_batch", 256, Slots::LstdGroup, Handle::Agent, kLstd | kBatchLstd},      // (handle: refused, whole batches only)
     {AgentFamily::TdAcBetaReg, "k_train_tdac_beta", 32, Slots::LstdGroup, Handle::Agent, kPolicyW | kVCritic | kLstd},      // (handle: rsrl_hip_handle_f32)
     {AgentFamily::NacBetaReg, "k_train_nac_beta", 256, Slots::Block, Handle::Agent, kPolicyW},      // (handle: rsrl_hip_handle_f32; a step is a long scalar chain: 256 as the memory-resident loops)
+    {AgentFamily::GtdReg, "k_train_gtd", 4096, Slots::Block, Handle::Agent, 0},      // (4 096: TdReg's depth, taken over and not measured)
 };
 constexpr bool family_rows_in_order() {
     for (size_t i = 0; i < sizeof(kFamily) / sizeof(kFamily[0]); ++i) if ((size_t)kFamily[i].family != i) return false;
@@ -310,7 +317,7 @@ struct rsrl_hip_ctx {
     // lambda agents over ONE shared tile table: every learner's sparse trace + the step's mailbox (kernels_sparse_lambda.hpp)
     uint16_t* sp_keys = nullptr; float* sp_vals = nullptr; uint32_t* sp_len = nullptr;    // sparse traces: [N][kSparseCap] slice-relative keys (16 bit) and values, lengths [N][n_tilings]
     bool sp_lds = false;             //   one tiling's slice of the delta table fits LDS (k_sparse_trace_scatter)
-    float* Z = nullptr;              // auxiliary matrix f32[A][F][N]: eligibility traces (lambda agents) / fa_td weights (GreedyGQ) / the actor's theta (ActorCritic)
+    float* Z = nullptr;              // auxiliary matrix f32[A][F][N]: eligibility traces (lambda agents) / fa_td weights (GreedyGQ; GTD2's fa_w, TDC's td_est) / the actor's theta (ActorCritic)
                                      // -- of W's shape, except TdAcReg's / TdAcLstdReg's theta: A columns against W's one (aux_cols)
     float* Zb = nullptr;             // REINFORCE only: the behaviour snapshot theta_b f32[A][F][N] (theta when the open episode began)
     float* ret_g = nullptr;          //   and the open episode's running return g f32[N]
@@ -492,6 +499,13 @@ static LambdaParams make_lambda(const rsrl_hip_ctx* c) {
     if (c->cfg.trace == RSRL_TRACE_DUTCH) rate *= (1.0 - c->cfg.alpha);       // traces.rs:233-239
     lp.rate = (float)rate; lp.alpha = (float)c->cfg.alpha; lp.trace = c->cfg.trace;
     return lp;
+}
+
+// GTD2 / TDC: the second weight column and its rate (theta travels as k.W, lr and gamma in k.alg)
+static inline GtdState make_gtd(const rsrl_hip_ctx* c) {
+    GtdState gs;
+    gs.w = c->Z; gs.lr_td = (float)c->cfg.lr_td;
+    return gs;
 }
 
 static GqParams make_gq(const rsrl_hip_ctx* c) {

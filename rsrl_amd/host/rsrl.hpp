@@ -7,6 +7,7 @@
 //   rsrl::fa::linear::{basis::Fourier, optim::SGD, LFA}  rsrl/src/fa/linear.rs (re-exports of crate lfa)
 //   rsrl::policies::{Greedy, EpsilonGreedy, Softmax, Random}   rsrl/src/policies/*.rs
 //   rsrl::control::td::{QLearning, SARSA, ExpectedSARSA, PAL, SARSALambda, QLambda, GreedyGQ, QSigma}   rsrl/src/control/td/*.rs
+//   rsrl::prediction::td::{TD, TDLambda, GTD2, TDC}         rsrl/src/prediction/td/*.rs
 //   rsrl::control::nac::NAC, rsrl::fa::linear::basis::SCB, LFA::scalar, control::td::SARSA over them      rsrl/src/control/nac.rs, fa/linear.rs:79-103
 //   rsrl::make_shared / Shared<T>                            rsrl/src/core.rs:13-44
 //
@@ -267,7 +268,7 @@ struct BaselineREINFORCE : td::Agent {
 };
 }}  // namespace control::mc
 
-// ---- rsrl::prediction::td: TD { v_func, gamma } / TDLambda { fa_theta, trace, gamma }   (td.rs:25-30, td_lambda.rs:25-32)
+// ---- rsrl::prediction::td: TD { v_func, gamma } / TDLambda { fa_theta, trace, gamma } / GTD2 / TDC   (td.rs:25-30, td_lambda.rs:25-32)
 // The value function is a ScalarLFA (one weight column); drive these with policies::Random.
 namespace prediction { namespace td {
 struct TD : control::td::Agent {
@@ -276,6 +277,19 @@ struct TD : control::td::Agent {
 struct TDLambda : control::td::Agent {
     TDLambda(Shared<fa::linear::LFA> fa_theta, const traces::Trace& tr, double gamma)
         : control::td::Agent{RSRL_TD_LAMBDA, std::move(fa_theta), gamma, 1.0, tr.rule, tr.lambda} {}
+};
+// GTD2 { fa_theta, fa_w, gamma } / TDC { q_func, td_est, gamma }                    (gtd2.rs:27-33, tdc.rs:41-47)
+// Gradient TD over two ScalarLFAs on one basis: the first is the value function (Session::weights), the second the correction's estimator
+// (Session::td_weights).  The second LFA's rate goes to lr_td, as GreedyGQ's fa_td does.  The reference applies theta's updates -- and GTD2's w
+// update -- past the optimiser, with step size 1, which diverges on a Fourier basis: here the first LFA's rate scales every move of theta and the
+// second's every move of w (include/rsrl_hip.h, RSRL_GTD2); SGD(1.0) on both is the literal GTD2, SGD(1.0) on q_func the literal TDC.
+struct GTD2 : control::td::Agent {
+    GTD2(Shared<fa::linear::LFA> fa_theta, const fa::linear::LFA& fa_w, double gamma)
+        : control::td::Agent{RSRL_GTD2, std::move(fa_theta), gamma, 1.0, RSRL_TRACE_ACCUMULATE, 0.0, fa_w.lr} {}
+};
+struct TDC : control::td::Agent {
+    TDC(Shared<fa::linear::LFA> q_func, const fa::linear::LFA& td_est, double gamma)
+        : control::td::Agent{RSRL_TDC, std::move(q_func), gamma, 1.0, RSRL_TRACE_ACCUMULATE, 0.0, td_est.lr} {}
 };
 }}  // namespace prediction::td
 
@@ -477,9 +491,9 @@ public:
     std::vector<float> trace(int64_t env = 0) {
         std::vector<float> z((size_t)F_ * O_); check(rsrl_hip_get_traces(ctx_, env, z.data())); return z;
     }
-    // the pub field `fa_td` of GreedyGQ                                             (greedy_gq.rs:52)
+    // the pub field `fa_td` of GreedyGQ (greedy_gq.rs:52), [F][A]; `fa_w` of GTD2 / `td_est` of TDC (gtd2.rs:29, tdc.rs:43), [F][1]
     std::vector<float> td_weights(int64_t env = 0) {
-        std::vector<float> v((size_t)F_ * A_); check(rsrl_hip_get_td_weights(ctx_, env, v.data())); return v;
+        std::vector<float> v((size_t)F_ * O_); check(rsrl_hip_get_td_weights(ctx_, env, v.data())); return v;
     }
     // RecursiveLSTD / iLSTD (and ActorCritic::tdac over iLSTD): one learner's exact f64 state -- theta [F], the matrix [F][F] (C / A, row-major), iLSTD's mu [F] (empty otherwise)
     struct LstdState { std::vector<double> theta, mat, mu; };

@@ -7,7 +7,8 @@ fixture of its own; and GRID_BETA, the continuous axis: MountainCar and Continuo
 (19), the iLSTD ActorCritic (21) and the unassigned 27, with agent_policy -1 / Softmax / Beta (15 360 configurations) -> create_admission_beta.json
 (tests/test_tdac_beta_cpu.py); and GRID_NAC: ContinuousMountainCar / MountainCar x Softmax / Random / Beta x the algos 21, the unassigned 27 and NAC
 (28) x agent_policy -1 / Beta x the Fourier orders 0-6 x n_steps (NAC's period) 0, 1, 100, 65 536, 65 537 (1 260 configurations) ->
-create_admission_nac.json (tests/test_nac_beta_cpu.py).
+create_admission_nac.json (tests/test_nac_beta_cpu.py); and GRID_GTD: GRID's axes with the algos 29 (unassigned), GTD2 (30), TDC (31) and 32 (past
+the last) and an lr_td axis 0 / -1 (81 920 configurations) -> create_admission_gtd.json (tests/test_gtd_cpu.py).
     python scripts/admission_matrix.py            writes tests/golden/create_admission.json, create_admission_agents.json,
                                                   create_admission_agents2.json and create_admission_agents3.json
                                                   (tests/test_create_admission_cpu.py, tests/test_tdac_lstd_cpu.py and tests/test_gmc_cpu.py
@@ -28,6 +29,7 @@ AGENTS2_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_agents
 AGENTS3_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_agents3.json")
 BETA_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_beta.json")
 NAC_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_nac.json")
+GTD_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_gtd.json")
 EINVAL, EHIP = -1, -2
 
 # (config field, values): the first axis varies slowest
@@ -74,9 +76,11 @@ GRID_NAC = [
     ("order", [0, 1, 2, 3, 4, 5, 6]),
     ("n_steps", [0, 1, 100, 65536, 65537]),
 ]
+# GTD2 (30) and TDC (31) between the unassigned 29 and 32, on GRID's other axes, with the second column's rate: 0 and a negative one
+GRID_GTD = [(name, [29, 30, 31, 32] if name == "algo" else vals) for name, vals in GRID] + [("lr_td", [0.0, -1.0])]
 # (grid, fixture, fields set on every configuration)
 GRIDS = ((GRID, FIXTURE, {}), (GRID_AGENTS, AGENTS_FIXTURE, {}), (GRID_AGENTS2, AGENTS2_FIXTURE, {}), (GRID_AGENTS3, AGENTS3_FIXTURE, FIXED_AGENTS3),
-         (GRID_BETA, BETA_FIXTURE, {}), (GRID_NAC, NAC_FIXTURE, {}))
+         (GRID_BETA, BETA_FIXTURE, {}), (GRID_NAC, NAC_FIXTURE, {}), (GRID_GTD, GTD_FIXTURE, {}))
 
 
 def sweep(grid=GRID, fixed=None):

@@ -17,6 +17,8 @@ PG = dict(policy=rsrl_amd.SOFTMAX, alpha=0.001, gamma=0.99)
 AGENTS = {
     "TD": dict(algo=rsrl_amd.TD, policy=rsrl_amd.RANDOM, lr=0.001, gamma=0.99),
     "TDLambda": dict(algo=rsrl_amd.TD_LAMBDA, policy=rsrl_amd.RANDOM, lam=0.7, lr=0.001, gamma=0.99),
+    "GTD2": dict(algo=rsrl_amd.GTD2, policy=rsrl_amd.RANDOM, lr=0.001, lr_td=0.002, gamma=0.99),
+    "TDC": dict(algo=rsrl_amd.TDC, policy=rsrl_amd.RANDOM, lr=0.001, lr_td=0.002, gamma=0.99),
     "GreedyGQ": dict(algo=rsrl_amd.GREEDY_GQ, lr_td=0.001, lr=0.001, gamma=1.0, **EG),
     "SARSALambda": dict(algo=rsrl_amd.SARSA_LAMBDA, lam=0.7, alpha=0.01, gamma=0.99, **EG),
     "QLambda": dict(algo=rsrl_amd.Q_LAMBDA, lam=0.7, alpha=0.01, gamma=0.99, **EG),
