@@ -518,13 +518,14 @@ int rsrl_hip_get_epsilons(rsrl_hip_ctx* c, float* eps_out) {
     if (c->eps) {
         HIP_TRY(hipMemcpyAsync(eps_out, c->eps, sizeof(float) * (size_t)N, hipMemcpyDefault, c->stream));
     } else {
-        OutBuf<float> ob;
-        TRY(stage_out(c, 0, eps_out, (size_t)N, &ob));
-        hipLaunchKernelGGL(k_fill_f32, dim3(grid_for(N)), dim3(kBlock), 0, c->stream, ob.dev, N, (float)c->cfg.epsilon);
+        CallFrame f(c);
+        float* d_eps;
+        TRY(f.out(eps_out, (size_t)N, &d_eps));
+        hipLaunchKernelGGL(k_fill_f32, dim3(grid_for(N)), dim3(kBlock), 0, c->stream, d_eps, N, (float)c->cfg.epsilon);
         KCHECK();
-        bool sync = false; TRY(flush_out(c, &ob, &sync));
+        TRY(f.finish());
     }
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));      // (an accessor: synchronous for device memory too)
     return RSRL_HIP_OK;
 }
 
@@ -568,9 +569,10 @@ int rsrl_hip_get_states(rsrl_hip_ctx* c, float* states) {
 int rsrl_hip_set_states(rsrl_hip_ctx* c, const float* states) {
     CHECK_CTX(c); FLUSH(c);
     if (!states) return fail(RSRL_HIP_EINVAL, "null argument");
-    TRY(check_host_states(c, states, (size_t)c->cfg.n_envs));
+    CallFrame f(c);      // (asked where the array lives; nothing is staged: the copy below is the runtime's own)
+    TRY(check_host_states(f, states, (size_t)c->cfg.n_envs));
     HIP_TRY(hipSetDevice(c->cfg.device));
-    if (is_device_ptr(states)) {
+    if (f.device(states)) {
         // same rule as for a host array, checked where the data is; a refused array leaves the ctx untouched
         StateLimits lim; state_limits(c, lim.lo, lim.hi);
         TRY(scratch_reserve(c, 7, sizeof(unsigned)));
@@ -620,7 +622,8 @@ int rsrl_hip_set_actions(rsrl_hip_ctx* c, const int32_t* actions) {
     CHECK_CTX(c); FLUSH(c); if (!actions) return fail(RSRL_HIP_EINVAL, "null argument");
     NEEDS_INDEX_ACTIONS(c, "rsrl_hip_set_actions");
     HIP_TRY(hipSetDevice(c->cfg.device));
-    TRY(check_host_actions(actions, (size_t)c->cfg.n_envs, c->A));
+    CallFrame f(c);
+    TRY(check_host_actions(f, actions, (size_t)c->cfg.n_envs, c->A));
     HIP_TRY(hipMemcpyAsync(c->action, actions, sizeof(int32_t) * (size_t)c->cfg.n_envs, hipMemcpyDefault, c->stream));
     hipLaunchKernelGGL(k_clamp_actions, dim3(grid_for(c->cfg.n_envs)), dim3(kBlock), 0, c->stream, c->action, c->cfg.n_envs, c->A);
     KCHECK();
@@ -640,7 +643,8 @@ int rsrl_hip_set_actions_f32(rsrl_hip_ctx* c, const float* actions) {
     CHECK_CTX(c); FLUSH(c); if (!actions) return fail(RSRL_HIP_EINVAL, "null argument");
     NEEDS_F32_ACTIONS(c, "rsrl_hip_set_actions");
     HIP_TRY(hipSetDevice(c->cfg.device));
-    TRY(check_host_actions_f32(actions, (size_t)c->cfg.n_envs, true));
+    CallFrame f(c);
+    TRY(check_host_actions_f32(f, actions, (size_t)c->cfg.n_envs, true));
     HIP_TRY(hipMemcpyAsync(c->action_f, actions, sizeof(float) * (size_t)c->cfg.n_envs, hipMemcpyDefault, c->stream));
     launch_cmc_clamp_actions(c->stream, c->action_f, c->cfg.n_envs);
     KCHECK();
@@ -681,14 +685,14 @@ int rsrl_hip_get_episode_record(rsrl_hip_ctx* c, float* states, float* rewards) 
     if (!keeps_record(c->cfg.algo)) return fail(RSRL_HIP_ESTATE, "%s", kNoEpisodeRecord);
     HIP_TRY(hipSetDevice(c->cfg.device));
     const int64_t N = c->cfg.n_envs, cap = (int64_t)c->cfg.max_episode_steps;
-    OutBuf<float> os, orw;
-    TRY(stage_out(c, 0, states, (size_t)cap * (size_t)c->D * (size_t)N, &os));
-    TRY(stage_out(c, 1, rewards, (size_t)cap * (size_t)N, &orw));
-    launch_gmc_record_get(c->stream, make_gmc(c), c->ep_step, N, cap, c->D, os.dev, orw.dev);
+    CallFrame f(c);
+    float* d_states; float* d_rew;
+    TRY(f.out(states, (size_t)cap * (size_t)c->D * (size_t)N, &d_states));
+    TRY(f.out(rewards, (size_t)cap * (size_t)N, &d_rew));
+    launch_gmc_record_get(c->stream, make_gmc(c), c->ep_step, N, cap, c->D, d_states, d_rew);
     KCHECK();
-    bool sync = false;
-    TRY(flush_out(c, &os, &sync)); TRY(flush_out(c, &orw, &sync));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    TRY(f.finish());
+    HIP_TRY(hipStreamSynchronize(c->stream));      // (an accessor: synchronous for device memory too)
     return RSRL_HIP_OK;
 }
 int rsrl_hip_set_episode_record(rsrl_hip_ctx* c, const float* states, const float* rewards) {

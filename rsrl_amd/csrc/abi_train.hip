@@ -597,55 +597,50 @@ static int rollout_impl(rsrl_hip_ctx* c, int64_t step_limit, int64_t M, uint32_t
             return fail(RSRL_HIP_ESTATE, "rsrl_hip_rollout_trajectory and rsrl_hip_rollout_policy write int32 action indices: this ctx's domain (ContinuousMountainCar) "
                                          "has one f32 action -- rsrl_hip_rollout_greedy runs policy.mode");
         HIP_TRY(hipSetDevice(c->cfg.device));
-        OutBuf<uint32_t> on; OutBuf<float> ot;
-        TRY(stage_out(c, 0, n_states_out, (size_t)M, &on));
-        TRY(stage_out(c, 1, total_reward_out, (size_t)M, &ot));
+        CallFrame f(c);
+        uint32_t* d_n; float* d_total;
+        TRY(f.out(n_states_out, (size_t)M, &d_n));
+        TRY(f.out(total_reward_out, (size_t)M, &d_total));
         // (NAC: the loop's mapping, Domain::rollout(|s| 2 * policy.mode(s) - 1), nac_beta.rs:81-82)
-        if (!(is_nac(c->cfg.algo) ? launch_nac_rollout_mode(c->cfg.order, c->stream, make_common(c), c->Z, step_limit, on.dev, ot.dev)
-                                  : launch_beta_rollout_mode(c->cfg.order, c->stream, make_common(c), c->Z, step_limit, on.dev, ot.dev))) return NO_MODEL(c);
+        if (!(is_nac(c->cfg.algo) ? launch_nac_rollout_mode(c->cfg.order, c->stream, make_common(c), c->Z, step_limit, d_n, d_total)
+                                  : launch_beta_rollout_mode(c->cfg.order, c->stream, make_common(c), c->Z, step_limit, d_n, d_total))) return NO_MODEL(c);
         KCHECK();
-        bool sync = false;
-        TRY(flush_out(c, &on, &sync)); TRY(flush_out(c, &ot, &sync));
-        if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
-        return RSRL_HIP_OK;
+        return f.finish();
     }
     if (is_v_only(c->cfg.algo))          // (W is one column: the model kernels below would read A of them)
         return fail(RSRL_HIP_ESTATE, "a prediction agent has a state-value function only: no action values to roll out with");
     if (!rp.sample && c->cfg.policy == RSRL_RANDOM) return fail(RSRL_HIP_EINVAL, "Random policy has no mode.");
     HIP_TRY(hipSetDevice(c->cfg.device));
     if (step_limit == 1) { actions_out = nullptr; rewards_out = nullptr; }      // Trajectory.steps is empty
-    OutBuf<uint32_t> on; OutBuf<float> ot, os, orw; OutBuf<int32_t> oa; OutBuf<uint8_t> otm;
-    const size_t tr_rows = (size_t)(step_limit - 1) * (size_t)M;
-    TRY(stage_out(c, 0, n_states_out, (size_t)M, &on));
-    TRY(stage_out(c, 1, total_reward_out, (size_t)M, &ot));
-    TRY(stage_out(c, 2, states_out, (size_t)step_limit * c->D * (size_t)M, &os));
-    TRY(stage_out(c, 3, actions_out, tr_rows, &oa));
-    TRY(stage_out(c, 4, rewards_out, tr_rows, &orw));
-    TRY(stage_out(c, 5, terminal_out, (size_t)M, &otm));
+    CallFrame f(c);
+    uint32_t* d_n; float* d_total; TrajOut tr{};
+    const size_t tr_rows = (size_t)(step_limit - 1) * (size_t)M, st_elems = (size_t)step_limit * c->D * (size_t)M;
+    TRY(f.out(n_states_out, (size_t)M, &d_n));
+    TRY(f.out(total_reward_out, (size_t)M, &d_total));
+    TRY(f.out(states_out, st_elems, &tr.states));
+    TRY(f.out(actions_out, tr_rows, &tr.actions));
+    TRY(f.out(rewards_out, tr_rows, &tr.rewards));
+    TRY(f.out(terminal_out, (size_t)M, &tr.terminal));
+    tr.Mn = M;
     // rows past a trajectory's end stay as the caller left them in device memory; staged host outputs start from zero
-    if (os.staged) HIP_TRY(hipMemsetAsync(os.dev, 0, sizeof(float) * os.count, c->stream));
-    if (oa.staged) HIP_TRY(hipMemsetAsync(oa.dev, 0, sizeof(int32_t) * oa.count, c->stream));
-    if (orw.staged) HIP_TRY(hipMemsetAsync(orw.dev, 0, sizeof(float) * orw.count, c->stream));
-    const TrajOut tr{os.dev, oa.dev, orw.dev, otm.dev, M};
+    if (f.host(states_out)) HIP_TRY(hipMemsetAsync(tr.states, 0, sizeof(float) * st_elems, c->stream));
+    if (f.host(actions_out)) HIP_TRY(hipMemsetAsync(tr.actions, 0, sizeof(int32_t) * tr_rows, c->stream));
+    if (f.host(rewards_out)) HIP_TRY(hipMemsetAsync(tr.rewards, 0, sizeof(float) * tr_rows, c->stream));
     const Common k = make_policy_common(c);             // Domain::rollout(|s| policy.mode(s) / .sample): ActorCritic's policy is the actor
     const BasisGeom g = make_geom(c);
     if (c->family == AgentFamily::Hiv) {
-        launch_hiv_rollout(c->stream, k, g, step_limit, on.dev, ot.dev, M, tr, rp);
+        launch_hiv_rollout(c->stream, k, g, step_limit, d_n, d_total, M, tr, rp);
     } else if (is_wave_family(c->family)) {
         for_wave(c, [&](auto tag) {
             using T = decltype(tag); using WT = typename T::wt;
-            hipLaunchKernelGGL((k_wave_rollout<T::domain, WT>), dim3(wave_grid_for(M)), dim3(kBlock), 0, c->stream, k, (const WT*)c->W, step_limit, on.dev, ot.dev, M, tr, rp);
+            hipLaunchKernelGGL((k_wave_rollout<T::domain, WT>), dim3(wave_grid_for(M)), dim3(kBlock), 0, c->stream, k, (const WT*)c->W, step_limit, d_n, d_total, M, tr, rp);
         });
     } else if (!for_model(c, [&](auto tag) {
             using Mo = typename decltype(tag)::type;
-            hipLaunchKernelGGL((k_rollout<Mo>), dim3(grid_for(M)), dim3(kBlock), 0, c->stream, k, g, step_limit, on.dev, ot.dev, M, tr, rp);
+            hipLaunchKernelGGL((k_rollout<Mo>), dim3(grid_for(M)), dim3(kBlock), 0, c->stream, k, g, step_limit, d_n, d_total, M, tr, rp);
         })) return NO_MODEL(c);
     KCHECK();
-    bool sync = false;
-    TRY(flush_out(c, &on, &sync)); TRY(flush_out(c, &ot, &sync)); TRY(flush_out(c, &os, &sync));
-    TRY(flush_out(c, &oa, &sync)); TRY(flush_out(c, &orw, &sync)); TRY(flush_out(c, &otm, &sync));
-    if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
-    return RSRL_HIP_OK;
+    return f.finish();
 }
 int rsrl_hip_rollout_greedy(rsrl_hip_ctx* c, int64_t step_limit, uint32_t* n_states_out, float* total_reward_out) {
     CHECK_CTX(c);

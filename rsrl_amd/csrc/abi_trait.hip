@@ -70,7 +70,28 @@ int flush_pending(rsrl_hip_ctx* c) {
     c->pending = 0;
     return train_now(c, n, nullptr);
 }
-// fused register-family loop: any split of n batch-steps into launches gives bit-identical results (Q(s,.) is carried between
+// Domain::transition's five arrays, as the kernels take them.  Act: int32_t indices or f32 actions (rsrl_hip_domain_step_f32)
+template <class Act>
+struct StepArrays { const Act* act; float* from; float* next; float* rew; uint8_t* term; };
+template <class Act>
+static int stage_step(CallFrame& f, const Act* actions, float* from, float* next, float* rew, uint8_t* term, StepArrays<Act>* s) {
+    const size_t N = (size_t)f.c->cfg.n_envs, DN = (size_t)f.c->D * N;
+    TRY(f.in(actions, N, &s->act));
+    TRY(f.out(from, DN, &s->from)); TRY(f.out(next, DN, &s->next));
+    TRY(f.out(rew, N, &s->rew)); TRY(f.out(term, N, &s->term));
+    return RSRL_HIP_OK;
+}
+// Handler::handle's M transitions (launch.hpp), int32 or f32 actions alike
+template <class Act>
+static int stage_transitions(CallFrame& f, const float* from, const Act* act, const float* rew, const float* to, const uint8_t* term, int64_t M, float* td_out,
+                             TransitionsOf<Act>* io) {
+    const size_t DM = (size_t)f.c->D * M;
+    TRY(f.in(from, DM, &io->from)); TRY(f.in(act, (size_t)M, &io->act)); TRY(f.in(rew, (size_t)M, &io->rew));
+    TRY(f.in(to, DM, &io->to)); TRY(f.in(term, (size_t)M, &io->term));
+    TRY(f.out(td_out, (size_t)M, &io->td_out));
+    io->M = M;
+    return RSRL_HIP_OK;
+}
 
 RSRL_API_BEGIN
 
@@ -83,27 +104,19 @@ int rsrl_hip_domain_step(rsrl_hip_ctx* c, const int32_t* actions, float* from_st
     // the trait-granular loop on a ctx-owned stream: a transition handed over in device arrays is ACCEPTED here and launched with the calls that
     // follow it (rsrl_hip_handle on exactly these arrays, rsrl_hip_domain_reset on the terminal flags, rsrl_hip_policy_sample of the ctx's envs) as
     // one kernel -- or, by whatever other call comes next, as the kernel it would have been now.  Same results, same order (kernels_trait.hpp).
-    if (trait_fast(c) && c->own_stream && actions && from_states && next_states && rewards && terminal && is_device_ptr(actions) &&
-        is_device_ptr(from_states) && is_device_ptr(next_states) && is_device_ptr(rewards) && is_device_ptr(terminal) && !c->sw.no_trait_defer) {
+    CallFrame f(c);
+    if (trait_fast(c) && c->own_stream && !c->sw.no_trait_defer && f.device(actions) && f.device(from_states) && f.device(next_states) && f.device(rewards) &&
+        f.device(terminal)) {
         c->tp = rsrl_hip_ctx::TraitPend{};
         c->tp.stage = 1; c->tp.act = actions; c->tp.from = from_states; c->tp.to = next_states; c->tp.rew = rewards; c->tp.term = terminal;
         return RSRL_HIP_OK;
     }
-    const int64_t N = c->cfg.n_envs; const size_t DN = (size_t)c->D * N;
-    const int32_t* d_act; OutBuf<float> ofrom, onext, orew; OutBuf<uint8_t> oterm;
-    TRY(check_host_actions(actions, (size_t)N, c->A));
-    TRY(stage_in(c, 0, actions, (size_t)N, &d_act));
-    TRY(stage_out(c, 1, from_states, DN, &ofrom));
-    TRY(stage_out(c, 2, next_states, DN, &onext));
-    TRY(stage_out(c, 3, rewards, (size_t)N, &orew));
-    TRY(stage_out(c, 4, terminal, (size_t)N, &oterm));
+    TRY(check_host_actions(f, actions, (size_t)c->cfg.n_envs, c->A));
+    StepArrays<int32_t> s;
+    TRY(stage_step(f, actions, from_states, next_states, rewards, terminal, &s));
     const Common k = make_common(c);
-    TRY(launch_domain_step(c, k, d_act, ofrom.dev, onext.dev, orew.dev, oterm.dev));
-    bool sync = false;
-    TRY(flush_out(c, &ofrom, &sync)); TRY(flush_out(c, &onext, &sync));
-    TRY(flush_out(c, &orew, &sync)); TRY(flush_out(c, &oterm, &sync));
-    if (sync || (actions && !is_device_ptr(actions))) HIP_TRY(hipStreamSynchronize(c->stream));
-    return RSRL_HIP_OK;
+    TRY(launch_domain_step(c, k, s.act, s.from, s.next, s.rew, s.term));
+    return f.finish();
 }
 
 int rsrl_hip_domain_reset(rsrl_hip_ctx* c, const uint8_t* mask) {
@@ -113,14 +126,14 @@ int rsrl_hip_domain_reset(rsrl_hip_ctx* c, const uint8_t* mask) {
     c->q_valid = false;
     HIP_TRY(hipSetDevice(c->cfg.device));
     const int64_t N = c->cfg.n_envs;
+    CallFrame f(c);
     const uint8_t* d_mask;
-    TRY(stage_in(c, 0, mask, (size_t)N, &d_mask));
+    TRY(f.in(mask, (size_t)N, &d_mask));
     const Common k = make_common(c);
     TRY(launch_domain_reset(c, k, d_mask));
     // REINFORCE: the restarted learners begin new episodes, sampled from theta as it stands (theta_b <- theta, g <- 0)
     if (c->family == AgentFamily::ReinforceReg) { launch_reinforce_restart(c->stream, make_reinforce(c), N, (int64_t)c->F * c->A, d_mask); KCHECK(); }
-    if (mask && !is_device_ptr(mask)) HIP_TRY(hipStreamSynchronize(c->stream));
-    return RSRL_HIP_OK;
+    return f.finish();
 }
 
 static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* fout, size_t fcount, int32_t* iout,
@@ -142,14 +155,14 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
     if (c->cfg.algo == RSRL_REINFORCE && (op == QOP_EVALUATE || op == QOP_FIND_MAX || op == QOP_FIND_MIN || op == QOP_EXPECTED))
         return fail(RSRL_HIP_ESTATE, "REINFORCE has no value function (use the policy operations; BaselineREINFORCE's value side is its baseline)");
     HIP_TRY(hipSetDevice(c->cfg.device));
-    const float* d_states; OutBuf<float> of; OutBuf<int32_t> oi;
-    TRY(stage_in(c, 0, states, (size_t)c->D * M_, &d_states));
-    TRY(stage_out(c, 1, fout, fcount, &of));
-    TRY(stage_out(c, 2, iout, icount ? icount : (size_t)M_, &oi));
-    const float* d_fin = nullptr; const int32_t* d_iin = nullptr;
-    if (iin) TRY(check_host_actions(iin, (size_t)M_, c->A));
-    TRY(stage_in(c, 3, fin, fin_count, &d_fin));
-    TRY(stage_in(c, 4, iin, (size_t)M_, &d_iin));
+    CallFrame f(c);
+    const float* d_states; float* d_fout; int32_t* d_iout; const float* d_fin; const int32_t* d_iin;
+    TRY(f.in(states, (size_t)c->D * M_, &d_states));
+    TRY(f.out(fout, fcount, &d_fout));
+    TRY(f.out(iout, icount ? icount : (size_t)M_, &d_iout));
+    TRY(check_host_actions(f, iin, (size_t)M_, c->A));
+    TRY(f.in(fin, fin_count, &d_fin));
+    TRY(f.in(iin, (size_t)M_, &d_iin));
     // the policy's operations read the policy's weights (ActorCritic: the Gibbs actor's theta), the rest the action-value function
     const bool policy_op = op == QOP_SAMPLE || op == QOP_SAMPLE_STEP || op == QOP_SAMPLE_INIT || op == QOP_MODE || op == QOP_PROBS || op == QOP_PROB_SA;
     Common k = policy_op ? make_policy_common(c) : make_common(c);
@@ -159,11 +172,11 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
     if (op == QOP_SAMPLE) c->api_calls++;
     const BasisGeom g = make_geom(c);
     if (has_lstd_state(c) && op == QOP_EVALUATE) {                        // V(s) = f32(phi(s) . theta), in f64 (k_lstd_v)
-        if (!launch_lstd_v(feature_domain(c), c->cfg.order, c->stream, c->lstd_theta, d_states, M_, of.dev)) return NO_MODEL(c);
+        if (!launch_lstd_v(feature_domain(c), c->cfg.order, c->stream, c->lstd_theta, d_states, M_, d_fout)) return NO_MODEL(c);
     } else if (is_continuous(c)) {                                        // QOP_FEATURES: MountainCar's projection at the same order
         bool ok = false;
 #define X(DM, OR) if (DM == RSRL_MOUNTAIN_CAR && c->cfg.order == OR) { \
-            hipLaunchKernelGGL((k_qop<FourierModel<DM, OR>>), dim3(grid_for(M_)), dim3(kBlock), 0, c->stream, k, g, op, d_states, M_, call, of.dev, oi.dev, d_fin, d_iin); ok = true; }
+            hipLaunchKernelGGL((k_qop<FourierModel<DM, OR>>), dim3(grid_for(M_)), dim3(kBlock), 0, c->stream, k, g, op, d_states, M_, call, d_fout, d_iout, d_fin, d_iin); ok = true; }
         RSRL_REG_FOURIER(X)
 #undef X
         if (!ok) return NO_MODEL(c);
@@ -173,31 +186,28 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
         case AgentFamily::WaveAux:
             for_wave(c, [&](auto tag) {
                 using T = decltype(tag); using WT = typename T::wt;
-                hipLaunchKernelGGL((k_wave_v_evaluate<T::domain, WT>), dim3(wave_grid_for(M_)), dim3(kBlock), 0, c->stream, (const WT*)c->W, d_states, M_, of.dev);
+                hipLaunchKernelGGL((k_wave_v_evaluate<T::domain, WT>), dim3(wave_grid_for(M_)), dim3(kBlock), 0, c->stream, (const WT*)c->W, d_states, M_, d_fout);
             });
             break;
-        case AgentFamily::TdTile: ok = launch_v_tile(c->cfg.domain, c->cfg.n_tilings, c->stream, k, g, d_states, M_, of.dev); break;
-        case AgentFamily::TdGeneric: ok = launch_v_model(c->cfg, dim3(grid_for(M_)), dim3(kBlock), c->stream, k, g, d_states, M_, of.dev); break;
-        default: ok = launch_v_evaluate(c->cfg.domain, c->cfg.order, dim3(grid_for(M_)), dim3(kBlock), c->stream, k, d_states, M_, of.dev); break;
+        case AgentFamily::TdTile: ok = launch_v_tile(c->cfg.domain, c->cfg.n_tilings, c->stream, k, g, d_states, M_, d_fout); break;
+        case AgentFamily::TdGeneric: ok = launch_v_model(c->cfg, dim3(grid_for(M_)), dim3(kBlock), c->stream, k, g, d_states, M_, d_fout); break;
+        default: ok = launch_v_evaluate(c->cfg.domain, c->cfg.order, dim3(grid_for(M_)), dim3(kBlock), c->stream, k, d_states, M_, d_fout); break;
         }
         if (!ok) return NO_MODEL(c);
     } else if (c->family == AgentFamily::Hiv) {
-        launch_hiv_qop(c->stream, k, g, op, d_states, M_, call, of.dev, oi.dev, d_fin, d_iin);
+        launch_hiv_qop(c->stream, k, g, op, d_states, M_, call, d_fout, d_iout, d_fin, d_iin);
     } else if (is_wave_family(c->family)) {
         for_wave(c, [&](auto tag) {
             using T = decltype(tag); using WT = typename T::wt;
-            hipLaunchKernelGGL((k_wave_qop<T::domain, WT>), dim3(wave_grid_for(M_)), dim3(kBlock), 0, c->stream, k, (const WT*)c->W, op, d_states, M_, call, of.dev, oi.dev,
+            hipLaunchKernelGGL((k_wave_qop<T::domain, WT>), dim3(wave_grid_for(M_)), dim3(kBlock), 0, c->stream, k, (const WT*)c->W, op, d_states, M_, call, d_fout, d_iout,
                                d_fin, d_iin);
         });
     } else if (!for_model(c, [&](auto tag) {
             using M = typename decltype(tag)::type;
-            hipLaunchKernelGGL((k_qop<M>), dim3(grid_for(M_)), dim3(kBlock), 0, c->stream, k, g, op, d_states, M_, call, of.dev, oi.dev, d_fin, d_iin);
+            hipLaunchKernelGGL((k_qop<M>), dim3(grid_for(M_)), dim3(kBlock), 0, c->stream, k, g, op, d_states, M_, call, d_fout, d_iout, d_fin, d_iin);
         })) return NO_MODEL(c);
     KCHECK();
-    bool sync = !is_device_ptr(states) || (fin && !is_device_ptr(fin)) || (iin && !is_device_ptr(iin));
-    TRY(flush_out(c, &of, &sync)); TRY(flush_out(c, &oi, &sync));
-    if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
-    return RSRL_HIP_OK;
+    return f.finish();
 }
 
 int rsrl_hip_q_find_min(rsrl_hip_ctx* c, const float* states, int64_t M, int32_t* idx_out, float* val_out) {
@@ -224,23 +234,20 @@ static int sample_emit(rsrl_hip_ctx* c, int64_t M, int32_t* actions_out) {
     NEEDS_INDEX_ACTIONS(c, "rsrl_hip_policy_sample");
     if (M != c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "policy_sample(states = NULL) samples for the ctx's own envs: M must be n_envs (%lld), got %lld", (long long)c->cfg.n_envs, (long long)M);
     if (is_pred(c->cfg.algo)) return fail(RSRL_HIP_ESTATE, "a prediction agent has a state-value function only (use rsrl_hip_q_evaluate for V(s))");
-    const bool dev_out = is_device_ptr(actions_out);
+    CallFrame f(c);
+    int32_t* d_out;
     if (c->family == AgentFamily::LstdReg || c->family == AgentFamily::GmcReg || c->family == AgentFamily::LstdBatchReg || c->family == AgentFamily::GtdReg) {
         // RecursiveLSTD / iLSTD / GradientMC / LSTD / LSTDLambda / GTD2 / TDC: the driver loop's Random sample (what rsrl_hip_train draws at batch-step step_count - 1; the initial sample's stream
         // before the first handle), so that the trait-granular loop runs on the driver loop's draws
         FLUSH(c);
         HIP_TRY(hipSetDevice(c->cfg.device));
-        OutBuf<int32_t> oa;
-        TRY(stage_out(c, 2, actions_out, (size_t)M, &oa));
+        TRY(f.out(actions_out, (size_t)M, &d_out));
         const Common k = make_common(c);
-        launch_lstd_sample(c->cfg.domain, c->stream, k, c->t ? c->t - 1 : 0, c->t ? BLK_STEP : BLK_INIT, oa.dev);
+        launch_lstd_sample(c->cfg.domain, c->stream, k, c->t ? c->t - 1 : 0, c->t ? BLK_STEP : BLK_INIT, d_out);
         KCHECK();
-        bool sync = false;
-        TRY(flush_out(c, &oa, &sync));
-        if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
-        return RSRL_HIP_OK;
+        return f.finish();
     }
-    if (c->tp.stage == 3 && dev_out) {
+    if (c->tp.stage == 3 && f.device(actions_out)) {
         // the whole batch-step -- transition, handle, new episodes, sample -- as ONE kernel
         const rsrl_hip_ctx::TraitPend p = c->tp;
         c->tp.stage = 0;
@@ -260,24 +267,19 @@ static int sample_emit(rsrl_hip_ctx* c, int64_t M, int32_t* actions_out) {
     HIP_TRY(hipSetDevice(c->cfg.device));
     const uint64_t t = c->t ? c->t - 1 : 0;
     const uint32_t blk = c->t ? BLK_STEP : BLK_INIT;
+    TRY(f.out(actions_out, (size_t)M, &d_out));
     if (trait_fast(c)) {
-        OutBuf<int32_t> oa;
-        TRY(stage_out(c, 2, actions_out, (size_t)M, &oa));
         TRY(trait_cache_ready(c));
         const Common k = make_common(c);
         TRY(timing_begin(c));
-        if (!launch_trait_sample(c->cfg.domain, c->cfg.order, c->stream, k, nullptr, M, t, blk, c->tq_key, c->tq_q, oa.dev)) return NO_MODEL(c);
+        if (!launch_trait_sample(c->cfg.domain, c->cfg.order, c->stream, k, nullptr, M, t, blk, c->tq_key, c->tq_q, d_out)) return NO_MODEL(c);
         KCHECK();
         TRY(timing_end(c));
-        bool sync = false;
-        TRY(flush_out(c, &oa, &sync));
-        if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
-        return RSRL_HIP_OK;
+        return f.finish();
     }
-    TRY(qop(c, c->t ? QOP_SAMPLE_STEP : QOP_SAMPLE_INIT, c->state, M, nullptr, 0, actions_out, 0, nullptr, 0, nullptr, t));
-    HIP_TRY(hipMemcpyAsync(c->action, actions_out, sizeof(int32_t) * (size_t)M, hipMemcpyDefault, c->stream));
-    if (!dev_out) HIP_TRY(hipStreamSynchronize(c->stream));
-    return RSRL_HIP_OK;
+    TRY(qop(c, c->t ? QOP_SAMPLE_STEP : QOP_SAMPLE_INIT, c->state, M, nullptr, 0, d_out, 0, nullptr, 0, nullptr, t));      // (device pointers: the frame is this call's)
+    HIP_TRY(hipMemcpyAsync(c->action, d_out, sizeof(int32_t) * (size_t)M, hipMemcpyDefault, c->stream));
+    return f.finish();
 }
 int rsrl_hip_policy_sample(rsrl_hip_ctx* c, const float* states, int64_t M, int32_t* actions_out) {
     CHECK_CTX(c);
@@ -288,18 +290,16 @@ int rsrl_hip_policy_sample(rsrl_hip_ctx* c, const float* states, int64_t M, int3
         // the fast path's sample: a state the hand-over cache holds costs 20 B instead of the learner's 432 B of weights; same bits either way
         FLUSH(c);
         HIP_TRY(hipSetDevice(c->cfg.device));
-        const float* d_states; OutBuf<int32_t> oa;
-        TRY(stage_in(c, 0, states, (size_t)c->D * M, &d_states));
-        TRY(stage_out(c, 2, actions_out, (size_t)M, &oa));
+        CallFrame f(c);
+        const float* d_states; int32_t* d_out;
+        TRY(f.in(states, (size_t)c->D * M, &d_states));
+        TRY(f.out(actions_out, (size_t)M, &d_out));
         TRY(trait_cache_ready(c));
         const Common k = make_common(c);
         const uint64_t call = c->api_calls++;
-        if (!launch_trait_sample(c->cfg.domain, c->cfg.order, c->stream, k, d_states, M, call, BLK_API, c->tq_key, c->tq_q, oa.dev)) return NO_MODEL(c);
+        if (!launch_trait_sample(c->cfg.domain, c->cfg.order, c->stream, k, d_states, M, call, BLK_API, c->tq_key, c->tq_q, d_out)) return NO_MODEL(c);
         KCHECK();
-        bool sync = !is_device_ptr(states);
-        TRY(flush_out(c, &oa, &sync));
-        if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
-        return RSRL_HIP_OK;
+        return f.finish();
     }
     return qop(c, QOP_SAMPLE, states, M, nullptr, 0, actions_out);
 }
@@ -342,8 +342,9 @@ int rsrl_hip_handle(rsrl_hip_ctx* c, const float* from_states, const int32_t* ac
     if (c->family == AgentFamily::LstdBatchReg)
         return fail(RSRL_HIP_ESTATE, "LSTD and LSTDLambda handle whole batches only (Handler<&Batch>, then solve()): use rsrl_hip_handle_transitions");
     // the transition rsrl_hip_domain_step has just been handed (same arrays, every learner): accepted, launched with it (rsrl_hip_domain_step)
+    CallFrame f(c);
     if (c->tp.stage == 1 && from_states == c->tp.from && actions == c->tp.act && rewards == c->tp.rew && to_states == c->tp.to && terminal == c->tp.term &&
-        M == c->cfg.n_envs && (!td_error_out || is_device_ptr(td_error_out))) {
+        M == c->cfg.n_envs && !f.host(td_error_out)) {
         c->tp.stage = 2; c->tp.td = td_error_out; c->tp.t_handle = c->t;
         c->t += 1;
         return RSRL_HIP_OK;
@@ -352,16 +353,9 @@ int rsrl_hip_handle(rsrl_hip_ctx* c, const float* from_states, const int32_t* ac
     if (c->st_rccl_group) return fail(RSRL_HIP_ESTATE, "this ctx is a rank of a single-thread RCCL group: handle() all-reduces the mini-batch delta, and one thread "
                                                        "cannot issue that for one rank at a time -- use one thread / process per rank, or RSRL_EXCHANGE_PEER");
     HIP_TRY(hipSetDevice(c->cfg.device));
-    TRY(check_host_actions(actions, (size_t)M, c->A));
-    const float *d_from, *d_rew, *d_to; const int32_t* d_act; const uint8_t* d_term; OutBuf<float> otd;
-    const bool all_device = is_device_ptr(from_states) && is_device_ptr(actions) && is_device_ptr(rewards) && is_device_ptr(to_states) && is_device_ptr(terminal) &&
-                            (!td_error_out || is_device_ptr(td_error_out));
-    TRY(stage_in(c, 0, from_states, (size_t)c->D * M, &d_from));
-    TRY(stage_in(c, 1, actions, (size_t)M, &d_act));
-    TRY(stage_in(c, 2, rewards, (size_t)M, &d_rew));
-    TRY(stage_in(c, 3, to_states, (size_t)c->D * M, &d_to));
-    TRY(stage_in(c, 4, terminal, (size_t)M, &d_term));
-    TRY(stage_out(c, 5, td_error_out, (size_t)M, &otd));
+    TRY(check_host_actions(f, actions, (size_t)M, c->A));
+    Transitions io;
+    TRY(stage_transitions(f, from_states, actions, rewards, to_states, terminal, M, td_error_out, &io));
     const Common k = make_common(c);
     const BasisGeom g = make_geom(c);
     if (c->family == AgentFamily::SharedSparseLambda) {
@@ -373,8 +367,8 @@ int rsrl_hip_handle(rsrl_hip_ctx* c, const float* from_states, const int32_t* ac
         if (!for_model(c, [&](auto tag) {
                 using Mo = typename decltype(tag)::type;
                 if constexpr (Mo::kSparse) {
-                    hipLaunchKernelGGL((k_sparse_handle<Mo>), dim3(grid_for(M)), dim3(kBlock), 0, c->stream, ks, g, d_from, d_act, d_rew, d_to, d_term, M, c->t,
-                                       c->cfg.algo == RSRL_Q_LAMBDA ? 1 : 0, c->flags, c->sc_keys, c->sc_terms, otd.dev);
+                    hipLaunchKernelGGL((k_sparse_handle<Mo>), dim3(grid_for(M)), dim3(kBlock), 0, c->stream, ks, g, io.from, io.act, io.rew, io.to, io.term, M, c->t,
+                                       c->cfg.algo == RSRL_Q_LAMBDA ? 1 : 0, c->flags, c->sc_keys, c->sc_terms, io.td_out);
                     launch_sparse_trace_scatter(c, M, 0);
                 }
             })) return NO_MODEL(c);
@@ -391,32 +385,26 @@ int rsrl_hip_handle(rsrl_hip_ctx* c, const float* from_states, const int32_t* ac
         }
         c->q_valid = false; c->tq_valid = false;
         c->t += 1;
-        bool sync = !all_device;
-        TRY(flush_out(c, &otd, &sync));
-        if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
-        return RSRL_HIP_OK;
+        return f.finish();
     }
     if (trait_fast(c)) {
-        TRY(launch_trait_handle(c, k, d_from, d_act, d_rew, d_to, d_term, M, c->t, otd.dev));
+        TRY(launch_trait_handle(c, k, io.from, io.act, io.rew, io.to, io.term, M, c->t, io.td_out));
     } else {
         switch (family_row(c).handle) {
         case Handle::Wave:
             for_wave(c, [&](auto tag) {
                 using T = decltype(tag); using WT = typename T::wt;
-                hipLaunchKernelGGL((k_wave_handle<T::domain, WT>), dim3(wave_grid_for(M)), dim3(kBlock), 0, c->stream, k, (WT*)c->W, d_from, d_act, d_rew, d_to, d_term, M, c->t,
-                                   otd.dev);
+                hipLaunchKernelGGL((k_wave_handle<T::domain, WT>), dim3(wave_grid_for(M)), dim3(kBlock), 0, c->stream, k, (WT*)c->W, io.from, io.act, io.rew, io.to, io.term, M, c->t,
+                                   io.td_out);
             });
             break;
         case Handle::Model:
             if (!for_model(c, [&](auto tag) {
                     using Mo = typename decltype(tag)::type;
-                    hipLaunchKernelGGL((k_handle<Mo>), dim3(grid_for(M)), dim3(kBlock), 0, c->stream, k, g, d_from, d_act, d_rew, d_to, d_term, M, c->t, otd.dev, c->h_fx);
+                    hipLaunchKernelGGL((k_handle<Mo>), dim3(grid_for(M)), dim3(kBlock), 0, c->stream, k, g, io.from, io.act, io.rew, io.to, io.term, M, c->t, io.td_out, c->h_fx);
                 })) return NO_MODEL(c);
             break;
-        case Handle::Agent: {
-            const Transitions io{d_from, d_act, d_rew, d_to, d_term, M, otd.dev};
-            TRY(launch_agent(c, k, g, c->t, 1, nullptr, &io));
-        }
+        case Handle::Agent: TRY(launch_agent(c, k, g, c->t, 1, nullptr, &io));
         }
     }
     KCHECK();
@@ -435,10 +423,7 @@ int rsrl_hip_handle(rsrl_hip_ctx* c, const float* from_states, const int32_t* ac
     if (!trait_fast(c)) c->tq_valid = false;
     c->t += 1;          // one handle call = one batch-step of learning: the agent-side draws (SARSA's inner sample,
                         // bf16 stochastic rounding) advance exactly as they do inside rsrl_hip_train
-    bool sync = !all_device;   // host inputs are staged asynchronously: they must have been read when the call returns; device arrays are asynchronous
-    TRY(flush_out(c, &otd, &sync));
-    if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
-    return RSRL_HIP_OK;
+    return f.finish();
 }
 
 // ---- f32 actions: the twins of the calls above for a continuous ctx (ContinuousMountainCar with the Beta policy; kernels_tdac_beta.hpp)
@@ -447,24 +432,16 @@ int rsrl_hip_domain_step_f32(rsrl_hip_ctx* c, const float* actions, float* from_
     NEEDS_F32_ACTIONS(c, "rsrl_hip_domain_step");
     c->q_valid = false;
     HIP_TRY(hipSetDevice(c->cfg.device));
-    const int64_t N = c->cfg.n_envs; const size_t DN = (size_t)c->D * N;
-    const float* d_act; OutBuf<float> ofrom, onext, orew; OutBuf<uint8_t> oterm;
-    TRY(check_host_actions_f32(actions, (size_t)N, false));      // (Domain::transition maps the action onto its bounds itself)
-    TRY(stage_in(c, 0, actions, (size_t)N, &d_act));
-    TRY(stage_out(c, 1, from_states, DN, &ofrom));
-    TRY(stage_out(c, 2, next_states, DN, &onext));
-    TRY(stage_out(c, 3, rewards, (size_t)N, &orew));
-    TRY(stage_out(c, 4, terminal, (size_t)N, &oterm));
+    CallFrame f(c);
+    TRY(check_host_actions_f32(f, actions, (size_t)c->cfg.n_envs, false));      // (Domain::transition maps the action onto its bounds itself)
+    StepArrays<float> s;
+    TRY(stage_step(f, actions, from_states, next_states, rewards, terminal, &s));
     const Common k = make_common(c);
     // (NAC: explicit actions are the domain's, the pending ones the agent's -- stepped on through the loop's 2a - 1)
-    if (is_nac(c->cfg.algo)) launch_nac_domain_step(c->stream, k, d_act, c->action_f, ofrom.dev, onext.dev, orew.dev, oterm.dev);
-    else launch_cmc_domain_step(c->stream, k, d_act, c->action_f, ofrom.dev, onext.dev, orew.dev, oterm.dev);
+    if (is_nac(c->cfg.algo)) launch_nac_domain_step(c->stream, k, s.act, c->action_f, s.from, s.next, s.rew, s.term);
+    else launch_cmc_domain_step(c->stream, k, s.act, c->action_f, s.from, s.next, s.rew, s.term);
     KCHECK();
-    bool sync = false;
-    TRY(flush_out(c, &ofrom, &sync)); TRY(flush_out(c, &onext, &sync));
-    TRY(flush_out(c, &orew, &sync)); TRY(flush_out(c, &oterm, &sync));
-    if (sync || (actions && !is_device_ptr(actions))) HIP_TRY(hipStreamSynchronize(c->stream));
-    return RSRL_HIP_OK;
+    return f.finish();
 }
 
 int rsrl_hip_handle_f32(rsrl_hip_ctx* c, const float* from_states, const float* actions, const float* rewards, const float* to_states,
@@ -475,45 +452,33 @@ int rsrl_hip_handle_f32(rsrl_hip_ctx* c, const float* from_states, const float* 
     NEEDS_F32_ACTIONS(c, "rsrl_hip_handle");
     FLUSH(c);
     HIP_TRY(hipSetDevice(c->cfg.device));
-    TRY(check_host_actions_f32(actions, (size_t)M, false));      // (the update clamps the action to the sample's interval)
+    CallFrame f(c);
+    TRY(check_host_actions_f32(f, actions, (size_t)M, false));      // (the update clamps the action to the sample's interval)
     TransitionsF32 io;
-    OutBuf<float> otd;
-    const bool all_device = is_device_ptr(from_states) && is_device_ptr(actions) && is_device_ptr(rewards) && is_device_ptr(to_states) && is_device_ptr(terminal) &&
-                            (!td_error_out || is_device_ptr(td_error_out));
-    TRY(stage_in(c, 0, from_states, (size_t)c->D * M, &io.from));
-    TRY(stage_in(c, 1, actions, (size_t)M, &io.act));
-    TRY(stage_in(c, 2, rewards, (size_t)M, &io.rew));
-    TRY(stage_in(c, 3, to_states, (size_t)c->D * M, &io.to));
-    TRY(stage_in(c, 4, terminal, (size_t)M, &io.term));
-    TRY(stage_out(c, 5, td_error_out, (size_t)M, &otd));
-    io.M = M; io.td_out = otd.dev;
+    TRY(stage_transitions(f, from_states, actions, rewards, to_states, terminal, M, td_error_out, &io));
     const Common k = make_common(c);
     if (!(is_nac(c->cfg.algo) ? launch_nac_beta(c->cfg.order, c->stream, k, make_nac_beta(c), c->t, 1, nullptr, &io)      // critic.handle: SARSA over SCB
                               : launch_tdac_beta(c->cfg.order, c->stream, k, make_tdac_beta(c), c->t, 1, nullptr, &io))) return NO_MODEL(c);
     KCHECK();
     c->q_valid = false;
     c->t += 1;          // one handle call = one batch-step, as rsrl_hip_handle
-    bool sync = !all_device;
-    TRY(flush_out(c, &otd, &sync));
-    if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
-    return RSRL_HIP_OK;
+    return f.finish();
 }
 
 // the policy side on explicit states (or, for the sample, the ctx's own envs): one launch of k_beta_policy
 static int beta_op(rsrl_hip_ctx* c, int op, const float* states, int64_t M, uint64_t t, uint32_t purpose, const float* act_in, float* out0, float* out1, float* keep) {
+    CallFrame f(c);
+    TRY(check_host_actions_f32(f, act_in, (size_t)M, false));      // (rsrl_hip_policy_pdf's actions, the one caller with any)
     HIP_TRY(hipSetDevice(c->cfg.device));
-    const float* d_states; const float* d_act; OutBuf<float> o0, o1;
-    TRY(stage_in(c, 0, states, (size_t)c->D * M, &d_states));
-    TRY(stage_in(c, 3, act_in, (size_t)M, &d_act));
-    TRY(stage_out(c, 1, out0, (size_t)M, &o0));
-    TRY(stage_out(c, 2, out1, (size_t)M, &o1));
+    const float* d_states; const float* d_act; float* d_out0; float* d_out1;
+    TRY(f.in(states, (size_t)c->D * M, &d_states));
+    TRY(f.in(act_in, (size_t)M, &d_act));
+    TRY(f.out(out0, (size_t)M, &d_out0));
+    TRY(f.out(out1, (size_t)M, &d_out1));
     const Common k = make_common(c);
-    if (!launch_beta_policy(c->cfg.order, c->stream, k, c->Z, op, d_states, M, t, purpose, d_act, o0.dev, o1.dev, keep)) return NO_MODEL(c);
+    if (!launch_beta_policy(c->cfg.order, c->stream, k, c->Z, op, d_states, M, t, purpose, d_act, d_out0, d_out1, keep)) return NO_MODEL(c);
     KCHECK();
-    bool sync = (states && !is_device_ptr(states)) || (act_in && !is_device_ptr(act_in));
-    TRY(flush_out(c, &o0, &sync)); TRY(flush_out(c, &o1, &sync));
-    if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
-    return RSRL_HIP_OK;
+    return f.finish();
 }
 static int beta_batch(rsrl_hip_ctx* c, const float* states, int64_t M) {
     if (!states || M < 1 || M > c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "bad batch (M=%lld, n_envs=%lld)", (long long)M, (long long)c->cfg.n_envs);
@@ -556,7 +521,6 @@ int rsrl_hip_policy_pdf(rsrl_hip_ctx* c, const float* states, const float* actio
     if (!is_continuous(c)) return fail(RSRL_HIP_ESTATE, "%s", kNoBetaPolicy);
     FLUSH(c);
     TRY(beta_batch(c, states, M));
-    TRY(check_host_actions_f32(actions, (size_t)M, false));
     return beta_op(c, BETA_OP_PDF, states, M, 0, 0, actions, out, nullptr, nullptr);
 }
 
@@ -568,18 +532,16 @@ int rsrl_hip_q_evaluate_f32(rsrl_hip_ctx* c, const float* states, const float* a
     if (!is_nac(c->cfg.algo)) return fail(RSRL_HIP_ESTATE, "%s", kNoNac);
     FLUSH(c);
     TRY(beta_batch(c, states, M));
-    TRY(check_host_actions_f32(actions, (size_t)M, false));      // (the score clamps the action to the sample's interval)
+    CallFrame f(c);
+    TRY(check_host_actions_f32(f, actions, (size_t)M, false));      // (the score clamps the action to the sample's interval)
     HIP_TRY(hipSetDevice(c->cfg.device));
-    const float* d_states; const float* d_act; OutBuf<float> oq;
-    TRY(stage_in(c, 0, states, (size_t)c->D * M, &d_states));
-    TRY(stage_in(c, 1, actions, (size_t)M, &d_act));
-    TRY(stage_out(c, 2, q_out, (size_t)M, &oq));
-    if (!launch_nac_q(c->cfg.order, c->stream, make_common(c), make_nac_beta(c), d_states, d_act, M, oq.dev)) return NO_MODEL(c);
+    const float* d_states; const float* d_act; float* d_q;
+    TRY(f.in(states, (size_t)c->D * M, &d_states));
+    TRY(f.in(actions, (size_t)M, &d_act));
+    TRY(f.out(q_out, (size_t)M, &d_q));
+    if (!launch_nac_q(c->cfg.order, c->stream, make_common(c), make_nac_beta(c), d_states, d_act, M, d_q)) return NO_MODEL(c);
     KCHECK();
-    bool sync = !is_device_ptr(states) || !is_device_ptr(actions);
-    TRY(flush_out(c, &oq, &sync));
-    if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
-    return RSRL_HIP_OK;
+    return f.finish();
 }
 int rsrl_hip_nac_update(rsrl_hip_ctx* c, const uint8_t* mask, float* norm_out) {
     CHECK_CTX(c);
@@ -587,16 +549,14 @@ int rsrl_hip_nac_update(rsrl_hip_ctx* c, const uint8_t* mask, float* norm_out) {
     FLUSH(c);
     HIP_TRY(hipSetDevice(c->cfg.device));
     const size_t N = (size_t)c->cfg.n_envs;
-    const uint8_t* d_mask; OutBuf<float> on;
-    TRY(stage_in(c, 0, mask, N, &d_mask));
-    TRY(stage_out(c, 1, norm_out, N, &on));
-    if (!launch_nac_update(c->cfg.order, c->stream, make_common(c), make_nac_beta(c), d_mask, on.dev)) return NO_MODEL(c);
+    CallFrame f(c);
+    const uint8_t* d_mask; float* d_norm;
+    TRY(f.in(mask, N, &d_mask));
+    TRY(f.out(norm_out, N, &d_norm));
+    if (!launch_nac_update(c->cfg.order, c->stream, make_common(c), make_nac_beta(c), d_mask, d_norm)) return NO_MODEL(c);
     KCHECK();
     c->q_valid = false;
-    bool sync = mask && !is_device_ptr(mask);
-    TRY(flush_out(c, &on, &sync));
-    if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
-    return RSRL_HIP_OK;
+    return f.finish();
 }
 
 int rsrl_hip_handle_batch(rsrl_hip_ctx* c, int64_t T, const float* states, const int32_t* actions, const float* rewards, const uint32_t* lengths,
@@ -614,7 +574,8 @@ int rsrl_hip_handle_batch(rsrl_hip_ctx* c, int64_t T, const float* states, const
     HIP_TRY(hipSetDevice(c->cfg.device));
     const int64_t N = c->cfg.n_envs;
     // host arrays are validated where a learner's batch reads them (its rows 0 .. lengths[i]-1); device arrays are clamped by the kernel instead
-    const bool host_len = !is_device_ptr(lengths), host_act = actions && !is_device_ptr(actions);
+    CallFrame f(c);
+    const bool host_len = f.host(lengths), host_act = f.host(actions);
     if (host_len)
         for (int64_t i = 0; i < N; ++i)
             if ((int64_t)lengths[i] > T) return fail(RSRL_HIP_EINVAL, "lengths[%lld] = %u is more than the batch's %lld rows", (long long)i, lengths[i], (long long)T);
@@ -623,16 +584,14 @@ int rsrl_hip_handle_batch(rsrl_hip_ctx* c, int64_t T, const float* states, const
             for (int64_t t = 0; t < (int64_t)lengths[i]; ++t)
                 if (actions[t * N + i] < 0 || actions[t * N + i] >= c->A)
                     return fail(RSRL_HIP_EINVAL, "actions[%lld][%lld] = %d is outside [0, %d)", (long long)t, (long long)i, actions[t * N + i], c->A);
-    const bool all_device = !host_len && (T == 0 || (is_device_ptr(states) && !host_act && is_device_ptr(rewards))) && (!returns_out || is_device_ptr(returns_out));
     ReinforceBatch io;
-    const size_t TN = (size_t)T * (size_t)N;
-    TRY(stage_in(c, 0, T > 0 ? states : nullptr, TN * (size_t)c->D, &io.states));
-    TRY(stage_in(c, 1, T > 0 ? actions : nullptr, TN, &io.act));
-    TRY(stage_in(c, 2, T > 0 ? rewards : nullptr, TN, &io.rew));
-    TRY(stage_in(c, 3, lengths, (size_t)N, &io.len));
-    OutBuf<float> oret;
-    TRY(stage_out(c, 4, T > 0 ? returns_out : nullptr, TN, &oret));
-    io.T = T; io.ret_out = oret.dev;
+    const size_t TN = (size_t)T * (size_t)N;      // (T == 0: no rows to read, an empty copy back)
+    TRY(f.in(T > 0 ? states : nullptr, TN * (size_t)c->D, &io.states));
+    TRY(f.in(T > 0 ? actions : nullptr, TN, &io.act));
+    TRY(f.in(T > 0 ? rewards : nullptr, TN, &io.rew));
+    TRY(f.in(lengths, (size_t)N, &io.len));
+    TRY(f.out(returns_out, TN, &io.ret_out));
+    io.T = T;
     if (T > 0) {
         const Common k = make_common(c);
         const GmcBatch gio{io.states, io.rew, io.len, io.T, io.ret_out};
@@ -644,10 +603,7 @@ int rsrl_hip_handle_batch(rsrl_hip_ctx* c, int64_t T, const float* states, const
     }
     c->q_valid = false;
     c->t += 1;          // one handle_batch call = one batch-step, as rsrl_hip_handle: the trait loop stays on the driver loop's draw streams
-    bool sync = !all_device;
-    TRY(flush_out(c, &oret, &sync));
-    if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
-    return RSRL_HIP_OK;
+    return f.finish();
 }
 
 // Handler<&Batch>::handle of LSTD / LSTDLambda for every learner (kernels_lstd_batch.hpp): whole transitions, then solve()
@@ -663,22 +619,19 @@ int rsrl_hip_handle_transitions(rsrl_hip_ctx* c, int64_t T, const float* from_st
     FLUSH(c);
     HIP_TRY(hipSetDevice(c->cfg.device));
     const int64_t N = c->cfg.n_envs;
-    const bool host_len = !is_device_ptr(lengths);      // host lengths are validated; device ones are clamped by the kernel
-    if (host_len)
+    CallFrame f(c);
+    if (f.host(lengths))      // host lengths are validated; device ones are clamped by the kernel
         for (int64_t i = 0; i < N; ++i)
             if ((int64_t)lengths[i] > T) return fail(RSRL_HIP_EINVAL, "lengths[%lld] = %u is more than the batch's %lld rows", (long long)i, lengths[i], (long long)T);
-    const bool all_device = !host_len && (T == 0 || (is_device_ptr(from_states) && is_device_ptr(rewards) && is_device_ptr(to_states) && is_device_ptr(terminal))) &&
-                            (!td_out || is_device_ptr(td_out));
     TransitionBatch io;
-    const size_t TN = (size_t)T * (size_t)N;
-    TRY(stage_in(c, 0, T > 0 ? from_states : nullptr, TN * (size_t)c->D, &io.from));
-    TRY(stage_in(c, 1, T > 0 ? rewards : nullptr, TN, &io.rew));
-    TRY(stage_in(c, 2, T > 0 ? to_states : nullptr, TN * (size_t)c->D, &io.to));
-    TRY(stage_in(c, 3, T > 0 ? terminal : nullptr, TN, &io.term));
-    TRY(stage_in(c, 4, lengths, (size_t)N, &io.len));
-    OutBuf<float> otd;
-    TRY(stage_out(c, 5, T > 0 ? td_out : nullptr, TN, &otd));
-    io.T = T; io.td_out = otd.dev;
+    const size_t TN = (size_t)T * (size_t)N;      // (T == 0: no rows to read, an empty copy back)
+    TRY(f.in(T > 0 ? from_states : nullptr, TN * (size_t)c->D, &io.from));
+    TRY(f.in(T > 0 ? rewards : nullptr, TN, &io.rew));
+    TRY(f.in(T > 0 ? to_states : nullptr, TN * (size_t)c->D, &io.to));
+    TRY(f.in(T > 0 ? terminal : nullptr, TN, &io.term));
+    TRY(f.in(lengths, (size_t)N, &io.len));
+    TRY(f.out(td_out, TN, &io.td_out));
+    io.T = T;
     if (T > 0) {
         const Common k = make_common(c);
         if (!launch_lstd_batch(c->cfg.domain, c->cfg.order, c->cfg.algo == RSRL_LSTD_LAMBDA, c->stream, k, make_lstd_batch(c), c->t, 1, nullptr, &io)) return NO_MODEL(c);
@@ -686,10 +639,7 @@ int rsrl_hip_handle_transitions(rsrl_hip_ctx* c, int64_t T, const float* from_st
     }
     c->q_valid = false;
     c->t += 1;          // one call = one batch-step, as rsrl_hip_handle_batch: the trait loop stays on the driver loop's draw streams
-    bool sync = !all_device;
-    TRY(flush_out(c, &otd, &sync));
-    if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
-    return RSRL_HIP_OK;
+    return f.finish();
 }
 
 // the agents' public solve() (lstd.rs:40, lstd_lambda.rs:44) for every learner

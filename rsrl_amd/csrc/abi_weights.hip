@@ -3,25 +3,18 @@
 #include "ctx.hpp"
 
 // One learner's array between the caller's memory (host or device) and the device: launch(d_out, d_in) enqueues the kernel that fills d_out (a read,
-// d_in null) or consumes d_in (a write, d_out null), n floats either way.  A host array goes through scratch slot 0 and costs one synchronise;
-// *synced says that a read waited for the device.
+// d_in null) or consumes d_in (a write, d_out null), n floats either way.  The call's frame is this helper's: a host array is staged and costs one
+// synchronise; *synced says that a read waited for the device.
 template <class Launch>
 static int staged_rw(rsrl_hip_ctx* c, size_t n, float* out, const float* in, Launch&& launch, bool* synced = nullptr) {
-    if (out) {
-        OutBuf<float> ob;
-        TRY(stage_out(c, 0, out, n, &ob));
-        launch(ob.dev, (const float*)nullptr);
-        KCHECK();
-        bool sync = false; TRY(flush_out(c, &ob, &sync));
-        if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
-        if (synced) *synced = sync;
-    } else {
-        const float* d_in;
-        TRY(stage_in(c, 0, in, n, &d_in));
-        launch((float*)nullptr, d_in);
-        KCHECK();
-        if (!is_device_ptr(in)) HIP_TRY(hipStreamSynchronize(c->stream));
-    }
+    CallFrame f(c);
+    float* d_out = nullptr; const float* d_in = nullptr;
+    if (out) TRY(f.out(out, n, &d_out));
+    else TRY(f.in(in, n, &d_in));
+    launch(d_out, d_in);
+    KCHECK();
+    TRY(f.finish());
+    if (synced && out) *synced = !f.all_device();
     return RSRL_HIP_OK;
 }
 // one learner's dense f32[F][cols] matrix out of, or into, a device buffer of W's layout (tile: the tile-coded tables'); wi = the learner's offset in it
@@ -90,14 +83,13 @@ int traces_rw(rsrl_hip_ctx* c, int64_t env_index, float* out, const float* in) {
         if (env_index < 0 || env_index >= c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "env_index out of range");
         HIP_TRY(hipSetDevice(c->cfg.device));
         const int n = c->F * c->Aw;
-        OutBuf<float> oz;
-        TRY(stage_out(c, 0, out, (size_t)n, &oz));
-        HIP_TRY(hipMemsetAsync(oz.dev, 0, sizeof(float) * (size_t)n, c->stream));
-        hipLaunchKernelGGL(k_sparse_trace_get, dim3(kSparseCap / 256), dim3(256), 0, c->stream, SparseTrace{c->sp_keys, c->sp_vals, c->sp_len}, c->cfg.n_tilings, n / c->cfg.n_tilings, env_index, oz.dev);
+        CallFrame f(c);
+        float* d_out;
+        TRY(f.out(out, (size_t)n, &d_out));
+        HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(float) * (size_t)n, c->stream));
+        hipLaunchKernelGGL(k_sparse_trace_get, dim3(kSparseCap / 256), dim3(256), 0, c->stream, SparseTrace{c->sp_keys, c->sp_vals, c->sp_len}, c->cfg.n_tilings, n / c->cfg.n_tilings, env_index, d_out);
         KCHECK();
-        bool sync = false; TRY(flush_out(c, &oz, &sync));
-        if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
-        return RSRL_HIP_OK;
+        return f.finish();
     }
     if (!c->Z) return fail(RSRL_HIP_ESTATE, "this agent has no auxiliary matrix (eligibility trace / fa_td weights)");
     if (env_index < 0 || env_index >= c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "env_index out of range");

@@ -596,7 +596,11 @@ static inline unsigned wave_grid_for(int64_t items) { return (unsigned)((items +
     "no communicator, peer exchange or group (shard by env_offset instead)"); } while (0)
 #define NO_MODEL(c) fail(RSRL_HIP_EINVAL, "no kernel for basis %d domain %d order %d tilings %d", (c)->cfg.basis, (c)->cfg.domain, (c)->cfg.order, (c)->cfg.n_tilings)
 
-// ---- host/device pointer staging ---------------------------------------------------------
+#define TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
+// ---- host / device array arguments: the call frame ------------------------------------------------------------------------------------
+// THE rule (include/rsrl_hip.h, "Conventions"): a device or managed pointer is used in place and the call is asynchronous; a host array is staged
+// through a scratch buffer of the ctx, and the call returns once host inputs have been read and host outputs have landed.  So a call synchronises
+// exactly when at least one non-null array it registered is host memory -- that is finish(), and no entry point says it again.
 static bool is_device_ptr(const void* p) {
     hipPointerAttribute_t attr;
     hipError_t e = hipPointerGetAttributes(&attr, p);
@@ -611,50 +615,74 @@ static int scratch_reserve(rsrl_hip_ctx* c, int slot, size_t bytes) {
     s.cap = bytes;
     return RSRL_HIP_OK;
 }
-// input: returns a device pointer holding the caller's data
-template <class T>
-static int stage_in(rsrl_hip_ctx* c, int slot, const T* user, size_t count, const T** dev) {
-    if (!user) { *dev = nullptr; return RSRL_HIP_OK; }
-    if (is_device_ptr(user)) { *dev = user; return RSRL_HIP_OK; }
-    int rc = scratch_reserve(c, slot, count * sizeof(T));
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(c->scratch[slot].p, user, count * sizeof(T), hipMemcpyHostToDevice, c->stream));
-    *dev = (const T*)c->scratch[slot].p;
-    return RSRL_HIP_OK;
-}
-// output: returns the device pointer kernels should write; flush copies back if user is host memory
-template <class T>
-struct OutBuf { T* user = nullptr; T* dev = nullptr; size_t count = 0; bool staged = false; };
-template <class T>
-static int stage_out(rsrl_hip_ctx* c, int slot, T* user, size_t count, OutBuf<T>* ob) {
-    ob->user = user; ob->count = count; ob->staged = false; ob->dev = nullptr;
-    if (!user) return RSRL_HIP_OK;
-    if (is_device_ptr(user)) { ob->dev = user; return RSRL_HIP_OK; }
-    int rc = scratch_reserve(c, slot, count * sizeof(T));
-    if (rc) return rc;
-    ob->dev = (T*)c->scratch[slot].p; ob->staged = true;
-    return RSRL_HIP_OK;
-}
-template <class T>
-static int flush_out(rsrl_hip_ctx* c, OutBuf<T>* ob, bool* need_sync) {
-    if (ob->staged) {
-        HIP_TRY(hipMemcpyAsync(ob->user, ob->dev, ob->count * sizeof(T), hipMemcpyDeviceToHost, c->stream));
-        *need_sync = true;
+// One CallFrame per entry-point call.  in() / out() register the call's arrays: null gives null, a device pointer itself, a host array the next
+// scratch slot (0 .. 6 in registration order; slot 7 belongs to the two direct users of scratch_reserve, the checksum of abi_weights.hip and
+// set_states' device validation in abi_ctx.hip).  finish() copies the staged outputs back in registration order and synchronises once, by the rule
+// above; an error return before it does not synchronise.  The runtime is asked about a pointer once per call: host() / device() remember the
+// answer, for the validators and the deferral tests that need it before anything is staged.
+// A helper that runs inside an entry point either OWNS the call's frame (qop, beta_op, staged_rw) or is handed device pointers only
+// (launch_trait_handle; qop under sample_emit: a frame that sees device pointers alone takes no slot and never synchronises) -- two frames that
+// both staged would hand out the same slots.
+struct CallFrame {
+    rsrl_hip_ctx* const c;
+    explicit CallFrame(rsrl_hip_ctx* ctx) : c(ctx) {}
+    bool host(const void* p) {           // a non-null array in host memory
+        if (!p) return false;
+        for (int i = 0; i < n_seen; ++i) if (seen[i].p == p) return seen[i].host;
+        const bool h = !is_device_ptr(p);
+        if (n_seen < kArrays) seen[n_seen++] = {p, h};      // (no call has more than 8 arrays; a ninth would be asked about again)
+        return h;
     }
-    return RSRL_HIP_OK;
-}
+    bool device(const void* p) { return p && !host(p); }
+    bool all_device() const { return !any_host; }      // of the arrays registered so far
+    template <class T> int in(const T* user, size_t count, const T** dev) {
+        void* d = nullptr;
+        TRY(place(user, count * sizeof(T), &d));
+        if (d != user && count) HIP_TRY(hipMemcpyAsync(d, user, count * sizeof(T), hipMemcpyHostToDevice, c->stream));
+        *dev = (const T*)d;
+        return RSRL_HIP_OK;
+    }
+    template <class T> int out(T* user, size_t count, T** dev) {
+        void* d = nullptr;
+        TRY(place(user, count * sizeof(T), &d));
+        if (d != user) outs[n_out++] = {user, d, count * sizeof(T)};
+        *dev = (T*)d;
+        return RSRL_HIP_OK;
+    }
+    int finish() {
+        for (int i = 0; i < n_out; ++i)
+            if (outs[i].bytes) HIP_TRY(hipMemcpyAsync(outs[i].user, outs[i].dev, outs[i].bytes, hipMemcpyDeviceToHost, c->stream));
+        if (any_host) HIP_TRY(hipStreamSynchronize(c->stream));
+        return RSRL_HIP_OK;
+    }
+private:
+    static constexpr int kArrays = 8, kSlots = 7;
+    struct Seen { const void* p; bool host; } seen[kArrays];
+    struct Out { void* user; const void* dev; size_t bytes; } outs[kSlots];
+    int n_seen = 0, n_out = 0, n_slots = 0;
+    bool any_host = false;
+    int place(const void* user, size_t bytes, void** dev) {
+        *dev = const_cast<void*>(user);
+        if (!host(user)) return RSRL_HIP_OK;
+        any_host = true;
+        if (n_slots == kSlots) return fail(RSRL_HIP_EINVAL, "internal: a call stages more than %d host arrays", kSlots);
+        TRY(scratch_reserve(c, n_slots, bytes));
+        *dev = c->scratch[n_slots++].p;
+        return RSRL_HIP_OK;
+    }
+};
 // caller-supplied actions index weight columns (W[:,a]): a HOST array is validated (EINVAL, where the reference would
 // panic on the out-of-range column); a DEVICE array cannot be inspected from here and is clamped by the kernels instead
-static int check_host_actions(const int32_t* a, size_t n, int A) {
-    if (!a || is_device_ptr(a)) return RSRL_HIP_OK;
+static int check_host_actions(CallFrame& f, const int32_t* a, size_t n, int A) {
+    if (!f.host(a)) return RSRL_HIP_OK;
     for (size_t i = 0; i < n; ++i)
         if (a[i] < 0 || a[i] >= A) return fail(RSRL_HIP_EINVAL, "action[%zu] = %d is outside [0, %d)", i, a[i], A);
     return RSRL_HIP_OK;
 }
 // caller-supplied f32 actions (a continuous ctx): a HOST array must hold finite values (bounded: inside ContinuousMountainCar's action bounds too); a
 // DEVICE array is clamped by the kernels instead
-static int check_host_actions_f32(const float* a, size_t n, bool bounded) {
-    if (!a || is_device_ptr(a)) return RSRL_HIP_OK;
+static int check_host_actions_f32(CallFrame& f, const float* a, size_t n, bool bounded) {
+    if (!f.host(a)) return RSRL_HIP_OK;
     for (size_t i = 0; i < n; ++i) {
         if (!std::isfinite(a[i])) return fail(RSRL_HIP_EINVAL, "action[%zu] = %g is not finite", i, (double)a[i]);
         if (bounded && !(a[i] >= -1.0f && a[i] <= 1.0f)) return fail(RSRL_HIP_EINVAL, "action[%zu] = %g is outside [-1, 1]", i, (double)a[i]);
@@ -666,8 +694,9 @@ static int check_host_actions_f32(const float* a, size_t n, bool bounded) {
 // component finite and within 1000 widths of its dimension's bounds); a DEVICE array cannot be inspected from here and is clamped into that range
 // by k_clamp_states (NaN stays NaN: comparisons with it are false, nothing loops).
 extern "C" __attribute__((visibility("hidden"))) void state_limits(const rsrl_hip_ctx* c, float* lo, float* hi);      // (abi_ctx.hip; internal: hidden visibility)
-static int check_host_states(const rsrl_hip_ctx* c, const float* s, size_t n_cols) {
-    if (!s || is_device_ptr(s)) return RSRL_HIP_OK;
+static int check_host_states(CallFrame& f, const float* s, size_t n_cols) {
+    if (!f.host(s)) return RSRL_HIP_OK;
+    const rsrl_hip_ctx* c = f.c;
     float lo[8], hi[8];
     state_limits(c, lo, hi);
     for (int d = 0; d < c->D; ++d)
@@ -692,7 +721,6 @@ static __global__ void k_check_states(const float* __restrict__ s, int64_t n, in
     }
     if (cnt) atomicAdd(bad, cnt);
 }
-#define TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
 #define KCHECK() HIP_TRY(hipGetLastError())
 
 #define NCCL_TRY(expr)                                                                                   \
