@@ -68,7 +68,8 @@ typedef enum {
  *   v = clip(-0.07, v + 0.0015 a' - 0.0025 cos(3x), 0.07); x = clip(-1.2, x + v, 0.6); terminal iff x >= 0.6; reward 0 on a terminal step, -1
  *   otherwise.  The action set is not enumerable: rsrl_hip_n_actions is 0, rsrl_hip_action_bounds gives (-1, 1), and every action of the ctx is
  *   f32 (the *_f32 entry points below; their int32 twins are ESTATE, as the *_f32 calls are on the other domains).  Supported:
- *   RSRL_ILSTD_ACTOR_CRITIC and RSRL_NAC with policy RSRL_BETA on the Fourier orders 1-5; every other combination is EINVAL at create. */
+ *   RSRL_ILSTD_ACTOR_CRITIC and RSRL_NAC with policy RSRL_BETA, and RSRL_NAC with policy RSRL_GAUSSIAN, on the Fourier orders 1-5; every other
+ *   combination is EINVAL at create. */
 typedef enum { RSRL_MOUNTAIN_CAR = 0, RSRL_CART_POLE = 1, RSRL_ACROBOT = 2, RSRL_HIV_TREATMENT = 3, RSRL_CONTINUOUS_MOUNTAIN_CAR = 4 } rsrl_domain;
 /* lfa::basis::{Fourier (+with_bias), TileCoding}  (re-exported by rsrl/src/fa/linear.rs:11-14) */
 typedef enum { RSRL_FOURIER = 0, RSRL_TILE_CODING = 1 } rsrl_basis;
@@ -265,8 +266,18 @@ typedef enum { RSRL_QLEARNING = 0, RSRL_SARSA = 1, RSRL_EXPECTED_SARSA = 2, RSRL
                 * 1-5, per-learner f32 weights, no epsilon schedule; everything else is EINVAL at create.  The checkpoint is aux_kind 12.
                 * DEPARTURES: f32 for the reference's f64; the score, modes() and map_onto recalled (RSRL_BETA, RSRL_CONTINUOUS_MOUNTAIN_CAR); the
                 * action clamped to [2^-24, 1 - 2^-24] before its logarithms; SARSA's thread_rng() draw is a keyed stream (distribution parity is
-                * the contract); the period is a parameter.  Not built: nac.rs (the Gaussian policy's normal::Grad is not in the reference tree)
-                * and nac_softmax.rs (kernels_nac_beta.hpp) */
+                * the contract); the period is a parameter (kernels_nac_beta.hpp).
+                * With policy RSRL_GAUSSIAN the same algo is the agent and the loop of examples/nac.rs (kernels_nac_gauss.hpp): the critic, the
+                * actor's update (w_m, w_s in w_a's and w_b's place), the value side, the accessors and the ESTATE list are the ones above, with
+                *   psi(s, a) = [ g_mu phi(s) ; g_Sigma sigma(x_s) phi(s) ; phi(s) ]     (g_mu, g_Sigma, x_s, sigma: RSRL_GAUSSIAN's, below)
+                * and ONE difference in the loop: the domain sees the action itself (nac.rs:63), no 2a - 1 -- rsrl_hip_domain_step_f32 with
+                * actions == NULL steps on the pending actions literally, rsrl_hip_rollout_greedy is Domain::rollout(|s| policy.mode(s))
+                * (nac.rs:81).  The inner draw na is the Gaussian sample on BLK_INNER; a caller's action is any finite f32, not clamped.  The
+                * example's constants: lr 0.01, gamma 0.999, alpha 0.01, order 3, P = 100, cap 1 000.  Supported: as above with RSRL_GAUSSIAN in
+                * RSRL_BETA's place.  The checkpoint is aux_kind 14 (aux_kind 12's sections): a Beta NAC file does not load into a Gaussian ctx, nor
+                * the other way round.  DEPARTURES: f32; the score DEFINED (RSRL_GAUSSIAN); the keyed stream; the period a parameter.
+                * Not built: nac_softmax.rs; Gaussian<M, f64> (the fixed-variance policy, policies/gaussian/fixed_var.rs); the Gaussian policy
+                * under RSRL_ILSTD_ACTOR_CRITIC; CACLA; IPP */
                RSRL_NAC = 28,
                /* (29 is no algo.)  GTD2 (prediction/td/gtd2.rs:27-86) and TDC (prediction/td/tdc.rs:41-101): gradient-TD prediction over TWO
                 * ScalarLFAs on one basis, theta (fa_theta / q_func: the value function) and w (fa_w / td_est: the second weight column), per
@@ -313,8 +324,23 @@ typedef enum { RSRL_TRACE_ACCUMULATE = 0, RSRL_TRACE_SATURATE = 1, RSRL_TRACE_DU
  *           rstat::univariate::beta, not pinned by the reference tree);  w_a += e g_a sigma(x_a) phi(s),  w_b += e g_b sigma(x_b) phi(s), sigma =
  *           Softplus's gradient (1 for x >= 10, else the logistic), SGD(1.0) (beta.rs:153-187); both parameters are read before either column
  *           moves.  DEPARTURE: a caller-supplied action is clamped to the sample's interval before its logarithms (the reference would produce
- *           infinities for 0 and 1), in the spirit of the index actions' clamp. */
-typedef enum { RSRL_GREEDY = 0, RSRL_EPSILON_GREEDY = 1, RSRL_SOFTMAX = 2, RSRL_RANDOM = 3, RSRL_BETA = 4 } rsrl_policy;
+ *           infinities for 0 and 1), in the spirit of the index actions' clamp.
+ * (5 is no policy.)  Gaussian (policies/gaussian/{mod,general}.rs), Gaussian<ScalarLFA, Composition<ScalarLFA, Softplus>> with SGD(1.0) on both
+ *   (nac.rs:31-35): the second CONTINUOUS policy, for RSRL_NAC on RSRL_CONTINUOUS_MOUNTAIN_CAR only (EINVAL elsewhere, RSRL_ILSTD_ACTOR_CRITIC
+ *   included, and as agent_policy).  Per learner two weight columns w_m, w_s f32[F] (zero at create; get/set_policy_weights: f32[F][2], column 0 =
+ *   the mean's, column 1 = the stddev's; rsrl_hip_n_policy_outputs = 2).  With x_m = <w_m, phi(s)>, x_s likewise (f32):
+ *   params  mu = x_m, sd = softplus(x_s) + 0.01 (MIN_TOL, mod.rs:37, :67), Sigma = sd * sd (into_cov: mod.rs:82 builds the distribution from the
+ *           VARIANCE).  rsrl_hip_policy_params writes (mu, sd).
+ *   sample  a = fma(sd, z, mu), z = sqrt(-2 ln u1) cos(2 pi u2) from the whole Philox block at block word P + 256 (P: the step's draw, the critic's
+ *           inner draw, the initial sample, an API call), words x and y converted as Beta's (u1 in (0, 1], u2 in [0, 1)): one block, no loop, so
+ *           |z| <= sqrt(48 ln 2) < 5.77.  NOT clamped: the domain clips (map_onto).  A function of (seed, global learner id, t, purpose) only.
+ *   mode    mu (general.rs:177).
+ *   density exp(-(a - mu)^2 / (2 Sigma)) / sqrt(2 pi Sigma) (rsrl_hip_policy_pdf).
+ *   score   g_mu = (a - mu) / Sigma, g_Sigma = ((a - mu)^2 - Sigma) / (2 Sigma^2): the derivatives of the log density in the builder's two
+ *           arguments, the mean and the variance.  DEFINED here: rstat's normal::Grad is not in the reference tree.  grad_log (general.rs:142-157)
+ *           is [ g_mu phi ; g_Sigma sigma(x_s) phi ], literally: the reference does not multiply the second block by d Sigma / d sd = 2 sd.
+ *   A caller-supplied action is any finite f32, taken as it is (NaN or infinity in a host array: EINVAL). */
+typedef enum { RSRL_GREEDY = 0, RSRL_EPSILON_GREEDY = 1, RSRL_SOFTMAX = 2, RSRL_RANDOM = 3, RSRL_BETA = 4, RSRL_GAUSSIAN = 6 } rsrl_policy;
 /* one LFA per learner (independent replicas) or one LFA shared by all learners
  * (synchronous mini-batch rule; N=1 == the reference rule) */
 typedef enum { RSRL_W_PER_ENV = 0, RSRL_W_SHARED = 1 } rsrl_weight_mode;
@@ -471,16 +497,20 @@ int rsrl_hip_get_actions(rsrl_hip_ctx* ctx, int32_t* actions /*[N]*/);
 int rsrl_hip_set_actions(rsrl_hip_ctx* ctx, const int32_t* actions /*[N]*/);
 /* ---- f32 actions: the twins of the int32 calls for a ctx on a continuous domain (RSRL_CONTINUOUS_MOUNTAIN_CAR), with their conventions -- host or
  * device pointers, the same asynchrony, the same meaning of the step counter.  A HOST array of actions is validated (EINVAL unless every value is
- * finite; rsrl_hip_set_actions_f32: inside the action bounds too), a DEVICE array is clamped by the kernels.  On such a ctx the int32 calls --
+ * finite; rsrl_hip_set_actions_f32: inside the action bounds too), a DEVICE array is clamped by the kernels.  (RSRL_GAUSSIAN: an action is any
+ * finite f32 -- a sample is not bounded --, so rsrl_hip_set_actions_f32 checks a host array for finite values only and clamps nothing; a device
+ * array is the caller's.)  On such a ctx the int32 calls --
  * rsrl_hip_get/set_actions, _domain_step, _handle, _policy_sample, _policy_mode -- are ESTATE; on every other ctx the f32 calls are.
  *   rsrl_hip_domain_step_f32      rsrl_hip_domain_step            rsrl_hip_policy_sample_f32   rsrl_hip_policy_sample (states == NULL as there)
  *   rsrl_hip_handle_f32           rsrl_hip_handle                 rsrl_hip_policy_mode_f32     rsrl_hip_policy_mode
  * rsrl_hip_policy_params is beta.rs's pub compute_alpha / compute_beta, rsrl_hip_policy_pdf its Function<(S, A)> (the density, of the action
- * clamped to [2^-24, 1 - 2^-24]); both read-only, state i against learner i's columns.
+ * clamped to [2^-24, 1 - 2^-24]); both read-only, state i against learner i's columns.  With RSRL_GAUSSIAN rsrl_hip_policy_params is
+ * compute_mean / compute_stddev (gaussian/mod.rs:56-68): alpha_out receives mu, beta_out sd; rsrl_hip_policy_pdf is the normal density of the action as given.
  * On an RSRL_NAC ctx (the loop of nac_beta.rs: the domain sees 2a - 1, the agent a) rsrl_hip_domain_step_f32 takes explicit actions literally, as the
  * DOMAIN's, and with actions == NULL applies the loop's 2a - 1 to the ctx's pending actions (the agent's); rsrl_hip_handle_f32 is critic.handle.
+ * With RSRL_GAUSSIAN (the loop of nac.rs) there is no mapping: actions == NULL steps on the pending actions as they are, which the domain clips.
  * rsrl_hip_q_evaluate_f32 is Function<(S, A)>::evaluate of RSRL_NAC's critic, Q(s_i, a_i) = <w_i, psi(s_i, a_i)> against learner i's w and columns
- * (read-only; the action is clamped as above); rsrl_hip_nac_update is NAC::handle(()) (control/nac.rs:47-59) for the learners whose mask byte is
+ * (read-only; the action is clamped as above -- RSRL_GAUSSIAN: taken as it is); rsrl_hip_nac_update is NAC::handle(()) (control/nac.rs:47-59) for the learners whose mask byte is
  * non-zero (mask == NULL: every learner): norm_out, which may be NULL, receives Response.norm, 0 for a learner left out.  Both are ESTATE on
  * every other algo */
 int rsrl_hip_get_actions_f32(rsrl_hip_ctx* ctx, float* actions /*[N]*/);
@@ -669,6 +699,7 @@ int rsrl_hip_lstd_solve(rsrl_hip_ctx* ctx);
  *   11 the Beta iLSTD ActorCritic's state            10          f64 theta, matrices, mu, the policy's columns
  *   12 NAC's critic and the policy's columns         10          weights (3F rows), the policy's columns
  *   13 GTD2 / TDC: theta and the second column w     10          weights, auxiliary matrix
+ *   14 NAC with RSRL_GAUSSIAN: critic and columns    10          weights (3F rows), the policy's columns
  * and a ctx with config.epsilon_decay (aux_kind 0 or 1) writes version 4 instead, with f32 eps[N] behind the payload.  No other pairing of
  * version and aux_kind is a file of this library; load refuses it.  Little-endian, serialised field by field (no padding):
  *   offset  0  char magic[8] = "RSRLHIPW"
@@ -679,7 +710,7 @@ int rsrl_hip_lstd_solve(rsrl_hip_ctx* ctx);
  *                   6 the TD ActorCritic's theta, 7 REINFORCE's theta and open episode, 8 the LSTD agents' f64 state,
  *                   9 the iLSTD ActorCritic's f64 state and theta, 10 LSTD / LSTDLambda's f64 state,
  *                   11 the Beta iLSTD ActorCritic's f64 state and policy columns, 12 NAC's critic and policy columns,
- *                   13 GTD2's / TDC's second weight column)
+ *                   13 GTD2's / TDC's second weight column, 14 the Gaussian NAC's critic and policy columns)
  *                                                                                                                 [11 x i32]
  *          56  i64  n_learners (1 in shared mode)
  *          64  u64  step_count
@@ -704,6 +735,8 @@ int rsrl_hip_lstd_solve(rsrl_hip_ctx* ctx);
  *              sections of its iLSTD critic (mu included), then n_learners x f32[F][2] of the policy's columns (alpha's, beta's);
  *              if aux_kind is 12 (file version 10 too; RSRL_NAC; the header's F is n_features, A = 1): the weights
  *              are the critic's w, n_learners x f32[3F][1], then n_learners x f32[F][2] of the policy's columns;
+ *              if aux_kind is 14 (file version 10 too; RSRL_NAC with RSRL_GAUSSIAN): aux_kind 12's sections, the columns the mean's and the
+ *              stddev's -- the kind alone tells the two policies' files apart, and neither loads into a ctx of the other;
  *              if aux_kind is 13 (file version 10 too; RSRL_GTD2 / RSRL_TDC; A = 1, the weights are theta): n_learners x f32[F][1] of the
  *              second weight column w (fa_w / td_est);
  *              if aux_kind is 3 (file version 3): u32 head[N], u32 len[N], f32 entries[D + 5][n_steps][N] -- every learner's

@@ -7,7 +7,7 @@ import numpy as np
 from . import _abi
 
 MOUNTAIN_CAR, CART_POLE, ACROBOT, HIV_TREATMENT = 0, 1, 2, 3
-CONTINUOUS_MOUNTAIN_CAR = 4                     # mountain_car/continuous.rs: one f32 action in [-1, 1] (Context.continuous; ILSTD_ACTOR_CRITIC with BETA only)
+CONTINUOUS_MOUNTAIN_CAR = 4                     # mountain_car/continuous.rs: one f32 action in [-1, 1] (Context.continuous; ILSTD_ACTOR_CRITIC and NAC with BETA, NAC with GAUSSIAN)
 FOURIER, TILE_CODING = 0, 1
 QLEARNING, SARSA, EXPECTED_SARSA, SARSA_LAMBDA, Q_LAMBDA, PAL, GREEDY_GQ, TD, TD_LAMBDA, Q_SIGMA = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 ACTOR_CRITIC, Q_ACTOR_CRITIC = 10, 11          # ActorCritic (control/ac.rs) with a Gibbs actor and a SARSA critic: a2c.rs's closure / QCritic
@@ -17,11 +17,12 @@ RECURSIVE_LSTD, ILSTD = 18, 19                  # (17 is no algo) prediction/lst
 ILSTD_ACTOR_CRITIC = 21                        # (20 is no algo) ActorCritic::tdac over iLSTD, tdac.rs's agent: lr = iLSTD's alpha, n_steps = its n_updates, alpha = the actor's
 GRADIENT_MC = 23                               # (22 is no algo) prediction/mc.rs: GradientMC (Handler<&Trajectory>: handle_batch; episode_record)
 LSTD, LSTD_LAMBDA = 25, 26                      # (24 is no algo) prediction/lstd: LSTD, LSTDLambda (Handler<&Batch> on whole transitions: handle_transitions; lstd_solve; get/set_lstd_batch_state)
-NAC = 28                                        # (27 is no algo) control/nac.rs with the BETA policy and a SARSA critic over the stable compatible basis on CONTINUOUS_MOUNTAIN_CAR (nac_beta.rs): n_weight_rows = 3 F; q_evaluate_f32; nac_update
+NAC = 28                                        # (27 is no algo) control/nac.rs with the BETA (nac_beta.rs) or the GAUSSIAN policy (nac.rs) and a SARSA critic over the stable compatible basis on CONTINUOUS_MOUNTAIN_CAR: n_weight_rows = 3 F; q_evaluate_f32; nac_update
 GTD2, TDC = 30, 31                              # (29 is no algo) prediction/td: GTD2, TDC -- gradient TD with a second weight column (get/set_td_weights, (F, 1)); lr scales theta's moves, lr_td w's
 TRACE_ACCUMULATE, TRACE_SATURATE, TRACE_DUTCH = 0, 1, 2
 GREEDY, EPSILON_GREEDY, SOFTMAX, RANDOM = 0, 1, 2, 3
 BETA = 4                                        # policies/beta.rs over two Softplus-composed scalar LFAs: ILSTD_ACTOR_CRITIC on CONTINUOUS_MOUNTAIN_CAR
+GAUSSIAN = 6                                    # (5 is no policy) policies/gaussian: the mean a scalar LFA, the stddev a Softplus-composed one: NAC on CONTINUOUS_MOUNTAIN_CAR (nac.rs)
 W_PER_ENV, W_SHARED = 0, 1
 W_F32, W_BF16 = 0, 1
 EXCHANGE_RCCL, EXCHANGE_PEER, EXCHANGE_AUTO = 0, 1, 2
@@ -124,7 +125,7 @@ class Context:
         self.n_out = self._L.rsrl_hip_n_outputs(self._h)      # weight columns: A, or 1 for TD / TDLambda
         self.F = self._L.rsrl_hip_n_features(self._h)
         self.n_weight_rows = self._L.rsrl_hip_n_weight_rows(self._h)      # rows of the weight matrix: F, or NAC's 3 F (SCB::n_features)
-        self.n_policy_out = self._L.rsrl_hip_n_policy_outputs(self._h)      # columns of the policy's own weights: A (Gibbs), 2 (BETA), 0 (the policy reads Q)
+        self.n_policy_out = self._L.rsrl_hip_n_policy_outputs(self._h)      # columns of the policy's own weights: A (Gibbs), 2 (BETA, GAUSSIAN), 0 (the policy reads Q)
         self._policy_cols = self.n_policy_out or self.A                     # (the accessors' array shape; an agent without policy weights is refused by the library)
         self._td_cols = 1 if algo in (GTD2, TDC) else self.A                # (get/set_td_weights' array shape: GreedyGQ's fa_td has A columns)
         self.continuous = domain == CONTINUOUS_MOUNTAIN_CAR                 # actions are f32 values (the *_f32 entry points), not int32 indices
@@ -373,14 +374,15 @@ class Context:
         return out
 
     def policy_params(self, states):
-        """BETA's pub compute_alpha / compute_beta -> (alpha (M,), beta (M,)): state i against learner i's columns"""
+        """BETA's pub compute_alpha / compute_beta -> (alpha (M,), beta (M,)), GAUSSIAN's compute_mean / compute_stddev -> (mu (M,), sd (M,)):
+        state i against learner i's columns"""
         states, M = self._batch(states)
         a, b = np.empty(M, dtype=np.float32), np.empty(M, dtype=np.float32)
         _abi.check(self._L.rsrl_hip_policy_params(self._h, _p(states), M, _p(a), _p(b)))
         return a, b
 
     def policy_pdf(self, states, actions):
-        """BETA's Function<(S, A)>: the density of actions (M,) f32, each clamped to [2^-24, 1 - 2^-24]"""
+        """BETA's Function<(S, A)>: the density of actions (M,) f32, each clamped to [2^-24, 1 - 2^-24]; GAUSSIAN's: of the actions as given"""
         states, M = self._batch(states)
         out = np.empty(M, dtype=np.float32)
         _abi.check(self._L.rsrl_hip_policy_pdf(self._h, _p(states), _p(_in(actions, np.float32, (M,))), M, _p(out)))

@@ -47,7 +47,7 @@ static AgentFamily classify(const rsrl_hip_config& cfg, size_t w_elems) {
     if (is_tdac_lstd(al)) return cfg.domain == RSRL_CONTINUOUS_MOUNTAIN_CAR ? F::TdAcBetaReg : F::TdAcLstdReg;
     if (is_gmc(al)) return F::GmcReg;
     if (is_lstd_batch(al)) return F::LstdBatchReg;
-    if (is_nac(al)) return F::NacBetaReg;
+    if (is_nac(al)) return cfg.policy == RSRL_GAUSSIAN ? F::NacGaussReg : F::NacBetaReg;
     if (is_gtd(al)) return F::GtdReg;
     if (cfg.weight_mode == RSRL_W_SHARED) return fourier ? F::SharedDense : (is_sparse_lambda(cfg) ? F::SharedSparseLambda : F::SharedTile);
     if (wave && is_wave_aux_algo(al)) return F::WaveAux;
@@ -167,19 +167,21 @@ static int check_reg_only(const rsrl_hip_config& cfg, const AlgoRow& a, bool sto
 // (state dimension, action count) of MountainCar, CartPole, Acrobot, HIVTreatment, ContinuousMountainCar (0: the action set is not enumerable)
 static const int kDomainShape[5][2] = {{2, 3}, {4, 2}, {4, 3}, {6, 4}, {2, 0}};
 
-// ContinuousMountainCar and the Beta policy (train_tdac_beta.hip, train_nac_beta.hip): each exists for the other only, under the iLSTD ActorCritic
-// and NAC -- and NAC for them only
+// ContinuousMountainCar and the continuous policies (train_tdac_beta.hip, train_nac_beta.hip, train_nac_gauss.hip): the domain exists for them only and
+// they for it, Beta under the iLSTD ActorCritic and NAC, Gaussian under NAC -- and NAC for them only
 static int check_continuous(const rsrl_hip_config& cfg, const AlgoRow& a, bool storage) {
     const bool nac = cfg.algo == RSRL_NAC;
-    if (cfg.domain != RSRL_CONTINUOUS_MOUNTAIN_CAR || cfg.policy != RSRL_BETA || (cfg.algo != RSRL_ILSTD_ACTOR_CRITIC && !nac) || !storage || cfg.agent_policy != -1)
-        return fail(RSRL_HIP_EINVAL, "ContinuousMountainCar (RSRL_CONTINUOUS_MOUNTAIN_CAR), the Beta policy (RSRL_BETA) and NAC (RSRL_NAC) support the iLSTD "
-                                     "ActorCritic (RSRL_ILSTD_ACTOR_CRITIC) and NAC with policy = Beta on ContinuousMountainCar, Fourier orders 1-5, per-learner f32 "
-                                     "weights, agent_policy = -1 and no epsilon schedule -- and nothing else (got domain %d, basis %d, order %d, algo %d, weight "
+    const bool pair = (cfg.policy == RSRL_BETA && (cfg.algo == RSRL_ILSTD_ACTOR_CRITIC || nac)) || (cfg.policy == RSRL_GAUSSIAN && nac);
+    if (cfg.domain != RSRL_CONTINUOUS_MOUNTAIN_CAR || !pair || !storage || cfg.agent_policy != -1)
+        return fail(RSRL_HIP_EINVAL, "ContinuousMountainCar (RSRL_CONTINUOUS_MOUNTAIN_CAR), the Beta policy (RSRL_BETA), the Gaussian policy (RSRL_GAUSSIAN) and "
+                                     "NAC (RSRL_NAC) support the iLSTD ActorCritic (RSRL_ILSTD_ACTOR_CRITIC) with policy = Beta and NAC with policy = Beta or "
+                                     "Gaussian on ContinuousMountainCar, Fourier orders 1-5, per-learner f32 weights, agent_policy = -1 and no epsilon schedule "
+                                     "-- and nothing else (got domain %d, basis %d, order %d, algo %d, weight "
                                      "mode %d, dtype %d, policy %d, agent_policy %d, epsilon_decay %g)",
                     cfg.domain, cfg.basis, cfg.order, cfg.algo, cfg.weight_mode, cfg.weight_dtype, cfg.policy, cfg.agent_policy, cfg.epsilon_decay);
     if (nac) {
         if (cfg.n_steps < 1 || cfg.n_steps > 65536)
-            return fail(RSRL_HIP_EINVAL, "%s: n_steps (the actor's period: NAC::handle(()) runs at every n_steps-th step of an episode, 100 in nac_beta.rs) must be "
+            return fail(RSRL_HIP_EINVAL, "%s: n_steps (the actor's period: NAC::handle(()) runs at every n_steps-th step of an episode, 100 in nac_beta.rs and nac.rs) must be "
                                          "in [1, 65536], got %d", a.name, cfg.n_steps);
         return RSRL_HIP_OK;
     }
@@ -198,7 +200,7 @@ static int check_config(const rsrl_hip_config& cfg) {
     if (cfg.n_envs < 1) return fail(RSRL_HIP_EINVAL, "n_envs must be >= 1");
     if (cfg.n_envs + cfg.env_offset > (int64_t)0xffffffffLL || cfg.env_offset < 0) return fail(RSRL_HIP_EINVAL, "global env ids must fit 32 bits");
     if (cfg.algo < 0 || cfg.algo > RSRL_TDC || !kAlgo[cfg.algo].name) return fail(RSRL_HIP_EINVAL, "unknown algo %d", cfg.algo);
-    if (cfg.policy < 0 || cfg.policy > RSRL_BETA) return fail(RSRL_HIP_EINVAL, "unknown policy %d", cfg.policy);
+    if (cfg.policy < 0 || (cfg.policy > RSRL_BETA && cfg.policy != RSRL_GAUSSIAN)) return fail(RSRL_HIP_EINVAL, "unknown policy %d", cfg.policy);      // (5 is no policy)
     // Softmax::new panics for |tau| < 1e-7 (policies/softmax.rs:63-66)
     if (cfg.policy == RSRL_SOFTMAX && std::fabs(cfg.tau) < 1e-7) return fail(RSRL_HIP_EINVAL, "Tau parameter in Softmax must be non-zero.");
     // the reference admits any non-zero tau; the kernels evaluate the max-shifted form exp((q - max q) / tau), whose exponents are >= 0 for tau < 0
@@ -239,7 +241,7 @@ static int check_config(const rsrl_hip_config& cfg) {
     const bool tile = cfg.basis == RSRL_TILE_CODING, reg = is_reg_fourier(cfg), wave = is_wave(cfg);
     const bool f32 = cfg.weight_dtype == RSRL_W_F32, esched = cfg.epsilon_decay != 1.0;
     const bool one_step = kAlgo[al].agent == Agent::OneStep;
-    if (cfg.domain == RSRL_CONTINUOUS_MOUNTAIN_CAR || cfg.policy == RSRL_BETA || al == RSRL_NAC)
+    if (cfg.domain == RSRL_CONTINUOUS_MOUNTAIN_CAR || cfg.policy == RSRL_BETA || cfg.policy == RSRL_GAUSSIAN || al == RSRL_NAC)
         return check_continuous(cfg, kAlgo[al], is_cmc_fourier(cfg) && per_env && f32 && !esched);
     if (kAlgo[al].reg_policy >= 0) return check_reg_only(cfg, kAlgo[al], reg && per_env && f32 && !esched);
     if (cfg.domain == RSRL_HIV_TREATMENT) {
@@ -301,7 +303,7 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
     c->w_stride = shared ? 1 : N;
     const AlgoRow& agent = kAlgo[cfg->algo];
     c->Aw = agent.v ? 1 : c->A;
-    c->Ap = cfg->policy == RSRL_BETA ? 2 : (agent.reg_policy == RSRL_SOFTMAX ? c->A : 0);
+    c->Ap = (cfg->policy == RSRL_BETA || cfg->policy == RSRL_GAUSSIAN) ? 2 : (agent.reg_policy == RSRL_SOFTMAX ? c->A : 0);
     c->Fw = is_nac(cfg->algo) ? 3 * c->F : c->F;      // (SCB::n_features: the score's two blocks and the basis itself)
     c->w_elems = (size_t)c->Aw * c->Fw * (size_t)(shared ? 1 : N);
     c->family = classify(*cfg, c->w_elems);
@@ -540,7 +542,9 @@ int rsrl_hip_reset(rsrl_hip_ctx* c) {
     if (c->family == AgentFamily::ReinforceReg) { launch_reinforce_restart(c->stream, make_reinforce(c), c->cfg.n_envs, (int64_t)c->F * c->A, nullptr); KCHECK(); }
     const Common k = make_policy_common(c);              // the initial policy.sample (ActorCritic: the actor's theta)
     const BasisGeom g = make_geom(c);
-    if (c->family == AgentFamily::TdAcBetaReg || c->family == AgentFamily::NacBetaReg) {      // (both agents' state is untouched: the initial sample reads the policy's columns)
+    if (c->family == AgentFamily::NacGaussReg) {      // (as the two below)
+        if (!launch_gauss_reset(c->cfg.order, c->stream, k, c->Z, c->t, c->action_f)) return NO_MODEL(c);
+    } else if (c->family == AgentFamily::TdAcBetaReg || c->family == AgentFamily::NacBetaReg) {      // (both agents' state is untouched: the initial sample reads the policy's columns)
         if (!launch_beta_reset(c->cfg.order, c->stream, k, c->Z, c->t, c->action_f)) return NO_MODEL(c);
     } else if (c->family == AgentFamily::Hiv) {
         launch_hiv_reset(c->stream, k, g, c->hiv_y, c->t);
@@ -644,10 +648,9 @@ int rsrl_hip_set_actions_f32(rsrl_hip_ctx* c, const float* actions) {
     NEEDS_F32_ACTIONS(c, "rsrl_hip_set_actions");
     HIP_TRY(hipSetDevice(c->cfg.device));
     CallFrame f(c);
-    TRY(check_host_actions_f32(f, actions, (size_t)c->cfg.n_envs, true));
+    TRY(check_host_actions_f32(f, actions, (size_t)c->cfg.n_envs, !is_gaussian(c)));      // (a Gaussian sample is any finite f32)
     HIP_TRY(hipMemcpyAsync(c->action_f, actions, sizeof(float) * (size_t)c->cfg.n_envs, hipMemcpyDefault, c->stream));
-    launch_cmc_clamp_actions(c->stream, c->action_f, c->cfg.n_envs);
-    KCHECK();
+    if (!is_gaussian(c)) { launch_cmc_clamp_actions(c->stream, c->action_f, c->cfg.n_envs); KCHECK(); }
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RSRL_HIP_OK;
 }

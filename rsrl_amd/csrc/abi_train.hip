@@ -432,6 +432,9 @@ int launch_agent(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, uint64_t 
     case AgentFamily::NacBetaReg:        // (io: as above)
         ok = !io && launch_nac_beta(cf.order, c->stream, k, make_nac_beta(c), t, chunk, d_stats, nullptr);
         break;
+    case AgentFamily::NacGaussReg:       // (io: as above)
+        ok = !io && launch_nac_gauss(cf.order, c->stream, k, make_nac_beta(c), t, chunk, d_stats, nullptr);
+        break;
     case AgentFamily::GtdReg: ok = launch_gtd(cf.domain, cf.order, cf.algo == RSRL_TDC, grid, block, c->stream, k, make_gtd(c), t, chunk, d_stats, io); break;
     default: ok = false; break;      // (the shared-W families: enqueue_shared_step)
     }
@@ -602,7 +605,9 @@ static int rollout_impl(rsrl_hip_ctx* c, int64_t step_limit, int64_t M, uint32_t
         TRY(f.out(n_states_out, (size_t)M, &d_n));
         TRY(f.out(total_reward_out, (size_t)M, &d_total));
         // (NAC: the loop's mapping, Domain::rollout(|s| 2 * policy.mode(s) - 1), nac_beta.rs:81-82)
-        if (!(is_nac(c->cfg.algo) ? launch_nac_rollout_mode(c->cfg.order, c->stream, make_common(c), c->Z, step_limit, d_n, d_total)
+        // (the Gaussian policy: Domain::rollout(|s| policy.mode(s)), nac.rs:81 -- no mapping)
+        if (!(is_gaussian(c)      ? launch_gauss_rollout_mode(c->cfg.order, c->stream, make_common(c), c->Z, step_limit, d_n, d_total)
+              : is_nac(c->cfg.algo) ? launch_nac_rollout_mode(c->cfg.order, c->stream, make_common(c), c->Z, step_limit, d_n, d_total)
                                   : launch_beta_rollout_mode(c->cfg.order, c->stream, make_common(c), c->Z, step_limit, d_n, d_total))) return NO_MODEL(c);
         KCHECK();
         return f.finish();

@@ -437,8 +437,8 @@ int rsrl_hip_domain_step_f32(rsrl_hip_ctx* c, const float* actions, float* from_
     StepArrays<float> s;
     TRY(stage_step(f, actions, from_states, next_states, rewards, terminal, &s));
     const Common k = make_common(c);
-    // (NAC: explicit actions are the domain's, the pending ones the agent's -- stepped on through the loop's 2a - 1)
-    if (is_nac(c->cfg.algo)) launch_nac_domain_step(c->stream, k, s.act, c->action_f, s.from, s.next, s.rew, s.term);
+    // (NAC with Beta: explicit actions are the domain's, the pending ones the agent's -- stepped on through the loop's 2a - 1; nac.rs's loop maps nothing)
+    if (is_nac(c->cfg.algo) && !is_gaussian(c)) launch_nac_domain_step(c->stream, k, s.act, c->action_f, s.from, s.next, s.rew, s.term);
     else launch_cmc_domain_step(c->stream, k, s.act, c->action_f, s.from, s.next, s.rew, s.term);
     KCHECK();
     return f.finish();
@@ -453,11 +453,12 @@ int rsrl_hip_handle_f32(rsrl_hip_ctx* c, const float* from_states, const float* 
     FLUSH(c);
     HIP_TRY(hipSetDevice(c->cfg.device));
     CallFrame f(c);
-    TRY(check_host_actions_f32(f, actions, (size_t)M, false));      // (the update clamps the action to the sample's interval)
+    TRY(check_host_actions_f32(f, actions, (size_t)M, false));      // (the update clamps the action to the sample's interval; Gaussian: taken as it is)
     TransitionsF32 io;
     TRY(stage_transitions(f, from_states, actions, rewards, to_states, terminal, M, td_error_out, &io));
     const Common k = make_common(c);
-    if (!(is_nac(c->cfg.algo) ? launch_nac_beta(c->cfg.order, c->stream, k, make_nac_beta(c), c->t, 1, nullptr, &io)      // critic.handle: SARSA over SCB
+    if (!(is_gaussian(c)      ? launch_nac_gauss(c->cfg.order, c->stream, k, make_nac_beta(c), c->t, 1, nullptr, &io)     // critic.handle: SARSA over SCB
+          : is_nac(c->cfg.algo) ? launch_nac_beta(c->cfg.order, c->stream, k, make_nac_beta(c), c->t, 1, nullptr, &io)
                               : launch_tdac_beta(c->cfg.order, c->stream, k, make_tdac_beta(c), c->t, 1, nullptr, &io))) return NO_MODEL(c);
     KCHECK();
     c->q_valid = false;
@@ -465,7 +466,7 @@ int rsrl_hip_handle_f32(rsrl_hip_ctx* c, const float* from_states, const float* 
     return f.finish();
 }
 
-// the policy side on explicit states (or, for the sample, the ctx's own envs): one launch of k_beta_policy
+// the policy side on explicit states (or, for the sample, the ctx's own envs): one launch of k_beta_policy, or of k_gauss_policy
 static int beta_op(rsrl_hip_ctx* c, int op, const float* states, int64_t M, uint64_t t, uint32_t purpose, const float* act_in, float* out0, float* out1, float* keep) {
     CallFrame f(c);
     TRY(check_host_actions_f32(f, act_in, (size_t)M, false));      // (rsrl_hip_policy_pdf's actions, the one caller with any)
@@ -476,7 +477,8 @@ static int beta_op(rsrl_hip_ctx* c, int op, const float* states, int64_t M, uint
     TRY(f.out(out0, (size_t)M, &d_out0));
     TRY(f.out(out1, (size_t)M, &d_out1));
     const Common k = make_common(c);
-    if (!launch_beta_policy(c->cfg.order, c->stream, k, c->Z, op, d_states, M, t, purpose, d_act, d_out0, d_out1, keep)) return NO_MODEL(c);
+    if (!(is_gaussian(c) ? launch_gauss_policy(c->cfg.order, c->stream, k, c->Z, op, d_states, M, t, purpose, d_act, d_out0, d_out1, keep)
+                         : launch_beta_policy(c->cfg.order, c->stream, k, c->Z, op, d_states, M, t, purpose, d_act, d_out0, d_out1, keep))) return NO_MODEL(c);
     KCHECK();
     return f.finish();
 }
@@ -506,7 +508,8 @@ int rsrl_hip_policy_mode_f32(rsrl_hip_ctx* c, const float* states, int64_t M, fl
     TRY(beta_batch(c, states, M));
     return beta_op(c, BETA_OP_MODE, states, M, 0, 0, nullptr, actions_out, nullptr, nullptr);
 }
-static const char* const kNoBetaPolicy = "only the Beta policy (RSRL_BETA, on ContinuousMountainCar) has shape parameters and a density";
+static const char* const kNoBetaPolicy = "only the Beta policy (RSRL_BETA, on ContinuousMountainCar) has shape parameters and a density (and the Gaussian policy, "
+                                         "RSRL_GAUSSIAN, a mean, a standard deviation and a density)";
 int rsrl_hip_policy_params(rsrl_hip_ctx* c, const float* states, int64_t M, float* alpha_out, float* beta_out) {
     CHECK_CTX(c);
     if (!alpha_out || !beta_out) return fail(RSRL_HIP_EINVAL, "null argument");
@@ -533,13 +536,14 @@ int rsrl_hip_q_evaluate_f32(rsrl_hip_ctx* c, const float* states, const float* a
     FLUSH(c);
     TRY(beta_batch(c, states, M));
     CallFrame f(c);
-    TRY(check_host_actions_f32(f, actions, (size_t)M, false));      // (the score clamps the action to the sample's interval)
+    TRY(check_host_actions_f32(f, actions, (size_t)M, false));      // (the score clamps the action to the sample's interval; Gaussian: taken as it is)
     HIP_TRY(hipSetDevice(c->cfg.device));
     const float* d_states; const float* d_act; float* d_q;
     TRY(f.in(states, (size_t)c->D * M, &d_states));
     TRY(f.in(actions, (size_t)M, &d_act));
     TRY(f.out(q_out, (size_t)M, &d_q));
-    if (!launch_nac_q(c->cfg.order, c->stream, make_common(c), make_nac_beta(c), d_states, d_act, M, d_q)) return NO_MODEL(c);
+    if (!(is_gaussian(c) ? launch_nac_gauss_q(c->cfg.order, c->stream, make_common(c), make_nac_beta(c), d_states, d_act, M, d_q)
+                         : launch_nac_q(c->cfg.order, c->stream, make_common(c), make_nac_beta(c), d_states, d_act, M, d_q))) return NO_MODEL(c);
     KCHECK();
     return f.finish();
 }
@@ -553,6 +557,7 @@ int rsrl_hip_nac_update(rsrl_hip_ctx* c, const uint8_t* mask, float* norm_out) {
     const uint8_t* d_mask; float* d_norm;
     TRY(f.in(mask, N, &d_mask));
     TRY(f.out(norm_out, N, &d_norm));
+    // (k_nac_update reads w's first 2F rows and the two columns, whatever the policy: the Gaussian ctx runs it too)
     if (!launch_nac_update(c->cfg.order, c->stream, make_common(c), make_nac_beta(c), d_mask, d_norm)) return NO_MODEL(c);
     KCHECK();
     c->q_valid = false;

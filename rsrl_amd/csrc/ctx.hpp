@@ -97,7 +97,8 @@ constexpr AlgoRow kAlgo[RSRL_TDC + 1] = {
     /* 25 */ {"LSTD (RSRL_LSTD)", Agent::LstdBatch, true, Aux::None, 10, false, true, RSRL_RANDOM},
     /* 26 */ {"LSTDLambda (RSRL_LSTD_LAMBDA)", Agent::LstdBatch, true, Aux::None, 10, false, true, RSRL_RANDOM},
     /* 27 */ {},
-    // (W is the SCB critic's one column of 3F rows -- weight_rows() --, the Beta policy's two columns in Z; admitted by check_continuous, not check_reg_only)
+    // (W is the SCB critic's one column of 3F rows -- weight_rows() --, the Beta or the Gaussian policy's two columns in Z; admitted by check_continuous, not
+    // check_reg_only; aux_kind 12 with Beta, 14 with Gaussian: aux_kind_of)
     /* 28 */ {"NAC (RSRL_NAC)", Agent::Nac, true, Aux::Policy, 12},
     /* 29 */ {},
     // (the gradient-TD agents: W is theta's one column, TD's layout; Z is the second column w -- fa_w / td_est --, [F][1])
@@ -208,8 +209,10 @@ enum class AgentFamily : uint8_t {
     NacBetaReg,           // NAC with the Beta policy and the SCB SARSA critic on ContinuousMountainCar, Fourier orders 1-5: k_train_nac_beta (train_nac_beta.hip),
                           // one thread per learner; the critic's w in W (3F rows, one column), the policy's two columns in Z, f32 actions in action_f
     GtdReg,               // GTD2 / TDC, same configurations as LstdReg: k_train_gtd (train_gtd.hip); theta in W (one column), the second column w in Z
+    NacGaussReg,          // NAC with the Gaussian policy, NacBetaReg's configurations and layout: k_train_nac_gauss (train_nac_gauss.hip); the policy's columns
+                          // (the mean's, the stddev's) in Z
 };
-constexpr size_t kAgentFamilies = (size_t)AgentFamily::GtdReg + 1;      // (the enum's last value)
+constexpr size_t kAgentFamilies = (size_t)AgentFamily::NacGaussReg + 1;      // (the enum's last value)
 // ---- THE family table: which kernels serve a family and what they can do, one row per AgentFamily value in the enum's order.  classify() (abi_ctx.hip: a
 // decision) and launch_agent (abi_train.hip: it instantiates the templates) are the two other places a new family is entered.
 enum class Slots : uint8_t { Block, Block64, WaveBlock, Learner, LstdGroup };      // a statistics slot per: kBlock learners, 64 learners (k_train_lambda_mem4; the
@@ -266,6 +269,7 @@ constexpr FamilyRow kFamily[] = {
     {AgentFamily::TdAcBetaReg, "k_train_tdac_beta", 32, Slots::LstdGroup, Handle::Agent, kPolicyW | kVCritic | kLstd},      // (handle: rsrl_hip_handle_f32)
     {AgentFamily::NacBetaReg, "k_train_nac_beta", 256, Slots::Block, Handle::Agent, kPolicyW},      // (handle: rsrl_hip_handle_f32; a step is a long scalar chain: 256 as the memory-resident loops)
     {AgentFamily::GtdReg, "k_train_gtd", 4096, Slots::Block, Handle::Agent, 0},      // (4 096: TdReg's depth, taken over and not measured)
+    {AgentFamily::NacGaussReg, "k_train_nac_gauss", 256, Slots::Block, Handle::Agent, kPolicyW},      // (handle: rsrl_hip_handle_f32; NacBetaReg's depth, taken over)
 };
 constexpr bool family_rows_in_order() {
     for (size_t i = 0; i < sizeof(kFamily) / sizeof(kFamily[0]); ++i) if ((size_t)kFamily[i].family != i) return false;
@@ -439,6 +443,8 @@ static inline bool is_v_actor_critic(const rsrl_hip_ctx* c) { return family_row(
 static inline int aux_cols(const rsrl_hip_ctx* c) { return kAlgo[c->cfg.algo].aux == Aux::Policy ? c->Ap : c->Aw; }
 // a ctx whose actions are f32 values, not indices (ContinuousMountainCar): the *_f32 entry points are its own, their int32 twins ESTATE
 static inline bool is_continuous(const rsrl_hip_ctx* c) { return c->cfg.domain == RSRL_CONTINUOUS_MOUNTAIN_CAR; }
+// the continuous ctx's policy is the Gaussian (kernels_gaussian.hpp), not Beta: its own kernels, actions any finite f32, no 2a - 1 in NAC's loop
+static inline bool is_gaussian(const rsrl_hip_ctx* c) { return c->cfg.policy == RSRL_GAUSSIAN; }
 #define NEEDS_INDEX_ACTIONS(c, call) do { if (is_continuous(c)) return fail(RSRL_HIP_ESTATE, "%s carries int32 action indices: this ctx's domain " \
     "(ContinuousMountainCar) has one f32 action -- use %s_f32", call, call); } while (0)
 #define NEEDS_F32_ACTIONS(c, call) do { if (!is_continuous(c)) return fail(RSRL_HIP_ESTATE, "%s_f32 carries f32 actions: this ctx's domain has a finite " \

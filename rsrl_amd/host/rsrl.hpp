@@ -4,6 +4,7 @@
 //
 //   rsrl::domains::{MountainCar, CartPole, Acrobot}      rsrl_domains/src/{mountain_car/discrete,cart_pole,acrobot}.rs
 //   rsrl::domains::ContinuousMountainCar, rsrl::policies::Beta      rsrl_domains/src/mountain_car/continuous.rs, rsrl/src/policies/beta.rs
+//   rsrl::policies::Gaussian                                        rsrl/src/policies/gaussian/{mod,general}.rs
 //   rsrl::fa::linear::{basis::Fourier, optim::SGD, LFA}  rsrl/src/fa/linear.rs (re-exports of crate lfa)
 //   rsrl::policies::{Greedy, EpsilonGreedy, Softmax, Random}   rsrl/src/policies/*.rs
 //   rsrl::control::td::{QLearning, SARSA, ExpectedSARSA, PAL, SARSALambda, QLambda, GreedyGQ, QSigma}   rsrl/src/control/td/*.rs
@@ -84,7 +85,7 @@ struct Fourier {                          // Fourier::from_space(order, space).w
     Fourier with_bias() const { Fourier f = *this; f.bias = true; return f; }
 };
 struct TileCoding { int n_tilings, tiles_per_dim; };
-struct SCB;                               // (below policies::Beta, which it holds)
+struct SCB;                               // (below namespace policies: it holds one)
 }  // namespace basis
 namespace optim { struct SGD { double lr; explicit SGD(double l) : lr(l) {} }; }
 struct LFA {                              // LFA::vector(basis, SGD(lr), n_actions)  (q_learning.rs:25)
@@ -140,13 +141,22 @@ struct Beta : Policy {
     explicit Beta(const fa::linear::basis::Fourier& basis)
         : Policy{RSRL_BETA}, q(make_shared(fa::linear::LFA::vector(basis, fa::linear::optim::SGD(1.0), 1))) {}
 };
+// Gaussian::new(mean, stddev) (policies/gaussian/mod.rs) with mean = ScalarLFA and stddev = Composition<ScalarLFA, Softplus> over the basis, SGD(1.0)
+// on both, zero weights: the policy of examples/nac.rs on ContinuousMountainCar.  Its two weight columns (the mean's, the stddev's) are read through
+// Session::policy_weights ([F][2]); Session::policy_params gives (mu, sd)
+struct Gaussian : Policy {
+    Shared<fa::linear::LFA> q;
+    explicit Gaussian(const fa::linear::basis::Fourier& basis)
+        : Policy{RSRL_GAUSSIAN}, q(make_shared(fa::linear::LFA::vector(basis, fa::linear::optim::SGD(1.0), 1))) {}
+};
 }  // namespace policies
 
 // SCB { policy, basis } (fa/linear.rs:79-103), the stable compatible basis: project((s, a)) = grad_log pi(a|s) chained with basis.project(s), 3F
-// features over policies::Beta.  LFA::scalar(SCB, SGD(lr)) is the q_func of NAC's SARSA critic (examples/nac_beta.rs)
+// features over policies::Beta or policies::Gaussian (held as the Policy they are: its kind is all the descriptor reads).  LFA::scalar(SCB, SGD(lr))
+// is the q_func of NAC's SARSA critic (examples/nac_beta.rs, examples/nac.rs)
 namespace fa { namespace linear {
 namespace basis {
-struct SCB { policies::Beta policy; Fourier basis; };
+struct SCB { policies::Policy policy; Fourier basis; };
 }  // namespace basis
 inline LFA LFA::scalar(const basis::SCB& b, optim::SGD o) { return LFA::vector(b.basis, o, 1); }
 }}  // namespace fa::linear
@@ -244,13 +254,16 @@ struct ActorCritic : td::Agent {
 };
 }}  // namespace control::ac
 
-// ---- rsrl::control::nac: NAC::new(critic, policy, alpha) (control/nac.rs) with policies::Beta and a SARSA critic over fa::linear::basis::SCB on
-// domains::ContinuousMountainCar, the agent of examples/nac_beta.rs.  critic: its q_func (the SGD rate) and gamma; it shares the policy, as the
+// ---- rsrl::control::nac: NAC::new(critic, policy, alpha) (control/nac.rs) with policies::Beta or policies::Gaussian and a SARSA critic over
+// fa::linear::basis::SCB on domains::ContinuousMountainCar, the agents of examples/nac_beta.rs and examples/nac.rs (whose loop hands the domain the
+// action itself: Session::train and rollout_total_reward follow the policy's kind).  critic: its q_func (the SGD rate) and gamma; it shares the policy, as the
 // example does.  `period`: the loop runs agent.handle(()) at every period-th step of an episode (nac_beta.rs:69 hard-codes 100).  The Session's
 // weights are the critic's w [3F][1]; Session::handle(TransitionF32) is critic.handle, Session::nac_update() agent.handle(())
 namespace control { namespace nac {
 struct NAC : td::Agent {
     NAC(const td::SARSA& critic, const policies::Beta& /*policy*/, double alpha_, int period = 100)
+        : td::Agent{RSRL_NAC, critic.q_func, critic.gamma, alpha_} { n_steps = period; }
+    NAC(const td::SARSA& critic, const policies::Gaussian& /*policy*/, double alpha_, int period = 100)
         : td::Agent{RSRL_NAC, critic.q_func, critic.gamma, alpha_} { n_steps = period; }
 };
 }}  // namespace control::nac
@@ -421,7 +434,7 @@ public:
     std::vector<float> q_evaluate(const std::vector<float>& states, const std::vector<float>& actions) {
         std::vector<float> q(N_); check(rsrl_hip_q_evaluate_f32(ctx_, states.data(), actions.data(), N_, q.data())); return q;
     }
-    // Domain::rollout(|s| policy.mode(s), Some(limit)).total_reward() for every learner (NAC: the loop's |s| 2 * policy.mode(s) - 1)
+    // Domain::rollout(|s| policy.mode(s), Some(limit)).total_reward() for every learner (NAC with Beta: the loop's |s| 2 * policy.mode(s) - 1)
     std::vector<float> rollout_total_reward(int64_t step_limit) {
         std::vector<uint32_t> n(N_); std::vector<float> tot(N_); check(rsrl_hip_rollout_greedy(ctx_, step_limit, n.data(), tot.data())); return tot;
     }

@@ -8,7 +8,9 @@ fixture of its own; and GRID_BETA, the continuous axis: MountainCar and Continuo
 (tests/test_tdac_beta_cpu.py); and GRID_NAC: ContinuousMountainCar / MountainCar x Softmax / Random / Beta x the algos 21, the unassigned 27 and NAC
 (28) x agent_policy -1 / Beta x the Fourier orders 0-6 x n_steps (NAC's period) 0, 1, 100, 65 536, 65 537 (1 260 configurations) ->
 create_admission_nac.json (tests/test_nac_beta_cpu.py); and GRID_GTD: GRID's axes with the algos 29 (unassigned), GTD2 (30), TDC (31) and 32 (past
-the last) and an lr_td axis 0 / -1 (81 920 configurations) -> create_admission_gtd.json (tests/test_gtd_cpu.py).
+the last) and an lr_td axis 0 / -1 (81 920 configurations) -> create_admission_gtd.json (tests/test_gtd_cpu.py); and GRID_GAUSS: the policies Beta (4),
+the unassigned 5, Gaussian (6) and 7 (past the last) x the iLSTD ActorCritic (21) and NAC (28) x MountainCar / ContinuousMountainCar x agent_policy
+-1 / Gaussian x the Fourier orders 0-6 x GRID_NAC's n_steps (1 120 configurations) -> create_admission_gauss.json (tests/test_nac_gaussian_cpu.py).
     python scripts/admission_matrix.py            writes tests/golden/create_admission.json, create_admission_agents.json,
                                                   create_admission_agents2.json and create_admission_agents3.json
                                                   (tests/test_create_admission_cpu.py, tests/test_tdac_lstd_cpu.py and tests/test_gmc_cpu.py
@@ -30,6 +32,7 @@ AGENTS3_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_agents
 BETA_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_beta.json")
 NAC_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_nac.json")
 GTD_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_gtd.json")
+GAUSS_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_gauss.json")
 EINVAL, EHIP = -1, -2
 
 # (config field, values): the first axis varies slowest
@@ -78,9 +81,19 @@ GRID_NAC = [
 ]
 # GTD2 (30) and TDC (31) between the unassigned 29 and 32, on GRID's other axes, with the second column's rate: 0 and a negative one
 GRID_GTD = [(name, [29, 30, 31, 32] if name == "algo" else vals) for name, vals in GRID] + [("lr_td", [0.0, -1.0])]
+# the Gaussian policy (6) between Beta, the unassigned 5 and 7: under NAC, its one agent, and under the iLSTD ActorCritic, which has Beta only
+GRID_GAUSS = [
+    ("policy", [4, 5, 6, 7]),                # 5, 7: no such policy
+    ("algo", [21, 28]),
+    ("domain", [0, 4]),
+    ("agent_policy", [-1, 6]),
+    ("order", [0, 1, 2, 3, 4, 5, 6]),
+    ("n_steps", [0, 1, 100, 65536, 65537]),
+]
 # (grid, fixture, fields set on every configuration)
 GRIDS = ((GRID, FIXTURE, {}), (GRID_AGENTS, AGENTS_FIXTURE, {}), (GRID_AGENTS2, AGENTS2_FIXTURE, {}), (GRID_AGENTS3, AGENTS3_FIXTURE, FIXED_AGENTS3),
-         (GRID_BETA, BETA_FIXTURE, {}), (GRID_NAC, NAC_FIXTURE, {}), (GRID_GTD, GTD_FIXTURE, {}))
+         (GRID_BETA, BETA_FIXTURE, {}), (GRID_NAC, NAC_FIXTURE, {}), (GRID_GTD, GTD_FIXTURE, {}),
+         (GRID_GAUSS, GAUSS_FIXTURE, {}))
 
 
 def sweep(grid=GRID, fixed=None):
