@@ -68,8 +68,8 @@ typedef enum {
  *   v = clip(-0.07, v + 0.0015 a' - 0.0025 cos(3x), 0.07); x = clip(-1.2, x + v, 0.6); terminal iff x >= 0.6; reward 0 on a terminal step, -1
  *   otherwise.  The action set is not enumerable: rsrl_hip_n_actions is 0, rsrl_hip_action_bounds gives (-1, 1), and every action of the ctx is
  *   f32 (the *_f32 entry points below; their int32 twins are ESTATE, as the *_f32 calls are on the other domains).  Supported:
- *   RSRL_ILSTD_ACTOR_CRITIC and RSRL_NAC with policy RSRL_BETA, and RSRL_NAC with policy RSRL_GAUSSIAN, on the Fourier orders 1-5; every other
- *   combination is EINVAL at create. */
+ *   RSRL_ILSTD_ACTOR_CRITIC and RSRL_NAC with policy RSRL_BETA, and RSRL_NAC and RSRL_CACLA with policy RSRL_GAUSSIAN, on the Fourier orders 1-5;
+ *   every other combination is EINVAL at create. */
 typedef enum { RSRL_MOUNTAIN_CAR = 0, RSRL_CART_POLE = 1, RSRL_ACROBOT = 2, RSRL_HIV_TREATMENT = 3, RSRL_CONTINUOUS_MOUNTAIN_CAR = 4 } rsrl_domain;
 /* lfa::basis::{Fourier (+with_bias), TileCoding}  (re-exported by rsrl/src/fa/linear.rs:11-14) */
 typedef enum { RSRL_FOURIER = 0, RSRL_TILE_CODING = 1 } rsrl_basis;
@@ -277,7 +277,7 @@ typedef enum { RSRL_QLEARNING = 0, RSRL_SARSA = 1, RSRL_EXPECTED_SARSA = 2, RSRL
                 * RSRL_BETA's place.  The checkpoint is aux_kind 14 (aux_kind 12's sections): a Beta NAC file does not load into a Gaussian ctx, nor
                 * the other way round.  DEPARTURES: f32; the score DEFINED (RSRL_GAUSSIAN); the keyed stream; the period a parameter.
                 * Not built: nac_softmax.rs; Gaussian<M, f64> (the fixed-variance policy, policies/gaussian/fixed_var.rs); the Gaussian policy
-                * under RSRL_ILSTD_ACTOR_CRITIC; CACLA; IPP */
+                * under RSRL_ILSTD_ACTOR_CRITIC; IPP */
                RSRL_NAC = 28,
                /* (29 is no algo.)  GTD2 (prediction/td/gtd2.rs:27-86) and TDC (prediction/td/tdc.rs:41-101): gradient-TD prediction over TWO
                 * ScalarLFAs on one basis, theta (fa_theta / q_func: the value function) and w (fa_w / td_est: the second weight column), per
@@ -304,7 +304,47 @@ typedef enum { RSRL_QLEARNING = 0, RSRL_SARSA = 1, RSRL_EXPECTED_SARSA = 2, RSRL
                 * transitions as RSRL_TD's does; td_error_out and the statistics' sum |delta| are td.  handle_batch, handle_transitions, traces,
                 * policy weights and the lstd state are ESTATE.  The checkpoint is aux_kind 13 (theta, then w); a file of one of the two agents
                 * does not load into a ctx of the other */
-               RSRL_GTD2 = 30, RSRL_TDC = 31 } rsrl_algo;
+               RSRL_GTD2 = 30, RSRL_TDC = 31,
+               /* (32 is no algo.)  CACLA (control/cacla.rs:42-64), the continuous actor-critic learning automaton, over the Gaussian policy with a
+                * TD(0) state-value critic.  CACLA{critic, policy, alpha, gamma}: the critic is a closure over V that the agent reads and never
+                * writes -- a caller trains it; here it is eval = TD{v_func: LFA::scalar(basis, SGD(lr)), gamma} (prediction/td/td.rs:38-58), w
+                * f32[F] per learner, zero at create.  Per transition (s, a, r, s', term), cacla.rs:42-64:
+                *   v = critic(s);   target = r (terminal: r alone) | r + gamma critic(s');   if target > v (strict):
+                *   policy.handle(StateActionUpdate{s, a, error: (a - policy.mode(s)) * alpha})
+                * and Gaussian::handle (policies/gaussian/general.rs:196-212) is  w_m += (error g_mu) phi(s),  w_s += (error g_Sigma) grad stddev(s)
+                * with grad stddev(s) = sigma(x_s) phi(s) for the Softplus composition (g_mu, g_Sigma, x_s, sigma: RSRL_GAUSSIAN's, below).
+                * The reference has no example for CACLA, so the loop is this library's, in the order tdac.rs, tdac_beta.rs and nac.rs all use:
+                * t = env.transition(a) -- the domain sees the action itself, as in nac.rs:63 --; eval.handle(&t); agent.handle(&t), whose critic
+                * reads eval's UPDATED weights; a = policy.sample(s') with the updated columns, taken after the restart if the episode ended
+                * (terminal or cut by max_episode_steps: one sample per step, on BLK_STEP).  There is no inner draw.
+                * The f32 operation order is fixed (kernels_cacla.hpp, cacla_step; tests/cacla_numpy.py restates it):
+                *   1. x_m = <w_m, phi(s)>, x_s = <w_s, phi(s)>
+                *   2. RSRL_TD's arithmetic: v_s = <w, phi(s)>, v_n = <w, phi(s')>; td = r - v_s (terminal) | r + gamma v_n - v_s;
+                *      w += (lr td) phi(s), one fused multiply-add per element
+                *   3. with the updated w: v = <w, phi(s)>; target = r (terminal) | r + gamma <w, phi(s')>; gate = target > v (a NaN closes it)
+                *   4. gate open: (mu, sd) from (x_m, x_s); e = (a - mu) alpha; c_m = g_mu, c_s = g_Sigma sigma(x_s);
+                *      w_m += (e c_m) phi(s), w_s += (e c_s) phi(s), one fused multiply-add per element
+                * w and td are the bits of an RSRL_TD ctx's on the same transitions whatever the columns are; a closed gate leaves both columns'
+                * bits as they were, even where the coefficients would not be finite (the update sits behind the gate, not behind a product with 0).
+                * THE LITERAL RULE, a statement about the reference: the mean's step is e c_m = alpha (a - mu)^2 / Sigma >= 0 whatever side of the
+                * mean the action lay on -- the error already holds (a - mu), and the policy multiplies it by its score once more.  This is not
+                * van Hasselt's mu += alpha (a - mu).  The reference's rule is what is built (the stance taken for RSRL_GTD2 and for the Gaussian
+                * RSRL_NAC), with no safeguard: sd is floored at 0.01 only, so the coefficients reach 1e4 and a run need not stay finite.
+                * config: lr = TD's SGD rate, gamma = TD's and CACLA's, alpha = CACLA.alpha (rounded to f32 once); n_steps is not read;
+                * max_episode_steps may be 0, truncation is not terminal.  The statistics' sum |delta| is TD's.
+                * The value side is V, as RSRL_TD's: rsrl_hip_n_outputs is 1, rsrl_hip_n_weight_rows is F, rsrl_hip_q_evaluate writes f32(phi . w),
+                * rsrl_hip_get/set_weights carry w as f32[F][1]; q_find_max / _min, q_expected_value and q_evaluate_f32 are ESTATE.  The policy
+                * side is RSRL_GAUSSIAN's unchanged (policy_sample_f32 / _mode_f32 / _params / _pdf, get/set_policy_weights f32[F][2],
+                * n_policy_outputs 2, reset's initial sample on BLK_INIT; reset leaves all three columns alone).  rsrl_hip_handle_f32 is eval.handle
+                * then CACLA::handle on caller transitions (td_error_out = TD's error; a NaN or infinite host action: EINVAL);
+                * rsrl_hip_domain_step_f32 with actions == NULL steps on the pending actions literally; rsrl_hip_rollout_greedy is
+                * Domain::rollout(|s| policy.mode(s)); rsrl_hip_nac_update, rollout_trajectory / _policy, handle_batch, handle_transitions, traces,
+                * td weights and the lstd state are ESTATE.  Supported: RSRL_CONTINUOUS_MOUNTAIN_CAR with policy RSRL_GAUSSIAN, agent_policy -1,
+                * Fourier orders 1-5, per-learner f32 weights, no epsilon schedule; everything else is EINVAL at create -- RSRL_BETA included (no
+                * reference loop says whether the domain would see a or 2a - 1).  The checkpoint is aux_kind 15 (w, then the two columns): a CACLA
+                * file does not load into an RSRL_NAC ctx, nor the other way round.  DEPARTURES: f32 for the reference's f64; the score DEFINED
+                * (RSRL_GAUSSIAN); the loop is this library's.  Not built: Gaussian<M, f64>, the fixed-variance policy */
+               RSRL_CACLA = 33 } rsrl_algo;
 /* rsrl::traces::{Accumulate, Saturate (Trace::replacing), Dutch}      traces.rs:188-240 */
 typedef enum { RSRL_TRACE_ACCUMULATE = 0, RSRL_TRACE_SATURATE = 1, RSRL_TRACE_DUTCH = 2 } rsrl_trace;
 /* rsrl::policies::{Greedy, EpsilonGreedy, Softmax, Random}
@@ -326,7 +366,7 @@ typedef enum { RSRL_TRACE_ACCUMULATE = 0, RSRL_TRACE_SATURATE = 1, RSRL_TRACE_DU
  *           moves.  DEPARTURE: a caller-supplied action is clamped to the sample's interval before its logarithms (the reference would produce
  *           infinities for 0 and 1), in the spirit of the index actions' clamp.
  * (5 is no policy.)  Gaussian (policies/gaussian/{mod,general}.rs), Gaussian<ScalarLFA, Composition<ScalarLFA, Softplus>> with SGD(1.0) on both
- *   (nac.rs:31-35): the second CONTINUOUS policy, for RSRL_NAC on RSRL_CONTINUOUS_MOUNTAIN_CAR only (EINVAL elsewhere, RSRL_ILSTD_ACTOR_CRITIC
+ *   (nac.rs:31-35): the second CONTINUOUS policy, for RSRL_NAC and RSRL_CACLA on RSRL_CONTINUOUS_MOUNTAIN_CAR only (EINVAL elsewhere, RSRL_ILSTD_ACTOR_CRITIC
  *   included, and as agent_policy).  Per learner two weight columns w_m, w_s f32[F] (zero at create; get/set_policy_weights: f32[F][2], column 0 =
  *   the mean's, column 1 = the stddev's; rsrl_hip_n_policy_outputs = 2).  With x_m = <w_m, phi(s)>, x_s likewise (f32):
  *   params  mu = x_m, sd = softplus(x_s) + 0.01 (MIN_TOL, mod.rs:37, :67), Sigma = sd * sd (into_cov: mod.rs:82 builds the distribution from the
@@ -700,6 +740,7 @@ int rsrl_hip_lstd_solve(rsrl_hip_ctx* ctx);
  *   12 NAC's critic and the policy's columns         10          weights (3F rows), the policy's columns
  *   13 GTD2 / TDC: theta and the second column w     10          weights, auxiliary matrix
  *   14 NAC with RSRL_GAUSSIAN: critic and columns    10          weights (3F rows), the policy's columns
+ *   15 CACLA: the V learner's w and the columns      10          weights, the policy's columns
  * and a ctx with config.epsilon_decay (aux_kind 0 or 1) writes version 4 instead, with f32 eps[N] behind the payload.  No other pairing of
  * version and aux_kind is a file of this library; load refuses it.  Little-endian, serialised field by field (no padding):
  *   offset  0  char magic[8] = "RSRLHIPW"
@@ -710,7 +751,8 @@ int rsrl_hip_lstd_solve(rsrl_hip_ctx* ctx);
  *                   6 the TD ActorCritic's theta, 7 REINFORCE's theta and open episode, 8 the LSTD agents' f64 state,
  *                   9 the iLSTD ActorCritic's f64 state and theta, 10 LSTD / LSTDLambda's f64 state,
  *                   11 the Beta iLSTD ActorCritic's f64 state and policy columns, 12 NAC's critic and policy columns,
- *                   13 GTD2's / TDC's second weight column, 14 the Gaussian NAC's critic and policy columns)
+ *                   13 GTD2's / TDC's second weight column, 14 the Gaussian NAC's critic and policy columns,
+ *                   15 CACLA's V weights and policy columns)
  *                                                                                                                 [11 x i32]
  *          56  i64  n_learners (1 in shared mode)
  *          64  u64  step_count
@@ -737,6 +779,8 @@ int rsrl_hip_lstd_solve(rsrl_hip_ctx* ctx);
  *              are the critic's w, n_learners x f32[3F][1], then n_learners x f32[F][2] of the policy's columns;
  *              if aux_kind is 14 (file version 10 too; RSRL_NAC with RSRL_GAUSSIAN): aux_kind 12's sections, the columns the mean's and the
  *              stddev's -- the kind alone tells the two policies' files apart, and neither loads into a ctx of the other;
+ *              if aux_kind is 15 (file version 10 too; RSRL_CACLA; A = 1, the weights are the V learner's w): n_learners x f32[F][2] of the
+ *              Gaussian policy's columns (the mean's, the stddev's);
  *              if aux_kind is 13 (file version 10 too; RSRL_GTD2 / RSRL_TDC; A = 1, the weights are theta): n_learners x f32[F][1] of the
  *              second weight column w (fa_w / td_est);
  *              if aux_kind is 3 (file version 3): u32 head[N], u32 len[N], f32 entries[D + 5][n_steps][N] -- every learner's

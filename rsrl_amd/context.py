@@ -7,7 +7,7 @@ import numpy as np
 from . import _abi
 
 MOUNTAIN_CAR, CART_POLE, ACROBOT, HIV_TREATMENT = 0, 1, 2, 3
-CONTINUOUS_MOUNTAIN_CAR = 4                     # mountain_car/continuous.rs: one f32 action in [-1, 1] (Context.continuous; ILSTD_ACTOR_CRITIC and NAC with BETA, NAC with GAUSSIAN)
+CONTINUOUS_MOUNTAIN_CAR = 4                     # mountain_car/continuous.rs: one f32 action in [-1, 1] (Context.continuous; ILSTD_ACTOR_CRITIC and NAC with BETA, NAC and CACLA with GAUSSIAN)
 FOURIER, TILE_CODING = 0, 1
 QLEARNING, SARSA, EXPECTED_SARSA, SARSA_LAMBDA, Q_LAMBDA, PAL, GREEDY_GQ, TD, TD_LAMBDA, Q_SIGMA = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 ACTOR_CRITIC, Q_ACTOR_CRITIC = 10, 11          # ActorCritic (control/ac.rs) with a Gibbs actor and a SARSA critic: a2c.rs's closure / QCritic
@@ -19,10 +19,11 @@ GRADIENT_MC = 23                               # (22 is no algo) prediction/mc.r
 LSTD, LSTD_LAMBDA = 25, 26                      # (24 is no algo) prediction/lstd: LSTD, LSTDLambda (Handler<&Batch> on whole transitions: handle_transitions; lstd_solve; get/set_lstd_batch_state)
 NAC = 28                                        # (27 is no algo) control/nac.rs with the BETA (nac_beta.rs) or the GAUSSIAN policy (nac.rs) and a SARSA critic over the stable compatible basis on CONTINUOUS_MOUNTAIN_CAR: n_weight_rows = 3 F; q_evaluate_f32; nac_update
 GTD2, TDC = 30, 31                              # (29 is no algo) prediction/td: GTD2, TDC -- gradient TD with a second weight column (get/set_td_weights, (F, 1)); lr scales theta's moves, lr_td w's
+CACLA = 33                                      # (32 is no algo) control/cacla.rs over the GAUSSIAN policy with a TD(0) critic on CONTINUOUS_MOUNTAIN_CAR: lr = TD's rate, alpha = CACLA's; q_evaluate -> V(s); handle = eval.handle then CACLA::handle
 TRACE_ACCUMULATE, TRACE_SATURATE, TRACE_DUTCH = 0, 1, 2
 GREEDY, EPSILON_GREEDY, SOFTMAX, RANDOM = 0, 1, 2, 3
 BETA = 4                                        # policies/beta.rs over two Softplus-composed scalar LFAs: ILSTD_ACTOR_CRITIC on CONTINUOUS_MOUNTAIN_CAR
-GAUSSIAN = 6                                    # (5 is no policy) policies/gaussian: the mean a scalar LFA, the stddev a Softplus-composed one: NAC on CONTINUOUS_MOUNTAIN_CAR (nac.rs)
+GAUSSIAN = 6                                    # (5 is no policy) policies/gaussian: the mean a scalar LFA, the stddev a Softplus-composed one: NAC (nac.rs) and CACLA on CONTINUOUS_MOUNTAIN_CAR
 W_PER_ENV, W_SHARED = 0, 1
 W_F32, W_BF16 = 0, 1
 EXCHANGE_RCCL, EXCHANGE_PEER, EXCHANGE_AUTO = 0, 1, 2

@@ -435,6 +435,9 @@ int launch_agent(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, uint64_t 
     case AgentFamily::NacGaussReg:       // (io: as above)
         ok = !io && launch_nac_gauss(cf.order, c->stream, k, make_nac_beta(c), t, chunk, d_stats, nullptr);
         break;
+    case AgentFamily::CaclaGaussReg:     // (io: as above)
+        ok = !io && launch_cacla(cf.order, c->stream, k, make_cacla(c), t, chunk, d_stats, nullptr);
+        break;
     case AgentFamily::GtdReg: ok = launch_gtd(cf.domain, cf.order, cf.algo == RSRL_TDC, grid, block, c->stream, k, make_gtd(c), t, chunk, d_stats, io); break;
     default: ok = false; break;      // (the shared-W families: enqueue_shared_step)
     }

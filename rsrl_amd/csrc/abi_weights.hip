@@ -213,7 +213,7 @@ struct CkptKind {
     bool reads_kind0;            // a ctx of this kind also reads its configuration's version-2 / aux_kind-0 file, written before the kind's own section
     SectionId sections[3];       // travelled: the weights load, that section's state starts empty
 };
-constexpr int kCkptKinds = 15;
+constexpr int kCkptKinds = 16;
 constexpr CkptKind kCkptKind[kCkptKinds] = {
     /* 0 weights only                           */ {2, 0, true, false, {S_WEIGHTS}},
     /* 1 eligibility traces                     */ {2, 0, true, false, {S_WEIGHTS, S_AUX}},
@@ -231,6 +231,7 @@ constexpr CkptKind kCkptKind[kCkptKinds] = {
                                                                                                                       // the versions read, and tests hold its text)
     /* 13 GTD2 / TDC: theta, the second column w */ {10, 0, false, false, {S_WEIGHTS, S_AUX}},      // (version 10 as well; the header's algo tells the two agents apart)
     /* 14 NAC with the Gaussian policy: kind 12's sections */ {10, 0, false, false, {S_WEIGHTS, S_AUX}},      // (the kind alone tells the two policies' files apart)
+    /* 15 CACLA: the V learner's w, the Gaussian policy's two columns */ {10, 0, false, false, {S_WEIGHTS, S_AUX}},      // (version 10 as well)
 };
 // (the kinds the configuration decides, not the algo: SARSALambda / QLambda over ONE shared tile table keep sparse traces instead of Z; the iLSTD
 // ActorCritic with the Beta policy keeps two policy columns instead of the Gibbs actor's A; NAC's columns are the Gaussian policy's, not Beta's)

@@ -49,7 +49,7 @@ using namespace rsrl;
 
 // ---- THE agent table: what the reference's agent of each rsrl_algo is, one row per number.  Admission (check_config), the ctx's buffers (create_impl),
 // the accessors and the checkpoint read it; a new agent adds its row here, a line of classify() and a case of launch_agent ("Adding an agent").
-enum class Agent : uint8_t { None, OneStep, Lambda, Gq, Pred, QSigma, Ac, TdAc, Reinforce, Lstd, TdAcLstd, Gmc, LstdBatch, Nac, Gtd };      // the group classify() and the kernels' dispatch know it by
+enum class Agent : uint8_t { None, OneStep, Lambda, Gq, Pred, QSigma, Ac, TdAc, Reinforce, Lstd, TdAcLstd, Gmc, LstdBatch, Nac, Gtd, Cacla };      // the group classify() and the kernels' dispatch know it by
 enum class Aux : uint8_t { None, LikeW, Policy };      // the second per-learner matrix Z: none, of W's shape, or the actor's A columns next to a one-column W
 struct AlgoRow {
     const char* name = nullptr;      // as the admission messages print it (nullptr: the number is unassigned)
@@ -63,7 +63,7 @@ struct AlgoRow {
     // one of them), the message's words behind it and behind "agent_policy = -1", and what it calls config.n_steps in front of "n_updates" (nullptr: not read)
     int reg_policy = -1; const char* policy_words = ""; const char* shares_words = ""; const char* n_updates = nullptr;
 };
-constexpr AlgoRow kAlgo[RSRL_TDC + 1] = {
+constexpr AlgoRow kAlgo[RSRL_CACLA + 1] = {
     /*  0 */ {"QLearning", Agent::OneStep},
     /*  1 */ {"SARSA", Agent::OneStep},
     /*  2 */ {"ExpectedSARSA", Agent::OneStep},
@@ -104,6 +104,9 @@ constexpr AlgoRow kAlgo[RSRL_TDC + 1] = {
     // (the gradient-TD agents: W is theta's one column, TD's layout; Z is the second column w -- fa_w / td_est --, [F][1])
     /* 30 */ {"GTD2 (RSRL_GTD2)", Agent::Gtd, true, Aux::LikeW, 13, false, false, RSRL_RANDOM},
     /* 31 */ {"TDC (RSRL_TDC)", Agent::Gtd, true, Aux::LikeW, 13, false, false, RSRL_RANDOM},
+    /* 32 */ {},
+    // (W is the V learner's one column, TD's layout; the Gaussian policy's two columns in Z; admitted by check_continuous, not check_reg_only)
+    /* 33 */ {"CACLA (RSRL_CACLA)", Agent::Cacla, true, Aux::Policy, 15},
 };
 // (readers of the table, for configurations check_config has admitted: the algo is a row with a name)
 static inline bool is_lambda(int algo) { return kAlgo[algo].agent == Agent::Lambda; }
@@ -117,6 +120,7 @@ static inline bool is_gmc(int algo) { return kAlgo[algo].agent == Agent::Gmc; }
 static inline bool is_lstd_batch(int algo) { return kAlgo[algo].agent == Agent::LstdBatch; }
 static inline bool is_nac(int algo) { return kAlgo[algo].agent == Agent::Nac; }
 static inline bool is_gtd(int algo) { return kAlgo[algo].agent == Agent::Gtd; }
+static inline bool is_cacla(int algo) { return kAlgo[algo].agent == Agent::Cacla; }
 // the agents that keep every learner's open episode on the device (rec_s / rec_r, max_episode_steps rows) and sweep it when it ends
 static inline bool keeps_record(int algo) { return is_gmc(algo) || is_lstd_batch(algo); }
 // the agents whose value function is V alone and whose behaviour is Random: no action values to search, weigh, sample from or roll out with
@@ -211,8 +215,10 @@ enum class AgentFamily : uint8_t {
     GtdReg,               // GTD2 / TDC, same configurations as LstdReg: k_train_gtd (train_gtd.hip); theta in W (one column), the second column w in Z
     NacGaussReg,          // NAC with the Gaussian policy, NacBetaReg's configurations and layout: k_train_nac_gauss (train_nac_gauss.hip); the policy's columns
                           // (the mean's, the stddev's) in Z
+    CaclaGaussReg,        // CACLA over the Gaussian policy with a TD(0) critic, NacBetaReg's configurations: k_train_cacla (train_cacla.hip); the V learner's w
+                          // in W (one column, F rows), the policy's columns in Z, f32 actions in action_f
 };
-constexpr size_t kAgentFamilies = (size_t)AgentFamily::NacGaussReg + 1;      // (the enum's last value)
+constexpr size_t kAgentFamilies = (size_t)AgentFamily::CaclaGaussReg + 1;      // (the enum's last value)
 // ---- THE family table: which kernels serve a family and what they can do, one row per AgentFamily value in the enum's order.  classify() (abi_ctx.hip: a
 // decision) and launch_agent (abi_train.hip: it instantiates the templates) are the two other places a new family is entered.
 enum class Slots : uint8_t { Block, Block64, WaveBlock, Learner, LstdGroup };      // a statistics slot per: kBlock learners, 64 learners (k_train_lambda_mem4; the
@@ -270,6 +276,8 @@ constexpr FamilyRow kFamily[] = {
     {AgentFamily::NacBetaReg, "k_train_nac_beta", 256, Slots::Block, Handle::Agent, kPolicyW},      // (handle: rsrl_hip_handle_f32; a step is a long scalar chain: 256 as the memory-resident loops)
     {AgentFamily::GtdReg, "k_train_gtd", 4096, Slots::Block, Handle::Agent, 0},      // (4 096: TdReg's depth, taken over and not measured)
     {AgentFamily::NacGaussReg, "k_train_nac_gauss", 256, Slots::Block, Handle::Agent, kPolicyW},      // (handle: rsrl_hip_handle_f32; NacBetaReg's depth, taken over)
+    {AgentFamily::CaclaGaussReg, "k_train_cacla", 4096, Slots::Block, Handle::Agent, kPolicyW | kVCritic},      // (handle: rsrl_hip_handle_f32; measured at 65 536 order-3
+                                                                                                               // learners: 0.984 / 0.961 / 0.952 us per batch-step at 256 / 1 024 / 4 096 steps per launch, profiles/cacla_rate.md)
 };
 constexpr bool family_rows_in_order() {
     for (size_t i = 0; i < sizeof(kFamily) / sizeof(kFamily[0]); ++i) if ((size_t)kFamily[i].family != i) return false;
@@ -443,7 +451,7 @@ static inline bool is_v_actor_critic(const rsrl_hip_ctx* c) { return family_row(
 static inline int aux_cols(const rsrl_hip_ctx* c) { return kAlgo[c->cfg.algo].aux == Aux::Policy ? c->Ap : c->Aw; }
 // a ctx whose actions are f32 values, not indices (ContinuousMountainCar): the *_f32 entry points are its own, their int32 twins ESTATE
 static inline bool is_continuous(const rsrl_hip_ctx* c) { return c->cfg.domain == RSRL_CONTINUOUS_MOUNTAIN_CAR; }
-// the continuous ctx's policy is the Gaussian (kernels_gaussian.hpp), not Beta: its own kernels, actions any finite f32, no 2a - 1 in NAC's loop
+// the continuous ctx's policy is the Gaussian (kernels_gaussian.hpp), not Beta: its own kernels, actions any finite f32, no 2a - 1 in NAC's loop (nor in CACLA's)
 static inline bool is_gaussian(const rsrl_hip_ctx* c) { return c->cfg.policy == RSRL_GAUSSIAN; }
 #define NEEDS_INDEX_ACTIONS(c, call) do { if (is_continuous(c)) return fail(RSRL_HIP_ESTATE, "%s carries int32 action indices: this ctx's domain " \
     "(ContinuousMountainCar) has one f32 action -- use %s_f32", call, call); } while (0)
@@ -490,6 +498,12 @@ static inline NacBetaState make_nac_beta(const rsrl_hip_ctx* c) {
     NacBetaState ns;
     ns.pol = c->Z; ns.action = c->action_f; ns.period = (uint32_t)c->cfg.n_steps;
     return ns;
+}
+
+static inline CaclaState make_cacla(const rsrl_hip_ctx* c) {
+    CaclaState cs;
+    cs.pol = c->Z; cs.action = c->action_f;
+    return cs;
 }
 
 static inline TdacBetaState make_tdac_beta(const rsrl_hip_ctx* c) {

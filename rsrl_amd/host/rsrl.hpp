@@ -5,6 +5,7 @@
 //   rsrl::domains::{MountainCar, CartPole, Acrobot}      rsrl_domains/src/{mountain_car/discrete,cart_pole,acrobot}.rs
 //   rsrl::domains::ContinuousMountainCar, rsrl::policies::Beta      rsrl_domains/src/mountain_car/continuous.rs, rsrl/src/policies/beta.rs
 //   rsrl::policies::Gaussian                                        rsrl/src/policies/gaussian/{mod,general}.rs
+//   rsrl::control::cacla::CACLA                                     rsrl/src/control/cacla.rs
 //   rsrl::fa::linear::{basis::Fourier, optim::SGD, LFA}  rsrl/src/fa/linear.rs (re-exports of crate lfa)
 //   rsrl::policies::{Greedy, EpsilonGreedy, Softmax, Random}   rsrl/src/policies/*.rs
 //   rsrl::control::td::{QLearning, SARSA, ExpectedSARSA, PAL, SARSALambda, QLambda, GreedyGQ, QSigma}   rsrl/src/control/td/*.rs
@@ -339,6 +340,21 @@ struct LSTDLambda : control::td::Agent {
         : control::td::Agent{RSRL_LSTD_LAMBDA, make_shared(fa::linear::LFA::vector(basis, fa::linear::optim::SGD(0.0), 1)), gamma, 1.0, RSRL_TRACE_ACCUMULATE, lambda_} {}
 };
 }}  // namespace prediction::lstd
+// ---- rsrl::control::cacla: CACLA::new(critic, policy, alpha, gamma) (control/cacla.rs:11-29) with policies::Gaussian on
+// domains::ContinuousMountainCar.  critic: the reference's is any Function<(S,)> the agent reads and never writes; here it is the TD learner the
+// caller would train beside it -- prediction::td::TD{v_func, gamma}, handled before the agent on every transition (the order of tdac.rs and nac.rs;
+// the reference has no example for CACLA).  gamma must be the critic's: the library runs both with one.  The Session's weights are V's [F][1];
+// Session::handle(TransitionF32) is eval.handle then agent.handle.  The rule is the reference's, literally: the mean's step is
+// alpha (a - mu)^2 / Sigma >= 0 on either side of the mean (include/rsrl_hip.h, RSRL_CACLA)
+namespace control { namespace cacla {
+struct CACLA : td::Agent {
+    CACLA(const prediction::td::TD& critic, const policies::Gaussian& /*policy*/, double alpha_, double gamma_)
+        : td::Agent{RSRL_CACLA, critic.q_func, gamma_, alpha_} {
+        if (gamma_ != critic.gamma) throw Error(RSRL_HIP_EINVAL, "CACLA over a TD critic: the library runs CACLA and TD with one gamma");
+    }
+};
+}}  // namespace control::cacla
+
 inline control::ac::ActorCritic control::ac::ActorCritic::tdac(const prediction::lstd::iLSTD& eval, const policies::Gibbs& policy, double alpha_, double gamma) {
     if (gamma != eval.gamma) throw Error(RSRL_HIP_EINVAL, "ActorCritic::tdac over iLSTD: the library runs TDCritic and iLSTD with one gamma");
     fa::linear::LFA v = *eval.q_func;

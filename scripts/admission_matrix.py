@@ -10,7 +10,9 @@ fixture of its own; and GRID_BETA, the continuous axis: MountainCar and Continuo
 create_admission_nac.json (tests/test_nac_beta_cpu.py); and GRID_GTD: GRID's axes with the algos 29 (unassigned), GTD2 (30), TDC (31) and 32 (past
 the last) and an lr_td axis 0 / -1 (81 920 configurations) -> create_admission_gtd.json (tests/test_gtd_cpu.py); and GRID_GAUSS: the policies Beta (4),
 the unassigned 5, Gaussian (6) and 7 (past the last) x the iLSTD ActorCritic (21) and NAC (28) x MountainCar / ContinuousMountainCar x agent_policy
--1 / Gaussian x the Fourier orders 0-6 x GRID_NAC's n_steps (1 120 configurations) -> create_admission_gauss.json (tests/test_nac_gaussian_cpu.py).
+-1 / Gaussian x the Fourier orders 0-6 x GRID_NAC's n_steps (1 120 configurations) -> create_admission_gauss.json (tests/test_nac_gaussian_cpu.py); and
+GRID_CACLA: NAC (28), the unassigned 32, CACLA (33) and 34 (past the last) x the policies Random, Beta, Gaussian x MountainCar / ContinuousMountainCar x
+agent_policy -1 / Gaussian x the Fourier orders 0-6 (336 configurations) -> create_admission_cacla.json (tests/test_cacla_cpu.py).
     python scripts/admission_matrix.py            writes tests/golden/create_admission.json, create_admission_agents.json,
                                                   create_admission_agents2.json and create_admission_agents3.json
                                                   (tests/test_create_admission_cpu.py, tests/test_tdac_lstd_cpu.py and tests/test_gmc_cpu.py
@@ -33,6 +35,7 @@ BETA_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_beta.json
 NAC_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_nac.json")
 GTD_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_gtd.json")
 GAUSS_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_gauss.json")
+CACLA_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_cacla.json")
 EINVAL, EHIP = -1, -2
 
 # (config field, values): the first axis varies slowest
@@ -90,10 +93,18 @@ GRID_GAUSS = [
     ("order", [0, 1, 2, 3, 4, 5, 6]),
     ("n_steps", [0, 1, 100, 65536, 65537]),
 ]
+# CACLA (33) between the unassigned 32 and 34, next to NAC: under the Gaussian policy, its one policy, and under Beta and Random, which it refuses
+GRID_CACLA = [
+    ("algo", [28, 32, 33, 34]),              # 32, 34: no such algo
+    ("policy", [3, 4, 6]),
+    ("domain", [0, 4]),
+    ("agent_policy", [-1, 6]),
+    ("order", [0, 1, 2, 3, 4, 5, 6]),
+]
 # (grid, fixture, fields set on every configuration)
 GRIDS = ((GRID, FIXTURE, {}), (GRID_AGENTS, AGENTS_FIXTURE, {}), (GRID_AGENTS2, AGENTS2_FIXTURE, {}), (GRID_AGENTS3, AGENTS3_FIXTURE, FIXED_AGENTS3),
          (GRID_BETA, BETA_FIXTURE, {}), (GRID_NAC, NAC_FIXTURE, {}), (GRID_GTD, GTD_FIXTURE, {}),
-         (GRID_GAUSS, GAUSS_FIXTURE, {}))
+         (GRID_GAUSS, GAUSS_FIXTURE, {}), (GRID_CACLA, CACLA_FIXTURE, {}))
 
 
 def sweep(grid=GRID, fixed=None):
