@@ -68,7 +68,8 @@ typedef enum {
  *   v = clip(-0.07, v + 0.0015 a' - 0.0025 cos(3x), 0.07); x = clip(-1.2, x + v, 0.6); terminal iff x >= 0.6; reward 0 on a terminal step, -1
  *   otherwise.  The action set is not enumerable: rsrl_hip_n_actions is 0, rsrl_hip_action_bounds gives (-1, 1), and every action of the ctx is
  *   f32 (the *_f32 entry points below; their int32 twins are ESTATE, as the *_f32 calls are on the other domains).  Supported:
- *   RSRL_ILSTD_ACTOR_CRITIC and RSRL_NAC with policy RSRL_BETA, and RSRL_NAC and RSRL_CACLA with policy RSRL_GAUSSIAN, on the Fourier orders 1-5;
+ *   RSRL_ILSTD_ACTOR_CRITIC, RSRL_NAC and RSRL_CONTINUOUS_TD_ACTOR_CRITIC with policy RSRL_BETA, and RSRL_NAC, RSRL_CACLA and
+ *   RSRL_CONTINUOUS_TD_ACTOR_CRITIC with policy RSRL_GAUSSIAN, on the Fourier orders 1-5;
  *   every other combination is EINVAL at create. */
 typedef enum { RSRL_MOUNTAIN_CAR = 0, RSRL_CART_POLE = 1, RSRL_ACROBOT = 2, RSRL_HIV_TREATMENT = 3, RSRL_CONTINUOUS_MOUNTAIN_CAR = 4 } rsrl_domain;
 /* lfa::basis::{Fourier (+with_bias), TileCoding}  (re-exported by rsrl/src/fa/linear.rs:11-14) */
@@ -305,6 +306,51 @@ typedef enum { RSRL_QLEARNING = 0, RSRL_SARSA = 1, RSRL_EXPECTED_SARSA = 2, RSRL
                 * policy weights and the lstd state are ESTATE.  The checkpoint is aux_kind 13 (theta, then w); a file of one of the two agents
                 * does not load into a ctx of the other */
                RSRL_GTD2 = 30, RSRL_TDC = 31,
+               /* (34 is no algo.)  The continuous TD ActorCritic: ActorCritic::tdac(v_func, policy, alpha, gamma) (control/ac.rs:32-52, :87-115) with a
+                * TD(0) state-value critic over the Gaussian or the Beta policy on RSRL_CONTINUOUS_MOUNTAIN_CAR -- RSRL_TD_ACTOR_CRITIC's arithmetic for
+                * the critic half, RSRL_CACLA's layout for everything else.  (Listed before RSRL_CACLA, which stays the enum's last enumerator; a new
+                * number and not RSRL_TD_ACTOR_CRITIC on this domain, which stays refused there.)  eval = TD{v_func: LFA::scalar(basis, SGD(lr)), gamma}
+                * (prediction/td/td.rs:38-58), w f32[F] per learner, zero at create; the policy's two columns f32[F][2], zero at create, read as
+                * get/set_policy_weights read them for each policy (RSRL_GAUSSIAN: the mean's, the stddev's; RSRL_BETA: alpha's, beta's).
+                * The loop is that of tdac.rs and tdac_beta.rs: t = env.transition(..); eval.handle(&t); agent.handle(&t), whose critic reads eval's
+                * UPDATED weights; a = policy.sample(s') with the updated columns, taken after the restart if the episode ended (terminal or cut by
+                * max_episode_steps: one sample per step, on BLK_STEP).  There is no inner draw.  The domain sees the action itself under
+                * RSRL_GAUSSIAN (nac.rs:63's convention, as RSRL_CACLA) and 2a - 1 under RSRL_BETA (nac_beta.rs:63's mapping of the sample's [0, 1] onto
+                * the domain's [-1, 1]; tdac_beta.rs itself hands the domain a, which RSRL_ILSTD_ACTOR_CRITIC keeps); the agent sees a.
+                * The f32 operation order is fixed (kernels_tdac_cont.hpp, tdac_cont_step; tests/tdac_cont_numpy.py restates it in f64).  Per
+                * transition (s, a, r, s', term):
+                *   1. x0 = <col0, phi(s)>, x1 = <col1, phi(s)>, the columns before any move
+                *   2. RSRL_TD's arithmetic: v_s = <w, phi(s)>, v_n = <w, phi(s')>; td = r - v_s (terminal) | r + gamma v_n - v_s;
+                *      w += (lr td) phi(s), one fused multiply-add per element
+                *   3. TDCritic::target with the updated w (ac.rs:40-50), literally: nv = <w, phi(s')>; c = r - nv on a terminal transition (it reads
+                *      V of the terminal state itself, as RSRL_TD_ACTOR_CRITIC does), else c = r + gamma nv - <w, phi(s)>; e = alpha c, alpha rounded
+                *      to f32 once
+                *   4. policy.handle(StateActionUpdate{s, a, error: e}), always (no gate):
+                *      RSRL_GAUSSIAN  (mu, sd) from (x0, x1); c_m = g_mu, c_s = g_Sigma sigma(x1); w_m += (e c_m) phi(s), w_s += (e c_s) phi(s) --
+                *                     RSRL_CACLA's expressions with this e (general.rs:196-212)
+                *      RSRL_BETA      ac = the action clamped to [2^-24, 1 - 2^-24]; g_a = ln ac - psi(alpha) + psi(alpha + beta), g_b = ln(1 - ac) -
+                *                     psi(beta) + psi(alpha + beta), one shared psi(alpha + beta); s_a = e g_a sigma(x_a), s_b likewise;
+                *                     w_a += s_a phi(s), w_b += s_b phi(s) -- RSRL_ILSTD_ACTOR_CRITIC's actor expressions, left to right
+                *   There is no safeguard: a coefficient that is not finite propagates, as in the reference.
+                * w and td are the bits of an RSRL_TD ctx's on the same transitions, whatever the columns hold.  With c < 0 and a > mu the Gaussian
+                * mean's preference <w_m, phi(s)> DECREASES (e c_m = alpha c (a - mu) / Sigma < 0): the standard policy-gradient step, where
+                * RSRL_CACLA's literal rule moves it up on either side.
+                * config: lr = TD's SGD rate, gamma = TD's and TDCritic's, alpha = ActorCritic.alpha; n_steps is not read; max_episode_steps may be
+                * 0, truncation is not terminal.  The statistics' sum |delta| is TD's.
+                * The value side is V, as RSRL_CACLA's: rsrl_hip_n_outputs is 1, rsrl_hip_q_evaluate writes f32(phi . w), rsrl_hip_get/set_weights
+                * carry w as f32[F][1]; q_find_max / _min, q_expected_value and q_evaluate_f32 are ESTATE.  The policy side is the chosen policy's,
+                * unchanged (policy_sample_f32 / _mode_f32 / _params / _pdf, get/set_policy_weights f32[F][2], n_policy_outputs 2, reset's initial
+                * sample on BLK_INIT; reset leaves all three columns alone).  rsrl_hip_handle_f32 is eval.handle then ActorCritic::handle on caller
+                * transitions (td_error_out = TD's error; host actions by each policy's rule: Beta clamps, a NaN or infinite one is EINVAL);
+                * rsrl_hip_domain_step_f32 with actions == NULL applies each policy's loop convention to the pending actions;
+                * rsrl_hip_rollout_greedy is each policy's mode rollout (2 mode - 1 under RSRL_BETA, mode under RSRL_GAUSSIAN); rsrl_hip_nac_update,
+                * rsrl_hip_handle, handle_batch, handle_transitions, rollout_trajectory / _policy, traces, td weights and the lstd state are ESTATE.
+                * Supported: RSRL_CONTINUOUS_MOUNTAIN_CAR with policy RSRL_GAUSSIAN or RSRL_BETA, agent_policy -1, Fourier orders 1-5, per-learner
+                * f32 weights, no epsilon schedule; everything else is EINVAL at create.  The checkpoint is aux_kind 16 (Beta) / 17 (Gaussian), w then
+                * the two columns as aux_kind 15: a file of either loads into no other ctx, and no other kind into these.  DEPARTURES: f32 for the
+                * reference's f64; the scores as defined for each policy (RSRL_BETA, RSRL_GAUSSIAN); the Gaussian loop is this library's (the
+                * reference has no tdac example over its Gaussian policy), the Beta loop tdac_beta.rs's order with nac_beta.rs's action mapping */
+               RSRL_CONTINUOUS_TD_ACTOR_CRITIC = 35,
                /* (32 is no algo.)  CACLA (control/cacla.rs:42-64), the continuous actor-critic learning automaton, over the Gaussian policy with a
                 * TD(0) state-value critic.  CACLA{critic, policy, alpha, gamma}: the critic is a closure over V that the agent reads and never
                 * writes -- a caller trains it; here it is eval = TD{v_func: LFA::scalar(basis, SGD(lr)), gamma} (prediction/td/td.rs:38-58), w
@@ -366,7 +412,7 @@ typedef enum { RSRL_TRACE_ACCUMULATE = 0, RSRL_TRACE_SATURATE = 1, RSRL_TRACE_DU
  *           moves.  DEPARTURE: a caller-supplied action is clamped to the sample's interval before its logarithms (the reference would produce
  *           infinities for 0 and 1), in the spirit of the index actions' clamp.
  * (5 is no policy.)  Gaussian (policies/gaussian/{mod,general}.rs), Gaussian<ScalarLFA, Composition<ScalarLFA, Softplus>> with SGD(1.0) on both
- *   (nac.rs:31-35): the second CONTINUOUS policy, for RSRL_NAC and RSRL_CACLA on RSRL_CONTINUOUS_MOUNTAIN_CAR only (EINVAL elsewhere, RSRL_ILSTD_ACTOR_CRITIC
+ *   (nac.rs:31-35): the second CONTINUOUS policy, for RSRL_NAC, RSRL_CACLA and RSRL_CONTINUOUS_TD_ACTOR_CRITIC on RSRL_CONTINUOUS_MOUNTAIN_CAR only (EINVAL elsewhere, RSRL_ILSTD_ACTOR_CRITIC
  *   included, and as agent_policy).  Per learner two weight columns w_m, w_s f32[F] (zero at create; get/set_policy_weights: f32[F][2], column 0 =
  *   the mean's, column 1 = the stddev's; rsrl_hip_n_policy_outputs = 2).  With x_m = <w_m, phi(s)>, x_s likewise (f32):
  *   params  mu = x_m, sd = softplus(x_s) + 0.01 (MIN_TOL, mod.rs:37, :67), Sigma = sd * sd (into_cov: mod.rs:82 builds the distribution from the
@@ -741,6 +787,8 @@ int rsrl_hip_lstd_solve(rsrl_hip_ctx* ctx);
  *   13 GTD2 / TDC: theta and the second column w     10          weights, auxiliary matrix
  *   14 NAC with RSRL_GAUSSIAN: critic and columns    10          weights (3F rows), the policy's columns
  *   15 CACLA: the V learner's w and the columns      10          weights, the policy's columns
+ *   16 the continuous TD ActorCritic with RSRL_BETA  10          weights, the policy's columns
+ *   17 ... with RSRL_GAUSSIAN                        10          weights, the policy's columns
  * and a ctx with config.epsilon_decay (aux_kind 0 or 1) writes version 4 instead, with f32 eps[N] behind the payload.  No other pairing of
  * version and aux_kind is a file of this library; load refuses it.  Little-endian, serialised field by field (no padding):
  *   offset  0  char magic[8] = "RSRLHIPW"
@@ -752,7 +800,8 @@ int rsrl_hip_lstd_solve(rsrl_hip_ctx* ctx);
  *                   9 the iLSTD ActorCritic's f64 state and theta, 10 LSTD / LSTDLambda's f64 state,
  *                   11 the Beta iLSTD ActorCritic's f64 state and policy columns, 12 NAC's critic and policy columns,
  *                   13 GTD2's / TDC's second weight column, 14 the Gaussian NAC's critic and policy columns,
- *                   15 CACLA's V weights and policy columns)
+ *                   15 CACLA's V weights and policy columns, 16 / 17 the continuous TD ActorCritic's V weights and its Beta / Gaussian policy
+ *                   columns)
  *                                                                                                                 [11 x i32]
  *          56  i64  n_learners (1 in shared mode)
  *          64  u64  step_count
@@ -781,6 +830,8 @@ int rsrl_hip_lstd_solve(rsrl_hip_ctx* ctx);
  *              stddev's -- the kind alone tells the two policies' files apart, and neither loads into a ctx of the other;
  *              if aux_kind is 15 (file version 10 too; RSRL_CACLA; A = 1, the weights are the V learner's w): n_learners x f32[F][2] of the
  *              Gaussian policy's columns (the mean's, the stddev's);
+ *              if aux_kind is 16 or 17 (file version 10 too; RSRL_CONTINUOUS_TD_ACTOR_CRITIC with RSRL_BETA / RSRL_GAUSSIAN): aux_kind 15's sections,
+ *              the columns alpha's and beta's / the mean's and the stddev's;
  *              if aux_kind is 13 (file version 10 too; RSRL_GTD2 / RSRL_TDC; A = 1, the weights are theta): n_learners x f32[F][1] of the
  *              second weight column w (fa_w / td_est);
  *              if aux_kind is 3 (file version 3): u32 head[N], u32 len[N], f32 entries[D + 5][n_steps][N] -- every learner's

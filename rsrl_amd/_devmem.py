@@ -43,6 +43,9 @@ class DeviceBuffer:
         self.ptr = int(p.value)
         if zero and self.nbytes:
             _ok(hip().hipMemset(C.c_void_p(self.ptr), 0, self.nbytes), "hipMemset")
+            # hipMemset of device memory returns before the fill has run, and a ctx's stream does not wait for the null stream: without this a
+            # copy the library enqueues into the fresh buffer can land BEFORE the fill's tail (seen: the last 12 bytes of a 268-byte buffer zero)
+            _ok(hip().hipDeviceSynchronize(), "hipDeviceSynchronize")
 
     def at(self, element_offset):
         """address of element `element_offset`"""

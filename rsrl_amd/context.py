@@ -7,7 +7,7 @@ import numpy as np
 from . import _abi
 
 MOUNTAIN_CAR, CART_POLE, ACROBOT, HIV_TREATMENT = 0, 1, 2, 3
-CONTINUOUS_MOUNTAIN_CAR = 4                     # mountain_car/continuous.rs: one f32 action in [-1, 1] (Context.continuous; ILSTD_ACTOR_CRITIC and NAC with BETA, NAC and CACLA with GAUSSIAN)
+CONTINUOUS_MOUNTAIN_CAR = 4                     # mountain_car/continuous.rs: one f32 action in [-1, 1] (Context.continuous; ILSTD_ACTOR_CRITIC, NAC and CONTINUOUS_TD_ACTOR_CRITIC with BETA; NAC, CACLA and CONTINUOUS_TD_ACTOR_CRITIC with GAUSSIAN)
 FOURIER, TILE_CODING = 0, 1
 QLEARNING, SARSA, EXPECTED_SARSA, SARSA_LAMBDA, Q_LAMBDA, PAL, GREEDY_GQ, TD, TD_LAMBDA, Q_SIGMA = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 ACTOR_CRITIC, Q_ACTOR_CRITIC = 10, 11          # ActorCritic (control/ac.rs) with a Gibbs actor and a SARSA critic: a2c.rs's closure / QCritic
@@ -20,6 +20,7 @@ LSTD, LSTD_LAMBDA = 25, 26                      # (24 is no algo) prediction/lst
 NAC = 28                                        # (27 is no algo) control/nac.rs with the BETA (nac_beta.rs) or the GAUSSIAN policy (nac.rs) and a SARSA critic over the stable compatible basis on CONTINUOUS_MOUNTAIN_CAR: n_weight_rows = 3 F; q_evaluate_f32; nac_update
 GTD2, TDC = 30, 31                              # (29 is no algo) prediction/td: GTD2, TDC -- gradient TD with a second weight column (get/set_td_weights, (F, 1)); lr scales theta's moves, lr_td w's
 CACLA = 33                                      # (32 is no algo) control/cacla.rs over the GAUSSIAN policy with a TD(0) critic on CONTINUOUS_MOUNTAIN_CAR: lr = TD's rate, alpha = CACLA's; q_evaluate -> V(s); handle = eval.handle then CACLA::handle
+CONTINUOUS_TD_ACTOR_CRITIC = 35                 # (34 is no algo) ActorCritic::tdac (control/ac.rs) with a TD(0) critic over the GAUSSIAN or the BETA policy on CONTINUOUS_MOUNTAIN_CAR: lr = TD's rate, alpha = ActorCritic's; q_evaluate -> V(s); handle = eval.handle then ActorCritic::handle; the domain sees a (GAUSSIAN) or 2a - 1 (BETA)
 TRACE_ACCUMULATE, TRACE_SATURATE, TRACE_DUTCH = 0, 1, 2
 GREEDY, EPSILON_GREEDY, SOFTMAX, RANDOM = 0, 1, 2, 3
 BETA = 4                                        # policies/beta.rs over two Softplus-composed scalar LFAs: ILSTD_ACTOR_CRITIC on CONTINUOUS_MOUNTAIN_CAR

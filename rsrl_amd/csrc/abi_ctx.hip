@@ -50,6 +50,7 @@ static AgentFamily classify(const rsrl_hip_config& cfg, size_t w_elems) {
     if (is_nac(al)) return cfg.policy == RSRL_GAUSSIAN ? F::NacGaussReg : F::NacBetaReg;
     if (is_gtd(al)) return F::GtdReg;
     if (is_cacla(al)) return F::CaclaGaussReg;
+    if (is_tdac_cont(al)) return cfg.policy == RSRL_GAUSSIAN ? F::TdAcGaussReg : F::TdAcBetaTdReg;
     if (cfg.weight_mode == RSRL_W_SHARED) return fourier ? F::SharedDense : (is_sparse_lambda(cfg) ? F::SharedSparseLambda : F::SharedTile);
     if (wave && is_wave_aux_algo(al)) return F::WaveAux;
     if (is_pred(al)) return tile ? F::TdTile : (reg ? F::TdReg : F::TdGeneric);
@@ -168,15 +169,17 @@ static int check_reg_only(const rsrl_hip_config& cfg, const AlgoRow& a, bool sto
 // (state dimension, action count) of MountainCar, CartPole, Acrobot, HIVTreatment, ContinuousMountainCar (0: the action set is not enumerable)
 static const int kDomainShape[5][2] = {{2, 3}, {4, 2}, {4, 3}, {6, 4}, {2, 0}};
 
-// ContinuousMountainCar and the continuous policies (train_tdac_beta.hip, train_nac_beta.hip, train_nac_gauss.hip, train_cacla.hip): the domain exists for
-// them only and they for it, Beta under the iLSTD ActorCritic and NAC, Gaussian under NAC and CACLA -- and NAC and CACLA for them only
+// ContinuousMountainCar and the continuous policies (train_tdac_beta.hip, train_nac_beta.hip, train_nac_gauss.hip, train_cacla.hip, train_tdac_cont.hip):
+// the domain exists for them only and they for it, Beta under the iLSTD ActorCritic, NAC and the continuous TD ActorCritic, Gaussian under NAC, CACLA
+// and the continuous TD ActorCritic -- and NAC, CACLA and the continuous TD ActorCritic for them only
 static int check_continuous(const rsrl_hip_config& cfg, const AlgoRow& a, bool storage) {
-    const bool nac = cfg.algo == RSRL_NAC, cacla = cfg.algo == RSRL_CACLA;
-    const bool pair = (cfg.policy == RSRL_BETA && (cfg.algo == RSRL_ILSTD_ACTOR_CRITIC || nac)) || (cfg.policy == RSRL_GAUSSIAN && (nac || cacla));
+    const bool nac = cfg.algo == RSRL_NAC, cacla = cfg.algo == RSRL_CACLA, tdac = cfg.algo == RSRL_CONTINUOUS_TD_ACTOR_CRITIC;
+    const bool pair = (cfg.policy == RSRL_BETA && (cfg.algo == RSRL_ILSTD_ACTOR_CRITIC || nac || tdac)) || (cfg.policy == RSRL_GAUSSIAN && (nac || cacla || tdac));
     if (cfg.domain != RSRL_CONTINUOUS_MOUNTAIN_CAR || !pair || !storage || cfg.agent_policy != -1)
         return fail(RSRL_HIP_EINVAL, "ContinuousMountainCar (RSRL_CONTINUOUS_MOUNTAIN_CAR), the Beta policy (RSRL_BETA), the Gaussian policy (RSRL_GAUSSIAN), "
-                                     "NAC (RSRL_NAC) and CACLA (RSRL_CACLA) support the iLSTD ActorCritic (RSRL_ILSTD_ACTOR_CRITIC) with policy = Beta, NAC with "
-                                     "policy = Beta or Gaussian and CACLA with policy = Gaussian on ContinuousMountainCar, Fourier orders 1-5, per-learner f32 "
+                                     "NAC (RSRL_NAC), CACLA (RSRL_CACLA) and the continuous TD ActorCritic (RSRL_CONTINUOUS_TD_ACTOR_CRITIC) support the iLSTD "
+                                     "ActorCritic (RSRL_ILSTD_ACTOR_CRITIC) with policy = Beta, NAC and the continuous TD ActorCritic with policy = Beta or "
+                                     "Gaussian and CACLA with policy = Gaussian on ContinuousMountainCar, Fourier orders 1-5, per-learner f32 "
                                      "weights, agent_policy = -1 and no epsilon schedule -- and nothing else (got domain %d, basis %d, order %d, algo %d, weight "
                                      "mode %d, dtype %d, policy %d, agent_policy %d, epsilon_decay %g)",
                     cfg.domain, cfg.basis, cfg.order, cfg.algo, cfg.weight_mode, cfg.weight_dtype, cfg.policy, cfg.agent_policy, cfg.epsilon_decay);
@@ -186,7 +189,7 @@ static int check_continuous(const rsrl_hip_config& cfg, const AlgoRow& a, bool s
                                          "in [1, 65536], got %d", a.name, cfg.n_steps);
         return RSRL_HIP_OK;
     }
-    if (cacla) return RSRL_HIP_OK;      // (n_steps is not read)
+    if (cacla || tdac) return RSRL_HIP_OK;      // (n_steps is not read)
     if (cfg.n_steps < 1 || cfg.n_steps > 32)
         return fail(RSRL_HIP_EINVAL, "%s: n_steps (%sn_updates, the rounds of solve() per transition) must be in [1, 32], got %d", a.name, a.n_updates, cfg.n_steps);
     return RSRL_HIP_OK;
@@ -201,7 +204,7 @@ static int check_config(const rsrl_hip_config& cfg) {
     const int D = kDomainShape[cfg.domain][0], A = kDomainShape[cfg.domain][1];
     if (cfg.n_envs < 1) return fail(RSRL_HIP_EINVAL, "n_envs must be >= 1");
     if (cfg.n_envs + cfg.env_offset > (int64_t)0xffffffffLL || cfg.env_offset < 0) return fail(RSRL_HIP_EINVAL, "global env ids must fit 32 bits");
-    if (cfg.algo < 0 || cfg.algo > RSRL_CACLA || !kAlgo[cfg.algo].name) return fail(RSRL_HIP_EINVAL, "unknown algo %d", cfg.algo);
+    if (cfg.algo < 0 || cfg.algo > kLastAlgo || !kAlgo[cfg.algo].name) return fail(RSRL_HIP_EINVAL, "unknown algo %d", cfg.algo);
     if (cfg.policy < 0 || (cfg.policy > RSRL_BETA && cfg.policy != RSRL_GAUSSIAN)) return fail(RSRL_HIP_EINVAL, "unknown policy %d", cfg.policy);      // (5 is no policy)
     // Softmax::new panics for |tau| < 1e-7 (policies/softmax.rs:63-66)
     if (cfg.policy == RSRL_SOFTMAX && std::fabs(cfg.tau) < 1e-7) return fail(RSRL_HIP_EINVAL, "Tau parameter in Softmax must be non-zero.");
@@ -243,7 +246,7 @@ static int check_config(const rsrl_hip_config& cfg) {
     const bool tile = cfg.basis == RSRL_TILE_CODING, reg = is_reg_fourier(cfg), wave = is_wave(cfg);
     const bool f32 = cfg.weight_dtype == RSRL_W_F32, esched = cfg.epsilon_decay != 1.0;
     const bool one_step = kAlgo[al].agent == Agent::OneStep;
-    if (cfg.domain == RSRL_CONTINUOUS_MOUNTAIN_CAR || cfg.policy == RSRL_BETA || cfg.policy == RSRL_GAUSSIAN || al == RSRL_NAC || al == RSRL_CACLA)
+    if (cfg.domain == RSRL_CONTINUOUS_MOUNTAIN_CAR || cfg.policy == RSRL_BETA || cfg.policy == RSRL_GAUSSIAN || al == RSRL_NAC || al == RSRL_CACLA || al == RSRL_CONTINUOUS_TD_ACTOR_CRITIC)
         return check_continuous(cfg, kAlgo[al], is_cmc_fourier(cfg) && per_env && f32 && !esched);
     if (kAlgo[al].reg_policy >= 0) return check_reg_only(cfg, kAlgo[al], reg && per_env && f32 && !esched);
     if (cfg.domain == RSRL_HIV_TREATMENT) {
@@ -544,9 +547,9 @@ int rsrl_hip_reset(rsrl_hip_ctx* c) {
     if (c->family == AgentFamily::ReinforceReg) { launch_reinforce_restart(c->stream, make_reinforce(c), c->cfg.n_envs, (int64_t)c->F * c->A, nullptr); KCHECK(); }
     const Common k = make_policy_common(c);              // the initial policy.sample (ActorCritic: the actor's theta)
     const BasisGeom g = make_geom(c);
-    if (is_gaussian(c)) {      // (NAC and CACLA over the Gaussian policy: as the two below)
+    if (is_gaussian(c)) {      // (NAC, CACLA and the continuous TD ActorCritic over the Gaussian policy: as the two below)
         if (!launch_gauss_reset(c->cfg.order, c->stream, k, c->Z, c->t, c->action_f)) return NO_MODEL(c);
-    } else if (c->family == AgentFamily::TdAcBetaReg || c->family == AgentFamily::NacBetaReg) {      // (both agents' state is untouched: the initial sample reads the policy's columns)
+    } else if (c->family == AgentFamily::TdAcBetaReg || c->family == AgentFamily::NacBetaReg || c->family == AgentFamily::TdAcBetaTdReg) {      // (the agents' state is untouched: the initial sample reads the policy's columns)
         if (!launch_beta_reset(c->cfg.order, c->stream, k, c->Z, c->t, c->action_f)) return NO_MODEL(c);
     } else if (c->family == AgentFamily::Hiv) {
         launch_hiv_reset(c->stream, k, g, c->hiv_y, c->t);

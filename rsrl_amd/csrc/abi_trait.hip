@@ -173,7 +173,7 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
     const BasisGeom g = make_geom(c);
     if (has_lstd_state(c) && op == QOP_EVALUATE) {                        // V(s) = f32(phi(s) . theta), in f64 (k_lstd_v)
         if (!launch_lstd_v(feature_domain(c), c->cfg.order, c->stream, c->lstd_theta, d_states, M_, d_fout)) return NO_MODEL(c);
-    } else if (is_cacla(c->cfg.algo) && op == QOP_EVALUATE) {             // V(s) of CACLA's TD learner: k_v_evaluate on MountainCar's projection
+    } else if (is_td_v_continuous(c->cfg.algo) && op == QOP_EVALUATE) {   // V(s) of CACLA's / the continuous TD ActorCritic's TD learner: k_v_evaluate on MountainCar's projection
         if (!launch_v_evaluate(feature_domain(c), c->cfg.order, dim3(grid_for(M_)), dim3(kBlock), c->stream, k, d_states, M_, d_fout)) return NO_MODEL(c);
     } else if (is_continuous(c)) {                                        // QOP_FEATURES: MountainCar's projection at the same order
         bool ok = false;
@@ -439,8 +439,9 @@ int rsrl_hip_domain_step_f32(rsrl_hip_ctx* c, const float* actions, float* from_
     StepArrays<float> s;
     TRY(stage_step(f, actions, from_states, next_states, rewards, terminal, &s));
     const Common k = make_common(c);
-    // (NAC with Beta: explicit actions are the domain's, the pending ones the agent's -- stepped on through the loop's 2a - 1; nac.rs's loop maps nothing)
-    if (is_nac(c->cfg.algo) && !is_gaussian(c)) launch_nac_domain_step(c->stream, k, s.act, c->action_f, s.from, s.next, s.rew, s.term);
+    // (NAC and the continuous TD ActorCritic with Beta: explicit actions are the domain's, the pending ones the agent's -- stepped on through the loop's
+    // 2a - 1; the Gaussian loops map nothing)
+    if (maps_beta_action(c)) launch_nac_domain_step(c->stream, k, s.act, c->action_f, s.from, s.next, s.rew, s.term);
     else launch_cmc_domain_step(c->stream, k, s.act, c->action_f, s.from, s.next, s.rew, s.term);
     KCHECK();
     return f.finish();
@@ -459,7 +460,8 @@ int rsrl_hip_handle_f32(rsrl_hip_ctx* c, const float* from_states, const float* 
     TransitionsF32 io;
     TRY(stage_transitions(f, from_states, actions, rewards, to_states, terminal, M, td_error_out, &io));
     const Common k = make_common(c);
-    if (!(is_cacla(c->cfg.algo) ? launch_cacla(c->cfg.order, c->stream, k, make_cacla(c), c->t, 1, nullptr, &io)          // eval.handle, then CACLA::handle
+    if (!(is_tdac_cont(c->cfg.algo) ? launch_tdac_cont(c->cfg.order, cont_policy(c), c->stream, k, make_tdac_cont(c), c->t, 1, nullptr, &io)      // eval.handle, then ActorCritic::handle
+          : is_cacla(c->cfg.algo) ? launch_cacla(c->cfg.order, c->stream, k, make_cacla(c), c->t, 1, nullptr, &io)          // eval.handle, then CACLA::handle
           : is_gaussian(c)    ? launch_nac_gauss(c->cfg.order, c->stream, k, make_nac_beta(c), c->t, 1, nullptr, &io)     // critic.handle: SARSA over SCB
           : is_nac(c->cfg.algo) ? launch_nac_beta(c->cfg.order, c->stream, k, make_nac_beta(c), c->t, 1, nullptr, &io)
                               : launch_tdac_beta(c->cfg.order, c->stream, k, make_tdac_beta(c), c->t, 1, nullptr, &io))) return NO_MODEL(c);

@@ -213,7 +213,7 @@ struct CkptKind {
     bool reads_kind0;            // a ctx of this kind also reads its configuration's version-2 / aux_kind-0 file, written before the kind's own section
     SectionId sections[3];       // travelled: the weights load, that section's state starts empty
 };
-constexpr int kCkptKinds = 16;
+constexpr int kCkptKinds = 18;
 constexpr CkptKind kCkptKind[kCkptKinds] = {
     /* 0 weights only                           */ {2, 0, true, false, {S_WEIGHTS}},
     /* 1 eligibility traces                     */ {2, 0, true, false, {S_WEIGHTS, S_AUX}},
@@ -232,11 +232,14 @@ constexpr CkptKind kCkptKind[kCkptKinds] = {
     /* 13 GTD2 / TDC: theta, the second column w */ {10, 0, false, false, {S_WEIGHTS, S_AUX}},      // (version 10 as well; the header's algo tells the two agents apart)
     /* 14 NAC with the Gaussian policy: kind 12's sections */ {10, 0, false, false, {S_WEIGHTS, S_AUX}},      // (the kind alone tells the two policies' files apart)
     /* 15 CACLA: the V learner's w, the Gaussian policy's two columns */ {10, 0, false, false, {S_WEIGHTS, S_AUX}},      // (version 10 as well)
+    /* 16 the continuous TD ActorCritic with the Beta policy: kind 15's sections */ {10, 0, false, false, {S_WEIGHTS, S_AUX}},
+    /* 17 ... with the Gaussian policy */ {10, 0, false, false, {S_WEIGHTS, S_AUX}},      // (the kind alone tells the two policies' files, and CACLA's, apart)
 };
 // (the kinds the configuration decides, not the algo: SARSALambda / QLambda over ONE shared tile table keep sparse traces instead of Z; the iLSTD
 // ActorCritic with the Beta policy keeps two policy columns instead of the Gibbs actor's A; NAC's columns are the Gaussian policy's, not Beta's)
 int aux_kind_of(const rsrl_hip_ctx* c) {
     if (c->family == AgentFamily::NacGaussReg) return 14;
+    if (c->family == AgentFamily::TdAcGaussReg) return 17;
     return c->sp_keys ? 4 : (c->family == AgentFamily::TdAcBetaReg ? 11 : kAlgo[c->cfg.algo].aux_kind);
 }
 // is (version, aux_kind) a header this library writes, or ever wrote?

@@ -49,7 +49,7 @@ using namespace rsrl;
 
 // ---- THE agent table: what the reference's agent of each rsrl_algo is, one row per number.  Admission (check_config), the ctx's buffers (create_impl),
 // the accessors and the checkpoint read it; a new agent adds its row here, a line of classify() and a case of launch_agent ("Adding an agent").
-enum class Agent : uint8_t { None, OneStep, Lambda, Gq, Pred, QSigma, Ac, TdAc, Reinforce, Lstd, TdAcLstd, Gmc, LstdBatch, Nac, Gtd, Cacla };      // the group classify() and the kernels' dispatch know it by
+enum class Agent : uint8_t { None, OneStep, Lambda, Gq, Pred, QSigma, Ac, TdAc, Reinforce, Lstd, TdAcLstd, Gmc, LstdBatch, Nac, Gtd, Cacla, TdAcCont };      // the group classify() and the kernels' dispatch know it by
 enum class Aux : uint8_t { None, LikeW, Policy };      // the second per-learner matrix Z: none, of W's shape, or the actor's A columns next to a one-column W
 struct AlgoRow {
     const char* name = nullptr;      // as the admission messages print it (nullptr: the number is unassigned)
@@ -63,7 +63,8 @@ struct AlgoRow {
     // one of them), the message's words behind it and behind "agent_policy = -1", and what it calls config.n_steps in front of "n_updates" (nullptr: not read)
     int reg_policy = -1; const char* policy_words = ""; const char* shares_words = ""; const char* n_updates = nullptr;
 };
-constexpr AlgoRow kAlgo[RSRL_CACLA + 1] = {
+constexpr int kLastAlgo = RSRL_CONTINUOUS_TD_ACTOR_CRITIC;      // the highest assigned number (RSRL_CACLA stays the enum's textually last enumerator)
+constexpr AlgoRow kAlgo[kLastAlgo + 1] = {
     /*  0 */ {"QLearning", Agent::OneStep},
     /*  1 */ {"SARSA", Agent::OneStep},
     /*  2 */ {"ExpectedSARSA", Agent::OneStep},
@@ -107,6 +108,10 @@ constexpr AlgoRow kAlgo[RSRL_CACLA + 1] = {
     /* 32 */ {},
     // (W is the V learner's one column, TD's layout; the Gaussian policy's two columns in Z; admitted by check_continuous, not check_reg_only)
     /* 33 */ {"CACLA (RSRL_CACLA)", Agent::Cacla, true, Aux::Policy, 15},
+    /* 34 */ {},
+    // (CACLA's layout: W is the V learner's one column, the Gaussian or the Beta policy's two columns in Z; admitted by check_continuous; aux_kind 16 with
+    // Beta, 17 with Gaussian: aux_kind_of)
+    /* 35 */ {"the continuous TD ActorCritic (RSRL_CONTINUOUS_TD_ACTOR_CRITIC)", Agent::TdAcCont, true, Aux::Policy, 16},
 };
 // (readers of the table, for configurations check_config has admitted: the algo is a row with a name)
 static inline bool is_lambda(int algo) { return kAlgo[algo].agent == Agent::Lambda; }
@@ -121,6 +126,9 @@ static inline bool is_lstd_batch(int algo) { return kAlgo[algo].agent == Agent::
 static inline bool is_nac(int algo) { return kAlgo[algo].agent == Agent::Nac; }
 static inline bool is_gtd(int algo) { return kAlgo[algo].agent == Agent::Gtd; }
 static inline bool is_cacla(int algo) { return kAlgo[algo].agent == Agent::Cacla; }
+static inline bool is_tdac_cont(int algo) { return kAlgo[algo].agent == Agent::TdAcCont; }
+// the continuous agents whose value function is a TD(0) V learner in W, TD's layout (rsrl_hip_q_evaluate -> V(s): k_v_evaluate)
+static inline bool is_td_v_continuous(int algo) { return is_cacla(algo) || is_tdac_cont(algo); }
 // the agents that keep every learner's open episode on the device (rec_s / rec_r, max_episode_steps rows) and sweep it when it ends
 static inline bool keeps_record(int algo) { return is_gmc(algo) || is_lstd_batch(algo); }
 // the agents whose value function is V alone and whose behaviour is Random: no action values to search, weigh, sample from or roll out with
@@ -217,8 +225,12 @@ enum class AgentFamily : uint8_t {
                           // (the mean's, the stddev's) in Z
     CaclaGaussReg,        // CACLA over the Gaussian policy with a TD(0) critic, NacBetaReg's configurations: k_train_cacla (train_cacla.hip); the V learner's w
                           // in W (one column, F rows), the policy's columns in Z, f32 actions in action_f
+    TdAcGaussReg,         // ActorCritic::tdac with a TD(0) critic over the Gaussian policy, CaclaGaussReg's configurations and layout: k_train_tdac_cont
+                          // (train_tdac_cont.hip)
+    TdAcBetaTdReg,        // ... over the Beta policy (the columns alpha's and beta's; the loop hands the domain 2a - 1): k_train_tdac_cont.  (TdAcBetaReg is
+                          // the iLSTD critic's family)
 };
-constexpr size_t kAgentFamilies = (size_t)AgentFamily::CaclaGaussReg + 1;      // (the enum's last value)
+constexpr size_t kAgentFamilies = (size_t)AgentFamily::TdAcBetaTdReg + 1;      // (the enum's last value)
 // ---- THE family table: which kernels serve a family and what they can do, one row per AgentFamily value in the enum's order.  classify() (abi_ctx.hip: a
 // decision) and launch_agent (abi_train.hip: it instantiates the templates) are the two other places a new family is entered.
 enum class Slots : uint8_t { Block, Block64, WaveBlock, Learner, LstdGroup };      // a statistics slot per: kBlock learners, 64 learners (k_train_lambda_mem4; the
@@ -278,6 +290,10 @@ constexpr FamilyRow kFamily[] = {
     {AgentFamily::NacGaussReg, "k_train_nac_gauss", 256, Slots::Block, Handle::Agent, kPolicyW},      // (handle: rsrl_hip_handle_f32; NacBetaReg's depth, taken over)
     {AgentFamily::CaclaGaussReg, "k_train_cacla", 4096, Slots::Block, Handle::Agent, kPolicyW | kVCritic},      // (handle: rsrl_hip_handle_f32; measured at 65 536 order-3
                                                                                                                // learners: 0.984 / 0.961 / 0.952 us per batch-step at 256 / 1 024 / 4 096 steps per launch, profiles/cacla_rate.md)
+    {AgentFamily::TdAcGaussReg, "k_train_tdac_cont", 4096, Slots::Block, Handle::Agent, kPolicyW | kVCritic},      // (handle: rsrl_hip_handle_f32; measured at 65 536 order-3 learners: 1.02 / 1.00 /
+                                                                                                                   // 0.99 us per batch-step at 256 / 1 024 / 4 096 steps per launch, profiles/tdac_cont_rate.md)
+    {AgentFamily::TdAcBetaTdReg, "k_train_tdac_cont", 4096, Slots::Block, Handle::Agent, kPolicyW | kVCritic},     // (handle: rsrl_hip_handle_f32; 3.18 / 3.14 / 3.12 us at the same depths: the
+                                                                                                                   // Beta sampler's scalar chain dominates, the depth is CaclaGaussReg's all the same)
 };
 constexpr bool family_rows_in_order() {
     for (size_t i = 0; i < sizeof(kFamily) / sizeof(kFamily[0]); ++i) if ((size_t)kFamily[i].family != i) return false;
@@ -453,6 +469,9 @@ static inline int aux_cols(const rsrl_hip_ctx* c) { return kAlgo[c->cfg.algo].au
 static inline bool is_continuous(const rsrl_hip_ctx* c) { return c->cfg.domain == RSRL_CONTINUOUS_MOUNTAIN_CAR; }
 // the continuous ctx's policy is the Gaussian (kernels_gaussian.hpp), not Beta: its own kernels, actions any finite f32, no 2a - 1 in NAC's loop (nor in CACLA's)
 static inline bool is_gaussian(const rsrl_hip_ctx* c) { return c->cfg.policy == RSRL_GAUSSIAN; }
+// the Beta loops that hand the domain 2a - 1 for the agent's action a (nac_beta.rs:63; NAC and the continuous TD ActorCritic): the pending-action
+// domain step and the mode rollout apply it.  (The iLSTD ActorCritic's loop, tdac_beta.rs, hands the domain the action itself)
+static inline bool maps_beta_action(const rsrl_hip_ctx* c) { return !is_gaussian(c) && (is_nac(c->cfg.algo) || is_tdac_cont(c->cfg.algo)); }
 #define NEEDS_INDEX_ACTIONS(c, call) do { if (is_continuous(c)) return fail(RSRL_HIP_ESTATE, "%s carries int32 action indices: this ctx's domain " \
     "(ContinuousMountainCar) has one f32 action -- use %s_f32", call, call); } while (0)
 #define NEEDS_F32_ACTIONS(c, call) do { if (!is_continuous(c)) return fail(RSRL_HIP_ESTATE, "%s_f32 carries f32 actions: this ctx's domain has a finite " \
@@ -505,6 +524,13 @@ static inline CaclaState make_cacla(const rsrl_hip_ctx* c) {
     cs.pol = c->Z; cs.action = c->action_f;
     return cs;
 }
+
+static inline TdacContState make_tdac_cont(const rsrl_hip_ctx* c) {
+    TdacContState ts;
+    ts.pol = c->Z; ts.action = c->action_f;
+    return ts;
+}
+static inline ContPolicy cont_policy(const rsrl_hip_ctx* c) { return c->cfg.policy == RSRL_GAUSSIAN ? ContPolicy::Gaussian : ContPolicy::Beta; }
 
 static inline TdacBetaState make_tdac_beta(const rsrl_hip_ctx* c) {
     TdacBetaState ts;

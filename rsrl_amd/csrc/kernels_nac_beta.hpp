@@ -273,6 +273,9 @@ __global__ __launch_bounds__(kBlock) void k_nac_rollout_mode(Common c, const flo
     if (total) total[i] = tot;
 }
 
+// (the kernel below is no template: a second unit that includes this file for its device functions -- train_tdac_cont.hip -- defines
+// RSRL_NAC_BETA_DEVICE_FUNCTIONS_ONLY and leaves its one definition to train_nac_beta.hip, as RSRL_BETA_DEVICE_FUNCTIONS_ONLY does in kernels_tdac_beta.hpp)
+#ifndef RSRL_NAC_BETA_DEVICE_FUNCTIONS_ONLY
 // Domain::transition on the ctx's envs (k_cmc_domain_step's contract): explicit actions are the domain's own, taken literally; actions == nullptr
 // steps on the ctx's pending actions through the loop's mapping 2a - 1
 __global__ __launch_bounds__(kBlock) void k_nac_domain_step(Common c, const float* __restrict__ actions, const float* __restrict__ pending,
@@ -300,5 +303,6 @@ __global__ __launch_bounds__(kBlock) void k_nac_domain_step(Common c, const floa
     if (rew_out) rew_out[i] = r;
     if (term_out) term_out[i] = term ? 1 : 0;
 }
+#endif
 
 }  // namespace rsrl

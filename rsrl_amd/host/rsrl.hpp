@@ -6,6 +6,7 @@
 //   rsrl::domains::ContinuousMountainCar, rsrl::policies::Beta      rsrl_domains/src/mountain_car/continuous.rs, rsrl/src/policies/beta.rs
 //   rsrl::policies::Gaussian                                        rsrl/src/policies/gaussian/{mod,general}.rs
 //   rsrl::control::cacla::CACLA                                     rsrl/src/control/cacla.rs
+//   rsrl::control::ac::ActorCritic::tdac(TD, Gaussian | Beta, ..)    rsrl/src/control/ac.rs over prediction/td/td.rs (RSRL_CONTINUOUS_TD_ACTOR_CRITIC)
 //   rsrl::fa::linear::{basis::Fourier, optim::SGD, LFA}  rsrl/src/fa/linear.rs (re-exports of crate lfa)
 //   rsrl::policies::{Greedy, EpsilonGreedy, Softmax, Random}   rsrl/src/policies/*.rs
 //   rsrl::control::td::{QLearning, SARSA, ExpectedSARSA, PAL, SARSALambda, QLambda, GreedyGQ, QSigma}   rsrl/src/control/td/*.rs
@@ -227,7 +228,7 @@ struct GreedyGQ : Agent {
 // ---- rsrl::control::ac: ActorCritic { critic, policy, alpha } with the Gibbs actor and a SARSA critic    (control/ac.rs:49-115, examples/a2c.rs)
 // critic: the SARSA evaluator (its q_func and gamma; it shares the actor as its policy, as the example does); the target is a2c.rs's closure
 // Q(s,a) - sum_b Q(s,b) pi(b|s), or Q(s,a) for ActorCritic::qac (QCritic).  The Session's policy must be the same Gibbs object.
-namespace prediction { namespace lstd { struct iLSTD; } }
+namespace prediction { namespace lstd { struct iLSTD; } namespace td { struct TD; } }
 namespace control { namespace ac {
 // TDCritic { gamma, v_func } (ac.rs:32-52): the target r + gamma V(s') - V(s), or r - V(s') on a terminal transition
 struct TDCritic {
@@ -252,6 +253,14 @@ struct ActorCritic : td::Agent {
     static inline ActorCritic tdac(const prediction::lstd::iLSTD& eval, const policies::Gibbs& policy, double alpha_, double gamma);
     // ... generic over the policy: with policies::Beta on domains::ContinuousMountainCar, the agent of examples/tdac_beta.rs (same algo)
     static inline ActorCritic tdac(const prediction::lstd::iLSTD& eval, const policies::Beta& policy, double alpha_, double gamma);
+    // ActorCritic::tdac over the continuous policies with TD(0) as `eval` (RSRL_CONTINUOUS_TD_ACTOR_CRITIC): prediction::td::TD{v_func, gamma}
+    // handled before the agent on every transition, on domains::ContinuousMountainCar.  gamma is TDCritic's and must be eval's: the library runs
+    // both with one.  The Session's weights are V's [F][1]; Session::handle(TransitionF32) is eval.handle then agent.handle.  The loop hands the
+    // domain the action itself under Gaussian and 2a - 1 under Beta (include/rsrl_hip.h)  (defined below TD)
+    static inline ActorCritic tdac(const prediction::td::TD& eval, const policies::Gaussian& policy, double alpha_, double gamma);
+    static inline ActorCritic tdac(const prediction::td::TD& eval, const policies::Beta& policy, double alpha_, double gamma);
+private:
+    static inline ActorCritic tdac_cont(const prediction::td::TD& eval, double alpha_, double gamma);
 };
 }}  // namespace control::ac
 
@@ -366,6 +375,19 @@ inline control::ac::ActorCritic control::ac::ActorCritic::tdac(const prediction:
 
 inline control::ac::ActorCritic control::ac::ActorCritic::tdac(const prediction::lstd::iLSTD& eval, const policies::Beta&, double alpha_, double gamma) {
     return tdac(eval, policies::Gibbs::standard(eval.q_func), alpha_, gamma);      // (the Session's policy decides the kind)
+}
+
+inline control::ac::ActorCritic control::ac::ActorCritic::tdac_cont(const prediction::td::TD& eval, double alpha_, double gamma) {
+    if (gamma != eval.gamma) throw Error(RSRL_HIP_EINVAL, "ActorCritic::tdac over TD: the library runs TDCritic and TD with one gamma");
+    ActorCritic a(TDCritic{gamma, eval.q_func}, policies::Gibbs::standard(eval.q_func), alpha_);      // (the Session's policy decides the kind)
+    a.algo = RSRL_CONTINUOUS_TD_ACTOR_CRITIC;
+    return a;
+}
+inline control::ac::ActorCritic control::ac::ActorCritic::tdac(const prediction::td::TD& eval, const policies::Gaussian&, double alpha_, double gamma) {
+    return tdac_cont(eval, alpha_, gamma);
+}
+inline control::ac::ActorCritic control::ac::ActorCritic::tdac(const prediction::td::TD& eval, const policies::Beta&, double alpha_, double gamma) {
+    return tdac_cont(eval, alpha_, gamma);
 }
 
 // ---- the bound object graph: env + agent + policy sharing one q_func on one MI355X -------------------

@@ -12,7 +12,10 @@ the last) and an lr_td axis 0 / -1 (81 920 configurations) -> create_admission_g
 the unassigned 5, Gaussian (6) and 7 (past the last) x the iLSTD ActorCritic (21) and NAC (28) x MountainCar / ContinuousMountainCar x agent_policy
 -1 / Gaussian x the Fourier orders 0-6 x GRID_NAC's n_steps (1 120 configurations) -> create_admission_gauss.json (tests/test_nac_gaussian_cpu.py); and
 GRID_CACLA: NAC (28), the unassigned 32, CACLA (33) and 34 (past the last) x the policies Random, Beta, Gaussian x MountainCar / ContinuousMountainCar x
-agent_policy -1 / Gaussian x the Fourier orders 0-6 (336 configurations) -> create_admission_cacla.json (tests/test_cacla_cpu.py).
+agent_policy -1 / Gaussian x the Fourier orders 0-6 (336 configurations) -> create_admission_cacla.json (tests/test_cacla_cpu.py); and
+GRID_TDAC_CONT: CACLA (33), the unassigned 34, the continuous TD ActorCritic (35) and 36 (past the last) x the policies Softmax, Random, Beta, Gaussian x
+MountainCar / ContinuousMountainCar x agent_policy -1 / Gaussian x the Fourier orders 0-6 (448 configurations) -> create_admission_tdac_cont.json
+(tests/test_tdac_cont_cpu.py).
     python scripts/admission_matrix.py            writes tests/golden/create_admission.json, create_admission_agents.json,
                                                   create_admission_agents2.json and create_admission_agents3.json
                                                   (tests/test_create_admission_cpu.py, tests/test_tdac_lstd_cpu.py and tests/test_gmc_cpu.py
@@ -36,6 +39,7 @@ NAC_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_nac.json")
 GTD_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_gtd.json")
 GAUSS_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_gauss.json")
 CACLA_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_cacla.json")
+TDAC_CONT_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_tdac_cont.json")
 EINVAL, EHIP = -1, -2
 
 # (config field, values): the first axis varies slowest
@@ -101,10 +105,19 @@ GRID_CACLA = [
     ("agent_policy", [-1, 6]),
     ("order", [0, 1, 2, 3, 4, 5, 6]),
 ]
+# the continuous TD ActorCritic (35) between the unassigned 34 and 36, next to CACLA: under Beta and Gaussian, its two policies, and under Softmax and
+# Random, which it refuses
+GRID_TDAC_CONT = [
+    ("algo", [33, 34, 35, 36]),              # 34, 36: no such algo
+    ("policy", [2, 3, 4, 6]),
+    ("domain", [0, 4]),
+    ("agent_policy", [-1, 6]),
+    ("order", [0, 1, 2, 3, 4, 5, 6]),
+]
 # (grid, fixture, fields set on every configuration)
 GRIDS = ((GRID, FIXTURE, {}), (GRID_AGENTS, AGENTS_FIXTURE, {}), (GRID_AGENTS2, AGENTS2_FIXTURE, {}), (GRID_AGENTS3, AGENTS3_FIXTURE, FIXED_AGENTS3),
          (GRID_BETA, BETA_FIXTURE, {}), (GRID_NAC, NAC_FIXTURE, {}), (GRID_GTD, GTD_FIXTURE, {}),
-         (GRID_GAUSS, GAUSS_FIXTURE, {}), (GRID_CACLA, CACLA_FIXTURE, {}))
+         (GRID_GAUSS, GAUSS_FIXTURE, {}), (GRID_CACLA, CACLA_FIXTURE, {}), (GRID_TDAC_CONT, TDAC_CONT_FIXTURE, {}))
 
 
 def sweep(grid=GRID, fixed=None):
