@@ -26,7 +26,7 @@ constexpr float kTwoPi = 6.2831854820251465f;
 
 __device__ __forceinline__ void gauss_params(float xm, float xs, float& mu, float& sd) {
     mu = xm;
-    sd = softplus_dev(xs) + kGaussMinTol;
+    sd = softplus_rel_dev(xs) + kGaussMinTol;             // (the form that keeps Softplus's relative accuracy: sd's spacing at the floor is 9e-10)
 }
 // Box-Muller's cosine normal of (seed, gid, t, purpose)
 __device__ __forceinline__ float gauss_normal(uint64_t seed, uint32_t gid, uint64_t t, uint32_t purpose) {
@@ -41,21 +41,19 @@ __device__ __forceinline__ float gauss_normal(uint64_t seed, uint32_t gid, uint6
 __device__ __forceinline__ float gauss_sample(uint64_t seed, uint32_t gid, uint64_t t, uint32_t purpose, float mu, float sd) {
     return fmaf(sd, gauss_normal(seed, gid, t, purpose), mu);
 }
+// the density and the score divide by sd, never by Sigma: sd * sd is infinite in f32 from sd = 1.85e19 on, and (d^2 - inf) / (2 inf) a NaN where the
+// result is an ordinary number.  With t = d / sd: density = exp(-t^2 / 2) / (sd sqrt(2 pi)), g_mu = t / sd, and
+// g_Sigma sigma(x_s) = (g_mu (g_mu sigma) - sigma / sd^2) / 2 -- sigma inside the square, so that a tiny sigma meets g_mu before g_mu^2 overflows.
+// The same conditioning as the expressions above (tests/continuous_edges.py gauss_b)
 __device__ __forceinline__ float gauss_pdf(float mu, float sd, float a) {
-    const float var = sd * sd, d = a - mu;
-    return expf(-(d * d) / (2.0f * var)) / sqrtf(kTwoPi * var);
-}
-__device__ __forceinline__ void gauss_score(float mu, float sd, float a, float& g_mu, float& g_var) {
-    const float var = sd * sd, d = a - mu;
-    g_mu = d / var;
-    g_var = (d * d - var) / (2.0f * (var * var));
+    const float t = (a - mu) / sd;
+    return expf(-0.5f * t * t) * ((1.0f / sd) * 0.3989422804014327f);
 }
 // grad_log's two coefficients of phi: (g_mu, g_Sigma sigma(x_s))
 __device__ __forceinline__ void gauss_coef(float xs, float mu, float sd, float a, float& cm, float& cs) {
-    float g_mu, g_var;
-    gauss_score(mu, sd, a, g_mu, g_var);
-    cm = g_mu;
-    cs = g_var * softplus_grad_dev(xs);
+    const float inv = 1.0f / sd, sig = softplus_grad_dev(xs);
+    cm = ((a - mu) / sd) * inv;
+    cs = 0.5f * fmaf(cm, cm * sig, -((inv * inv) * sig));
 }
 
 // the two preferences of state s against learner i's columns (the single-column forms, as k_beta_policy's)

@@ -38,11 +38,24 @@ constexpr int kBetaRounds = 8;
 constexpr float kBetaLo = 5.9604644775390625e-08f;        // 2^-24
 constexpr float kBetaHi = 0.999999940395355224609375f;    // 1 - 2^-24
 
-// Softplus and its gradient (fa/transforms.rs:196-218)
+// Softplus and its gradient (fa/transforms.rs:196-218).  The sum u = 1 + e^x is a multiple of 2^-23, so the literal ln(u) carries an absolute error
+// of 6e-8 for every negative x.  That is nothing beside Beta's + 1 (alpha and beta have that spacing anyway), and softplus_dev stays the literal
+// form: the Beta agents' runs keep their bits.  It is 6e-6 of the Gaussian's sd at its 0.01 floor: gauss_params takes softplus_rel_dev, which
+// keeps Softplus's RELATIVE accuracy.  The rounding error of the sum, r = (u - 1) - e^x, is exact for x <= 0, and
+// ln(1 + e^x) = ln(u - r) = ln(u) - r / u to first order: one v_rcp_f32 (the term is below 6e-8, its own relative error does not matter), where
+// log1pf costs 0.37 us per batch-step (tests/continuous_edges.py, profiles/continuous_edges.md)
 __device__ __forceinline__ float softplus_dev(float x) { return x >= 10.0f ? x : logf(1.0f + exp_dev(x)); }
+__device__ __forceinline__ float softplus_rel_dev(float x) {
+    if (x >= 10.0f) return x;
+    const float e = exp_dev(x), u = 1.0f + e;
+    return fmaf(e - (u - 1.0f), __builtin_amdgcn_rcpf(u), logf(u));
+}
 __device__ __forceinline__ float softplus_grad_dev(float x) {
     if (x >= 10.0f) return 1.0f;
-    const float e = exp_dev(-fabsf(x));                   // the stable logistic: no overflow on either side
+    // the stable logistic: no overflow on either side.  exp_dev is 0 below -87 where e^x is a subnormal: there e^x = e^(x + 40) e^-40, the sum exact
+    const bool far = x < -80.0f;
+    const float e0 = exp_dev(far ? x + 40.0f : -fabsf(x));
+    const float e = far ? e0 * 4.248354255291589e-18f : e0;
     return x >= 0.0f ? 1.0f / (1.0f + e) : e / (1.0f + e);
 }
 // digamma for x >= 1: the recurrence psi(x) = psi(x + 1) - 1 / x up to an argument >= 6 (at most five steps), then the asymptotic series

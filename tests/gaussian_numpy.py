@@ -73,11 +73,18 @@ def sarsa_handle(w, W, phi_s, a, r, phi_n, na, term, gamma, lr):
     return delta, w + lr * delta * psi(W, phi_s, a)
 
 
-def gauss_normal(seed, gid, t, purpose):
-    """z of (seed, global learner id, t, purpose), gid an array: Box-Muller's cosine normal on the whole block at block word purpose + 256"""
+def gauss_normal_parts(seed, gid, t, purpose):
+    """(z, rad) of (seed, global learner id, t, purpose), gid an array: Box-Muller's cosine normal on the whole block at block word purpose + 256,
+    and its radius sqrt(-2 ln u1) beside it (the sample's condition number needs it: tests/continuous_edges.py)"""
     w = bn.philox_block(seed, np.asarray(gid), t, purpose + 256).astype(np.float64)
     u1, u2 = (np.floor(w[..., 0] / 256.0) + 1.0) / 16777216.0, np.floor(w[..., 1] / 256.0) / 16777216.0
-    return np.sqrt(-2.0 * np.log(u1)) * np.cos(float(np.float32(6.2831854820251465)) * u2)
+    rad = np.sqrt(-2.0 * np.log(u1))
+    return rad * np.cos(float(np.float32(6.2831854820251465)) * u2), rad
+
+
+def gauss_normal(seed, gid, t, purpose):
+    """z of (seed, global learner id, t, purpose)"""
+    return gauss_normal_parts(seed, gid, t, purpose)[0]
 
 
 def gauss_sample(seed, gid, t, purpose, mu, sd):
