@@ -423,11 +423,10 @@ __device__ __forceinline__ float expected_value(const float (&q)[A], const float
 // c: the kernel's Common, or a pointer to it that is null where the step reads nothing of it (pw::k_train_reg, see there).
 __device__ __forceinline__ const Common& step_common(const Common& c) { return c; }
 __device__ __forceinline__ const Common& step_common(const Common* c) { return *c; }
-template <int DOMAIN, int ORDER, int ALGO, int POLICY, bool ESCHED, bool STATS, int D, class Pre, int A, int F, bool PK, class C>
+template <int DOMAIN, int ORDER, int ALGO, int POLICY, bool ESCHED, bool STATS, class Bas = FourierReg<DOMAIN, ORDER>, int D, class Pre, int A, int F, bool PK, class C>
 __device__ __forceinline__ auto reg_step(float (&s)[D], int& a, Pre& pre_s, uint32_t& ep, const uint32_t& cap, WBuf<A, F, PK>& w, QCarry& q_s, const AlgoParams& alg,
                                          PolicyParams& pol, const C& c, float& facc_abs, float& facc_r, uint32_t& n_ep, uint32_t& n_trunc) {
     using Dom = Domain<DOMAIN>;
-    using Bas = FourierReg<DOMAIN, ORDER>;
     using Phi = PhiBuf<F, PK>;
     // x = this batch-step's behaviour-policy draw, xin = the agent's own (SARSA): halves of Philox blocks shared by two steps
     return [&](const Phi& phi_s, Phi& phi_n, const U4& x, const U4& xin) {
@@ -442,7 +441,11 @@ __device__ __forceinline__ auto reg_step(float (&s)[D], int& a, Pre& pre_s, uint
         if (term) Dom::reset(ns);              // select, not a branch: phi/Q of s0 take the s' slot
         pre_s = Dom::pre(ns);                  // action-independent part of the NEXT transition, off the critical path
         float q_n[A];
-        { float ph[F]; Bas::project(ns, ph); phi_n.set(ph); }
+        if constexpr (std::is_same<Bas, FourierReg<DOMAIN, ORDER>>::value) {
+            { float ph[F]; Bas::project(ns, ph); phi_n.set(ph); }
+        } else {
+            Bas::project(ns, phi_n.v);         // a basis class of a kernel's own writes the buffer's pairs itself (pw::FourierRegPw)
+        }
         w.q(phi_n, q_n);
         // ---- handle: delta with the PRE-update weights
         static_assert(A <= 3, "ActionMask covers three actions");
@@ -486,7 +489,7 @@ __device__ __forceinline__ auto reg_step(float (&s)[D], int& a, Pre& pre_s, uint
             ep = 0;
             Dom::reset(ns);
             pre_s = Dom::pre(ns);
-            { float ph[F]; Bas::project(ns, ph); phi_n.set(ph); }
+            { float ph[F]; FourierReg<DOMAIN, ORDER>::project(ns, ph); phi_n.set(ph); }      // (the rare path: FourierReg's own projection whatever Bas is)
             w.q(phi_n, q_n);
             na = policy_sample<A, true>(pol, q_n, x);    // the step's one behaviour sample: the same draw (BLK_RESET == BLK_STEP)
         }
