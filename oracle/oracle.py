@@ -92,6 +92,9 @@ def _declare(L):
         g = lambda n: getattr(L, f"{n}_{S}")
         g("orc_domain_step").restype = C.c_int
         g("orc_domain_step").argtypes = [C.c_int, Rp, C.c_int, Rp]
+        g("orc_cmc_step").restype = C.c_int
+        g("orc_cmc_step").argtypes = [Rp, R, Rp, Rp]
+        g("orc_domain_step_raw").argtypes = [C.c_int, Rp, C.c_int, Rp]
         g("orc_domain_is_terminal").restype = C.c_int
         g("orc_domain_is_terminal").argtypes = [C.c_int, Rp]
         g("orc_domain_reset").argtypes = [C.c_int, Rp]
@@ -230,6 +233,24 @@ def domain_step(domain, s, a, prec="f64"):
     r = ct(0)
     term = getattr(lib(), f"orc_domain_step_{prec}")(domain, _ptr(ns, ct), int(a), C.byref(r))
     return ns, float(r.value), bool(term)
+
+
+def cmc_step(s, a, prec="f64"):
+    """ContinuousMountainCar::step from (x, v) with the real action a -> (s', reward, terminal, (x + v', v + dv) before their clips)"""
+    dt, ct = _np_dtype(prec), _ct(prec)
+    ns, raw = np.array(s, dtype=dt).copy(), np.zeros(2, dtype=dt)
+    r = ct(0)
+    term = getattr(lib(), f"orc_cmc_step_{prec}")(_ptr(ns, ct), ct(float(a)), C.byref(r), _ptr(raw, ct))
+    return ns, float(r.value), bool(term), raw
+
+
+def domain_step_raw(domain, s, a, prec="f64"):
+    """the successor of Domain::step before its clips and wraps (MountainCar: (x + v', v + dv); CartPole, Acrobot: the RK4 result)"""
+    dt, ct = _np_dtype(prec), _ct(prec)
+    s = np.array(s, dtype=dt)
+    raw = np.zeros(len(s), dtype=dt)
+    getattr(lib(), f"orc_domain_step_raw_{prec}")(domain, _ptr(s, ct), int(a), _ptr(raw, ct))
+    return raw
 
 
 def domain_reset(domain, prec="f64"):

@@ -38,6 +38,10 @@
  *     QSigma; orc_run_train_sparse_lambda (traces.rs:5-12 over params/sparse.rs:
  *     eligibility traces over one shared tile table, sparse per learner, checked
  *     against a dense numpy restatement in tests/test_oracle_round5.py).
+ *   CRAFTED STATES (tests/state_edges.py): orc_cmc_step restates ContinuousMountainCar
+ *     (mountain_car/continuous.rs; map_onto recalled as a clip), orc_domain_step_raw gives
+ *     a successor before its clips and wraps; the f32d sincospi01 selects its quadrant on
+ *     q & 3, as the device's bit logic does, so scaled states outside [0, 1] agree too.
  * ============================================================================
  */
 #include <math.h>

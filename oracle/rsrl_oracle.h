@@ -89,6 +89,8 @@ void orc_agent_init(orc_agent* ag, int domain, int basis_kind, int order, int n_
     void  orc_domain_reset_##S(int domain, R* s);                                                       \
     int   orc_domain_is_terminal_##S(int domain, const R* s);                                           \
     int   orc_domain_step_##S(int domain, R* s, int a, R* reward);                                      \
+    int   orc_cmc_step_##S(R* s, R a, R* reward, R* raw);                                               \
+    void  orc_domain_step_raw_##S(int domain, const R* s, int a, R* raw);                               \
     void  orc_fourier_project_##S(int order, int D, const R* lo, const R* hi, const R* s, R* phi);      \
     void  orc_q_evaluate_##S(const orc_basis* b, const R* W, int A, const R* s, R* q);                  \
     R     orc_q_evaluate_index_##S(const orc_basis* b, const R* W, int A, const R* s, int a);           \

@@ -41,9 +41,9 @@ static inline void FN(sincospi01_dev)(R x, R* sn, R* cs) {       /* sin(pi x), c
     pc = fmaf(pc, u, 4.058707237243652f);
     pc = fmaf(pc, u, -4.934802055358887f);
     c = fmaf(pc, u, 1.0f);
-    qi = (int)q;
-    *sn = (qi == 1) ? c : ((qi == 2) ? -s : s);
-    *cs = (qi == 1) ? -s : ((qi == 2) ? -c : c);
+    qi = ((int)q) & 3;                                              /* 0, 1, 2 on [0, 1]; the device's select is periodic in q, so is this one */
+    *sn = (qi == 0) ? s : ((qi == 1) ? c : ((qi == 2) ? -s : -c));
+    *cs = (qi == 0) ? c : ((qi == 1) ? -s : ((qi == 2) ? -c : s));
 }
 static inline void FN(sincos_cw_dev)(R x, R* sn, R* cs) {        /* sin(x), cos(x), |x| <= 100 */
     const R n = rintf(x * 0.6366197466850281f);
@@ -243,6 +243,42 @@ int FN(orc_domain_step)(int domain, R* s, int a, R* reward) {
         *reward = term ? (R)0.0 : (R)-1.0; break;
     }
     return term;
+}
+
+/* ContinuousMountainCar::step           mountain_car/continuous.rs:41-48, 64-75; constants :8-22.  MountainCar's update with FORCE_CAR = 0.0015
+ * and the action ONE real number, brought into [-1, 1] by action_space.map_onto (the `spaces` crate, not in the reference tree: recalled as a
+ * clip, as on the device -- rsrl_amd/csrc/device_core.hpp Domain<4>).  raw (when not NULL) receives x + v' and v + dv before their clips. */
+int FN(orc_cmc_step)(R* s, R a, R* reward, R* raw) {
+    const R X_MIN = (R)-1.2, X_MAX = (R)0.6, V_MIN = (R)-0.07, V_MAX = (R)0.07;
+    const R FORCE_G = (R)-0.0025, FORCE_CAR = (R)0.0015, HILL_FREQ = (R)3.0;
+    const R act = FN(clip_)((R)-1.0, a, (R)1.0);
+    R x = s[0], v = s[1], xr, vr;
+    int term;
+    R dv = FORCE_CAR * act + FORCE_G * FN(cos_)(HILL_FREQ * x);
+    vr = v + dv;
+    v = FN(clip_)(V_MIN, vr, V_MAX);
+    xr = x + v;
+    x = FN(clip_)(X_MIN, xr, X_MAX);
+    s[0] = x; s[1] = v;
+    if (raw) { raw[0] = xr; raw[1] = vr; }
+    term = x >= X_MAX;
+    *reward = term ? (R)0.0 : (R)-1.0;
+    return term;
+}
+/* The successor of Domain::step BEFORE its clips and wraps (tests/state_edges.py: how far a row is from a clip, a wrap or a terminal
+ * threshold): MountainCar (x + v', v + dv) with v' the clipped velocity; CartPole and Acrobot the RK4 result. */
+void FN(orc_domain_step_raw)(int domain, const R* s, int a, R* raw) {
+    int i;
+    if (domain == ORC_MOUNTAIN_CAR) {
+        const R act = (R)(a - 1);
+        const R dv = (R)0.001 * act + (R)-0.0025 * FN(cos_)((R)3.0 * s[0]);
+        raw[1] = s[1] + dv;
+        raw[0] = s[0] + FN(clip_)((R)-0.07, raw[1], (R)0.07);
+        return;
+    }
+    for (i = 0; i < 4; i++) raw[i] = s[i];
+    if (domain == ORC_CART_POLE) FN(rk4)(FN(cp_grad), (a == 0) ? (R)-10.0 : (R)10.0, raw, (R)0.02);
+    else FN(rk4)(FN(ac_grad), (R)(a - 1), raw, (R)0.2);
 }
 
 /* ------------------------------------------------------------------ */

@@ -100,7 +100,9 @@ constexpr double kPi = 3.14159265358979323846;
 // ---------------------------------------------------------------------------------------
 // Branch-free fp32 trigonometry (no large-argument slow path => one basic block, so the
 // scheduler can interleave it with the Philox / FMA chains of a lone wave per SIMD).
-// Measured against f64: |err| <= 9e-8 (<= 1.7 ulp) on the stated ranges.
+// Against f64 on EVERY fp32 input of the stated ranges (oracle/check_devpoly.c, profiles/state_edges.md): |err| <= 9e-8 for both; in units
+// of the result's last place sincospi01 stays <= 1.7 ulp, sincos_cw does not next to the zeros of sin and cos (5.8 ulp at x = fl(3 pi)).
+// Outside them, as far as the ABI admits a state: sincospi01 unchanged on [-1000, 1001], sincos_cw |err| <= 9e-8 up to |x| = 2^17.
 // ---------------------------------------------------------------------------------------
 // (sin, cos) of r + q*pi/2 from (s, c) = (sin r, cos r), q in 0..3:  (s, c), (c, -s), (-s, -c), (-c, s).
 // Written as one swap (two selects) and two sign-bit xors: as a ternary chain the compiler turned it into exec-mask
@@ -220,7 +222,7 @@ __device__ __forceinline__ float lane_pick3(int lane, float x0, float x1, float 
 // exp(x) for the softmax policy: n = rint(x log2 e), two-term Cody-Waite reduction by ln 2, degree-5 polynomial on top of
 // 1 + r, scaled by 2^n (v_ldexp_f32).  Below -87 the result is 0 (no denormals), above 88.5 +inf.  Written out (instead
 // of expf -> v_exp_f32, whose bits are unspecified) so that the test oracle can restate it and compare the softmax paths
-// bitwise; <= 1.5 ulp.
+// bitwise; <= 1.5 ulp (1.02 over every input of [-87, 88.5]).
 __device__ __forceinline__ float exp_dev(float x) {
     const float n = rintf(x * 1.4426950216293335f);
     float r = fmaf(n, -0.693145751953125f, x);

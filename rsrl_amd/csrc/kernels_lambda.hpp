@@ -87,7 +87,7 @@ __global__ __launch_bounds__(kBlock) void k_train_lambda(Common c, LambdaParams 
                 float ind[A];
 #pragma unroll
                 for (int b = 0; b < A; ++b) ind[b] = (a == b) ? 1.0f : 0.0f;
-                z.decay_add(rate_eff, ind, phi);
+                z.template decay_add<true>(rate_eff, ind, phi);
                 if (lp.trace == TRACE_SATURATE) z.clip(-1.0f, 1.0f);
             }
             float ns[D];

@@ -224,11 +224,18 @@ template <int A, int F, bool PK> struct WBuf {
     }
     // trace decay + gradient: z[b] = fma(rate, z[b], ind[b] * phi), ind in {0, 1} (the product is exact; a multiply
     // instead of a per-element select: v_cndmask issues at half the FMA rate at one wave per SIMD)
+    // PZ: the gradient's zeros are made +0 (0 * phi is -0 for a negative phi, and with a zero rate over a negative z -- the step after a
+    // terminal -- (-0) + (-0) left -0 in the trace where the reference's reset trace, the memory families and the oracle have +0)
+    template <bool PZ = false>
     __device__ __forceinline__ void decay_add(float rate, const float (&ind)[A], const PhiBuf<F, PK>& phi) {
 #pragma unroll
         for (int b = 0; b < A; ++b)
 #pragma unroll
-            for (int f = 0; f < F; ++f) w[b][f] = fmaf(rate, w[b][f], ind[b] * phi.v[f]);
+            for (int f = 0; f < F; ++f) {
+                float g = ind[b] * phi.v[f];
+                if constexpr (PZ) g = g + 0.0f;
+                w[b][f] = fmaf(rate, w[b][f], g);
+            }
     }
     __device__ __forceinline__ void clip(float lo, float hi) {
 #pragma unroll
@@ -257,13 +264,18 @@ template <int A, int F> struct WBuf<A, F, true> {
 #pragma unroll
             for (int j = 0; j < F / 2; ++j) w[b][j] = __builtin_elementwise_fma(s2, o.w[b][j], w[b][j]);
     }
+    template <bool PZ = false>
     __device__ __forceinline__ void decay_add(float rate, const float (&ind)[A], const PhiBuf<F, true>& phi) {
         const f2 r2 = {rate, rate};
 #pragma unroll
         for (int b = 0; b < A; ++b) {
             const f2 i2 = {ind[b], ind[b]};
 #pragma unroll
-            for (int j = 0; j < F / 2; ++j) w[b][j] = __builtin_elementwise_fma(r2, w[b][j], i2 * phi.v[j]);
+            for (int j = 0; j < F / 2; ++j) {
+                f2 g = i2 * phi.v[j];
+                if constexpr (PZ) g = g + f2{0.0f, 0.0f};
+                w[b][j] = __builtin_elementwise_fma(r2, w[b][j], g);
+            }
         }
     }
     __device__ __forceinline__ void clip(float lo, float hi) {

@@ -139,6 +139,53 @@ def test_constant_division_is_the_ieee_quotient(orc, tmp_path):
     assert bad.returncode == 1 and "mismatches" in bad.stdout and " 0 mismatches" not in bad.stdout
 
 
+def test_device_polynomials_on_every_fp32_input(tmp_path):
+    # The three hand-written polynomials of rsrl_amd/csrc/device_core.hpp (sincospi01, sincos_cw, exp_dev), in the restatement the f32d oracle compares
+    # the device with bit for bit, against f64 on EVERY fp32 input of their stated ranges (oracle/check_devpoly.c; profiles/state_edges.md has the
+    # figures).  Exhaustive and deterministic: no margin.  The header's claims: |err| <= 9e-8 for both trigonometric functions, <= 1.7 ulp for
+    # sincospi01, <= 1.5 ulp for exp_dev.  Its "<= 1.7 ulp" for sincos_cw did NOT hold in units of the result's last place: next to the zeros of sin and
+    # cos the absolute error stays below 8e-8 but the result is small -- 5.79 ulp at x = fl(3 pi) (sin) and fl(3 pi / 2) (cos).  The comment and DESIGN
+    # now say so, and the true maximum is asserted.
+    import os
+    import subprocess
+    here = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle")
+    exe = str(tmp_path / "check_devpoly")
+    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-pthread", "-o", exe,
+                           os.path.join(here, "check_devpoly.c"), "-lm"])
+    n = min(16, len(os.sched_getaffinity(0)))
+
+    def sweep(fn, lo, hi):
+        out = subprocess.run([exe, fn, str(n), repr(lo), repr(hi)], capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stdout + out.stderr
+        print(out.stdout.strip())
+        f = dict(kv.split("=") for kv in out.stdout.split())
+        return {k: (int(v, 16) if k.endswith("_at") or k == "rule_first" else int(v) if k in ("inputs", "rule_bad") else v if k == "fn" else float(v)) for k, v in f.items()}
+
+    r = sweep("sincospi", 0.0, 1.0)
+    assert r["inputs"] == 0x3f800000 + 2                                               # every float of [0, 1], and -0.0
+    assert r["sin_abs"] <= 9e-8 and r["cos_abs"] <= 9e-8 and r["sin_ulp"] <= 1.7 and r["cos_ulp"] <= 1.7, r
+    r = sweep("sincos", -100.0, 100.0)
+    assert r["inputs"] == 2 * (0x42c80000 + 1)
+    assert r["sin_abs"] <= 9e-8 and r["cos_abs"] <= 9e-8, r
+    assert r["sin_ulp"] <= 5.7932 and r["cos_ulp"] <= 5.7932, r                        # measured: 5.793176, both
+    assert r["sin_ulp"] > 1.7 and (r["sin_ulp_at"] & 0x7fffffff) == 0x4116cbe4 and (r["cos_ulp_at"] & 0x7fffffff) == 0x4096cbe4, r      # fl(3 pi), fl(3 pi / 2)
+    r = sweep("exp", -87.0, 88.5)
+    assert r["inputs"] == 1 << 32 and r["rule_bad"] == 0, r                            # exactly 0 below -87, +inf above 88.5 (both infinities too), NaN for NaN
+    assert r["ulp"] <= 1.5, r                                                          # measured 1.012829
+    # Beyond the stated ranges: what rsrl_hip_set_states admits (abi_ctx.hip state_limits: every component within 1000 widths of its bounds).  There
+    # was no claim; these are the measured figures, held from now on.  sincospi01 takes s~ = (s - lo) / (hi - lo), so [-1000, 1001]: x - q / 2 stays
+    # exact and the select is periodic in q, the in-range figures hold unchanged.  sincos_cw takes MountainCar's 3x (|3x| <= 3 (1.2 + 1800) = 5404),
+    # CartPole's theta and Acrobot's theta2, theta1 + theta2 - pi / 2, theta1 - pi / 2 at the RK4 stage points: stage 1 is the state (CartPole 2001 pi /
+    # 15 = 419; Acrobot 2 * 2001 pi + pi / 2 = 12 575), stage 2 adds dt / 2 times the admitted velocities (0.01 * 4002 = 40; 0.1 * 13 pi * 2001 =
+    # 8 172: 20 747 in all); stages 3 and 4 move by the earlier stages' accelerations, which the admission does not bound in closed form (theta'^2
+    # terms).  The sweep goes to 2^17 = 131 072, six times the stage-2 bound; the two-term reduction keeps the absolute error there (the third term
+    # of pi / 2 it leaves out is 1.7e-15 per quadrant), while the error in units of the RESULT's last place is unbounded next to the zeros (32 281).
+    r = sweep("sincospi", -1000.0, 1001.0)
+    assert r["sin_abs"] <= 9e-8 and r["cos_abs"] <= 9e-8 and r["sin_ulp"] <= 1.7 and r["cos_ulp"] <= 1.7, r
+    r = sweep("sincos", -131072.0, 131072.0)
+    assert r["sin_abs"] <= 9e-8 and r["cos_abs"] <= 9e-8, r                            # measured 8.12e-8, 8.11e-8
+
+
 # The independent leg of the chain for the round-4 families: the device is compared BITWISE with the oracle's f32d
 # instantiation (tests/test_gpu_round4.py), which restates the device's own polynomials and evaluation order -- so f32d itself has to be
 # held to the reference's arithmetic: the f64 run of the same agent, same seeds, within a tolerance.
