@@ -169,7 +169,7 @@ static int check_reg_only(const rsrl_hip_config& cfg, const AlgoRow& a, bool sto
 // (state dimension, action count) of MountainCar, CartPole, Acrobot, HIVTreatment, ContinuousMountainCar (0: the action set is not enumerable)
 static const int kDomainShape[5][2] = {{2, 3}, {4, 2}, {4, 3}, {6, 4}, {2, 0}};
 
-// ContinuousMountainCar and the continuous policies (train_tdac_beta.hip, train_nac_beta.hip, train_nac_gauss.hip, train_cacla.hip, train_tdac_cont.hip):
+// ContinuousMountainCar and the continuous policies (cont_policy.hpp; train_tdac_beta.hip, train_nac.hip, train_cont.hip):
 // the domain exists for them only and they for it, Beta under the iLSTD ActorCritic, NAC and the continuous TD ActorCritic, Gaussian under NAC, CACLA
 // and the continuous TD ActorCritic -- and NAC, CACLA and the continuous TD ActorCritic for them only
 static int check_continuous(const rsrl_hip_config& cfg, const AlgoRow& a, bool storage) {
@@ -547,10 +547,8 @@ int rsrl_hip_reset(rsrl_hip_ctx* c) {
     if (c->family == AgentFamily::ReinforceReg) { launch_reinforce_restart(c->stream, make_reinforce(c), c->cfg.n_envs, (int64_t)c->F * c->A, nullptr); KCHECK(); }
     const Common k = make_policy_common(c);              // the initial policy.sample (ActorCritic: the actor's theta)
     const BasisGeom g = make_geom(c);
-    if (is_gaussian(c)) {      // (NAC, CACLA and the continuous TD ActorCritic over the Gaussian policy: as the two below)
-        if (!launch_gauss_reset(c->cfg.order, c->stream, k, c->Z, c->t, c->action_f)) return NO_MODEL(c);
-    } else if (c->family == AgentFamily::TdAcBetaReg || c->family == AgentFamily::NacBetaReg || c->family == AgentFamily::TdAcBetaTdReg) {      // (the agents' state is untouched: the initial sample reads the policy's columns)
-        if (!launch_beta_reset(c->cfg.order, c->stream, k, c->Z, c->t, c->action_f)) return NO_MODEL(c);
+    if (is_continuous(c)) {      // (the agents' state is untouched: the initial sample reads the policy's columns)
+        if (!launch_cont_reset(c->cfg.order, cont_policy(c), c->stream, k, c->Z, c->t, c->action_f)) return NO_MODEL(c);
     } else if (c->family == AgentFamily::Hiv) {
         launch_hiv_reset(c->stream, k, g, c->hiv_y, c->t);
     } else if (is_v_only(c->cfg.algo)) {       // (the LSTD agents' state is untouched: the weights are not reset either; GradientMC's records empty with ep_step = 0)

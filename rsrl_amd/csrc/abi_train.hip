@@ -430,17 +430,13 @@ int launch_agent(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, uint64_t 
         ok = !io && launch_tdac_beta(cf.order, c->stream, k, make_tdac_beta(c), t, chunk, d_stats, nullptr);
         break;
     case AgentFamily::NacBetaReg:        // (io: as above)
-        ok = !io && launch_nac_beta(cf.order, c->stream, k, make_nac_beta(c), t, chunk, d_stats, nullptr);
-        break;
-    case AgentFamily::NacGaussReg:       // (io: as above)
-        ok = !io && launch_nac_gauss(cf.order, c->stream, k, make_nac_beta(c), t, chunk, d_stats, nullptr);
+    case AgentFamily::NacGaussReg:
+        ok = !io && launch_nac(cf.order, cont_policy(c), c->stream, k, make_cont(c), nac_period(c), t, chunk, d_stats, nullptr);
         break;
     case AgentFamily::CaclaGaussReg:     // (io: as above)
-        ok = !io && launch_cacla(cf.order, c->stream, k, make_cacla(c), t, chunk, d_stats, nullptr);
-        break;
-    case AgentFamily::TdAcGaussReg:      // (io: as above)
+    case AgentFamily::TdAcGaussReg:
     case AgentFamily::TdAcBetaTdReg:
-        ok = !io && launch_tdac_cont(cf.order, cont_policy(c), c->stream, k, make_tdac_cont(c), t, chunk, d_stats, nullptr);
+        ok = !io && launch_td0_cont(cf.order, is_cacla(cf.algo), cont_policy(c), c->stream, k, make_cont(c), t, chunk, d_stats, nullptr);
         break;
     case AgentFamily::GtdReg: ok = launch_gtd(cf.domain, cf.order, cf.algo == RSRL_TDC, grid, block, c->stream, k, make_gtd(c), t, chunk, d_stats, io); break;
     default: ok = false; break;      // (the shared-W families: enqueue_shared_step)
@@ -614,9 +610,7 @@ static int rollout_impl(rsrl_hip_ctx* c, int64_t step_limit, int64_t M, uint32_t
         // (NAC: the loop's mapping, Domain::rollout(|s| 2 * policy.mode(s) - 1), nac_beta.rs:81-82)
         // (the Gaussian policy: Domain::rollout(|s| policy.mode(s)), nac.rs:81 -- no mapping)
         // (the continuous TD ActorCritic: each policy's loop convention, 2 mode - 1 under Beta as NAC's)
-        if (!(is_gaussian(c)      ? launch_gauss_rollout_mode(c->cfg.order, c->stream, make_common(c), c->Z, step_limit, d_n, d_total)
-              : maps_beta_action(c) ? launch_nac_rollout_mode(c->cfg.order, c->stream, make_common(c), c->Z, step_limit, d_n, d_total)
-                                  : launch_beta_rollout_mode(c->cfg.order, c->stream, make_common(c), c->Z, step_limit, d_n, d_total))) return NO_MODEL(c);
+        if (!launch_cont_rollout_mode(c->cfg.order, cont_policy(c), maps_beta_action(c), c->stream, make_common(c), c->Z, step_limit, d_n, d_total)) return NO_MODEL(c);
         KCHECK();
         return f.finish();
     }

@@ -428,7 +428,7 @@ int rsrl_hip_handle(rsrl_hip_ctx* c, const float* from_states, const int32_t* ac
     return f.finish();
 }
 
-// ---- f32 actions: the twins of the calls above for a continuous ctx (ContinuousMountainCar with the Beta policy; kernels_tdac_beta.hpp)
+// ---- f32 actions: the twins of the calls above for a continuous ctx (ContinuousMountainCar; cont_policy.hpp)
 int rsrl_hip_domain_step_f32(rsrl_hip_ctx* c, const float* actions, float* from_states, float* next_states, float* rewards, uint8_t* terminal) {
     CHECK_CTX(c); FLUSH(c);
     NEEDS_F32_ACTIONS(c, "rsrl_hip_domain_step");
@@ -441,8 +441,7 @@ int rsrl_hip_domain_step_f32(rsrl_hip_ctx* c, const float* actions, float* from_
     const Common k = make_common(c);
     // (NAC and the continuous TD ActorCritic with Beta: explicit actions are the domain's, the pending ones the agent's -- stepped on through the loop's
     // 2a - 1; the Gaussian loops map nothing)
-    if (maps_beta_action(c)) launch_nac_domain_step(c->stream, k, s.act, c->action_f, s.from, s.next, s.rew, s.term);
-    else launch_cmc_domain_step(c->stream, k, s.act, c->action_f, s.from, s.next, s.rew, s.term);
+    launch_cmc_domain_step(c->stream, k, s.act, c->action_f, maps_beta_action(c), s.from, s.next, s.rew, s.term);
     KCHECK();
     return f.finish();
 }
@@ -460,18 +459,18 @@ int rsrl_hip_handle_f32(rsrl_hip_ctx* c, const float* from_states, const float* 
     TransitionsF32 io;
     TRY(stage_transitions(f, from_states, actions, rewards, to_states, terminal, M, td_error_out, &io));
     const Common k = make_common(c);
-    if (!(is_tdac_cont(c->cfg.algo) ? launch_tdac_cont(c->cfg.order, cont_policy(c), c->stream, k, make_tdac_cont(c), c->t, 1, nullptr, &io)      // eval.handle, then ActorCritic::handle
-          : is_cacla(c->cfg.algo) ? launch_cacla(c->cfg.order, c->stream, k, make_cacla(c), c->t, 1, nullptr, &io)          // eval.handle, then CACLA::handle
-          : is_gaussian(c)    ? launch_nac_gauss(c->cfg.order, c->stream, k, make_nac_beta(c), c->t, 1, nullptr, &io)     // critic.handle: SARSA over SCB
-          : is_nac(c->cfg.algo) ? launch_nac_beta(c->cfg.order, c->stream, k, make_nac_beta(c), c->t, 1, nullptr, &io)
-                              : launch_tdac_beta(c->cfg.order, c->stream, k, make_tdac_beta(c), c->t, 1, nullptr, &io))) return NO_MODEL(c);
+    const int order = c->cfg.order;
+    if (!(is_nac(c->cfg.algo)           ? launch_nac(order, cont_policy(c), c->stream, k, make_cont(c), nac_period(c), c->t, 1, nullptr, &io)      // critic.handle: SARSA over SCB
+          : has_lstd_state(c)           ? launch_tdac_beta(order, c->stream, k, make_tdac_beta(c), c->t, 1, nullptr, &io)
+                                        : launch_td0_cont(order, is_cacla(c->cfg.algo), cont_policy(c), c->stream, k, make_cont(c), c->t, 1, nullptr, &io)))      // eval.handle, then the agent's
+        return NO_MODEL(c);
     KCHECK();
     c->q_valid = false;
     c->t += 1;          // one handle call = one batch-step, as rsrl_hip_handle
     return f.finish();
 }
 
-// the policy side on explicit states (or, for the sample, the ctx's own envs): one launch of k_beta_policy, or of k_gauss_policy
+// the policy side on explicit states (or, for the sample, the ctx's own envs): one launch of k_cont_policy
 static int beta_op(rsrl_hip_ctx* c, int op, const float* states, int64_t M, uint64_t t, uint32_t purpose, const float* act_in, float* out0, float* out1, float* keep) {
     CallFrame f(c);
     TRY(check_host_actions_f32(f, act_in, (size_t)M, false));      // (rsrl_hip_policy_pdf's actions, the one caller with any)
@@ -482,8 +481,7 @@ static int beta_op(rsrl_hip_ctx* c, int op, const float* states, int64_t M, uint
     TRY(f.out(out0, (size_t)M, &d_out0));
     TRY(f.out(out1, (size_t)M, &d_out1));
     const Common k = make_common(c);
-    if (!(is_gaussian(c) ? launch_gauss_policy(c->cfg.order, c->stream, k, c->Z, op, d_states, M, t, purpose, d_act, d_out0, d_out1, keep)
-                         : launch_beta_policy(c->cfg.order, c->stream, k, c->Z, op, d_states, M, t, purpose, d_act, d_out0, d_out1, keep))) return NO_MODEL(c);
+    if (!launch_cont_policy(c->cfg.order, cont_policy(c), c->stream, k, c->Z, op, d_states, M, t, purpose, d_act, d_out0, d_out1, keep)) return NO_MODEL(c);
     KCHECK();
     return f.finish();
 }
@@ -532,7 +530,7 @@ int rsrl_hip_policy_pdf(rsrl_hip_ctx* c, const float* states, const float* actio
     return beta_op(c, BETA_OP_PDF, states, M, 0, 0, actions, out, nullptr, nullptr);
 }
 
-// ---- NAC (kernels_nac_beta.hpp): the critic's Function<(S, A)> and the actor's update
+// ---- NAC (kernels_cont.hpp): the critic's Function<(S, A)> and the actor's update
 static const char* const kNoNac = "only NAC (RSRL_NAC) has a critic over the stable compatible basis and an actor update of its own";
 int rsrl_hip_q_evaluate_f32(rsrl_hip_ctx* c, const float* states, const float* actions, int64_t M, float* q_out) {
     CHECK_CTX(c);
@@ -547,8 +545,7 @@ int rsrl_hip_q_evaluate_f32(rsrl_hip_ctx* c, const float* states, const float* a
     TRY(f.in(states, (size_t)c->D * M, &d_states));
     TRY(f.in(actions, (size_t)M, &d_act));
     TRY(f.out(q_out, (size_t)M, &d_q));
-    if (!(is_gaussian(c) ? launch_nac_gauss_q(c->cfg.order, c->stream, make_common(c), make_nac_beta(c), d_states, d_act, M, d_q)
-                         : launch_nac_q(c->cfg.order, c->stream, make_common(c), make_nac_beta(c), d_states, d_act, M, d_q))) return NO_MODEL(c);
+    if (!launch_nac_q(c->cfg.order, cont_policy(c), c->stream, make_common(c), make_cont(c), d_states, d_act, M, d_q)) return NO_MODEL(c);
     KCHECK();
     return f.finish();
 }
@@ -563,7 +560,7 @@ int rsrl_hip_nac_update(rsrl_hip_ctx* c, const uint8_t* mask, float* norm_out) {
     TRY(f.in(mask, N, &d_mask));
     TRY(f.out(norm_out, N, &d_norm));
     // (k_nac_update reads w's first 2F rows and the two columns, whatever the policy: the Gaussian ctx runs it too)
-    if (!launch_nac_update(c->cfg.order, c->stream, make_common(c), make_nac_beta(c), d_mask, d_norm)) return NO_MODEL(c);
+    if (!launch_nac_update(c->cfg.order, c->stream, make_common(c), make_cont(c), d_mask, d_norm)) return NO_MODEL(c);
     KCHECK();
     c->q_valid = false;
     return f.finish();

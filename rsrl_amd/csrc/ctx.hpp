@@ -218,15 +218,15 @@ enum class AgentFamily : uint8_t {
                           // lstd_mu (b) / lstd_z / lstd_sing, the open episodes in rec_s / rec_r
     TdAcBetaReg,          // ActorCritic with the iLSTD critic and the Beta policy on ContinuousMountainCar, Fourier orders 1-5: k_train_tdac_beta
                           // (train_tdac_beta.hip); iLSTD's f64 state as LstdReg's, the policy's two columns in Z, f32 actions in action_f
-    NacBetaReg,           // NAC with the Beta policy and the SCB SARSA critic on ContinuousMountainCar, Fourier orders 1-5: k_train_nac_beta (train_nac_beta.hip),
+    NacBetaReg,           // NAC with the Beta policy and the SCB SARSA critic on ContinuousMountainCar, Fourier orders 1-5: k_train_nac<ORDER, Beta>, reported as k_train_nac_beta (train_nac.hip),
                           // one thread per learner; the critic's w in W (3F rows, one column), the policy's two columns in Z, f32 actions in action_f
     GtdReg,               // GTD2 / TDC, same configurations as LstdReg: k_train_gtd (train_gtd.hip); theta in W (one column), the second column w in Z
-    NacGaussReg,          // NAC with the Gaussian policy, NacBetaReg's configurations and layout: k_train_nac_gauss (train_nac_gauss.hip); the policy's columns
+    NacGaussReg,          // NAC with the Gaussian policy, NacBetaReg's configurations and layout: k_train_nac<ORDER, Gaussian>, reported as k_train_nac_gauss (train_nac.hip); the policy's columns
                           // (the mean's, the stddev's) in Z
-    CaclaGaussReg,        // CACLA over the Gaussian policy with a TD(0) critic, NacBetaReg's configurations: k_train_cacla (train_cacla.hip); the V learner's w
+    CaclaGaussReg,        // CACLA over the Gaussian policy with a TD(0) critic, NacBetaReg's configurations: k_train_td0_cont<ORDER, CaclaRule>, reported as k_train_cacla (train_cont.hip); the V learner's w
                           // in W (one column, F rows), the policy's columns in Z, f32 actions in action_f
     TdAcGaussReg,         // ActorCritic::tdac with a TD(0) critic over the Gaussian policy, CaclaGaussReg's configurations and layout: k_train_tdac_cont
-                          // (train_tdac_cont.hip)
+                          // (train_cont.hip)
     TdAcBetaTdReg,        // ... over the Beta policy (the columns alpha's and beta's; the loop hands the domain 2a - 1): k_train_tdac_cont.  (TdAcBetaReg is
                           // the iLSTD critic's family)
 };
@@ -240,6 +240,8 @@ enum : uint8_t { kWave = 1, kCarriesQ = 2, kPolicyW = 4, kVCritic = 8, kLstd = 1
 struct FamilyRow {
     AgentFamily family;      // (its own index: checked below)
     const char* kernel;      // the driver-loop kernel timing_read names (WaveControl, RegStep: refined by train_kernel_name)
+                             // A LABEL, not always a symbol: k_train_cacla, k_train_tdac_cont, k_train_nac_gauss and k_train_nac_beta are the agents' names for
+                             // k_train_td0_cont<ORDER, Rule> and k_train_nac<ORDER, P> (kernels_cont.hpp), which is what a profiler's trace shows
     int depth;               // batch-steps per launch while config.steps_per_launch == 0 (the shared families: not read, they step one per launch)
     Slots slots;
     Handle handle;
@@ -467,7 +469,7 @@ static inline bool is_v_actor_critic(const rsrl_hip_ctx* c) { return family_row(
 static inline int aux_cols(const rsrl_hip_ctx* c) { return kAlgo[c->cfg.algo].aux == Aux::Policy ? c->Ap : c->Aw; }
 // a ctx whose actions are f32 values, not indices (ContinuousMountainCar): the *_f32 entry points are its own, their int32 twins ESTATE
 static inline bool is_continuous(const rsrl_hip_ctx* c) { return c->cfg.domain == RSRL_CONTINUOUS_MOUNTAIN_CAR; }
-// the continuous ctx's policy is the Gaussian (kernels_gaussian.hpp), not Beta: its own kernels, actions any finite f32, no 2a - 1 in NAC's loop (nor in CACLA's)
+// the continuous ctx's policy is the Gaussian (cont_policy.hpp), not Beta: actions any finite f32, no 2a - 1 in NAC's loop (nor in CACLA's)
 static inline bool is_gaussian(const rsrl_hip_ctx* c) { return c->cfg.policy == RSRL_GAUSSIAN; }
 // the Beta loops that hand the domain 2a - 1 for the agent's action a (nac_beta.rs:63; NAC and the continuous TD ActorCritic): the pending-action
 // domain step and the mode rollout apply it.  (The iLSTD ActorCritic's loop, tdac_beta.rs, hands the domain the action itself)
@@ -513,23 +515,13 @@ static inline TdacLstdState make_tdac_lstd(const rsrl_hip_ctx* c) {
     return ts;
 }
 
-static inline NacBetaState make_nac_beta(const rsrl_hip_ctx* c) {
-    NacBetaState ns;
-    ns.pol = c->Z; ns.action = c->action_f; ns.period = (uint32_t)c->cfg.n_steps;
-    return ns;
-}
-
-static inline CaclaState make_cacla(const rsrl_hip_ctx* c) {
-    CaclaState cs;
+// the thread-per-learner continuous agents (kernels_cont.hpp): the policy's columns and the pending f32 actions; NAC's actor period travels beside it
+static inline ContState make_cont(const rsrl_hip_ctx* c) {
+    ContState cs;
     cs.pol = c->Z; cs.action = c->action_f;
     return cs;
 }
-
-static inline TdacContState make_tdac_cont(const rsrl_hip_ctx* c) {
-    TdacContState ts;
-    ts.pol = c->Z; ts.action = c->action_f;
-    return ts;
-}
+static inline uint32_t nac_period(const rsrl_hip_ctx* c) { return (uint32_t)c->cfg.n_steps; }
 static inline ContPolicy cont_policy(const rsrl_hip_ctx* c) { return c->cfg.policy == RSRL_GAUSSIAN ? ContPolicy::Gaussian : ContPolicy::Beta; }
 
 static inline TdacBetaState make_tdac_beta(const rsrl_hip_ctx* c) {

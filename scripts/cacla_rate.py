@@ -16,7 +16,6 @@ One JSON line per figure set and per row; --out writes the markdown tables that 
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -25,6 +24,7 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 import rsrl_amd  # noqa: E402
 from tests import cacla_numpy as cn  # noqa: E402
+from rate_regions import alternate  # noqa: E402
 
 CMC = rsrl_amd.CONTINUOUS_MOUNTAIN_CAR
 
@@ -39,49 +39,6 @@ def measure(order):
     fig["open_per_round"] = [int(g.sum()) for g in arr["gates"]]
     fig["max_abs_column"] = float(np.max(np.abs(arr["want_cols"][arr["opened"]])))
     return fig
-
-
-def region(c, steps):
-    """us per batch-step of one timed train(steps) (device events around the launches: rsrl_hip_timing_read)"""
-    c.sync()
-    c.timing_enable(True)
-    c.train(steps, want_stats=False)
-    ms, launches, name = c.timing_read()
-    return ms * 1e3 / steps, launches, name
-
-
-def alternate(agents, a):
-    """agents: [(label, Context keywords)] -> one row per agent, their timed regions alternating (a drift of the machine falls on all)"""
-    ctxs = [rsrl_amd.Context(**{k: v for k, v in kw.items() if k != "v0"}) for _, kw in agents]
-    rows = []
-    try:
-        for c, (_, kw) in zip(ctxs, agents):
-            if kw.get("v0"):                            # V = v0 everywhere: the constant feature is the last one
-                w = np.zeros((c.F, 1), dtype=np.float32)
-                w[c.F - 1] = kw["v0"]
-                c.set_weights_all(w)
-            c.reset()
-            c.train(a.warmup, want_stats=False)
-            c.sync()
-        us, meta = [[] for _ in agents], [None] * len(agents)
-        for _ in range(a.regions):
-            for j, c in enumerate(ctxs):
-                u, launches, name = region(c, a.steps)
-                us[j].append(u)
-                meta[j] = (launches, name)
-        base = statistics.median(us[-1])
-        for j, (label, kw) in enumerate(agents):
-            med = statistics.median(us[j])
-            dead = sum(not (np.isfinite(ctxs[j].get_weights(i)).all() and np.isfinite(ctxs[j].get_policy_weights(i)).all()) for i in range(min(256, a.size)))
-            cols = max(float(np.max(np.abs(ctxs[j].get_policy_weights(i)))) for i in range(min(256, a.size)))
-            rows.append(dict(agent=label, max_abs_policy_column_of_first_256=cols, kernel=meta[j][1], order=kw["order"], features=ctxs[j].F, n_envs=a.size, batch_steps_per_region=a.steps,
-                             launches_per_region=meta[j][0], regions=a.regions, us_per_batch_step=round(med, 3),
-                             us_per_batch_step_regions=[round(x, 3) for x in us[j]], env_steps_per_s=a.size / (med * 1e-6), vs_last=round(base / med, 3),
-                             batch_steps_run=int(ctxs[j].step_count), non_finite_of_first_256=int(dead)))
-    finally:
-        for c in ctxs:
-            c.close()
-    return rows
 
 
 def main():
@@ -104,7 +61,7 @@ def main():
     for order in (int(x) for x in a.rate_orders.split(",")):
         rate_rows += alternate([("CACLA, from w = 0", dict(common, algo=rsrl_amd.CACLA, order=order)),
                                 ("CACLA, every gate open (V = -2000, lr = alpha = 0)", dict(common, algo=rsrl_amd.CACLA, order=order, lr=0.0, alpha=0.0, v0=-2000.0)),
-                                ("NAC, Gaussian policy (nac.rs)", dict(common, algo=rsrl_amd.NAC, order=order, n_steps=100))], a)
+                                ("NAC, Gaussian policy (nac.rs)", dict(common, algo=rsrl_amd.NAC, order=order, n_steps=100))], a, base=-1)
     depth_rows = alternate([("CACLA, %d steps per launch" % d, dict(common, algo=rsrl_amd.CACLA, order=3, steps_per_launch=d)) for d in (256, 1024, 4096)], a)
     for r in rate_rows + depth_rows:
         print(json.dumps(r), flush=True)
@@ -118,10 +75,10 @@ def main():
             f.write("| %d | %d | %.3e | %s | %.3g |\n" % (o, (o + 1) ** 2, figs[o]["cols"], " / ".join(str(x) for x in figs[o]["open_per_round"]), figs[o]["max_abs_column"]))
         f.write("\n## The driver loop's rate (%d learners, cap 1 000; median of %d regions of %d batch-steps after %d of warm-up, and the range)\n\n" %
                 (a.size, a.regions, a.steps, a.warmup))
-        f.write("| order | agent | kernel | us per batch-step | env-steps/s | rate relative to the Gaussian NAC | largest |policy column| afterwards, learners with a non-finite column (of the first 256) |\n"
+        f.write("| order | agent | kernel | us per batch-step | env-steps/s | time relative to the Gaussian NAC's | largest |policy column| afterwards, learners with a non-finite column (of the first 256) |\n"
                 "|---|---|---|---|---|---|---|\n")
         for r in rate_rows:
-            f.write("| %d | %s | `%s` | %s | %.3e | %.3f | %.3g, %d |\n" % (r["order"], r["agent"], r["kernel"], cell(r), r["env_steps_per_s"], r["vs_last"],
+            f.write("| %d | %s | `%s` | %s | %.3e | %.3f | %.3g, %d |\n" % (r["order"], r["agent"], r["kernel"], cell(r), r["env_steps_per_s"], r["vs_base"],
                                                                           r["max_abs_policy_column_of_first_256"], r["non_finite_of_first_256"]))
         f.write("\n## The launch depth (order 3, the same regions)\n\n| steps per launch | launches per region | us per batch-step |\n|---|---|---|\n")
         for r in depth_rows:

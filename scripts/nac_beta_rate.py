@@ -12,15 +12,7 @@ import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import rsrl_amd  # noqa: E402
-
-
-def region(c, steps):
-    """us per batch-step of one timed train(steps) (device events around the launches: rsrl_hip_timing_read)"""
-    c.sync()
-    c.timing_enable(True)
-    c.train(steps, want_stats=False)
-    ms, launches, name = c.timing_read()
-    return ms * 1e3 / steps, launches, name
+from rate_regions import timed  # noqa: E402
 
 
 def main():
@@ -40,17 +32,7 @@ def main():
         for n in [int(x) for x in a.sizes.split(",")]:
             ctxs = [rsrl_amd.Context(order=order, n_envs=n, **dict(common, **kw)) for _, _, kw in agents]
             try:
-                for c in ctxs:
-                    c.reset()
-                    c.train(a.warmup, want_stats=False)
-                    c.sync()
-                us = [[] for _ in agents]
-                meta = [None] * len(agents)
-                for _ in range(a.regions):                     # alternating: a drift of the machine falls on both
-                    for j, (c, (_, steps, _)) in enumerate(zip(ctxs, agents)):
-                        u, launches, name = region(c, steps)
-                        us[j].append(u)
-                        meta[j] = (launches, name)
+                us, meta = timed(ctxs, [steps for _, steps, _ in agents], a.regions, a.warmup)
                 base = n / (statistics.median(us[0]) * 1e-6)
                 for j, (agent, steps, _) in enumerate(agents):
                     med = statistics.median(us[j])

@@ -22,6 +22,7 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 import rsrl_amd  # noqa: E402
 from tests import gaussian_numpy as gn  # noqa: E402
+from rate_regions import timed  # noqa: E402
 
 NAMES = ("delta", "w", "q", "mu", "sd", "pdf", "sample")
 WHAT = {"delta": "`td_error_out` over the three rounds", "w": "w after the three rounds", "q": "`q_evaluate_f32` (the first round's states; actions -2.5, 1.5 and random in [-1.5, 1.5])",
@@ -38,15 +39,6 @@ def measure(order):
     return fig
 
 
-def region(c, steps):
-    """us per batch-step of one timed train(steps) (device events around the launches: rsrl_hip_timing_read)"""
-    c.sync()
-    c.timing_enable(True)
-    c.train(steps, want_stats=False)
-    ms, launches, name = c.timing_read()
-    return ms * 1e3 / steps, launches, name
-
-
 def rates(a):
     common = dict(domain=rsrl_amd.CONTINUOUS_MOUNTAIN_CAR, algo=rsrl_amd.NAC, order=a.rate_order, n_envs=a.size, max_episode_steps=1000, lr=0.01, gamma=0.999,
                   n_steps=100)
@@ -54,17 +46,7 @@ def rates(a):
     ctxs = [rsrl_amd.Context(**dict(common, **kw)) for _, kw in agents]
     rows = []
     try:
-        for c in ctxs:
-            c.reset()
-            c.train(a.warmup, want_stats=False)
-            c.sync()
-        us = [[] for _ in agents]
-        meta = [None] * len(agents)
-        for _ in range(a.regions):                     # alternating: a drift of the machine falls on both
-            for j, c in enumerate(ctxs):
-                u, launches, name = region(c, a.steps)
-                us[j].append(u)
-                meta[j] = (launches, name)
+        us, meta = timed(ctxs, a.steps, a.regions, a.warmup)
         base = statistics.median(us[0])
         for j, (agent, _) in enumerate(agents):
             med = statistics.median(us[j])

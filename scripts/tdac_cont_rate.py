@@ -15,7 +15,6 @@ One JSON line per figure set and per row; --out writes the markdown tables that 
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -24,6 +23,7 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 import rsrl_amd  # noqa: E402
 from tests import tdac_cont_numpy as tn  # noqa: E402
+from rate_regions import alternate  # noqa: E402
 
 CMC, TDAC = rsrl_amd.CONTINUOUS_MOUNTAIN_CAR, rsrl_amd.CONTINUOUS_TD_ACTOR_CRITIC
 POLICIES = ((rsrl_amd.GAUSSIAN, "Gaussian"), (rsrl_amd.BETA, "Beta"))
@@ -39,46 +39,6 @@ def measure(order, policy):
     fig["max_abs_column"] = float(np.max(np.abs(arr["want_cols"])))
     fig["max_move"] = float(np.max(np.abs(arr["want_cols"] - np.stack([W for _, W in case["init"]]))))
     return fig
-
-
-def region(c, steps):
-    """us per batch-step of one timed train(steps) (device events around the launches: rsrl_hip_timing_read)"""
-    c.sync()
-    c.timing_enable(True)
-    c.train(steps, want_stats=False)
-    ms, launches, name = c.timing_read()
-    return ms * 1e3 / steps, launches, name
-
-
-def alternate(agents, a):
-    """agents: [(label, Context keywords)] -> one row per agent, their timed regions alternating (a drift of the machine falls on all)"""
-    ctxs = [rsrl_amd.Context(**kw) for _, kw in agents]
-    rows = []
-    try:
-        for c in ctxs:
-            c.reset()
-            c.train(a.warmup, want_stats=False)
-            c.sync()
-        us, meta = [[] for _ in agents], [None] * len(agents)
-        for _ in range(a.regions):
-            for j, c in enumerate(ctxs):
-                u, launches, name = region(c, a.steps)
-                us[j].append(u)
-                meta[j] = (launches, name)
-        base = statistics.median(us[0])
-        for j, (label, kw) in enumerate(agents):
-            med = statistics.median(us[j])
-            first = range(min(256, a.size))
-            dead = sum(not np.isfinite(ctxs[j].get_policy_weights(i)).all() for i in first)
-            cols = max(float(np.nanmax(np.abs(ctxs[j].get_policy_weights(i)))) for i in first)
-            rows.append(dict(agent=label, kernel=meta[j][1], order=kw["order"], features=ctxs[j].F, n_envs=a.size, batch_steps_per_region=a.steps,
-                             launches_per_region=meta[j][0], regions=a.regions, us_per_batch_step=round(med, 3),
-                             us_per_batch_step_regions=[round(x, 3) for x in us[j]], env_steps_per_s=a.size / (med * 1e-6), vs_first=round(med / base, 3),
-                             batch_steps_run=int(ctxs[j].step_count), max_abs_policy_column_of_first_256=cols, non_finite_of_first_256=int(dead)))
-    finally:
-        for c in ctxs:
-            c.close()
-    return rows
 
 
 def main():
@@ -124,7 +84,7 @@ def main():
         f.write("| order | agent | kernel | us per batch-step | env-steps/s | time relative to the group's first row | largest |policy column| afterwards, learners with a non-finite column (of the first 256) |\n"
                 "|---|---|---|---|---|---|---|\n")
         for r in rate_rows:
-            f.write("| %d | %s | `%s` | %s | %.3e | %.3f | %.3g, %d |\n" % (r["order"], r["agent"], r["kernel"], cell(r), r["env_steps_per_s"], r["vs_first"],
+            f.write("| %d | %s | `%s` | %s | %.3e | %.3f | %.3g, %d |\n" % (r["order"], r["agent"], r["kernel"], cell(r), r["env_steps_per_s"], r["vs_base"],
                                                                           r["max_abs_policy_column_of_first_256"], r["non_finite_of_first_256"]))
         f.write("\n## The launch depth (order 3, the same regions)\n\n| policy, steps per launch | launches per region | us per batch-step |\n|---|---|---|\n")
         for r in depth_rows:

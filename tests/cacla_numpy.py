@@ -6,7 +6,7 @@ and Philox are tests/beta_numpy.py's, the policy's parameters, score and sample 
                     td = r - <w, phi_s> (terminal) | r + gamma <w, phi_n> - <w, phi_s>;   w += lr td phi_s
                     v = <w, phi_s>;  target = r (terminal: r alone) | r + gamma <w, phi_n>;  gate = target > v (strict)
                     gate open:  e = (a - mu) alpha;  w_m += e g_mu phi_s;  w_s += e g_Sigma sigma(x_s) phi_s    (mu, sd, x_s at phi_s, read first)
-  td_gate_f32   float32, the TD half and the gate in the DEVICE's operation order (kernels_cacla.hpp, cacla_step): tests/gtd_numpy.dot_f32's
+  td_gate_f32   float32, the TD half and the gate in the DEVICE's operation order (kernels_cont.hpp, CaclaRule::step): tests/gtd_numpy.dot_f32's
                     dot products, k_train_td's expression for the error, one fused multiply-add per element; vectorised over learners
   handle_case   the GPU rule test's inputs: every transition's f64 |target - v| is at least MARGIN, so the device's f32 decision cannot differ
   after         `handle` over every round of a case from given features -> w, the columns, the gates, the TD errors

@@ -1,4 +1,4 @@
-"""Crafted preferences and actions for the continuous policies' device code (kernels_tdac_beta.hpp softplus_dev .. beta_sample, kernels_gaussian.hpp
+"""Crafted preferences and actions for the continuous policies' device code (cont_policy.hpp: softplus_dev .. beta_sample,
 gauss_params .. gauss_coef) and the f64 answers on them.  The f64 formulas are tests/gaussian_numpy.py's and tests/beta_numpy.py's; nothing is restated.
 
 table(policy) -> (p0, p1, a float32 (n,), groups (n,) of str): a FIXED list (no random numbers), deduplicated by bit pattern.  The two preferences go in

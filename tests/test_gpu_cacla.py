@@ -1,4 +1,4 @@
-"""CACLA over the Gaussian policy with a TD(0) critic (RSRL_CACLA, train_cacla.hip) on the device, against tests/cacla_numpy.py: the TD half bit
+"""CACLA over the Gaussian policy with a TD(0) critic (RSRL_CACLA, train_cont.hip) on the device, against tests/cacla_numpy.py: the TD half bit
 for bit an RSRL_TD ctx's on RSRL_MOUNTAIN_CAR, the gate of every learner the restatement's, closed-gate learners' columns byte for byte their
 inputs (one of them with a c_s that overflows f32), open-gate columns against the f64 restatement, the agent contract through
 tests/agent_contract.py (train against the host trait loop / launch depths / shards, the checkpoint, foreign files, the C++ example), the

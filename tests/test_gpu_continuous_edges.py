@@ -1,4 +1,4 @@
-"""The Gaussian and the Beta policy code (kernels_gaussian.hpp, kernels_tdac_beta.hpp: softplus_dev, softplus_grad_dev, gauss_params .. gauss_coef,
+"""The Gaussian and the Beta policy code (cont_policy.hpp: softplus_dev, softplus_grad_dev, gauss_params .. gauss_coef,
 beta_params .. beta_sample, digamma_dev) against the reference's f64 semantics on the crafted table of tests/continuous_edges.py: sd at its 0.01
 floor, Softplus's switch at 10 from both sides, a = mu, |a - mu| = sd (where d^2 - Sigma cancels), the far tail and the underflow of the density,
 sd^2 beyond fp32, Beta's clamp edges and parameters a few ulps above 1, NaN and the infinities as preferences.  The comparison is staged
@@ -8,7 +8,7 @@ parameters, in units of 2^-24 cond(row), against four times what a float32 numpy
 The preferences are set through the weights (ce.columns: the constant feature alone), so they hold at EVERY state; each leg first checks that
 policy_params on random states returns the same parameters at every state.  One learner per row.
 
-  read-only legs     k_gauss_policy (from NAC) and k_beta_policy (from the iLSTD ActorCritic) at orders 1 (packed), 2 (unpacked), 5 (the largest
+  read-only legs     k_cont_policy under Gaussian (from NAC) and under Beta (from the iLSTD ActorCritic) at orders 1 (packed), 2 (unpacked), 5 (the largest
                      register footprint), the non-finite rows included: params, mode, pdf, two policy_sample(states) calls; twice the same bits;
                      the checksum and step_count unchanged
   coefficient legs   NAC (Gaussian, Beta): q_evaluate_f32 with the critic's w a unit vector at the state whose features are all exactly 1 is c_m /

@@ -1,4 +1,4 @@
-"""NAC with the Beta policy and the SCB SARSA critic (RSRL_NAC, train_nac_beta.hip) on the device, against tests/nac_numpy.py: the actor's update bit
+"""NAC with the Beta policy and the SCB SARSA critic (RSRL_NAC, train_nac.hip) on the device, against tests/nac_numpy.py: the actor's update bit
 for bit against the float32 restatement, the critic's rule and Q(s, a) against the f64 one, the agent contract through tests/agent_contract.py
 (train against the host trait loop / launch depths / shards, the checkpoint, foreign files, the C++ example), the refusals and the loop's 2a - 1.
 

@@ -1,4 +1,4 @@
-"""NAC with the Gaussian policy and the SCB SARSA critic (RSRL_NAC with RSRL_GAUSSIAN, train_nac_gauss.hip) on the device, against
+"""NAC with the Gaussian policy and the SCB SARSA critic (RSRL_NAC with RSRL_GAUSSIAN, train_nac.hip) on the device, against
 tests/gaussian_numpy.py: the actor's update bit for bit against the float32 restatement (tests/nac_numpy.nac_handle_f32), the critic's rule,
 Q(s, a) and the policy side against the f64 one, the agent contract through tests/agent_contract.py (train against the host trait loop / launch
 depths / shards, the checkpoint, foreign files, the C++ example), the refusals, and the loop that hands the domain the action itself.

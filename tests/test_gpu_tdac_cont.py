@@ -1,4 +1,4 @@
-"""ActorCritic::tdac with a TD(0) critic over the Gaussian and the Beta policy (RSRL_CONTINUOUS_TD_ACTOR_CRITIC, train_tdac_cont.hip) on the
+"""ActorCritic::tdac with a TD(0) critic over the Gaussian and the Beta policy (RSRL_CONTINUOUS_TD_ACTOR_CRITIC, train_cont.hip) on the
 device, against tests/tdac_cont_numpy.py: the TD half bit for bit an RSRL_TD ctx's on RSRL_MOUNTAIN_CAR, the columns of all 67 learners against
 the f64 restatement, alpha = 0, the agent contract through tests/agent_contract.py (train against the host trait loop / launch depths / shards,
 the checkpoint, foreign files, the C++ examples), the refusals, reset, the pending-action step and the mode rollout, device-pointer calls against

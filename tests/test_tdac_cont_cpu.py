@@ -150,7 +150,7 @@ def test_header_binding_constants_and_rust_block_agree():
     assert "pub const RSRL_CONTINUOUS_TD_ACTOR_CRITIC: i32 = 35;" in block and "pub const RSRL_CACLA: i32 = 33;" in block and block == gen.generate()
     assert len(gen.parse_header()[0]) == len(dict(gen.declared_functions(block))) == 96          # no new entry point
     # the step's order is stated where a caller reads it, and in the kernel file's head comment
-    k = open(os.path.join(ROOT, "rsrl_amd", "csrc", "kernels_tdac_cont.hpp")).read()
+    k = open(os.path.join(ROOT, "rsrl_amd", "csrc", "kernels_cont.hpp")).read()
     for text in (h, k):
         assert "TDCritic::target" in text and "before any move" in text and "no gate" in text
     mirror = open(os.path.join(ROOT, "rsrl_amd", "host", "rsrl.hpp")).read()
