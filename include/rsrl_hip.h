@@ -267,8 +267,8 @@ typedef enum { RSRL_QLEARNING = 0, RSRL_SARSA = 1, RSRL_EXPECTED_SARSA = 2, RSRL
                 * 1-5, per-learner f32 weights, no epsilon schedule; everything else is EINVAL at create.  The checkpoint is aux_kind 12.
                 * DEPARTURES: f32 for the reference's f64; the score, modes() and map_onto recalled (RSRL_BETA, RSRL_CONTINUOUS_MOUNTAIN_CAR); the
                 * action clamped to [2^-24, 1 - 2^-24] before its logarithms; SARSA's thread_rng() draw is a keyed stream (distribution parity is
-                * the contract); the period is a parameter (kernels_nac_beta.hpp).
-                * With policy RSRL_GAUSSIAN the same algo is the agent and the loop of examples/nac.rs (kernels_nac_gauss.hpp): the critic, the
+                * the contract); the period is a parameter (kernels_cont.hpp).
+                * With policy RSRL_GAUSSIAN the same algo is the agent and the loop of examples/nac.rs (kernels_cont.hpp): the critic, the
                 * actor's update (w_m, w_s in w_a's and w_b's place), the value side, the accessors and the ESTATE list are the ones above, with
                 *   psi(s, a) = [ g_mu phi(s) ; g_Sigma sigma(x_s) phi(s) ; phi(s) ]     (g_mu, g_Sigma, x_s, sigma: RSRL_GAUSSIAN's, below)
                 * and ONE difference in the loop: the domain sees the action itself (nac.rs:63), no 2a - 1 -- rsrl_hip_domain_step_f32 with
@@ -277,7 +277,7 @@ typedef enum { RSRL_QLEARNING = 0, RSRL_SARSA = 1, RSRL_EXPECTED_SARSA = 2, RSRL
                 * example's constants: lr 0.01, gamma 0.999, alpha 0.01, order 3, P = 100, cap 1 000.  Supported: as above with RSRL_GAUSSIAN in
                 * RSRL_BETA's place.  The checkpoint is aux_kind 14 (aux_kind 12's sections): a Beta NAC file does not load into a Gaussian ctx, nor
                 * the other way round.  DEPARTURES: f32; the score DEFINED (RSRL_GAUSSIAN); the keyed stream; the period a parameter.
-                * Not built: nac_softmax.rs; Gaussian<M, f64> (the fixed-variance policy, policies/gaussian/fixed_var.rs); the Gaussian policy
+                * (nac_softmax.rs, NAC over the Gibbs policy, is RSRL_GIBBS_NAC.)  Not built: Gaussian<M, f64> (the fixed-variance policy, policies/gaussian/fixed_var.rs); the Gaussian policy
                 * under RSRL_ILSTD_ACTOR_CRITIC; IPP */
                RSRL_NAC = 28,
                /* (29 is no algo.)  GTD2 (prediction/td/gtd2.rs:27-86) and TDC (prediction/td/tdc.rs:41-101): gradient-TD prediction over TWO
@@ -317,7 +317,7 @@ typedef enum { RSRL_QLEARNING = 0, RSRL_SARSA = 1, RSRL_EXPECTED_SARSA = 2, RSRL
                 * max_episode_steps: one sample per step, on BLK_STEP).  There is no inner draw.  The domain sees the action itself under
                 * RSRL_GAUSSIAN (nac.rs:63's convention, as RSRL_CACLA) and 2a - 1 under RSRL_BETA (nac_beta.rs:63's mapping of the sample's [0, 1] onto
                 * the domain's [-1, 1]; tdac_beta.rs itself hands the domain a, which RSRL_ILSTD_ACTOR_CRITIC keeps); the agent sees a.
-                * The f32 operation order is fixed (kernels_tdac_cont.hpp, tdac_cont_step; tests/tdac_cont_numpy.py restates it in f64).  Per
+                * The f32 operation order is fixed (kernels_cont.hpp, tdac_cont_step; tests/tdac_cont_numpy.py restates it in f64).  Per
                 * transition (s, a, r, s', term):
                 *   1. x0 = <col0, phi(s)>, x1 = <col1, phi(s)>, the columns before any move
                 *   2. RSRL_TD's arithmetic: v_s = <w, phi(s)>, v_n = <w, phi(s')>; td = r - v_s (terminal) | r + gamma v_n - v_s;
@@ -351,6 +351,50 @@ typedef enum { RSRL_QLEARNING = 0, RSRL_SARSA = 1, RSRL_EXPECTED_SARSA = 2, RSRL
                 * reference's f64; the scores as defined for each policy (RSRL_BETA, RSRL_GAUSSIAN); the Gaussian loop is this library's (the
                 * reference has no tdac example over its Gaussian policy), the Beta loop tdac_beta.rs's order with nac_beta.rs's action mapping */
                RSRL_CONTINUOUS_TD_ACTOR_CRITIC = 35,
+               /* (36 is no algo, and neither is 38.)  NAC over the Gibbs policy: the agent and the loop of examples/nac_softmax.rs (control/nac.rs:47-59)
+                * on the domains with an enumerable action set.  (Listed before RSRL_CACLA, which stays the enum's last enumerator; a new number and
+                * not RSRL_NAC with RSRL_SOFTMAX: RSRL_NAC keeps refusing Softmax and the discrete domains.)  policy = Gibbs::standard(LFA::vector(
+                * basis, SGD(1.0), A)) = Softmax(tau), theta f32[F][A] per learner, zero at create; the critic is SARSA{q_func: LFA::scalar(
+                * SCB{policy, basis}, SGD(lr)), policy, gamma} (control/td/sarsa.rs:53-75), w f32[(A+1) F] per learner, zero at create.
+                * Softmax::grad_log((s, a)) (policies/softmax.rs:113-128) is the (F, A) matrix whose column b is (1[b==a] - p_b) phi(s), p =
+                * softmax_stable(theta^T phi(s) / tau) -- no 1/tau, as for RSRL_ACTOR_CRITIC; SCB::n_features() (fa/linear.rs:85-89) is
+                * policy.n_weights() + basis.dim() = (A+1) F; NAC::handle(()) takes cw[0 .. F A], reshapes it row-major to (F, A) and steps the
+                * policy by (alpha / max(||grad||, 1e-3)) grad (softmax.rs:208-221).
+                * THE ONE DEFECT TAKEN OUT: SCB::project (fa/linear.rs:91-102) chains grad_log(..).index_axis_move(Axis(1), 0) -- column 0 only, F
+                * values -- with phi: 2F features against (A+1) F weights.  The Beta and Gaussian policies have one-column Jacobians, for Gibbs with
+                * A > 1 it is a length mismatch and the example stops at its first critic.handle.  Built with the flattening of the sibling
+                * CompatibleBasis::project (:42-46), grad_log(args).into_shape(n_features), row-major -- exactly the order NAC::handle reads back:
+                *   psi(s, a)[f*A + b] = (1[b==a] - p_b) * phi(s)[f]      (f < F, b < A)
+                *   psi(s, a)[F*A + f] = phi(s)[f]
+                *   Q(s, a) = <w, psi(s, a)>
+                * The f32 operation order is fixed (kernels_gibbs_nac.hpp; tests/gnac_numpy.py restates it):
+                *   p(s) = RSRL_ACTOR_CRITIC's probabilities on theta;  c_b = 1[b==a] - p_b;  d_b = <w_b, phi> for the A score blocks (w_b[f] =
+                *   w[f*A + b]), d_v = <w_v, phi> for the basis block, each in the weight dots' summation order;
+                *   Q(s, a) = fma(c_0, d_0, fma(c_1, d_1, ... fma(c_{A-1}, d_{A-1}, d_v)))
+                *   SARSA::handle: na = the sample from p(s') on the agent's own keyed draw (BLK_INNER, not consumed by a terminal transition);
+                *     delta = r - Q(s,a) (terminal) | fma(gamma, Q(s',na), r) - Q(s,a);  sc = lr delta;  block b += (sc c_b) phi, the basis block
+                *     += sc phi, one fused multiply-add per entry;  theta does not move
+                *   NAC::handle(()): ss = sum over j = 0 .. F A - 1 in that order of w[j] w[j], each square rounded before it is added;  norm =
+                *     max(sqrtf(ss), 1e-3f);  scale = alpha32 / norm;  theta[f][b] = fma(scale, w[f*A + b], theta[f][b]);  the critic is not
+                *     reset;  the response is norm
+                * The driver loop (nac_softmax.rs:57-78), i the 0-based index of the step in its episode: env.transition(a); critic.handle; a =
+                * policy.sample(s'), taken after the restart if the episode ended or was cut (BLK_STEP / BLK_RESET as the other loops); then
+                * NAC::handle(()) if i % P == 0, i = 0 included.  The statistics' sum |delta| is SARSA's.
+                * config: lr = the critic's SGD rate (0.01 in the example), gamma (0.999), alpha = NAC.alpha (0.01, rounded to f32 once), tau (1.0),
+                * n_steps = the actor's period P in [1, 65 536] (else EINVAL); max_episode_steps may be 0.
+                * rsrl_hip_n_outputs is 1 and rsrl_hip_n_weight_rows (A+1) F: rsrl_hip_get/set_weights carry w as f32[(A+1) F][1] in the row order
+                * above; theta travels through rsrl_hip_get/set_policy_weights as f32[F][A].  rsrl_hip_handle is critic.handle alone (td_error_out =
+                * delta; the actor does not move; the inner draw is batch-step t's); rsrl_hip_nac_update is NAC::handle(()); rsrl_hip_q_evaluate
+                * writes f32[A][M], row b = Q(s_i, b) against learner i's w and theta, read-only.  The policy side is RSRL_ACTOR_CRITIC's,
+                * unchanged (policy_sample / _mode / _probs / _prob on theta, reset's initial sample on BLK_INIT, the rollouts, n_policy_outputs =
+                * A).  q_find_max / _min, q_expected_value, every *_f32 call, handle_batch, handle_transitions, traces, td, behaviour and lstd
+                * accessors and the episode record are ESTATE; the q carry is EINVAL.
+                * Supported: policy RSRL_SOFTMAX, agent_policy -1, the register-family Fourier orders (MountainCar 1-5, CartPole 1, Acrobot 1),
+                * per-learner f32 weights, no epsilon schedule; everything else -- shared or bf16 weights, RSRL_HIV_TREATMENT,
+                * RSRL_CONTINUOUS_MOUNTAIN_CAR -- is EINVAL at create.  The checkpoint is aux_kind 18 (w, then theta): it loads into no other
+                * agent's ctx, and no other agent's file into this one.  DEPARTURES: f32 for the reference's f64; psi flattened as stated; SARSA's
+                * thread_rng() draw is a keyed stream (distribution parity is the contract); the period is a parameter (the example hard-codes it) */
+               RSRL_GIBBS_NAC = 37,
                /* (32 is no algo.)  CACLA (control/cacla.rs:42-64), the continuous actor-critic learning automaton, over the Gaussian policy with a
                 * TD(0) state-value critic.  CACLA{critic, policy, alpha, gamma}: the critic is a closure over V that the agent reads and never
                 * writes -- a caller trains it; here it is eval = TD{v_func: LFA::scalar(basis, SGD(lr)), gamma} (prediction/td/td.rs:38-58), w
@@ -363,7 +407,7 @@ typedef enum { RSRL_QLEARNING = 0, RSRL_SARSA = 1, RSRL_EXPECTED_SARSA = 2, RSRL
                 * t = env.transition(a) -- the domain sees the action itself, as in nac.rs:63 --; eval.handle(&t); agent.handle(&t), whose critic
                 * reads eval's UPDATED weights; a = policy.sample(s') with the updated columns, taken after the restart if the episode ended
                 * (terminal or cut by max_episode_steps: one sample per step, on BLK_STEP).  There is no inner draw.
-                * The f32 operation order is fixed (kernels_cacla.hpp, cacla_step; tests/cacla_numpy.py restates it):
+                * The f32 operation order is fixed (kernels_cont.hpp, cacla_step; tests/cacla_numpy.py restates it):
                 *   1. x_m = <w_m, phi(s)>, x_s = <w_s, phi(s)>
                 *   2. RSRL_TD's arithmetic: v_s = <w, phi(s)>, v_n = <w, phi(s')>; td = r - v_s (terminal) | r + gamma v_n - v_s;
                 *      w += (lr td) phi(s), one fused multiply-add per element
@@ -553,8 +597,9 @@ int rsrl_hip_n_outputs(const rsrl_hip_ctx* ctx);
  * 0 for the agents whose policy reads Q */
 int rsrl_hip_n_policy_outputs(const rsrl_hip_ctx* ctx);
 int rsrl_hip_n_features(const rsrl_hip_ctx* ctx);
-/* rows of the weight matrix (rsrl_hip_get/set_weights carry f32[n_weight_rows][n_outputs]): 3 n_features for RSRL_NAC, whose critic's basis is the
- * stable compatible basis (SCB::n_features, fa/linear.rs:79-103); n_features on every other ctx */
+/* rows of the weight matrix (rsrl_hip_get/set_weights carry f32[n_weight_rows][n_outputs]): 3 n_features for RSRL_NAC and (n_actions + 1)
+ * n_features for RSRL_GIBBS_NAC, whose critic's basis is the stable compatible basis (SCB::n_features, fa/linear.rs:79-103); n_features on every
+ * other ctx */
 int rsrl_hip_n_weight_rows(const rsrl_hip_ctx* ctx);
 int64_t rsrl_hip_n_envs(const rsrl_hip_ctx* ctx);
 /* state_space() bounds: mountain_car/discrete.rs:97-99, cart_pole.rs:112-118, acrobot.rs:143-149 */
@@ -658,7 +703,8 @@ int rsrl_hip_domain_step(rsrl_hip_ctx* ctx, const int32_t* actions,
 int rsrl_hip_domain_reset(rsrl_hip_ctx* ctx, const uint8_t* mask);
 
 /* Function<(S,)>::evaluate for VectorLFA: Q(s,.) = W^T phi(s)      rsrl/src/fa/linear.rs:303-311
- * state m is evaluated with learner m's weights (or the shared weights). */
+ * state m is evaluated with learner m's weights (or the shared weights).  An RSRL_GIBBS_NAC ctx writes f32[n_actions][M] although its
+ * n_outputs is 1: row b = Q(s_m, b) of the critic over the stable compatible basis, against learner m's w and theta. */
 int rsrl_hip_q_evaluate(rsrl_hip_ctx* ctx, const float* states /*[D][M]*/, int64_t M, float* q_out /*[A][M]*/);
 /*   prediction agents: the same call is Function<(S,)>::evaluate of the ScalarLFA (fa/linear.rs:213-221), q_out = V f32[1][M];
  *   find_max / policy_mode / policy_probs / policy_sample / rollout_greedy return RSRL_HIP_ESTATE for them (no Q function). */
@@ -832,6 +878,8 @@ int rsrl_hip_lstd_solve(rsrl_hip_ctx* ctx);
  *              Gaussian policy's columns (the mean's, the stddev's);
  *              if aux_kind is 16 or 17 (file version 10 too; RSRL_CONTINUOUS_TD_ACTOR_CRITIC with RSRL_BETA / RSRL_GAUSSIAN): aux_kind 15's sections,
  *              the columns alpha's and beta's / the mean's and the stddev's;
+ *              if aux_kind is 18 (file version 10 too; RSRL_GIBBS_NAC; the header's F is n_features, A = 1): the weights are n_learners x
+ *              f32[(n_actions + 1) F][1] of the critic's w, then n_learners x f32[F][n_actions] of the Gibbs policy's theta;
  *              if aux_kind is 13 (file version 10 too; RSRL_GTD2 / RSRL_TDC; A = 1, the weights are theta): n_learners x f32[F][1] of the
  *              second weight column w (fa_w / td_est);
  *              if aux_kind is 3 (file version 3): u32 head[N], u32 len[N], f32 entries[D + 5][n_steps][N] -- every learner's

@@ -24,6 +24,7 @@ CONTINUOUS_TD_ACTOR_CRITIC = 35                 # (34 is no algo) ActorCritic::t
 TRACE_ACCUMULATE, TRACE_SATURATE, TRACE_DUTCH = 0, 1, 2
 GREEDY, EPSILON_GREEDY, SOFTMAX, RANDOM = 0, 1, 2, 3
 BETA = 4                                        # policies/beta.rs over two Softplus-composed scalar LFAs: ILSTD_ACTOR_CRITIC on CONTINUOUS_MOUNTAIN_CAR
+GIBBS_NAC = 37                                  # (36 is no algo) control/nac.rs over the Gibbs policy (nac_softmax.rs: policy=SOFTMAX) and a SARSA critic over the stable compatible basis on the discrete domains: n_weight_rows = (A + 1) F; q_evaluate -> (A, M); handle = critic.handle; nac_update; n_steps = the actor's period
 GAUSSIAN = 6                                    # (5 is no policy) policies/gaussian: the mean a scalar LFA, the stddev a Softplus-composed one: NAC (nac.rs) and CACLA on CONTINUOUS_MOUNTAIN_CAR
 W_PER_ENV, W_SHARED = 0, 1
 W_F32, W_BF16 = 0, 1
@@ -126,7 +127,8 @@ class Context:
         self.A = self._L.rsrl_hip_n_actions(self._h)
         self.n_out = self._L.rsrl_hip_n_outputs(self._h)      # weight columns: A, or 1 for TD / TDLambda
         self.F = self._L.rsrl_hip_n_features(self._h)
-        self.n_weight_rows = self._L.rsrl_hip_n_weight_rows(self._h)      # rows of the weight matrix: F, or NAC's 3 F (SCB::n_features)
+        self.n_weight_rows = self._L.rsrl_hip_n_weight_rows(self._h)      # rows of the weight matrix: F, or NAC's 3 F / GIBBS_NAC's (A + 1) F (SCB::n_features)
+        self._q_rows = self.A if algo == GIBBS_NAC else self.n_out          # (q_evaluate's array shape: GIBBS_NAC's critic has one weight column and a value per action)
         self.n_policy_out = self._L.rsrl_hip_n_policy_outputs(self._h)      # columns of the policy's own weights: A (Gibbs), 2 (BETA, GAUSSIAN), 0 (the policy reads Q)
         self._policy_cols = self.n_policy_out or self.A                     # (the accessors' array shape; an agent without policy weights is refused by the library)
         self._td_cols = 1 if algo in (GTD2, TDC) else self.A                # (get/set_td_weights' array shape: GreedyGQ's fa_td has A columns)
@@ -267,7 +269,7 @@ class Context:
 
     def q_evaluate(self, states):
         states, M = self._batch(states)
-        out = np.empty((self.n_out, M), dtype=np.float32)
+        out = np.empty((self._q_rows, M), dtype=np.float32)
         _abi.check(self._L.rsrl_hip_q_evaluate(self._h, _p(states), M, _p(out)))
         return out
 

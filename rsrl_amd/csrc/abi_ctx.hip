@@ -48,6 +48,7 @@ static AgentFamily classify(const rsrl_hip_config& cfg, size_t w_elems) {
     if (is_gmc(al)) return F::GmcReg;
     if (is_lstd_batch(al)) return F::LstdBatchReg;
     if (is_nac(al)) return cfg.policy == RSRL_GAUSSIAN ? F::NacGaussReg : F::NacBetaReg;
+    if (is_gibbs_nac(al)) return F::GibbsNacReg;            // (before the prediction agents: W is one column, but the policy is the actor's)
     if (is_gtd(al)) return F::GtdReg;
     if (is_cacla(al)) return F::CaclaGaussReg;
     if (is_tdac_cont(al)) return cfg.policy == RSRL_GAUSSIAN ? F::TdAcGaussReg : F::TdAcBetaTdReg;
@@ -159,6 +160,9 @@ static int check_reg_only(const rsrl_hip_config& cfg, const AlgoRow& a, bool sto
                     cfg.domain, cfg.basis, cfg.order, cfg.weight_mode, cfg.weight_dtype, cfg.policy, cfg.agent_policy, cfg.epsilon_decay);
     if (a.n_updates && (cfg.n_steps < 1 || cfg.n_steps > 32))
         return fail(RSRL_HIP_EINVAL, "%s: n_steps (%sn_updates, the rounds of solve() per transition) must be in [1, 32], got %d", a.name, a.n_updates, cfg.n_steps);
+    if (a.agent == Agent::GibbsNac && (cfg.n_steps < 1 || cfg.n_steps > 65536))
+        return fail(RSRL_HIP_EINVAL, "%s: n_steps (the actor's period: NAC::handle(()) runs at every n_steps-th step of an episode, nac_softmax.rs) must be "
+                                     "in [1, 65536], got %d", a.name, cfg.n_steps);
     // GradientMC, LSTD and LSTDLambda keep every learner's open episode on the device, max_episode_steps rows of it
     if ((a.agent == Agent::Gmc || a.agent == Agent::LstdBatch) && cfg.max_episode_steps < 1)
         return fail(RSRL_HIP_EINVAL, "%s: max_episode_steps must be >= 1 -- the device records every learner's open episode, and an unbounded episode "
@@ -246,6 +250,8 @@ static int check_config(const rsrl_hip_config& cfg) {
     const bool tile = cfg.basis == RSRL_TILE_CODING, reg = is_reg_fourier(cfg), wave = is_wave(cfg);
     const bool f32 = cfg.weight_dtype == RSRL_W_F32, esched = cfg.epsilon_decay != 1.0;
     const bool one_step = kAlgo[al].agent == Agent::OneStep;
+    // (NAC over the Gibbs policy names itself in every refusal, the continuous domain's and policies' included)
+    if (is_gibbs_nac(al)) return check_reg_only(cfg, kAlgo[al], reg && per_env && f32 && !esched);
     if (cfg.domain == RSRL_CONTINUOUS_MOUNTAIN_CAR || cfg.policy == RSRL_BETA || cfg.policy == RSRL_GAUSSIAN || al == RSRL_NAC || al == RSRL_CACLA || al == RSRL_CONTINUOUS_TD_ACTOR_CRITIC)
         return check_continuous(cfg, kAlgo[al], is_cmc_fourier(cfg) && per_env && f32 && !esched);
     if (kAlgo[al].reg_policy >= 0) return check_reg_only(cfg, kAlgo[al], reg && per_env && f32 && !esched);
@@ -309,7 +315,8 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
     const AlgoRow& agent = kAlgo[cfg->algo];
     c->Aw = agent.v ? 1 : c->A;
     c->Ap = (cfg->policy == RSRL_BETA || cfg->policy == RSRL_GAUSSIAN) ? 2 : (agent.reg_policy == RSRL_SOFTMAX ? c->A : 0);
-    c->Fw = is_nac(cfg->algo) ? 3 * c->F : c->F;      // (SCB::n_features: the score's two blocks and the basis itself)
+    // (SCB::n_features: the score's blocks -- two columns, or the Gibbs policy's A -- and the basis itself)
+    c->Fw = is_nac(cfg->algo) ? 3 * c->F : (is_gibbs_nac(cfg->algo) ? (c->A + 1) * c->F : c->F);
     c->w_elems = (size_t)c->Aw * c->Fw * (size_t)(shared ? 1 : N);
     c->family = classify(*cfg, c->w_elems);
     // a ctx that steps one batch-step per launch streams W every step: learner-major rows (W[N][A][F]) let k_step_reg_lm

@@ -438,6 +438,7 @@ int launch_agent(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, uint64_t 
     case AgentFamily::TdAcBetaTdReg:
         ok = !io && launch_td0_cont(cf.order, is_cacla(cf.algo), cont_policy(c), c->stream, k, make_cont(c), t, chunk, d_stats, nullptr);
         break;
+    case AgentFamily::GibbsNacReg: ok = launch_gibbs_nac(cf.domain, cf.order, grid, block, c->stream, k, c->Z, nac_period(c), t, chunk, d_stats, io); break;
     case AgentFamily::GtdReg: ok = launch_gtd(cf.domain, cf.order, cf.algo == RSRL_TDC, grid, block, c->stream, k, make_gtd(c), t, chunk, d_stats, io); break;
     default: ok = false; break;      // (the shared-W families: enqueue_shared_step)
     }

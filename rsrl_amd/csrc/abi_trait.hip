@@ -151,6 +151,11 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
     // the TD ActorCritic: its value side is V(s) (no action values to search or weigh), its policy side the actor's theta
     if (is_v_actor_critic(c) && (op == QOP_FIND_MAX || op == QOP_FIND_MIN || op == QOP_EXPECTED))
         return fail(RSRL_HIP_ESTATE, "the TD ActorCritic's critic is a state-value function (use rsrl_hip_q_evaluate for V(s), the policy operations for the actor)");
+    // NAC over the Gibbs policy: the critic is Q(s, a) = <w, psi(s, a)> over the stable compatible basis -- evaluated for every action (k_gibbs_nac_q); W is
+    // one column of (A+1) F rows, not the A columns the searches and the weighted sum read
+    if (is_gibbs_nac(c->cfg.algo) && (op == QOP_FIND_MAX || op == QOP_FIND_MIN || op == QOP_EXPECTED))
+        return fail(RSRL_HIP_ESTATE, "RSRL_GIBBS_NAC's critic is Q(s, a) over the stable compatible basis: rsrl_hip_q_evaluate writes it for every action "
+                                     "(no search or weighted sum over it; the policy operations read the actor)");
     // REINFORCE has no value function (BaselineREINFORCE's is the baseline B): only the policy's operations and the projection
     if (c->cfg.algo == RSRL_REINFORCE && (op == QOP_EVALUATE || op == QOP_FIND_MAX || op == QOP_FIND_MIN || op == QOP_EXPECTED))
         return fail(RSRL_HIP_ESTATE, "REINFORCE has no value function (use the policy operations; BaselineREINFORCE's value side is its baseline)");
@@ -171,7 +176,9 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
     const uint64_t call = (op == QOP_SAMPLE_STEP || op == QOP_SAMPLE_INIT) ? step_t : c->api_calls;      // (the driver loop's sample: addressed by the batch-step)
     if (op == QOP_SAMPLE) c->api_calls++;
     const BasisGeom g = make_geom(c);
-    if (has_lstd_state(c) && op == QOP_EVALUATE) {                        // V(s) = f32(phi(s) . theta), in f64 (k_lstd_v)
+    if (is_gibbs_nac(c->cfg.algo) && op == QOP_EVALUATE) {                // Q(s, b) for every b: f32[A][M] against the learners' w and theta
+        if (!launch_gibbs_nac_q(c->cfg.domain, c->cfg.order, c->stream, k, c->Z, d_states, M_, d_fout)) return NO_MODEL(c);
+    } else if (has_lstd_state(c) && op == QOP_EVALUATE) {                 // V(s) = f32(phi(s) . theta), in f64 (k_lstd_v)
         if (!launch_lstd_v(feature_domain(c), c->cfg.order, c->stream, c->lstd_theta, d_states, M_, d_fout)) return NO_MODEL(c);
     } else if (is_td_v_continuous(c->cfg.algo) && op == QOP_EVALUATE) {   // V(s) of CACLA's / the continuous TD ActorCritic's TD learner: k_v_evaluate on MountainCar's projection
         if (!launch_v_evaluate(feature_domain(c), c->cfg.order, dim3(grid_for(M_)), dim3(kBlock), c->stream, k, d_states, M_, d_fout)) return NO_MODEL(c);
@@ -225,7 +232,8 @@ int rsrl_hip_policy_prob(rsrl_hip_ctx* c, const float* states, const int32_t* ac
 }
 int rsrl_hip_q_evaluate(rsrl_hip_ctx* c, const float* states, int64_t M, float* q_out) {
     if (!q_out) return fail(RSRL_HIP_EINVAL, "null argument");
-    return qop(c, QOP_EVALUATE, states, M, q_out, c ? (size_t)c->Aw * M : 0, nullptr);
+    // (RSRL_GIBBS_NAC: one weight column, but a value per action)
+    return qop(c, QOP_EVALUATE, states, M, q_out, c ? (size_t)(is_gibbs_nac(c->cfg.algo) ? c->A : c->Aw) * M : 0, nullptr);
 }
 int rsrl_hip_q_find_max(rsrl_hip_ctx* c, const float* states, int64_t M, int32_t* idx_out, float* val_out) {
     return qop(c, QOP_FIND_MAX, states, M, val_out, (size_t)M, idx_out);
@@ -551,7 +559,7 @@ int rsrl_hip_q_evaluate_f32(rsrl_hip_ctx* c, const float* states, const float* a
 }
 int rsrl_hip_nac_update(rsrl_hip_ctx* c, const uint8_t* mask, float* norm_out) {
     CHECK_CTX(c);
-    if (!is_nac(c->cfg.algo)) return fail(RSRL_HIP_ESTATE, "%s", kNoNac);
+    if (!has_nac_update(c->cfg.algo)) return fail(RSRL_HIP_ESTATE, "%s", kNoNac);
     FLUSH(c);
     HIP_TRY(hipSetDevice(c->cfg.device));
     const size_t N = (size_t)c->cfg.n_envs;
@@ -560,7 +568,8 @@ int rsrl_hip_nac_update(rsrl_hip_ctx* c, const uint8_t* mask, float* norm_out) {
     TRY(f.in(mask, N, &d_mask));
     TRY(f.out(norm_out, N, &d_norm));
     // (k_nac_update reads w's first 2F rows and the two columns, whatever the policy: the Gaussian ctx runs it too)
-    if (!launch_nac_update(c->cfg.order, c->stream, make_common(c), make_cont(c), d_mask, d_norm)) return NO_MODEL(c);
+    if (!(is_gibbs_nac(c->cfg.algo) ? launch_gibbs_nac_update(c->cfg.domain, c->cfg.order, c->stream, make_common(c), c->Z, d_mask, d_norm)      // (theta steps along w's first F A rows)
+                                    : launch_nac_update(c->cfg.order, c->stream, make_common(c), make_cont(c), d_mask, d_norm))) return NO_MODEL(c);
     KCHECK();
     c->q_valid = false;
     return f.finish();

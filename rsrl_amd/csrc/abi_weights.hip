@@ -213,7 +213,7 @@ struct CkptKind {
     bool reads_kind0;            // a ctx of this kind also reads its configuration's version-2 / aux_kind-0 file, written before the kind's own section
     SectionId sections[3];       // travelled: the weights load, that section's state starts empty
 };
-constexpr int kCkptKinds = 18;
+constexpr int kCkptKinds = 19;
 constexpr CkptKind kCkptKind[kCkptKinds] = {
     /* 0 weights only                           */ {2, 0, true, false, {S_WEIGHTS}},
     /* 1 eligibility traces                     */ {2, 0, true, false, {S_WEIGHTS, S_AUX}},
@@ -234,6 +234,7 @@ constexpr CkptKind kCkptKind[kCkptKinds] = {
     /* 15 CACLA: the V learner's w, the Gaussian policy's two columns */ {10, 0, false, false, {S_WEIGHTS, S_AUX}},      // (version 10 as well)
     /* 16 the continuous TD ActorCritic with the Beta policy: kind 15's sections */ {10, 0, false, false, {S_WEIGHTS, S_AUX}},
     /* 17 ... with the Gaussian policy */ {10, 0, false, false, {S_WEIGHTS, S_AUX}},      // (the kind alone tells the two policies' files, and CACLA's, apart)
+    /* 18 NAC over the Gibbs policy: the critic's w ((A+1) F rows), theta (A columns) */ {10, 0, false, false, {S_WEIGHTS, S_AUX}},
 };
 // (the kinds the configuration decides, not the algo: SARSALambda / QLambda over ONE shared tile table keep sparse traces instead of Z; the iLSTD
 // ActorCritic with the Beta policy keeps two policy columns instead of the Gibbs actor's A; NAC's columns are the Gaussian policy's, not Beta's)

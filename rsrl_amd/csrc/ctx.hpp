@@ -49,7 +49,7 @@ using namespace rsrl;
 
 // ---- THE agent table: what the reference's agent of each rsrl_algo is, one row per number.  Admission (check_config), the ctx's buffers (create_impl),
 // the accessors and the checkpoint read it; a new agent adds its row here, a line of classify() and a case of launch_agent ("Adding an agent").
-enum class Agent : uint8_t { None, OneStep, Lambda, Gq, Pred, QSigma, Ac, TdAc, Reinforce, Lstd, TdAcLstd, Gmc, LstdBatch, Nac, Gtd, Cacla, TdAcCont };      // the group classify() and the kernels' dispatch know it by
+enum class Agent : uint8_t { None, OneStep, Lambda, Gq, Pred, QSigma, Ac, TdAc, Reinforce, Lstd, TdAcLstd, Gmc, LstdBatch, Nac, Gtd, Cacla, TdAcCont, GibbsNac };      // the group classify() and the kernels' dispatch know it by
 enum class Aux : uint8_t { None, LikeW, Policy };      // the second per-learner matrix Z: none, of W's shape, or the actor's A columns next to a one-column W
 struct AlgoRow {
     const char* name = nullptr;      // as the admission messages print it (nullptr: the number is unassigned)
@@ -63,7 +63,7 @@ struct AlgoRow {
     // one of them), the message's words behind it and behind "agent_policy = -1", and what it calls config.n_steps in front of "n_updates" (nullptr: not read)
     int reg_policy = -1; const char* policy_words = ""; const char* shares_words = ""; const char* n_updates = nullptr;
 };
-constexpr int kLastAlgo = RSRL_CONTINUOUS_TD_ACTOR_CRITIC;      // the highest assigned number (RSRL_CACLA stays the enum's textually last enumerator)
+constexpr int kLastAlgo = RSRL_GIBBS_NAC;      // the highest assigned number (RSRL_CACLA stays the enum's textually last enumerator)
 constexpr AlgoRow kAlgo[kLastAlgo + 1] = {
     /*  0 */ {"QLearning", Agent::OneStep},
     /*  1 */ {"SARSA", Agent::OneStep},
@@ -112,6 +112,10 @@ constexpr AlgoRow kAlgo[kLastAlgo + 1] = {
     // (CACLA's layout: W is the V learner's one column, the Gaussian or the Beta policy's two columns in Z; admitted by check_continuous; aux_kind 16 with
     // Beta, 17 with Gaussian: aux_kind_of)
     /* 35 */ {"the continuous TD ActorCritic (RSRL_CONTINUOUS_TD_ACTOR_CRITIC)", Agent::TdAcCont, true, Aux::Policy, 16},
+    /* 36 */ {},
+    // (W is the SCB critic's one column of (A+1) F rows -- weight_rows() --, the Gibbs policy's theta, A columns, in Z; config.n_steps is the actor's period,
+    // checked by check_reg_only itself)
+    /* 37 */ {"NAC over the Gibbs policy (RSRL_GIBBS_NAC)", Agent::GibbsNac, true, Aux::Policy, 18, false, false, RSRL_SOFTMAX, " (the Gibbs policy)", " (the critic shares the policy)"},
 };
 // (readers of the table, for configurations check_config has admitted: the algo is a row with a name)
 static inline bool is_lambda(int algo) { return kAlgo[algo].agent == Agent::Lambda; }
@@ -127,6 +131,9 @@ static inline bool is_nac(int algo) { return kAlgo[algo].agent == Agent::Nac; }
 static inline bool is_gtd(int algo) { return kAlgo[algo].agent == Agent::Gtd; }
 static inline bool is_cacla(int algo) { return kAlgo[algo].agent == Agent::Cacla; }
 static inline bool is_tdac_cont(int algo) { return kAlgo[algo].agent == Agent::TdAcCont; }
+static inline bool is_gibbs_nac(int algo) { return kAlgo[algo].agent == Agent::GibbsNac; }
+// the agents with NAC::handle(()) (rsrl_hip_nac_update): over the continuous policies, or over the Gibbs policy
+static inline bool has_nac_update(int algo) { return is_nac(algo) || is_gibbs_nac(algo); }
 // the continuous agents whose value function is a TD(0) V learner in W, TD's layout (rsrl_hip_q_evaluate -> V(s): k_v_evaluate)
 static inline bool is_td_v_continuous(int algo) { return is_cacla(algo) || is_tdac_cont(algo); }
 // the agents that keep every learner's open episode on the device (rec_s / rec_r, max_episode_steps rows) and sweep it when it ends
@@ -229,8 +236,10 @@ enum class AgentFamily : uint8_t {
                           // (train_cont.hip)
     TdAcBetaTdReg,        // ... over the Beta policy (the columns alpha's and beta's; the loop hands the domain 2a - 1): k_train_tdac_cont.  (TdAcBetaReg is
                           // the iLSTD critic's family)
+    GibbsNacReg,          // NAC over the Gibbs policy with the SCB SARSA critic, AcReg's configurations: k_train_gibbs_nac (train_gibbs_nac.hip); the critic's w in W
+                          // ((A+1) F rows, one column), theta in Z (A columns)
 };
-constexpr size_t kAgentFamilies = (size_t)AgentFamily::TdAcBetaTdReg + 1;      // (the enum's last value)
+constexpr size_t kAgentFamilies = (size_t)AgentFamily::GibbsNacReg + 1;      // (the enum's last value)
 // ---- THE family table: which kernels serve a family and what they can do, one row per AgentFamily value in the enum's order.  classify() (abi_ctx.hip: a
 // decision) and launch_agent (abi_train.hip: it instantiates the templates) are the two other places a new family is entered.
 enum class Slots : uint8_t { Block, Block64, WaveBlock, Learner, LstdGroup };      // a statistics slot per: kBlock learners, 64 learners (k_train_lambda_mem4; the
@@ -296,6 +305,8 @@ constexpr FamilyRow kFamily[] = {
                                                                                                                    // 0.99 us per batch-step at 256 / 1 024 / 4 096 steps per launch, profiles/tdac_cont_rate.md)
     {AgentFamily::TdAcBetaTdReg, "k_train_tdac_cont", 4096, Slots::Block, Handle::Agent, kPolicyW | kVCritic},     // (handle: rsrl_hip_handle_f32; 3.18 / 3.14 / 3.12 us at the same depths: the
                                                                                                                    // Beta sampler's scalar chain dominates, the depth is CaclaGaussReg's all the same)
+    {AgentFamily::GibbsNacReg, "k_train_gibbs_nac", 4096, Slots::Block, Handle::Agent, kPolicyW},      // (measured at 65 536 order-3 learners: 1.75 / 1.72 / 1.70 us per batch-step at
+                                                                                                       // 256 / 1 024 / 4 096 steps per launch, k_train_ac 1.66 in the same process: profiles/gibbs_nac_rate.md)
 };
 constexpr bool family_rows_in_order() {
     for (size_t i = 0; i < sizeof(kFamily) / sizeof(kFamily[0]); ++i) if ((size_t)kFamily[i].family != i) return false;
@@ -330,7 +341,7 @@ struct rsrl_hip_ctx {
     int Ap = 0;                      // columns of the policy's own weights (rsrl_hip_n_policy_outputs): A for the Gibbs actors, 2 for Beta, 0 when the policy reads Q
     float* W = nullptr; float* dW = nullptr;
     int Aw = 0;                      // columns of the weight matrix: A (control) or 1 (prediction: ScalarLFA)
-    int Fw = 0;                      // rows of the weight matrix (rsrl_hip_n_weight_rows): F, or NAC's 3F (the critic's basis is SCB)
+    int Fw = 0;                      // rows of the weight matrix (rsrl_hip_n_weight_rows): F, or NAC's 3F / the Gibbs NAC's (A+1) F (the critic's basis is SCB)
     long long* dW_rep = nullptr; int n_rep = 1;  // shared tile coding: n_rep copies of the fixed-point (64-bit) delta table
     long long* sh_tab = nullptr;     // shared-W dense basis: 3 sets x kTabRep copies of the fixed-point delta table (models.hpp DeltaTab)
     long long* h_fx = nullptr;       // shared W: fixed-point delta table of rsrl_hip_handle (one entry per weight)
@@ -521,6 +532,7 @@ static inline ContState make_cont(const rsrl_hip_ctx* c) {
     cs.pol = c->Z; cs.action = c->action_f;
     return cs;
 }
+// (RSRL_GIBBS_NAC's too)
 static inline uint32_t nac_period(const rsrl_hip_ctx* c) { return (uint32_t)c->cfg.n_steps; }
 static inline ContPolicy cont_policy(const rsrl_hip_ctx* c) { return c->cfg.policy == RSRL_GAUSSIAN ? ContPolicy::Gaussian : ContPolicy::Beta; }
 

@@ -12,6 +12,7 @@
 //   rsrl::control::td::{QLearning, SARSA, ExpectedSARSA, PAL, SARSALambda, QLambda, GreedyGQ, QSigma}   rsrl/src/control/td/*.rs
 //   rsrl::prediction::td::{TD, TDLambda, GTD2, TDC}         rsrl/src/prediction/td/*.rs
 //   rsrl::control::nac::NAC, rsrl::fa::linear::basis::SCB, LFA::scalar, control::td::SARSA over them      rsrl/src/control/nac.rs, fa/linear.rs:79-103
+//   (over policies::Beta, policies::Gaussian and policies::Gibbs: examples/nac_beta.rs, nac.rs, nac_softmax.rs)
 //   rsrl::make_shared / Shared<T>                            rsrl/src/core.rs:13-44
 //
 // Everything is BATCHED: a Domain is N environments, a state is a column of a [D][N] array.  The objects
@@ -154,7 +155,7 @@ struct Gaussian : Policy {
 }  // namespace policies
 
 // SCB { policy, basis } (fa/linear.rs:79-103), the stable compatible basis: project((s, a)) = grad_log pi(a|s) chained with basis.project(s), 3F
-// features over policies::Beta or policies::Gaussian (held as the Policy they are: its kind is all the descriptor reads).  LFA::scalar(SCB, SGD(lr))
+// features over policies::Beta or policies::Gaussian, (A + 1) F over policies::Gibbs (held as the Policy they are: its kind is all the descriptor reads).  LFA::scalar(SCB, SGD(lr))
 // is the q_func of NAC's SARSA critic (examples/nac_beta.rs, examples/nac.rs)
 namespace fa { namespace linear {
 namespace basis {
@@ -275,6 +276,12 @@ struct NAC : td::Agent {
         : td::Agent{RSRL_NAC, critic.q_func, critic.gamma, alpha_} { n_steps = period; }
     NAC(const td::SARSA& critic, const policies::Gaussian& /*policy*/, double alpha_, int period = 100)
         : td::Agent{RSRL_NAC, critic.q_func, critic.gamma, alpha_} { n_steps = period; }
+    // NAC over policies::Gibbs on the domains with an enumerable action set, the agent of examples/nac_softmax.rs (RSRL_GIBBS_NAC): SCB's features are
+    // grad_log flattened row-major, then phi -- (A + 1) F of them (include/rsrl_hip.h states the one line of SCB::project this restores).  The Session's
+    // weights are the critic's w [(A + 1) F][1], Session::policy_weights the Gibbs policy's theta [F][A]; Session::handle(Transition) is critic.handle,
+    // Session::nac_update() agent.handle(()), Session::evaluate Q(s, b) for every action b ([A][N])
+    NAC(const td::SARSA& critic, const policies::Gibbs& /*policy*/, double alpha_, int period = 100)
+        : td::Agent{RSRL_GIBBS_NAC, critic.q_func, critic.gamma, alpha_} { n_steps = period; }
 };
 }}  // namespace control::nac
 
@@ -414,6 +421,7 @@ public:
         check(rsrl_hip_create(&cfg, &ctx_));
         D_ = rsrl_hip_state_dim(ctx_); A_ = rsrl_hip_n_actions(ctx_); F_ = rsrl_hip_n_features(ctx_); N_ = env.n_envs;
         O_ = rsrl_hip_n_outputs(ctx_); P_ = rsrl_hip_n_policy_outputs(ctx_); R_ = rsrl_hip_n_weight_rows(ctx_);
+        Q_ = agent.algo == RSRL_GIBBS_NAC ? A_ : O_;
     }
     ~Session() { rsrl_hip_destroy(ctx_); }
     Session(const Session&) = delete;
@@ -512,7 +520,7 @@ public:
     }
     // Function<(S,)>::evaluate                                                    (fa/linear.rs:303-311)
     std::vector<float> evaluate(const std::vector<float>& states) {
-        std::vector<float> q((size_t)O_ * N_); check(rsrl_hip_q_evaluate(ctx_, states.data(), N_, q.data())); return q;
+        std::vector<float> q((size_t)Q_ * N_); check(rsrl_hip_q_evaluate(ctx_, states.data(), N_, q.data())); return q;
     }
     // Enumerable::find_max / find_min -> (index, value), ties -> last index        (core.rs:86-105)
     std::pair<std::vector<int32_t>, std::vector<float>> find_max(const std::vector<float>& states) {
@@ -601,6 +609,7 @@ public:
 private:
     rsrl_hip_ctx* ctx_ = nullptr;
     int D_ = 0, A_ = 0, F_ = 0, O_ = 0, P_ = 0, R_ = 0;      // O_: weight columns (A_, or 1 for the prediction agents); P_: the policy's own (A_, or Beta's 2); R_: weight rows (F_, or NAC's 3 F_)
+    int Q_ = 0;                                              // rows of evaluate(): O_, or A_ for NAC over the Gibbs policy (one weight column, a value per action)
     int64_t N_ = 0;
 };
 
