@@ -70,10 +70,24 @@ typedef enum {
  *   f32 (the *_f32 entry points below; their int32 twins are ESTATE, as the *_f32 calls are on the other domains).  Supported:
  *   RSRL_ILSTD_ACTOR_CRITIC, RSRL_NAC and RSRL_CONTINUOUS_TD_ACTOR_CRITIC with policy RSRL_BETA, and RSRL_NAC, RSRL_CACLA and
  *   RSRL_CONTINUOUS_TD_ACTOR_CRITIC with policy RSRL_GAUSSIAN, on the Fourier orders 1-5;
- *   every other combination is EINVAL at create. */
-typedef enum { RSRL_MOUNTAIN_CAR = 0, RSRL_CART_POLE = 1, RSRL_ACROBOT = 2, RSRL_HIV_TREATMENT = 3, RSRL_CONTINUOUS_MOUNTAIN_CAR = 4 } rsrl_domain;
-/* lfa::basis::{Fourier (+with_bias), TileCoding}  (re-exported by rsrl/src/fa/linear.rs:11-14) */
-typedef enum { RSRL_FOURIER = 0, RSRL_TILE_CODING = 1 } rsrl_basis;
+ *   every other combination is EINVAL at create.
+ * CliffWalk (cliff_walk.rs:9-75 over grid_world.rs:87-125): CliffWalk::default() = CliffWalk::new(5, 12), height 5, width 12.  The state is
+ *   loc = [x, y] (D = 2), carried as two f32 that hold the exact integers x in 0..11 and y in 0..4 (rsrl_hip_state_bounds: (0, 11) and (0, 4)), the
+ *   start state [0, 0]; 4 actions, ALL_ACTIONS: 0 North (y <- min(y + 1, 4)), 1 East (x <- min(x + 1, 11)), 2 South (y <- max(y - 1, 0)), 3 West
+ *   (x <- max(x - 1, 0)); terminal iff x > 0 && y == 0 on the new location (cliff_walk.rs:41-47); reward +50 on a terminal step with x == 11, -50 on
+ *   any other terminal step, 0 otherwise (:49-62).  A state component a caller hands in (set_states, handle's from / to, the query calls) is read as
+ *   floor(clamp(s, 0, size - 1)), NaN as 0.  Supported: QLearning, SARSA, ExpectedSARSA, PAL with basis RSRL_TABLE, per-learner f32 tables, no epsilon
+ *   schedule; every other combination that names the domain or the basis is EINVAL at create. */
+typedef enum { RSRL_MOUNTAIN_CAR = 0, RSRL_CART_POLE = 1, RSRL_ACROBOT = 2, RSRL_HIV_TREATMENT = 3, RSRL_CONTINUOUS_MOUNTAIN_CAR = 4,
+               RSRL_CLIFF_WALK = 5 } rsrl_domain;
+/* lfa::basis::{Fourier (+with_bias), TileCoding}  (re-exported by rsrl/src/fa/linear.rs:11-14)
+ * RSRL_TABLE: the tabular function approximator, rsrl/src/fa/tabular/dense.rs, Table<Array2<f64>> -- with RSRL_CLIFF_WALK only, and CliffWalk with it
+ *   only.  F = 60 rows and 4 columns, zero-initialised (Table::zeros); Q(s, .) is the row of s (dense.rs:79-83), the update Q[row, a] += error
+ *   (:118-127).  The reference gives no map from the domain's [usize; 2] to the usize Table is indexed by: here row = x * 5 + y, first component
+ *   major (as the Fourier coefficient order).  Table has no optimiser, so the reference's agents step with size 1; config.lr scales the error (as
+ *   for GTD2 / TDC), and at lr = 1 -- an exact multiplication -- the rule is the reference's literal one.  rsrl_hip_get/set_weights carry the
+ *   (60, 4) matrix row-major; order, n_tilings and tiles_per_dim are not read. */
+typedef enum { RSRL_FOURIER = 0, RSRL_TILE_CODING = 1, RSRL_TABLE = 2 } rsrl_basis;
 /* rsrl::control::td::{QLearning, SARSA, ExpectedSARSA}
  *   q_learning.rs:35-71, sarsa.rs:35-75, expected_sarsa.rs:22-66
  * the eligibility-trace agents {SARSALambda, QLambda}

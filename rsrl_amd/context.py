@@ -8,7 +8,9 @@ from . import _abi
 
 MOUNTAIN_CAR, CART_POLE, ACROBOT, HIV_TREATMENT = 0, 1, 2, 3
 CONTINUOUS_MOUNTAIN_CAR = 4                     # mountain_car/continuous.rs: one f32 action in [-1, 1] (Context.continuous; ILSTD_ACTOR_CRITIC, NAC and CONTINUOUS_TD_ACTOR_CRITIC with BETA; NAC, CACLA and CONTINUOUS_TD_ACTOR_CRITIC with GAUSSIAN)
+CLIFF_WALK = 5                                  # cliff_walk.rs, CliffWalk::default() (height 5, width 12): states (x, y) as exact integers in f32, 4 actions (N, E, S, W); with basis TABLE only
 FOURIER, TILE_CODING = 0, 1
+TABLE = 2                                       # fa/tabular/dense.rs, Table<Array2<f64>>: 60 rows (row = x * 5 + y) of 4 entries, with CLIFF_WALK only; weights (60, 4); lr scales the error (lr = 1: the reference's rule)
 QLEARNING, SARSA, EXPECTED_SARSA, SARSA_LAMBDA, Q_LAMBDA, PAL, GREEDY_GQ, TD, TD_LAMBDA, Q_SIGMA = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 ACTOR_CRITIC, Q_ACTOR_CRITIC = 10, 11          # ActorCritic (control/ac.rs) with a Gibbs actor and a SARSA critic: a2c.rs's closure / QCritic
 TD_ACTOR_CRITIC = 13                           # ActorCritic::tdac: the Gibbs actor with TDCritic over a TD(0) V (12 is no algo)
@@ -77,8 +79,9 @@ def device_count():
 class Context:
     """One object graph of the reference on one GPU, times `n_envs` independent environments in lock-step:
 
-        env    = MountainCar | CartPole | Acrobot | HIVTreatment ::default()                    (domain)
+        env    = MountainCar | CartPole | Acrobot | HIVTreatment | CliffWalk ::default()        (domain)
         basis  = Fourier::from_space(order, ..).with_bias() | TileCoding           (basis, order | n_tilings, tiles_per_dim)
+                 | Table::zeros((60, 4)) for CliffWalk                             (basis=TABLE: the one-step agents on a tabular Q)
         q_func = make_shared(LFA::vector(basis, SGD(lr), n_actions))               (lr; weight_mode: one per env or one shared)
         policy = Greedy | EpsilonGreedy(epsilon) | Softmax(tau) | Random           (policy, epsilon, tau)
         agent  = QLearning{gamma} | SARSA | ExpectedSARSA{alpha} | PAL{alpha}      (algo, gamma, alpha)

@@ -28,6 +28,7 @@ static Switches read_switches() {
     if (const char* e = getenv("RSRL_PEER_TIMEOUT_MS")) sw.peer_timeout_ms = atol(e);
     if (const char* e = getenv("RSRL_WAVE_PK")) sw.no_wave_pk = e[0] == '0';
     if (const char* e = getenv("RSRL_REG_PRODUCER")) sw.no_reg_producer = e[0] == '0';
+    if (const char* e = getenv("RSRL_TABLE_MEM")) sw.table_mem = e[0] != '0' ? 1 : 0;
     return sw;
 }
 bool no_coalesce_switch() { return getenv("RSRL_NO_COALESCE") != nullptr; }
@@ -40,6 +41,7 @@ static AgentFamily classify(const rsrl_hip_config& cfg, size_t w_elems) {
     const bool wave = is_wave(cfg), reg = is_reg_fourier(cfg);
     const int al = cfg.algo;
     if (cfg.domain == RSRL_HIV_TREATMENT) return F::Hiv;
+    if (cfg.domain == RSRL_CLIFF_WALK) return F::CliffTable;
     if (is_ac(al)) return F::AcReg;                         // (before the one-step agents: carries_q is false, no trait fast path)
     if (is_tdac(al)) return F::TdAcReg;                     // (before the prediction agents: W is V's one column, but the policy is the actor's)
     if (is_reinforce(al)) return F::ReinforceReg;
@@ -68,6 +70,7 @@ static const char* train_kernel_name(const rsrl_hip_ctx* c) {
     // (the two families whose kernel the configuration refines; every other name is the family's row of kFamily)
     if (c->family == AgentFamily::WaveControl && c->cfg.weight_dtype == RSRL_W_BF16 && !c->sw.no_wave_pk) return "k_train_wave_pk";
     if (c->family == AgentFamily::RegStep && c->w_ls != 1) return c->k1_quad ? "k_step_reg_q4" : "k_step_reg_lm";
+    if (c->family == AgentFamily::CliffTable && c->sw.table_mem == 1) return "k_table_train_mem";      // (by launch depth otherwise: launch_agent names it)
     return family_row(c).kernel;
 }
 // one statistics slot per thread block of the family's driver-loop kernel
@@ -170,8 +173,8 @@ static int check_reg_only(const rsrl_hip_config& cfg, const AlgoRow& a, bool sto
     return RSRL_HIP_OK;
 }
 
-// (state dimension, action count) of MountainCar, CartPole, Acrobot, HIVTreatment, ContinuousMountainCar (0: the action set is not enumerable)
-static const int kDomainShape[5][2] = {{2, 3}, {4, 2}, {4, 3}, {6, 4}, {2, 0}};
+// (state dimension, action count) of MountainCar, CartPole, Acrobot, HIVTreatment, ContinuousMountainCar (0: the action set is not enumerable), CliffWalk
+static const int kDomainShape[6][2] = {{2, 3}, {4, 2}, {4, 3}, {6, 4}, {2, 0}, {2, 4}};
 
 // ContinuousMountainCar and the continuous policies (cont_policy.hpp; train_tdac_beta.hip, train_nac.hip, train_cont.hip):
 // the domain exists for them only and they for it, Beta under the iLSTD ActorCritic, NAC and the continuous TD ActorCritic, Gaussian under NAC, CACLA
@@ -204,7 +207,7 @@ static int check_continuous(const rsrl_hip_config& cfg, const AlgoRow& a, bool s
 // which kernels exist, one block per agent group; the register-family-only agents (check_reg_only) and HIVTreatment are whole rules of their own.
 static int check_config(const rsrl_hip_config& cfg) {
     // ---- field ranges
-    if (cfg.domain < RSRL_MOUNTAIN_CAR || cfg.domain > RSRL_CONTINUOUS_MOUNTAIN_CAR) return fail(RSRL_HIP_EINVAL, "unknown domain %d", cfg.domain);
+    if (cfg.domain < RSRL_MOUNTAIN_CAR || cfg.domain > RSRL_CLIFF_WALK) return fail(RSRL_HIP_EINVAL, "unknown domain %d", cfg.domain);
     const int D = kDomainShape[cfg.domain][0], A = kDomainShape[cfg.domain][1];
     if (cfg.n_envs < 1) return fail(RSRL_HIP_EINVAL, "n_envs must be >= 1");
     if (cfg.n_envs + cfg.env_offset > (int64_t)0xffffffffLL || cfg.env_offset < 0) return fail(RSRL_HIP_EINVAL, "global env ids must fit 32 bits");
@@ -230,7 +233,7 @@ static int check_config(const rsrl_hip_config& cfg) {
         if (cells > (int64_t)1 << 30 || cells * cfg.n_tilings > (int64_t)1 << 30) return fail(RSRL_HIP_EINVAL, "tile table too large");
         // (a shared table is gathered through one 32-bit buffer descriptor)
         if (shared && cells * cfg.n_tilings * A * 4 >= (int64_t)1 << 31) return fail(RSRL_HIP_EINVAL, "a shared tile table must be smaller than 2 GiB");
-    } else {
+    } else if (cfg.basis != RSRL_TABLE) {      // (the table reads none of order, n_tilings, tiles_per_dim)
         return fail(RSRL_HIP_EINVAL, "unknown basis %d", cfg.basis);
     }
     if (cfg.algo == RSRL_TD_LAMBDA || is_lambda(cfg.algo)) {
@@ -250,6 +253,17 @@ static int check_config(const rsrl_hip_config& cfg) {
     const bool tile = cfg.basis == RSRL_TILE_CODING, reg = is_reg_fourier(cfg), wave = is_wave(cfg);
     const bool f32 = cfg.weight_dtype == RSRL_W_F32, esched = cfg.epsilon_decay != 1.0;
     const bool one_step = kAlgo[al].agent == Agent::OneStep;
+    // train_table.hip: CliffWalk exists for the tabular Q only and the table for it only -- a rule of its own, in front of every agent's: whatever else the
+    // configuration names, the refusal names CliffWalk
+    if (cfg.domain == RSRL_CLIFF_WALK || cfg.basis == RSRL_TABLE) {
+        if (cfg.domain != RSRL_CLIFF_WALK || cfg.basis != RSRL_TABLE || !one_step || !per_env || !f32 || esched || cfg.policy > RSRL_RANDOM)
+            return fail(RSRL_HIP_EINVAL, "CliffWalk (RSRL_CLIFF_WALK) and the tabular Q (RSRL_TABLE) support each other only, with QLearning, SARSA, ExpectedSARSA "
+                                         "and PAL under the Greedy, EpsilonGreedy, Softmax and Random policies, per-learner f32 tables and no epsilon schedule: "
+                                         "this combination is unknown to the library (got domain %d, basis %d, algo %d, policy %d, weight mode %d, dtype %d, "
+                                         "epsilon_decay %g)",
+                        cfg.domain, cfg.basis, al, cfg.policy, cfg.weight_mode, cfg.weight_dtype, cfg.epsilon_decay);
+        return RSRL_HIP_OK;
+    }
     // (NAC over the Gibbs policy names itself in every refusal, the continuous domain's and policies' included)
     if (is_gibbs_nac(al)) return check_reg_only(cfg, kAlgo[al], reg && per_env && f32 && !esched);
     if (cfg.domain == RSRL_CONTINUOUS_MOUNTAIN_CAR || cfg.policy == RSRL_BETA || cfg.policy == RSRL_GAUSSIAN || al == RSRL_NAC || al == RSRL_CACLA || al == RSRL_CONTINUOUS_TD_ACTOR_CRITIC)
@@ -297,6 +311,7 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
     c->F = 1;
     for (int i = 0; i < c->D; ++i) c->F *= cfg->basis == RSRL_FOURIER ? cfg->order + 1 : cfg->tiles_per_dim;
     if (cfg->basis == RSRL_TILE_CODING) c->F *= cfg->n_tilings;
+    if (cfg->basis == RSRL_TABLE) c->F = Domain<5>::kCells;      // one row per cell
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (ndev < 1) return fail(RSRL_HIP_EHIP, "no HIP device");
@@ -492,6 +507,7 @@ int rsrl_hip_state_bounds(const rsrl_hip_ctx* c, double* lo, double* hi) {
         case 1: lo[i] = Domain<1>::lo_d(i); hi[i] = Domain<1>::hi_d(i); break;
         case 2: lo[i] = Domain<2>::lo_d(i); hi[i] = Domain<2>::hi_d(i); break;
         case 4: lo[i] = Domain<4>::lo_d(i); hi[i] = Domain<4>::hi_d(i); break;
+        case 5: lo[i] = Domain<5>::lo_d(i); hi[i] = Domain<5>::hi_d(i); break;
         default: lo[i] = -5.0; hi[i] = 8.0; break;            // HIVTreatment: LIMITS of every observation component (hiv.rs:34, :137-145)
         }
     }
@@ -558,6 +574,8 @@ int rsrl_hip_reset(rsrl_hip_ctx* c) {
         if (!launch_cont_reset(c->cfg.order, cont_policy(c), c->stream, k, c->Z, c->t, c->action_f)) return NO_MODEL(c);
     } else if (c->family == AgentFamily::Hiv) {
         launch_hiv_reset(c->stream, k, g, c->hiv_y, c->t);
+    } else if (c->family == AgentFamily::CliffTable) {
+        launch_table_reset(c->stream, k, c->t);
     } else if (is_v_only(c->cfg.algo)) {       // (the LSTD agents' state is untouched: the weights are not reset either; GradientMC's records empty with ep_step = 0)
         if (!launch_reset_td(c->cfg.domain, dim3(grid_for(k.n_envs)), dim3(kBlock), c->stream, k, c->t)) return NO_MODEL(c);
     } else if (is_wave_family(c->family)) {

@@ -411,6 +411,14 @@ int launch_agent(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, uint64_t 
         if (io) launch_hiv_handle(c->stream, k, g, *io, t);
         else launch_hiv_train(c->stream, k, g, c->hiv_y, t, chunk, d_stats);
         break;
+    case AgentFamily::CliffTable:
+        if (io) { launch_table_handle(c->stream, k, *io, t); break; }
+        {   // the memory loop for launches too short to pay for staging the tables (RSRL_TABLE_MEM=1 forces it, =0 forbids it); the same bits either way
+            const bool mem = c->sw.table_mem >= 0 ? c->sw.table_mem == 1 : chunk < kTableMemBelow;
+            launch_table_train(c->stream, k, !mem, t, chunk, d_stats);
+            c->train_kernel = mem ? "k_table_train_mem" : "k_table_train_lds";
+        }
+        break;
     case AgentFamily::AcReg:
         ok = launch_ac(cf.domain, cf.order, cf.algo == RSRL_Q_ACTOR_CRITIC ? AC_CRITIC_Q : AC_CRITIC_ADVANTAGE, grid, block, c->stream, k, c->Z, t, chunk, d_stats, io);
         break;
@@ -638,6 +646,8 @@ static int rollout_impl(rsrl_hip_ctx* c, int64_t step_limit, int64_t M, uint32_t
     const BasisGeom g = make_geom(c);
     if (c->family == AgentFamily::Hiv) {
         launch_hiv_rollout(c->stream, k, g, step_limit, d_n, d_total, M, tr, rp);
+    } else if (c->family == AgentFamily::CliffTable) {
+        launch_table_rollout(c->stream, k, step_limit, d_n, d_total, M, tr, rp);
     } else if (is_wave_family(c->family)) {
         for_wave(c, [&](auto tag) {
             using T = decltype(tag); using WT = typename T::wt;

@@ -16,6 +16,7 @@ int trait_cache_ready(rsrl_hip_ctx* c) {
 int launch_domain_step(rsrl_hip_ctx* c, const Common& k, const int32_t* d_act, float* from, float* next, float* rew, uint8_t* term) {
     const dim3 g(grid_for(c->cfg.n_envs)), b(kBlock);
     if (c->hiv_y) { launch_hiv_domain_step(c->stream, k, c->hiv_y, d_act, from, next, rew, term); KCHECK(); return RSRL_HIP_OK; }
+    if (c->family == AgentFamily::CliffTable) { launch_table_domain_step(c->stream, k, d_act, from, next, rew, term); KCHECK(); return RSRL_HIP_OK; }
     switch (c->cfg.domain) {
     case 0: hipLaunchKernelGGL(k_domain_step<0>, g, b, 0, c->stream, k, d_act, from, next, rew, term); break;
     case 1: hipLaunchKernelGGL(k_domain_step<1>, g, b, 0, c->stream, k, d_act, from, next, rew, term); break;
@@ -28,6 +29,7 @@ int launch_domain_step(rsrl_hip_ctx* c, const Common& k, const int32_t* d_act, f
 int launch_domain_reset(rsrl_hip_ctx* c, const Common& k, const uint8_t* d_mask) {
     const dim3 g(grid_for(c->cfg.n_envs)), b(kBlock);
     if (c->hiv_y) { launch_hiv_domain_reset(c->stream, k, c->hiv_y, d_mask); KCHECK(); return RSRL_HIP_OK; }
+    if (c->family == AgentFamily::CliffTable) { launch_table_domain_reset(c->stream, k, d_mask); KCHECK(); return RSRL_HIP_OK; }
     switch (c->cfg.domain) {
     case 0: case RSRL_CONTINUOUS_MOUNTAIN_CAR:      // (ContinuousMountainCar: MountainCar's state space and start state)
         hipLaunchKernelGGL(k_domain_reset<0>, g, b, 0, c->stream, k, d_mask); break;
@@ -205,6 +207,8 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
         if (!ok) return NO_MODEL(c);
     } else if (c->family == AgentFamily::Hiv) {
         launch_hiv_qop(c->stream, k, g, op, d_states, M_, call, d_fout, d_iout, d_fin, d_iin);
+    } else if (c->family == AgentFamily::CliffTable) {
+        launch_table_qop(c->stream, k, op, d_states, M_, call, d_fout, d_iout, d_fin, d_iin);
     } else if (is_wave_family(c->family)) {
         for_wave(c, [&](auto tag) {
             using T = decltype(tag); using WT = typename T::wt;

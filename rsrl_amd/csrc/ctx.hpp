@@ -238,8 +238,10 @@ enum class AgentFamily : uint8_t {
                           // the iLSTD critic's family)
     GibbsNacReg,          // NAC over the Gibbs policy with the SCB SARSA critic, AcReg's configurations: k_train_gibbs_nac (train_gibbs_nac.hip); the critic's w in W
                           // ((A+1) F rows, one column), theta in Z (A columns)
+    CliffTable,           // CliffWalk over the tabular Q (RSRL_TABLE): one-step agents, per-learner f32 tables W f32[4][60][N]: k_table_train_lds, or
+                          // k_table_train_mem for launches below kTableMemBelow batch-steps (train_table.hip)
 };
-constexpr size_t kAgentFamilies = (size_t)AgentFamily::GibbsNacReg + 1;      // (the enum's last value)
+constexpr size_t kAgentFamilies = (size_t)AgentFamily::CliffTable + 1;      // (the enum's last value)
 // ---- THE family table: which kernels serve a family and what they can do, one row per AgentFamily value in the enum's order.  classify() (abi_ctx.hip: a
 // decision) and launch_agent (abi_train.hip: it instantiates the templates) are the two other places a new family is entered.
 enum class Slots : uint8_t { Block, Block64, WaveBlock, Learner, LstdGroup };      // a statistics slot per: kBlock learners, 64 learners (k_train_lambda_mem4; the
@@ -266,6 +268,13 @@ struct FamilyRow {
 // sub-steps per learner, ~1 ms at 65 536 learners -- 16 keep a launch in the tens of milliseconds.  GradientMC starts from TdReg's 4 096: at 65 536
 // MountainCar order-3 learners (cap 1 000) the median of seven 8 192-step regions is 1.887 / 1.890 / 1.800 us per batch-step at 1 024 / 4 096 /
 // 16 384 steps per launch, inside the regions' own drift (1.14 -> 2.13 us as the learners' episodes fall out of step; profiles/gmc_rate.md).
+// CliffWalk's two loops (train_table.hip): k_table_train_lds stages 960 B per learner each way around a launch, k_table_train_mem gathers every row from
+// memory.  Measured at 65 536 learners (QLearning, EpsilonGreedy; profiles/cliff_walk_rate.md), us per batch-step: the LDS loop 2.94 / 1.41 / 1.32 at
+// 16 / 256 / 4 096 batch-steps per launch, the memory loop 8.00 / 2.91 / 2.52 at 1 / 16 / 256.  kTableDepth: the fastest LDS depth measured.
+// kTableMemBelow: launches of FEWER batch-steps take the memory loop -- the curves (1.32 + 26 / d against 2.52 + 5.5 / d) cross at d = 17, and at 16 the
+// two medians are 1.2 % apart, inside the memory loop's own range
+constexpr int kTableDepth = 4096;
+constexpr int kTableMemBelow = 16;
 constexpr FamilyRow kFamily[] = {
     {AgentFamily::SharedDense, "k_shared_step", 256, Slots::Block, Handle::Model, 0},
     {AgentFamily::SharedTile, "k_shared_ca", 256, Slots::Block, Handle::Model, 0},
@@ -307,6 +316,8 @@ constexpr FamilyRow kFamily[] = {
                                                                                                                    // Beta sampler's scalar chain dominates, the depth is CaclaGaussReg's all the same)
     {AgentFamily::GibbsNacReg, "k_train_gibbs_nac", 4096, Slots::Block, Handle::Agent, kPolicyW},      // (measured at 65 536 order-3 learners: 1.75 / 1.72 / 1.70 us per batch-step at
                                                                                                        // 256 / 1 024 / 4 096 steps per launch, k_train_ac 1.66 in the same process: profiles/gibbs_nac_rate.md)
+    {AgentFamily::CliffTable, "k_table_train_lds", kTableDepth, Slots::Block64, Handle::Agent, 0},      // (one wave per block; the depth and the switch to k_table_train_mem:
+                                                                                                        // kTableDepth / kTableMemBelow above, profiles/cliff_walk_rate.md)
 };
 constexpr bool family_rows_in_order() {
     for (size_t i = 0; i < sizeof(kFamily) / sizeof(kFamily[0]); ++i) if ((size_t)kFamily[i].family != i) return false;
@@ -326,6 +337,7 @@ struct Switches {
     long peer_timeout_ms = 0;         // RSRL_PEER_TIMEOUT_MS (0 = unset)
     bool no_wave_pk = false;          // RSRL_WAVE_PK=0: bf16 ctxs of the order-7 wave family on the fp32-register kernel k_train_wave
     bool no_reg_producer = false;     // RSRL_REG_PRODUCER=0: the fused loop keeps generating its own draws (k_train_reg instead of pw::k_train_reg)
+    int table_mem = -1;               // RSRL_TABLE_MEM: 1 forces CliffWalk's memory loop (k_table_train_mem), 0 forbids it, -1 = by launch depth (kTableMemBelow)
 };
 
 struct rsrl_hip_ctx {
@@ -643,6 +655,8 @@ static bool is_wave(const rsrl_hip_config& cfg) {
 static inline unsigned wave_grid_for(int64_t items) { return (unsigned)((items + (kBlock / 64) - 1) / (kBlock / 64)); }
 // the HIVTreatment entry point of a multi-rank call: per-learner weights only, nothing to exchange
 #define HIV_NO_EXCHANGE(c) do { if ((c)->cfg.domain == RSRL_HIV_TREATMENT) return fail(RSRL_HIP_EINVAL, "HIVTreatment supports per-learner weights only: " \
+    "no communicator, peer exchange or group (shard by env_offset instead)"); \
+    if ((c)->cfg.domain == RSRL_CLIFF_WALK) return fail(RSRL_HIP_EINVAL, "CliffWalk supports per-learner tables only: " \
     "no communicator, peer exchange or group (shard by env_offset instead)"); } while (0)
 #define NO_MODEL(c) fail(RSRL_HIP_EINVAL, "no kernel for basis %d domain %d order %d tilings %d", (c)->cfg.basis, (c)->cfg.domain, (c)->cfg.order, (c)->cfg.n_tilings)
 

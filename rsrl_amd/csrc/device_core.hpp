@@ -456,6 +456,37 @@ template <> struct Domain<2> {
     }
 };
 
+// CliffWalk::default() = CliffWalk::new(5, 12)      rsrl_domains/src/cliff_walk.rs:9-75 over grid_world.rs:87-125
+// loc = [x, y], x in 0..11, y in 0..4, carried as two f32 that hold the exact integers; the motions clamp at the four walls, the episode ends on
+// the bottom row right of the start column (the cliff, and the goal at x = 11).  A component a caller hands in is read as
+// floor(clamp(s, 0, size - 1)), NaN as 0 (cell): the tile coder's idiom -- whatever the input, the cell is one of the 60.
+template <> struct Domain<5> {
+    static constexpr int D = 2, A = 4;
+    static constexpr int kWidth = 12, kHeight = 5, kCells = kWidth * kHeight;
+    __host__ __device__ static constexpr double lo_d(int) { return 0.0; }
+    __host__ __device__ static constexpr double hi_d(int i) { return i == 0 ? (double)(kWidth - 1) : (double)(kHeight - 1); }
+    __device__ static __forceinline__ int cell(float s, int size) { return (int)floorf(fminf(fmaxf(s, 0.0f), (float)(size - 1))); }      // (fmaxf(NaN, 0) = 0)
+    // the Table's row of [x, y]: first component major (the reference gives no map from [usize; 2] to Table's usize: the library's choice)
+    __device__ static __forceinline__ int row(int x, int y) { return x * kHeight + y; }
+    // ALL_ACTIONS: 0 North (y + 1), 1 East (x + 1), 2 South (y - 1), 3 West (x - 1) (grid_world.rs:87-125); terminal iff x > 0 && y == 0 on the new
+    // location (cliff_walk.rs:41-47); reward +50 at the goal, -50 in the cliff, 0 otherwise
+    __device__ static __forceinline__ bool step_cell(int& x, int& y, int a, float& r) {
+        const int nx = a == 1 ? min(x + 1, kWidth - 1) : (a == 3 ? max(x - 1, 0) : x);
+        const int ny = a == 0 ? min(y + 1, kHeight - 1) : (a == 2 ? max(y - 1, 0) : y);
+        x = nx; y = ny;
+        const bool term = nx > 0 && ny == 0;
+        r = term ? (nx == kWidth - 1 ? 50.0f : -50.0f) : 0.0f;
+        return term;
+    }
+    __device__ static __forceinline__ void reset(float (&s)[D]) { s[0] = 0.0f; s[1] = 0.0f; }
+    __device__ static __forceinline__ bool step(float (&s)[D], int a, float& r) {
+        int x = cell(s[0], kWidth), y = cell(s[1], kHeight);
+        const bool term = step_cell(x, y, a, r);
+        s[0] = (float)x; s[1] = (float)y;
+        return term;
+    }
+};
+
 // ---------------------------------------------------------------------------------------
 // argmax helpers and policies
 // ---------------------------------------------------------------------------------------

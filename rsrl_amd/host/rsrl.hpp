@@ -8,6 +8,7 @@
 //   rsrl::control::cacla::CACLA                                     rsrl/src/control/cacla.rs
 //   rsrl::control::ac::ActorCritic::tdac(TD, Gaussian | Beta, ..)    rsrl/src/control/ac.rs over prediction/td/td.rs (RSRL_CONTINUOUS_TD_ACTOR_CRITIC)
 //   rsrl::fa::linear::{basis::Fourier, optim::SGD, LFA}  rsrl/src/fa/linear.rs (re-exports of crate lfa)
+//   rsrl::domains::CliffWalk, rsrl::fa::tabular::Table              rsrl_domains/src/cliff_walk.rs, rsrl/src/fa/tabular/dense.rs
 //   rsrl::policies::{Greedy, EpsilonGreedy, Softmax, Random}   rsrl/src/policies/*.rs
 //   rsrl::control::td::{QLearning, SARSA, ExpectedSARSA, PAL, SARSALambda, QLambda, GreedyGQ, QSigma}   rsrl/src/control/td/*.rs
 //   rsrl::prediction::td::{TD, TDLambda, GTD2, TDC}         rsrl/src/prediction/td/*.rs
@@ -76,6 +77,9 @@ struct Acrobot : Domain { explicit Acrobot(int64_t n = 1) : Domain{RSRL_ACROBOT,
 struct HIVTreatment : Domain { explicit HIVTreatment(int64_t n = 1) : Domain{RSRL_HIV_TREATMENT, n} {} };     // hiv.rs: f64 hidden state (rsrl_hip_get_hidden_states)
 // mountain_car/continuous.rs: MountainCar's state space with one f32 action in [-1, 1] (Session::transition_f32 / sample_f32; n_actions() is 0)
 struct ContinuousMountainCar : Domain { explicit ContinuousMountainCar(int64_t n = 1) : Domain{RSRL_CONTINUOUS_MOUNTAIN_CAR, n} {} };
+// cliff_walk.rs: CliffWalk::default(), height 5, width 12; states (x, y) as exact integers in f32, 4 actions (North, East, South, West); with
+// fa::tabular::Table only
+struct CliffWalk : Domain { explicit CliffWalk(int64_t n = 1) : Domain{RSRL_CLIFF_WALK, n} {} };
 }  // namespace domains
 
 // ---- rsrl::fa::linear ------------------------------------------------------------------------------
@@ -105,6 +109,20 @@ struct LFA {                              // LFA::vector(basis, SGD(lr), n_actio
     static inline LFA scalar(const basis::SCB& b, optim::SGD o);      // LFA::scalar(SCB{policy, basis}, SGD(lr)) (nac_beta.rs:38-42; defined below SCB)
 };
 }}  // namespace fa::linear
+
+// ---- rsrl::fa::tabular (fa/tabular/dense.rs) ---------------------------------------------------------
+// Table::zeros((n_rows, n_actions)): Q(s, .) is a row, the update adds the error to one entry.  The reference's Table has no optimiser (its agents step
+// with size 1): `step` scales the error on the device, 1.0 being the reference's literal rule.  For domains::CliffWalk, 60 rows (row = x * 5 + y) of 4
+namespace fa { namespace tabular {
+struct Table : linear::LFA {
+    static Table zeros(int n_rows, int n_actions, double step = 1.0) {
+        if (n_rows != 60 || n_actions != 4) throw Error(RSRL_HIP_EINVAL, "the device table is CliffWalk::default()'s: 60 rows of 4 actions");
+        Table t;
+        t.basis_kind = RSRL_TABLE; t.order = 0; t.n_tilings = 0; t.tiles_per_dim = 0; t.lr = step;
+        return t;
+    }
+};
+}}  // namespace fa::tabular
 
 // ---- rsrl::policies --------------------------------------------------------------------------------
 namespace policies {
