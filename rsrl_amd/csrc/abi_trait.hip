@@ -17,12 +17,8 @@ int launch_domain_step(rsrl_hip_ctx* c, const Common& k, const int32_t* d_act, f
     const dim3 g(grid_for(c->cfg.n_envs)), b(kBlock);
     if (c->hiv_y) { launch_hiv_domain_step(c->stream, k, c->hiv_y, d_act, from, next, rew, term); KCHECK(); return RSRL_HIP_OK; }
     if (c->family == AgentFamily::CliffTable) { launch_table_domain_step(c->stream, k, d_act, from, next, rew, term); KCHECK(); return RSRL_HIP_OK; }
-    switch (c->cfg.domain) {
-    case 0: hipLaunchKernelGGL(k_domain_step<0>, g, b, 0, c->stream, k, d_act, from, next, rew, term); break;
-    case 1: hipLaunchKernelGGL(k_domain_step<1>, g, b, 0, c->stream, k, d_act, from, next, rew, term); break;
-    case RSRL_CONTINUOUS_MOUNTAIN_CAR: return fail(RSRL_HIP_ESTATE, "ContinuousMountainCar steps on f32 actions (rsrl_hip_domain_step_f32)");
-    default: hipLaunchKernelGGL(k_domain_step<2>, g, b, 0, c->stream, k, d_act, from, next, rew, term); break;
-    }
+    if (c->cfg.domain == RSRL_CONTINUOUS_MOUNTAIN_CAR) return fail(RSRL_HIP_ESTATE, "ContinuousMountainCar steps on f32 actions (rsrl_hip_domain_step_f32)");
+    if (!for_domain3(c->cfg.domain, [&](auto d) { hipLaunchKernelGGL(k_domain_step<d.value>, g, b, 0, c->stream, k, d_act, from, next, rew, term); })) return NO_MODEL(c);
     KCHECK();
     return RSRL_HIP_OK;
 }
@@ -30,12 +26,9 @@ int launch_domain_reset(rsrl_hip_ctx* c, const Common& k, const uint8_t* d_mask)
     const dim3 g(grid_for(c->cfg.n_envs)), b(kBlock);
     if (c->hiv_y) { launch_hiv_domain_reset(c->stream, k, c->hiv_y, d_mask); KCHECK(); return RSRL_HIP_OK; }
     if (c->family == AgentFamily::CliffTable) { launch_table_domain_reset(c->stream, k, d_mask); KCHECK(); return RSRL_HIP_OK; }
-    switch (c->cfg.domain) {
-    case 0: case RSRL_CONTINUOUS_MOUNTAIN_CAR:      // (ContinuousMountainCar: MountainCar's state space and start state)
-        hipLaunchKernelGGL(k_domain_reset<0>, g, b, 0, c->stream, k, d_mask); break;
-    case 1: hipLaunchKernelGGL(k_domain_reset<1>, g, b, 0, c->stream, k, d_mask); break;
-    default: hipLaunchKernelGGL(k_domain_reset<2>, g, b, 0, c->stream, k, d_mask); break;
-    }
+    // (ContinuousMountainCar: MountainCar's state space and start state)
+    const int domain = c->cfg.domain == RSRL_CONTINUOUS_MOUNTAIN_CAR ? RSRL_MOUNTAIN_CAR : c->cfg.domain;
+    if (!for_domain3(domain, [&](auto d) { hipLaunchKernelGGL(k_domain_reset<d.value>, g, b, 0, c->stream, k, d_mask); })) return NO_MODEL(c);
     KCHECK();
     return RSRL_HIP_OK;
 }
@@ -185,12 +178,9 @@ static int qop(rsrl_hip_ctx* c, int op, const float* states, int64_t M_, float* 
     } else if (is_td_v_continuous(c->cfg.algo) && op == QOP_EVALUATE) {   // V(s) of CACLA's / the continuous TD ActorCritic's TD learner: k_v_evaluate on MountainCar's projection
         if (!launch_v_evaluate(feature_domain(c), c->cfg.order, dim3(grid_for(M_)), dim3(kBlock), c->stream, k, d_states, M_, d_fout)) return NO_MODEL(c);
     } else if (is_continuous(c)) {                                        // QOP_FEATURES: MountainCar's projection at the same order
-        bool ok = false;
-#define X(DM, OR) if (DM == RSRL_MOUNTAIN_CAR && c->cfg.order == OR) { \
-            hipLaunchKernelGGL((k_qop<FourierModel<DM, OR>>), dim3(grid_for(M_)), dim3(kBlock), 0, c->stream, k, g, op, d_states, M_, call, d_fout, d_iout, d_fin, d_iin); ok = true; }
-        RSRL_REG_FOURIER(X)
-#undef X
-        if (!ok) return NO_MODEL(c);
+        if (!for_reg_fourier(RSRL_MOUNTAIN_CAR, c->cfg.order, [&](auto m) {
+                hipLaunchKernelGGL((k_qop<typename decltype(m)::type>), dim3(grid_for(M_)), dim3(kBlock), 0, c->stream, k, g, op, d_states, M_, call, d_fout, d_iout, d_fin, d_iin);
+            })) return NO_MODEL(c);
     } else if ((is_pred(c->cfg.algo) || is_tdac(c->cfg.algo) || is_gmc(c->cfg.algo) || is_gtd(c->cfg.algo)) && op == QOP_EVALUATE) {      // V(s) (the TD ActorCritic, GradientMC: their w; GTD2 / TDC: theta; k_v_evaluate)
         bool ok = true;
         switch (c->family) {

@@ -615,7 +615,6 @@ static bool for_wave(const rsrl_hip_ctx* c, Fn&& fn) {
     return false;
 }
 
-static inline unsigned grid_for(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 // resolution of the fixed-point delta tables of shared tile coding: 2^(floor(log2 |lr|) - 28), the same bits the kernel derives
 static inline float tile_lsb(float lr) {
     uint32_t u; memcpy(&u, &lr, 4);
@@ -628,22 +627,12 @@ constexpr int kSharedBlock = 512;    // learners per block of k_shared_step: 256
 
 // ---- (basis, domain, parameter) -> Model type: model_list.hpp
 static bool model_supported(const rsrl_hip_config& cfg) {
-    if (is_reg_fourier(cfg)) return true;
-#define X(TYPE, BS, DM, P) if (model_match(cfg, BS, DM, P)) return true;
-    RSRL_MEM_MODELS(X)
-#undef X
-    return false;
+    return is_reg_fourier(cfg) || for_mem_model(cfg, [](auto) {});
 }
-// calls fn(Tag<Model>{}) for the ctx's model, first match; false if none matches
+// calls fn(tag) with tag::type the ctx's model, first match; false if none matches
 template <class Fn>
 static bool for_model(const rsrl_hip_ctx* c, Fn&& fn) {
-#define X(DM, OR) if (model_match(c->cfg, RSRL_FOURIER, DM, OR)) { fn(Tag<FourierModel<DM, OR>>{}); return true; }
-    RSRL_REG_FOURIER(X)
-#undef X
-#define X(TYPE, BS, DM, P) if (model_match(c->cfg, BS, DM, P)) { fn(Tag<RSRL_UNPAREN TYPE>{}); return true; }
-    RSRL_MEM_MODELS(X)
-#undef X
-    return false;
+    return (c->cfg.basis == RSRL_FOURIER && for_reg_fourier(c->cfg.domain, c->cfg.order, fn)) || for_mem_model(c->cfg, fn);
 }
 static BasisGeom make_geom(const rsrl_hip_ctx* c) {
     return BasisGeom{c->F, c->cfg.basis == RSRL_FOURIER ? c->cfg.order : c->cfg.tiles_per_dim};

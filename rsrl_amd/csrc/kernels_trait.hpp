@@ -25,6 +25,7 @@
 #pragma once
 
 #include "kernels_reg.hpp"
+#include "launch.hpp"
 
 namespace rsrl {
 
@@ -257,23 +258,22 @@ bool launch_trait_lm(int domain, int order, int algo, int policy, hipStream_t st
 bool launch_trait_sample(int domain, int order, hipStream_t st, const Common& k, const float* states, int64_t Mn, uint64_t t, uint32_t blk, float* qkey,
                          float* qval, int32_t* actions_out);
 bool trait_lm_available(int domain, int order, int algo);
-}  // namespace rsrl
 
-#define RSRL_TRAIT_CASE(DM, OR, AL)                                                                                                              \
-    if (domain == DM && order == OR && algo == AL) {                                                                                             \
-        const dim3 grid((unsigned)(((policy < 0 ? io.Mn : k.n_envs) + kBlock - 1) / kBlock)), block(kBlock);                                   \
-        switch (policy) {                                                                                                                        \
-        case 0: hipLaunchKernelGGL((k_trait_lm<DM, OR, AL, 0, TRAIT_STEP>), grid, block, 0, st, k, io, t); break;                              \
-        case 1: hipLaunchKernelGGL((k_trait_lm<DM, OR, AL, 1, TRAIT_STEP>), grid, block, 0, st, k, io, t); break;                              \
-        case 2: hipLaunchKernelGGL((k_trait_lm<DM, OR, AL, 2, TRAIT_STEP>), grid, block, 0, st, k, io, t); break;                              \
-        case 3: hipLaunchKernelGGL((k_trait_lm<DM, OR, AL, 3, TRAIT_STEP>), grid, block, 0, st, k, io, t); break;                              \
-        default: hipLaunchKernelGGL((k_trait_lm<DM, OR, AL, -1, TRAIT_HANDLE>), grid, block, 0, st, k, io, t); break;                          \
-        }                                                                                                                                        \
-        return true;                                                                                                                             \
-    }
-#define RSRL_TRAIT_ALGOS(DM, OR) RSRL_TRAIT_CASE(DM, OR, 0) RSRL_TRAIT_CASE(DM, OR, 1) RSRL_TRAIT_CASE(DM, OR, 2) RSRL_TRAIT_CASE(DM, OR, 5)
-#define RSRL_TRAIT_SAMPLE_CASE(DM, OR)                                                                                                           \
-    if (domain == DM && order == OR) {                                                                                                           \
-        hipLaunchKernelGGL((k_trait_sample<DM, OR>), dim3((unsigned)((Mn + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, k, states, Mn, t, blk, qkey, qval, actions_out); \
-        return true;                                                                                                                             \
-    }
+// the (MountainCar, ORs...) or (DM, 1) instantiations of one translation unit
+template <int DM, int... ORs>
+static inline bool launch_trait_lm_orders(int order, int algo, int policy, hipStream_t st, const Common& k, const TraitIo& io, uint64_t t) {
+    bool found = false;
+    for_int<ORs...>(order, [&](auto o) { found = for_one_step_algo(algo, [&](auto al) {
+        constexpr int OR = decltype(o)::value, AL = al.value;
+        const dim3 grid(grid_for(policy < 0 ? io.Mn : k.n_envs)), block(kBlock);
+        switch (policy) {
+        case 0: hipLaunchKernelGGL((k_trait_lm<DM, OR, AL, 0, TRAIT_STEP>), grid, block, 0, st, k, io, t); break;
+        case 1: hipLaunchKernelGGL((k_trait_lm<DM, OR, AL, 1, TRAIT_STEP>), grid, block, 0, st, k, io, t); break;
+        case 2: hipLaunchKernelGGL((k_trait_lm<DM, OR, AL, 2, TRAIT_STEP>), grid, block, 0, st, k, io, t); break;
+        case 3: hipLaunchKernelGGL((k_trait_lm<DM, OR, AL, 3, TRAIT_STEP>), grid, block, 0, st, k, io, t); break;
+        default: hipLaunchKernelGGL((k_trait_lm<DM, OR, AL, -1, TRAIT_HANDLE>), grid, block, 0, st, k, io, t); break;
+        }
+    }); });
+    return found;
+}
+}  // namespace rsrl

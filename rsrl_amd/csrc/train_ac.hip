@@ -8,19 +8,15 @@
 
 namespace rsrl {
 
-#define RSRL_AC_CASE(DM, OR, CR)                                                                                                            \
-    if (domain == DM && order == OR && critic == CR) {                                                                                    \
-        if (io) hipLaunchKernelGGL((k_handle_ac<DM, OR, CR>), grid, block, 0, st, k, theta, io->from, io->act, io->rew, io->to, io->term, io->M, t, \
-                                   io->td_out);                                                                                           \
-        else hipLaunchKernelGGL((k_train_ac<DM, OR, CR>), grid, block, 0, st, k, theta, t, chunk, stats);                                  \
-        return true;                                                                                                                      \
-    }
-#define RSRL_AC_CRITICS(DM, OR) RSRL_AC_CASE(DM, OR, AC_CRITIC_ADVANTAGE) RSRL_AC_CASE(DM, OR, AC_CRITIC_Q)
-
 bool launch_ac(int domain, int order, int critic, dim3 grid, dim3 block, hipStream_t st, const Common& k, float* theta, uint64_t t, int chunk,
                DevStats* stats, const Transitions* io) {
-    RSRL_REG_FOURIER(RSRL_AC_CRITICS)
-    return false;
+    bool found = false;
+    for_reg_fourier(domain, order, [&](auto m) { found = for_int<AC_CRITIC_ADVANTAGE, AC_CRITIC_Q>(critic, [&](auto cr) {
+        constexpr int DM = decltype(m)::domain, OR = decltype(m)::order, CR = cr.value;
+        if (io) hipLaunchKernelGGL((k_handle_ac<DM, OR, CR>), grid, block, 0, st, k, theta, io->from, io->act, io->rew, io->to, io->term, io->M, t, io->td_out);
+        else hipLaunchKernelGGL((k_train_ac<DM, OR, CR>), grid, block, 0, st, k, theta, t, chunk, stats);
+    }); });
+    return found;
 }
 
 }  // namespace rsrl

@@ -7,40 +7,30 @@
 
 namespace rsrl {
 
-static inline dim3 grid1(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
-// X(OR, P) for `order` and `policy` given as values; X is the using function's own, defined after this and undefined by it
-#define RSRL_CONT_CASE(OR) if (order == OR) { if (policy == ContPolicy::Gaussian) { X(OR, ContPolicy::Gaussian) } else { X(OR, ContPolicy::Beta) } return true; }
-
 bool launch_cont_policy(int order, ContPolicy policy, hipStream_t st, const Common& k, const float* w, int op, const float* states, int64_t M, uint64_t t,
                         uint32_t purpose, const float* act_in, float* out0, float* out1, float* keep) {
-#define X(OR, P) hipLaunchKernelGGL((k_cont_policy<OR, P>), grid1(M), dim3(kBlock), 0, st, k, w, op, states, M, t, purpose, act_in, out0, out1, keep);
-    RSRL_CMC_ORDERS(RSRL_CONT_CASE)
-#undef X
-    return false;
+    return for_cmc_order(order, [&](auto o) { for_cont_policy(policy, [&](auto p) {
+        hipLaunchKernelGGL((k_cont_policy<decltype(o)::value, p.value>), dim3(grid_for(M)), dim3(kBlock), 0, st, k, w, op, states, M, t, purpose, act_in, out0, out1, keep);
+    }); });
 }
 
 bool launch_cont_reset(int order, ContPolicy policy, hipStream_t st, const Common& k, const float* w, uint64_t t, float* action) {
-#define X(OR, P) hipLaunchKernelGGL((k_cont_reset<OR, P>), grid1(k.n_envs), dim3(kBlock), 0, st, k, w, t, action);
-    RSRL_CMC_ORDERS(RSRL_CONT_CASE)
-#undef X
-    return false;
+    return for_cmc_order(order, [&](auto o) { for_cont_policy(policy, [&](auto p) {
+        hipLaunchKernelGGL((k_cont_reset<decltype(o)::value, p.value>), dim3(grid_for(k.n_envs)), dim3(kBlock), 0, st, k, w, t, action);
+    }); });
 }
 
 bool launch_cont_rollout_mode(int order, ContPolicy policy, bool map, hipStream_t st, const Common& k, const float* w, int64_t step_limit, uint32_t* n_states,
                               float* total) {
-    if (map) {      // (2 * mode - 1 is the Beta loops' mapping)
-#define X(OR) if (order == OR && policy == ContPolicy::Beta) { hipLaunchKernelGGL((k_cont_rollout_mode<OR, ContPolicy::Beta, true>), grid1(k.n_envs), dim3(kBlock), 0, st, k, w, step_limit, n_states, total); return true; }
-        RSRL_CMC_ORDERS(X)
-#undef X
-        return false;
-    }
-#define X(OR, P) hipLaunchKernelGGL((k_cont_rollout_mode<OR, P, false>), grid1(k.n_envs), dim3(kBlock), 0, st, k, w, step_limit, n_states, total);
-    RSRL_CMC_ORDERS(RSRL_CONT_CASE)
-#undef X
-    return false;
+    const dim3 grid(grid_for(k.n_envs)), block(kBlock);
+    if (map)        // (2 * mode - 1 is the Beta loops' mapping)
+        return policy == ContPolicy::Beta && for_cmc_order(order, [&](auto o) {
+            hipLaunchKernelGGL((k_cont_rollout_mode<o.value, ContPolicy::Beta, true>), grid, block, 0, st, k, w, step_limit, n_states, total);
+        });
+    return for_cmc_order(order, [&](auto o) { for_cont_policy(policy, [&](auto p) {
+        hipLaunchKernelGGL((k_cont_rollout_mode<decltype(o)::value, p.value, false>), grid, block, 0, st, k, w, step_limit, n_states, total);
+    }); });
 }
-
-#undef RSRL_CONT_CASE
 
 // Domain::transition on the ctx's envs with f32 actions (k_domain_step's contract): explicit actions are the domain's own, taken literally;
 // actions == nullptr steps on the ctx's pending ones -- through the loop's mapping 2a - 1 when map is set
@@ -77,8 +67,8 @@ __global__ void k_cmc_clamp_actions(float* __restrict__ a, int64_t n) {
 
 void launch_cmc_domain_step(hipStream_t st, const Common& k, const float* act, const float* pending, bool map, float* from, float* next, float* rew,
                             uint8_t* term) {
-    hipLaunchKernelGGL(k_cmc_domain_step, grid1(k.n_envs), dim3(kBlock), 0, st, k, act, pending, map, from, next, rew, term);
+    hipLaunchKernelGGL(k_cmc_domain_step, grid_for(k.n_envs), dim3(kBlock), 0, st, k, act, pending, map, from, next, rew, term);
 }
-void launch_cmc_clamp_actions(hipStream_t st, float* a, int64_t n) { hipLaunchKernelGGL(k_cmc_clamp_actions, grid1(n), dim3(kBlock), 0, st, a, n); }
+void launch_cmc_clamp_actions(hipStream_t st, float* a, int64_t n) { hipLaunchKernelGGL(k_cmc_clamp_actions, grid_for(n), dim3(kBlock), 0, st, a, n); }
 
 }  // namespace rsrl

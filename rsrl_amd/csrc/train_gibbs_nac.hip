@@ -8,34 +8,24 @@
 
 namespace rsrl {
 
-static inline dim3 grid1(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
-
 bool launch_gibbs_nac(int domain, int order, dim3 grid, dim3 block, hipStream_t st, const Common& k, float* theta, uint32_t period, uint64_t t, int chunk,
                       DevStats* stats, const Transitions* io) {
-#define X(DM, OR)                                                                                                                                  \
-    if (domain == DM && order == OR) {                                                                                                             \
-        if (io) hipLaunchKernelGGL((k_handle_gibbs_nac<DM, OR>), grid, block, 0, st, k, theta, io->from, io->act, io->rew, io->to, io->term, io->M, t, \
-                                   io->td_out);                                                                                                    \
-        else hipLaunchKernelGGL((k_train_gibbs_nac<DM, OR>), grid, block, 0, st, k, theta, period, t, chunk, stats);                                 \
-        return true;                                                                                                                               \
-    }
-    RSRL_REG_FOURIER(X)
-#undef X
-    return false;
+    return for_reg_fourier(domain, order, [&](auto m) {
+        if (io) hipLaunchKernelGGL((k_handle_gibbs_nac<m.domain, m.order>), grid, block, 0, st, k, theta, io->from, io->act, io->rew, io->to, io->term, io->M, t, io->td_out);
+        else hipLaunchKernelGGL((k_train_gibbs_nac<m.domain, m.order>), grid, block, 0, st, k, theta, period, t, chunk, stats);
+    });
 }
 
 bool launch_gibbs_nac_update(int domain, int order, hipStream_t st, const Common& k, float* theta, const uint8_t* mask, float* norm_out) {
-#define X(DM, OR) if (domain == DM && order == OR) { hipLaunchKernelGGL((k_gibbs_nac_update<DM, OR>), grid1(k.n_envs), dim3(kBlock), 0, st, k, theta, mask, norm_out); return true; }
-    RSRL_REG_FOURIER(X)
-#undef X
-    return false;
+    return for_reg_fourier(domain, order, [&](auto m) {
+        hipLaunchKernelGGL((k_gibbs_nac_update<m.domain, m.order>), dim3(grid_for(k.n_envs)), dim3(kBlock), 0, st, k, theta, mask, norm_out);
+    });
 }
 
 bool launch_gibbs_nac_q(int domain, int order, hipStream_t st, const Common& k, const float* theta, const float* states, int64_t M, float* q_out) {
-#define X(DM, OR) if (domain == DM && order == OR) { hipLaunchKernelGGL((k_gibbs_nac_q<DM, OR>), grid1(M), dim3(kBlock), 0, st, k, theta, states, M, q_out); return true; }
-    RSRL_REG_FOURIER(X)
-#undef X
-    return false;
+    return for_reg_fourier(domain, order, [&](auto m) {
+        hipLaunchKernelGGL((k_gibbs_nac_q<m.domain, m.order>), dim3(grid_for(M)), dim3(kBlock), 0, st, k, theta, states, M, q_out);
+    });
 }
 
 }  // namespace rsrl

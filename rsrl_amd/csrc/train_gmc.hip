@@ -7,22 +7,17 @@
 
 namespace rsrl {
 
-#define RSRL_GMC_CASE(DM, OR)                                                                                                                   \
-    if (domain == DM && order == OR) {                                                                                                          \
-        if (io) hipLaunchKernelGGL((k_handle_gmc<DM, OR>), grid, block, 0, st, k, io->states, io->rew, io->len, io->T, io->ret_out);            \
-        else hipLaunchKernelGGL((k_train_gmc<DM, OR>), grid, block, 0, st, k, gs, t, chunk, stats);                                             \
-        return true;                                                                                                                            \
-    }
-
 bool launch_gmc(int domain, int order, dim3 grid, dim3 block, hipStream_t st, const Common& k, const GmcState& gs, uint64_t t, int chunk, DevStats* stats,
                 const GmcBatch* io) {
-    RSRL_REG_FOURIER(RSRL_GMC_CASE)
-    return false;
+    return for_reg_fourier(domain, order, [&](auto m) {
+        if (io) hipLaunchKernelGGL((k_handle_gmc<m.domain, m.order>), grid, block, 0, st, k, io->states, io->rew, io->len, io->T, io->ret_out);
+        else hipLaunchKernelGGL((k_train_gmc<m.domain, m.order>), grid, block, 0, st, k, gs, t, chunk, stats);
+    });
 }
 
 void launch_gmc_record_get(hipStream_t st, const GmcState& gs, const uint32_t* ep_step, int64_t N, int64_t cap, int D, float* states, float* rew) {
     const int64_t n = cap * N;
-    hipLaunchKernelGGL(k_gmc_record_get, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gs, ep_step, N, cap, D, states, rew);
+    hipLaunchKernelGGL(k_gmc_record_get, dim3(grid_for(n)), dim3(kBlock), 0, st, gs, ep_step, N, cap, D, states, rew);
 }
 
 }  // namespace rsrl

@@ -7,18 +7,13 @@
 
 namespace rsrl {
 
-#define RSRL_GTD_CASE(DM, OR)                                                                                                                   \
-    if (domain == DM && order == OR) {                                                                                                          \
-        if (io) hipLaunchKernelGGL((k_handle_gtd<DM, OR>), grid, block, 0, st, k, gs, tdc ? 1 : 0, io->from, io->rew, io->to, io->term, io->M, io->td_out); \
-        else if (tdc) hipLaunchKernelGGL((k_train_gtd<DM, OR, true>), grid, block, 0, st, k, gs, t, chunk, stats);                              \
-        else hipLaunchKernelGGL((k_train_gtd<DM, OR, false>), grid, block, 0, st, k, gs, t, chunk, stats);                                      \
-        return true;                                                                                                                            \
-    }
-
 bool launch_gtd(int domain, int order, bool tdc, dim3 grid, dim3 block, hipStream_t st, const Common& k, const GtdState& gs, uint64_t t, int chunk,
                 DevStats* stats, const Transitions* io) {
-    RSRL_REG_FOURIER(RSRL_GTD_CASE)
-    return false;
+    return for_reg_fourier(domain, order, [&](auto m) {
+        if (io) hipLaunchKernelGGL((k_handle_gtd<m.domain, m.order>), grid, block, 0, st, k, gs, tdc ? 1 : 0, io->from, io->rew, io->to, io->term, io->M, io->td_out);
+        else if (tdc) hipLaunchKernelGGL((k_train_gtd<m.domain, m.order, true>), grid, block, 0, st, k, gs, t, chunk, stats);
+        else hipLaunchKernelGGL((k_train_gtd<m.domain, m.order, false>), grid, block, 0, st, k, gs, t, chunk, stats);
+    });
 }
 
 }  // namespace rsrl

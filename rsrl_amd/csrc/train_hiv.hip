@@ -224,32 +224,31 @@ __global__ __launch_bounds__(kBlock) void k_hiv_rollout(Common c, BasisGeom g, i
 }
 
 // ---- launchers (launch.hpp)
-static inline dim3 hiv_grid(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
 void launch_hiv_reset(hipStream_t st, const Common& k, const BasisGeom& g, double* Y, uint64_t t) {
-    hipLaunchKernelGGL(k_hiv_reset, hiv_grid(k.n_envs), dim3(kBlock), 0, st, k, g, Y, t);
+    hipLaunchKernelGGL(k_hiv_reset, grid_for(k.n_envs), dim3(kBlock), 0, st, k, g, Y, t);
 }
 void launch_hiv_domain_step(hipStream_t st, const Common& k, double* Y, const int32_t* act, float* from, float* next, float* rew, uint8_t* term) {
-    hipLaunchKernelGGL(k_hiv_domain_step, hiv_grid(k.n_envs), dim3(kBlock), 0, st, k, Y, act, from, next, rew, term);
+    hipLaunchKernelGGL(k_hiv_domain_step, grid_for(k.n_envs), dim3(kBlock), 0, st, k, Y, act, from, next, rew, term);
 }
 void launch_hiv_domain_reset(hipStream_t st, const Common& k, double* Y, const uint8_t* mask) {
-    hipLaunchKernelGGL(k_hiv_domain_reset, hiv_grid(k.n_envs), dim3(kBlock), 0, st, k, Y, mask);
+    hipLaunchKernelGGL(k_hiv_domain_reset, grid_for(k.n_envs), dim3(kBlock), 0, st, k, Y, mask);
 }
 void launch_hiv_emit(hipStream_t st, double* Y, float* state, int64_t N, bool from_obs) {
-    hipLaunchKernelGGL(k_hiv_emit, hiv_grid(N), dim3(kBlock), 0, st, Y, state, N, from_obs ? 1 : 0);
+    hipLaunchKernelGGL(k_hiv_emit, grid_for(N), dim3(kBlock), 0, st, Y, state, N, from_obs ? 1 : 0);
 }
 void launch_hiv_qop(hipStream_t st, const Common& k, const BasisGeom& g, int op, const float* states, int64_t Mn, uint64_t call, float* fout, int32_t* iout,
                     const float* fin, const int32_t* iin) {
-    hipLaunchKernelGGL(k_hiv_qop, hiv_grid(Mn), dim3(kBlock), 0, st, k, g, op, states, Mn, call, fout, iout, fin, iin);
+    hipLaunchKernelGGL(k_hiv_qop, grid_for(Mn), dim3(kBlock), 0, st, k, g, op, states, Mn, call, fout, iout, fin, iin);
 }
 void launch_hiv_handle(hipStream_t st, const Common& k, const BasisGeom& g, const Transitions& io, uint64_t t) {
-    hipLaunchKernelGGL(k_hiv_handle, hiv_grid(io.M), dim3(kBlock), 0, st, k, g, io.from, io.act, io.rew, io.to, io.term, io.M, t, io.td_out);
+    hipLaunchKernelGGL(k_hiv_handle, grid_for(io.M), dim3(kBlock), 0, st, k, g, io.from, io.act, io.rew, io.to, io.term, io.M, t, io.td_out);
 }
 void launch_hiv_train(hipStream_t st, const Common& k, const BasisGeom& g, double* Y, uint64_t t, int chunk, DevStats* stats) {
-    hipLaunchKernelGGL(k_hiv_train, hiv_grid(k.n_envs), dim3(kBlock), 0, st, k, g, Y, t, chunk, stats);
+    hipLaunchKernelGGL(k_hiv_train, grid_for(k.n_envs), dim3(kBlock), 0, st, k, g, Y, t, chunk, stats);
 }
 void launch_hiv_rollout(hipStream_t st, const Common& k, const BasisGeom& g, int64_t step_limit, uint32_t* n_states, float* total, int64_t Mn, const TrajOut& tr,
                         const RolloutPolicy& rp) {
-    hipLaunchKernelGGL(k_hiv_rollout, hiv_grid(Mn), dim3(kBlock), 0, st, k, g, step_limit, n_states, total, Mn, tr, rp);
+    hipLaunchKernelGGL(k_hiv_rollout, grid_for(Mn), dim3(kBlock), 0, st, k, g, step_limit, n_states, total, Mn, tr, rp);
 }
 
 }  // namespace rsrl

@@ -155,29 +155,27 @@ __global__ __launch_bounds__(kBlock) void k_table_rollout(Common c, int64_t step
 }
 
 // ---- launchers (launch.hpp)
-static inline dim3 table_grid(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
-static inline dim3 table_wave_grid(int64_t n) { return dim3((unsigned)((n + kLanes - 1) / kLanes)); }
-void launch_table_reset(hipStream_t st, const Common& k, uint64_t t) { hipLaunchKernelGGL(k_table_reset, table_grid(k.n_envs), dim3(kBlock), 0, st, k, t); }
+void launch_table_reset(hipStream_t st, const Common& k, uint64_t t) { hipLaunchKernelGGL(k_table_reset, grid_for(k.n_envs), dim3(kBlock), 0, st, k, t); }
 void launch_table_domain_step(hipStream_t st, const Common& k, const int32_t* act, float* from, float* next, float* rew, uint8_t* term) {
-    hipLaunchKernelGGL(k_table_domain_step, table_grid(k.n_envs), dim3(kBlock), 0, st, k, act, from, next, rew, term);
+    hipLaunchKernelGGL(k_table_domain_step, grid_for(k.n_envs), dim3(kBlock), 0, st, k, act, from, next, rew, term);
 }
 void launch_table_domain_reset(hipStream_t st, const Common& k, const uint8_t* mask) {
-    hipLaunchKernelGGL(k_table_domain_reset, table_grid(k.n_envs), dim3(kBlock), 0, st, k, mask);
+    hipLaunchKernelGGL(k_table_domain_reset, grid_for(k.n_envs), dim3(kBlock), 0, st, k, mask);
 }
 void launch_table_qop(hipStream_t st, const Common& k, int op, const float* states, int64_t Mn, uint64_t call, float* fout, int32_t* iout, const float* fin,
                       const int32_t* iin) {
-    hipLaunchKernelGGL(k_table_qop, table_grid(Mn), dim3(kBlock), 0, st, k, op, states, Mn, call, fout, iout, fin, iin);
+    hipLaunchKernelGGL(k_table_qop, grid_for(Mn), dim3(kBlock), 0, st, k, op, states, Mn, call, fout, iout, fin, iin);
 }
 void launch_table_handle(hipStream_t st, const Common& k, const Transitions& io, uint64_t t) {
-    hipLaunchKernelGGL(k_table_handle, table_grid(io.M), dim3(kBlock), 0, st, k, io.from, io.act, io.rew, io.to, io.term, io.M, t, io.td_out);
+    hipLaunchKernelGGL(k_table_handle, grid_for(io.M), dim3(kBlock), 0, st, k, io.from, io.act, io.rew, io.to, io.term, io.M, t, io.td_out);
 }
 void launch_table_train(hipStream_t st, const Common& k, bool lds, uint64_t t, int chunk, DevStats* stats) {
-    if (lds) hipLaunchKernelGGL(k_table_train_lds, table_wave_grid(k.n_envs), dim3(kLanes), 0, st, k, t, chunk, stats);
-    else hipLaunchKernelGGL(k_table_train_mem, table_wave_grid(k.n_envs), dim3(kLanes), 0, st, k, t, chunk, stats);
+    if (lds) hipLaunchKernelGGL(k_table_train_lds, grid_for(k.n_envs, kLanes), dim3(kLanes), 0, st, k, t, chunk, stats);
+    else hipLaunchKernelGGL(k_table_train_mem, grid_for(k.n_envs, kLanes), dim3(kLanes), 0, st, k, t, chunk, stats);
 }
 void launch_table_rollout(hipStream_t st, const Common& k, int64_t step_limit, uint32_t* n_states, float* total, int64_t Mn, const TrajOut& tr,
                           const RolloutPolicy& rp) {
-    hipLaunchKernelGGL(k_table_rollout, table_grid(Mn), dim3(kBlock), 0, st, k, step_limit, n_states, total, Mn, tr, rp);
+    hipLaunchKernelGGL(k_table_rollout, grid_for(Mn), dim3(kBlock), 0, st, k, step_limit, n_states, total, Mn, tr, rp);
 }
 
 }  // namespace rsrl

@@ -7,17 +7,12 @@
 
 namespace rsrl {
 
-#define RSRL_TDAC_CASE(DM, OR)                                                                                                                  \
-    if (domain == DM && order == OR) {                                                                                                          \
-        if (io) hipLaunchKernelGGL((k_handle_tdac<DM, OR>), grid, block, 0, st, k, theta, io->from, io->act, io->rew, io->to, io->term, io->M, io->td_out); \
-        else hipLaunchKernelGGL((k_train_tdac<DM, OR>), grid, block, 0, st, k, theta, t, chunk, stats);                                        \
-        return true;                                                                                                                            \
-    }
-
 bool launch_tdac(int domain, int order, dim3 grid, dim3 block, hipStream_t st, const Common& k, float* theta, uint64_t t, int chunk, DevStats* stats,
                  const Transitions* io) {
-    RSRL_REG_FOURIER(RSRL_TDAC_CASE)
-    return false;
+    return for_reg_fourier(domain, order, [&](auto m) {
+        if (io) hipLaunchKernelGGL((k_handle_tdac<m.domain, m.order>), grid, block, 0, st, k, theta, io->from, io->act, io->rew, io->to, io->term, io->M, io->td_out);
+        else hipLaunchKernelGGL((k_train_tdac<m.domain, m.order>), grid, block, 0, st, k, theta, t, chunk, stats);
+    });
 }
 
 }  // namespace rsrl

@@ -8,16 +8,11 @@
 namespace rsrl {
 
 bool launch_tdac_beta(int order, hipStream_t st, const Common& k, const TdacBetaState& ts, uint64_t t, int chunk, DevStats* stats, const TransitionsF32* io) {
-#define X(OR)                                                                                                                                   \
-    if (order == OR) {                                                                                                                          \
-        const dim3 grid = lstd_grid(io ? io->M : k.n_envs, LstdGroup<FourierReg<kCmc, OR>::F>::G), block(kBlock);                               \
-        if (io) hipLaunchKernelGGL((k_handle_tdac_beta<OR>), grid, block, 0, st, k, ts, io->from, io->act, io->rew, io->to, io->term, io->M, io->td_out); \
-        else hipLaunchKernelGGL((k_train_tdac_beta<OR>), grid, block, 0, st, k, ts, t, chunk, stats);                                          \
-        return true;                                                                                                                            \
-    }
-    RSRL_CMC_ORDERS(X)
-#undef X
-    return false;
+    return for_cmc_order(order, [&](auto o) {
+        const dim3 grid = lstd_grid(io ? io->M : k.n_envs, LstdGroup<FourierReg<kCmc, o.value>::F>::G), block(kBlock);
+        if (io) hipLaunchKernelGGL((k_handle_tdac_beta<o.value>), grid, block, 0, st, k, ts, io->from, io->act, io->rew, io->to, io->term, io->M, io->td_out);
+        else hipLaunchKernelGGL((k_train_tdac_beta<o.value>), grid, block, 0, st, k, ts, t, chunk, stats);
+    });
 }
 
 }  // namespace rsrl

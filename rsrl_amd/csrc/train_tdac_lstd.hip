@@ -8,18 +8,13 @@
 
 namespace rsrl {
 
-#define RSRL_TDAC_LSTD_CASE(DM, OR)                                                                                                             \
-    if (domain == DM && order == OR) {                                                                                                          \
-        const dim3 grid = lstd_grid(io ? io->M : k.n_envs, LstdGroup<FourierReg<DM, OR>::F>::G), block(kBlock);                                 \
-        if (io) hipLaunchKernelGGL((k_handle_tdac_lstd<DM, OR>), grid, block, 0, st, k, ts, io->from, io->act, io->rew, io->to, io->term, io->M, io->td_out); \
-        else hipLaunchKernelGGL((k_train_tdac_lstd<DM, OR>), grid, block, 0, st, k, ts, t, chunk, stats);                                      \
-        return true;                                                                                                                            \
-    }
-
 bool launch_tdac_lstd(int domain, int order, hipStream_t st, const Common& k, const TdacLstdState& ts, uint64_t t, int chunk, DevStats* stats,
                       const Transitions* io) {
-    RSRL_REG_FOURIER(RSRL_TDAC_LSTD_CASE)
-    return false;
+    return for_reg_fourier(domain, order, [&](auto m) {
+        const dim3 grid = lstd_grid(io ? io->M : k.n_envs, LstdGroup<FourierReg<m.domain, m.order>::F>::G), block(kBlock);
+        if (io) hipLaunchKernelGGL((k_handle_tdac_lstd<m.domain, m.order>), grid, block, 0, st, k, ts, io->from, io->act, io->rew, io->to, io->term, io->M, io->td_out);
+        else hipLaunchKernelGGL((k_train_tdac_lstd<m.domain, m.order>), grid, block, 0, st, k, ts, t, chunk, stats);
+    });
 }
 
 }  // namespace rsrl

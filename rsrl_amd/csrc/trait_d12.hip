@@ -4,12 +4,11 @@ namespace rsrl {
 bool launch_trait_lm_d0_low(int domain, int order, int algo, int policy, hipStream_t st, const Common& k, const TraitIo& io, uint64_t t);
 bool launch_trait_lm_d0_high(int domain, int order, int algo, int policy, hipStream_t st, const Common& k, const TraitIo& io, uint64_t t);
 static bool launch_trait_lm_d12(int domain, int order, int algo, int policy, hipStream_t st, const Common& k, const TraitIo& io, uint64_t t) {
-    RSRL_TRAIT_ALGOS(1, 1) RSRL_TRAIT_ALGOS(2, 1)
-    return false;
+    if (domain == 1) return launch_trait_lm_orders<1, 1>(order, algo, policy, st, k, io, t);
+    return domain == 2 && launch_trait_lm_orders<2, 1>(order, algo, policy, st, k, io, t);
 }
 bool trait_lm_available(int domain, int order, int algo) {
-    const bool basis = (domain == 0 && (order == 1 || order == 3 || order == 5)) || ((domain == 1 || domain == 2) && order == 1);
-    return basis && (algo == 0 || algo == 1 || algo == 2 || algo == 5);
+    return for_trait_fourier(domain, order, [](auto) {}) && is_one_step_algo(algo);
 }
 bool launch_trait_lm(int domain, int order, int algo, int policy, hipStream_t st, const Common& k, const TraitIo& io, uint64_t t) {
     if (!trait_lm_available(domain, order, algo)) return false;
@@ -18,7 +17,8 @@ bool launch_trait_lm(int domain, int order, int algo, int policy, hipStream_t st
 }
 bool launch_trait_sample(int domain, int order, hipStream_t st, const Common& k, const float* states, int64_t Mn, uint64_t t, uint32_t blk, float* qkey,
                          float* qval, int32_t* actions_out) {
-    RSRL_TRAIT_SAMPLE_CASE(0, 1) RSRL_TRAIT_SAMPLE_CASE(0, 3) RSRL_TRAIT_SAMPLE_CASE(0, 5) RSRL_TRAIT_SAMPLE_CASE(1, 1) RSRL_TRAIT_SAMPLE_CASE(2, 1)
-    return false;
+    return for_trait_fourier(domain, order, [&](auto m) {
+        hipLaunchKernelGGL((k_trait_sample<m.domain, m.order>), dim3(grid_for(Mn)), dim3(kBlock), 0, st, k, states, Mn, t, blk, qkey, qval, actions_out);
+    });
 }
 }  // namespace rsrl
