@@ -250,8 +250,7 @@ typedef enum { RSRL_QLEARNING = 0, RSRL_SARSA = 1, RSRL_EXPECTED_SARSA = 2, RSRL
                 * rsrl_hip_get/set_episode_record, set_episode_steps, reset and domain_reset behave as for RSRL_GRADIENT_MC (a reset leaves the agent's
                 * state alone).  td_out and the statistics' sum |delta| are the diagnostic r + gamma V(s') - V(s) (terminal: r - V(s)) with theta as it
                 * stood before the batch's solve, booked at the step that ended the episode: the agents compute no TD error.  The checkpoint is aux_kind 10;
-                * the open record is the caller's to carry.  Not built: LambdaLSPE (its solve() zeroes A and b, so every batch shorter than F is a
-                * rank-deficient system that only the SVD fallback answers) */
+                * the open record is the caller's to carry.  (LambdaLSPE, the third batch agent of prediction/lstd, is RSRL_LAMBDA_LSPE.) */
                RSRL_LSTD = 25, RSRL_LSTD_LAMBDA = 26,
                /* (27 is no algo.)  NAC (control/nac.rs:47-59), natural actor-critic, with the Beta policy and a SARSA critic over the stable
                 * compatible basis: the agent and the loop of examples/nac_beta.rs.  critic = SARSA{q_func: LFA::scalar(SCB{policy, basis},
@@ -409,6 +408,33 @@ typedef enum { RSRL_QLEARNING = 0, RSRL_SARSA = 1, RSRL_EXPECTED_SARSA = 2, RSRL
                 * agent's ctx, and no other agent's file into this one.  DEPARTURES: f32 for the reference's f64; psi flattened as stated; SARSA's
                 * thread_rng() draw is a keyed stream (distribution parity is the contract); the period is a parameter (the example hard-codes it) */
                RSRL_GIBBS_NAC = 37,
+               /* (40 is no algo.)  LambdaLSPE (prediction/lstd/lambda_lspe.rs:27-107), least-squares policy evaluation: the last agent of
+                * prediction/lstd, Handler<&Batch> as RSRL_LSTD_LAMBDA.  Everything is f64 on RSRL_LSTD's features and every product is rounded.
+                * LambdaLSPE::new(basis, alpha, gamma, lambda) (:28-43): theta = 0, A = 1e-6 I, b = 0, and the scalar return correction delta = 0.
+                * handle (:71-106) walks the batch LAST TO FIRST; theta does not move during the walk.  For each transition:
+                *   delta = delta * (gamma * lambda)                                                                        (:76)
+                *   terminal (:78-86):  b += (delta + r) phi(s);  A += phi(s) (x) phi(s);  delta = 0      -- theta . phi(s) is NOT added here
+                *   otherwise (:87-100): v_s = phi(s) . theta and v_n = phi(s') . theta (ascending index, the sum starting at 0);
+                *     delta = delta + (r + gamma * v_n - v_s);  b += (v_s + delta) phi(s);  A += phi(s) (x) phi(s)
+                * The scalar in front of phi(s) is one rounded sum; each element of b and A is one rounded product, then added.  Then solve()
+                * (:47-62; PRIVATE in the reference, served here as rsrl_hip_lstd_solve exactly as handle ends with it): x = A.solve(b) by RSRL_LSTD's
+                * fixed elimination (no SVD); on success theta_r = (1 - alpha) * theta_r + alpha * x_r -- 1 - alpha computed once in f64, three rounded
+                * operations per element -- and A, b and delta are set to zero.  An abandoned elimination keeps theta, A, b AND delta (what the
+                * reference does when both of its attempts fail) and counts in singular_solves.
+                * DEPARTURE, THE ROW RULE.  The reference's solve() zeroes A and b, so a batch shorter than F leaves a Gram matrix of fewer than F
+                * vectors: singular in exact arithmetic and answered there by the SVD fallback, which this library does not have -- and which plain
+                * elimination does not even report (in rounding such a system gets pivots near 1e-17 and one arbitrary member of its solution set
+                * comes back).  So every learner holds a row count `rows` in 0 .. F: F at create (the identity's F rows make the first system full
+                * rank); every handled batch sets rows = min(rows + len, F); a successful solve sets it to 0.  solve() runs the elimination only when
+                * rows == F.  Otherwise the solve is DEFERRED: nothing moves, singular_solves does not count, and the next batch adds to the same A,
+                * b and delta.
+                * The driver loop is RSRL_LSTD's, draw for draw.  config: alpha (finite, else EINVAL), gamma, lambda; max_episode_steps >= 1.  Supported:
+                * exactly as RSRL_LSTD_LAMBDA.  rsrl_hip_get/set_lstd_batch_state carry the state through RSRL_LSTD_LAMBDA's signature: z[0] = delta and
+                * z[1] = rows as an exact integer; get writes z[2 ..] as 0 and set does not read it; z == NULL: neither is read or written; a set whose rows
+                * is not an integer in 0 .. F is EINVAL and moves nothing.  The value side, handle_transitions, the episode record, reset, domain_reset,
+                * the ESTATE refusals (handle, handle_batch, get/set_lstd_state), td_out and the statistics are RSRL_LSTD's.  The checkpoint is
+                * aux_kind 19: RSRL_LSTD's sections, then f64 (delta, rows)[N], then u32 singular_solves[N].  Not built: the SVD fallback */
+               RSRL_LAMBDA_LSPE = 39,
                /* (32 is no algo.)  CACLA (control/cacla.rs:42-64), the continuous actor-critic learning automaton, over the Gaussian policy with a
                 * TD(0) state-value critic.  CACLA{critic, policy, alpha, gamma}: the critic is a closure over V that the agent reads and never
                 * writes -- a caller trains it; here it is eval = TD{v_func: LFA::scalar(basis, SGD(lr)), gamma} (prediction/td/td.rs:38-58), w
@@ -757,7 +783,7 @@ int rsrl_hip_handle(rsrl_hip_ctx* ctx, const float* from_states, const int32_t* 
  * ESTATE on every other agent. */
 int rsrl_hip_handle_batch(rsrl_hip_ctx* ctx, int64_t T, const float* states /*[T][D][N]*/, const int32_t* actions /*[T][N]*/,
                           const float* rewards /*[T][N]*/, const uint32_t* lengths /*[N]*/, float* returns_out /*[T][N], optional*/);
-/* RSRL_LSTD / RSRL_LSTD_LAMBDA: Handler<&Batch>::handle for every learner, on whole transitions.  Learner i's batch is rows 0 .. lengths[i]-1 of its
+/* RSRL_LSTD / RSRL_LSTD_LAMBDA / RSRL_LAMBDA_LSPE (last to first): Handler<&Batch>::handle for every learner, on whole transitions.  Learner i's batch is rows 0 .. lengths[i]-1 of its
  * column; any row may be terminal; LSTD walks the rows first to last, LSTDLambda last to first, and both end in solve().  lengths[i] = 0 means no
  * call: the learner keeps its bytes and no solve runs.  actions are not read.  td_out receives the diagnostic r + gamma V(s') - V(s) (terminal:
  * r - V(s)) with theta as it stood before the solve at each handled row, NaN past a learner's length.  The ctx's own open record is not touched.
@@ -819,14 +845,18 @@ int rsrl_hip_set_return_carry(rsrl_hip_ctx* ctx, const float* g /*[N]*/);
 int rsrl_hip_get_lstd_state(rsrl_hip_ctx* ctx, int64_t env_index, double* theta /*[F]*/, double* mat /*[F][F]*/, double* mu /*[F], iLSTD only, may be NULL*/);
 int rsrl_hip_set_lstd_state(rsrl_hip_ctx* ctx, int64_t env_index, const double* theta /*[F]*/, const double* mat /*[F][F]*/,
                             const double* mu /*[F], iLSTD only, may be NULL*/);
-/* LSTD / LSTDLambda: the exact f64 state of one learner -- theta, A (row-major), b, LSTDLambda's z (may be NULL: not read or written; ignored by
- * LSTD) -- and its count of abandoned solves.  Host or device arrays.  ESTATE on every other agent */
+/* LSTD / LSTDLambda / LambdaLSPE: the exact f64 state of one learner -- theta, A (row-major), b, LSTDLambda's z (may be NULL: not read or written;
+ * ignored by LSTD) -- and its count of abandoned solves.  RSRL_LAMBDA_LSPE: z[0] = delta and z[1] = rows, an exact integer in 0 .. F; get writes
+ * z[2 ..] as 0, set does not read it and refuses any other rows with EINVAL before anything moves.  Host or device arrays.  ESTATE on every other
+ * agent */
 int rsrl_hip_get_lstd_batch_state(rsrl_hip_ctx* ctx, int64_t env_index, double* theta /*[F]*/, double* A /*[F][F]*/, double* b /*[F]*/,
                                   double* z /*[F], LSTDLambda only, may be NULL*/, uint32_t* singular_solves);
 int rsrl_hip_set_lstd_batch_state(rsrl_hip_ctx* ctx, int64_t env_index, const double* theta /*[F]*/, const double* A /*[F][F]*/, const double* b /*[F]*/,
                                   const double* z /*[F], LSTDLambda only, may be NULL*/, const uint32_t* singular_solves);
 /* LSTD / LSTDLambda: the agents' public solve() (lstd.rs:40, lstd_lambda.rs:44) for every learner: theta <- A.solve(b) in the library's fixed
- * operation order; A, b and z are not written.  An abandoned solve keeps theta and counts in singular_solves.  ESTATE on every other agent */
+ * operation order; A, b and z are not written.  An abandoned solve keeps theta and counts in singular_solves.  RSRL_LAMBDA_LSPE: the agent's
+ * solve() exactly as handle ends with it (lambda_lspe.rs:47-62, a PRIVATE function in the reference): the row rule, the relaxed step, the
+ * zeroing of A, b, delta and rows.  ESTATE on every other agent */
 int rsrl_hip_lstd_solve(rsrl_hip_ctx* ctx);
 /* Checkpoint of the approximator(s) (the reference's only persistence story is the optional serde
  * derive on the agents, rsrl/Cargo.toml:26).  The file version follows from the header's aux_kind:
@@ -882,6 +912,8 @@ int rsrl_hip_lstd_solve(rsrl_hip_ctx* ctx);
  *              if aux_kind is 10 (file version 10 too; RSRL_LSTD / RSRL_LSTD_LAMBDA): the weights section is ABSENT;
  *              then n_learners x f64[F] of theta, n_learners x f64[F][F] of A (row-major), n_learners x f64[F] of b, for LSTDLambda
  *              n_learners x f64[F] of z, then u32 singular_solves[N].  The open episodes are not in the file (as RSRL_GRADIENT_MC's);
+ *              if aux_kind is 19 (file version 10 too; RSRL_LAMBDA_LSPE): aux_kind 10's theta, A and b, then n_learners x f64[2] of (delta, rows),
+ *              then u32 singular_solves[N]; a row count that is no integer in 0 .. F is EINVAL at load;
  *              if aux_kind is 11 (file version 10 too; RSRL_ILSTD_ACTOR_CRITIC with RSRL_BETA on RSRL_CONTINUOUS_MOUNTAIN_CAR): aux_kind 8's
  *              sections of its iLSTD critic (mu included), then n_learners x f32[F][2] of the policy's columns (alpha's, beta's);
  *              if aux_kind is 12 (file version 10 too; RSRL_NAC; the header's F is n_features, A = 1): the weights

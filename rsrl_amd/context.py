@@ -27,6 +27,7 @@ TRACE_ACCUMULATE, TRACE_SATURATE, TRACE_DUTCH = 0, 1, 2
 GREEDY, EPSILON_GREEDY, SOFTMAX, RANDOM = 0, 1, 2, 3
 BETA = 4                                        # policies/beta.rs over two Softplus-composed scalar LFAs: ILSTD_ACTOR_CRITIC on CONTINUOUS_MOUNTAIN_CAR
 GIBBS_NAC = 37                                  # (36 is no algo) control/nac.rs over the Gibbs policy (nac_softmax.rs: policy=SOFTMAX) and a SARSA critic over the stable compatible basis on the discrete domains: n_weight_rows = (A + 1) F; q_evaluate -> (A, M); handle = critic.handle; nac_update; n_steps = the actor's period
+LAMBDA_LSPE = 39                                # (38 and 40 are no algos) prediction/lstd: LambdaLSPE (LSTD_LAMBDA's calls; get/set_lstd_batch_state carry z[0] = delta, z[1] = rows)
 GAUSSIAN = 6                                    # (5 is no policy) policies/gaussian: the mean a scalar LFA, the stddev a Softplus-composed one: NAC (nac.rs) and CACLA on CONTINUOUS_MOUNTAIN_CAR
 W_PER_ENV, W_SHARED = 0, 1
 W_F32, W_BF16 = 0, 1
@@ -482,22 +483,25 @@ class Context:
         return theta, mat, mu
 
     def get_lstd_batch_state(self, env_index=0):
-        """LSTD / LSTDLambda: one learner's exact f64 state -> (theta (F,), A (F, F), b (F,), z (F,) for LSTDLambda else None, singular_solves)"""
+        """LSTD / LSTDLambda / LambdaLSPE: one learner's exact f64 state -> (theta (F,), A (F, F), b (F,), z (F,) for LSTDLambda, (delta, rows, 0 ...)
+        for LambdaLSPE, else None, singular_solves)"""
         theta, A, b = np.empty(self.F, dtype=np.float64), np.empty((self.F, self.F), dtype=np.float64), np.empty(self.F, dtype=np.float64)
-        z = np.empty(self.F, dtype=np.float64) if self.cfg.algo == LSTD_LAMBDA else None
+        z = np.empty(self.F, dtype=np.float64) if self.cfg.algo in (LSTD_LAMBDA, LAMBDA_LSPE) else None
         sing = np.zeros(1, dtype=np.uint32)
         _abi.check(self._L.rsrl_hip_get_lstd_batch_state(self._h, int(env_index), _p(theta), _p(A), _p(b), _p(z), _p(sing)))
         return theta, A, b, z, int(sing[0])
 
     def set_lstd_batch_state(self, theta, A, b, z=None, singular_solves=0, env_index=0):
-        """LSTD / LSTDLambda: install one learner's f64 state exactly (z: LSTDLambda only; None leaves it as it is)"""
+        """LSTD / LSTDLambda / LambdaLSPE: install one learner's f64 state exactly (z: LSTDLambda's trace, LambdaLSPE's z[0] = delta and z[1] = rows --
+        an integer in 0 .. F; None leaves it as it is)"""
         sing = np.array([singular_solves], dtype=np.uint32)
         _abi.check(self._L.rsrl_hip_set_lstd_batch_state(self._h, int(env_index), _p(_in(theta, np.float64, (self.F,))), _p(_in(A, np.float64, (self.F, self.F))),
                                                          _p(_in(b, np.float64, (self.F,))), _p(None if z is None else _in(z, np.float64, (self.F,))), _p(sing)))
 
     def lstd_solve(self):
         """LSTD / LSTDLambda: the agents' public solve() for every learner -- theta <- A.solve(b) in the library's fixed operation order; an abandoned
-        solve (no pivot above 0) keeps theta and counts in singular_solves"""
+        solve (no pivot above 0) keeps theta and counts in singular_solves.  LambdaLSPE: its solve() as handle ends with it (deferred below F rows; the
+        relaxed step; A, b, delta and rows zeroed on success)"""
         _abi.check(self._L.rsrl_hip_lstd_solve(self._h))
 
     def set_lstd_state(self, theta, mat, mu=None, env_index=0):

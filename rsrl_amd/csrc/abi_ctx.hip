@@ -70,6 +70,7 @@ static const char* train_kernel_name(const rsrl_hip_ctx* c) {
     // (the two families whose kernel the configuration refines; every other name is the family's row of kFamily)
     if (c->family == AgentFamily::WaveControl && c->cfg.weight_dtype == RSRL_W_BF16 && !c->sw.no_wave_pk) return "k_train_wave_pk";
     if (c->family == AgentFamily::RegStep && c->w_ls != 1) return c->k1_quad ? "k_step_reg_q4" : "k_step_reg_lm";
+    if (c->family == AgentFamily::LstdBatchReg && c->cfg.algo == RSRL_LAMBDA_LSPE) return "k_train_lspe";
     if (c->family == AgentFamily::CliffTable && c->sw.table_mem == 1) return "k_table_train_mem";      // (by launch depth otherwise: launch_agent names it)
     return family_row(c).kernel;
 }
@@ -152,7 +153,7 @@ int rsrl_hip_destroy(rsrl_hip_ctx* c) {
 }
 
 // The agents that exist only on the register-family Fourier orders with per-learner f32 weights (train_ac.hip, train_tdac.hip, train_reinforce.hip,
-// train_lstd.hip, train_tdac_lstd.hip, train_gmc.hip, train_lstd_batch.hip, train_gtd.hip): the policy is the agent's own -- the Gibbs actor / policy, or the prediction agents' Random behaviour -- and the
+// train_lstd.hip, train_tdac_lstd.hip, train_gmc.hip, train_lstd_batch.hip, train_lspe.hip, train_gtd.hip): the policy is the agent's own -- the Gibbs actor / policy, or the prediction agents' Random behaviour -- and the
 // critic shares it; iLSTD's n_updates travel as config.n_steps.  `storage`: register-family order, per-learner f32 weights, no epsilon schedule
 static int check_reg_only(const rsrl_hip_config& cfg, const AlgoRow& a, bool storage) {
     if (!storage || cfg.policy != a.reg_policy || cfg.agent_policy != -1)
@@ -166,10 +167,12 @@ static int check_reg_only(const rsrl_hip_config& cfg, const AlgoRow& a, bool sto
     if (a.agent == Agent::GibbsNac && (cfg.n_steps < 1 || cfg.n_steps > 65536))
         return fail(RSRL_HIP_EINVAL, "%s: n_steps (the actor's period: NAC::handle(()) runs at every n_steps-th step of an episode, nac_softmax.rs) must be "
                                      "in [1, 65536], got %d", a.name, cfg.n_steps);
-    // GradientMC, LSTD and LSTDLambda keep every learner's open episode on the device, max_episode_steps rows of it
+    // GradientMC, LSTD, LSTDLambda and LambdaLSPE keep every learner's open episode on the device, max_episode_steps rows of it
     if ((a.agent == Agent::Gmc || a.agent == Agent::LstdBatch) && cfg.max_episode_steps < 1)
         return fail(RSRL_HIP_EINVAL, "%s: max_episode_steps must be >= 1 -- the device records every learner's open episode, and an unbounded episode "
                                      "(max_episode_steps = 0) has no record size", a.name);
+    if (cfg.algo == RSRL_LAMBDA_LSPE && !std::isfinite(cfg.alpha))
+        return fail(RSRL_HIP_EINVAL, "%s: alpha (the relaxation theta <- (1 - alpha) theta + alpha x of solve(), lambda_lspe.rs:55-56) must be finite, got %g", a.name, cfg.alpha);
     return RSRL_HIP_OK;
 }
 
@@ -409,6 +412,13 @@ static int create_impl(const rsrl_hip_config* cfg, rsrl_hip_ctx* c) {
         KCHECK();
         if (cfg->algo != RSRL_RECURSIVE_LSTD) TRY(ctx_alloc(c, &c->lstd_mu, sizeof(double) * nv, true));
         if (cfg->algo == RSRL_LSTD_LAMBDA) TRY(ctx_alloc(c, &c->lstd_z, sizeof(double) * nv, true));
+        if (cfg->algo == RSRL_LAMBDA_LSPE) {
+            // LambdaLSPE: delta = 0 (lambda_lspe.rs:41) and the row count F -- the identity's F rows make the first system full rank
+            const std::vector<double> pair = [&] { std::vector<double> v(2 * (size_t)N, 0.0); for (size_t i = 0; i < (size_t)N; ++i) v[2 * i + 1] = (double)c->F; return v; }();
+            TRY(ctx_alloc(c, &c->lstd_z, sizeof(double) * pair.size()));
+            HIP_TRY(hipMemcpyAsync(c->lstd_z, pair.data(), sizeof(double) * pair.size(), hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        }
         if (batch) TRY(ctx_alloc(c, &c->lstd_sing, sizeof(uint32_t) * (size_t)N, true));
     }
     if (keeps_record(cfg->algo)) {
@@ -710,7 +720,7 @@ int rsrl_hip_set_episode_steps(rsrl_hip_ctx* c, const uint32_t* steps) {
     return RSRL_HIP_OK;
 }
 // GradientMC's open episodes (rec_s / rec_r): read with NaN past each learner's episode_steps, installed whole
-static const char* const kNoEpisodeRecord = "only GradientMC, LSTD and LSTDLambda (RSRL_GRADIENT_MC, RSRL_LSTD, RSRL_LSTD_LAMBDA) keep the learners' open episodes on the device";
+static const char* const kNoEpisodeRecord = "only GradientMC, LSTD, LSTDLambda and LambdaLSPE (RSRL_GRADIENT_MC, RSRL_LSTD, RSRL_LSTD_LAMBDA, RSRL_LAMBDA_LSPE) keep the learners' open episodes on the device";
 int rsrl_hip_get_episode_record(rsrl_hip_ctx* c, float* states, float* rewards) {
     CHECK_CTX(c); FLUSH(c); if (!states || !rewards) return fail(RSRL_HIP_EINVAL, "null argument");
     if (!keeps_record(c->cfg.algo)) return fail(RSRL_HIP_ESTATE, "%s", kNoEpisodeRecord);

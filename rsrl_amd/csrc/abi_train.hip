@@ -432,7 +432,8 @@ int launch_agent(rsrl_hip_ctx* c, const Common& k, const BasisGeom& g, uint64_t 
         ok = !io && launch_gmc(cf.domain, cf.order, grid, block, c->stream, k, make_gmc(c), t, chunk, d_stats, nullptr);
         break;
     case AgentFamily::LstdBatchReg:      // (io: rsrl_hip_handle refuses the agents before it gets here; rsrl_hip_handle_transitions launches its own)
-        ok = !io && launch_lstd_batch(cf.domain, cf.order, cf.algo == RSRL_LSTD_LAMBDA, c->stream, k, make_lstd_batch(c), t, chunk, d_stats, nullptr);
+        if (cf.algo == RSRL_LAMBDA_LSPE) ok = !io && launch_lspe(cf.domain, cf.order, c->stream, k, make_lspe(c), t, chunk, d_stats, nullptr);
+        else ok = !io && launch_lstd_batch(cf.domain, cf.order, cf.algo == RSRL_LSTD_LAMBDA, c->stream, k, make_lstd_batch(c), t, chunk, d_stats, nullptr);
         break;
     case AgentFamily::TdAcBetaReg:       // (io: the int32 rsrl_hip_handle refuses a continuous ctx before it gets here; rsrl_hip_handle_f32 launches its own)
         ok = !io && launch_tdac_beta(cf.order, c->stream, k, make_tdac_beta(c), t, chunk, d_stats, nullptr);

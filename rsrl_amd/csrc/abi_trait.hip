@@ -344,7 +344,7 @@ int rsrl_hip_handle(rsrl_hip_ctx* c, const float* from_states, const int32_t* ac
     if (c->family == AgentFamily::GmcReg)
         return fail(RSRL_HIP_ESTATE, "GradientMC handles whole trajectories only (Handler<&Trajectory>, visited last to first): use rsrl_hip_handle_batch");
     if (c->family == AgentFamily::LstdBatchReg)
-        return fail(RSRL_HIP_ESTATE, "LSTD and LSTDLambda handle whole batches only (Handler<&Batch>, then solve()): use rsrl_hip_handle_transitions");
+        return fail(RSRL_HIP_ESTATE, "LSTD, LSTDLambda and LambdaLSPE handle whole batches only (Handler<&Batch>, then solve()): use rsrl_hip_handle_transitions");
     // the transition rsrl_hip_domain_step has just been handed (same arrays, every learner): accepted, launched with it (rsrl_hip_domain_step)
     CallFrame f(c);
     if (c->tp.stage == 1 && from_states == c->tp.from && actions == c->tp.act && rewards == c->tp.rew && to_states == c->tp.to && terminal == c->tp.term &&
@@ -616,13 +616,13 @@ int rsrl_hip_handle_batch(rsrl_hip_ctx* c, int64_t T, const float* states, const
     return f.finish();
 }
 
-// Handler<&Batch>::handle of LSTD / LSTDLambda for every learner (kernels_lstd_batch.hpp): whole transitions, then solve()
+// Handler<&Batch>::handle of LSTD / LSTDLambda / LambdaLSPE for every learner (kernels_lstd_batch.hpp): whole transitions, then solve()
 int rsrl_hip_handle_transitions(rsrl_hip_ctx* c, int64_t T, const float* from_states, const int32_t* actions, const float* rewards, const float* to_states,
                                 const uint8_t* terminal, const uint32_t* lengths, float* td_out) {
     CHECK_CTX(c);
     (void)actions;      // (neither agent reads them)
     if (c->family != AgentFamily::LstdBatchReg)
-        return fail(RSRL_HIP_ESTATE, "only LSTD and LSTDLambda handle batches of whole transitions (Handler<&Batch> reading from, to, reward and the terminal "
+        return fail(RSRL_HIP_ESTATE, "only LSTD, LSTDLambda and LambdaLSPE handle batches of whole transitions (Handler<&Batch> reading from, to, reward and the terminal "
                                      "flag); see rsrl_hip_handle and rsrl_hip_handle_batch for the other agents");
     if (T < 0) return fail(RSRL_HIP_EINVAL, "bad batch length T = %lld", (long long)T);
     if (!lengths || (T > 0 && (!from_states || !rewards || !to_states || !terminal))) return fail(RSRL_HIP_EINVAL, "null argument");
@@ -644,7 +644,10 @@ int rsrl_hip_handle_transitions(rsrl_hip_ctx* c, int64_t T, const float* from_st
     io.T = T;
     if (T > 0) {
         const Common k = make_common(c);
-        if (!launch_lstd_batch(c->cfg.domain, c->cfg.order, c->cfg.algo == RSRL_LSTD_LAMBDA, c->stream, k, make_lstd_batch(c), c->t, 1, nullptr, &io)) return NO_MODEL(c);
+        const bool launched = c->cfg.algo == RSRL_LAMBDA_LSPE
+            ? launch_lspe(c->cfg.domain, c->cfg.order, c->stream, k, make_lspe(c), c->t, 1, nullptr, &io)
+            : launch_lstd_batch(c->cfg.domain, c->cfg.order, c->cfg.algo == RSRL_LSTD_LAMBDA, c->stream, k, make_lstd_batch(c), c->t, 1, nullptr, &io);
+        if (!launched) return NO_MODEL(c);
         KCHECK();
     }
     c->q_valid = false;
@@ -652,12 +655,15 @@ int rsrl_hip_handle_transitions(rsrl_hip_ctx* c, int64_t T, const float* from_st
     return f.finish();
 }
 
-// the agents' public solve() (lstd.rs:40, lstd_lambda.rs:44) for every learner
+// the agents' public solve() (lstd.rs:40, lstd_lambda.rs:44) for every learner; LambdaLSPE's private one (lambda_lspe.rs:47) as handle ends with it
 int rsrl_hip_lstd_solve(rsrl_hip_ctx* c) {
     CHECK_CTX(c); FLUSH(c);
-    if (c->family != AgentFamily::LstdBatchReg) return fail(RSRL_HIP_ESTATE, "only LSTD and LSTDLambda have a solve() of their own");
+    if (c->family != AgentFamily::LstdBatchReg) return fail(RSRL_HIP_ESTATE, "only LSTD, LSTDLambda and LambdaLSPE have a solve() of their own");
     HIP_TRY(hipSetDevice(c->cfg.device));
-    if (!launch_lstd_batch_solve(c->cfg.domain, c->cfg.order, c->cfg.algo == RSRL_LSTD_LAMBDA, c->stream, make_lstd_batch(c), c->cfg.n_envs)) return NO_MODEL(c);
+    const bool launched = c->cfg.algo == RSRL_LAMBDA_LSPE
+        ? launch_lspe_solve(c->cfg.domain, c->cfg.order, c->stream, make_lspe(c), c->cfg.n_envs)
+        : launch_lstd_batch_solve(c->cfg.domain, c->cfg.order, c->cfg.algo == RSRL_LSTD_LAMBDA, c->stream, make_lstd_batch(c), c->cfg.n_envs);
+    if (!launched) return NO_MODEL(c);
     KCHECK();
     c->q_valid = false;
     HIP_TRY(hipStreamSynchronize(c->stream));

@@ -129,7 +129,7 @@ static int lstd_state_rw(rsrl_hip_ctx* c, int64_t env_index, double* theta, doub
                          const double* mu_in) {
     CHECK_CTX(c); FLUSH(c);
     if (!has_lstd_state(c)) return fail(RSRL_HIP_ESTATE, "only RecursiveLSTD and iLSTD (the iLSTD ActorCritic's critic included) carry a least-squares state");
-    if (has_batch_lstd_state(c)) return fail(RSRL_HIP_ESTATE, "LSTD and LSTDLambda carry A, b, z and singular_solves: rsrl_hip_get/set_lstd_batch_state");
+    if (has_batch_lstd_state(c)) return fail(RSRL_HIP_ESTATE, "LSTD, LSTDLambda and LambdaLSPE carry A, b, z and singular_solves: rsrl_hip_get/set_lstd_batch_state");
     if (env_index < 0 || env_index >= c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "env_index out of range");
     HIP_TRY(hipSetDevice(c->cfg.device));
     c->q_valid = false;
@@ -149,17 +149,28 @@ int rsrl_hip_set_lstd_state(rsrl_hip_ctx* c, int64_t env_index, const double* th
     if (!theta || !mat) return fail(RSRL_HIP_EINVAL, "null argument");
     return lstd_state_rw(c, env_index, nullptr, nullptr, nullptr, theta, mat, mu);
 }
-// LSTD / LSTDLambda: one learner's exact f64 state (theta [F], A [F][F], b [F], LSTDLambda's z [F] -- may be null) and its count of abandoned
-// solves.  Host or device arrays
+// LSTD / LSTDLambda / LambdaLSPE: one learner's exact f64 state (theta [F], A [F][F], b [F], z [F] -- may be null: LSTDLambda's trace, or
+// LambdaLSPE's z[0] = delta and z[1] = rows with zeros behind them) and its count of abandoned solves.  Host or device arrays
 static int lstd_batch_state_rw(rsrl_hip_ctx* c, int64_t env_index, double* const out[4], const double* const in[4], uint32_t* sing, const uint32_t* sing_in) {
     CHECK_CTX(c); FLUSH(c);
-    if (!has_batch_lstd_state(c)) return fail(RSRL_HIP_ESTATE, "only LSTD and LSTDLambda carry the batch least-squares state (theta, A, b, z)");
+    if (!has_batch_lstd_state(c)) return fail(RSRL_HIP_ESTATE, "only LSTD, LSTDLambda and LambdaLSPE carry the batch least-squares state (theta, A, b, z)");
     if (env_index < 0 || env_index >= c->cfg.n_envs) return fail(RSRL_HIP_EINVAL, "env_index out of range");
     HIP_TRY(hipSetDevice(c->cfg.device));
-    c->q_valid = false;
     const size_t F = (size_t)c->F, i = (size_t)env_index;
+    const size_t nz = lstd_z_per_learner(c->cfg.algo, c->F);      // (of the caller's F: LambdaLSPE's pair leads it)
+    const std::vector<double> zeros(out && out[3] && c->lstd_z && nz < F ? F - nz : 0, 0.0);      // (get: LambdaLSPE's z[2 ..]; alive until the synchronise below)
+    if (in && in[3] && c->cfg.algo == RSRL_LAMBDA_LSPE) {
+        // the row count steers the solve: checked before anything is installed (a device array through a host copy)
+        double pair[2];
+        HIP_TRY(hipMemcpyAsync(pair, in[3], sizeof(pair), hipMemcpyDefault, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (!(pair[1] >= 0.0 && pair[1] <= (double)F && pair[1] == std::floor(pair[1])))
+            return fail(RSRL_HIP_EINVAL, "LambdaLSPE: z[1] is the learner's row count, an integer in [0, %zu] (got %g)", F, pair[1]);
+    }
+    c->q_valid = false;
     const struct { double* dev; size_t n; } parts[4] = {
-        {c->lstd_theta + i * F, F}, {c->lstd_mat + i * F * F, F * F}, {c->lstd_mu + i * F, F}, {c->lstd_z ? c->lstd_z + i * F : nullptr, F}};
+        {c->lstd_theta + i * F, F}, {c->lstd_mat + i * F * F, F * F}, {c->lstd_mu + i * F, F}, {c->lstd_z ? c->lstd_z + i * nz : nullptr, nz}};
+    if (!zeros.empty()) HIP_TRY(hipMemcpyAsync(out[3] + nz, zeros.data(), 8 * zeros.size(), hipMemcpyDefault, c->stream));
     for (int p = 0; p < 4; ++p) {      // (z: LSTDLambda's only, and the caller's is optional)
         if (!parts[p].dev) continue;
         if (out && out[p]) HIP_TRY(hipMemcpyAsync(out[p], parts[p].dev, 8 * parts[p].n, hipMemcpyDefault, c->stream));
@@ -213,7 +224,7 @@ struct CkptKind {
     bool reads_kind0;            // a ctx of this kind also reads its configuration's version-2 / aux_kind-0 file, written before the kind's own section
     SectionId sections[3];       // travelled: the weights load, that section's state starts empty
 };
-constexpr int kCkptKinds = 19;
+constexpr int kCkptKinds = 20;
 constexpr CkptKind kCkptKind[kCkptKinds] = {
     /* 0 weights only                           */ {2, 0, true, false, {S_WEIGHTS}},
     /* 1 eligibility traces                     */ {2, 0, true, false, {S_WEIGHTS, S_AUX}},
@@ -235,6 +246,7 @@ constexpr CkptKind kCkptKind[kCkptKinds] = {
     /* 16 the continuous TD ActorCritic with the Beta policy: kind 15's sections */ {10, 0, false, false, {S_WEIGHTS, S_AUX}},
     /* 17 ... with the Gaussian policy */ {10, 0, false, false, {S_WEIGHTS, S_AUX}},      // (the kind alone tells the two policies' files, and CACLA's, apart)
     /* 18 NAC over the Gibbs policy: the critic's w ((A+1) F rows), theta (A columns) */ {10, 0, false, false, {S_WEIGHTS, S_AUX}},
+    /* 19 LambdaLSPE: f64 theta, A, b, (delta, rows) */ {10, 0, false, false, {S_LSTD, S_LSTD_BATCH}},      // (kind 10's sections; the pair in z's place)
 };
 // (the kinds the configuration decides, not the algo: SARSALambda / QLambda over ONE shared tile table keep sparse traces instead of Z; the iLSTD
 // ActorCritic with the Beta policy keeps two policy columns instead of the Gibbs actor's A; NAC's columns are the Gaussian policy's, not Beta's)
@@ -373,8 +385,9 @@ int lstd_install(CkptIo& io) {
     rsrl_hip_ctx* c = io.c; const size_t nv = (size_t)c->F * (size_t)c->cfg.n_envs; const double* in = io.lstd.data();
     return copy_sync(c, hipMemcpyHostToDevice, {{c->lstd_theta, in, 8 * nv}, {c->lstd_mat, in + nv, 8 * nv * c->F}, {c->lstd_mu, in + nv + nv * c->F, 8 * nv}}, "installing the LSTD state");
 }
-// ---- LSTD / LSTDLambda, behind S_LSTD's theta, A and b: f64 z[N][F] (LSTDLambda only), then u32 singular_solves[N] ----
-size_t lstd_z_doubles(const rsrl_hip_ctx* c) { return c->lstd_z ? (size_t)c->F * (size_t)c->cfg.n_envs : 0; }
+// ---- LSTD / LSTDLambda / LambdaLSPE, behind S_LSTD's theta, A and b: f64 z[N][F] (LSTDLambda) or f64 (delta, rows)[N] (LambdaLSPE), then u32
+// singular_solves[N] ----
+size_t lstd_z_doubles(const rsrl_hip_ctx* c) { return lstd_z_per_learner(c->cfg.algo, c->F) * (size_t)c->cfg.n_envs; }
 int lstd_batch_size(CkptIo& io) { io.expect += (long long)lstd_z_doubles(io.c) * 8 + (long long)io.c->cfg.n_envs * 4; return RSRL_HIP_OK; }
 int lstd_batch_write(CkptIo& io) {
     rsrl_hip_ctx* c = io.c;
@@ -385,7 +398,11 @@ int lstd_batch_write(CkptIo& io) {
 }
 int lstd_batch_read(CkptIo& io) {
     io.lstd_z.resize(lstd_z_doubles(io.c)); io.lstd_sing.resize((size_t)io.c->cfg.n_envs);
-    const int rc = get(io, io.lstd_z.data(), io.lstd_z.size());
+    int rc = get(io, io.lstd_z.data(), io.lstd_z.size());
+    for (size_t i = 0; rc == RSRL_HIP_OK && io.c->cfg.algo == RSRL_LAMBDA_LSPE && i < io.lstd_sing.size(); ++i) {
+        const double rows = io.lstd_z[2 * i + 1];      // (the solve is steered by it)
+        if (!(rows >= 0.0 && rows <= (double)io.c->F && rows == std::floor(rows))) rc = fail(RSRL_HIP_EINVAL, "%s: corrupt LambdaLSPE row count of learner %zu", io.path, i);
+    }
     return rc == RSRL_HIP_OK ? get(io, io.lstd_sing.data(), io.lstd_sing.size()) : rc;
 }
 int lstd_batch_install(CkptIo& io) {
@@ -556,7 +573,7 @@ const Section kSection[S_COUNT] = {
     /* S_AUX       */ {aux_size, aux_write, aux_read, nothing},                                  // n_learners x f32[F][aux_cols]: traces / fa_td's weights / the actor's theta
     /* S_BEHAVIOUR */ {behaviour_size, behaviour_write, behaviour_read, behaviour_install},      // n_learners x f32[F][A] of theta_b, then g[N]
     /* S_LSTD      */ {lstd_size, lstd_write, lstd_read, lstd_install},                          // f64: every learner's theta, then matrix, then (iLSTD) mu
-    /* S_LSTD_BATCH */ {lstd_batch_size, lstd_batch_write, lstd_batch_read, lstd_batch_install},     // f64 z (LSTDLambda), then u32 singular_solves[N]
+    /* S_LSTD_BATCH */ {lstd_batch_size, lstd_batch_write, lstd_batch_read, lstd_batch_install},     // f64 z (LSTDLambda) or (delta, rows) (LambdaLSPE), then u32 singular_solves[N]
     /* S_RING      */ {ring_size, ring_write, ring_read, ring_install},                          // head[N], len[N], entries (SoA [field][slot][learner])
     /* S_SPARSE    */ {sparse_size, sparse_write, sparse_read, sparse_install},                  // owner prefix, len[N], every learner's keys and values
     /* S_EPS       */ {eps_size, eps_write, eps_read, eps_install},                              // eps[N]
@@ -692,7 +709,7 @@ int rsrl_hip_checksum(rsrl_hip_ctx* c, uint64_t out[2]) {
     run(c->lstd_theta, c->lstd_theta ? sizeof(double) * c->F * N : 0, (size_t)1 << 41, 0);
     run(c->lstd_mat, c->lstd_mat ? sizeof(double) * c->F * c->F * N : 0, (size_t)1 << 42, 0);
     run(c->lstd_mu, c->lstd_mu ? sizeof(double) * c->F * N : 0, (size_t)1 << 43, 0);
-    run(c->lstd_z, c->lstd_z ? sizeof(double) * c->F * N : 0, (size_t)1 << 44, 0);            // LSTDLambda's trace, LSTD / LSTDLambda's abandoned solves
+    run(c->lstd_z, c->lstd_z ? sizeof(double) * lstd_z_per_learner(c->cfg.algo, c->F) * N : 0, (size_t)1 << 44, 0);      // LSTDLambda's trace or LambdaLSPE's (delta, rows); the batch agents' abandoned solves
     run(c->lstd_sing, c->lstd_sing ? sizeof(uint32_t) * N : 0, (size_t)1 << 45, 0);
     KCHECK();
     unsigned long long h[2];

@@ -63,7 +63,7 @@ struct AlgoRow {
     // one of them), the message's words behind it and behind "agent_policy = -1", and what it calls config.n_steps in front of "n_updates" (nullptr: not read)
     int reg_policy = -1; const char* policy_words = ""; const char* shares_words = ""; const char* n_updates = nullptr;
 };
-constexpr int kLastAlgo = RSRL_GIBBS_NAC;      // the highest assigned number (RSRL_CACLA stays the enum's textually last enumerator)
+constexpr int kLastAlgo = RSRL_LAMBDA_LSPE;      // the highest assigned number (RSRL_CACLA stays the enum's textually last enumerator)
 constexpr AlgoRow kAlgo[kLastAlgo + 1] = {
     /*  0 */ {"QLearning", Agent::OneStep},
     /*  1 */ {"SARSA", Agent::OneStep},
@@ -116,6 +116,9 @@ constexpr AlgoRow kAlgo[kLastAlgo + 1] = {
     // (W is the SCB critic's one column of (A+1) F rows -- weight_rows() --, the Gibbs policy's theta, A columns, in Z; config.n_steps is the actor's period,
     // checked by check_reg_only itself)
     /* 37 */ {"NAC over the Gibbs policy (RSRL_GIBBS_NAC)", Agent::GibbsNac, true, Aux::Policy, 18, false, false, RSRL_SOFTMAX, " (the Gibbs policy)", " (the critic shares the policy)"},
+    /* 38 */ {},
+    // (LSTDLambda's row in every column but the checkpoint's: lstd_z holds (delta, rows) per learner instead of the trace)
+    /* 39 */ {"LambdaLSPE (RSRL_LAMBDA_LSPE)", Agent::LstdBatch, true, Aux::None, 19, false, true, RSRL_RANDOM},
 };
 // (readers of the table, for configurations check_config has admitted: the algo is a row with a name)
 static inline bool is_lambda(int algo) { return kAlgo[algo].agent == Agent::Lambda; }
@@ -127,6 +130,8 @@ static inline bool is_lstd(int algo) { return kAlgo[algo].agent == Agent::Lstd; 
 static inline bool is_tdac_lstd(int algo) { return kAlgo[algo].agent == Agent::TdAcLstd; }
 static inline bool is_gmc(int algo) { return kAlgo[algo].agent == Agent::Gmc; }
 static inline bool is_lstd_batch(int algo) { return kAlgo[algo].agent == Agent::LstdBatch; }
+// the batch agents' lstd_z, doubles per learner: LSTDLambda's trace z[F]; LambdaLSPE's (delta, rows); LSTD has none
+static inline size_t lstd_z_per_learner(int algo, int F) { return algo == RSRL_LSTD_LAMBDA ? (size_t)F : (algo == RSRL_LAMBDA_LSPE ? 2 : 0); }
 static inline bool is_nac(int algo) { return kAlgo[algo].agent == Agent::Nac; }
 static inline bool is_gtd(int algo) { return kAlgo[algo].agent == Agent::Gtd; }
 static inline bool is_cacla(int algo) { return kAlgo[algo].agent == Agent::Cacla; }
@@ -222,7 +227,8 @@ enum class AgentFamily : uint8_t {
                           // LstdReg's, theta in Z (A columns)
     GmcReg,               // GradientMC, same configurations as LstdReg: k_train_gmc (train_gmc.hip); w in W (one column), the open episodes in rec_s / rec_r
     LstdBatchReg,         // LSTD / LSTDLambda, same configurations as GmcReg: k_train_lstd_batch (train_lstd_batch.hip); f64 state in lstd_theta / lstd_mat (A) /
-                          // lstd_mu (b) / lstd_z / lstd_sing, the open episodes in rec_s / rec_r
+                          // lstd_mu (b) / lstd_z / lstd_sing, the open episodes in rec_s / rec_r.  LambdaLSPE too: k_train_lspe (train_lspe.hip), named by
+                          // train_kernel_name; lstd_z is (delta, rows) per learner
     TdAcBetaReg,          // ActorCritic with the iLSTD critic and the Beta policy on ContinuousMountainCar, Fourier orders 1-5: k_train_tdac_beta
                           // (train_tdac_beta.hip); iLSTD's f64 state as LstdReg's, the policy's two columns in Z, f32 actions in action_f
     NacBetaReg,           // NAC with the Beta policy and the SCB SARSA critic on ContinuousMountainCar, Fourier orders 1-5: k_train_nac<ORDER, Beta>, reported as k_train_nac_beta (train_nac.hip),
@@ -378,8 +384,8 @@ struct rsrl_hip_ctx {
     double* lstd_theta = nullptr;    // RecursiveLSTD / iLSTD / the iLSTD ActorCritic only: theta f64[N][F], the matrix (C / A) f64[N][F][F], iLSTD's mu f64[N][F] (learner-major)
     double* lstd_mat = nullptr;
     double* lstd_mu = nullptr;       //   (LSTD / LSTDLambda: A in lstd_mat, b in lstd_mu)
-    double* lstd_z = nullptr;        // LSTDLambda only: the trace z f64[N][F]
-    uint32_t* lstd_sing = nullptr;   // LSTD / LSTDLambda only: u32[N], the solves abandoned on a zero pivot
+    double* lstd_z = nullptr;        // LSTDLambda: the trace z f64[N][F]; LambdaLSPE: (delta, rows) f64[N][2] (lstd_z_per_learner)
+    uint32_t* lstd_sing = nullptr;   // LSTD / LSTDLambda / LambdaLSPE only: u32[N], the solves abandoned on a zero pivot
     float* rec_s = nullptr;          // GradientMC, LSTD / LSTDLambda only: every learner's open episode, rows 0 .. ep_step[i]-1 of f32[max_episode_steps][D][N] (`from`) and
     float* rec_r = nullptr;          //   f32[max_episode_steps][N] (the reward)
     bool q_valid = false;            // false whenever weights / states were changed from outside the driver loop
@@ -522,6 +528,12 @@ static inline LstdBatchState make_lstd_batch(const rsrl_hip_ctx* c) {
     ls.theta = c->lstd_theta; ls.mat = c->lstd_mat; ls.b = c->lstd_mu; ls.z = c->lstd_z; ls.sing = c->lstd_sing;
     ls.rec_s = c->rec_s; ls.rec_r = c->rec_r;
     ls.gamma = c->cfg.gamma; ls.lambda = c->cfg.lambda;
+    return ls;
+}
+static inline LspeState make_lspe(const rsrl_hip_ctx* c) {
+    LspeState ls;
+    static_cast<LstdBatchState&>(ls) = make_lstd_batch(c);
+    ls.alpha = c->cfg.alpha;
     return ls;
 }
 static inline LstdState make_lstd(const rsrl_hip_ctx* c) {

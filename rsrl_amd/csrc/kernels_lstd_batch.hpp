@@ -349,4 +349,259 @@ __global__ __launch_bounds__(kBlock) void k_lstd_batch_solve(LstdBatchState ls, 
     L.store_solution(ls, i, r);
 }
 
+// ---- LambdaLSPE   rsrl/src/prediction/lstd/lambda_lspe.rs:27-107   theta, A (starts at 1e-6 I), b as above, plus the scalar return correction
+// delta and the row count `rows` (LstdBatchState::z holds the pair per learner: z[2 i] = delta, z[2 i + 1] = rows, an exact integer in 0 .. F).
+// handle walks the batch LAST TO FIRST (lambda_lspe.rs:72-101); theta does not move during the walk:
+//     delta = delta * (gamma * lambda)
+//     terminal:      b += (delta + r) phi(s);   A += phi(s) (x) phi(s);   delta = 0            (theta . phi(s) is NOT added: lambda_lspe.rs:81)
+//     non-terminal:  v_s = phi(s) . theta, v_n = phi(s') . theta (ascending index, from 0);   delta = delta + (r + gamma * v_n - v_s);
+//                    b += (v_s + delta) phi(s);   A += phi(s) (x) phi(s)
+// and ends in solve() (lambda_lspe.rs:47-62): x = A.solve(b) by LstdBatchLane::solve's elimination; on success theta_r = (1 - alpha) * theta_r +
+// alpha * x_r (1 - alpha once, three rounded operations per element) and A, b, delta are zeroed.  An abandoned elimination keeps theta, A, b AND
+// delta (the reference when both of its attempts fail) and counts in singular_solves.
+// DEPARTURE, the row rule: the reference's solve() zeroes A and b, so every batch shorter than F leaves a Gram matrix of fewer than F vectors --
+// singular in exact arithmetic, answered there by the SVD this library does not have, and in rounding NOT reported by the elimination (pivots near
+// 1e-17, one arbitrary member of the solution set).  So each learner counts the rows its A holds: F at create (the identity's), min(rows + len, F)
+// after every handled batch, 0 after a successful solve -- and solve() runs the elimination only at rows == F.  Otherwise the solve is DEFERRED:
+// nothing moves, singular_solves does not count, the next batch adds to the same A, b and delta.
+// The lane is LstdBatchLane<F, false> (row r of A, b_r, theta_r, the elimination) with delta and rows beside it, held redundantly by every lane of
+// the group and stored by lane 0.  Instantiated from train_lspe.hip alone: the two agents above keep their machine code.
+template <int F>
+struct LspeLane {
+    LstdBatchLane<F, false> m;
+    double delta, rows;
+
+    __device__ __forceinline__ void load(const LstdBatchState& ls, int64_t i, int r) {
+        m.load(ls, i, r);
+        delta = ls.z[2 * i];
+        rows = ls.z[2 * i + 1];
+    }
+    __device__ __forceinline__ void store_scalars(const LstdBatchState& ls, int64_t i, int r) const {
+        if (r != 0) return;
+        ls.z[2 * i] = delta;
+        ls.z[2 * i + 1] = rows;
+    }
+    __device__ __forceinline__ void store(const LstdBatchState& ls, int64_t i, int r) const {
+        m.store(ls, i, r);
+        store_scalars(ls, i, r);
+    }
+
+    // one transition of the lane's learner into A, b and delta; arguments and the returned diagnostic as LstdBatchLane::accumulate's -- here the
+    // two dot products are part of the rule, and the non-terminal diagnostic IS the rule's residual
+    __device__ __forceinline__ double accumulate(const LstdBatchState& ls, double (*lv)[F], int r, double phs, double phn, double rew, bool term, bool live) {
+        const double gamma = ls.gamma;
+        if (r < F) {
+            lv[LB_V][r] = phs;
+            lv[LB_X][r] = phs * m.theta;
+            lv[LB_Y][r] = phn * m.theta;
+        }
+        lstd_wave_sync();
+        const double v_s = lstd_sum<F>(lv[LB_X]);
+        const double v_n = lstd_sum<F>(lv[LB_Y]);
+        const double res = term ? rew - v_s : rew + gamma * v_n - v_s;
+        const double d0 = delta * (gamma * ls.lambda);
+        const double d1 = d0 + res;                       // (non-terminal)
+        const double coef = term ? d0 + rew : v_s + d1;
+        m.b = live ? m.b + coef * phs : m.b;
+#pragma unroll
+        for (int j = 0; j < F; ++j) m.row[j] = live ? m.row[j] + phs * lv[LB_V][j] : m.row[j];
+        delta = live ? (term ? 0.0 : d1) : delta;
+        lstd_wave_sync();                                 // (this transition's reads before the next one's writes)
+        return res;
+    }
+
+    // the rows a handled batch of `len` transitions adds (len = 0: none)
+    __device__ __forceinline__ void count_rows(int64_t len) {
+        const double n = rows + (double)len;
+        rows = n < (double)F ? n : (double)F;
+    }
+
+    // solve() as handle ends with it: the row rule, the relaxed step, the zeroing.  commit: the learner takes part (the other groups of the wave,
+    // and the learners whose solve is deferred, run along).  Every lane of the wave calls it
+    __device__ __forceinline__ void solve(const LspeState& ls, double (*lv)[F], int r, bool commit) {
+        const bool full = commit && rows == (double)F;
+        const double theta0 = m.theta;
+        const uint32_t sing0 = m.sing;
+        m.solve(lv, r, full);                             // theta <- x, or sing + 1
+        const bool done = full && m.sing == sing0;
+        const double alpha = ls.alpha;
+        const double keep = 1.0 - alpha;
+        const double relaxed = keep * theta0 + alpha * m.theta;
+        m.theta = done ? relaxed : theta0;
+#pragma unroll
+        for (int j = 0; j < F; ++j) m.row[j] = done ? 0.0 : m.row[j];
+        m.b = done ? 0.0 : m.b;
+        delta = done ? 0.0 : delta;
+        rows = done ? 0.0 : rows;
+    }
+};
+
+// Handler<&Batch>::handle's walk for LambdaLSPE, without the solve: lstd_batch_sweep's arguments, walked last to first as its LSTDLambda branch
+// (a record's phi(s) is kept as the next visit's phi(s'))
+template <int DOMAIN, int ORDER, int F>
+__device__ __forceinline__ double lspe_sweep(LspeLane<F>& L, const LstdBatchState& ls, double (*lv)[F], int r, const float* from, const float* to,
+                                             const float* rew, const uint8_t* term, int64_t N, int64_t i, int64_t len,
+                                             const float (&last_to)[Domain<DOMAIN>::D], bool last_term, float* __restrict__ td_out) {
+    constexpr int D = Domain<DOMAIN>::D;
+    double acc = 0.0, carry = 0.0;
+    for (int64_t k = 0; __ballot(k < len) != 0ull; ++k) {
+        const bool live = k < len;
+        const int64_t idx = live ? len - 1 - k : 0;       // (a group that runs along reads row 0: in bounds, not used)
+        const bool last = idx + 1 >= len;
+        const double rw = (double)rew[idx * N + i];
+        float s[D];
+#pragma unroll
+        for (int d = 0; d < D; ++d) s[d] = from[(idx * D + d) * N + i];
+        const double phs = lstd_feature<DOMAIN, ORDER>(s, r);
+        double phn;
+        bool tm;
+        if (to) {
+            float ns[D];
+#pragma unroll
+            for (int d = 0; d < D; ++d) ns[d] = to[(idx * D + d) * N + i];
+            tm = term[idx * N + i] != 0;
+            phn = lstd_feature<DOMAIN, ORDER>(ns, r);
+        } else {
+            phn = k == 0 ? lstd_feature<DOMAIN, ORDER>(last_to, r) : carry;
+            carry = phs;
+            tm = last && last_term;
+        }
+        const double res = L.accumulate(ls, lv, r, phs, phn, rw, tm, live);
+        if (live) {
+            acc = acc + fabs(res);
+            if (td_out && r == 0) td_out[idx * N + i] = (float)res;
+        }
+    }
+    return acc;
+}
+
+// LambdaLSPE's driver loop: k_train_lstd_batch's, draw for draw -- the record, the episode's end, the restart and the Random sample are that kernel's
+// text; the sweep and the solve are this agent's
+template <int DOMAIN, int ORDER>
+__global__ __launch_bounds__(kBlock) void k_train_lspe(Common c, LspeState ls, uint64_t t0, int n_steps, DevStats* __restrict__ stats) {
+    using Dom = Domain<DOMAIN>;
+    constexpr int D = Dom::D, A = Dom::A, F = FourierReg<DOMAIN, ORDER>::F;
+    constexpr int G = LstdGroup<F>::G;
+    __shared__ double lds[LstdGroup<F>::kPerBlock][LB_N][F];
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = tid / G;
+    const int r = (int)(tid % G);
+    const int64_t N = c.n_envs;
+    unsigned long long n_ep = 0, n_trunc = 0, sum_len = 0;
+    double sum_abs = 0.0, sum_r = 0.0;
+    if (i < N) {                                          // (whole groups: a group never straddles the bound)
+        double (*lv)[F] = lds[threadIdx.x / G];
+        PolicyParams pol = c.pol; pol.kind = POL_RANDOM;
+        const float q0[A] = {};
+        const uint32_t gid = (uint32_t)(c.env_offset + i);
+        const uint32_t cap = c.max_episode_steps;         // (>= 1: admission)
+        float s[D];
+#pragma unroll
+        for (int d = 0; d < D; ++d) s[d] = c.state[(int64_t)d * N + i];
+        int a = c.action[i];
+        uint32_t ep = c.ep_step[i];
+        LspeLane<F> L;
+        L.load(ls, i, r);
+        double acc_abs = 0.0, acc_r = 0.0;
+        for (int k = 0; k < n_steps; ++k) {
+            const uint64_t t = t0 + (uint64_t)k;
+            float ns[D];
+#pragma unroll
+            for (int d = 0; d < D; ++d) ns[d] = s[d];
+            float rw;
+            const bool term = Dom::step(ns, a, rw);
+            ep += 1;
+            const bool trunc = !term && ep >= cap;
+            const bool has_row = ep <= cap;               // (an episode_steps of cap set from outside: its one step has no row, and ends the episode)
+            if (has_row && r == 0) {
+                const int64_t row = (int64_t)ep - 1;
+#pragma unroll
+                for (int d = 0; d < D; ++d) ls.rec_s[(row * D + d) * N + i] = s[d];
+                ls.rec_r[row * N + i] = rw;
+            }
+            lstd_wave_sync();                             // (lane 0's row before the group's reads of it)
+            acc_r += (double)rw;
+            const bool ended = term || trunc;
+            if (__ballot(ended) != 0ull) {
+                // (the row-less step: the record's last `to` is this step's `from`, and the step itself is dropped)
+                float last_to[D];
+#pragma unroll
+                for (int d = 0; d < D; ++d) last_to[d] = has_row ? ns[d] : s[d];
+                const int64_t len = ended ? (int64_t)(ep < cap ? ep : cap) : 0;
+                acc_abs += lspe_sweep<DOMAIN, ORDER, F>(L, ls, lv, r, ls.rec_s, nullptr, ls.rec_r, nullptr, N, i, len, last_to, has_row && term, nullptr);
+                L.count_rows(len);
+                L.solve(ls, lv, r, ended);
+            }
+            if (term) Dom::reset(ns);
+            const U4 x = draw(c.seed, gid, t, BLK_STEP);
+            int na = policy_sample<A>(pol, q0, x);
+            if (term) { n_ep += 1; sum_len += ep; ep = 0; }
+            if (trunc) {
+                n_ep += 1; n_trunc += 1; sum_len += ep; ep = 0;
+                Dom::reset(ns);
+                const U4 xr = draw(c.seed, gid, t, BLK_RESET);
+                na = policy_sample<A>(pol, q0, xr);
+            }
+#pragma unroll
+            for (int d = 0; d < D; ++d) s[d] = ns[d];
+            a = na;
+        }
+        L.store(ls, i, r);
+        if (r == 0) {
+#pragma unroll
+            for (int d = 0; d < D; ++d) c.state[(int64_t)d * N + i] = s[d];
+            c.action[i] = a;
+            c.ep_step[i] = ep;
+            sum_abs = acc_abs; sum_r = acc_r;
+        } else {
+            n_ep = 0; n_trunc = 0; sum_len = 0;
+        }
+    }
+    if (stats) block_stats_accumulate(stats, n_ep, n_trunc, sum_len, sum_abs, sum_r);
+}
+
+// Handler<&Batch>::handle of LambdaLSPE for every learner: k_handle_lstd_batch's arguments and conventions (a learner of length 0 keeps its bytes:
+// no rows counted, no solve)
+template <int DOMAIN, int ORDER>
+__global__ __launch_bounds__(kBlock) void k_handle_lspe(LspeState ls, const float* __restrict__ from, const float* __restrict__ rew,
+                                                        const float* __restrict__ to, const uint8_t* __restrict__ term,
+                                                        const uint32_t* __restrict__ len, int64_t T, int64_t N, float* __restrict__ td_out) {
+    using Dom = Domain<DOMAIN>;
+    constexpr int D = Dom::D, F = FourierReg<DOMAIN, ORDER>::F;
+    constexpr int G = LstdGroup<F>::G;
+    __shared__ double lds[LstdGroup<F>::kPerBlock][LB_N][F];
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = tid / G;
+    const int r = (int)(tid % G);
+    if (i >= N) return;                                   // (whole groups: a group never straddles the bound)
+    double (*lv)[F] = lds[threadIdx.x / G];
+    const int64_t Ln = (int64_t)len[i] < T ? (int64_t)len[i] : T;      // (a device array of lengths is not inspected by the host: clamped here)
+    if (td_out && r == 0)
+        for (int64_t t = Ln; t < T; ++t) td_out[t * N + i] = __builtin_nanf("");
+    if (__ballot(Ln > 0) == 0ull) return;
+    LspeLane<F> L;
+    L.load(ls, i, r);
+    const float none[D] = {};
+    lspe_sweep<DOMAIN, ORDER, F>(L, ls, lv, r, from, to, rew, term, N, i, Ln, none, false, td_out);
+    L.count_rows(Ln);
+    L.solve(ls, lv, r, Ln > 0);
+    if (Ln > 0) L.store(ls, i, r);
+}
+
+// LambdaLSPE's solve() for every learner, exactly as handle ends with it (private in the reference: lambda_lspe.rs:47)
+template <int DOMAIN, int ORDER>
+__global__ __launch_bounds__(kBlock) void k_lspe_solve(LspeState ls, int64_t N) {
+    constexpr int F = FourierReg<DOMAIN, ORDER>::F;
+    constexpr int G = LstdGroup<F>::G;
+    __shared__ double lds[LstdGroup<F>::kPerBlock][LB_N][F];
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = tid / G;
+    const int r = (int)(tid % G);
+    if (i >= N) return;
+    LspeLane<F> L;
+    L.load(ls, i, r);
+    L.solve(ls, lds[threadIdx.x / G], r, true);
+    L.store(ls, i, r);
+}
+
 }  // namespace rsrl

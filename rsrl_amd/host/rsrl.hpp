@@ -373,6 +373,13 @@ struct LSTDLambda : control::td::Agent {
     LSTDLambda(const fa::linear::basis::Fourier& basis, double gamma, double lambda_)
         : control::td::Agent{RSRL_LSTD_LAMBDA, make_shared(fa::linear::LFA::vector(basis, fa::linear::optim::SGD(0.0), 1)), gamma, 1.0, RSRL_TRACE_ACCUMULATE, lambda_} {}
 };
+// LambdaLSPE::new(basis, alpha, gamma, lambda)   (lambda_lspe.rs:28-43).  Driven as LSTDLambda; Session::solve() is the agent's (private) solve() as
+// handle ends with it.  Session::lstd_batch_state(env, true): z[0] is the return correction delta and z[1] the learner's row count -- the solve is
+// deferred until A holds F rows (include/rsrl_hip.h RSRL_LAMBDA_LSPE, the row rule), then theta <- (1 - alpha) theta + alpha A^-1 b
+struct LambdaLSPE : control::td::Agent {
+    LambdaLSPE(const fa::linear::basis::Fourier& basis, double alpha_, double gamma, double lambda_)
+        : control::td::Agent{RSRL_LAMBDA_LSPE, make_shared(fa::linear::LFA::vector(basis, fa::linear::optim::SGD(0.0), 1)), gamma, alpha_, RSRL_TRACE_ACCUMULATE, lambda_} {}
+};
 }}  // namespace prediction::lstd
 // ---- rsrl::control::cacla: CACLA::new(critic, policy, alpha, gamma) (control/cacla.rs:11-29) with policies::Gaussian on
 // domains::ContinuousMountainCar.  critic: the reference's is any Function<(S,)> the agent reads and never writes; here it is the TD learner the

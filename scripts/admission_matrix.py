@@ -15,7 +15,8 @@ GRID_CACLA: NAC (28), the unassigned 32, CACLA (33) and 34 (past the last) x the
 agent_policy -1 / Gaussian x the Fourier orders 0-6 (336 configurations) -> create_admission_cacla.json (tests/test_cacla_cpu.py); and
 GRID_TDAC_CONT: CACLA (33), the unassigned 34, the continuous TD ActorCritic (35) and 36 (past the last) x the policies Softmax, Random, Beta, Gaussian x
 MountainCar / ContinuousMountainCar x agent_policy -1 / Gaussian x the Fourier orders 0-6 (448 configurations) -> create_admission_tdac_cont.json
-(tests/test_tdac_cont_cpu.py).
+(tests/test_tdac_cont_cpu.py); and GRID_LSPE: LambdaLSPE (39) between the unassigned 38 and 40 (past the last) on GRID's other axes, with
+max_episode_steps = 200 on every configuration as GRID_AGENTS3 (30 720 configurations) -> create_admission_lspe.json (tests/test_lspe_cpu.py).
     python scripts/admission_matrix.py            writes tests/golden/create_admission.json, create_admission_agents.json,
                                                   create_admission_agents2.json and create_admission_agents3.json
                                                   (tests/test_create_admission_cpu.py, tests/test_tdac_lstd_cpu.py and tests/test_gmc_cpu.py
@@ -40,6 +41,7 @@ GTD_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_gtd.json")
 GAUSS_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_gauss.json")
 CACLA_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_cacla.json")
 TDAC_CONT_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_tdac_cont.json")
+LSPE_FIXTURE = os.path.join(ROOT, "tests", "golden", "create_admission_lspe.json")
 EINVAL, EHIP = -1, -2
 
 # (config field, values): the first axis varies slowest
@@ -114,10 +116,14 @@ GRID_TDAC_CONT = [
     ("agent_policy", [-1, 6]),
     ("order", [0, 1, 2, 3, 4, 5, 6]),
 ]
+# LambdaLSPE (39) between the unassigned 38 and 40, on GRID's other axes; FIXED_AGENTS3 on every configuration (the agent records its open episodes)
+GRID_LSPE = [(name, [38, 39, 40] if name == "algo" else vals) for name, vals in GRID]
 # (grid, fixture, fields set on every configuration)
 GRIDS = ((GRID, FIXTURE, {}), (GRID_AGENTS, AGENTS_FIXTURE, {}), (GRID_AGENTS2, AGENTS2_FIXTURE, {}), (GRID_AGENTS3, AGENTS3_FIXTURE, FIXED_AGENTS3),
          (GRID_BETA, BETA_FIXTURE, {}), (GRID_NAC, NAC_FIXTURE, {}), (GRID_GTD, GTD_FIXTURE, {}),
          (GRID_GAUSS, GAUSS_FIXTURE, {}), (GRID_CACLA, CACLA_FIXTURE, {}), (GRID_TDAC_CONT, TDAC_CONT_FIXTURE, {}))
+# the grids added since (tests/test_tdac_cont_cpu.py holds GRIDS to its ten entries): swept and checked with them
+GRIDS_SINCE = ((GRID_LSPE, LSPE_FIXTURE, FIXED_AGENTS3),)
 
 
 def sweep(grid=GRID, fixed=None):
@@ -145,7 +151,7 @@ def admitted(results):
 
 def main():
     ok = True
-    for grid, fixture, fixed in GRIDS:
+    for grid, fixture, fixed in GRIDS + GRIDS_SINCE:
         res = sweep(grid, fixed)
         if any(rc == 0 for rc, _ in res.values()):
             sys.exit("a ctx was created: run this on a machine without a GPU")
