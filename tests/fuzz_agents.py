@@ -11,8 +11,7 @@ counts (ragged waves and LSTD lane groups), env offsets, discounts, step sizes, 
 
     python tests/fuzz_agents.py [n_cases=200] [seed=0]          (GPU box; test infrastructure: imports oracle/)
 
-One line per case and a SUMMARY {json} line; exit code 1 on any mismatch."""
-import json
+One line per case and a SUMMARY {json} line (tests/campaign.run); exit code 1 on any mismatch."""
 import os
 import sys
 import tempfile
@@ -27,7 +26,9 @@ from oracle import oracle as orc  # noqa: E402
 import fuzz_parity as fp  # noqa: E402
 from tests import hiv_numpy as hv  # noqa: E402
 from tests.ac_numpy import ac_rule, near_boundary  # noqa: E402
+from tests import campaign as cg  # noqa: E402
 from tests.agent_contract import diff, learner_state, rand_states, snapshot, trait_loop  # noqa: E402
+from tests.campaign import TOP_OF_IDS, count  # noqa: E402
 from tests.lstd_numpy import ilstd, near_tie_band, recursive_lstd  # noqa: E402
 from tests.reinforce_numpy import reinforce_batch  # noqa: E402
 from tests.tdac_numpy import tdac_rule  # noqa: E402
@@ -44,9 +45,6 @@ TRAIT_LOOP = (10, 11, 13, 18, 19, 0, 1, 2, 5)                        # whose tes
 AGENTS = (10, 11, 13, 15, 16, 18, 19, -1)                           # -1: HIVTreatment with a one-step agent
 
 
-TOP_OF_IDS = -1      # env_offset choice resolved to 2^32 - 1 - n_envs once n_envs is known
-
-
 def sample(rng, idx=None):
     """-> device kwargs of one configuration (case idx: the agents in turn)"""
     algo = AGENTS[idx % len(AGENTS)] if idx is not None else int(rng.choice(AGENTS))
@@ -61,8 +59,7 @@ def sample(rng, idx=None):
               lr=float(rng.choice([0.02, 0.2])) / F, alpha=float(rng.choice([0.02, 0.2])) / F, tau=float(rng.choice([0.05, 0.5, 1.0, 5.0])),
               n_envs=int(rng.choice([1, 3, 5, 63, 64, 65, 130, 257, 1000])), env_offset=int(rng.choice([0, 64, 1000003, (1 << 31) - 65, TOP_OF_IDS])),
               max_episode_steps=int(rng.choice([0, 1, 25, 200])), steps_per_launch=int(rng.choice([0, 1, 5])))
-    if kw["env_offset"] == TOP_OF_IDS:       # the shard that ends at the largest learner id a ctx admits ((1 << 31) - 65: ids that straddle the sign bit)
-        kw["env_offset"] = (1 << 32) - 1 - kw["n_envs"]
+    cg.top_of_ids(kw)                        # ((1 << 31) - 65: ids that straddle the sign bit)
     if algo in (10, 11, 13, 15, 16):
         kw["policy"] = ra.SOFTMAX
     elif algo in (18, 19):
@@ -249,43 +246,31 @@ def batch_leg(c, kw, rng, worst):
 
 
 def self_leg(kw, rng, legs):
-    """-> findings: random splits with queries between, the trait loop, shards, a checkpoint -- each against one uninterrupted run"""
-    bad = []
+    """-> findings: random splits with queries between, the trait loop, shards, a checkpoint -- each against one uninterrupted run.  Three
+    learners are compared, and the checksum with the split alone; the trait, shard and checkpoint parts run in half of the cases each"""
+    bad, made, counter = [], [], {}
     N, K = kw["n_envs"], int(rng.choice([10, 25, 40]))
     look = sorted(set([0, N // 2, N - 1]))
-    with ra.Context(**kw) as c:
-        c.reset()
-        c.train(K, want_stats=False)
-        ref = snapshot(c, look)
-        ck = c.checksum()
-    cuts = sorted(set(int(x) for x in rng.integers(1, K, size=int(rng.integers(1, 4)))))
-    calls = [b - a for a, b in zip([0] + cuts, cuts + [K])]
-    with ra.Context(**kw) as c, tempfile.TemporaryDirectory() as td:
-        c.reset()
-        made, counter = [], {}
-        for j, k in enumerate(calls):
-            c.train(k, want_stats=bool(rng.integers(0, 2)))
-            if j + 1 < len(calls):
-                b_, m_ = fp.query_leg(c, rng, td, counter)
-                bad += b_; made += m_
-        if diff(snapshot(c, look), ref) or c.checksum() != ck:
-            bad.append(f"train {calls} with queries {made} != train({K})")
-        legs["split+query"] = legs.get("split+query", 0) + 1
+
+    def full(c):
+        return snapshot(c, look)
+    ref = cg.reference_run(kw, K, full)
+    with tempfile.TemporaryDirectory() as td:
+        def between(c):
+            b_, m_ = fp.query_leg(c, rng, td, counter)
+            bad.extend(b_); made.extend(m_)
+        got, calls = cg.split_run(kw, rng, K, cg.draw_calls(rng, K, 1, 4), full, between=between)
+    if cg.differs(got, ref):
+        bad.append(f"train {calls} with queries {made} != train({K})")
+    count(legs, "split+query")
     if kw["algo"] in TRAIT_LOOP and rng.random() < 0.5:
-        with ra.Context(**kw) as c:
-            c.reset()
-            trait_loop(c, K, kw["max_episode_steps"])
-            if diff(snapshot(c, look), ref):
-                bad.append("the host trait loop != train")
-        legs["trait"] = legs.get("trait", 0) + 1
+        if cg.differs(cg.trait_run(kw, K, kw["max_episode_steps"], trait_loop, full), ref, checksum=False):
+            bad.append("the host trait loop != train")
+        count(legs, "trait")
     if N >= 3 and rng.random() < 0.5:
+        # a ragged shard point, and its own comparison: the env side and the learners on either side of each seam against a second unsharded run
         n1 = int(rng.integers(1, N))
-        parts = []
-        for off, cnt in ((0, n1), (n1, N - n1)):
-            with ra.Context(**dict(kw, n_envs=cnt, env_offset=kw["env_offset"] + off)) as cs:
-                cs.reset()
-                cs.train(K, want_stats=False)
-                parts.append((cs.states, cs.actions, learner_state(cs, 0), learner_state(cs, cnt - 1)))
+        parts = cg.shard_run(kw, K, (n1, N - n1), lambda cs: (cs.states, cs.actions, learner_state(cs, 0), learner_state(cs, cs.N - 1)))
         with ra.Context(**kw) as cf:
             cf.reset()
             cf.train(K, want_stats=False)
@@ -295,28 +280,20 @@ def self_leg(kw, rng, legs):
                 not diff(parts[1][2], learner_state(cf, n1)) and not diff(parts[1][3], learner_state(cf, N - 1))
         if not okp:
             bad.append(f"shards {n1} + {N - n1} != the unsharded run")
-        legs["shard"] = legs.get("shard", 0) + 1
+        count(legs, "shard")
     if rng.random() < 0.5:
         k1 = int(rng.integers(1, K))
-        with ra.Context(**kw) as c, ra.Context(**kw) as c2, tempfile.TemporaryDirectory() as td:
-            c.reset()
-            c.train(k1, want_stats=False)
-            path = os.path.join(td, "w.rsrlw")
-            c.save_weights(path)
-            c2.reset()
-            c2.train(2, want_stats=False)                           # (something to overwrite)
-            c2.load_weights(path)
-            c2.states, c2.actions, c2.episode_steps = c.states, c.actions, c.episode_steps
+
+        def carry(c, c2):
             if kw["domain"] == 3:
                 c2.set_hidden_states(c.get_hidden_states())            # (after the observations: set_states re-derives the hidden state from them)
             if kw["algo"] in (15, 16):
                 c2.return_carry = c.return_carry
                 for i in range(N):
                     c2.set_behaviour_weights(c.get_behaviour_weights(i), i)
-            c2.train(K - k1, want_stats=False)
-            if diff(snapshot(c2, look), ref):
-                bad.append(f"checkpoint at {k1} resumed != train({K})")
-        legs["ckpt"] = legs.get("ckpt", 0) + 1
+        if cg.differs(cg.resume_run(kw, K, k1, full, carry=carry), ref, checksum=False):
+            bad.append(f"checkpoint at {k1} resumed != train({K})")
+        count(legs, "ckpt")
     return bad
 
 
@@ -325,45 +302,27 @@ def run_case(rng, idx, worst, legs):
     al = kw["algo"]
     tag = f"{idx:4d} {NAMES[al]:18s} dom {kw['domain']} ord {kw['order']} N {kw['n_envs']:4d} off {kw['env_offset']:7d} cap {kw['max_episode_steps']:3d} " \
           f"spl {kw['steps_per_launch']}"
-    try:
-        c = ra.Context(**kw)
-    except ra.RsrlHipError as e:
-        return "refused", tag + f"  REFUSED: {str(e)[:90]}", kw
+    c, refused = cg.create(tag, kw)
+    if refused:
+        return refused
     bad = []
     with c:
         c.reset()
         if al in (15, 16):
             bad += [f"batch: {b}" for b in batch_leg(c, kw, rng, worst)]
-            legs["batch"] = legs.get("batch", 0) + 1
+            count(legs, "batch")
         else:
             bad += [f"f64: {b}" for b in f64_leg(c, kw, rng, worst)]
-            legs["f64"] = legs.get("f64", 0) + 1
+            count(legs, "f64")
     bad += [f"self: {b}" for b in self_leg(kw, rng, legs)]
-    if bad:
-        return "MISMATCH", tag + f"  MISMATCH {bad[:4]}", kw
-    return "ok", tag + "  ok", kw
+    return cg.verdict(tag, kw, bad)
 
 
 def main():
-    n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
-    rng = np.random.default_rng(seed)
-    counts, per_agent, failures, worst, legs = {}, {}, [], {}, {}
-    for idx in range(n_cases):
-        try:
-            status, line, kw = run_case(rng, idx, worst, legs)
-        except Exception as e:      # noqa: BLE001
-            status, line, kw = "ERROR", f"{idx:4d} ERROR {type(e).__name__}: {str(e)[:200]}", None
-        counts[status] = counts.get(status, 0) + 1
-        if kw is not None:
-            a = per_agent.setdefault(NAMES[kw["algo"]], {})
-            a[status] = a.get(status, 0) + 1
-        print(line, flush=True)
-        if status in ("MISMATCH", "ERROR"):
-            failures.append({"case": idx, "line": line, "config": kw})
-    print("SUMMARY " + json.dumps({"cases": n_cases, "seed": seed, "counts": counts, "per_agent": per_agent, "legs": legs,
-                                   "worst_vs_f64": worst, "failures": failures}, default=str), flush=True)
-    sys.exit(1 if failures else 0)
+    n_cases, seed = cg.parse_cases(sys.argv[1:])
+    rng = np.random.default_rng(seed)                               # one generator through the whole run: a leg's draws decide the next case
+    worst, legs = {}, {}
+    cg.run(lambda idx: run_case(rng, idx, worst, legs), n_cases, seed, NAMES, lambda failures: {"legs": legs, "worst_vs_f64": worst})
 
 
 if __name__ == "__main__":

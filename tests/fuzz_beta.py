@@ -21,8 +21,8 @@ neighbours and interior values.  Legs:
 Case idx draws everything from case_rng(seed, idx, agents), the host inputs of its f64 leg first (tests/test_fuzz_late_cpu.py rebuilds them without
 a device).  A learner-round whose decision the f64 restatement finds within a rounding of its boundary -- an inner draw within MARGIN of an
 acceptance test (28), an |mu_j| next to iLSTD's tie band (21) -- is left out of the tolerance comparisons only; at most 5 % of the replayed
-learner-rounds of a run, asserted here.  The bounds: bound_of below.  One line per case and a SUMMARY {json} line; exit code 1 on any mismatch."""
-import json
+learner-rounds of a run, asserted here.  The bounds: bound_of below.  One line per case and a SUMMARY {json} line
+(tests/campaign.run); exit code 1 on any mismatch."""
 import os
 import sys
 import tempfile
@@ -35,8 +35,9 @@ import rsrl_amd as ra  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
 from tests import beta_numpy as bn  # noqa: E402
 from tests import nac_numpy as nn  # noqa: E402
+from tests import campaign as cg  # noqa: E402
 from tests.agent_contract import diff, join_shards, learner_state, snapshot, trait_loop  # noqa: E402
-from tests.fuzz_episodic import parse_agents  # noqa: E402
+from tests.campaign import TOP_OF_IDS, count  # noqa: E402
 from tests.lstd_numpy import near_tie_band  # noqa: E402
 from tests.test_gpu_nac_beta import MEASURED as NAC_MEASURED  # noqa: E402
 from tests.test_gpu_tdac_beta import MEASURED as TDAC_MEASURED  # noqa: E402
@@ -44,8 +45,6 @@ from tests.test_gpu_tdac_beta import MEASURED as TDAC_MEASURED  # noqa: E402
 NAMES = {21: "BetaActorCritic", 28: "NAC"}
 AGENTS = (21, 28)
 CMC = ra.CONTINUOUS_MOUNTAIN_CAR
-REFUSALS = (-1, -5)
-TOP_OF_IDS = -1
 MAX_K = 60
 REPLAYED = 8
 ROUNDS = 2
@@ -79,7 +78,7 @@ def bound_of(name, order):
 
 
 def case_rng(seed, idx, agents=AGENTS):
-    return np.random.default_rng([seed, idx, agents[idx % len(agents)]])
+    return cg.case_rng(seed, idx, agents[idx % len(agents)])
 
 
 def sample(rng, idx=None, agents=AGENTS):
@@ -90,9 +89,7 @@ def sample(rng, idx=None, agents=AGENTS):
               n_envs=int(rng.choice([1, 3, 5, 63, 64, 65, 130, 257])), env_offset=int(rng.choice([0, 64, 1000003, (1 << 31) - 65, TOP_OF_IDS])),
               max_episode_steps=int(rng.choice([0, 1, 7, 23, 200])), steps_per_launch=int(rng.choice([0, 1, 5, 64])),
               n_steps=int(rng.integers(1, 5)) if algo == 21 else int(rng.choice([1, 2, 7, 100])))
-    if kw["env_offset"] == TOP_OF_IDS:
-        kw["env_offset"] = (1 << 32) - 1 - kw["n_envs"]
-    return kw
+    return cg.top_of_ids(kw)
 
 
 def preference(rng, branch):
@@ -339,6 +336,7 @@ def nac_trait_loop(c, K, cap):
 
 
 def read_only_calls(c, rng, tmp):
+    """this campaign's named calls, on its own draws, through tests/campaign.read_only_calls -> (findings, the calls made)"""
     N = c.N
     S = rng.uniform(LO_S, HI_S, size=(N, 2)).T.astype(np.float32)
     a = edge_actions(rng, N)
@@ -351,80 +349,40 @@ def read_only_calls(c, rng, tmp):
         calls.update({"q_evaluate": lambda: c.q_evaluate(S), "get_lstd_state": lambda: c.get_lstd_state(i)})
     else:
         calls["q_evaluate_f32"] = lambda: c.q_evaluate_f32(S, a)
-    names, bad, made = list(calls), [], []
-    for j in rng.permutation(len(names))[: int(rng.integers(1, 5))]:
-        name = names[int(j)]
-        made.append(name)
-        ck = c.checksum()
-        try:
-            calls[name]()
-        except ra.RsrlHipError as e:
-            if e.code not in REFUSALS:
-                bad.append(f"{name}: {str(e)[:80]}")
-        if c.checksum() != ck:
-            bad.append(f"{name} moved the checksum")
-    return bad, made
+    return cg.read_only_calls(c, rng, calls)
 
 
 def self_leg(kw, rng, legs):
     """-> (findings, the reason the case diverged or None)"""
-    bad = []
+    bad, made = [], []
     N, cap, al = kw["n_envs"], kw["max_episode_steps"], kw["algo"]
     K = int(rng.choice([10, 25, 40, MAX_K]))
-    trait = trait_loop if al == 21 else nac_trait_loop
-    with ra.Context(**kw) as c:
-        start_near_the_goal(c, 0)
-        c.train(K, want_stats=False)
-        ref, ck = snapshot(c), c.checksum()
-    if not all(np.isfinite(v).all() for v in ref.values()):
+    ref = cg.reference_run(kw, K, snapshot, start_near_the_goal)
+    if not all(np.isfinite(v).all() for v in ref[0].values()):
         return bad, f"train({K}) left non-finite state (lr {kw['lr']:.3g}, alpha {kw['alpha']:.3g})"
-    cuts = sorted(set(int(x) for x in rng.integers(1, K, size=int(rng.integers(1, 4)))))
-    calls = [b - a for a, b in zip([0] + cuts, cuts + [K])]
-    with ra.Context(**kw) as c, tempfile.TemporaryDirectory() as td:
-        start_near_the_goal(c, 0)
-        made = []
-        for j, k in enumerate(calls):
-            c.train(k, want_stats=bool(rng.integers(0, 2)))
-            if j + 1 < len(calls):
-                b_, m_ = read_only_calls(c, rng, td)
-                bad += b_; made += m_
-        names = diff(snapshot(c), ref)
-        if names or c.checksum() != ck:
-            bad.append(f"train {calls} with {made} != train({K}): {names or 'checksum'}")
-    legs["split+query"] = legs.get("split+query", 0) + 1
-    with ra.Context(**kw) as c:
-        start_near_the_goal(c, 0)
-        trait(c, K, cap)
-        names = diff(snapshot(c), ref)
-        if names:
-            bad.append(f"the host trait loop != train({K}): {names}")
-    legs["trait"] = legs.get("trait", 0) + 1
+    with tempfile.TemporaryDirectory() as td:
+        def between(c):
+            b_, m_ = read_only_calls(c, rng, td)
+            bad.extend(b_); made.extend(m_)
+        got, calls = cg.split_run(kw, rng, K, cg.draw_calls(rng, K, 1, 4), snapshot, start_near_the_goal, between)
+    names = cg.differs(got, ref)
+    if names:
+        bad.append(f"train {calls} with {made} != train({K}): {names}")
+    count(legs, "split+query")
+    names = cg.differs(cg.trait_run(kw, K, cap, trait_loop if al == 21 else nac_trait_loop, snapshot, start_near_the_goal), ref, checksum=False)
+    if names:
+        bad.append(f"the host trait loop != train({K}): {names}")
+    count(legs, "trait")
     if N % 2 == 0:
-        parts = []
-        for off in (0, N // 2):
-            with ra.Context(**dict(kw, n_envs=N // 2, env_offset=kw["env_offset"] + off)) as cs:
-                start_near_the_goal(cs, off)
-                cs.train(K, want_stats=False)
-                parts.append(snapshot(cs))
-        names = diff(join_shards(*parts), ref)
+        names = diff(join_shards(*cg.shard_run(kw, K, (N // 2, N // 2), snapshot, start_near_the_goal)), ref[0])
         if names:
             bad.append(f"two shards of {N // 2} joined != train({K}): {names}")
-        legs["shard"] = legs.get("shard", 0) + 1
+        count(legs, "shard")
     k1 = int(rng.integers(1, K))
-    with ra.Context(**kw) as a, ra.Context(**kw) as b, tempfile.TemporaryDirectory() as td:
-        start_near_the_goal(a, 0)
-        a.train(k1, want_stats=False)
-        path = os.path.join(td, "w.ckpt")
-        a.save_weights(path)
-        b.reset()
-        b.train(2, want_stats=False)                                # (something to overwrite)
-        b.load_weights(path)
-        b.states, b.actions, b.episode_steps = a.states, a.actions, a.episode_steps
-        b.train(K - k1, want_stats=False)
-        names = diff(snapshot(b), ref)
-        if names or b.checksum() != ck:
-            bad.append(f"checkpoint at {k1} resumed != train({K}): {names or 'checksum'}")
-    legs["ckpt"] = legs.get("ckpt", 0) + 1
+    names = cg.differs(cg.resume_run(kw, K, k1, snapshot, start_near_the_goal), ref)
+    if names:
+        bad.append(f"checkpoint at {k1} resumed != train({K}): {names}")
+    count(legs, "ckpt")
     return bad, None
 
 
@@ -435,10 +393,9 @@ def run_case(seed, idx, agents, worst, legs, tally):
     io = f64_inputs(rng, kw)
     tag = f"{idx:4d} {NAMES[al]:15s} ord {kw['order']} N {kw['n_envs']:3d} off {kw['env_offset']:10d} cap {kw['max_episode_steps']:3d} spl {kw['steps_per_launch']:2d} " \
           f"gamma {kw['gamma']} lr {kw['lr']:.2e} alpha {kw['alpha']:.2e} n_steps {kw['n_steps']:3d}"
-    try:
-        c = ra.Context(**kw)
-    except ra.RsrlHipError as e:
-        return "refused", tag + f"  REFUSED: {str(e)[:90]}", kw
+    c, refused = cg.create(tag, kw)
+    if refused:
+        return refused
     bad = []
     w = worst.setdefault(NAMES[al], {})
     with c:
@@ -447,39 +404,23 @@ def run_case(seed, idx, agents, worst, legs, tally):
                 bad += [f"f64: {b}" for b in f64_leg_tdac(c, v, kw, io, rng, w, tally)]
         else:
             bad += [f"f64: {b}" for b in f64_leg_nac(c, kw, io, rng, w, tally)]
-        legs["f64"] = legs.get("f64", 0) + 1
+        count(legs, "f64")
     b_, why = self_leg(kw, rng, legs)
     bad += [f"self: {b}" for b in b_]
-    if bad:
-        return "MISMATCH", tag + f"  MISMATCH {bad[:4]}", kw
-    if why is not None:
-        return "diverged", tag + f"  diverged: {why}", kw
-    return "ok", tag + "  ok", kw
+    return cg.verdict(tag, kw, bad, why)
 
 
 def main():
-    pos = [a for a in sys.argv[1:] if "=" not in a]
-    n_cases = int(pos[0]) if len(pos) > 0 else 200
-    seed = int(pos[1]) if len(pos) > 1 else 0
-    agents = parse_agents(sys.argv[1:], NAMES) or AGENTS
-    counts, per_agent, failures, worst, legs, tally = {}, {}, [], {}, {}, {"replayed": 0, "left_out": 0}
-    for idx in range(n_cases):
-        try:
-            status, line, kw = run_case(seed, idx, agents, worst, legs, tally)
-        except Exception as e:      # noqa: BLE001
-            status, line, kw = "ERROR", f"{idx:4d} ERROR {type(e).__name__}: {str(e)[:200]}", None
-        counts[status] = counts.get(status, 0) + 1
-        if kw is not None:
-            a = per_agent.setdefault(NAMES[kw["algo"]], {})
-            a[status] = a.get(status, 0) + 1
-        print(line, flush=True)
-        if status in ("MISMATCH", "ERROR"):
-            failures.append({"case": idx, "line": line, "config": kw})
-    if tally["left_out"] > LEFT_OUT_CAP * max(tally["replayed"], 1):
-        failures.append({"case": None, "line": f"{tally['left_out']} of {tally['replayed']} replayed learner-rounds left out: more than {LEFT_OUT_CAP:.0%}", "config": None})
-    print("SUMMARY " + json.dumps({"cases": n_cases, "seed": seed, "counts": counts, "per_agent": per_agent, "legs": legs, "worst": worst,
-                                   "replayed": tally["replayed"], "left_out": tally["left_out"], "failures": failures}, default=str), flush=True)
-    sys.exit(1 if failures else 0)
+    n_cases, seed = cg.parse_cases(sys.argv[1:])
+    agents = cg.parse_agents(sys.argv[1:], NAMES) or AGENTS
+    worst, legs, tally = {}, {}, {"replayed": 0, "left_out": 0}
+
+    def left_out_cap(failures):
+        if tally["left_out"] > LEFT_OUT_CAP * max(tally["replayed"], 1):
+            line = f"{tally['left_out']} of {tally['replayed']} replayed learner-rounds left out: more than {LEFT_OUT_CAP:.0%}"
+            failures.append({"case": None, "line": line, "config": None})
+    cg.run(lambda idx: run_case(seed, idx, agents, worst, legs, tally), n_cases, seed, NAMES,
+           lambda failures: {"legs": legs, "worst": worst, "replayed": tally["replayed"], "left_out": tally["left_out"]}, left_out_cap)
 
 
 if __name__ == "__main__":

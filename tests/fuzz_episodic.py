@@ -21,8 +21,7 @@ read for 25 / 26; they solve at every episode end), so there is none to draw.  L
 
 Case idx draws everything from case_rng(seed, idx, agents) -- the host inputs of its batch leg first -- so that a case's inputs can be rebuilt without
 a device (tests/test_fuzz_late_cpu.py).  An LSTD case whose f64 accumulators are not finite is counted as `diverged`, with the reason printed.
-One line per case and a SUMMARY {json} line; exit code 1 on any mismatch."""
-import json
+One line per case and a SUMMARY {json} line (tests/campaign.run); exit code 1 on any mismatch."""
 import os
 import sys
 import tempfile
@@ -33,7 +32,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import rsrl_amd as ra  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
+from tests import campaign as cg  # noqa: E402
 from tests.agent_contract import diff, gmc_trait_loop, join_shards, learner_state, lstd_batch_trait_loop, rand_states, record_bits, snapshot  # noqa: E402
+from tests.campaign import TOP_OF_IDS, bits, count  # noqa: E402
 from tests.gmc_numpy import td_chain  # noqa: E402
 from tests.lstd_batch_numpy import handle, lu_solve, state_of  # noqa: E402
 from tests.test_gpu_lstd_batch import crafted  # noqa: E402
@@ -43,26 +44,15 @@ AGENTS = (23, 25, 26)
 REG = [(0, o) for o in (1, 2, 3, 4, 5)] + [(1, 1), (2, 1)]          # the register-family Fourier orders check_config admits for them
 N_DIM = {0: 2, 1: 4, 2: 4}
 EPS64 = np.finfo(np.float64).eps
-REFUSALS = (-1, -5)                                                 # EINVAL, ESTATE: what a read-only call may refuse with
-TOP_OF_IDS = -1      # env_offset choice resolved to 2^32 - 1 - n_envs once n_envs is known
 MAX_K = 60           # horizon of the self and env legs, batch-steps
 MAX_T_LSTD = 12      # rows of the LSTD batch leg (the restatement is Python loops over F^2 per row)
 REPLAYED = 8
 SUITE_SEED, SUITE_CASES = 20261020, 24      # the slice tests/test_gpu_fuzz.py runs per agent (tests/test_fuzz_late_cpu.py checks its shares on the CPU)
 
 
-def parse_agents(argv, names):
-    """the agents= argument: numbers or names, comma separated -> tuple of algo numbers"""
-    for a in argv:
-        if a.startswith("agents="):
-            by_name = {v: k for k, v in names.items()}
-            return tuple(int(x) if x.lstrip("-").isdigit() else by_name[x] for x in a[7:].split(",") if x)
-    return None
-
-
 def case_rng(seed, idx, agents=AGENTS):
     """case idx's generator: keyed by the seed, the case and its agent, so that an agent's slice is not another's with the algo swapped"""
-    return np.random.default_rng([seed, idx, agents[idx % len(agents)]])
+    return cg.case_rng(seed, idx, agents[idx % len(agents)])
 
 
 def sample(rng, idx=None, agents=AGENTS):
@@ -74,9 +64,7 @@ def sample(rng, idx=None, agents=AGENTS):
               lam=float(rng.choice([0.0, 0.5, 0.8, 1.0])), lr=float(rng.choice([0.02, 0.2])) / F,
               n_envs=int(rng.choice([1, 3, 5, 63, 64, 65, 130, 257])), env_offset=int(rng.choice([0, 64, 1000003, (1 << 31) - 65, TOP_OF_IDS])),
               max_episode_steps=int(rng.choice([1, 2, 7, 25, 200])), steps_per_launch=int(rng.choice([0, 1, 5, 64])))
-    if kw["env_offset"] == TOP_OF_IDS:       # the shard that ends at the largest learner id a ctx admits
-        kw["env_offset"] = (1 << 32) - 1 - kw["n_envs"]
-    return kw
+    return cg.top_of_ids(kw)
 
 
 def batch_inputs(rng, kw):
@@ -122,10 +110,6 @@ def finite_state(st):
     return all(np.isfinite(np.asarray(st[k], dtype=np.float64)).all() for k in ("theta", "A", "b") + (("z",) if "z" in st else ()))
 
 
-def bits(x):
-    return np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
-
-
 def full(c, learners=None):
     out = snapshot(c, learners)
     out.update(record_bits(c))
@@ -157,7 +141,7 @@ def batch_leg_gmc(c, kw, io, worst):
             bad.append(f"returns of learner {i} (length {n} of {T})")
         if not np.array_equal(bits(got[i]), bits(w)):
             bad.append(f"weights of learner {i} (length {n} of {T})")
-        worst["replayed"] = worst.get("replayed", 0) + 1
+        count(worst, "replayed")
     return bad
 
 
@@ -214,14 +198,14 @@ def batch_leg_lstd(c, kw, io, worst):
         if s_theta.tobytes() != np.asarray(want_theta, dtype=np.float64).tobytes() or s_sing != g_sing + s:
             bad.append(f"lstd_solve of learner {i}{' (planted kind %d)' % io['planted'][1] if io['planted'] and io['planted'][0] == i else ''}: "
                        f"singular {s_sing}, want {g_sing + s}")
-        worst["replayed"] = worst.get("replayed", 0) + 1
+        count(worst, "replayed")
     if io["planted"] and io["planted"][1] == 3 and F > 1 and c.get_lstd_batch_state(io["planted"][0])[4] != io["init"][io["planted"][0]][4] + 1:
         bad.append("two equal rows were not counted as an abandoned solve")
     return bad, None
 
 
 def read_only_calls(c, rng, tmp):
-    """1-4 random calls that change nothing: the checksum before and after each is equal -> (findings, the calls made)"""
+    """this campaign's named calls, on its own draws, through tests/campaign.read_only_calls -> (findings, the calls made)"""
     N = c.N
     M = int(rng.integers(1, N + 1))
     S = rand_states(orc, c.cfg.domain, M, rng)
@@ -231,98 +215,50 @@ def read_only_calls(c, rng, tmp):
              "episode_steps": lambda: c.episode_steps, "project": lambda: c.project(S), "save_weights": lambda: c.save_weights(os.path.join(tmp, "q.ckpt"))}
     if c.cfg.algo in (25, 26):
         calls["get_lstd_batch_state"] = lambda: c.get_lstd_batch_state(i)
-    names, bad, made = list(calls), [], []
-    for j in rng.permutation(len(names))[: int(rng.integers(1, 5))]:
-        name = names[int(j)]
-        made.append(name)
-        ck = c.checksum()
-        try:
-            calls[name]()
-        except ra.RsrlHipError as e:
-            if e.code not in REFUSALS:
-                bad.append(f"{name}: {str(e)[:80]}")
-        if c.checksum() != ck:
-            bad.append(f"{name} moved the checksum")
-    return bad, made
+    return cg.read_only_calls(c, rng, calls)
 
 
 def self_leg(kw, rng, legs):
     """-> (findings, the reason the case diverged or None)"""
-    bad = []
+    bad, made = [], []
     N, cap, al = kw["n_envs"], kw["max_episode_steps"], kw["algo"]
     K = int(rng.choice([10, 25, 40, MAX_K]))
-    trait = gmc_trait_loop if al == 23 else lstd_batch_trait_loop
-    with ra.Context(**kw) as c:
-        c.reset()
-        c.train(K, want_stats=False)
-        ref, ck = full(c), c.checksum()
-    if al != 23 and not all(np.isfinite(ref[n]).all() for n in ("lstd_theta", "lstd_A", "lstd_b")):
+    ref = cg.reference_run(kw, K, full)
+    if al != 23 and not all(np.isfinite(ref[0][n]).all() for n in ("lstd_theta", "lstd_A", "lstd_b")):
         return bad, f"train({K}) left a non-finite f64 state"
-    cuts = sorted(set(int(x) for x in rng.integers(1, K, size=int(rng.integers(1, 4)))))
-    calls = [b - a for a, b in zip([0] + cuts, cuts + [K])]
-    with ra.Context(**kw) as c, tempfile.TemporaryDirectory() as td:
-        c.reset()
-        made = []
-        for j, k in enumerate(calls):
-            c.train(k, want_stats=bool(rng.integers(0, 2)))
-            if j + 1 < len(calls):
-                b_, m_ = read_only_calls(c, rng, td)
-                bad += b_; made += m_
-        names = diff(full(c), ref)
-        if names or c.checksum() != ck:
-            bad.append(f"train {calls} with {made} != train({K}): {names or 'checksum'}")
-    legs["split+query"] = legs.get("split+query", 0) + 1
-    with ra.Context(**kw) as c:
-        c.reset()
-        trait(c, K, cap)
-        names = diff(full(c), ref)
-        if names:
-            bad.append(f"the host trait loop != train({K}): {names}")
-    legs["trait"] = legs.get("trait", 0) + 1
+    with tempfile.TemporaryDirectory() as td:
+        def between(c):
+            b_, m_ = read_only_calls(c, rng, td)
+            bad.extend(b_); made.extend(m_)
+        got, calls = cg.split_run(kw, rng, K, cg.draw_calls(rng, K, 1, 4), full, between=between)
+    names = cg.differs(got, ref)
+    if names:
+        bad.append(f"train {calls} with {made} != train({K}): {names}")
+    count(legs, "split+query")
+    names = cg.differs(cg.trait_run(kw, K, cap, gmc_trait_loop if al == 23 else lstd_batch_trait_loop, full), ref, checksum=False)
+    if names:
+        bad.append(f"the host trait loop != train({K}): {names}")
+    count(legs, "trait")
     if N % 2 == 0:
-        parts = []
-        for off in (0, N // 2):
-            with ra.Context(**dict(kw, n_envs=N // 2, env_offset=kw["env_offset"] + off)) as cs:
-                cs.reset()
-                cs.train(K, want_stats=False)
-                parts.append(full(cs))
-        names = diff(join_shards(*parts), ref)
+        names = diff(join_shards(*cg.shard_run(kw, K, (N // 2, N // 2), full)), ref[0])
         if names:
             bad.append(f"two shards of {N // 2} joined != train({K}): {names}")
-        legs["shard"] = legs.get("shard", 0) + 1
+        count(legs, "shard")
     k1 = int(rng.integers(1, K))
-    with ra.Context(**kw) as a, ra.Context(**kw) as b, tempfile.TemporaryDirectory() as td:
-        a.reset()
-        a.train(k1, want_stats=False)
-        path = os.path.join(td, "w.ckpt")
-        a.save_weights(path)
-        b.reset()
-        b.train(2, want_stats=False)                                # (something to overwrite)
-        b.load_weights(path)
-        b.states, b.actions, b.episode_steps, b.episode_record = a.states, a.actions, a.episode_steps, a.episode_record
-        b.train(K - k1, want_stats=False)
-        names = diff(full(b), ref)
-        if names or b.checksum() != ck:
-            bad.append(f"checkpoint at {k1} resumed != train({K}): {names or 'checksum'}")
-    legs["ckpt"] = legs.get("ckpt", 0) + 1
+
+    def carry(a, b):
+        b.episode_record = a.episode_record
+    names = cg.differs(cg.resume_run(kw, K, k1, full, carry=carry), ref)
+    if names:
+        bad.append(f"checkpoint at {k1} resumed != train({K}): {names}")
+    count(legs, "ckpt")
     return bad, None
 
 
 def env_leg(kw, rng, legs):
     """tests/test_gpu_gmc.py test_environment_side_is_tds, randomised: both agents sample Random on the same draws"""
-    bad = []
-    K = int(rng.integers(1, MAX_K + 1))
-    with ra.Context(**kw) as c, ra.Context(**dict(kw, algo=ra.TD, lr=0.01)) as t:
-        c.reset()
-        t.reset()
-        sc, stt = c.train(K), t.train(K)
-        for name in ("states", "actions", "episode_steps"):
-            if not np.array_equal(getattr(c, name).view(np.uint32), getattr(t, name).view(np.uint32)):
-                bad.append(f"{name} after train({K}) != RSRL_TD's")
-        for name in ("env_steps", "episodes", "episodes_truncated", "sum_episode_steps"):
-            if sc[name] != stt[name]:
-                bad.append(f"{name}: {sc[name]} != RSRL_TD's {stt[name]}")
-    legs["env"] = legs.get("env", 0) + 1
+    bad = cg.env_side(kw, dict(kw, algo=ra.TD, lr=0.01), int(rng.integers(1, MAX_K + 1)))
+    count(legs, "env")
     return bad
 
 
@@ -333,10 +269,9 @@ def run_case(seed, idx, agents, worst, legs):
     io = batch_inputs(rng, kw)
     tag = f"{idx:4d} {NAMES[al]:10s} dom {kw['domain']} ord {kw['order']} N {kw['n_envs']:3d} off {kw['env_offset']:10d} cap {kw['max_episode_steps']:3d} " \
           f"spl {kw['steps_per_launch']:2d} gamma {kw['gamma']} lam {kw['lam']} T {io['T']:3d}"
-    try:
-        c = ra.Context(**kw)
-    except ra.RsrlHipError as e:
-        return "refused", tag + f"  REFUSED: {str(e)[:90]}", kw
+    c, refused = cg.create(tag, kw)
+    if refused:
+        return refused
     bad, why = [], None
     with c:
         c.reset()
@@ -346,40 +281,20 @@ def run_case(seed, idx, agents, worst, legs):
         else:
             b_, why = batch_leg_lstd(c, kw, io, w)
             bad += [f"batch: {b}" for b in b_]
-        legs["batch"] = legs.get("batch", 0) + 1
+        count(legs, "batch")
     if why is None:
         b_, why = self_leg(kw, rng, legs)
         bad += [f"self: {b}" for b in b_]
     if why is None:
         bad += [f"env: {b}" for b in env_leg(kw, rng, legs)]
-    if bad:
-        return "MISMATCH", tag + f"  MISMATCH {bad[:4]}", kw
-    if why is not None:
-        return "diverged", tag + f"  diverged: {why}", kw
-    return "ok", tag + "  ok", kw
+    return cg.verdict(tag, kw, bad, why)
 
 
 def main():
-    pos = [a for a in sys.argv[1:] if "=" not in a]
-    n_cases = int(pos[0]) if len(pos) > 0 else 200
-    seed = int(pos[1]) if len(pos) > 1 else 0
-    agents = parse_agents(sys.argv[1:], NAMES) or AGENTS
-    counts, per_agent, failures, worst, legs = {}, {}, [], {}, {}
-    for idx in range(n_cases):
-        try:
-            status, line, kw = run_case(seed, idx, agents, worst, legs)
-        except Exception as e:      # noqa: BLE001
-            status, line, kw = "ERROR", f"{idx:4d} ERROR {type(e).__name__}: {str(e)[:200]}", None
-        counts[status] = counts.get(status, 0) + 1
-        if kw is not None:
-            a = per_agent.setdefault(NAMES[kw["algo"]], {})
-            a[status] = a.get(status, 0) + 1
-        print(line, flush=True)
-        if status in ("MISMATCH", "ERROR"):
-            failures.append({"case": idx, "line": line, "config": kw})
-    print("SUMMARY " + json.dumps({"cases": n_cases, "seed": seed, "counts": counts, "per_agent": per_agent, "legs": legs, "worst": worst,
-                                   "left_out": 0, "failures": failures}, default=str), flush=True)
-    sys.exit(1 if failures else 0)
+    n_cases, seed = cg.parse_cases(sys.argv[1:])
+    agents = cg.parse_agents(sys.argv[1:], NAMES) or AGENTS
+    worst, legs = {}, {}
+    cg.run(lambda idx: run_case(seed, idx, agents, worst, legs), n_cases, seed, NAMES, lambda failures: {"legs": legs, "worst": worst, "left_out": 0})
 
 
 if __name__ == "__main__":

@@ -14,8 +14,7 @@ Fourier order at random learner counts (partial blocks), env offsets (ids that s
 
     python tests/fuzz_gtd.py [n_cases=200] [seed=0] [agents=GTD2,TDC]      (GPU box; test infrastructure: imports oracle/)
 
-One line per case and a SUMMARY {json} line; exit code 1 on any mismatch."""
-import json
+One line per case and a SUMMARY {json} line (tests/campaign.run); exit code 1 on any mismatch."""
 import os
 import sys
 import tempfile
@@ -27,20 +26,19 @@ sys.path.insert(0, ROOT)
 import rsrl_amd as ra  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
 from tests import gtd_numpy as gn  # noqa: E402
+from tests import campaign as cg  # noqa: E402
 from tests.agent_contract import diff, join_shards, rand_states, snapshot  # noqa: E402
-from tests.fuzz_episodic import parse_agents  # noqa: E402
+from tests.campaign import TOP_OF_IDS, bits, count  # noqa: E402
 
 NAMES = {30: "GTD2", 31: "TDC"}
 AGENTS = (30, 31)
 REG = [(0, o) for o in (1, 2, 3, 4, 5)] + [(1, 1), (2, 1)]          # the register-family Fourier orders check_config admits for them
-REFUSALS = (-1, -5)                                                 # EINVAL, ESTATE: what a read-only call may refuse with
-TOP_OF_IDS = -1
 MAX_K = 60
 SUITE_SEED, SUITE_CASES = 20261020, 30                              # the slice tests/test_gpu_gtd.py runs
 
 
 def case_rng(seed, idx, agents=AGENTS):
-    return np.random.default_rng([seed, idx, agents[idx % len(agents)]])
+    return cg.case_rng(seed, idx, agents[idx % len(agents)])
 
 
 def sample(rng, idx=None, agents=AGENTS):
@@ -50,13 +48,7 @@ def sample(rng, idx=None, agents=AGENTS):
               lr=float(rng.choice([0.0, 0.001, 0.02, 0.05])), lr_td=float(rng.choice([0.0, 0.005, 0.02, 0.05])),
               n_envs=int(rng.choice([1, 3, 5, 63, 64, 65, 130, 257])), env_offset=int(rng.choice([0, 64, 1000003, (1 << 31) - 65, TOP_OF_IDS])),
               max_episode_steps=int(rng.choice([0, 1, 2, 7, 25, 200])), steps_per_launch=int(rng.choice([0, 1, 5, 64])))
-    if kw["env_offset"] == TOP_OF_IDS:
-        kw["env_offset"] = (1 << 32) - 1 - kw["n_envs"]
-    return kw
-
-
-def bits(x):
-    return np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    return cg.top_of_ids(kw)
 
 
 def columns(c):
@@ -95,12 +87,12 @@ def handle_leg(c, kw, rng, legs):
             bad.append(f"theta or w of call {call} (M {M})")
         if not np.array_equal(bits(g_th[M:]), bits(th[M:])) or not np.array_equal(bits(g_w[M:]), bits(w[M:])):
             bad.append(f"a learner past M = {M} moved in call {call}")
-    legs["handle"] = legs.get("handle", 0) + 1
+    count(legs, "handle")
     return bad
 
 
 def read_only_calls(c, rng, tmp):
-    """1-4 random calls that change nothing: the checksum before and after each is equal -> (findings, the calls made)"""
+    """this campaign's named calls, on its own draws, through tests/campaign.read_only_calls -> (findings, the calls made)"""
     N = c.N
     M = int(rng.integers(1, N + 1))
     S = rand_states(orc, c.cfg.domain, M, rng)
@@ -109,75 +101,38 @@ def read_only_calls(c, rng, tmp):
              "checksum": lambda: c.checksum(), "policy_sample": lambda: c.policy_sample(S), "states": lambda: c.states, "actions": lambda: c.actions,
              "episode_steps": lambda: c.episode_steps, "project": lambda: c.project(S), "q_find_max": lambda: c.q_find_max(S),
              "get_traces": lambda: c.get_traces(i), "save_weights": lambda: c.save_weights(os.path.join(tmp, "q.ckpt"))}
-    names, bad, made = list(calls), [], []
-    for j in rng.permutation(len(names))[: int(rng.integers(1, 5))]:
-        name = names[int(j)]
-        made.append(name)
-        ck = c.checksum()
-        try:
-            calls[name]()
-        except ra.RsrlHipError as e:
-            if e.code not in REFUSALS:
-                bad.append(f"{name}: {str(e)[:80]}")
-        if c.checksum() != ck:
-            bad.append(f"{name} moved the checksum")
-    return bad, made
+    return cg.read_only_calls(c, rng, calls)
 
 
 def self_leg(kw, rng, legs):
-    bad = []
+    bad, made = [], []
     N = kw["n_envs"]
     K = int(rng.choice([10, 25, 40, MAX_K]))
-    with ra.Context(**kw) as c:
-        c.reset()
-        c.train(K, want_stats=False)
-        ref, ck = full(c), c.checksum()
-    if not (np.isfinite(ref["weights"]).all() and np.isfinite(ref["td_weights"]).all()):
+    ref = cg.reference_run(kw, K, full)
+    if not (np.isfinite(ref[0]["weights"]).all() and np.isfinite(ref[0]["td_weights"]).all()):
         return bad, f"train({K}) left a non-finite column"
-    cuts = sorted(set(int(x) for x in rng.integers(1, K, size=int(rng.integers(1, 4)))))
-    calls = [b - a for a, b in zip([0] + cuts, cuts + [K])]
-    with ra.Context(**kw) as c, tempfile.TemporaryDirectory() as td:
-        c.reset()
-        made = []
-        for j, k in enumerate(calls):
-            c.train(k, want_stats=bool(rng.integers(0, 2)))
-            if j + 1 < len(calls):
-                b_, m_ = read_only_calls(c, rng, td)
-                bad += b_; made += m_
-        names = diff(full(c), ref)
-        if names or c.checksum() != ck:
-            bad.append(f"train {calls} with {made} != train({K}): {names or 'checksum'}")
-    legs["split+query"] = legs.get("split+query", 0) + 1
+    with tempfile.TemporaryDirectory() as td:
+        def between(c):
+            b_, m_ = read_only_calls(c, rng, td)
+            bad.extend(b_); made.extend(m_)
+        got, calls = cg.split_run(kw, rng, K, cg.draw_calls(rng, K, 1, 4), full, between=between)
+    names = cg.differs(got, ref)
+    if names:
+        bad.append(f"train {calls} with {made} != train({K}): {names}")
+    count(legs, "split+query")
     if N % 2 == 0:
-        parts = []
-        for off in (0, N // 2):
-            with ra.Context(**dict(kw, n_envs=N // 2, env_offset=kw["env_offset"] + off)) as cs:
-                cs.reset()
-                cs.train(K, want_stats=False)
-                parts.append(full(cs))
-        names = diff(join_shards(*parts), ref)
+        names = diff(join_shards(*cg.shard_run(kw, K, (N // 2, N // 2), full)), ref[0])
         if names:
             bad.append(f"two shards of {N // 2} joined != train({K}): {names}")
-        legs["shard"] = legs.get("shard", 0) + 1
+        count(legs, "shard")
     return bad, None
 
 
 def td_leg(kw, rng, legs):
-    bad = []
     K = int(rng.integers(1, MAX_K + 1))
     td_kw = dict(kw, algo=ra.TD, lr_td=0.0)
-    # the environment side at the case's own rates
-    with ra.Context(**kw) as c, ra.Context(**td_kw) as t:
-        c.reset()
-        t.reset()
-        sc, stt = c.train(K), t.train(K)
-        for name in ("states", "actions", "episode_steps"):
-            if not np.array_equal(getattr(c, name).view(np.uint32), getattr(t, name).view(np.uint32)):
-                bad.append(f"{name} after train({K}) != RSRL_TD's")
-        for name in ("env_steps", "episodes", "episodes_truncated", "sum_episode_steps"):
-            if sc[name] != stt[name]:
-                bad.append(f"{name}: {sc[name]} != RSRL_TD's {stt[name]}")
-    legs["env"] = legs.get("env", 0) + 1
+    bad = cg.env_side(kw, td_kw, K)                                  # the environment side at the case's own rates
+    count(legs, "env")
     # TDC without its estimator is TD
     with ra.Context(**dict(kw, algo=ra.TDC, lr_td=0.0)) as c, ra.Context(**td_kw) as t:
         c.reset()
@@ -195,7 +150,7 @@ def td_leg(kw, rng, legs):
         for name in ("states", "actions", "episode_steps"):
             if not np.array_equal(getattr(c, name).view(np.uint32), getattr(t, name).view(np.uint32)):
                 bad.append(f"TDC(lr_td = 0): {name} after train({K}) != RSRL_TD's")
-    legs["identity"] = legs.get("identity", 0) + 1
+    count(legs, "identity")
     return bad
 
 
@@ -205,44 +160,23 @@ def run_case(seed, idx, agents, legs):
     al = kw["algo"]
     tag = f"{idx:4d} {NAMES[al]:5s} dom {kw['domain']} ord {kw['order']} N {kw['n_envs']:3d} off {kw['env_offset']:10d} cap {kw['max_episode_steps']:3d} " \
           f"spl {kw['steps_per_launch']:2d} gamma {kw['gamma']} lr {kw['lr']} lr_td {kw['lr_td']}"
-    try:
-        c = ra.Context(**kw)
-    except ra.RsrlHipError as e:
-        return "refused", tag + f"  REFUSED: {str(e)[:90]}", kw
+    c, refused = cg.create(tag, kw)
+    if refused:
+        return refused
     with c:
         c.reset()
         bad = [f"handle: {b}" for b in handle_leg(c, kw, rng, legs)]
     b_, why = self_leg(kw, rng, legs)
     bad += [f"self: {b}" for b in b_]
     bad += [f"td: {b}" for b in td_leg(kw, rng, legs)]
-    if bad:
-        return "MISMATCH", tag + f"  MISMATCH {bad[:4]}", kw
-    if why is not None:
-        return "diverged", tag + f"  diverged: {why}", kw
-    return "ok", tag + "  ok", kw
+    return cg.verdict(tag, kw, bad, why)
 
 
 def main():
-    pos = [a for a in sys.argv[1:] if "=" not in a]
-    n_cases = int(pos[0]) if len(pos) > 0 else 200
-    seed = int(pos[1]) if len(pos) > 1 else 0
-    agents = parse_agents(sys.argv[1:], NAMES) or AGENTS
-    counts, per_agent, failures, legs = {}, {}, [], {}
-    for idx in range(n_cases):
-        try:
-            status, line, kw = run_case(seed, idx, agents, legs)
-        except Exception as e:      # noqa: BLE001
-            status, line, kw = "ERROR", f"{idx:4d} ERROR {type(e).__name__}: {str(e)[:200]}", None
-        counts[status] = counts.get(status, 0) + 1
-        if kw is not None:
-            a = per_agent.setdefault(NAMES[kw["algo"]], {})
-            a[status] = a.get(status, 0) + 1
-        print(line, flush=True)
-        if status in ("MISMATCH", "ERROR"):
-            failures.append({"case": idx, "line": line, "config": kw})
-    print("SUMMARY " + json.dumps({"cases": n_cases, "seed": seed, "counts": counts, "per_agent": per_agent, "legs": legs, "failures": failures}, default=str),
-          flush=True)
-    sys.exit(1 if failures else 0)
+    n_cases, seed = cg.parse_cases(sys.argv[1:])
+    agents = cg.parse_agents(sys.argv[1:], NAMES) or AGENTS
+    legs = {}
+    cg.run(lambda idx: run_case(seed, idx, agents, legs), n_cases, seed, NAMES, lambda failures: {"legs": legs})
 
 
 if __name__ == "__main__":

@@ -16,6 +16,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import rsrl_amd as ra  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
+from tests import campaign as cg  # noqa: E402
 
 ONE_STEP = (ra.QLEARNING, ra.SARSA, ra.EXPECTED_SARSA, ra.PAL)
 LAMBDA = (ra.SARSA_LAMBDA, ra.Q_LAMBDA)
@@ -469,21 +470,9 @@ def main():
                 failures.append({"case": idx, "line": line, "config": dev})
         print("SUMMARY " + json.dumps({"cases": n_cases, "counts": counts, "failures": failures}, default=str), flush=True)
         sys.exit(1 if failures else 0)
-    n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+    n_cases, seed = cg.parse_cases(sys.argv[1:])
     rng = np.random.default_rng(seed)
-    counts, failures = {}, []
-    for idx in range(n_cases):
-        try:
-            status, line, dev = run_case(rng, idx)
-        except Exception as e:      # noqa: BLE001
-            status, line, dev = "ERROR", f"{idx:4d} ERROR {type(e).__name__}: {str(e)[:200]}", None
-        counts[status] = counts.get(status, 0) + 1
-        print(line, flush=True)
-        if status in ("MISMATCH", "ERROR"):
-            failures.append({"case": idx, "line": line, "config": dev})
-    print("SUMMARY " + json.dumps({"cases": n_cases, "seed": seed, "counts": counts, "failures": failures}, default=str), flush=True)
-    sys.exit(1 if failures else 0)
+    cg.run(lambda idx: run_case(rng, idx), n_cases, seed)
 
 
 if __name__ == "__main__":

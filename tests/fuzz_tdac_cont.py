@@ -14,11 +14,9 @@ range), discounts, rates, episode caps (0: none; 1: every step ends an episode),
 
     python tests/fuzz_tdac_cont.py [n_cases=200] [seed=0]      (GPU box; test infrastructure: imports oracle/)
 
-One line per case and a SUMMARY {json} line (with the largest f64 figure met); exit code 1 on any mismatch."""
-import json
+One line per case and a SUMMARY {json} line (tests/campaign.run; with the largest f64 figure met); exit code 1 on any mismatch."""
 import os
 import sys
-import tempfile
 
 import numpy as np
 
@@ -28,9 +26,10 @@ import rsrl_amd as ra  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
 from tests import cacla_numpy as cn  # noqa: E402
 from tests import tdac_cont_numpy as tn  # noqa: E402
+from tests import campaign as cg  # noqa: E402
 from tests.agent_contract import diff, join_shards, snapshot  # noqa: E402
+from tests.campaign import TOP_OF_IDS, bits, count  # noqa: E402
 
-TOP_OF_IDS = -1
 MAX_K = 24
 SUITE_SEED, SUITE_CASES = 20261020, 24                               # the slice tests/test_gpu_tdac_cont.py runs
 # max |d column| / max(1, |column|) of one handle call against f64: four times the largest figure profiles/tdac_cont_rate.md records for the rule
@@ -39,7 +38,7 @@ F64_BOUND = 4 * 1.443e-7
 
 
 def case_rng(seed, idx):
-    return np.random.default_rng([seed, idx, tn.TDAC_CONT])
+    return cg.case_rng(seed, idx, tn.TDAC_CONT)
 
 
 def sample(rng):
@@ -48,13 +47,7 @@ def sample(rng):
               alpha=float(rng.choice([0.0, 0.001, 0.01])), n_envs=int(rng.choice([1, 2, 5, 63, 64, 66, 130, 257])),
               env_offset=int(rng.choice([0, 64, 1000003, (1 << 31) - 33, TOP_OF_IDS])), max_episode_steps=int(rng.choice([0, 1, 7, 23, 200])),
               steps_per_launch=int(rng.choice([0, 1, 5, 64])))
-    if kw["env_offset"] == TOP_OF_IDS:
-        kw["env_offset"] = (1 << 32) - 1 - kw["n_envs"]
-    return kw
-
-
-def bits(x):
-    return np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    return cg.top_of_ids(kw)
 
 
 def full(c):
@@ -64,8 +57,8 @@ def full(c):
     return out
 
 
-def start(c):
-    """reset, then every third learner (by global id) near the goal, so that terminal ends occur as well as cut ones"""
+def start(c, off=0):
+    """reset, then every third learner (by global id, so a shard needs no `off`) near the goal, so that terminal ends occur as well as cut ones"""
     c.reset()
     ids = np.arange(c.N) + c.cfg.env_offset
     s = c.states
@@ -149,7 +142,7 @@ def f64_leg(c, kw, rng, legs):
         if kw["alpha"] == 0 and not np.array_equal(g_W, W):                      # (e = 0: fma(0, phi, w) is w as a value)
             bad.append(f"alpha = 0 moved a column in call {call}")
         W = g_W
-    legs["f64"] = legs.get("f64", 0) + 1
+    count(legs, "f64")
     legs["f64_max"] = max(legs.get("f64_max", 0.0), worst)
     return bad
 
@@ -158,48 +151,20 @@ def self_leg(kw, rng, legs, shard, ckpt):
     bad = []
     N, cap = kw["n_envs"], kw["max_episode_steps"]
     K = int(rng.integers(2, MAX_K + 1))
-    cuts = sorted(set(int(x) for x in rng.integers(1, K, size=int(rng.integers(0, 3)))))
-    calls = [b - a for a, b in zip([0] + cuts, cuts + [K])]
-    with ra.Context(**kw) as c:
-        start(c)
-        for k in calls:
-            c.train(k, want_stats=bool(rng.integers(0, 2)))
-        ref, ck = full(c), c.checksum()
-    with ra.Context(**dict(kw, steps_per_launch=0)) as c:
-        start(c)
-        trait_loop(c, K, cap)
-        names = diff(full(c), ref)
-        if names or c.checksum() != ck:
-            bad.append(f"the trait loop != train {calls}: {names or 'checksum'}")
-    legs["self"] = legs.get("self", 0) + 1
+    ref, calls = cg.split_run(kw, rng, K, cg.draw_calls(rng, K, 0, 3), full, start)
+    names = cg.differs(cg.trait_run(dict(kw, steps_per_launch=0), K, cap, trait_loop, full, start), ref)
+    if names:
+        bad.append(f"the trait loop != train {calls}: {names}")
+    count(legs, "self")
     if shard and N % 2 == 0:
-        parts = []
-        for off in (0, N // 2):
-            with ra.Context(**dict(kw, n_envs=N // 2, env_offset=kw["env_offset"] + off)) as cs:
-                start(cs)
-                cs.train(K, want_stats=False)
-                parts.append(full(cs))
-        names = diff(join_shards(*parts), ref)
+        names = diff(join_shards(*cg.shard_run(kw, K, (N // 2, N // 2), full, start)), ref[0])
         if names:
             bad.append(f"two shards of {N // 2} joined != train({K}): {names}")
-        legs["shard"] = legs.get("shard", 0) + 1
+        count(legs, "shard")
     if ckpt:
         k1, k2 = int(rng.integers(1, MAX_K)), int(rng.integers(1, MAX_K))
-        with ra.Context(**kw) as a, ra.Context(**kw) as b, tempfile.TemporaryDirectory() as td:
-            path = os.path.join(td, "tdac_cont.ckpt")
-            start(a)
-            a.train(k1, want_stats=False)
-            a.save_weights(path)
-            b.load_weights(path)
-            b.states, b.actions, b.episode_steps = a.states, a.actions, a.episode_steps
-            if b.step_count != a.step_count or diff(full(b), full(a)) or a.checksum() != b.checksum():
-                bad.append(f"the loaded ctx differs after train({k1})")
-            a.train(k2, want_stats=False)
-            b.train(k2, want_stats=False)
-            names = diff(full(b), full(a))
-            if names or a.checksum() != b.checksum():
-                bad.append(f"{k2} steps after the load: {names or 'checksum'}")
-        legs["ckpt"] = legs.get("ckpt", 0) + 1
+        bad += cg.twin_resume(kw, k1, k2, full, start)
+        count(legs, "ckpt")
     return bad
 
 
@@ -208,35 +173,20 @@ def run_case(seed, idx, legs):
     kw = sample(rng)
     tag = f"{idx:4d} pol {kw['policy']} ord {kw['order']} N {kw['n_envs']:3d} off {kw['env_offset']:10d} cap {kw['max_episode_steps']:3d} spl {kw['steps_per_launch']:2d} " \
           f"gamma {kw['gamma']} lr {kw['lr']} alpha {kw['alpha']}"
-    try:
-        c = ra.Context(**kw)
-    except ra.RsrlHipError as e:
-        return "refused", tag + f"  REFUSED: {str(e)[:90]}", kw
+    c, refused = cg.create(tag, kw)
+    if refused:
+        return refused
     with c:
         c.reset()
         bad = [f"f64: {b}" for b in f64_leg(c, kw, rng, legs)]
     bad += [f"self: {b}" for b in self_leg(kw, rng, legs, idx % 3 == 0, idx % 3 == 1)]
-    if bad:
-        return "MISMATCH", tag + f"  MISMATCH {bad[:4]}", kw
-    return "ok", tag + "  ok", kw
+    return cg.verdict(tag, kw, bad)
 
 
 def main():
-    pos = [a for a in sys.argv[1:] if "=" not in a]
-    n_cases = int(pos[0]) if len(pos) > 0 else 200
-    seed = int(pos[1]) if len(pos) > 1 else 0
-    counts, failures, legs = {}, [], {}
-    for idx in range(n_cases):
-        try:
-            status, line, kw = run_case(seed, idx, legs)
-        except Exception as e:      # noqa: BLE001
-            status, line, kw = "ERROR", f"{idx:4d} ERROR {type(e).__name__}: {str(e)[:200]}", None
-        counts[status] = counts.get(status, 0) + 1
-        print(line, flush=True)
-        if status in ("MISMATCH", "ERROR"):
-            failures.append({"case": idx, "line": line, "config": kw})
-    print("SUMMARY " + json.dumps({"cases": n_cases, "seed": seed, "counts": counts, "legs": legs, "failures": failures}, default=str), flush=True)
-    sys.exit(1 if failures else 0)
+    n_cases, seed = cg.parse_cases(sys.argv[1:])
+    legs = {}
+    cg.run(lambda idx: run_case(seed, idx, legs), n_cases, seed, extras=lambda failures: {"legs": legs})
 
 
 if __name__ == "__main__":

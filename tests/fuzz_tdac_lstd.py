@@ -11,11 +11,10 @@ episode caps and launch depths.  Legs:
 
     python tests/fuzz_tdac_lstd.py [n_cases=100] [seed=0] [agents=21]          (GPU box; test infrastructure: imports oracle/)
 
-One line per case and a SUMMARY {json} line; exit code 1 on any mismatch."""
+One line per case and a SUMMARY {json} line (tests/campaign.run); exit code 1 on any mismatch."""
 import json
 import os
 import sys
-import tempfile
 
 import numpy as np
 
@@ -23,6 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import rsrl_amd as ra  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
+from tests import campaign as cg  # noqa: E402
 from tests.agent_contract import diff, join_shards, learner_state, rand_states, snapshot, trait_loop  # noqa: E402
 from tests.lstd_numpy import near_tie_band  # noqa: E402
 from tests.tdac_lstd_numpy import tdac_lstd_rule  # noqa: E402
@@ -95,80 +95,57 @@ def leg_f64(kw, rng):
 
 
 def leg_self(kw, rng):
+    """(this campaign's drift, kept: every train call asks for statistics, the calls are drawn one by one until they sum to K, the queries run
+    after the last call too, no checksum is compared and the checkpoint loads into a ctx that has not trained)"""
     bad = []
     K, N, cap = int(rng.integers(5, 40)), kw["n_envs"], kw["max_episode_steps"]
-    with ra.Context(**kw) as c:
-        c.reset()
-        c.train(K)
-        ref = snapshot(c)
-    with ra.Context(**kw) as c:                                      # random splits, policy queries in between
-        c.reset()
-        done = 0
-        while done < K:
-            k = int(rng.integers(1, K - done + 1))
-            c.train(k, want_stats=bool(rng.integers(2)))
-            done += k
-            S = c.states
-            c.policy_probs(S); c.policy_sample(S); c.q_evaluate(S)
-        if diff(snapshot(c), ref):
-            bad.append("splits with queries")
-    with ra.Context(**kw) as c:
-        c.reset()
-        trait_loop(c, K, cap)
-        if diff(snapshot(c), ref):
-            bad.append("trait loop")
+    ref = cg.reference_run(kw, K, snapshot, want_stats=True)
+    done = []
+
+    def calls():
+        while sum(done) < K:
+            done.append(int(rng.integers(1, K - sum(done) + 1)))
+            yield done[-1]
+
+    def queries(c):
+        S = c.states
+        c.policy_probs(S); c.policy_sample(S); c.q_evaluate(S)
+    if cg.differs(cg.split_run(kw, rng, K, calls(), snapshot, between=queries, after_last=True)[0], ref, checksum=False):
+        bad.append("splits with queries")
+    if cg.differs(cg.trait_run(kw, K, cap, trait_loop, snapshot), ref, checksum=False):
+        bad.append("trait loop")
     if N >= 2:
-        h, parts = N // 2, []
-        for off, n in ((0, h), (h, N - h)):
-            with ra.Context(**dict(kw, n_envs=n, env_offset=kw["env_offset"] + off)) as c:
-                c.reset()
-                c.train(K)
-                parts.append(snapshot(c))
-        if diff(join_shards(*parts), ref):
+        if diff(join_shards(*cg.shard_run(kw, K, (N // 2, N - N // 2), snapshot, want_stats=True)), ref[0]):
             bad.append("shards")
-    with tempfile.TemporaryDirectory() as tmp, ra.Context(**kw) as a, ra.Context(**kw) as b:
-        k1 = int(rng.integers(1, K)) if K > 1 else 1
-        a.reset()
-        a.train(k1)
-        path = os.path.join(tmp, "f.ckpt")
-        a.save_weights(path)
-        b.load_weights(path)
-        b.states, b.actions, b.episode_steps = a.states, a.actions, a.episode_steps
-        b.train(K - k1)
-        if K - k1 >= 0 and diff(snapshot(b), ref):
-            bad.append("checkpoint resume")
+    k1 = int(rng.integers(1, K))
+    if cg.differs(cg.resume_run(kw, K, k1, snapshot, overwrite=False, want_stats=True), ref, checksum=False):
+        bad.append("checkpoint resume")
     return bad
 
 
+def run_case(kw, rng, case):
+    """-> (status, line, kw[, the failure's record]).  An exception inside a leg is a finding of the case, whose configuration is known: it is
+    reported as a MISMATCH with the configuration, not as the runner's ERROR"""
+    try:
+        with ra.Context(**kw):
+            pass
+    except ra.RsrlHipError as e:
+        return "refused", f"case {case}: REFUSED {str(e)[:90]} {json.dumps(kw)}", kw
+    try:
+        bad = [("f64", x) for x in leg_f64(kw, rng)] + [("self", x) for x in leg_self(kw, rng)]
+    except Exception as e:      # noqa: BLE001
+        bad = [("error", f"{type(e).__name__}: {str(e)[:200]}")]
+    line = f"case {case}: {'FAIL ' + json.dumps(bad) if bad else 'ok'} {json.dumps(kw)}"
+    return ("MISMATCH", line, kw, {"case": case, "legs": bad, "config": kw}) if bad else ("ok", line, kw)
+
+
 def main():
-    pos = [a for a in sys.argv[1:] if "=" not in a]
-    n_cases = int(pos[0]) if len(pos) > 0 else 100
-    seed = int(pos[1]) if len(pos) > 1 else 0
-    agents = [a[7:] for a in sys.argv[1:] if a.startswith("agents=")]
-    if agents and agents[0] not in ("21", NAME):                    # (the one agent of this campaign: the argument exists for the suite's uniform call)
+    n_cases, seed = cg.parse_cases(sys.argv[1:], 100)
+    agents = cg.parse_agents(sys.argv[1:], {21: NAME})
+    if agents not in (None, (21,)):                                 # (the one agent of this campaign: the argument exists for the suite's uniform call)
         sys.exit(f"agents= must be 21 or {NAME}")
-    rng = np.random.default_rng(seed)
-    counts, failures = {}, []
-    for case in range(n_cases):
-        kw = draw_config(rng)
-        try:
-            with ra.Context(**kw):
-                pass
-        except ra.RsrlHipError as e:
-            counts["refused"] = counts.get("refused", 0) + 1
-            print(f"case {case}: REFUSED {str(e)[:90]} {json.dumps(kw)}", flush=True)
-            continue
-        try:
-            bad = [("f64", x) for x in leg_f64(kw, rng)] + [("self", x) for x in leg_self(kw, rng)]
-        except Exception as e:      # noqa: BLE001
-            bad = [("error", f"{type(e).__name__}: {str(e)[:200]}")]
-        status = "MISMATCH" if bad else "ok"
-        counts[status] = counts.get(status, 0) + 1
-        if bad:
-            failures.append({"case": case, "legs": bad, "config": kw})
-        print(f"case {case}: {'FAIL ' + json.dumps(bad) if bad else 'ok'} {json.dumps(kw)}", flush=True)
-    print("SUMMARY " + json.dumps(dict(cases=n_cases, seed=seed, counts=counts, per_agent={NAME: counts}, failures=failures, failed=len(failures))), flush=True)
-    sys.exit(1 if failures else 0)
+    rng = np.random.default_rng(seed)                               # one generator through the whole run: a leg's draws decide the next case
+    cg.run(lambda case: run_case(draw_config(rng), rng, case), n_cases, seed, {21: NAME}, lambda failures: {"failures": failures, "failed": len(failures)})
 
 
 if __name__ == "__main__":

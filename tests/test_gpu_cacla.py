@@ -10,10 +10,7 @@ the test prints its figure before it asserts.  N = 67: one full wave and a parti
 (9) and the packed register path."""
 import ctypes as C
 import functools
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -25,6 +22,7 @@ from tests import beta_numpy as bn
 from tests import cacla_numpy as cn
 from tests import gaussian_numpy as gn
 from tests.agent_contract import check_checkpoint_resume, check_foreign_checkpoints_refused, check_train_invariance, run_example
+from tests.campaign import run_slice
 
 pytestmark = pytest.mark.gpu
 
@@ -332,12 +330,8 @@ def test_random_configurations():
     # tests/fuzz_cacla.py: orders 1-5 at random learner counts, seeds, env offsets up to the top of the id range, caps from 0 (none) and 1 (every
     # step ends an episode), launch depths and shards: train against the host trait loop bit for bit, a checkpoint leg and a handle leg
     from tests.fuzz_cacla import SUITE_CASES, SUITE_SEED
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "fuzz_cacla.py"), str(SUITE_CASES), str(SUITE_SEED)], capture_output=True, text=True,
-                       timeout=600)
-    line = [l for l in p.stdout.splitlines() if l.startswith("SUMMARY ")]
-    assert line, (p.stdout[-2000:], p.stderr[-2000:])
-    d = json.loads(line[0][8:])
+    d = run_slice("fuzz_cacla.py", SUITE_CASES, SUITE_SEED)
     print(d["counts"], d["legs"])
-    assert p.returncode == 0 and not d["failures"], d["failures"][:3]
+    assert d["exit_code"] == 0 and not d["failures"], d["failures"][:3]
     assert SUITE_CASES == 150 and d["counts"] == {"ok": SUITE_CASES}, d["counts"]
     assert d["legs"]["handle"] == SUITE_CASES and d["legs"]["trait"] == SUITE_CASES and d["legs"]["ckpt"] == SUITE_CASES // 3 and d["legs"].get("shard", 0) >= 10, d["legs"]

@@ -9,6 +9,8 @@ import json
 
 import pytest
 
+from tests.campaign import run_slice
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -81,11 +83,8 @@ def test_random_configurations_of_the_newer_agents():
     # order and the one-step agents on HIVTreatment, at random learner counts, offsets, caps and launch depths: handle on partial batches against the f64
     # rules (learners M..N-1 untouched), REINFORCE's ragged batches, and train against its splits (with queries between them), the trait loop, shards
     # and a checkpoint, bit for bit.
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "fuzz_agents.py"), "200", "20261016"], capture_output=True, text=True, timeout=600)
-    line = [l for l in p.stdout.splitlines() if l.startswith("SUMMARY ")]
-    assert line, (p.stdout[-2000:], p.stderr[-2000:])
-    d = json.loads(line[0][8:])
-    assert p.returncode == 0 and not d["failures"], d["failures"][:3]
+    d = run_slice("fuzz_agents.py", 200, 20261016)
+    assert d["exit_code"] == 0 and not d["failures"], d["failures"][:3]
     assert d["counts"].get("refused", 0) == 0, d["counts"]
     per = d["per_agent"]
     for name in ("ActorCritic", "QActorCritic", "TDActorCritic", "REINFORCE", "BaselineREINFORCE", "RecursiveLSTD", "iLSTD"):
@@ -97,13 +96,9 @@ def _campaign_slice(script, agent):
     """one agent's slice of a campaign script as a subprocess -> its SUMMARY; asserts what every slice asserts: exit code 0, no failure, every
     sampled configuration created, at least 20 of the 24 cases ok for the agent, and at most 5 % of the replayed learner-rounds left out"""
     from tests.fuzz_episodic import SUITE_CASES, SUITE_SEED      # (24 cases on one seed: tests/test_fuzz_late_cpu.py checks the same slice's shares)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", script), str(SUITE_CASES), str(SUITE_SEED), "agents=" + agent], capture_output=True,
-                       text=True, timeout=600)
-    line = [l for l in p.stdout.splitlines() if l.startswith("SUMMARY ")]
-    assert line, (p.stdout[-2000:], p.stderr[-2000:])
-    d = json.loads(line[0][8:])
+    d = run_slice(script, SUITE_CASES, SUITE_SEED, agent)
     print(agent, d["counts"], d.get("legs"), d.get("worst"))
-    assert p.returncode == 0 and not d["failures"], d["failures"][:3]
+    assert d["exit_code"] == 0 and not d["failures"], d["failures"][:3]
     assert d["counts"].get("refused", 0) == 0, d["counts"]
     assert d["per_agent"].get(agent, {}).get("ok", 0) >= 20, d["per_agent"]
     replayed = d.get("replayed", sum(w.get("replayed", 0) for w in d.get("worst", {}).values() if isinstance(w, dict)))

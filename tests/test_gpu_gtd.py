@@ -2,10 +2,7 @@
 bounds of the f64 rule, TDC without its estimator against a TD ctx, the environment side against TD's, train against the trait-granular loop /
 launch depths / shards bit for bit (the second column included), checkpoints, the value side reading theta, the refusals, the checksum, the C++
 example and a slice of the random campaign (tests/fuzz_gtd.py)."""
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,6 +11,7 @@ import rsrl_amd
 from rsrl_amd import RsrlHipError
 from tests import gtd_numpy as gn
 from tests.agent_contract import check_checkpoint_resume, check_foreign_checkpoints_refused, check_train_invariance, rand_states, run_example
+from tests.campaign import run_slice
 
 pytestmark = pytest.mark.gpu
 
@@ -271,13 +269,9 @@ def test_random_configurations_of_the_gradient_td_agents():
     # against the f32 numpy rule bit for bit, train against its splits with read-only calls between them and against shards, the TD identity and the
     # environment side against RSRL_TD's.
     from tests.fuzz_gtd import SUITE_CASES, SUITE_SEED
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "fuzz_gtd.py"), str(SUITE_CASES), str(SUITE_SEED)], capture_output=True, text=True,
-                       timeout=600)
-    line = [l for l in p.stdout.splitlines() if l.startswith("SUMMARY ")]
-    assert line, (p.stdout[-2000:], p.stderr[-2000:])
-    d = json.loads(line[0][8:])
+    d = run_slice("fuzz_gtd.py", SUITE_CASES, SUITE_SEED)
     print(d["counts"], d["legs"])
-    assert p.returncode == 0 and not d["failures"], d["failures"][:3]
+    assert d["exit_code"] == 0 and not d["failures"], d["failures"][:3]
     assert d["counts"].get("refused", 0) == 0 and d["counts"].get("diverged", 0) == 0, d["counts"]
     for name in ("GTD2", "TDC"):
         assert d["per_agent"].get(name, {}).get("ok", 0) == SUITE_CASES // 2, d["per_agent"]

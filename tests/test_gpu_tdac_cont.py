@@ -11,10 +11,7 @@ second run of the device.  N = 67: one full wave and a partial one; orders 1, 2,
 register path."""
 import ctypes as C
 import functools
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -26,6 +23,7 @@ from tests import beta_numpy as bn
 from tests import gaussian_numpy as gn
 from tests import tdac_cont_numpy as tn
 from tests.agent_contract import check_checkpoint_resume, check_foreign_checkpoints_refused, check_train_invariance, run_example
+from tests.campaign import run_slice
 from tests.fuzz_tdac_cont import trait_loop
 
 pytestmark = pytest.mark.gpu
@@ -370,12 +368,8 @@ def test_random_configurations():
     # tests/fuzz_tdac_cont.py: both policies, orders 1-5 at random learner counts, seeds, env offsets up to the top of the id range, caps from 0
     # (none) and 1 (every step ends an episode), launch depths and shards: the f64 leg and the self leg
     from tests.fuzz_tdac_cont import SUITE_CASES, SUITE_SEED
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "fuzz_tdac_cont.py"), str(SUITE_CASES), str(SUITE_SEED)], capture_output=True, text=True,
-                       timeout=600)
-    line = [l for l in p.stdout.splitlines() if l.startswith("SUMMARY ")]
-    assert line, (p.stdout[-2000:], p.stderr[-2000:])
-    d = json.loads(line[0][8:])
+    d = run_slice("fuzz_tdac_cont.py", SUITE_CASES, SUITE_SEED)
     print(d["counts"], d["legs"])
-    assert p.returncode == 0 and not d["failures"], d["failures"][:3]
+    assert d["exit_code"] == 0 and not d["failures"], d["failures"][:3]
     assert SUITE_CASES == 24 and d["counts"] == {"ok": SUITE_CASES}, d["counts"]
     assert d["legs"]["f64"] == SUITE_CASES and d["legs"]["self"] == SUITE_CASES and d["legs"]["ckpt"] == SUITE_CASES // 3 and d["legs"].get("shard", 0) >= 2, d["legs"]
